@@ -8,7 +8,10 @@ resident in HBM.  With N GPUs (torchrun, one process per GPU) every rank decodes
 own frames: weak scaling, no data-path collective; the step time is the max over
 ranks and `value` counts the pixels of all ranks.
 
-Prints ONE JSON line (rank 0).  Also reports:
+Prints ONE JSON line (rank 0).  A plain run (`--gpus 1 --steps N --warmup W`) sets up, warms
+up, times the N steps of the headline (HIP-graph replays of the fused pipeline), writes the
+last timed step's outputs when `--dump-outputs DIR` is given, and prints the line.  Everything
+below needs `--full`, which also reports:
   roofline     -- the dominant kernel's algorithmic FLOP/s (HIP events on the launch
                   stream) vs the FP32 peak, plus HBM traffic from the committed PMC
                   profile (profiles/*pmc*.json) when present;
@@ -208,9 +211,37 @@ class Pipeline:
         self.stream.wait_event(self.join)
 
 
-def measure_path_a(inp, B, steps, warmup, mode, overlap, dist, dev, join_before_last=False):
+DUMP_MAX_ELEMS = 6 << 20  # per array: 24 MiB of float32, two arrays
+DUMP_SEED = 20240607
+
+
+def sample_outputs(pipe):
+    """What a caller of the timed path receives from a step -- the 420 frames (`yuv`, [B, H W 3/2])
+    and the per-latent rates (`rate`, [B, n_latents]) -- as float32 numpy arrays.  An array of more
+    than DUMP_MAX_ELEMS elements is cut to that many flat positions, drawn once with a fixed seed
+    and sorted, so two runs with the same arguments hold the same positions."""
+    out = {}
+    for name, t in (("yuv", pipe.yuv), ("rate", pipe.rate)):
+        if t.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator().manual_seed(DUMP_SEED)
+            idx = torch.randint(t.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        out[name] = t.float().cpu().numpy()
+    return out
+
+
+def write_outputs(outs, path):
+    import numpy as np
+    path = Path(path)
+    path.mkdir(parents=True, exist_ok=True)
+    for name, a in outs.items():
+        np.save(path / f"{name}.npy", a)
+
+
+def measure_path_a(inp, B, steps, warmup, mode, overlap, dist, dev, join_before_last=False, keep=None):
     """Time `steps` pipeline steps (after `warmup`), barrier + synchronize on both sides;
-    returns (max-over-ranks seconds, per-stage ms per step from HIP events)."""
+    returns (max-over-ranks seconds, per-stage ms per step from HIP events).  `keep`: a dict
+    that receives sample_outputs() of the last timed step."""
     pipe = Pipeline(inp, B, dev)
     pipe.join_before_last = join_before_last
     names = Pipeline.STAGES[mode]
@@ -226,6 +257,8 @@ def measure_path_a(inp, B, steps, warmup, mode, overlap, dist, dev, join_before_
         pipe.step(ev[k], mode, overlap)
     torch.cuda.synchronize()
     t1 = time.perf_counter()
+    if keep is not None:
+        keep.update(sample_outputs(pipe))
     if dist: dist.barrier()
     dt = t1 - t0
     if dist:
@@ -249,10 +282,12 @@ def measure_path_a(inp, B, steps, warmup, mode, overlap, dist, dev, join_before_
     return dt, stage_ms
 
 
-def measure_path_a_graph(inp, B, steps, warmup, dist, dev, per_graph=10, overlap=False):
+def measure_path_a_graph(inp, B, steps, warmup, dist, dev, per_graph=10, overlap=False, check=True, keep=None):
     """The fused pipeline captured in a HIP graph (`per_graph` steps per graph, one stream):
     replays remove the host launch gaps between the step's small pyramid kernels.  Returns
-    the max-over-ranks seconds for `steps` steps (a multiple of per_graph)."""
+    the max-over-ranks seconds for `steps` steps (a multiple of per_graph), the steps done and,
+    with `check`, whether one more replay into cleared buffers reproduces the eager outputs
+    (None without).  `keep`: a dict that receives sample_outputs() of the last timed step."""
     pipe = Pipeline(inp, B, dev)
     pipe.join_before_last = overlap
     s = torch.cuda.Stream(dev)
@@ -262,9 +297,10 @@ def measure_path_a_graph(inp, B, steps, warmup, dist, dev, per_graph=10, overlap
     try:
         with torch.cuda.stream(s):
             pipe.stream = s
-            pipe.step(mode="fused", overlap=overlap)
+            for _ in range(max(1, warmup)):  # eager: a capture needs warmed-up launches
+                pipe.step(mode="fused", overlap=overlap)
             s.synchronize()
-            ref = (pipe.yuv.clone(), pipe.rate.clone())  # eager outputs, to check the replays
+            ref = (pipe.yuv.clone(), pipe.rate.clone()) if check else None  # eager outputs, to check the replays
             # thread_local: the process group's watchdog thread may query events meanwhile
             with torch.cuda.graph(g, stream=s, capture_error_mode="thread_local"):
                 for _ in range(per_graph):
@@ -290,11 +326,15 @@ def measure_path_a_graph(inp, B, steps, warmup, dist, dev, per_graph=10, overlap
         g.replay()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if keep is not None:
+        keep.update(sample_outputs(pipe))
     if dist: dist.barrier()
     if dist:
         t = torch.tensor([dt], device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if not check:
+        return dt, reps * per_graph, None
     # a replay recomputes the outputs from scratch: clear them, replay once, compare
     pipe.yuv.zero_()
     pipe.rate.zero_()
@@ -848,6 +888,14 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=32, help="frames per step per GPU (720p headline and 1080p leg)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the event-instrumented eager pass (per-stage "
+                         "times, roofline, eager step rate) and the check of the graph replays against it, the "
+                         "1080p leg, the CPU baselines, the bit-exact decode / encode legs and the encoder "
+                         "overfit.  The options that size or skip those legs act only with --full")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (yuv, rate; "
+                         "sample_outputs) to DIR/<name>.npy, float32")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--decode-reps", type=int, default=64, help="class-E stream copies for the bit-exact decode leg")
     ap.add_argument("--staged", action="store_true",
@@ -922,28 +970,35 @@ def main():
     mode = "staged" if args.staged else "fused"
     ovp = args.overlap_pyramid and not args.serial and mode == "fused"
     overlap = (args.overlap or ovp) and not args.serial
-    dt, stage_ms = measure_path_a(inp, B, args.steps, args.warmup, mode, overlap, dist, dev, join_before_last=ovp)
-    fl = flops_per_frame()
-    fl["decode_fused"] = flops_fused_per_frame()
-    by = bytes_per_frame()
-    dom = max(("arm", "decode_fused" if mode == "fused" else "syn"), key=lambda n: stage_ms[n])
-    achieved = fl[dom] * B / (stage_ms[dom] * 1e-3) / 1e12
-    traffic, src = pmc_traffic(dom, B)
-
-    eager, graph_error, graph_same = None, None, None
     graph = not (args.no_graph or args.staged or (overlap and not ovp))
+    keep = {} if args.dump_outputs and rank == 0 else None  # outputs of the headline's last timed step
+
+    def eager_pass():
+        return measure_path_a(inp, B, args.steps, args.warmup, mode, overlap, dist, dev, join_before_last=ovp,
+                              keep=keep)
+
+    # the event-instrumented eager pass: the headline itself without graphs, else a run of its
+    # own (--full) that the per-stage times, the roofline and the eager step rate come from
+    dt, stage_ms = eager_pass() if args.full or not graph else (None, None)
+    eager, graph_error, graph_same = None, None, None
     if graph:
-        # headline: the same K steps replayed from HIP graphs (per-stage times and the
-        # roofline above come from the event-instrumented eager pass)
-        eager = {"value": round(B * args.steps * world * H * W / dt / 1e6, 2),
-                 "ms_per_step": round(dt / args.steps * 1e3, 4)}
+        # headline: the same K steps replayed from HIP graphs
+        if stage_ms is not None:
+            eager = {"value": round(B * args.steps * world * H * W / dt / 1e6, 2),
+                     "ms_per_step": round(dt / args.steps * 1e3, 4)}
         per = 10 if args.steps % 10 == 0 else 1
         try:
-            dt, n_done, graph_same = measure_path_a_graph(inp, B, args.steps, args.warmup, dist, dev, per, ovp)
+            dt_g, n_done, graph_same = measure_path_a_graph(inp, B, args.steps, args.warmup, dist, dev, per, ovp,
+                                                            check=args.full, keep=keep)
             assert n_done == args.steps
+            dt = dt_g
         except Exception as e:  # report the eager timing, and say so in the line
             graph_error = f"{type(e).__name__}: {e}"[:200]
             graph = False
+            if stage_ms is None:
+                dt, stage_ms = eager_pass()
+    if keep:
+        write_outputs(keep, args.dump_outputs)
     launch = "HIP graph replays (10 steps per graph)" if graph else (
         "eager launches" + (f" (graph capture failed: {graph_error})" if graph_error else ""))
     n_frames = B * args.steps * world
@@ -973,19 +1028,34 @@ def main():
                                else "ARM | upsampling | synthesis | post")
                    + (" (ARM on a second stream, concurrent with the pyramid)" if ovp else
                       " (ARM on a second stream, concurrent)" if overlap else " (one stream)")},
-        "stage_ms_per_step": {k: round(v, 4) for k, v in stage_ms.items()},
         "launch": launch,
         "graph_outputs_equal_eager": graph_same,
-        "eager": eager,
-        "ms_per_step_median_eager": round(measure_path_a.median_ms, 4),
-        "roofline": {"bound": "valu-fp32", "kernel": dom, "achieved": round(achieved, 3), "peak": PEAK_FP32_TFLOPS,
-                     "unit": "TFLOP/s", "frac": round(achieved / PEAK_FP32_TFLOPS, 4),
-                     "traffic": traffic, "traffic_source": src,
-                     "algorithmic_flop_per_launch": fl[dom] * B,
-                     "algorithmic_bytes_per_launch": by[dom] * B,
-                     "note": "FP32 VALU-bound fused kernel; peak = FP32 vector rate (= f32 MFMA rate, the same "
-                             "datapath on gfx950: profiles/r3_mfma_valu_overlap.txt) on MI355X"},
     }
+    if stage_ms is not None:  # what the eager pass measured
+        fl = flops_per_frame()
+        fl["decode_fused"] = flops_fused_per_frame()
+        by = bytes_per_frame()
+        dom = max(("arm", "decode_fused" if mode == "fused" else "syn"), key=lambda n: stage_ms[n])
+        achieved = fl[dom] * B / (stage_ms[dom] * 1e-3) / 1e12
+        traffic, src = pmc_traffic(dom, B)
+        res.update({
+            "stage_ms_per_step": {k: round(v, 4) for k, v in stage_ms.items()},
+            "eager": eager,
+            "ms_per_step_median_eager": round(measure_path_a.median_ms, 4),
+            "roofline": {"bound": "valu-fp32", "kernel": dom, "achieved": round(achieved, 3), "peak": PEAK_FP32_TFLOPS,
+                         "unit": "TFLOP/s", "frac": round(achieved / PEAK_FP32_TFLOPS, 4),
+                         "traffic": traffic, "traffic_source": src,
+                         "algorithmic_flop_per_launch": fl[dom] * B,
+                         "algorithmic_bytes_per_launch": by[dom] * B,
+                         "note": "FP32 VALU-bound fused kernel; peak = FP32 vector rate (= f32 MFMA rate, the same "
+                                 "datapath on gfx950: profiles/r3_mfma_valu_overlap.txt) on MI355X"},
+        })
+    if not args.full:  # a plain run: the headline alone
+        if rank == 0 or as_rank is not None:
+            print(json.dumps(res), flush=True)
+        if dist:
+            dist.destroy_process_group()
+        return
     if args.hd_steps > 0:
         res["path_a_1080p"] = bench_path_a_hd(B, args.hd_steps, args.warmup, rank, world, dist, dev)
     if rank == 0 and world == 1 and not args.no_cpu_baseline:

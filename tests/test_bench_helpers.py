@@ -105,3 +105,29 @@ def test_encoder_shard_covers_the_reference_lambdas_across_ranks():
     assert lms == set(bench.REF_LAMBDAS)
     assert bench.encoder_shard(7) == ([bench.REF_LAMBDAS[2]], 1)
     assert bench.encoder_shard(3, [0.02, 0.001]) == ([0.02, 0.001], 3)
+
+
+def test_sample_outputs_is_fixed_and_bounded(monkeypatch, tmp_path):
+    """--dump-outputs: small arrays are written whole, large ones as the same seeded, sorted
+    sample of flat positions every time; float32 .npy files, one per output."""
+    import types
+
+    import numpy as np
+    import torch
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMS", 1000)
+    yuv = torch.arange(3 * 700, dtype=torch.float32).reshape(3, 700)   # 2100 elements: sampled
+    rate = torch.arange(2 * 300, dtype=torch.float32).reshape(2, 300)  # 600 elements: whole
+    pipe = types.SimpleNamespace(yuv=yuv, rate=rate)
+    a, b = bench.sample_outputs(pipe), bench.sample_outputs(pipe)
+    assert sorted(a) == ["rate", "yuv"]
+    assert a["rate"].shape == (2, 300) and np.array_equal(a["rate"], rate.numpy())
+    assert a["yuv"].shape == (1000,) and a["yuv"].dtype == np.float32
+    assert np.array_equal(a["yuv"], b["yuv"])
+    # values are their own flat positions here: sorted, in range, and not just a prefix
+    assert np.all(np.diff(a["yuv"]) >= 0) and a["yuv"][-1] > 1500 and a["yuv"].max() < 2100
+    bench.write_outputs(a, tmp_path / "out")
+    assert sorted(f.name for f in (tmp_path / "out").iterdir()) == ["rate.npy", "yuv.npy"]
+    assert np.array_equal(np.load(tmp_path / "out" / "yuv.npy"), a["yuv"])
+    # the real cap keeps two float32 arrays under 64 MB
+    monkeypatch.undo()
+    assert 2 * 4 * bench.DUMP_MAX_ELEMS <= 64 * 10 ** 6

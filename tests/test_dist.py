@@ -137,7 +137,7 @@ def test_bench_two_ranks_gloo_on_one_gpu(tmp_path):
     env = dict(os.environ, CCMI_BENCH_BACKEND="gloo", OMP_NUM_THREADS="2")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", f"--master-port={_free_port()}", str(root / "bench.py"), "--gpus", "2",
-           "--steps", "2", "--warmup", "1", "--batch", "2", "--hd-steps", "0", "--decode-reps", "1",
+           "--full", "--steps", "2", "--warmup", "1", "--batch", "2", "--hd-steps", "0", "--decode-reps", "1",
            "--hd-decode-reps", "1", "--encode-images", "3", "--encode-scale", "0.002", "--no-cpu-baseline",
            "--no-single-stream"]
     p = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=110)
@@ -167,8 +167,8 @@ def test_bench_as_rank_runs_one_shard():
     import sys
     from pathlib import Path
     root = Path(__file__).resolve().parents[1]
-    cmd = [sys.executable, str(root / "bench.py"), "--as-rank", "6", "--as-world", "8", "--steps", "2", "--warmup",
-           "1", "--batch", "2", "--hd-steps", "0", "--decode-reps", "1", "--hd-decode-reps", "0", "--encode-images",
+    cmd = [sys.executable, str(root / "bench.py"), "--as-rank", "6", "--as-world", "8", "--full", "--steps", "2",
+           "--warmup", "1", "--batch", "2", "--hd-steps", "0", "--decode-reps", "1", "--hd-decode-reps", "0", "--encode-images",
            "2", "--encode-scale", "0.002", "--no-cpu-baseline", "--no-single-stream"]
     env = dict(os.environ, OMP_NUM_THREADS="2")
     p = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=110)
@@ -179,3 +179,49 @@ def test_bench_as_rank_runs_one_shard():
     e = r["encoder_overfit"]
     assert e["shard"] == {"lambdas": [0.0004], "seed": 1, "rank": 6}
     assert sorted(x["image"] for x in e["records"]) == ["kodim01", "kodim02"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path, gpu):
+    """Without --full: the headline's fields only, --steps timed steps, and --dump-outputs writes
+    the last timed step's frames and rates (float32, whole at this size): bit for bit what one
+    eager step of the same pipeline on the same seeded inputs computes in this process (graph
+    replays launch the same kernels; bench.py's own --full check asserts the same equality)."""
+    import importlib.util
+    import json
+    import subprocess
+    import sys
+    from pathlib import Path
+
+    import numpy as np
+    import torch
+    root = Path(__file__).resolve().parents[1]
+    cmd = [sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "2",
+           "--dump-outputs", str(tmp_path / "out")]
+    p = subprocess.run(cmd, cwd=root, env=dict(os.environ, OMP_NUM_THREADS="2"), capture_output=True, text=True,
+                       timeout=110)
+    assert p.returncode == 0, p.stderr[-3000:]
+    line = [x for x in p.stdout.splitlines() if x.startswith("{")]
+    assert len(line) == 1, p.stdout[-2000:]
+    r = json.loads(line[0])
+    assert r["steps"] == 3 and r["ms_per_step"] > 0 and r["unit"] == "Mpixel/s" and r["higher_is_better"] is True
+    assert r["dtype"] == "f32" and r["launch"].startswith("HIP graph replays")
+    assert r["value"] == pytest.approx(2 * 720 * 1280 / (r["ms_per_step"] * 1e-3) / 1e6, rel=1e-3)
+    for k in ("path_a_1080p", "cpu_baseline", "bitexact_decode", "bitexact_encode", "bitexact_decode_1080p",
+              "encoder_overfit", "eager", "roofline", "stage_ms_per_step"):
+        assert k not in r, k
+    assert sorted(f.name for f in (tmp_path / "out").iterdir()) == ["rate.npy", "yuv.npy"]
+    yuv, rate = np.load(tmp_path / "out" / "yuv.npy"), np.load(tmp_path / "out" / "rate.npy")
+    assert yuv.dtype == np.float32 and rate.dtype == np.float32
+
+    spec = importlib.util.spec_from_file_location("bench_mod3", root / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    inp = bench.make_inputs(2, gpu, seed=1)  # rank 0's seed; the pipeline holds raw pointers into it
+    pipe = bench.Pipeline(inp, 2, gpu)
+    pipe.step(mode="fused", overlap=False)
+    torch.cuda.synchronize()
+    assert yuv.shape == tuple(pipe.yuv.shape) and rate.shape == tuple(pipe.rate.shape)
+    assert float(pipe.yuv.std()) > 0 and float(pipe.rate.mean()) > 0  # a decoded picture, not a cleared buffer
+    assert np.array_equal(yuv, pipe.yuv.cpu().numpy())
+    assert np.array_equal(rate, pipe.rate.cpu().numpy())
