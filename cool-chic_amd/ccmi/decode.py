@@ -135,6 +135,114 @@ def decode_batch_workspace_bytes(streams: Sequence[bytes], output_bitdepth: int 
     return out.value
 
 
+class FrameGeom(C.Structure):
+    """ccmi_frame_geom: geometry of one stream's decoded tensor."""
+    _fields_ = [("width", C.c_int), ("height", C.c_int), ("bitdepth", C.c_int), ("chroma", C.c_int),
+                ("frame_data_type", C.c_int), ("elems", C.c_size_t)]
+
+
+SAMPLE_U8, SAMPLE_U16, SAMPLE_F32 = 0, 1, 2  # CCMI_SAMPLE_*
+
+
+def _bind_dev():
+    L = _bind()
+    if not getattr(L, "_ccmi_dec_dev_bound", False):
+        L.ccmi_decode_batch_dev_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                 C.c_void_p, C.c_void_p]
+        L.ccmi_decode_batch_dev_plan.restype = C.c_int
+        L.ccmi_decode_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
+                                            C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
+        L.ccmi_decode_batch_dev.restype = C.c_int
+        L._ccmi_dec_dev_bound = True
+    return L
+
+
+def _marshal(streams):
+    n = len(streams)
+    if n < 1:
+        raise ValueError("decode_batch_tensors: no streams")
+    bufs = [C.create_string_buffer(s, len(s)) for s in streams]
+    sp = (C.c_void_p * n)(*[C.cast(b, C.c_void_p) for b in bufs])
+    ln = (C.c_size_t * n)(*[len(s) for s in streams])
+    return bufs, sp, ln
+
+
+def _plan_dev(m, output_bitdepth, output_chroma_format, dtype):
+    """(sample type, ccmi_frame_geom array, workspace bytes) of marshalled streams."""
+    import torch
+    n = len(m[0])
+    geom = (FrameGeom * n)()
+    need = C.c_size_t(0)
+
+    def plan(sample):
+        check(_bind_dev().ccmi_decode_batch_dev_plan(m[1], m[2], n, output_bitdepth, output_chroma_format, sample,
+                                                     geom, C.byref(need)))
+    if dtype is None:
+        plan(SAMPLE_U16)  # any bitdepth: learns every stream's output bitdepth
+        sample = SAMPLE_U8 if all(g.bitdepth <= 8 for g in geom) else SAMPLE_U16
+    else:
+        table = {torch.uint8: SAMPLE_U8, torch.uint16: SAMPLE_U16, torch.float32: SAMPLE_F32}
+        if dtype not in table:
+            raise ValueError(f"decode_batch_tensors: dtype {dtype} (torch.uint8, torch.uint16, torch.float32 or None)")
+        sample = table[dtype]
+    plan(sample)
+    return sample, geom, need.value
+
+
+def decode_batch_geometry(streams: Sequence[bytes], output_bitdepth: int = 0, output_chroma_format: int = 0,
+                          dtype=None) -> tuple:
+    """Header-only pass of decode_batch_tensors (ccmi_decode_batch_dev_plan; no CABAC, no GPU):
+    ([{'width', 'height', 'bitdepth', 'chroma', 'frame_data_type', 'elems'} per stream],
+    device workspace bytes the same arguments need)."""
+    _, geom, need = _plan_dev(_marshal(streams), output_bitdepth, output_chroma_format, dtype)
+    return [{k: int(getattr(g, k)) for k, _ in FrameGeom._fields_} for g in geom], need
+
+
+def decode_batch_tensors(streams: Sequence[bytes], output_bitdepth: int = 0, output_chroma_format: int = 0,
+                         dtype=None, stack: bool = False, workspace=None, stream_handle: int | None = None):
+    """Decode independent intra .cool streams straight into device tensors
+    (ccmi_decode_batch_dev): the integers decode_batch's bytes hold, in planar tensor layout on
+    the current CUDA device; no frame data crosses PCIe.
+
+    dtype None: torch.uint8 when every output bitdepth is <= 8, else torch.uint16;
+    torch.float32: sample / (2^bitdepth - 1), bitwise what u.to(float32) / maxv gives.
+    Returns one item per stream: a [3, H, W] tensor for 444 output (RGB streams: planar R, G,
+    B), or for 420 the {'y', 'u', 'v'} views of one flat allocation (forward.split_420).
+    stack=True (equal geometry required): one [n, 3, H, W] tensor, or the dict of [n, ., .]
+    views over one [n, elems] allocation.  workspace: a uint8 CUDA tensor of at least
+    decode_batch_geometry(...)[1] bytes, else torch's caching allocator provides it."""
+    import torch
+    from .forward import split_420
+    m = _marshal(streams)
+    _, sp, ln = m
+    sample, geom, need = _plan_dev(m, output_bitdepth, output_chroma_format, dtype)
+    tdtype = (torch.uint8, torch.uint16, torch.float32)[sample]
+    n = len(streams)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    if stack:
+        g0 = geom[0]
+        if any((g.width, g.height, g.chroma) != (g0.width, g0.height, g0.chroma) for g in geom):
+            raise ValueError("decode_batch_tensors: stack=True needs streams of one geometry and chroma format")
+        flat = torch.empty(n, g0.elems, dtype=tdtype, device=dev)
+        outs = [flat[i] for i in range(n)]
+    else:
+        outs = [torch.empty(g.elems, dtype=tdtype, device=dev) for g in geom]
+    op = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
+    cap = (C.c_size_t * n)(*[o.numel() * o.element_size() for o in outs])
+    if stream_handle is None:
+        stream_handle = torch.cuda.current_stream(dev).cuda_stream
+    if workspace is None:
+        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    check(_bind_dev().ccmi_decode_batch_dev(sp, ln, n, op, cap, sample, output_bitdepth, output_chroma_format,
+                                            workspace.data_ptr(), workspace.numel(), stream_handle))
+
+    def shaped(t, g):
+        return split_420(t, g.height, g.width) if g.chroma == 420 else t.reshape(*t.shape[:-1], 3, g.height, g.width)
+    if stack:
+        return shaped(flat, geom[0])
+    return [shaped(o, g) for o, g in zip(outs, geom)]
+
+
 def weights_i32(stream: bytes):
     """(arm, ups, syn) fixed-point network integers of a stream's intra frame, as the
     decoder uses them (ccmi_decode_weights_i32; cc-frame-decoder.cpp:201-353)."""
@@ -245,4 +353,5 @@ def last_arm_flags() -> list[int]:
 
 
 __all__ = ["last_timing", "last_arm_flags", "decode_latents", "decode_file", "decode_batch", "decode_batch_workspace_bytes", "output_size",
+           "decode_batch_tensors", "decode_batch_geometry",
            "weights_i32", "ups_forward_i32", "syn_forward_i32", "CcmiError"]

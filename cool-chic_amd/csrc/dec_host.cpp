@@ -277,6 +277,39 @@ int out_format(const FrameHost &f, int out_bitdepth, int out_chroma, int as_yuv,
     return CCMI_OK;
 }
 
+// Where decode_many leaves the decoded frames.  Host bytes (the default): file layout,
+// staged in the workspace and copied to the caller's host buffers.  Device tensors: the
+// output kernel writes planar samples of type `sample` straight to the caller's device
+// pointers; nothing is staged and nothing is downloaded.
+struct Sink {
+    int sample = -1;             // -1 host bytes, else CCMI_SAMPLE_*
+    void *const *dev = nullptr;  // [n] device pointers (NULL: planning only)
+    ccmi_frame_geom *geom = nullptr; // [n], optional: filled by the header pass
+    bool device() const { return sample >= 0; }
+};
+
+size_t sample_bytes(int sample) { return sample == CCMI_SAMPLE_U8 ? 1 : sample == CCMI_SAMPLE_U16 ? 2 : 4; }
+
+// output of a device sink: planar 420 / 444 samples, no header; payload = bytes at the caller's pointer
+int tensor_format(const FrameHost &f, int out_bitdepth, int out_chroma, int sample, OutFmt &o, size_t *elems)
+{
+    if (sample != CCMI_SAMPLE_U8 && sample != CCMI_SAMPLE_U16 && sample != CCMI_SAMPLE_F32)
+        return ccmi_set_error(CCMI_ERR_ARG, "decode: unknown sample type %d", sample);
+    if (out_chroma != 0 && out_chroma != 420 && out_chroma != 444)
+        return ccmi_set_error(CCMI_ERR_ARG, "decode: output chroma format %d (0, 420 or 444)", out_chroma);
+    o.bitdepth = out_bitdepth ? out_bitdepth : f.bitdepth;
+    if (o.bitdepth < 1 || o.bitdepth > 16) return ccmi_set_error(CCMI_ERR_ARG, "decode: output bitdepth %d", o.bitdepth);
+    if (sample == CCMI_SAMPLE_U8 && o.bitdepth > 8)
+        return ccmi_set_error(CCMI_ERR_ARG, "decode: %d-bit samples do not fit CCMI_SAMPLE_U8", o.bitdepth);
+    const int chroma = out_chroma ? out_chroma : (f.frame_data_type == 1 ? 420 : 444);
+    const size_t npx = (size_t)f.h * f.w;
+    o.kind = chroma == 420 ? kYuv420 : kYuv444;
+    o.header = 0;
+    *elems = o.kind == kYuv420 ? npx + 2 * (size_t)(f.h / 2) * (f.w / 2) : 3 * npx;
+    o.payload = sample_bytes(sample) * *elems;
+    return CCMI_OK;
+}
+
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 struct DevPlan {
@@ -365,9 +398,12 @@ int decode_weights_all(std::vector<FrameHost> &fr)
 
 // ws / ws_bytes: caller-owned device workspace (NULL: one hipMalloc per call); need: when
 // not NULL, only the workspace size is computed (headers parsed, nothing decoded or launched).
+// sink: host bytes at outs[i] (as_yuv picks the file layout), or device tensors at sink.dev[i]
+// (outs NULL, as_yuv unused); caps[i] is the capacity in bytes of either.
 int decode_many(const uint8_t *const *streams, const size_t *lens, int n, uint8_t *const *outs, const size_t *caps,
                 size_t *sizes, int out_bitdepth, int out_chroma, int as_yuv, hipStream_t s,
-                int32_t *const *lat_out = nullptr, void *ws = nullptr, size_t ws_bytes = 0, size_t *need = nullptr)
+                int32_t *const *lat_out = nullptr, void *ws = nullptr, size_t ws_bytes = 0, size_t *need = nullptr,
+                const Sink &sink = Sink())
 {
     if (n < 1) return ccmi_set_error(CCMI_ERR_ARG, "decode: no streams");
     std::vector<FrameHost> fr(n);
@@ -378,8 +414,22 @@ int decode_many(const uint8_t *const *streams, const size_t *lens, int n, uint8_
             std::string m = ccmi_last_error();
             return ccmi_set_error(rc, "stream %d: %s", i, m.c_str());
         }
-        if (int rc = out_format(fr[i], out_bitdepth, out_chroma, as_yuv, of[i])) return rc;
-        if (outs && caps && caps[i] < of[i].header + of[i].payload)
+        if (sink.device()) {
+            size_t elems = 0;
+            if (int rc = tensor_format(fr[i], out_bitdepth, out_chroma, sink.sample, of[i], &elems)) return rc;
+            if (sink.geom)
+                sink.geom[i] = ccmi_frame_geom{fr[i].w, fr[i].h, of[i].bitdepth, of[i].kind == kYuv420 ? 420 : 444,
+                                               fr[i].frame_data_type, elems};
+            if (sink.dev) {
+                if (!sink.dev[i]) return ccmi_set_error(CCMI_ERR_ARG, "decode: output %d is NULL", i);
+                if (reinterpret_cast<uintptr_t>(sink.dev[i]) % sample_bytes(sink.sample))
+                    return ccmi_set_error(CCMI_ERR_ARG, "decode: output %d is not aligned to its %zu-byte samples", i,
+                                          sample_bytes(sink.sample));
+            }
+        } else if (int rc = out_format(fr[i], out_bitdepth, out_chroma, as_yuv, of[i])) {
+            return rc;
+        }
+        if ((outs || sink.dev) && caps && caps[i] < of[i].header + of[i].payload)
             return ccmi_set_error(CCMI_ERR_ARG, "stream %d: output buffer of %zu bytes, need %zu", i, caps[i],
                                   of[i].header + of[i].payload);
         if (sizes) sizes[i] = of[i].header + of[i].payload;
@@ -429,7 +479,7 @@ int decode_many(const uint8_t *const *streams, const size_t *lens, int n, uint8_
         p.synws_off = tot;
         tot += align_up(p.synws_elems * 4 + 4, 256);
         p.out_off = tot;
-        tot += align_up(of[i].payload, 256);
+        if (!sink.device()) tot += align_up(of[i].payload, 256); // device sinks write to the caller's memory
     }
     const size_t desc_off = tot;
     tot += align_up(sizeof(ArmStreamDesc) * (size_t)n * CCMI_MAX_GRIDS, 256);
@@ -611,7 +661,8 @@ int decode_many(const uint8_t *const *streams, const size_t *lens, int n, uint8_
         sa.f24 = syn_weights_fit24(f) ? 1 : 0;
         t.bitdepth = of[i].bitdepth;
         t.kind = of[i].kind;
-        t.dst = dev + p.out_off;
+        t.dst = sink.device() ? static_cast<uint8_t *>(sink.dev[i]) : dev + p.out_off;
+        t.sample = sink.sample;
     }
     // frames of one geometry share one launch per tail stage (960 class-E frames: 134 ms
     // against 264 ms with per-frame launches)
@@ -677,16 +728,19 @@ int decode_many(const uint8_t *const *streams, const size_t *lens, int n, uint8_
                                                   f.blend[0], f.blend[b], b == 1, cs))
                         return rc;
             }
-            if (int rc = launch_dec_output(synout, f.h, f.w, of[i].bitdepth, of[i].kind, dev + p.out_off, cs)) return rc;
+            if (int rc = sink.device() ? launch_dec_output_tensor(synout, f.h, f.w, of[i].bitdepth, of[i].kind,
+                                                                  sink.sample, tail[i].dst, cs)
+                                       : launch_dec_output(synout, f.h, f.w, of[i].bitdepth, of[i].kind, tail[i].dst, cs))
+                return rc;
         }
         return CCMI_OK;
     };
     // the decoded bytes of chunk c: headers on the host, payloads copied back on the chunk's
     // own stream right after its tail, so one chunk's download overlaps the other chunk's
     // ARM chains (pinned output buffers make these real DMA copies; pageable ones are staged
-    // by the runtime)
+    // by the runtime).  A device sink has nothing to download: its frames are where they belong.
     auto download_chunk = [&](int c, hipStream_t cs) -> int {
-        for (int i = 0; i < n && outs; ++i) {
+        for (int i = 0; i < n && outs && !sink.device(); ++i) {
             if (chunk_of[i] != c) continue;
             if (of[i].header) memcpy(outs[i], of[i].hdr, of[i].header);
             CCMI_HIP_CHECK(hipMemcpyAsync(outs[i] + of[i].header, dev + pl[i].out_off, of[i].payload,
@@ -792,6 +846,7 @@ int decode_many(const uint8_t *const *streams, const size_t *lens, int n, uint8_
             g_last_ms[3] = all - span;
             (void)hipGetLastError(); // a timing query that failed must not surface in the next call
         }
+        if (sink.device()) g_last_ms[3] = 0.f; // nothing was downloaded (the status words are not frame data)
     }
     return CCMI_OK;
 }
@@ -859,6 +914,33 @@ extern "C" int ccmi_decode_batch_ws(const uint8_t *const *streams, const size_t 
         return ccmi_set_error(CCMI_ERR_ARG, "decode_batch_ws: null argument");
     return decode_many(streams, lens, n, out, out_caps, out_sizes, out_bitdepth, out_chroma, as_yuv,
                        static_cast<hipStream_t>(stream), nullptr, workspace, workspace_bytes);
+}
+
+extern "C" int ccmi_decode_batch_dev_plan(const uint8_t *const *streams, const size_t *lens, int n, int out_bitdepth,
+                                          int out_chroma, int sample_type, ccmi_frame_geom *geom,
+                                          size_t *workspace_bytes)
+{
+    if (!streams || !lens || !geom || !workspace_bytes)
+        return ccmi_set_error(CCMI_ERR_ARG, "decode_batch_dev_plan: null argument");
+    Sink sink;
+    sink.sample = sample_type;
+    sink.geom = geom;
+    if (sample_type < 0) return ccmi_set_error(CCMI_ERR_ARG, "decode: unknown sample type %d", sample_type);
+    return decode_many(streams, lens, n, nullptr, nullptr, nullptr, out_bitdepth, out_chroma, 0, nullptr, nullptr,
+                       nullptr, 0, workspace_bytes, sink);
+}
+
+extern "C" int ccmi_decode_batch_dev(const uint8_t *const *streams, const size_t *lens, int n, void *const *out_dev,
+                                     const size_t *out_caps, int sample_type, int out_bitdepth, int out_chroma,
+                                     void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!streams || !lens || !out_dev || !out_caps) return ccmi_set_error(CCMI_ERR_ARG, "decode_batch_dev: null argument");
+    if (sample_type < 0) return ccmi_set_error(CCMI_ERR_ARG, "decode: unknown sample type %d", sample_type);
+    Sink sink;
+    sink.sample = sample_type;
+    sink.dev = out_dev;
+    return decode_many(streams, lens, n, nullptr, out_caps, nullptr, out_bitdepth, out_chroma, 0,
+                       static_cast<hipStream_t>(stream), nullptr, workspace, workspace_bytes, nullptr, sink);
 }
 
 extern "C" int ccmi_decode_latents(const uint8_t *stream, size_t len, int32_t *out, size_t cap, void *hstream)

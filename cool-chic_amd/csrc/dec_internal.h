@@ -112,6 +112,10 @@ int launch_dec_blend(int32_t *acc, const int32_t *x, int64_t n, int32_t b_acc, i
 // Output conversion (ccdecapi.cpp:59-240): syn output (12-bit) -> file bytes.
 // kind: 0 yuv420, 1 yuv444, 2 ppm payload (interleaved RGB).  bps = 1 or 2 bytes/sample.
 int launch_dec_output(const int32_t *syn, int h, int w, int bitdepth, int kind, uint8_t *dst, hipStream_t s);
+// The same samples as a planar device tensor (ccmi_decode_batch_dev): kind 0 Y[H][W] U V
+// [H/2][W/2], kind 1 [3][H][W]; sample = CCMI_SAMPLE_*; dst needs one sample's alignment only.
+int launch_dec_output_tensor(const int32_t *syn, int h, int w, int bitdepth, int kind, int sample, void *dst,
+                             hipStream_t s);
 
 // Batched decoder tail: frames with the same geometry and a fused-synthesis architecture
 // (single branch) share one launch per pyramid step, one synthesis and one output launch
@@ -123,6 +127,7 @@ struct DecTailFrame {
     DecSynArgs syn;
     int bitdepth, kind;
     uint8_t *dst;
+    int sample = -1; // -1: file bytes at dst (workspace staging); CCMI_SAMPLE_*: planar tensor at dst (caller's)
 };
 bool dec_tail_batchable(const DecTailFrame &f);
 bool dec_tail_same_group(const DecTailFrame &a, const DecTailFrame &b);

@@ -17,6 +17,8 @@
 //                   (syn_cpu.hpp / synlb_cpu.hpp) with replicate padding, one launch.
 //  dec_syn_layer    generic per-layer integer conv (any ks / widths).
 //  dec_output       444 -> 420/444 8/10-bit or PPM payload (ccdecapi.cpp:59-240).
+//  dec_output_tensor  the same samples as planar u8 / u16 / f32 device tensors (no file
+//                   layout): one packed store per 4 destination samples, any sample alignment.
 #include <stdlib.h>
 
 #include <type_traits>
@@ -1608,6 +1610,113 @@ __device__ __forceinline__ void output_body(const int32_t *__restrict__ syn, int
     }
 }
 
+// ------------------------------------------------------------------ output tensors
+// Device sink: the same samples as output_body (smp(), same 420 subsampling) in planar
+// tensor layout, never interleaved.  Both layouts are ONE flat array of samples:
+//   444: [3][H][W], sample j is smp(syn[j]);
+//   420: Y[H][W] then U, V [H/2][W/2], contiguous: j < HW as above, the rest a stride-2 gather.
+// A thread owns one naturally aligned group of 4 destination samples (one 32 / 64 / 128-bit
+// store for u8 / u16 / f32).  dst only has the alignment of one sample, so the groups are
+// laid out from the aligned address at or below dst: the first and the last group of a frame
+// are partial and take scalar stores, every other group one packed store -- the chroma
+// samples too, which the byte path writes one byte per thread.  DecOut::bps is unused here
+// (the sample type is the template argument).
+template <typename T> struct OutVec;
+template <> struct OutVec<uint8_t> { using type = uint32_t; };
+template <> struct OutVec<uint16_t> { using type = uint2; };
+template <> struct OutVec<float> { using type = float4; };
+
+template <typename T> __device__ __forceinline__ T out_sample(int32_t s, float fmax);
+template <> __device__ __forceinline__ uint8_t out_sample<uint8_t>(int32_t s, float) { return (uint8_t)s; }
+template <> __device__ __forceinline__ uint16_t out_sample<uint16_t>(int32_t s, float) { return (uint16_t)s; }
+// one correctly rounded division: what torch's u.to(float32) / maxv computes
+template <> __device__ __forceinline__ float out_sample<float>(int32_t s, float fmax) { return __fdiv_rn((float)s, fmax); }
+
+template <typename T>
+__device__ __forceinline__ void output_tensor_body(const int32_t *__restrict__ syn, int H, int W, int maxv, int kind,
+                                                   T *__restrict__ dst)
+{
+    const int64_t plane = (int64_t)H * W;
+    const int ch = H / 2, cw = W / 2;
+    const int64_t cp = (int64_t)ch * cw;
+    const int64_t elems = kind == 1 ? 3 * plane : plane + 2 * cp;
+    const int64_t direct = kind == 1 ? elems : plane; // samples below this index read syn[j]
+    const int mis = (int)((reinterpret_cast<uintptr_t>(dst) / sizeof(T)) & 3); // samples past the aligned address
+    const int64_t j0 = ((int64_t)blockIdx.x * kThreads + threadIdx.x) * 4 - mis;
+    if (j0 >= elems) return;
+    const float fmax = (float)maxv;
+    auto smp = [maxv](int32_t v) {
+        int32_t s = (v * maxv + (1 << (kSynPrec - 1))) >> kSynPrec;
+        return s < 0 ? 0 : (s > maxv ? maxv : s);
+    };
+    T v[4];
+    if (j0 >= 0 && j0 + 4 <= direct) { // the common case: 4 samples of the flat prefix
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = out_sample<T>(smp(syn[j0 + k]), fmax);
+    } else {
+        // a group that is partial, crosses into the chroma planes or lies in them: one
+        // division for its first chroma sample, the others step along the row
+        int64_t c = 0;
+        int cy = 0, cx = 0;
+        const int64_t jc = (j0 > direct ? j0 : direct) - direct; // first chroma index of the group
+        if (kind != 1 && cp > 0) {
+            c = jc / cp;
+            const int64_t ci = jc - c * cp;
+            cy = (int)(ci / cw);
+            cx = (int)(ci - (int64_t)cy * cw);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int64_t j = j0 + k;
+            v[k] = T(0);
+            if (j < 0 || j >= elems) continue;
+            if (j < direct) {
+                v[k] = out_sample<T>(smp(syn[j]), fmax);
+                continue;
+            }
+            v[k] = out_sample<T>(smp(syn[(1 + c) * plane + (int64_t)(2 * cy) * W + 2 * cx]), fmax);
+            if (++cx == cw) {
+                cx = 0;
+                if (++cy == ch) {
+                    cy = 0;
+                    ++c;
+                }
+            }
+        }
+    }
+    if (j0 >= 0 && j0 + 4 <= elems) {
+        typename OutVec<T>::type pk;
+        __builtin_memcpy(&pk, v, sizeof pk);
+        *reinterpret_cast<typename OutVec<T>::type *>(dst + j0) = pk;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (j0 + k >= 0 && j0 + k < elems) dst[j0 + k] = v[k];
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_output_tensor(const int32_t *__restrict__ syn, int H, int W, int maxv,
+                                                              int kind, T *__restrict__ dst)
+{
+    output_tensor_body<T>(syn, H, W, maxv, kind, dst);
+}
+
+template <typename T> __global__ __launch_bounds__(kThreads) void dec_output_tensor_batch(const DecOut *__restrict__ Os)
+{
+    const DecOut O = Os[blockIdx.y];
+    output_tensor_body<T>(O.syn, O.H, O.W, O.maxv, O.kind, reinterpret_cast<T *>(O.dst));
+}
+
+// blocks that cover the samples of one frame plus the up to 3 lead-in slots of an unaligned dst
+unsigned output_tensor_blocks(int h, int w, int kind)
+{
+    const int64_t plane = (int64_t)h * w;
+    const int64_t elems = kind == 1 ? 3 * plane : plane + 2 * (int64_t)(h / 2) * (w / 2);
+    const int64_t groups = (elems + 3 + 3) / 4;
+    return (unsigned)((groups + kThreads - 1) / kThreads);
+}
+
 } // namespace
 
 // ------------------------------------------------------------------ launchers
@@ -1852,6 +1961,31 @@ int launch_dec_output(const int32_t *syn, int h, int w, int bitdepth, int kind, 
     return CCMI_OK;
 }
 
+int launch_dec_output_tensor(const int32_t *syn, int h, int w, int bitdepth, int kind, int sample, void *dst,
+                             hipStream_t s)
+{
+    if (kind != 0 && kind != 1) return ccmi_set_error(CCMI_ERR_ARG, "dec: tensor output kind %d", kind);
+    const dim3 grid(output_tensor_blocks(h, w, kind));
+    const int maxv = (1 << bitdepth) - 1;
+    switch (sample) {
+    case CCMI_SAMPLE_U8:
+        hipLaunchKernelGGL(dec_output_tensor<uint8_t>, grid, dim3(kThreads), 0, s, syn, h, w, maxv, kind,
+                           static_cast<uint8_t *>(dst));
+        break;
+    case CCMI_SAMPLE_U16:
+        hipLaunchKernelGGL(dec_output_tensor<uint16_t>, grid, dim3(kThreads), 0, s, syn, h, w, maxv, kind,
+                           static_cast<uint16_t *>(dst));
+        break;
+    case CCMI_SAMPLE_F32:
+        hipLaunchKernelGGL(dec_output_tensor<float>, grid, dim3(kThreads), 0, s, syn, h, w, maxv, kind,
+                           static_cast<float *>(dst));
+        break;
+    default: return ccmi_set_error(CCMI_ERR_ARG, "dec: sample type %d", sample);
+    }
+    CCMI_HIP_CHECK(hipGetLastError());
+    return CCMI_OK;
+}
+
 // ------------------------------------------------------------------ batched decoder tail
 // fused-synthesis kernel arguments of one frame (syn_fast architectures only); the same
 // weight walk as launch_dec_syn
@@ -1903,6 +2037,8 @@ bool dec_tail_same_group(const DecTailFrame &a, const DecTailFrame &b)
     if (a.ups.n_layers != b.ups.n_layers) return false;
     for (int l = 0; l < a.ups.n_layers; ++l)
         if (a.ups.lh[l] != b.ups.lh[l] || a.ups.lw[l] != b.ups.lw[l]) return false;
+    // tensor outputs: the output grid is sized by the sample count, i.e. by the chroma format too
+    if (a.sample != b.sample || (a.sample >= 0 && a.kind != b.kind)) return false;
     return a.syn.n_layers == b.syn.n_layers && a.syn.c_in == b.syn.c_in && a.syn.h == b.syn.h && a.syn.w == b.syn.w;
 }
 
@@ -1963,8 +2099,19 @@ int launch_dec_tail_batch(const DecTailFrame &f0, int n, const void *dev_tab, hi
     }
     CCMI_HIP_CHECK(hipGetLastError());
     const int64_t plane = (int64_t)f0.syn.h * f0.syn.w;
-    hipLaunchKernelGGL(dec_output_batch, dim3((unsigned)((plane + kThreads - 1) / kThreads), n), dim3(kThreads), 0, s,
-                       oo);
+    if (f0.sample < 0) {
+        hipLaunchKernelGGL(dec_output_batch, dim3((unsigned)((plane + kThreads - 1) / kThreads), n), dim3(kThreads), 0,
+                           s, oo);
+    } else {
+        const dim3 grid(output_tensor_blocks(f0.syn.h, f0.syn.w, f0.kind), n); // one kind per group
+
+        switch (f0.sample) {
+        case CCMI_SAMPLE_U8: hipLaunchKernelGGL(dec_output_tensor_batch<uint8_t>, grid, dim3(kThreads), 0, s, oo); break;
+        case CCMI_SAMPLE_U16: hipLaunchKernelGGL(dec_output_tensor_batch<uint16_t>, grid, dim3(kThreads), 0, s, oo); break;
+        case CCMI_SAMPLE_F32: hipLaunchKernelGGL(dec_output_tensor_batch<float>, grid, dim3(kThreads), 0, s, oo); break;
+        default: return ccmi_set_error(CCMI_ERR_ARG, "dec: sample type %d", f0.sample);
+        }
+    }
     CCMI_HIP_CHECK(hipGetLastError());
     return CCMI_OK;
 }

@@ -212,7 +212,7 @@ int ccmi_decode_batch(const uint8_t *const *streams, const size_t *lens, int n,
 /* Device-side stage times (ms, HIP events on the decode stream) of this thread's last
  * successful ccmi_decode_batch / ccmi_decode_file: [0] upload of streams + weights,
  * [1] ARM + CABAC latent decode, [2] upsampling + synthesis + output conversion,
- * [3] download of the decoded bytes. */
+ * [3] download of the decoded bytes (0 after ccmi_decode_batch_dev: nothing is downloaded). */
 int ccmi_decode_last_timing(float *ms4);
 
 /* What the latent decode of this thread's last ccmi_decode_* call did, per stream: flags[i]
@@ -253,6 +253,43 @@ int ccmi_decode_batch_ws(const uint8_t *const *streams, const size_t *lens, int 
                          uint8_t *const *out, const size_t *out_caps, size_t *out_sizes,
                          int out_bitdepth, int out_chroma, int as_yuv, void *workspace,
                          size_t workspace_bytes, void *stream);
+
+/* Decoded frames as DEVICE tensors: the same decode as ccmi_decode_batch, but the samples
+ * stay on the GPU in planar tensor layout (the layout of ccmi_post_f32 and of the trainer's
+ * target): no frame data crosses PCIe, no file layout, no interleaving, no PPM header.
+ *   444 output: [3][H][W] (RGB streams: planar R, G, B);
+ *   420 output: Y[H][W], then U and V [H/2][W/2] (floor; the sample at the even row and
+ *               column, as the .yuv writer takes it), one contiguous array of `elems` samples.
+ * The sample values are exactly the integers the byte path writes for the same
+ * (out_bitdepth, out_chroma); out_bitdepth 0 = the header's, any of 1..16 is accepted (the
+ * .yuv writer's 8 / 10 limit is a file-format rule); out_chroma 0 = the header's, 420 or 444.
+ *   CCMI_SAMPLE_U8:  uint8,  bitdepth <= 8 (else CCMI_ERR_ARG);
+ *   CCMI_SAMPLE_U16: uint16, native byte order;
+ *   CCMI_SAMPLE_F32: (float)sample / (float)(2^bitdepth - 1), one correctly rounded division.
+ * ccmi_decode_batch_dev_plan() is the header-only pass (no CABAC, no GPU work): geometry of
+ * every stream's output and the device workspace the same arguments need.
+ * ccmi_decode_batch_dev(): out_dev[i] is a device pointer with room for out_caps[i] BYTES
+ * (>= elems * sample size); it only needs the alignment of one sample (frames of a stacked
+ * batch may start at any sample).  workspace NULL: the library allocates for the call;
+ * otherwise >= workspace_bytes of the plan, 256-byte aligned.  The call synchronises
+ * `stream` before it returns (the ARM status words are read back: a CCMI_ARM_FLAG_TIMEOUT is
+ * CCMI_ERR_HIP), ccmi_decode_last_arm_flags() works as for the byte path and
+ * ccmi_decode_last_timing() reports [3] (download) as 0. */
+enum { CCMI_SAMPLE_U8 = 0, CCMI_SAMPLE_U16 = 1, CCMI_SAMPLE_F32 = 2 };
+typedef struct ccmi_frame_geom {
+    int width, height;
+    int bitdepth;        /* of the output samples (out_bitdepth, or the header's) */
+    int chroma;          /* 420 or 444, of the output */
+    int frame_data_type; /* as in the stream header (0 rgb, 1 yuv420, 2 yuv444) */
+    size_t elems;        /* samples per frame: 3 H W, or H W + 2 (H/2)(W/2) */
+} ccmi_frame_geom;
+int ccmi_decode_batch_dev_plan(const uint8_t *const *streams, const size_t *lens, int n,
+                               int out_bitdepth, int out_chroma, int sample_type,
+                               ccmi_frame_geom *geom /* [n] */, size_t *workspace_bytes);
+int ccmi_decode_batch_dev(const uint8_t *const *streams, const size_t *lens, int n,
+                          void *const *out_dev, const size_t *out_caps, int sample_type,
+                          int out_bitdepth, int out_chroma, void *workspace,
+                          size_t workspace_bytes, void *stream);
 
 /* Network weights of a stream's intra frame as the decoder's fixed-point integers
  * (cc-frame-decoder.cpp:201-353, read_arm / read_ups / read_syn):
