@@ -141,6 +141,16 @@ class FrameGeom(C.Structure):
                 ("frame_data_type", C.c_int), ("elems", C.c_size_t)]
 
 
+class Rect(C.Structure):
+    """ccmi_rect: a region of a frame in luma samples, x / y = its top-left corner."""
+    _fields_ = [("x", C.c_int), ("y", C.c_int), ("w", C.c_int), ("h", C.c_int)]
+
+
+class RoiInfo(C.Structure):
+    """ccmi_roi_info: what a region decode of one stream does."""
+    _fields_ = [("n_grids", C.c_int), ("arm_rows", C.c_int * MAX_GRIDS), ("windowed", C.c_int)]
+
+
 SAMPLE_U8, SAMPLE_U16, SAMPLE_F32 = 0, 1, 2  # CCMI_SAMPLE_*
 
 
@@ -153,6 +163,14 @@ def _bind_dev():
         L.ccmi_decode_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
                                             C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
         L.ccmi_decode_batch_dev.restype = C.c_int
+        if hasattr(L, "ccmi_decode_batch_dev_roi"):  # absent from older builds loaded for A/B runs
+            L.ccmi_decode_batch_dev_roi_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                                         C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+            L.ccmi_decode_batch_dev_roi_plan.restype = C.c_int
+            L.ccmi_decode_batch_dev_roi.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                                    C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
+                                                    C.c_void_p]
+            L.ccmi_decode_batch_dev_roi.restype = C.c_int
         L._ccmi_dec_dev_bound = True
     return L
 
@@ -167,7 +185,30 @@ def _marshal(streams):
     return bufs, sp, ln
 
 
-def _plan_dev(m, output_bitdepth, output_chroma_format, dtype):
+def _rects(roi, streams, n):
+    """roi argument -> ccmi_rect array, or None for whole frames.  One (x, y, w, h) for every
+    stream, or a sequence with one entry per stream; an entry None is that stream's whole frame
+    (its size read from the stream's GOP header)."""
+    if roi is None:
+        return None
+    one = len(roi) == 4 and all(isinstance(v, int) for v in roi)
+    rois = [tuple(roi)] * n if one else list(roi)
+    if len(rois) != n:
+        raise ValueError(f"roi: one (x, y, w, h), or one entry per stream ({n}), got {len(rois)}")
+    arr = (Rect * n)()
+    for i, r in enumerate(rois):
+        if r is None:
+            s = streams[i]
+            if len(s) < 6:
+                raise ValueError(f"stream {i}: truncated GOP header")
+            r = (0, 0, int.from_bytes(s[4:6], "big"), int.from_bytes(s[2:4], "big"))
+        if len(r) != 4:
+            raise ValueError(f"roi[{i}]: (x, y, w, h) expected")
+        arr[i] = Rect(*[int(v) for v in r])
+    return arr
+
+
+def _plan_dev(m, output_bitdepth, output_chroma_format, dtype, rects=None, info=None):
     """(sample type, ccmi_frame_geom array, workspace bytes) of marshalled streams."""
     import torch
     n = len(m[0])
@@ -175,8 +216,12 @@ def _plan_dev(m, output_bitdepth, output_chroma_format, dtype):
     need = C.c_size_t(0)
 
     def plan(sample):
-        check(_bind_dev().ccmi_decode_batch_dev_plan(m[1], m[2], n, output_bitdepth, output_chroma_format, sample,
-                                                     geom, C.byref(need)))
+        if rects is None and info is None:
+            check(_bind_dev().ccmi_decode_batch_dev_plan(m[1], m[2], n, output_bitdepth, output_chroma_format, sample,
+                                                         geom, C.byref(need)))
+        else:
+            check(_bind_dev().ccmi_decode_batch_dev_roi_plan(m[1], m[2], n, rects, output_bitdepth,
+                                                             output_chroma_format, sample, geom, info, C.byref(need)))
     if dtype is None:
         plan(SAMPLE_U16)  # any bitdepth: learns every stream's output bitdepth
         sample = SAMPLE_U8 if all(g.bitdepth <= 8 for g in geom) else SAMPLE_U16
@@ -190,16 +235,30 @@ def _plan_dev(m, output_bitdepth, output_chroma_format, dtype):
 
 
 def decode_batch_geometry(streams: Sequence[bytes], output_bitdepth: int = 0, output_chroma_format: int = 0,
-                          dtype=None) -> tuple:
-    """Header-only pass of decode_batch_tensors (ccmi_decode_batch_dev_plan; no CABAC, no GPU):
+                          dtype=None, roi=None) -> tuple:
+    """Header-only pass of decode_batch_tensors (ccmi_decode_batch_dev_plan / _roi_plan; no
+    CABAC, no GPU):
     ([{'width', 'height', 'bitdepth', 'chroma', 'frame_data_type', 'elems'} per stream],
-    device workspace bytes the same arguments need)."""
-    _, geom, need = _plan_dev(_marshal(streams), output_bitdepth, output_chroma_format, dtype)
+    device workspace bytes the same arguments need).  roi as for decode_batch_tensors: width,
+    height and elems are then the region's."""
+    _, geom, need = _plan_dev(_marshal(streams), output_bitdepth, output_chroma_format, dtype,
+                              _rects(roi, streams, len(streams)))
     return [{k: int(getattr(g, k)) for k, _ in FrameGeom._fields_} for g in geom], need
 
 
+def roi_plan(streams: Sequence[bytes], roi, output_bitdepth: int = 0, output_chroma_format: int = 0, dtype=None) -> list:
+    """What a region decode will do, per stream (ccmi_decode_batch_dev_roi_plan, header-only):
+    {'arm_rows': [rows of latent grid l the ARM + CABAC decode produces], 'windowed': True when
+    the decoder tail runs on the region's windows, False when it runs on the whole frame and the
+    output kernel crops}."""
+    n = len(streams)
+    info = (RoiInfo * n)()
+    _plan_dev(_marshal(streams), output_bitdepth, output_chroma_format, dtype, _rects(roi, streams, n), info)
+    return [{"arm_rows": [int(v) for v in i.arm_rows[: i.n_grids]], "windowed": bool(i.windowed)} for i in info]
+
+
 def decode_batch_tensors(streams: Sequence[bytes], output_bitdepth: int = 0, output_chroma_format: int = 0,
-                         dtype=None, stack: bool = False, workspace=None, stream_handle: int | None = None):
+                         dtype=None, stack: bool = False, workspace=None, stream_handle: int | None = None, roi=None):
     """Decode independent intra .cool streams straight into device tensors
     (ccmi_decode_batch_dev): the integers decode_batch's bytes hold, in planar tensor layout on
     the current CUDA device; no frame data crosses PCIe.
@@ -208,21 +267,27 @@ def decode_batch_tensors(streams: Sequence[bytes], output_bitdepth: int = 0, out
     torch.float32: sample / (2^bitdepth - 1), bitwise what u.to(float32) / maxv gives.
     Returns one item per stream: a [3, H, W] tensor for 444 output (RGB streams: planar R, G,
     B), or for 420 the {'y', 'u', 'v'} views of one flat allocation (forward.split_420).
-    stack=True (equal geometry required): one [n, 3, H, W] tensor, or the dict of [n, ., .]
-    views over one [n, elems] allocation.  workspace: a uint8 CUDA tensor of at least
-    decode_batch_geometry(...)[1] bytes, else torch's caching allocator provides it."""
+    stack=True (one output size and chroma format required): one [n, 3, H, W] tensor, or the
+    dict of [n, ., .] views over one [n, elems] allocation.  workspace: a uint8 CUDA tensor of
+    at least decode_batch_geometry(...)[1] bytes, else torch's caching allocator provides it.
+    roi: decode a region only (ccmi_decode_batch_dev_roi): one (x, y, w, h) in luma samples for
+    every stream, or a sequence with one entry per stream (None: that stream's whole frame).
+    The result is, sample for sample, the crop [y:y+h, x:x+w] of the whole-frame decode (420: x
+    and y even, chroma [y/2 : y/2 + h/2, x/2 : x/2 + w/2]) and H, W above are the region's, so
+    stack=True takes equal-size crops of frames of different sizes."""
     import torch
     from .forward import split_420
     m = _marshal(streams)
     _, sp, ln = m
-    sample, geom, need = _plan_dev(m, output_bitdepth, output_chroma_format, dtype)
+    rects = _rects(roi, streams, len(streams))
+    sample, geom, need = _plan_dev(m, output_bitdepth, output_chroma_format, dtype, rects)
     tdtype = (torch.uint8, torch.uint16, torch.float32)[sample]
     n = len(streams)
     dev = torch.device("cuda", torch.cuda.current_device())
     if stack:
         g0 = geom[0]
         if any((g.width, g.height, g.chroma) != (g0.width, g0.height, g0.chroma) for g in geom):
-            raise ValueError("decode_batch_tensors: stack=True needs streams of one geometry and chroma format")
+            raise ValueError("decode_batch_tensors: stack=True needs outputs of one size and chroma format")
         flat = torch.empty(n, g0.elems, dtype=tdtype, device=dev)
         outs = [flat[i] for i in range(n)]
     else:
@@ -233,8 +298,13 @@ def decode_batch_tensors(streams: Sequence[bytes], output_bitdepth: int = 0, out
         stream_handle = torch.cuda.current_stream(dev).cuda_stream
     if workspace is None:
         workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-    check(_bind_dev().ccmi_decode_batch_dev(sp, ln, n, op, cap, sample, output_bitdepth, output_chroma_format,
-                                            workspace.data_ptr(), workspace.numel(), stream_handle))
+    if rects is None:
+        check(_bind_dev().ccmi_decode_batch_dev(sp, ln, n, op, cap, sample, output_bitdepth, output_chroma_format,
+                                                workspace.data_ptr(), workspace.numel(), stream_handle))
+    else:
+        check(_bind_dev().ccmi_decode_batch_dev_roi(sp, ln, n, rects, op, cap, sample, output_bitdepth,
+                                                    output_chroma_format, workspace.data_ptr(), workspace.numel(),
+                                                    stream_handle))
 
     def shaped(t, g):
         return split_420(t, g.height, g.width) if g.chroma == 420 else t.reshape(*t.shape[:-1], 3, g.height, g.width)
@@ -353,5 +423,5 @@ def last_arm_flags() -> list[int]:
 
 
 __all__ = ["last_timing", "last_arm_flags", "decode_latents", "decode_file", "decode_batch", "decode_batch_workspace_bytes", "output_size",
-           "decode_batch_tensors", "decode_batch_geometry",
+           "decode_batch_tensors", "decode_batch_geometry", "roi_plan",
            "weights_i32", "ups_forward_i32", "syn_forward_i32", "CcmiError"]

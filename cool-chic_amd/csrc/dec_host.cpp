@@ -285,13 +285,23 @@ struct Sink {
     int sample = -1;             // -1 host bytes, else CCMI_SAMPLE_*
     void *const *dev = nullptr;  // [n] device pointers (NULL: planning only)
     ccmi_frame_geom *geom = nullptr; // [n], optional: filled by the header pass
+    const ccmi_rect *roi = nullptr;  // [n], optional (device sinks): the region of each frame to decode
+    ccmi_roi_info *info = nullptr;   // [n], optional: what the region decode does, filled by the header pass
     bool device() const { return sample >= 0; }
+};
+
+// how a stream's decoder tail runs
+enum TailMode {
+    kTailFrame = 0,  // the whole frame (no region, or one that covers the frame)
+    kTailWindow = 1, // region decode on windows (batched tail, fused synthesis)
+    kTailCrop = 2,   // whole-frame per-frame tail, the region cropped by the output kernel
 };
 
 size_t sample_bytes(int sample) { return sample == CCMI_SAMPLE_U8 ? 1 : sample == CCMI_SAMPLE_U16 ? 2 : 4; }
 
 // output of a device sink: planar 420 / 444 samples, no header; payload = bytes at the caller's pointer
-int tensor_format(const FrameHost &f, int out_bitdepth, int out_chroma, int sample, OutFmt &o, size_t *elems)
+int tensor_format(const FrameHost &f, int out_bitdepth, int out_chroma, int sample, OutFmt &o, size_t *elems,
+                  const DecWindow *rect = nullptr)
 {
     if (sample != CCMI_SAMPLE_U8 && sample != CCMI_SAMPLE_U16 && sample != CCMI_SAMPLE_F32)
         return ccmi_set_error(CCMI_ERR_ARG, "decode: unknown sample type %d", sample);
@@ -302,10 +312,11 @@ int tensor_format(const FrameHost &f, int out_bitdepth, int out_chroma, int samp
     if (sample == CCMI_SAMPLE_U8 && o.bitdepth > 8)
         return ccmi_set_error(CCMI_ERR_ARG, "decode: %d-bit samples do not fit CCMI_SAMPLE_U8", o.bitdepth);
     const int chroma = out_chroma ? out_chroma : (f.frame_data_type == 1 ? 420 : 444);
-    const size_t npx = (size_t)f.h * f.w;
+    const int oh = rect ? rect->h() : f.h, ow = rect ? rect->w() : f.w;
+    const size_t npx = (size_t)oh * ow;
     o.kind = chroma == 420 ? kYuv420 : kYuv444;
     o.header = 0;
-    *elems = o.kind == kYuv420 ? npx + 2 * (size_t)(f.h / 2) * (f.w / 2) : 3 * npx;
+    *elems = o.kind == kYuv420 ? npx + 2 * (size_t)(oh / 2) * (ow / 2) : 3 * npx;
     o.payload = sample_bytes(sample) * *elems;
     return CCMI_OK;
 }
@@ -371,6 +382,30 @@ bool syn_weights_fit24(const FrameHost &f)
     return true;
 }
 
+// the architecture part of a frame's tail arguments (no device pointers): what
+// dec_tail_batchable() looks at, and the true plane sizes
+void tail_arch(const FrameHost &f, DecTailFrame &t)
+{
+    DecUpsArgs &ua = t.ups;
+    ua = DecUpsArgs{};
+    ua.n_layers = f.n_layers;
+    for (int l = 0; l < f.n_layers; ++l) {
+        ua.lh[l] = f.lh[l];
+        ua.lw[l] = f.lw[l];
+    }
+    ua.ups_ks = f.ups_ks;
+    ua.n_ups = f.n_ups;
+    ua.pre_ks = f.pre_ks;
+    ua.n_pre = f.n_pre;
+    DecSynArgs &sa = t.syn;
+    sa = DecSynArgs{};
+    sa.c_in = f.n_layers;
+    sa.h = f.h;
+    sa.w = f.w;
+    sa.n_layers = (int)f.layers.size();
+    for (int l = 0; l < sa.n_layers; ++l) sa.layers[l] = f.layers[l];
+}
+
 // CABAC decode of every frame's network weights: host threads over the frames (each
 // stream's weights are an independent few-hundred-symbol decode, ~50-100 us)
 int decode_weights_all(std::vector<FrameHost> &fr)
@@ -405,9 +440,12 @@ int decode_many(const uint8_t *const *streams, const size_t *lens, int n, uint8_
                 int32_t *const *lat_out = nullptr, void *ws = nullptr, size_t ws_bytes = 0, size_t *need = nullptr,
                 const Sink &sink = Sink())
 {
+    g_last_flags.clear(); // a call that fails reports no stream, not the previous call's
     if (n < 1) return ccmi_set_error(CCMI_ERR_ARG, "decode: no streams");
     std::vector<FrameHost> fr(n);
     std::vector<OutFmt> of(n);
+    std::vector<DecTailFrame> tail(n);
+    std::vector<int> mode(n, kTailFrame);
     for (int i = 0; i < n; ++i) {
         if (!streams[i]) return ccmi_set_error(CCMI_ERR_ARG, "decode: stream %d is NULL", i);
         if (int rc = parse_frame_header(streams[i], lens[i], fr[i])) {
@@ -416,18 +454,55 @@ int decode_many(const uint8_t *const *streams, const size_t *lens, int n, uint8_
         }
         if (sink.device()) {
             size_t elems = 0;
-            if (int rc = tensor_format(fr[i], out_bitdepth, out_chroma, sink.sample, of[i], &elems)) return rc;
+            const FrameHost &f = fr[i];
+            DecWindow rect{0, f.h, 0, f.w};
+            if (sink.roi) {
+                const ccmi_rect &q = sink.roi[i];
+                if (q.w < 1 || q.h < 1 || q.x < 0 || q.y < 0 || q.x > f.w - q.w || q.y > f.h - q.h)
+                    return ccmi_set_error(CCMI_ERR_ARG, "stream %d: region x %d y %d w %d h %d outside the %d x %d frame", i,
+                                          q.x, q.y, q.w, q.h, f.w, f.h);
+                rect = DecWindow{q.y, q.y + q.h, q.x, q.x + q.w};
+            }
+            if (int rc = tensor_format(f, out_bitdepth, out_chroma, sink.sample, of[i], &elems, &rect)) return rc;
+            if (of[i].kind == kYuv420 && ((rect.x0 | rect.y0) & 1))
+                return ccmi_set_error(CCMI_ERR_ARG, "stream %d: a 420 region needs an even origin (x %d y %d)", i, rect.x0,
+                                      rect.y0);
+            tail_arch(f, tail[i]);
+            int halo = 0;
+            for (const SynLayerDesc &L : f.layers) halo += (L.ks - 1) / 2;
+            DecRoi &R = tail[i].roi;
+            if (rect.h() == f.h && rect.w() == f.w) {
+                mode[i] = kTailFrame;
+            } else if (f.n_branches == 1 && dec_tail_batchable(tail[i])) {
+                mode[i] = kTailWindow;
+                dec_roi_plan(f.lh, f.lw, f.n_layers, f.ups_ks, f.pre_ks, halo, rect, R);
+            } else {
+                mode[i] = kTailCrop;
+            }
+            if (mode[i] != kTailWindow) { // the whole frame is decoded
+                dec_roi_plan(f.lh, f.lw, f.n_layers, f.ups_ks, f.pre_ks, halo, DecWindow{0, f.h, 0, f.w}, R);
+                R.rect = rect;
+            }
+            tail[i].windowed = mode[i] == kTailWindow;
             if (sink.geom)
-                sink.geom[i] = ccmi_frame_geom{fr[i].w, fr[i].h, of[i].bitdepth, of[i].kind == kYuv420 ? 420 : 444,
-                                               fr[i].frame_data_type, elems};
+                sink.geom[i] = ccmi_frame_geom{rect.w(), rect.h(), of[i].bitdepth, of[i].kind == kYuv420 ? 420 : 444,
+                                               f.frame_data_type, elems};
+            if (sink.info) {
+                ccmi_roi_info &I = sink.info[i];
+                I = ccmi_roi_info{};
+                I.n_grids = f.n_layers;
+                for (int l = 0; l < f.n_layers; ++l) I.arm_rows[l] = R.arm_rows[l];
+                I.windowed = f.n_branches == 1 && dec_tail_batchable(tail[i]) ? 1 : 0;
+            }
             if (sink.dev) {
                 if (!sink.dev[i]) return ccmi_set_error(CCMI_ERR_ARG, "decode: output %d is NULL", i);
                 if (reinterpret_cast<uintptr_t>(sink.dev[i]) % sample_bytes(sink.sample))
                     return ccmi_set_error(CCMI_ERR_ARG, "decode: output %d is not aligned to its %zu-byte samples", i,
                                           sample_bytes(sink.sample));
             }
-        } else if (int rc = out_format(fr[i], out_bitdepth, out_chroma, as_yuv, of[i])) {
-            return rc;
+        } else {
+            if (int rc = out_format(fr[i], out_bitdepth, out_chroma, as_yuv, of[i])) return rc;
+            for (int l = 0; l < fr[i].n_layers; ++l) tail[i].roi.arm_rows[l] = fr[i].lh[l];
         }
         if ((outs || sink.dev) && caps && caps[i] < of[i].header + of[i].payload)
             return ccmi_set_error(CCMI_ERR_ARG, "stream %d: output buffer of %zu bytes, need %zu", i, caps[i],
@@ -456,11 +531,16 @@ int decode_many(const uint8_t *const *streams, const size_t *lens, int n, uint8_
     for (int i = 0; i < n; ++i) {
         FrameHost &f = fr[i];
         DevPlan &p = pl[i];
+        // a region decode on windows: the latent planes keep their frame pitch and hold the rows
+        // the ARM decode produces, the pyramid stacks and the synthesis output hold the windows
+        const DecRoi &R = tail[i].roi;
+        const bool win = mode[i] == kTailWindow;
         p.lat_elems = 0;
-        for (int l = 0; l < f.n_layers; ++l) p.lat_elems += (size_t)f.lh[l] * f.lw[l];
-        p.ws_elems = dec_ups_workspace_elems(f.lh, f.lw, f.n_layers);
-        p.dense_elems = (size_t)f.n_layers * f.h * f.w;
-        p.synout_elems = (size_t)f.layers.back().n_out * f.h * f.w * f.n_branches;
+        for (int l = 0; l < f.n_layers; ++l) p.lat_elems += (size_t)R.arm_rows[l] * f.lw[l];
+        p.ws_elems = win ? dec_ups_workspace_elems_win(R, f.n_layers) : dec_ups_workspace_elems(f.lh, f.lw, f.n_layers);
+        p.dense_elems = win ? (size_t)f.n_layers * R.lev[0].h() * R.lev[0].w() : (size_t)f.n_layers * f.h * f.w;
+        p.synout_elems = win ? (size_t)f.layers.back().n_out * R.rect.h() * R.rect.w()
+                             : (size_t)f.layers.back().n_out * f.h * f.w * f.n_branches;
         DecSynArgs sa{};
         sa.c_in = f.n_layers;
         sa.h = f.h;
@@ -485,7 +565,7 @@ int decode_many(const uint8_t *const *streams, const size_t *lens, int n, uint8_
     tot += align_up(sizeof(ArmStreamDesc) * (size_t)n * CCMI_MAX_GRIDS, 256);
     // batched-tail argument tables: bounded by one single-frame table per frame
     size_t tail_cap = 0;
-    for (int i = 0; i < n; ++i) tail_cap += dec_tail_table_bytes(fr[i].n_layers, 1);
+    for (int i = 0; i < n; ++i) tail_cap += dec_tail_table_bytes(fr[i].n_layers, 1, mode[i] == kTailWindow);
     const size_t tail_off = tot;
     tot += align_up(tail_cap, 256);
     // one status word per (frame, latent grid) for the ARM kernels' CCMI_ARM_FLAG_* bits
@@ -566,15 +646,17 @@ int decode_many(const uint8_t *const *streams, const size_t *lens, int n, uint8_
         int32_t *lat = reinterpret_cast<int32_t *>(dev + p.lat_off);
         for (int l = 0; l < f.n_layers; ++l) {
             int32_t *plane = lat;
-            lat += (size_t)f.lh[l] * f.lw[l];
+            const int rows = tail[i].roi.arm_rows[l]; // == lh[l] unless a region decode stops early
+            lat += (size_t)rows * f.lw[l];
             if (f.lat_n[l] == 0) { // zero layer (cc-frame-decoder.cpp:479-484)
-                CCMI_HIP_CHECK(hipMemsetAsync(plane, 0, (size_t)f.lh[l] * f.lw[l] * 4, s));
+                CCMI_HIP_CHECK(hipMemsetAsync(plane, 0, (size_t)rows * f.lw[l] * 4, s));
                 continue;
             }
             ArmStreamDesc a{};
             a.bytes = reinterpret_cast<const uint32_t *>(dev + p.bytes_off[l]);
             a.nbytes = f.lat_n[l];
             a.h = f.lh[l];
+            a.rows = rows;
             a.w = f.lw[l];
             a.sig_blk = f.sig_blk;
             a.d = f.dim_arm;
@@ -615,7 +697,7 @@ int decode_many(const uint8_t *const *streams, const size_t *lens, int n, uint8_
     for (auto &g : groups) {
         // longest streams first: they bound the launch
         std::stable_sort(g.second.begin(), g.second.end(),
-                         [](const ArmStreamDesc &x, const ArmStreamDesc &y) { return x.h * x.w > y.h * y.w; });
+                         [](const ArmStreamDesc &x, const ArmStreamDesc &y) { return x.rows * x.w > y.rows * y.w; });
         all.insert(all.end(), g.second.begin(), g.second.end());
     }
     if (!all.empty())
@@ -624,37 +706,23 @@ int decode_many(const uint8_t *const *streams, const size_t *lens, int n, uint8_
 
     // ---- decoder tail arguments; frames of one geometry with a fused synthesis (single
     // branch) share one launch per stage
-    std::vector<DecTailFrame> tail(n);
     for (int i = 0; i < n; ++i) {
         FrameHost &f = fr[i];
         DevPlan &p = pl[i];
         DecTailFrame &t = tail[i];
+        tail_arch(f, t);
         DecUpsArgs &ua = t.ups;
-        ua = DecUpsArgs{};
         ua.lat = reinterpret_cast<const int32_t *>(dev + p.lat_off);
-        ua.n_layers = f.n_layers;
         int off = 0;
         for (int l = 0; l < f.n_layers; ++l) {
-            ua.lh[l] = f.lh[l];
-            ua.lw[l] = f.lw[l];
             ua.off[l] = off;
-            off += f.lh[l] * f.lw[l];
+            off += t.roi.arm_rows[l] * f.lw[l];
         }
         ua.kernels = reinterpret_cast<const int32_t *>(dev + p.ups_off);
-        ua.ups_ks = f.ups_ks;
-        ua.n_ups = f.n_ups;
-        ua.pre_ks = f.pre_ks;
-        ua.n_pre = f.n_pre;
         ua.workspace = reinterpret_cast<int32_t *>(dev + p.ws_off);
         ua.out = reinterpret_cast<int32_t *>(dev + p.dense_off);
         DecSynArgs &sa = t.syn;
-        sa = DecSynArgs{};
         sa.in = ua.out;
-        sa.c_in = f.n_layers;
-        sa.h = f.h;
-        sa.w = f.w;
-        sa.n_layers = (int)f.layers.size();
-        for (int l = 0; l < sa.n_layers; ++l) sa.layers[l] = f.layers[l];
         sa.params = reinterpret_cast<const int32_t *>(dev + p.syn_off);
         sa.out = reinterpret_cast<int32_t *>(dev + p.synout_off);
         sa.workspace = reinterpret_cast<int32_t *>(dev + p.synws_off);
@@ -681,6 +749,7 @@ int decode_many(const uint8_t *const *streams, const size_t *lens, int n, uint8_
         batched[i] = 1;
     }
     std::vector<size_t> tg_off(tgroups.size());
+    std::vector<std::vector<const DecTailFrame *>> tg_ptr;
     std::vector<uint8_t> tab(tail_cap > 0 ? tail_cap : 1);
     size_t tpos = 0;
     for (size_t g = 0; g < tgroups.size(); ++g) {
@@ -688,7 +757,8 @@ int decode_many(const uint8_t *const *streams, const size_t *lens, int n, uint8_
         for (int i : tgroups[g]) ptr.push_back(&tail[i]);
         tg_off[g] = tpos;
         dec_tail_fill(ptr.data(), (int)ptr.size(), tab.data() + tpos);
-        tpos += dec_tail_table_bytes(tail[tgroups[g][0]].ups.n_layers, (int)ptr.size());
+        tpos += dec_tail_table_bytes(tail[tgroups[g][0]].ups.n_layers, (int)ptr.size(), tail[tgroups[g][0]].windowed);
+        tg_ptr.push_back(std::move(ptr));
     }
     if (tpos) CCMI_HIP_CHECK(hipMemcpyAsync(dev + tail_off, tab.data(), tpos, hipMemcpyHostToDevice, s));
     ev.rec(1, s);
@@ -706,7 +776,7 @@ int decode_many(const uint8_t *const *streams, const size_t *lens, int n, uint8_
         if (arm_done) CCMI_HIP_CHECK(hipEventRecord(arm_done, cs));
         for (size_t g = 0; g < tgroups.size(); ++g)
             if (chunk_of[tgroups[g][0]] == c)
-                if (int rc = launch_dec_tail_batch(tail[tgroups[g][0]], (int)tgroups[g].size(), dev + tail_off + tg_off[g], cs))
+                if (int rc = launch_dec_tail_batch(tg_ptr[g].data(), (int)tgroups[g].size(), dev + tail_off + tg_off[g], cs))
                     return rc;
         for (int i = 0; i < n; ++i) {
             if (batched[i] || chunk_of[i] != c) continue;
@@ -728,9 +798,12 @@ int decode_many(const uint8_t *const *streams, const size_t *lens, int n, uint8_
                                                   f.blend[0], f.blend[b], b == 1, cs))
                         return rc;
             }
-            if (int rc = sink.device() ? launch_dec_output_tensor(synout, f.h, f.w, of[i].bitdepth, of[i].kind,
-                                                                  sink.sample, tail[i].dst, cs)
-                                       : launch_dec_output(synout, f.h, f.w, of[i].bitdepth, of[i].kind, tail[i].dst, cs))
+            if (int rc = mode[i] == kTailCrop
+                             ? launch_dec_output_tensor_roi(synout, f.h, f.w, tail[i].roi.rect, of[i].bitdepth, of[i].kind,
+                                                            sink.sample, tail[i].dst, cs)
+                         : sink.device() ? launch_dec_output_tensor(synout, f.h, f.w, of[i].bitdepth, of[i].kind,
+                                                                    sink.sample, tail[i].dst, cs)
+                                         : launch_dec_output(synout, f.h, f.w, of[i].bitdepth, of[i].kind, tail[i].dst, cs))
                 return rc;
         }
         return CCMI_OK;
@@ -939,6 +1012,38 @@ extern "C" int ccmi_decode_batch_dev(const uint8_t *const *streams, const size_t
     Sink sink;
     sink.sample = sample_type;
     sink.dev = out_dev;
+    return decode_many(streams, lens, n, nullptr, out_caps, nullptr, out_bitdepth, out_chroma, 0,
+                       static_cast<hipStream_t>(stream), nullptr, workspace, workspace_bytes, nullptr, sink);
+}
+
+extern "C" int ccmi_decode_batch_dev_roi_plan(const uint8_t *const *streams, const size_t *lens, int n,
+                                              const ccmi_rect *roi, int out_bitdepth, int out_chroma, int sample_type,
+                                              ccmi_frame_geom *geom, ccmi_roi_info *info, size_t *workspace_bytes)
+{
+    if (!streams || !lens || !geom || !workspace_bytes)
+        return ccmi_set_error(CCMI_ERR_ARG, "decode_batch_dev_roi_plan: null argument");
+    if (sample_type < 0) return ccmi_set_error(CCMI_ERR_ARG, "decode: unknown sample type %d", sample_type);
+    Sink sink;
+    sink.sample = sample_type;
+    sink.geom = geom;
+    sink.roi = roi;
+    sink.info = info;
+    return decode_many(streams, lens, n, nullptr, nullptr, nullptr, out_bitdepth, out_chroma, 0, nullptr, nullptr,
+                       nullptr, 0, workspace_bytes, sink);
+}
+
+extern "C" int ccmi_decode_batch_dev_roi(const uint8_t *const *streams, const size_t *lens, int n, const ccmi_rect *roi,
+                                         void *const *out_dev, const size_t *out_caps, int sample_type,
+                                         int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes,
+                                         void *stream)
+{
+    if (!streams || !lens || !out_dev || !out_caps)
+        return ccmi_set_error(CCMI_ERR_ARG, "decode_batch_dev_roi: null argument");
+    if (sample_type < 0) return ccmi_set_error(CCMI_ERR_ARG, "decode: unknown sample type %d", sample_type);
+    Sink sink;
+    sink.sample = sample_type;
+    sink.dev = out_dev;
+    sink.roi = roi;
     return decode_many(streams, lens, n, nullptr, out_caps, nullptr, out_bitdepth, out_chroma, 0,
                        static_cast<hipStream_t>(stream), nullptr, workspace, workspace_bytes, nullptr, sink);
 }

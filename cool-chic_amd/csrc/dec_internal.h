@@ -66,6 +66,10 @@ struct ArmStreamDesc {
     uint64_t *dbg;          // diagnostic builds only (CCMI_ARM_STAMPS): 8 counters per stream
     uint32_t *status;       // device word, zeroed by the host: CCMI_ARM_FLAG_* bits OR-ed in by the kernel
     int spin_cap;           // chain kernel: polls per wait before it gives up and flags CCMI_ARM_FLAG_TIMEOUT
+    // rows [0, rows) are decoded and written (a region decode stops below the last row its
+    // window reads); rows == h for a whole frame.  The block maps are decoded up front and
+    // use the true h.
+    int rows;
 };
 
 // One launch for n_streams streams sharing (d, nh); max_w / max_blocks size the LDS
@@ -117,6 +121,30 @@ int launch_dec_output(const int32_t *syn, int h, int w, int bitdepth, int kind, 
 int launch_dec_output_tensor(const int32_t *syn, int h, int w, int bitdepth, int kind, int sample, void *dst,
                              hipStream_t s);
 
+// A rectangle of one pyramid level, [y0, y1) x [x0, x1) in that level's coordinates.
+struct DecWindow {
+    int y0, y1, x0, x1;
+    int h() const { return y1 - y0; }
+    int w() const { return x1 - x0; }
+};
+// What a region decode of one frame computes: rect = the region (level-0 coordinates);
+// lev[k] = the window of pyramid level k the region needs (lev[0]: the synthesis input,
+// the region grown by the 3x3 layers' reach and clipped to the frame); arm_rows[l] = the
+// rows of latent grid l those windows read.  Planned on the host (dec_roi_plan).
+struct DecRoi {
+    DecWindow rect;
+    DecWindow lev[CCMI_MAX_GRIDS];
+    int arm_rows[CCMI_MAX_GRIDS];
+};
+// syn_halo: the sum of (ks - 1) / 2 over the synthesis layers
+void dec_roi_plan(const int *lh, const int *lw, int L, int ups_ks, int pre_ks, int syn_halo, const DecWindow &rect,
+                  DecRoi &r);
+size_t dec_ups_workspace_elems_win(const DecRoi &r, int L); // the stacks of levels 1..L-2, windows only
+// Whole-frame synthesis output (12-bit, [3][H][W]) -> the planar tensor of the region `rect`
+// (the per-frame tail of a region decode crops here).
+int launch_dec_output_tensor_roi(const int32_t *syn, int h, int w, const DecWindow &rect, int bitdepth, int kind,
+                                 int sample, void *dst, hipStream_t s);
+
 // Batched decoder tail: frames with the same geometry and a fused-synthesis architecture
 // (single branch) share one launch per pyramid step, one synthesis and one output launch
 // (grid.y = frame) instead of ~8 launches per frame.  The per-frame argument tables live
@@ -128,11 +156,17 @@ struct DecTailFrame {
     int bitdepth, kind;
     uint8_t *dst;
     int sample = -1; // -1: file bytes at dst (workspace staging); CCMI_SAMPLE_*: planar tensor at dst (caller's)
+    // region decode on windows: the latent planes keep their frame pitch and hold roi.arm_rows[l]
+    // rows, ups.workspace / ups.out / syn.out hold the windows roi.lev[k] / the region, compact
+    // (pitch = the window's width); ups.lh / lw and syn.h / w stay the frame's true sizes
+    bool windowed = false;
+    DecRoi roi{};
 };
 bool dec_tail_batchable(const DecTailFrame &f);
 bool dec_tail_same_group(const DecTailFrame &a, const DecTailFrame &b);
-size_t dec_tail_table_bytes(int n_layers, int n);
+size_t dec_tail_table_bytes(int n_layers, int n, bool windowed = false);
 void dec_tail_fill(const DecTailFrame *const *fr, int n, void *host_tab);
-int launch_dec_tail_batch(const DecTailFrame &f0, int n, const void *dev_tab, hipStream_t s);
+// fr: the group's frames, in table order (a window-form group sizes its grids by their windows)
+int launch_dec_tail_batch(const DecTailFrame *const *fr, int n, const void *dev_tab, hipStream_t s);
 
 } // namespace ccmi

@@ -21,6 +21,7 @@
 //                   layout): one packed store per 4 destination samples, any sample alignment.
 #include <stdlib.h>
 
+#include <algorithm>
 #include <type_traits>
 #include <utility>
 
@@ -161,6 +162,7 @@ __global__ __launch_bounds__(64) void dec_arm_kernel(const ArmStreamDesc *__rest
     const ArmStreamDesc S = streams[blockIdx.x];
     const int lane = threadIdx.x;
     const int h = S.h, w = S.w;
+    const int rows = S.rows; // the row loops' bound (<= h: a region decode stops early); h sizes the block maps
     // weights fit in 24 signed bits (host check): hidden layers >= 2 and the output layer
     // then use 24-bit multiplies (their inputs are ReLU-rounded sums, < 2^23 by construction)
     const bool w24 = (S.flags & 1) != 0;
@@ -236,7 +238,7 @@ __global__ __launch_bounds__(64) void dec_arm_kernel(const ArmStreamDesc *__rest
     const bool same_row = cdy == 0;
     int big = 0; // uniform: a decoded |latent| >= 2^15 was seen -> contexts may exceed 24 bits
 
-    for (int y = 0; y < h; ++y) {
+    for (int y = 0; y < rows; ++y) {
         int32_t *row = ring + (y % kRing) * pitch + kPad;
         const int32_t *up = ring + ((y + kRing - 1) % kRing) * pitch + kPad;
         const int32_t *crow = ring + ((y + cdy + kRing) % kRing) * pitch + kPad + cdx;
@@ -379,6 +381,7 @@ __global__ __launch_bounds__(64) void dec_arm_spec_kernel(const ArmStreamDesc *_
     const int grp = lane >> 4, o = lane & 15;
     const bool live = o < D;
     const int h = S.h, w = S.w;
+    const int rows = S.rows; // the row loops' bound (<= h: a region decode stops early); h sizes the block maps
     const bool w24 = (S.flags & 1) != 0;
 
     // context table with every static-context index already turned into its model state
@@ -458,7 +461,7 @@ __global__ __launch_bounds__(64) void dec_arm_spec_kernel(const ArmStreamDesc *_
     const uint64_t t_loop = __builtin_amdgcn_s_memtime();
 #endif
 
-    for (int y = 0; y < h; ++y) {
+    for (int y = 0; y < rows; ++y) {
         int32_t *row = ring + (y % kRingS) * pitch + kPad;
         const int32_t *up = ring + ((y + kRingS - 1) % kRingS) * pitch + kPad;
         const int32_t *crow = ring + ((y + cdy + kRingS) % kRingS) * pitch + kPad + cdx + grp;
@@ -794,6 +797,7 @@ __global__ __launch_bounds__(128) void dec_arm_chain_kernel(const ArmStreamDesc 
     const int grp = lane >> 4, o = lane & 15;
     const bool live = o < D;
     const int h = S.h, w = S.w;
+    const int rows = S.rows; // the row loops' bound (<= h: a region decode stops early); h sizes the block maps
     const bool w24 = (S.flags & 1) != 0;
     const int nch = (w + 63) >> 6; // 64-latent chunks per row
 
@@ -881,7 +885,7 @@ __global__ __launch_bounds__(128) void dec_arm_chain_kernel(const ArmStreamDesc 
         const int dmax = blk > 0 ? 0 : 1; // no block map: every latent coded
         int seq = 0;
         uint32_t hbits = 0;
-        for (int y = 0; y < h; ++y) {
+        for (int y = 0; y < rows; ++y) {
             const int brow = blk > 0 ? (y >> shift) * nbx : 0;
             for (int c = 0; c < nch; ++c, ++seq) {
                 CSTAMP(tw0);
@@ -1016,7 +1020,7 @@ __global__ __launch_bounds__(128) void dec_arm_chain_kernel(const ArmStreamDesc 
     const uint64_t t_loop = __builtin_amdgcn_s_memtime();
 #endif
 
-    for (int y = 0; y < h; ++y) {
+    for (int y = 0; y < rows; ++y) {
         int32_t *row = ring + (y & 3) * pitch + kPad;
         const int32_t *up = ring + ((y + 3) & 3) * pitch + kPad;
         const int brow = blk > 0 ? (y >> shift) * nbx : 0;
@@ -1228,13 +1232,33 @@ struct DecLevel {
     int tiles_x;
 };
 
-__device__ __forceinline__ void ups_level_body(const DecLevel &A, int32_t *s_in, int32_t *s_tmp);
+// Window form (region decode): the step computes the window [dy0, dy1) x [dx0, dx1) of the
+// destination level and stores it compactly (pitch = the window's width).  The source stack
+// holds the window [sy0, sy1] x [sx0, sx1] of its level at pitch `spitch` from the storage
+// origin (soy, sox) (a compact stack: the window's own origin; the raw coarsest latent plane:
+// 0, 0 at the frame pitch); the reference plane keeps the frame pitch and holds ref_rows rows.
+// Border rules use the true plane sizes of DecLevel (replicate for the source, zero for the
+// refine); source reads are clamped to the stored window on top, which changes nothing the
+// window's samples depend on (the host planned the windows from these very taps) and keeps
+// the surplus lanes of an edge tile inside the allocation.
+struct DecLevelWin {
+    DecLevel L;
+    int dy0, dy1, dx0, dx1;
+    int soy, sox, spitch;
+    int sy0, sy1, sx0, sx1; // inclusive clamp bounds
+    int64_t splane;
+    int ref_rows;
+};
+
+template <bool WIN>
+__device__ __forceinline__ void ups_level_body(const DecLevel &A, const DecLevelWin *Wn, int gtx, int32_t *s_in,
+                                               int32_t *s_tmp);
 
 __global__ __launch_bounds__(kThreads) void dec_ups_level(DecLevel A)
 {
     __shared__ int32_t s_in[(kTY + kMaxKs) * (kTX + kMaxKs)];
     __shared__ int32_t s_tmp[(kTY + kMaxKs) * kTX];
-    ups_level_body(A, s_in, s_tmp);
+    ups_level_body<false>(A, nullptr, A.tiles_x, s_in, s_tmp);
 }
 
 // frames of a batch (identical geometry): blockIdx.y = frame
@@ -1243,15 +1267,41 @@ __global__ __launch_bounds__(kThreads) void dec_ups_level_batch(const DecLevel *
     __shared__ int32_t s_in[(kTY + kMaxKs) * (kTX + kMaxKs)];
     __shared__ int32_t s_tmp[(kTY + kMaxKs) * kTX];
     const DecLevel A = As[blockIdx.y];
-    ups_level_body(A, s_in, s_tmp);
+    ups_level_body<false>(A, nullptr, A.tiles_x, s_in, s_tmp);
 }
 
-__device__ __forceinline__ void ups_level_body(const DecLevel &A, int32_t *s_in, int32_t *s_tmp)
+// region decode: blockIdx.y = frame, the grid's tiles cover the group's largest window
+// (gtx tiles across); a frame's blocks past its own window leave at once
+__global__ __launch_bounds__(kThreads) void dec_ups_level_win_batch(const DecLevelWin *__restrict__ As, int gtx)
 {
-    const int y0 = (blockIdx.x / A.tiles_x) * kTY;
-    const int x0 = (blockIdx.x % A.tiles_x) * kTX;
+    __shared__ int32_t s_in[(kTY + kMaxKs) * (kTX + kMaxKs)];
+    __shared__ int32_t s_tmp[(kTY + kMaxKs) * kTX];
+    const DecLevelWin *Wn = As + blockIdx.y;
+    const DecLevel A = Wn->L;
+    ups_level_body<true>(A, Wn, gtx, s_in, s_tmp);
+}
+
+template <bool WIN>
+__device__ __forceinline__ void ups_level_body(const DecLevel &A, const DecLevelWin *Wn, int gtx, int32_t *s_in,
+                                               int32_t *s_tmp)
+{
+    // window form: tiles from the window's origin rounded down to even (the upsampling phase
+    // of a tile row / column is its parity, as with the whole frame's multiples of 16 / 64)
+    int y0 = (blockIdx.x / gtx) * kTY;
+    int x0 = (blockIdx.x % gtx) * kTX;
+    int dy0 = 0, dy1 = A.hd, dx0 = 0, dx1 = A.wd, dpitch = A.wd, ref_rows = A.hd;
+    if (WIN) {
+        dy0 = Wn->dy0, dy1 = Wn->dy1, dx0 = Wn->dx0, dx1 = Wn->dx1;
+        dpitch = dx1 - dx0;
+        ref_rows = Wn->ref_rows;
+        y0 += dy0 & ~1;
+        x0 += dx0 & ~1;
+        if (y0 >= dy1 || x0 >= dx1) return;
+    }
     const int tid = threadIdx.x;
-    const int64_t dplane = (int64_t)A.hd * A.wd;
+    const int64_t dplane = WIN ? (int64_t)(dy1 - dy0) * dpitch : (int64_t)A.hd * A.wd;
+    auto dst_ok = [&](int y, int x) { return WIN ? (y >= dy0 && y < dy1 && x >= dx0 && x < dx1) : (y < A.hd && x < A.wd); };
+    auto dst_at = [&](int y, int x) { return WIN ? (int64_t)(y - dy0) * dpitch + (x - dx0) : (int64_t)y * A.wd + x; };
 
     // refine (ups_refine_cpu.hpp): zero padding, two passes with truncation, residual
     {
@@ -1260,7 +1310,7 @@ __device__ __forceinline__ void ups_level_body(const DecLevel &A, int32_t *s_in,
         for (int i = tid; i < rh * rw; i += kThreads) {
             const int r = i / rw, c = i - r * rw;
             const int y = y0 - pad + r, x = x0 - pad + c;
-            s_in[r * pitch + c] = (y >= 0 && y < A.hd && x >= 0 && x < A.wd) ? A.ref[y * A.wd + x] : 0;
+            s_in[r * pitch + c] = (y >= 0 && y < ref_rows && x >= 0 && x < A.wd) ? A.ref[y * A.wd + x] : 0;
         }
         __syncthreads();
         for (int i = tid; i < rh * kTX; i += kThreads) {
@@ -1275,11 +1325,11 @@ __device__ __forceinline__ void ups_level_body(const DecLevel &A, int32_t *s_in,
         for (int i = tid; i < kTY * kTX; i += kThreads) {
             const int r = i / kTX, c = i - r * kTX;
             const int y = y0 + r, x = x0 + c;
-            if (y < A.hd && x < A.wd) {
+            if (dst_ok(y, x)) {
                 int32_t acc = 0;
                 for (int k = 0; k < A.ks; ++k) acc += s_tmp[(r + k) * kTX + c] * A.kpre[k];
                 acc += (int32_t)((uint32_t)s_in[(r + pad) * pitch + c + pad] << (kUpsPrec - kArmPrec) << kUpsPrec);
-                A.dst[(int64_t)y * A.wd + x] = tshift(acc, kUpsPrec);
+                A.dst[dst_at(y, x)] = tshift(acc, kUpsPrec);
             }
         }
         __syncthreads();
@@ -1291,10 +1341,15 @@ __device__ __forceinline__ void ups_level_body(const DecLevel &A, int32_t *s_in,
     const int sy0 = y0 / 2 - pad, sx0 = x0 / 2 - pad;
     const int sh = kTY / 2 + ks, sw = kTX / 2 + ks, pitch = kTX / 2 + kMaxKs;
     for (int c = 0; c < A.C; ++c) {
-        const int32_t *sp = A.src + (int64_t)c * A.hs * A.ws;
+        const int32_t *sp = A.src + (WIN ? (int64_t)c * Wn->splane : (int64_t)c * A.hs * A.ws);
         for (int i = tid; i < sh * sw; i += kThreads) {
             const int r = i / sw, cc = i - r * sw;
-            s_in[r * pitch + cc] = sp[clampi(sy0 + r, A.hs - 1) * A.ws + clampi(sx0 + cc, A.ws - 1)];
+            if (WIN) {
+                const int yy = min(max(sy0 + r, Wn->sy0), Wn->sy1), xx = min(max(sx0 + cc, Wn->sx0), Wn->sx1);
+                s_in[r * pitch + cc] = sp[(int64_t)(yy - Wn->soy) * Wn->spitch + (xx - Wn->sox)];
+            } else {
+                s_in[r * pitch + cc] = sp[clampi(sy0 + r, A.hs - 1) * A.ws + clampi(sx0 + cc, A.ws - 1)];
+            }
         }
         __syncthreads();
         for (int i = tid; i < sh * kTX; i += kThreads) {
@@ -1308,11 +1363,11 @@ __device__ __forceinline__ void ups_level_body(const DecLevel &A, int32_t *s_in,
         for (int i = tid; i < kTY * kTX; i += kThreads) {
             const int r = i / kTX, cc = i - r * kTX;
             const int Y = y0 + r, X = x0 + cc;
-            if (Y < A.hd && X < A.wd) {
+            if (dst_ok(Y, X)) {
                 const int ys = Y >> 1, ph = Y & 1;
                 int32_t acc = 0;
                 for (int k = 0; k < ks; ++k) acc += s_tmp[(ys - pad + ph + k - sy0) * kTX + cc] * A.kup[2 * k + ph];
-                A.dst[(int64_t)(c + 1) * dplane + (int64_t)Y * A.wd + X] = tshift(acc, kUpsPrec);
+                A.dst[(int64_t)(c + 1) * dplane + dst_at(Y, X)] = tshift(acc, kUpsPrec);
             }
         }
         __syncthreads();
@@ -1336,15 +1391,29 @@ struct DecSynFused {
     int f24; // DecSynArgs::f24
 };
 
-template <int CIN, int CMID, bool F24>
-__device__ __forceinline__ void syn_fused_body(const DecSynFused &A, int32_t (*s_buf)[CMID][kRegion]);
+// Window form (region decode): the input holds the window [iy0, iy1] x [ix0, ix1] of the
+// frame's level-0 stack, compact at pitch `ipitch` (the region grown by the 3x3 layers' reach,
+// clipped to the frame); the output is the region [ry, ry + rh) x [rx, rx + rw), compact
+// [3][rh][rw].  Every replicate clamp still uses the frame's true H and W (DecSynFused): a
+// window edge that is not a frame edge is never padded.  Input reads are clamped to the stored
+// window on top (only the surplus lanes of a tile ever fall outside it).
+struct DecSynFusedWin {
+    DecSynFused F;
+    int iy0, iy1, ix0, ix1, ipitch;
+    int64_t iplane;
+    int ry, rx, rh, rw;
+};
+
+template <int CIN, int CMID, bool F24, bool WIN>
+__device__ __forceinline__ void syn_fused_body(const DecSynFused &A, const DecSynFusedWin *Wn, int gtx,
+                                               int32_t (*s_buf)[CMID][kRegion]);
 
 template <int CIN, int CMID>
 __global__ __launch_bounds__(kThreads) void dec_syn_fused(DecSynFused A)
 {
     __shared__ __attribute__((aligned(16))) int32_t s_buf[2][CMID][kRegion];
-    if (A.f24) syn_fused_body<CIN, CMID, true>(A, s_buf);
-    else syn_fused_body<CIN, CMID, false>(A, s_buf);
+    if (A.f24) syn_fused_body<CIN, CMID, true, false>(A, nullptr, A.tiles_x, s_buf);
+    else syn_fused_body<CIN, CMID, false, false>(A, nullptr, A.tiles_x, s_buf);
 }
 
 template <int CIN, int CMID>
@@ -1354,20 +1423,43 @@ __global__ __launch_bounds__(kThreads) void dec_syn_fused_batch(const DecSynFuse
     // by reference: the frame's argument record is read with scalar loads where it is used (a
     // by-value copy with runtime-indexed layer arrays lived in scratch, 160 bytes per lane)
     const DecSynFused &A = As[blockIdx.y];
-    if (A.f24) syn_fused_body<CIN, CMID, true>(A, s_buf);
-    else syn_fused_body<CIN, CMID, false>(A, s_buf);
+    if (A.f24) syn_fused_body<CIN, CMID, true, false>(A, nullptr, A.tiles_x, s_buf);
+    else syn_fused_body<CIN, CMID, false, false>(A, nullptr, A.tiles_x, s_buf);
 }
 
-template <int CIN, int CMID, bool F24>
-__device__ __forceinline__ void syn_fused_body(const DecSynFused &A, int32_t (*s_buf)[CMID][kRegion])
+// region decode: blockIdx.y = frame, gtx tiles across (the group shares one region size)
+template <int CIN, int CMID>
+__global__ __launch_bounds__(kThreads) void dec_syn_fused_win_batch(const DecSynFusedWin *__restrict__ As, int gtx)
+{
+    __shared__ __attribute__((aligned(16))) int32_t s_buf[2][CMID][kRegion];
+    const DecSynFusedWin *Wn = As + blockIdx.y;
+    const DecSynFused &A = Wn->F;
+    if (A.f24) syn_fused_body<CIN, CMID, true, true>(A, Wn, gtx, s_buf);
+    else syn_fused_body<CIN, CMID, false, true>(A, Wn, gtx, s_buf);
+}
+
+template <int CIN, int CMID, bool F24, bool WIN>
+__device__ __forceinline__ void syn_fused_body(const DecSynFused &A, const DecSynFusedWin *Wn, int gtx,
+                                               int32_t (*s_buf)[CMID][kRegion])
 {
     const int halo = A.n_sp;
     const int TX = kRW - 2 * halo, TY = kRH - 2 * halo;
-    const int y0 = (blockIdx.x / A.tiles_x) * TY, x0 = (blockIdx.x % A.tiles_x) * TX;
+    // frame coordinates throughout; the window form's tiles start at the region's origin
+    const int y0 = (blockIdx.x / gtx) * TY + (WIN ? Wn->ry : 0), x0 = (blockIdx.x % gtx) * TX + (WIN ? Wn->rx : 0);
+    // the exclusive end of what is written, and where sample (gy, gx) of output plane 0 goes
+    const int ye = WIN ? Wn->ry + Wn->rh : A.H, xe = WIN ? Wn->rx + Wn->rw : A.W;
+    if (WIN && (y0 >= ye || x0 >= xe)) return;
     const int oy = y0 - halo, ox = x0 - halo;
-    const int64_t plane = (int64_t)A.H * A.W;
+    const int64_t plane = WIN ? (int64_t)Wn->rh * Wn->rw : (int64_t)A.H * A.W;   // of the output
+    const int64_t iplane = WIN ? Wn->iplane : (int64_t)A.H * A.W;                // of the input
     const int c = threadIdx.x & (kRW - 1), r0 = threadIdx.x >> 6;
     const int gx = ox + c, cxg = clampi(gx, A.W - 1);
+    auto out_at = [&](int gy) { return WIN ? (int64_t)(gy - Wn->ry) * Wn->rw + (gx - Wn->rx) : (int64_t)gy * A.W + gx; };
+    auto in_pix = [&](int yy) { // input sample at row yy (any), this lane's column
+        if (WIN)
+            return (int64_t)(min(max(yy, Wn->iy0), Wn->iy1) - Wn->iy0) * Wn->ipitch + (min(max(gx, Wn->ix0), Wn->ix1) - Wn->ix0);
+        return (int64_t)clampi(yy, A.H - 1) * A.W + cxg;
+    };
 
     // the head's weight records (w0[j][0..CIN), b0[j], w1[0..CMID)[j]; 12 ints) in the second
     // ping-pong buffer, which the first 3x3 layer writes only after its barrier: read back as
@@ -1394,7 +1486,7 @@ __device__ __forceinline__ void syn_fused_body(const DecSynFused &A, int32_t (*s
         for (int m = 0; m < CMID; ++m) {
             const int32_t v = tshift(o[m], kSynPrec);
             if (halo == 0) {
-                if (gy < A.H && gx < A.W) A.out[m * plane + (int64_t)gy * A.W + gx] = v;
+                if (gy < ye && gx < xe) A.out[m * plane + out_at(gy)] = v;
             } else {
                 s_buf[0][m][r * kRW + c] = v;
             }
@@ -1409,9 +1501,9 @@ __device__ __forceinline__ void syn_fused_body(const DecSynFused &A, int32_t (*s
             int32_t x[2][CIN], o[2][CMID];
 #pragma unroll
             for (int p = 0; p < 2; ++p) {
-                const int64_t pix = (int64_t)clampi(oy + r + 4 * p, A.H - 1) * A.W + cxg;
+                const int64_t pix = in_pix(oy + r + 4 * p);
 #pragma unroll
-                for (int k = 0; k < CIN; ++k) x[p][k] = A.in[k * plane + pix];
+                for (int k = 0; k < CIN; ++k) x[p][k] = A.in[k * iplane + pix];
 #pragma unroll
                 for (int m = 0; m < CMID; ++m) o[p][m] = A.b1[m];
             }
@@ -1434,10 +1526,10 @@ __device__ __forceinline__ void syn_fused_body(const DecSynFused &A, int32_t (*s
         }
     } else {
         for (int r = r0; r < kRH; r += 4) {
-            const int64_t pix = (int64_t)clampi(oy + r, A.H - 1) * A.W + cxg;
+            const int64_t pix = in_pix(oy + r);
             int32_t x[CIN];
 #pragma unroll
-            for (int k = 0; k < CIN; ++k) x[k] = A.in[k * plane + pix];
+            for (int k = 0; k < CIN; ++k) x[k] = A.in[k * iplane + pix];
             int32_t o[CMID];
 #pragma unroll
             for (int m = 0; m < CMID; ++m) o[m] = A.b1[m];
@@ -1466,7 +1558,7 @@ __device__ __forceinline__ void syn_fused_body(const DecSynFused &A, int32_t (*s
         for (int d = 0; d < 3; ++d) lx[d] = clampi(cxg + d - 1, A.W - 1) - ox;
         for (int r = r0 + t; r < kRH - t; r += 4) {
             const int gy = oy + r;
-            if (!col_ok || (last && (gy >= A.H || gx >= A.W))) continue;
+            if (!col_ok || (last && (gy >= ye || gx >= xe))) continue;
             const int cyg = clampi(gy, A.H - 1);
             int ly[3];
 #pragma unroll
@@ -1490,7 +1582,7 @@ __device__ __forceinline__ void syn_fused_body(const DecSynFused &A, int32_t (*s
                         for (int dx = 0; dx < 3; ++dx) acc += imul<F24>(nb[k][dy][dx], wt[((m * CMID + k) * 3 + dy) * 3 + dx]);
                 const int32_t v = acc < 0 ? (A.relu[s] ? 0 : -((-acc) >> kSynPrec)) : acc >> kSynPrec;
                 if (last)
-                    A.out[m * plane + (int64_t)gy * A.W + gx] = v;
+                    A.out[m * plane + out_at(gy)] = v;
                 else
                     s_buf[cur ^ 1][m][r * kRW + c] = v;
             }
@@ -1632,11 +1724,21 @@ template <> __device__ __forceinline__ uint16_t out_sample<uint16_t>(int32_t s, 
 // one correctly rounded division: what torch's u.to(float32) / maxv computes
 template <> __device__ __forceinline__ float out_sample<float>(int32_t s, float fmax) { return __fdiv_rn((float)s, fmax); }
 
-template <typename T>
+// CROP (the per-frame tail of a region decode): H x W is the region, whose sample (y, x) of
+// plane c is syn[c * splane + (oy + y) * spitch + ox + x] of the whole-frame synthesis output
+// (oy, ox even for 420, so the chroma's even rows and columns are the frame's).
+template <typename T, bool CROP>
 __device__ __forceinline__ void output_tensor_body(const int32_t *__restrict__ syn, int H, int W, int maxv, int kind,
-                                                   T *__restrict__ dst)
+                                                   T *__restrict__ dst, int64_t splane = 0, int spitch = 0, int oy = 0,
+                                                   int ox = 0)
 {
     const int64_t plane = (int64_t)H * W;
+    auto direct_at = [&](int64_t j) { // flat sample j of the [.][H][W] prefix
+        if (!CROP) return j;
+        const int64_t c = j / plane, rem = j - c * plane;
+        const int y = (int)(rem / W), x = (int)(rem - (int64_t)y * W);
+        return c * splane + (int64_t)(oy + y) * spitch + ox + x;
+    };
     const int ch = H / 2, cw = W / 2;
     const int64_t cp = (int64_t)ch * cw;
     const int64_t elems = kind == 1 ? 3 * plane : plane + 2 * cp;
@@ -1652,7 +1754,7 @@ __device__ __forceinline__ void output_tensor_body(const int32_t *__restrict__ s
     T v[4];
     if (j0 >= 0 && j0 + 4 <= direct) { // the common case: 4 samples of the flat prefix
 #pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = out_sample<T>(smp(syn[j0 + k]), fmax);
+        for (int k = 0; k < 4; ++k) v[k] = out_sample<T>(smp(syn[direct_at(j0 + k)]), fmax);
     } else {
         // a group that is partial, crosses into the chroma planes or lies in them: one
         // division for its first chroma sample, the others step along the row
@@ -1671,10 +1773,12 @@ __device__ __forceinline__ void output_tensor_body(const int32_t *__restrict__ s
             v[k] = T(0);
             if (j < 0 || j >= elems) continue;
             if (j < direct) {
-                v[k] = out_sample<T>(smp(syn[j]), fmax);
+                v[k] = out_sample<T>(smp(syn[direct_at(j)]), fmax);
                 continue;
             }
-            v[k] = out_sample<T>(smp(syn[(1 + c) * plane + (int64_t)(2 * cy) * W + 2 * cx]), fmax);
+            v[k] = out_sample<T>(smp(syn[CROP ? (1 + c) * splane + (int64_t)(oy + 2 * cy) * spitch + ox + 2 * cx
+                                              : (1 + c) * plane + (int64_t)(2 * cy) * W + 2 * cx]),
+                                 fmax);
             if (++cx == cw) {
                 cx = 0;
                 if (++cy == ch) {
@@ -1699,13 +1803,22 @@ template <typename T>
 __global__ __launch_bounds__(kThreads) void dec_output_tensor(const int32_t *__restrict__ syn, int H, int W, int maxv,
                                                               int kind, T *__restrict__ dst)
 {
-    output_tensor_body<T>(syn, H, W, maxv, kind, dst);
+    output_tensor_body<T, false>(syn, H, W, maxv, kind, dst);
+}
+
+// h x w = the region at (oy, ox) of the H x W frame
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_output_tensor_crop(const int32_t *__restrict__ syn, int H, int W, int oy,
+                                                                   int ox, int h, int w, int maxv, int kind,
+                                                                   T *__restrict__ dst)
+{
+    output_tensor_body<T, true>(syn, h, w, maxv, kind, dst, (int64_t)H * W, W, oy, ox);
 }
 
 template <typename T> __global__ __launch_bounds__(kThreads) void dec_output_tensor_batch(const DecOut *__restrict__ Os)
 {
     const DecOut O = Os[blockIdx.y];
-    output_tensor_body<T>(O.syn, O.H, O.W, O.maxv, O.kind, reinterpret_cast<T *>(O.dst));
+    output_tensor_body<T, false>(O.syn, O.H, O.W, O.maxv, O.kind, reinterpret_cast<T *>(O.dst));
 }
 
 // blocks that cover the samples of one frame plus the up to 3 lead-in slots of an unaligned dst
@@ -1820,6 +1933,69 @@ static int make_levels(const DecUpsArgs &a, DecLevel *lv)
         A.tiles_x = ccmi_div_up(A.wd, kTX);
     }
     return L > 1 ? L - 1 : 0;
+}
+
+// The windows a region needs, finest level first, from the taps of ups_level_body and
+// syn_fused_body.  A destination row Y of a pyramid step reads source rows
+// (Y >> 1) - pad + (Y & 1) .. + ks - 1 (ks = ups_ks / 2 taps per phase, pad = ks / 2), clamped
+// to the plane; the refined channel of a level reads its latent grid pre_ks / 2 rows either
+// side, zero outside the plane.  Columns alike.
+void dec_roi_plan(const int *lh, const int *lw, int L, int ups_ks, int pre_ks, int syn_halo, const DecWindow &rect,
+                  DecRoi &r)
+{
+    r = DecRoi{};
+    r.rect = rect;
+    r.lev[0] = DecWindow{std::max(0, rect.y0 - syn_halo), std::min(lh[0], rect.y1 + syn_halo),
+                         std::max(0, rect.x0 - syn_halo), std::min(lw[0], rect.x1 + syn_halo)};
+    const int ks = ups_ks / 2, pad = ks / 2;
+    auto lo = [&](int a) { return std::max(0, (a >> 1) - pad + (a & 1)); };
+    auto hi = [&](int b, int n) { return std::min(n, ((b - 1) >> 1) + ((b - 1) & 1) - pad + ks); };
+    for (int k = 1; k < L; ++k) {
+        const DecWindow &d = r.lev[k - 1];
+        r.lev[k] = DecWindow{lo(d.y0), hi(d.y1, lh[k]), lo(d.x0), hi(d.x1, lw[k])};
+    }
+    for (int l = 0; l < L; ++l) r.arm_rows[l] = l == L - 1 ? r.lev[l].y1 : std::min(lh[l], r.lev[l].y1 + pre_ks / 2);
+}
+
+size_t dec_ups_workspace_elems_win(const DecRoi &r, int L)
+{
+    size_t n = 0;
+    for (int k = 1; k <= L - 2; ++k) n += (size_t)(L - k) * r.lev[k].h() * r.lev[k].w();
+    return n;
+}
+
+// window-form arguments of every pyramid step of one frame (coarsest first)
+static int make_levels_win(const DecTailFrame &f, DecLevelWin *lv)
+{
+    const DecUpsArgs &a = f.ups;
+    const DecRoi &R = f.roi;
+    const int L = a.n_layers;
+    DecLevel base[CCMI_MAX_GRIDS];
+    const int steps = make_levels(a, base);
+    int32_t *stack[CCMI_MAX_GRIDS] = {};
+    int32_t *ws = a.workspace;
+    for (int k = 1; k <= L - 2; ++k) {
+        stack[k] = ws;
+        ws += (size_t)(L - k) * R.lev[k].h() * R.lev[k].w();
+    }
+    for (int step = 0; step < steps; ++step) {
+        const int k = L - 1 - step;
+        DecLevelWin &Wn = lv[step];
+        Wn = DecLevelWin{};
+        Wn.L = base[step];
+        const DecWindow &sw = R.lev[k], &dw = R.lev[k - 1];
+        const bool raw = k == L - 1; // the coarsest latent plane itself: frame pitch, origin 0
+        Wn.L.src = raw ? a.lat + a.off[k] : stack[k];
+        Wn.L.dst = k - 1 == 0 ? a.out : stack[k - 1];
+        Wn.dy0 = dw.y0, Wn.dy1 = dw.y1, Wn.dx0 = dw.x0, Wn.dx1 = dw.x1;
+        Wn.soy = raw ? 0 : sw.y0;
+        Wn.sox = raw ? 0 : sw.x0;
+        Wn.spitch = raw ? a.lw[k] : sw.w();
+        Wn.splane = (int64_t)sw.h() * sw.w();
+        Wn.sy0 = sw.y0, Wn.sy1 = sw.y1 - 1, Wn.sx0 = sw.x0, Wn.sx1 = sw.x1 - 1;
+        Wn.ref_rows = R.arm_rows[k - 1];
+    }
+    return steps;
 }
 
 int launch_dec_ups(const DecUpsArgs &a, hipStream_t s)
@@ -1986,6 +2162,33 @@ int launch_dec_output_tensor(const int32_t *syn, int h, int w, int bitdepth, int
     return CCMI_OK;
 }
 
+int launch_dec_output_tensor_roi(const int32_t *syn, int h, int w, const DecWindow &rect, int bitdepth, int kind,
+                                 int sample, void *dst, hipStream_t s)
+{
+    if (kind != 0 && kind != 1) return ccmi_set_error(CCMI_ERR_ARG, "dec: tensor output kind %d", kind);
+    if (rect.y0 < 0 || rect.x0 < 0 || rect.y1 > h || rect.x1 > w || rect.h() < 1 || rect.w() < 1)
+        return ccmi_set_error(CCMI_ERR_ARG, "dec: region outside the frame");
+    const dim3 grid(output_tensor_blocks(rect.h(), rect.w(), kind));
+    const int maxv = (1 << bitdepth) - 1;
+    switch (sample) {
+    case CCMI_SAMPLE_U8:
+        hipLaunchKernelGGL(dec_output_tensor_crop<uint8_t>, grid, dim3(kThreads), 0, s, syn, h, w, rect.y0, rect.x0,
+                           rect.h(), rect.w(), maxv, kind, static_cast<uint8_t *>(dst));
+        break;
+    case CCMI_SAMPLE_U16:
+        hipLaunchKernelGGL(dec_output_tensor_crop<uint16_t>, grid, dim3(kThreads), 0, s, syn, h, w, rect.y0, rect.x0,
+                           rect.h(), rect.w(), maxv, kind, static_cast<uint16_t *>(dst));
+        break;
+    case CCMI_SAMPLE_F32:
+        hipLaunchKernelGGL(dec_output_tensor_crop<float>, grid, dim3(kThreads), 0, s, syn, h, w, rect.y0, rect.x0,
+                           rect.h(), rect.w(), maxv, kind, static_cast<float *>(dst));
+        break;
+    default: return ccmi_set_error(CCMI_ERR_ARG, "dec: sample type %d", sample);
+    }
+    CCMI_HIP_CHECK(hipGetLastError());
+    return CCMI_OK;
+}
+
 // ------------------------------------------------------------------ batched decoder tail
 // fused-synthesis kernel arguments of one frame (syn_fast architectures only); the same
 // weight walk as launch_dec_syn
@@ -2034,7 +2237,15 @@ bool dec_tail_batchable(const DecTailFrame &f)
 // synthesis input width (template); everything else is per-frame table data
 bool dec_tail_same_group(const DecTailFrame &a, const DecTailFrame &b)
 {
-    if (a.ups.n_layers != b.ups.n_layers) return false;
+    if (a.ups.n_layers != b.ups.n_layers || a.windowed != b.windowed) return false;
+    if (a.windowed) {
+        // region decode: the tables carry each frame's true plane sizes and its windows, the
+        // grids cover the group's largest window; one region size (the output grid), any
+        // frame size, any origin
+        if (a.sample != b.sample || a.kind != b.kind) return false;
+        return a.syn.n_layers == b.syn.n_layers && a.syn.c_in == b.syn.c_in && a.roi.rect.h() == b.roi.rect.h() &&
+               a.roi.rect.w() == b.roi.rect.w();
+    }
     for (int l = 0; l < a.ups.n_layers; ++l)
         if (a.ups.lh[l] != b.ups.lh[l] || a.ups.lw[l] != b.ups.lw[l]) return false;
     // tensor outputs: the output grid is sized by the sample count, i.e. by the chroma format too
@@ -2045,14 +2256,46 @@ bool dec_tail_same_group(const DecTailFrame &a, const DecTailFrame &b)
 static size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 // table of a group of n frames: [step][frame] DecLevel, [frame] DecSynFused, [frame] DecOut
-size_t dec_tail_table_bytes(int n_layers, int n)
+size_t dec_tail_table_bytes(int n_layers, int n, bool windowed)
 {
     const size_t steps = n_layers > 1 ? (size_t)(n_layers - 1) : 0;
+    if (windowed)
+        return al16(sizeof(DecLevelWin) * steps * n) + al16(sizeof(DecSynFusedWin) * (size_t)n) +
+               al16(sizeof(DecOut) * (size_t)n);
     return al16(sizeof(DecLevel) * steps * n) + al16(sizeof(DecSynFused) * (size_t)n) + al16(sizeof(DecOut) * (size_t)n);
+}
+
+// the window-form tables: [step][frame] DecLevelWin, [frame] DecSynFusedWin, [frame] DecOut
+static void dec_tail_fill_win(const DecTailFrame *const *fr, int n, void *host_tab)
+{
+    const int steps = fr[0]->ups.n_layers - 1;
+    uint8_t *p = static_cast<uint8_t *>(host_tab);
+    DecLevelWin *lv = reinterpret_cast<DecLevelWin *>(p);
+    DecSynFusedWin *sf = reinterpret_cast<DecSynFusedWin *>(p + al16(sizeof(DecLevelWin) * (size_t)steps * n));
+    DecOut *oo = reinterpret_cast<DecOut *>(reinterpret_cast<uint8_t *>(sf) + al16(sizeof(DecSynFusedWin) * (size_t)n));
+    for (int i = 0; i < n; ++i) {
+        DecLevelWin tmp[CCMI_MAX_GRIDS];
+        make_levels_win(*fr[i], tmp);
+        for (int st = 0; st < steps; ++st) lv[(size_t)st * n + i] = tmp[st];
+        const DecRoi &R = fr[i]->roi;
+        DecSynFusedWin &S = sf[i];
+        S = DecSynFusedWin{};
+        S.F = make_syn_fused(fr[i]->syn);
+        S.iy0 = R.lev[0].y0, S.iy1 = R.lev[0].y1 - 1, S.ix0 = R.lev[0].x0, S.ix1 = R.lev[0].x1 - 1;
+        S.ipitch = R.lev[0].w();
+        S.iplane = (int64_t)R.lev[0].h() * R.lev[0].w();
+        S.ry = R.rect.y0, S.rx = R.rect.x0, S.rh = R.rect.h(), S.rw = R.rect.w();
+        // the synthesis output is the region itself, compact: the whole-frame output kernel
+        // converts it as a frame of the region's size (420: the origin is even, so its even
+        // rows and columns are the frame's)
+        const int bd = fr[i]->bitdepth;
+        oo[i] = DecOut{fr[i]->syn.out, S.rh, S.rw, (1 << bd) - 1, fr[i]->kind, bd <= 8 ? 1 : 2, fr[i]->dst};
+    }
 }
 
 void dec_tail_fill(const DecTailFrame *const *fr, int n, void *host_tab)
 {
+    if (fr[0]->windowed) return dec_tail_fill_win(fr, n, host_tab);
     const int steps = fr[0]->ups.n_layers - 1;
     uint8_t *p = static_cast<uint8_t *>(host_tab);
     DecLevel *lv = reinterpret_cast<DecLevel *>(p);
@@ -2069,9 +2312,60 @@ void dec_tail_fill(const DecTailFrame *const *fr, int n, void *host_tab)
     }
 }
 
-int launch_dec_tail_batch(const DecTailFrame &f0, int n, const void *dev_tab, hipStream_t s)
+// region decode: one launch per stage for a window-form group (dec_tail_same_group); the
+// grids cover the group's largest window of each level
+static int launch_dec_tail_batch_win(const DecTailFrame *const *fr, int n, const void *dev_tab, hipStream_t s)
+{
+    const DecTailFrame &f0 = *fr[0];
+    const int L = f0.ups.n_layers, steps = L - 1;
+    if (f0.sample < 0) return ccmi_set_error(CCMI_ERR_ARG, "dec: a region decode writes tensors only");
+    const uint8_t *p = static_cast<const uint8_t *>(dev_tab);
+    const DecLevelWin *lv = reinterpret_cast<const DecLevelWin *>(p);
+    const DecSynFusedWin *sf = reinterpret_cast<const DecSynFusedWin *>(p + al16(sizeof(DecLevelWin) * (size_t)steps * n));
+    const DecOut *oo =
+        reinterpret_cast<const DecOut *>(reinterpret_cast<const uint8_t *>(sf) + al16(sizeof(DecSynFusedWin) * (size_t)n));
+    for (int st = 0; st < steps; ++st) {
+        const int k = L - 1 - st;
+        int gtx = 1, gty = 1; // tiles from each window's origin rounded down to even
+        for (int i = 0; i < n; ++i) {
+            const DecWindow &d = fr[i]->roi.lev[k - 1];
+            gtx = std::max(gtx, ccmi_div_up(d.x1 - (d.x0 & ~1), kTX));
+            gty = std::max(gty, ccmi_div_up(d.y1 - (d.y0 & ~1), kTY));
+        }
+        hipLaunchKernelGGL(dec_ups_level_win_batch, dim3(gtx * gty, n), dim3(kThreads), 0, s, lv + (size_t)st * n, gtx);
+        CCMI_HIP_CHECK(hipGetLastError());
+    }
+    const int halo = f0.syn.n_layers - 2;
+    const int rh = f0.roi.rect.h(), rw = f0.roi.rect.w();
+    const int gtx = ccmi_div_up(rw, kRW - 2 * halo);
+    const dim3 sg(gtx * ccmi_div_up(rh, kRH - 2 * halo), n);
+    switch (f0.syn.c_in) {
+    case 1: hipLaunchKernelGGL((dec_syn_fused_win_batch<1, 3>), sg, dim3(kThreads), 0, s, sf, gtx); break;
+    case 2: hipLaunchKernelGGL((dec_syn_fused_win_batch<2, 3>), sg, dim3(kThreads), 0, s, sf, gtx); break;
+    case 3: hipLaunchKernelGGL((dec_syn_fused_win_batch<3, 3>), sg, dim3(kThreads), 0, s, sf, gtx); break;
+    case 4: hipLaunchKernelGGL((dec_syn_fused_win_batch<4, 3>), sg, dim3(kThreads), 0, s, sf, gtx); break;
+    case 5: hipLaunchKernelGGL((dec_syn_fused_win_batch<5, 3>), sg, dim3(kThreads), 0, s, sf, gtx); break;
+    case 6: hipLaunchKernelGGL((dec_syn_fused_win_batch<6, 3>), sg, dim3(kThreads), 0, s, sf, gtx); break;
+    case 7: hipLaunchKernelGGL((dec_syn_fused_win_batch<7, 3>), sg, dim3(kThreads), 0, s, sf, gtx); break;
+    default: hipLaunchKernelGGL((dec_syn_fused_win_batch<8, 3>), sg, dim3(kThreads), 0, s, sf, gtx); break;
+    }
+    CCMI_HIP_CHECK(hipGetLastError());
+    const dim3 grid(output_tensor_blocks(rh, rw, f0.kind), n);
+    switch (f0.sample) {
+    case CCMI_SAMPLE_U8: hipLaunchKernelGGL(dec_output_tensor_batch<uint8_t>, grid, dim3(kThreads), 0, s, oo); break;
+    case CCMI_SAMPLE_U16: hipLaunchKernelGGL(dec_output_tensor_batch<uint16_t>, grid, dim3(kThreads), 0, s, oo); break;
+    case CCMI_SAMPLE_F32: hipLaunchKernelGGL(dec_output_tensor_batch<float>, grid, dim3(kThreads), 0, s, oo); break;
+    default: return ccmi_set_error(CCMI_ERR_ARG, "dec: sample type %d", f0.sample);
+    }
+    CCMI_HIP_CHECK(hipGetLastError());
+    return CCMI_OK;
+}
+
+int launch_dec_tail_batch(const DecTailFrame *const *fr, int n, const void *dev_tab, hipStream_t s)
 {
     if (n < 1 || n > 65535) return ccmi_set_error(CCMI_ERR_ARG, "dec: tail batch of %d frames", n);
+    if (fr[0]->windowed) return launch_dec_tail_batch_win(fr, n, dev_tab, s);
+    const DecTailFrame &f0 = *fr[0];
     const int L = f0.ups.n_layers, steps = L - 1;
     const uint8_t *p = static_cast<const uint8_t *>(dev_tab);
     const DecLevel *lv = reinterpret_cast<const DecLevel *>(p);

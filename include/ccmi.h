@@ -221,7 +221,9 @@ int ccmi_decode_last_timing(float *ms4);
  * output); the other bits say which integer multiply forms ran, i.e. which paths a stream
  * exercised (the reference's int32 ARM, arm_cpu.cpp:65-95, has one form).  The chain kernel's
  * wait limit is 2^24 polls, or the environment's CCMI_DEC_SPIN_CAP (a test hook: 0 makes
- * every wait give up at once). */
+ * every wait give up at once).  Every decode call clears the record when it starts, so a
+ * call that fails before its status words are read back reports no stream (*n = 0), not the
+ * streams of the call before it. */
 #define CCMI_ARM_FLAG_TIMEOUT 1u  /* a two-wave synchronisation wait gave up: decode invalid */
 #define CCMI_ARM_FLAG_Q32 2u      /* chain kernel: a |q| > 16383 switched layer 0 to 32-bit products */
 #define CCMI_ARM_FLAG_W32 4u      /* an ARM weight >= 2^23: every layer in 32-bit products */
@@ -290,6 +292,44 @@ int ccmi_decode_batch_dev(const uint8_t *const *streams, const size_t *lens, int
                           void *const *out_dev, const size_t *out_caps, int sample_type,
                           int out_bitdepth, int out_chroma, void *workspace,
                           size_t workspace_bytes, void *stream);
+
+/* A region of interest of the same decode: roi[i] (luma samples, x / y = top-left corner) is
+ * the window of stream i's frame that is decoded into out_dev[i]; roi NULL, or a rect of
+ * 0, 0, W, H, is the whole frame, with the samples and the workspace size of
+ * ccmi_decode_batch_dev / _plan.  geom[i].width / height are the rect's w / h and elems is
+ * 3 w h (444) or w h + 2 (h/2)(w/2) (420).  The samples are, one for one, the crop of the
+ * whole-frame decode:
+ *   444 output: [3][h][w] = full[:, y:y+h, x:x+w];
+ *   420 output: x and y must be even (else CCMI_ERR_ARG); Y = fullY[y:y+h, x:x+w], U and V =
+ *               full[y/2 : y/2 + h/2, x/2 : x/2 + w/2] (an odd w or h drops the chroma of the
+ *               last column or row, as an odd frame does).
+ * w < 1, h < 1, x < 0, y < 0, x + w > W or y + h > H is CCMI_ERR_ARG (the message names the
+ * stream) and nothing is written.  out_caps, the sample types, the one-sample alignment rule,
+ * the stream synchronisation, ccmi_decode_last_timing() and ccmi_decode_last_arm_flags() are
+ * those of ccmi_decode_batch_dev.
+ * Streams with a fused synthesis (single branch; every reference architecture) decode the
+ * window only (windowed = 1): the pyramid and the synthesis run on the windows the region
+ * needs at each level, the workspace is sized by them, and the ARM + CABAC decode of latent
+ * grid l stops after arm_rows[l] rows (the raster-order chain cannot skip rows above the
+ * window or columns beside it).  The ARM flags then describe the rows that were decoded: a
+ * wide-form latent below row arm_rows[l] is never seen.  Other streams run the whole-frame
+ * tail and crop in the output kernel (windowed = 0, arm_rows[l] = h_l, whole-frame workspace).
+ * Streams of one architecture, one frame size and one region size share their launches
+ * whatever their origins. */
+typedef struct ccmi_rect { int x, y, w, h; } ccmi_rect;
+typedef struct ccmi_roi_info {
+    int n_grids;
+    int arm_rows[CCMI_MAX_GRIDS_PUBLIC]; /* latent rows of grid l the ARM + CABAC decode produces */
+    int windowed;                        /* 1: the tail runs on windows; 0: whole-frame tail, cropped at the output stage */
+} ccmi_roi_info;
+int ccmi_decode_batch_dev_roi_plan(const uint8_t *const *streams, const size_t *lens, int n,
+                                   const ccmi_rect *roi /* [n] or NULL */, int out_bitdepth,
+                                   int out_chroma, int sample_type, ccmi_frame_geom *geom /* [n] */,
+                                   ccmi_roi_info *info /* [n] or NULL */, size_t *workspace_bytes);
+int ccmi_decode_batch_dev_roi(const uint8_t *const *streams, const size_t *lens, int n,
+                              const ccmi_rect *roi /* [n] or NULL */, void *const *out_dev,
+                              const size_t *out_caps, int sample_type, int out_bitdepth,
+                              int out_chroma, void *workspace, size_t workspace_bytes, void *stream);
 
 /* Network weights of a stream's intra frame as the decoder's fixed-point integers
  * (cc-frame-decoder.cpp:201-353, read_arm / read_ups / read_syn):
