@@ -1,4 +1,5 @@
-// dec_kernels.hip -- path B: HIP kernels of the bit-exact fixed-point .cool decoder.
+// dec_arm.hip -- path B: the ARM + CABAC kernels of the bit-exact fixed-point .cool decoder
+// (the decoder tail -- pyramid, synthesis, blend, output -- is dec_tail.hip).
 //
 // Compiled with -fwrapv: every accumulation is int32 with two's-complement wrap,
 // every right shift of a sum is the reference's truncation toward zero
@@ -10,15 +11,8 @@
 //                   4 causal rows live in an LDS ring; same-row contexts come from
 //                   registers, so the only per-latent LDS traffic is the above-row
 //                   gather.  Many streams (7 per frame x frames) run concurrently.
-//  dec_ups_level    one launch per pyramid level (ups_refine_cpu.hpp:11-79,
-//                   ups_upsample_cpu.hpp:12-91): integer refine + 2x polyphase upsample
-//                   with the reference's per-pass truncations, LDS-tiled.
-//  dec_syn_fused    1x1+1x1 fused head (synfused_cpu.hpp:17-109 semantics) + 3x3 layers
-//                   (syn_cpu.hpp / synlb_cpu.hpp) with replicate padding, one launch.
-//  dec_syn_layer    generic per-layer integer conv (any ks / widths).
-//  dec_output       444 -> 420/444 8/10-bit or PPM payload (ccdecapi.cpp:59-240).
-//  dec_output_tensor  the same samples as planar u8 / u16 / f32 device tensors (no file
-//                   layout): one packed store per 4 destination samples, any sample alignment.
+//  dec_arm_spec_kernel, dec_arm_chain_kernel  the faster forms for d <= 16 (described at
+//                   their definitions); launch_dec_arm picks one per (d, nh).
 #include <stdlib.h>
 
 #include <algorithm>
@@ -26,6 +20,7 @@
 #include <utility>
 
 #include "ccmi_cabac.h"
+#include "dec_device.h"
 #include "dec_internal.h"
 
 namespace ccmi {
@@ -49,9 +44,6 @@ constexpr CtxPack make_ctx_pack()
     return p;
 }
 __constant__ CtxPack c_ctx = make_ctx_pack();
-
-__device__ __forceinline__ int32_t tshift(int32_t s, int p) { return s < 0 ? -((-s) >> p) : s >> p; }
-__device__ __forceinline__ int clampi(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 // ------------------------------------------------------------------ device byte source
 // The stream is read through a constant-address-space pointer so that the wave-uniform
@@ -114,15 +106,6 @@ __device__ __forceinline__ void ctx_dydx(int i, int &dy, int &dx)
 constexpr int kRing = 5;   // rows y-4 .. y
 constexpr int kRingS = 4;  // speculative kernel (D <= 16: contexts reach row y-3): rows y-3 .. y
 constexpr int kPad = 8;    // zero columns either side of a ring row (speculative groups read x+3+4)
-
-// int32 multiply with two's-complement wrap; the 24-bit form (v_mad_i32_i24, full rate)
-// is exact whenever both operands fit in 24 signed bits.
-template <bool F24>
-__device__ __forceinline__ int32_t imul(int32_t a, int32_t b)
-{
-    if constexpr (F24) return __mul24(a, b);
-    else return (int32_t)((uint32_t)a * (uint32_t)b);
-}
 
 // OR of CCMI_ARM_FLAG_* bits into the stream's status word (one lane; a vector global atomic)
 __device__ __forceinline__ void put_status(const ArmStreamDesc &S, uint32_t bits)
@@ -1214,622 +1197,6 @@ __global__ __launch_bounds__(128) void dec_arm_chain_kernel(const ArmStreamDesc 
 #undef CSTAMP
 }
 
-// ------------------------------------------------------------------ upsampling (integer)
-constexpr int kThreads = 256;
-constexpr int kTY = 16, kTX = 64;
-constexpr int kMaxKs = 16;
-
-struct DecLevel {
-    const int32_t *src;      // level-k stack (or the raw coarsest latent plane)
-    int C, hs, ws, src_prec;
-    const int32_t *ref;      // latent plane of level k-1 (ARM precision)
-    int32_t *dst;            // level k-1 stack: C + 1 channels
-    int hd, wd;
-    const int32_t *kup;      // ksx2 taps
-    int ksx2;
-    const int32_t *kpre;     // ks taps
-    int ks;
-    int tiles_x;
-};
-
-// Window form (region decode): the step computes the window [dy0, dy1) x [dx0, dx1) of the
-// destination level and stores it compactly (pitch = the window's width).  The source stack
-// holds the window [sy0, sy1] x [sx0, sx1] of its level at pitch `spitch` from the storage
-// origin (soy, sox) (a compact stack: the window's own origin; the raw coarsest latent plane:
-// 0, 0 at the frame pitch); the reference plane keeps the frame pitch and holds ref_rows rows.
-// Border rules use the true plane sizes of DecLevel (replicate for the source, zero for the
-// refine); source reads are clamped to the stored window on top, which changes nothing the
-// window's samples depend on (the host planned the windows from these very taps) and keeps
-// the surplus lanes of an edge tile inside the allocation.
-struct DecLevelWin {
-    DecLevel L;
-    int dy0, dy1, dx0, dx1;
-    int soy, sox, spitch;
-    int sy0, sy1, sx0, sx1; // inclusive clamp bounds
-    int64_t splane;
-    int ref_rows;
-};
-
-template <bool WIN>
-__device__ __forceinline__ void ups_level_body(const DecLevel &A, const DecLevelWin *Wn, int gtx, int32_t *s_in,
-                                               int32_t *s_tmp);
-
-__global__ __launch_bounds__(kThreads) void dec_ups_level(DecLevel A)
-{
-    __shared__ int32_t s_in[(kTY + kMaxKs) * (kTX + kMaxKs)];
-    __shared__ int32_t s_tmp[(kTY + kMaxKs) * kTX];
-    ups_level_body<false>(A, nullptr, A.tiles_x, s_in, s_tmp);
-}
-
-// frames of a batch (identical geometry): blockIdx.y = frame
-__global__ __launch_bounds__(kThreads) void dec_ups_level_batch(const DecLevel *__restrict__ As)
-{
-    __shared__ int32_t s_in[(kTY + kMaxKs) * (kTX + kMaxKs)];
-    __shared__ int32_t s_tmp[(kTY + kMaxKs) * kTX];
-    const DecLevel A = As[blockIdx.y];
-    ups_level_body<false>(A, nullptr, A.tiles_x, s_in, s_tmp);
-}
-
-// region decode: blockIdx.y = frame, the grid's tiles cover the group's largest window
-// (gtx tiles across); a frame's blocks past its own window leave at once
-__global__ __launch_bounds__(kThreads) void dec_ups_level_win_batch(const DecLevelWin *__restrict__ As, int gtx)
-{
-    __shared__ int32_t s_in[(kTY + kMaxKs) * (kTX + kMaxKs)];
-    __shared__ int32_t s_tmp[(kTY + kMaxKs) * kTX];
-    const DecLevelWin *Wn = As + blockIdx.y;
-    const DecLevel A = Wn->L;
-    ups_level_body<true>(A, Wn, gtx, s_in, s_tmp);
-}
-
-template <bool WIN>
-__device__ __forceinline__ void ups_level_body(const DecLevel &A, const DecLevelWin *Wn, int gtx, int32_t *s_in,
-                                               int32_t *s_tmp)
-{
-    // window form: tiles from the window's origin rounded down to even (the upsampling phase
-    // of a tile row / column is its parity, as with the whole frame's multiples of 16 / 64)
-    int y0 = (blockIdx.x / gtx) * kTY;
-    int x0 = (blockIdx.x % gtx) * kTX;
-    int dy0 = 0, dy1 = A.hd, dx0 = 0, dx1 = A.wd, dpitch = A.wd, ref_rows = A.hd;
-    if (WIN) {
-        dy0 = Wn->dy0, dy1 = Wn->dy1, dx0 = Wn->dx0, dx1 = Wn->dx1;
-        dpitch = dx1 - dx0;
-        ref_rows = Wn->ref_rows;
-        y0 += dy0 & ~1;
-        x0 += dx0 & ~1;
-        if (y0 >= dy1 || x0 >= dx1) return;
-    }
-    const int tid = threadIdx.x;
-    const int64_t dplane = WIN ? (int64_t)(dy1 - dy0) * dpitch : (int64_t)A.hd * A.wd;
-    auto dst_ok = [&](int y, int x) { return WIN ? (y >= dy0 && y < dy1 && x >= dx0 && x < dx1) : (y < A.hd && x < A.wd); };
-    auto dst_at = [&](int y, int x) { return WIN ? (int64_t)(y - dy0) * dpitch + (x - dx0) : (int64_t)y * A.wd + x; };
-
-    // refine (ups_refine_cpu.hpp): zero padding, two passes with truncation, residual
-    {
-        const int pad = A.ks / 2;
-        const int rh = kTY + 2 * pad, rw = kTX + 2 * pad, pitch = kTX + kMaxKs;
-        for (int i = tid; i < rh * rw; i += kThreads) {
-            const int r = i / rw, c = i - r * rw;
-            const int y = y0 - pad + r, x = x0 - pad + c;
-            s_in[r * pitch + c] = (y >= 0 && y < ref_rows && x >= 0 && x < A.wd) ? A.ref[y * A.wd + x] : 0;
-        }
-        __syncthreads();
-        for (int i = tid; i < rh * kTX; i += kThreads) {
-            const int r = i / kTX, c = i - r * kTX;
-            const int y = y0 - pad + r;
-            int32_t acc = 0;
-            for (int k = 0; k < A.ks; ++k) acc += s_in[r * pitch + c + k] * A.kpre[k];
-            // rows outside the plane are the zero padding of the vertical pass
-            s_tmp[r * kTX + c] = (y >= 0 && y < A.hd) ? tshift(acc, kArmPrec) : 0;
-        }
-        __syncthreads();
-        for (int i = tid; i < kTY * kTX; i += kThreads) {
-            const int r = i / kTX, c = i - r * kTX;
-            const int y = y0 + r, x = x0 + c;
-            if (dst_ok(y, x)) {
-                int32_t acc = 0;
-                for (int k = 0; k < A.ks; ++k) acc += s_tmp[(r + k) * kTX + c] * A.kpre[k];
-                acc += (int32_t)((uint32_t)s_in[(r + pad) * pitch + c + pad] << (kUpsPrec - kArmPrec) << kUpsPrec);
-                A.dst[dst_at(y, x)] = tshift(acc, kUpsPrec);
-            }
-        }
-        __syncthreads();
-    }
-
-    // 2x upsample of every source channel (ups_upsample_cpu.hpp): replicate padding,
-    // horizontal pass >> src_prec into tmp (2*ws wide), vertical pass >> 12.
-    const int ks = A.ksx2 / 2, pad = ks / 2;
-    const int sy0 = y0 / 2 - pad, sx0 = x0 / 2 - pad;
-    const int sh = kTY / 2 + ks, sw = kTX / 2 + ks, pitch = kTX / 2 + kMaxKs;
-    for (int c = 0; c < A.C; ++c) {
-        const int32_t *sp = A.src + (WIN ? (int64_t)c * Wn->splane : (int64_t)c * A.hs * A.ws);
-        for (int i = tid; i < sh * sw; i += kThreads) {
-            const int r = i / sw, cc = i - r * sw;
-            if (WIN) {
-                const int yy = min(max(sy0 + r, Wn->sy0), Wn->sy1), xx = min(max(sx0 + cc, Wn->sx0), Wn->sx1);
-                s_in[r * pitch + cc] = sp[(int64_t)(yy - Wn->soy) * Wn->spitch + (xx - Wn->sox)];
-            } else {
-                s_in[r * pitch + cc] = sp[clampi(sy0 + r, A.hs - 1) * A.ws + clampi(sx0 + cc, A.ws - 1)];
-            }
-        }
-        __syncthreads();
-        for (int i = tid; i < sh * kTX; i += kThreads) {
-            const int r = i / kTX, cc = i - r * kTX;
-            const int X = x0 + cc, xs = X >> 1, ph = X & 1;
-            int32_t acc = 0;
-            for (int k = 0; k < ks; ++k) acc += s_in[r * pitch + (xs - pad + ph + k - sx0)] * A.kup[2 * k + ph];
-            s_tmp[r * kTX + cc] = tshift(acc, A.src_prec);
-        }
-        __syncthreads();
-        for (int i = tid; i < kTY * kTX; i += kThreads) {
-            const int r = i / kTX, cc = i - r * kTX;
-            const int Y = y0 + r, X = x0 + cc;
-            if (dst_ok(Y, X)) {
-                const int ys = Y >> 1, ph = Y & 1;
-                int32_t acc = 0;
-                for (int k = 0; k < ks; ++k) acc += s_tmp[(ys - pad + ph + k - sy0) * kTX + cc] * A.kup[2 * k + ph];
-                A.dst[(int64_t)(c + 1) * dplane + dst_at(Y, X)] = tshift(acc, kUpsPrec);
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// ------------------------------------------------------------------ synthesis (integer)
-constexpr int kRW = 64, kRH = 32, kRegion = kRW * kRH;
-constexpr int kMaxSp = 3;
-
-struct DecSynFused {
-    const int32_t *in;
-    int cin, H, W;
-    int hid;                // fused head width (always ReLU), output linear (synfused semantics)
-    const int32_t *w0, *b0, *w1, *b1;
-    int n_sp;
-    const int32_t *wsp[kMaxSp], *bsp[kMaxSp];
-    int res[kMaxSp], relu[kMaxSp];
-    int32_t *out;
-    int tiles_x;
-    int f24; // DecSynArgs::f24
-};
-
-// Window form (region decode): the input holds the window [iy0, iy1] x [ix0, ix1] of the
-// frame's level-0 stack, compact at pitch `ipitch` (the region grown by the 3x3 layers' reach,
-// clipped to the frame); the output is the region [ry, ry + rh) x [rx, rx + rw), compact
-// [3][rh][rw].  Every replicate clamp still uses the frame's true H and W (DecSynFused): a
-// window edge that is not a frame edge is never padded.  Input reads are clamped to the stored
-// window on top (only the surplus lanes of a tile ever fall outside it).
-struct DecSynFusedWin {
-    DecSynFused F;
-    int iy0, iy1, ix0, ix1, ipitch;
-    int64_t iplane;
-    int ry, rx, rh, rw;
-};
-
-template <int CIN, int CMID, bool F24, bool WIN>
-__device__ __forceinline__ void syn_fused_body(const DecSynFused &A, const DecSynFusedWin *Wn, int gtx,
-                                               int32_t (*s_buf)[CMID][kRegion]);
-
-template <int CIN, int CMID>
-__global__ __launch_bounds__(kThreads) void dec_syn_fused(DecSynFused A)
-{
-    __shared__ __attribute__((aligned(16))) int32_t s_buf[2][CMID][kRegion];
-    if (A.f24) syn_fused_body<CIN, CMID, true, false>(A, nullptr, A.tiles_x, s_buf);
-    else syn_fused_body<CIN, CMID, false, false>(A, nullptr, A.tiles_x, s_buf);
-}
-
-template <int CIN, int CMID>
-__global__ __launch_bounds__(kThreads) void dec_syn_fused_batch(const DecSynFused *__restrict__ As)
-{
-    __shared__ __attribute__((aligned(16))) int32_t s_buf[2][CMID][kRegion];
-    // by reference: the frame's argument record is read with scalar loads where it is used (a
-    // by-value copy with runtime-indexed layer arrays lived in scratch, 160 bytes per lane)
-    const DecSynFused &A = As[blockIdx.y];
-    if (A.f24) syn_fused_body<CIN, CMID, true, false>(A, nullptr, A.tiles_x, s_buf);
-    else syn_fused_body<CIN, CMID, false, false>(A, nullptr, A.tiles_x, s_buf);
-}
-
-// region decode: blockIdx.y = frame, gtx tiles across (the group shares one region size)
-template <int CIN, int CMID>
-__global__ __launch_bounds__(kThreads) void dec_syn_fused_win_batch(const DecSynFusedWin *__restrict__ As, int gtx)
-{
-    __shared__ __attribute__((aligned(16))) int32_t s_buf[2][CMID][kRegion];
-    const DecSynFusedWin *Wn = As + blockIdx.y;
-    const DecSynFused &A = Wn->F;
-    if (A.f24) syn_fused_body<CIN, CMID, true, true>(A, Wn, gtx, s_buf);
-    else syn_fused_body<CIN, CMID, false, true>(A, Wn, gtx, s_buf);
-}
-
-template <int CIN, int CMID, bool F24, bool WIN>
-__device__ __forceinline__ void syn_fused_body(const DecSynFused &A, const DecSynFusedWin *Wn, int gtx,
-                                               int32_t (*s_buf)[CMID][kRegion])
-{
-    const int halo = A.n_sp;
-    const int TX = kRW - 2 * halo, TY = kRH - 2 * halo;
-    // frame coordinates throughout; the window form's tiles start at the region's origin
-    const int y0 = (blockIdx.x / gtx) * TY + (WIN ? Wn->ry : 0), x0 = (blockIdx.x % gtx) * TX + (WIN ? Wn->rx : 0);
-    // the exclusive end of what is written, and where sample (gy, gx) of output plane 0 goes
-    const int ye = WIN ? Wn->ry + Wn->rh : A.H, xe = WIN ? Wn->rx + Wn->rw : A.W;
-    if (WIN && (y0 >= ye || x0 >= xe)) return;
-    const int oy = y0 - halo, ox = x0 - halo;
-    const int64_t plane = WIN ? (int64_t)Wn->rh * Wn->rw : (int64_t)A.H * A.W;   // of the output
-    const int64_t iplane = WIN ? Wn->iplane : (int64_t)A.H * A.W;                // of the input
-    const int c = threadIdx.x & (kRW - 1), r0 = threadIdx.x >> 6;
-    const int gx = ox + c, cxg = clampi(gx, A.W - 1);
-    auto out_at = [&](int gy) { return WIN ? (int64_t)(gy - Wn->ry) * Wn->rw + (gx - Wn->rx) : (int64_t)gy * A.W + gx; };
-    auto in_pix = [&](int yy) { // input sample at row yy (any), this lane's column
-        if (WIN)
-            return (int64_t)(min(max(yy, Wn->iy0), Wn->iy1) - Wn->iy0) * Wn->ipitch + (min(max(gx, Wn->ix0), Wn->ix1) - Wn->ix0);
-        return (int64_t)clampi(yy, A.H - 1) * A.W + cxg;
-    };
-
-    // the head's weight records (w0[j][0..CIN), b0[j], w1[0..CMID)[j]; 12 ints) in the second
-    // ping-pong buffer, which the first 3x3 layer writes only after its barrier: read back as
-    // three broadcast ds_read_b128 per hidden unit, issued ahead of use (scalar weight loads
-    // per unit made every unit wait for its own s_load round trip)
-    static_assert(CIN + 1 + CMID <= 12, "head record");
-    int32_t *s_rec = &s_buf[1][0][0];
-    const int hid = A.hid;
-    const bool recs = hid * 12 <= CMID * kRegion;
-    if (recs) {
-        for (int i = threadIdx.x; i < hid * 12; i += kThreads) {
-            const int j = i / 12, f = i - j * 12;
-            int32_t v = 0;
-            if (f < CIN) v = A.w0[j * CIN + f];
-            else if (f == CIN) v = A.b0[j];
-            else if (f < CIN + 1 + CMID) v = A.w1[(f - CIN - 1) * hid + j];
-            s_rec[i] = v;
-        }
-        __syncthreads();
-    }
-    auto store_head = [&](int r, const int32_t (&o)[CMID]) {
-        const int gy = oy + r;
-#pragma unroll
-        for (int m = 0; m < CMID; ++m) {
-            const int32_t v = tshift(o[m], kSynPrec);
-            if (halo == 0) {
-                if (gy < ye && gx < xe) A.out[m * plane + out_at(gy)] = v;
-            } else {
-                s_buf[0][m][r * kRW + c] = v;
-            }
-        }
-    };
-    if (recs) {
-        // two rows (r, r + 4) per pass over the records
-        typedef int i4v __attribute__((ext_vector_type(4)));
-        typedef const __attribute__((address_space(3))) i4v *lds_i4;
-        lds_i4 rb = (lds_i4)s_rec;
-        for (int r = r0; r < kRH; r += 8) {
-            int32_t x[2][CIN], o[2][CMID];
-#pragma unroll
-            for (int p = 0; p < 2; ++p) {
-                const int64_t pix = in_pix(oy + r + 4 * p);
-#pragma unroll
-                for (int k = 0; k < CIN; ++k) x[p][k] = A.in[k * iplane + pix];
-#pragma unroll
-                for (int m = 0; m < CMID; ++m) o[p][m] = A.b1[m];
-            }
-#pragma unroll 2
-            for (int j = 0; j < hid; ++j) {
-                const i4v q0 = rb[3 * j], q1 = rb[3 * j + 1], q2 = rb[3 * j + 2];
-                const int32_t w[12] = {q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w, q2.x, q2.y, q2.z, q2.w};
-#pragma unroll
-                for (int p = 0; p < 2; ++p) {
-                    int32_t acc = w[CIN];
-#pragma unroll
-                    for (int k = 0; k < CIN; ++k) acc += imul<F24>(x[p][k], w[k]);
-                    acc = acc < 0 ? 0 : acc >> kSynPrec;
-#pragma unroll
-                    for (int m = 0; m < CMID; ++m) o[p][m] += imul<F24>(acc, w[CIN + 1 + m]);
-                }
-            }
-            store_head(r, o[0]);
-            store_head(r + 4, o[1]);
-        }
-    } else {
-        for (int r = r0; r < kRH; r += 4) {
-            const int64_t pix = in_pix(oy + r);
-            int32_t x[CIN];
-#pragma unroll
-            for (int k = 0; k < CIN; ++k) x[k] = A.in[k * iplane + pix];
-            int32_t o[CMID];
-#pragma unroll
-            for (int m = 0; m < CMID; ++m) o[m] = A.b1[m];
-            for (int j = 0; j < hid; ++j) {
-                int32_t acc = A.b0[j];
-#pragma unroll
-                for (int k = 0; k < CIN; ++k) acc += imul<F24>(x[k], A.w0[j * CIN + k]);
-                acc = acc < 0 ? 0 : acc >> kSynPrec;
-#pragma unroll
-                for (int m = 0; m < CMID; ++m) o[m] += imul<F24>(acc, A.w1[m * hid + j]);
-            }
-            store_head(r, o);
-        }
-    }
-    if (halo == 0) return;
-
-    int cur = 0;
-    for (int s = 0; s < A.n_sp; ++s) {
-        __syncthreads();
-        const int t = s + 1;
-        const bool last = s == A.n_sp - 1;
-        const int32_t *wt = A.wsp[s], *bs = A.bsp[s];
-        const bool col_ok = c >= t && c < kRW - t;
-        int lx[3];
-#pragma unroll
-        for (int d = 0; d < 3; ++d) lx[d] = clampi(cxg + d - 1, A.W - 1) - ox;
-        for (int r = r0 + t; r < kRH - t; r += 4) {
-            const int gy = oy + r;
-            if (!col_ok || (last && (gy >= ye || gx >= xe))) continue;
-            const int cyg = clampi(gy, A.H - 1);
-            int ly[3];
-#pragma unroll
-            for (int d = 0; d < 3; ++d) ly[d] = (clampi(cyg + d - 1, A.H - 1) - oy) * kRW;
-            int32_t nb[CMID][3][3];
-#pragma unroll
-            for (int k = 0; k < CMID; ++k)
-#pragma unroll
-                for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-                    for (int dx = 0; dx < 3; ++dx) nb[k][dy][dx] = s_buf[cur][k][ly[dy] + lx[dx]];
-#pragma unroll
-            for (int m = 0; m < CMID; ++m) {
-                int32_t acc = bs[m];
-                if (A.res[s]) acc += (int32_t)((uint32_t)nb[m][1][1] << kSynPrec);
-#pragma unroll
-                for (int k = 0; k < CMID; ++k)
-#pragma unroll
-                    for (int dy = 0; dy < 3; ++dy)
-#pragma unroll
-                        for (int dx = 0; dx < 3; ++dx) acc += imul<F24>(nb[k][dy][dx], wt[((m * CMID + k) * 3 + dy) * 3 + dx]);
-                const int32_t v = acc < 0 ? (A.relu[s] ? 0 : -((-acc) >> kSynPrec)) : acc >> kSynPrec;
-                if (last)
-                    A.out[m * plane + out_at(gy)] = v;
-                else
-                    s_buf[cur ^ 1][m][r * kRW + c] = v;
-            }
-        }
-        cur ^= 1;
-    }
-}
-
-// generic integer conv layer (syn_cpu.hpp semantics, out-of-place, replicate padding).
-// fused_hidden > 0: this launch is the fused 1x1 pair with that hidden width.
-__global__ __launch_bounds__(kThreads) void dec_syn_layer(const int32_t *__restrict__ in, int cin, int H, int W,
-                                                          const int32_t *__restrict__ wt,
-                                                          const int32_t *__restrict__ bs, int nout, int ks,
-                                                          int residual, int relu, int32_t *__restrict__ out)
-{
-    const int64_t plane = (int64_t)H * W;
-    const int64_t p = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (p >= plane) return;
-    const int y = (int)(p / W), x = (int)(p - (int64_t)y * W);
-    const int pad = ks / 2;
-    for (int m = 0; m < nout; ++m) {
-        int32_t acc = bs[m];
-        if (residual) acc += (int32_t)((uint32_t)in[m * plane + p] << kSynPrec);
-        for (int k = 0; k < cin; ++k)
-            for (int dy = 0; dy < ks; ++dy) {
-                const int yy = clampi(y + dy - pad, H - 1);
-                for (int dx = 0; dx < ks; ++dx)
-                    acc += in[k * plane + (int64_t)yy * W + clampi(x + dx - pad, W - 1)] *
-                           wt[((m * cin + k) * ks + dy) * ks + dx];
-            }
-        out[m * plane + p] = acc < 0 ? (relu ? 0 : -((-acc) >> kSynPrec)) : acc >> kSynPrec;
-    }
-}
-
-__global__ __launch_bounds__(kThreads) void dec_syn_fused_generic(const int32_t *__restrict__ in, int cin, int64_t plane,
-                                                                  const int32_t *__restrict__ w0,
-                                                                  const int32_t *__restrict__ b0, int hid,
-                                                                  const int32_t *__restrict__ w1,
-                                                                  const int32_t *__restrict__ b1, int nout,
-                                                                  int32_t *__restrict__ out)
-{
-    const int64_t p = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (p >= plane) return;
-    for (int m = 0; m < nout; ++m) {
-        int32_t o = b1[m];
-        for (int j = 0; j < hid; ++j) {
-            int32_t acc = b0[j];
-            for (int k = 0; k < cin; ++k) acc += in[k * plane + p] * w0[j * cin + k];
-            acc = acc < 0 ? 0 : acc >> kSynPrec;
-            o += acc * w1[m * hid + j];
-        }
-        out[m * plane + p] = tshift(o, kSynPrec);
-    }
-}
-
-__global__ __launch_bounds__(kThreads) void dec_blend_kernel(int32_t *acc, const int32_t *x, int64_t n, int32_t b_acc,
-                                                             int32_t b_x, int first)
-{
-    const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (i >= n) return;
-    auto cl = [](int32_t v) { return v < 0 ? 0 : (v > (1 << kSynPrec) ? (1 << kSynPrec) : v); };
-    const int32_t x0 = cl(x[i]);
-    if (first) acc[i] = (cl(acc[i]) * b_acc + x0 * b_x) >> kSynPrec;
-    else acc[i] = acc[i] + ((x0 * b_x) >> kSynPrec);
-}
-
-// ------------------------------------------------------------------ output bytes
-struct DecOut {
-    const int32_t *syn;
-    int H, W, maxv, kind, bps;
-    uint8_t *dst;
-};
-
-__device__ __forceinline__ void output_body(const int32_t *__restrict__ syn, int H, int W, int maxv, int kind, int bps,
-                                            uint8_t *__restrict__ dst);
-
-__global__ __launch_bounds__(kThreads) void dec_output_kernel(const int32_t *__restrict__ syn, int H, int W, int maxv,
-                                                              int kind, int bps, uint8_t *__restrict__ dst)
-{
-    output_body(syn, H, W, maxv, kind, bps, dst);
-}
-
-__global__ __launch_bounds__(kThreads) void dec_output_batch(const DecOut *__restrict__ Os)
-{
-    const DecOut O = Os[blockIdx.y];
-    output_body(O.syn, O.H, O.W, O.maxv, O.kind, O.bps, O.dst);
-}
-
-__device__ __forceinline__ void output_body(const int32_t *__restrict__ syn, int H, int W, int maxv, int kind, int bps,
-                                            uint8_t *__restrict__ dst)
-{
-    const int64_t plane = (int64_t)H * W;
-    const int64_t p = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    if (p >= plane) return;
-    auto smp = [maxv](int32_t v) {
-        int32_t s = (v * maxv + (1 << (kSynPrec - 1))) >> kSynPrec;
-        return s < 0 ? 0 : (s > maxv ? maxv : s);
-    };
-    auto put = [&](int64_t idx, int32_t s, bool big_endian) {
-        if (bps == 1) dst[idx] = (uint8_t)s;
-        else if (big_endian) { dst[2 * idx] = (uint8_t)(s >> 8); dst[2 * idx + 1] = (uint8_t)s; }
-        else { dst[2 * idx] = (uint8_t)s; dst[2 * idx + 1] = (uint8_t)(s >> 8); }
-    };
-    const int y = (int)(p / W), x = (int)(p - (int64_t)y * W);
-    if (kind == 2) { // PPM: interleaved RGB, 16-bit big endian
-        for (int c = 0; c < 3; ++c) put(3 * p + c, smp(syn[c * plane + p]), true);
-        return;
-    }
-    put(p, smp(syn[p]), false);
-    if (kind == 1) {
-        put(plane + p, smp(syn[plane + p]), false);
-        put(2 * plane + p, smp(syn[2 * plane + p]), false);
-    } else if (!(y & 1) && !(x & 1) && (y >> 1) < H / 2 && (x >> 1) < W / 2) {
-        const int64_t cp = (int64_t)(H / 2) * (W / 2), ci = (int64_t)(y >> 1) * (W / 2) + (x >> 1);
-        put(plane + ci, smp(syn[plane + p]), false);
-        put(plane + cp + ci, smp(syn[2 * plane + p]), false);
-    }
-}
-
-// ------------------------------------------------------------------ output tensors
-// Device sink: the same samples as output_body (smp(), same 420 subsampling) in planar
-// tensor layout, never interleaved.  Both layouts are ONE flat array of samples:
-//   444: [3][H][W], sample j is smp(syn[j]);
-//   420: Y[H][W] then U, V [H/2][W/2], contiguous: j < HW as above, the rest a stride-2 gather.
-// A thread owns one naturally aligned group of 4 destination samples (one 32 / 64 / 128-bit
-// store for u8 / u16 / f32).  dst only has the alignment of one sample, so the groups are
-// laid out from the aligned address at or below dst: the first and the last group of a frame
-// are partial and take scalar stores, every other group one packed store -- the chroma
-// samples too, which the byte path writes one byte per thread.  DecOut::bps is unused here
-// (the sample type is the template argument).
-template <typename T> struct OutVec;
-template <> struct OutVec<uint8_t> { using type = uint32_t; };
-template <> struct OutVec<uint16_t> { using type = uint2; };
-template <> struct OutVec<float> { using type = float4; };
-
-template <typename T> __device__ __forceinline__ T out_sample(int32_t s, float fmax);
-template <> __device__ __forceinline__ uint8_t out_sample<uint8_t>(int32_t s, float) { return (uint8_t)s; }
-template <> __device__ __forceinline__ uint16_t out_sample<uint16_t>(int32_t s, float) { return (uint16_t)s; }
-// one correctly rounded division: what torch's u.to(float32) / maxv computes
-template <> __device__ __forceinline__ float out_sample<float>(int32_t s, float fmax) { return __fdiv_rn((float)s, fmax); }
-
-// CROP (the per-frame tail of a region decode): H x W is the region, whose sample (y, x) of
-// plane c is syn[c * splane + (oy + y) * spitch + ox + x] of the whole-frame synthesis output
-// (oy, ox even for 420, so the chroma's even rows and columns are the frame's).
-template <typename T, bool CROP>
-__device__ __forceinline__ void output_tensor_body(const int32_t *__restrict__ syn, int H, int W, int maxv, int kind,
-                                                   T *__restrict__ dst, int64_t splane = 0, int spitch = 0, int oy = 0,
-                                                   int ox = 0)
-{
-    const int64_t plane = (int64_t)H * W;
-    auto direct_at = [&](int64_t j) { // flat sample j of the [.][H][W] prefix
-        if (!CROP) return j;
-        const int64_t c = j / plane, rem = j - c * plane;
-        const int y = (int)(rem / W), x = (int)(rem - (int64_t)y * W);
-        return c * splane + (int64_t)(oy + y) * spitch + ox + x;
-    };
-    const int ch = H / 2, cw = W / 2;
-    const int64_t cp = (int64_t)ch * cw;
-    const int64_t elems = kind == 1 ? 3 * plane : plane + 2 * cp;
-    const int64_t direct = kind == 1 ? elems : plane; // samples below this index read syn[j]
-    const int mis = (int)((reinterpret_cast<uintptr_t>(dst) / sizeof(T)) & 3); // samples past the aligned address
-    const int64_t j0 = ((int64_t)blockIdx.x * kThreads + threadIdx.x) * 4 - mis;
-    if (j0 >= elems) return;
-    const float fmax = (float)maxv;
-    auto smp = [maxv](int32_t v) {
-        int32_t s = (v * maxv + (1 << (kSynPrec - 1))) >> kSynPrec;
-        return s < 0 ? 0 : (s > maxv ? maxv : s);
-    };
-    T v[4];
-    if (j0 >= 0 && j0 + 4 <= direct) { // the common case: 4 samples of the flat prefix
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = out_sample<T>(smp(syn[direct_at(j0 + k)]), fmax);
-    } else {
-        // a group that is partial, crosses into the chroma planes or lies in them: one
-        // division for its first chroma sample, the others step along the row
-        int64_t c = 0;
-        int cy = 0, cx = 0;
-        const int64_t jc = (j0 > direct ? j0 : direct) - direct; // first chroma index of the group
-        if (kind != 1 && cp > 0) {
-            c = jc / cp;
-            const int64_t ci = jc - c * cp;
-            cy = (int)(ci / cw);
-            cx = (int)(ci - (int64_t)cy * cw);
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int64_t j = j0 + k;
-            v[k] = T(0);
-            if (j < 0 || j >= elems) continue;
-            if (j < direct) {
-                v[k] = out_sample<T>(smp(syn[direct_at(j)]), fmax);
-                continue;
-            }
-            v[k] = out_sample<T>(smp(syn[CROP ? (1 + c) * splane + (int64_t)(oy + 2 * cy) * spitch + ox + 2 * cx
-                                              : (1 + c) * plane + (int64_t)(2 * cy) * W + 2 * cx]),
-                                 fmax);
-            if (++cx == cw) {
-                cx = 0;
-                if (++cy == ch) {
-                    cy = 0;
-                    ++c;
-                }
-            }
-        }
-    }
-    if (j0 >= 0 && j0 + 4 <= elems) {
-        typename OutVec<T>::type pk;
-        __builtin_memcpy(&pk, v, sizeof pk);
-        *reinterpret_cast<typename OutVec<T>::type *>(dst + j0) = pk;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (j0 + k >= 0 && j0 + k < elems) dst[j0 + k] = v[k];
-    }
-}
-
-template <typename T>
-__global__ __launch_bounds__(kThreads) void dec_output_tensor(const int32_t *__restrict__ syn, int H, int W, int maxv,
-                                                              int kind, T *__restrict__ dst)
-{
-    output_tensor_body<T, false>(syn, H, W, maxv, kind, dst);
-}
-
-// h x w = the region at (oy, ox) of the H x W frame
-template <typename T>
-__global__ __launch_bounds__(kThreads) void dec_output_tensor_crop(const int32_t *__restrict__ syn, int H, int W, int oy,
-                                                                   int ox, int h, int w, int maxv, int kind,
-                                                                   T *__restrict__ dst)
-{
-    output_tensor_body<T, true>(syn, h, w, maxv, kind, dst, (int64_t)H * W, W, oy, ox);
-}
-
-template <typename T> __global__ __launch_bounds__(kThreads) void dec_output_tensor_batch(const DecOut *__restrict__ Os)
-{
-    const DecOut O = Os[blockIdx.y];
-    output_tensor_body<T, false>(O.syn, O.H, O.W, O.maxv, O.kind, reinterpret_cast<T *>(O.dst));
-}
-
-// blocks that cover the samples of one frame plus the up to 3 lead-in slots of an unaligned dst
-unsigned output_tensor_blocks(int h, int w, int kind)
-{
-    const int64_t plane = (int64_t)h * w;
-    const int64_t elems = kind == 1 ? 3 * plane : plane + 2 * (int64_t)(h / 2) * (w / 2);
-    const int64_t groups = (elems + 3 + 3) / 4;
-    return (unsigned)((groups + kThreads - 1) / kThreads);
-}
-
 } // namespace
 
 // ------------------------------------------------------------------ launchers
@@ -1888,526 +1255,6 @@ int launch_dec_arm(const ArmStreamDesc *d_streams, int n_streams, int max_w, int
 #undef CCMI_ARM_D
 #undef CCMI_ARM_CASE
     return ccmi_set_error(CCMI_ERR_UNSUPPORTED, "dec: ARM with d=%d, %d hidden layers not supported", d, nh);
-}
-
-size_t dec_ups_workspace_elems(const int *lh, const int *lw, int L)
-{
-    size_t n = 0;
-    for (int k = 1; k <= L - 2; ++k) n += (size_t)(L - k) * lh[k] * lw[k];
-    return n;
-}
-
-static bool ups_ks_ok(const DecUpsArgs &a)
-{
-    return a.ups_ks >= 2 && a.ups_ks <= kMaxKs && a.pre_ks >= 1 && a.pre_ks <= kMaxKs - 1;
-}
-
-// kernel arguments of every pyramid step of one frame (coarsest first); returns the step count
-static int make_levels(const DecUpsArgs &a, DecLevel *lv)
-{
-    const int L = a.n_layers;
-    int32_t *stack[CCMI_MAX_GRIDS] = {};
-    int32_t *ws = a.workspace;
-    for (int k = 1; k <= L - 2; ++k) {
-        stack[k] = ws;
-        ws += (size_t)(L - k) * a.lh[k] * a.lw[k];
-    }
-    for (int step = 0; step < L - 1; ++step) {
-        const int k = L - 1 - step;
-        DecLevel &A = lv[step];
-        A = DecLevel{};
-        A.src = k == L - 1 ? a.lat + a.off[k] : stack[k];
-        A.C = L - k;
-        A.hs = a.lh[k];
-        A.ws = a.lw[k];
-        A.src_prec = k == L - 1 ? kArmPrec : kUpsPrec;
-        A.ref = a.lat + a.off[k - 1];
-        A.dst = k - 1 == 0 ? a.out : stack[k - 1];
-        A.hd = a.lh[k - 1];
-        A.wd = a.lw[k - 1];
-        // reference indices: ups layer (L-2-target)%n_ups, preconcat (L-2-layer)%n_pre; target = layer = k-1
-        A.kup = a.kernels + ((L - 2 - (k - 1)) % a.n_ups) * a.ups_ks;
-        A.ksx2 = a.ups_ks;
-        A.kpre = a.kernels + a.n_ups * a.ups_ks + ((L - 2 - (k - 1)) % a.n_pre) * a.pre_ks;
-        A.ks = a.pre_ks;
-        A.tiles_x = ccmi_div_up(A.wd, kTX);
-    }
-    return L > 1 ? L - 1 : 0;
-}
-
-// The windows a region needs, finest level first, from the taps of ups_level_body and
-// syn_fused_body.  A destination row Y of a pyramid step reads source rows
-// (Y >> 1) - pad + (Y & 1) .. + ks - 1 (ks = ups_ks / 2 taps per phase, pad = ks / 2), clamped
-// to the plane; the refined channel of a level reads its latent grid pre_ks / 2 rows either
-// side, zero outside the plane.  Columns alike.
-void dec_roi_plan(const int *lh, const int *lw, int L, int ups_ks, int pre_ks, int syn_halo, const DecWindow &rect,
-                  DecRoi &r)
-{
-    r = DecRoi{};
-    r.rect = rect;
-    r.lev[0] = DecWindow{std::max(0, rect.y0 - syn_halo), std::min(lh[0], rect.y1 + syn_halo),
-                         std::max(0, rect.x0 - syn_halo), std::min(lw[0], rect.x1 + syn_halo)};
-    const int ks = ups_ks / 2, pad = ks / 2;
-    auto lo = [&](int a) { return std::max(0, (a >> 1) - pad + (a & 1)); };
-    auto hi = [&](int b, int n) { return std::min(n, ((b - 1) >> 1) + ((b - 1) & 1) - pad + ks); };
-    for (int k = 1; k < L; ++k) {
-        const DecWindow &d = r.lev[k - 1];
-        r.lev[k] = DecWindow{lo(d.y0), hi(d.y1, lh[k]), lo(d.x0), hi(d.x1, lw[k])};
-    }
-    for (int l = 0; l < L; ++l) r.arm_rows[l] = l == L - 1 ? r.lev[l].y1 : std::min(lh[l], r.lev[l].y1 + pre_ks / 2);
-}
-
-size_t dec_ups_workspace_elems_win(const DecRoi &r, int L)
-{
-    size_t n = 0;
-    for (int k = 1; k <= L - 2; ++k) n += (size_t)(L - k) * r.lev[k].h() * r.lev[k].w();
-    return n;
-}
-
-// window-form arguments of every pyramid step of one frame (coarsest first)
-static int make_levels_win(const DecTailFrame &f, DecLevelWin *lv)
-{
-    const DecUpsArgs &a = f.ups;
-    const DecRoi &R = f.roi;
-    const int L = a.n_layers;
-    DecLevel base[CCMI_MAX_GRIDS];
-    const int steps = make_levels(a, base);
-    int32_t *stack[CCMI_MAX_GRIDS] = {};
-    int32_t *ws = a.workspace;
-    for (int k = 1; k <= L - 2; ++k) {
-        stack[k] = ws;
-        ws += (size_t)(L - k) * R.lev[k].h() * R.lev[k].w();
-    }
-    for (int step = 0; step < steps; ++step) {
-        const int k = L - 1 - step;
-        DecLevelWin &Wn = lv[step];
-        Wn = DecLevelWin{};
-        Wn.L = base[step];
-        const DecWindow &sw = R.lev[k], &dw = R.lev[k - 1];
-        const bool raw = k == L - 1; // the coarsest latent plane itself: frame pitch, origin 0
-        Wn.L.src = raw ? a.lat + a.off[k] : stack[k];
-        Wn.L.dst = k - 1 == 0 ? a.out : stack[k - 1];
-        Wn.dy0 = dw.y0, Wn.dy1 = dw.y1, Wn.dx0 = dw.x0, Wn.dx1 = dw.x1;
-        Wn.soy = raw ? 0 : sw.y0;
-        Wn.sox = raw ? 0 : sw.x0;
-        Wn.spitch = raw ? a.lw[k] : sw.w();
-        Wn.splane = (int64_t)sw.h() * sw.w();
-        Wn.sy0 = sw.y0, Wn.sy1 = sw.y1 - 1, Wn.sx0 = sw.x0, Wn.sx1 = sw.x1 - 1;
-        Wn.ref_rows = R.arm_rows[k - 1];
-    }
-    return steps;
-}
-
-int launch_dec_ups(const DecUpsArgs &a, hipStream_t s)
-{
-    if (!ups_ks_ok(a))
-        return ccmi_set_error(CCMI_ERR_UNSUPPORTED, "dec: upsampling kernel sizes %d/%d", a.ups_ks, a.pre_ks);
-    DecLevel lv[CCMI_MAX_GRIDS];
-    const int steps = make_levels(a, lv);
-    for (int step = 0; step < steps; ++step) {
-        const DecLevel &A = lv[step];
-        hipLaunchKernelGGL(dec_ups_level, dim3(A.tiles_x * ccmi_div_up(A.hd, kTY)), dim3(kThreads), 0, s, A);
-        CCMI_HIP_CHECK(hipGetLastError());
-    }
-    return CCMI_OK;
-}
-
-static int syn_maxc(const DecSynArgs &a)
-{
-    int m = a.c_in;
-    for (int l = 0; l < a.n_layers; ++l) m = a.layers[l].n_out > m ? a.layers[l].n_out : m;
-    return m;
-}
-
-static bool syn_fast(const DecSynArgs &a, int *cmid)
-{
-    if (a.n_layers < 2 || a.layers[0].ks != 1 || a.layers[1].ks != 1) return false;
-    if (a.c_in < 1 || a.c_in > 8) return false;
-    const int cm = a.layers[1].n_out;
-    if (cm != 3) return false;
-    if (a.n_layers - 2 > kMaxSp) return false;
-    for (int l = 2; l < a.n_layers; ++l)
-        if (a.layers[l].ks != 3 || a.layers[l].n_out != cm) return false;
-    *cmid = cm;
-    return true;
-}
-
-size_t dec_syn_workspace_elems(const DecSynArgs &a)
-{
-    int cm;
-    if (syn_fast(a, &cm)) return 0;
-    return 2 * (size_t)syn_maxc(a) * a.h * a.w;
-}
-
-int launch_dec_syn(const DecSynArgs &a, hipStream_t s)
-{
-    // weight offsets (per layer W then b)
-    const int32_t *wp[CCMI_MAX_SYN_LAYERS], *bp[CCMI_MAX_SYN_LAYERS];
-    int cin_of[CCMI_MAX_SYN_LAYERS];
-    {
-        const int32_t *q = a.params;
-        int c = a.c_in;
-        for (int l = 0; l < a.n_layers; ++l) {
-            cin_of[l] = c;
-            wp[l] = q;
-            q += (size_t)a.layers[l].n_out * c * a.layers[l].ks * a.layers[l].ks;
-            bp[l] = q;
-            q += a.layers[l].n_out;
-            c = a.layers[l].n_out;
-        }
-    }
-    int cm;
-    if (syn_fast(a, &cm)) {
-        DecSynFused F{};
-        F.in = a.in;
-        F.cin = a.c_in;
-        F.H = a.h;
-        F.W = a.w;
-        F.hid = a.layers[0].n_out;
-        F.w0 = wp[0];
-        F.b0 = bp[0];
-        F.w1 = wp[1];
-        F.b1 = bp[1];
-        F.n_sp = a.n_layers - 2;
-        for (int i = 0; i < F.n_sp; ++i) {
-            F.wsp[i] = wp[2 + i];
-            F.bsp[i] = bp[2 + i];
-            F.res[i] = a.layers[2 + i].residual;
-            F.relu[i] = a.layers[2 + i].relu;
-        }
-        F.out = a.out;
-        F.f24 = a.f24;
-        const int halo = F.n_sp;
-        F.tiles_x = ccmi_div_up(a.w, kRW - 2 * halo);
-        dim3 grid(F.tiles_x * ccmi_div_up(a.h, kRH - 2 * halo));
-        switch (a.c_in) {
-        case 1: hipLaunchKernelGGL((dec_syn_fused<1, 3>), grid, dim3(kThreads), 0, s, F); break;
-        case 2: hipLaunchKernelGGL((dec_syn_fused<2, 3>), grid, dim3(kThreads), 0, s, F); break;
-        case 3: hipLaunchKernelGGL((dec_syn_fused<3, 3>), grid, dim3(kThreads), 0, s, F); break;
-        case 4: hipLaunchKernelGGL((dec_syn_fused<4, 3>), grid, dim3(kThreads), 0, s, F); break;
-        case 5: hipLaunchKernelGGL((dec_syn_fused<5, 3>), grid, dim3(kThreads), 0, s, F); break;
-        case 6: hipLaunchKernelGGL((dec_syn_fused<6, 3>), grid, dim3(kThreads), 0, s, F); break;
-        case 7: hipLaunchKernelGGL((dec_syn_fused<7, 3>), grid, dim3(kThreads), 0, s, F); break;
-        default: hipLaunchKernelGGL((dec_syn_fused<8, 3>), grid, dim3(kThreads), 0, s, F); break;
-        }
-        CCMI_HIP_CHECK(hipGetLastError());
-        return CCMI_OK;
-    }
-    // generic: the reference fuses the first two layers whenever both are 1x1 (can_fuse)
-    const int64_t plane = (int64_t)a.h * a.w;
-    const int maxc = syn_maxc(a);
-    int32_t *bufs[2] = {a.workspace, a.workspace + (size_t)maxc * plane};
-    const int32_t *src = a.in;
-    dim3 grid((unsigned)((plane + kThreads - 1) / kThreads));
-    int l = 0, k = 0;
-    while (l < a.n_layers) {
-        const bool fused = l == 0 && a.n_layers >= 2 && a.layers[0].ks == 1 && a.layers[1].ks == 1;
-        const int last_layer = fused ? 1 : l;
-        int32_t *dst = last_layer == a.n_layers - 1 ? a.out : bufs[k & 1];
-        if (fused) {
-            hipLaunchKernelGGL(dec_syn_fused_generic, grid, dim3(kThreads), 0, s, src, cin_of[0], plane, wp[0], bp[0],
-                               a.layers[0].n_out, wp[1], bp[1], a.layers[1].n_out, dst);
-        } else {
-            const SynLayerDesc &L = a.layers[l];
-            hipLaunchKernelGGL(dec_syn_layer, grid, dim3(kThreads), 0, s, src, cin_of[l], a.h, a.w, wp[l], bp[l],
-                               L.n_out, L.ks, L.residual, L.relu, dst);
-        }
-        CCMI_HIP_CHECK(hipGetLastError());
-        src = dst;
-        l = last_layer + 1;
-        ++k;
-    }
-    return CCMI_OK;
-}
-
-int launch_dec_blend(int32_t *acc, const int32_t *x, int64_t n, int32_t b_acc, int32_t b_x, int first, hipStream_t s)
-{
-    hipLaunchKernelGGL(dec_blend_kernel, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, s, acc, x,
-                       n, b_acc, b_x, first);
-    CCMI_HIP_CHECK(hipGetLastError());
-    return CCMI_OK;
-}
-
-int launch_dec_output(const int32_t *syn, int h, int w, int bitdepth, int kind, uint8_t *dst, hipStream_t s)
-{
-    const int64_t plane = (int64_t)h * w;
-    hipLaunchKernelGGL(dec_output_kernel, dim3((unsigned)((plane + kThreads - 1) / kThreads)), dim3(kThreads), 0, s,
-                       syn, h, w, (1 << bitdepth) - 1, kind, bitdepth <= 8 ? 1 : 2, dst);
-    CCMI_HIP_CHECK(hipGetLastError());
-    return CCMI_OK;
-}
-
-int launch_dec_output_tensor(const int32_t *syn, int h, int w, int bitdepth, int kind, int sample, void *dst,
-                             hipStream_t s)
-{
-    if (kind != 0 && kind != 1) return ccmi_set_error(CCMI_ERR_ARG, "dec: tensor output kind %d", kind);
-    const dim3 grid(output_tensor_blocks(h, w, kind));
-    const int maxv = (1 << bitdepth) - 1;
-    switch (sample) {
-    case CCMI_SAMPLE_U8:
-        hipLaunchKernelGGL(dec_output_tensor<uint8_t>, grid, dim3(kThreads), 0, s, syn, h, w, maxv, kind,
-                           static_cast<uint8_t *>(dst));
-        break;
-    case CCMI_SAMPLE_U16:
-        hipLaunchKernelGGL(dec_output_tensor<uint16_t>, grid, dim3(kThreads), 0, s, syn, h, w, maxv, kind,
-                           static_cast<uint16_t *>(dst));
-        break;
-    case CCMI_SAMPLE_F32:
-        hipLaunchKernelGGL(dec_output_tensor<float>, grid, dim3(kThreads), 0, s, syn, h, w, maxv, kind,
-                           static_cast<float *>(dst));
-        break;
-    default: return ccmi_set_error(CCMI_ERR_ARG, "dec: sample type %d", sample);
-    }
-    CCMI_HIP_CHECK(hipGetLastError());
-    return CCMI_OK;
-}
-
-int launch_dec_output_tensor_roi(const int32_t *syn, int h, int w, const DecWindow &rect, int bitdepth, int kind,
-                                 int sample, void *dst, hipStream_t s)
-{
-    if (kind != 0 && kind != 1) return ccmi_set_error(CCMI_ERR_ARG, "dec: tensor output kind %d", kind);
-    if (rect.y0 < 0 || rect.x0 < 0 || rect.y1 > h || rect.x1 > w || rect.h() < 1 || rect.w() < 1)
-        return ccmi_set_error(CCMI_ERR_ARG, "dec: region outside the frame");
-    const dim3 grid(output_tensor_blocks(rect.h(), rect.w(), kind));
-    const int maxv = (1 << bitdepth) - 1;
-    switch (sample) {
-    case CCMI_SAMPLE_U8:
-        hipLaunchKernelGGL(dec_output_tensor_crop<uint8_t>, grid, dim3(kThreads), 0, s, syn, h, w, rect.y0, rect.x0,
-                           rect.h(), rect.w(), maxv, kind, static_cast<uint8_t *>(dst));
-        break;
-    case CCMI_SAMPLE_U16:
-        hipLaunchKernelGGL(dec_output_tensor_crop<uint16_t>, grid, dim3(kThreads), 0, s, syn, h, w, rect.y0, rect.x0,
-                           rect.h(), rect.w(), maxv, kind, static_cast<uint16_t *>(dst));
-        break;
-    case CCMI_SAMPLE_F32:
-        hipLaunchKernelGGL(dec_output_tensor_crop<float>, grid, dim3(kThreads), 0, s, syn, h, w, rect.y0, rect.x0,
-                           rect.h(), rect.w(), maxv, kind, static_cast<float *>(dst));
-        break;
-    default: return ccmi_set_error(CCMI_ERR_ARG, "dec: sample type %d", sample);
-    }
-    CCMI_HIP_CHECK(hipGetLastError());
-    return CCMI_OK;
-}
-
-// ------------------------------------------------------------------ batched decoder tail
-// fused-synthesis kernel arguments of one frame (syn_fast architectures only); the same
-// weight walk as launch_dec_syn
-static DecSynFused make_syn_fused(const DecSynArgs &a)
-{
-    const int32_t *wp[CCMI_MAX_SYN_LAYERS], *bp[CCMI_MAX_SYN_LAYERS];
-    const int32_t *q = a.params;
-    int c = a.c_in;
-    for (int l = 0; l < a.n_layers; ++l) {
-        wp[l] = q;
-        q += (size_t)a.layers[l].n_out * c * a.layers[l].ks * a.layers[l].ks;
-        bp[l] = q;
-        q += a.layers[l].n_out;
-        c = a.layers[l].n_out;
-    }
-    DecSynFused F{};
-    F.in = a.in;
-    F.cin = a.c_in;
-    F.H = a.h;
-    F.W = a.w;
-    F.hid = a.layers[0].n_out;
-    F.w0 = wp[0];
-    F.b0 = bp[0];
-    F.w1 = wp[1];
-    F.b1 = bp[1];
-    F.n_sp = a.n_layers - 2;
-    for (int i = 0; i < F.n_sp; ++i) {
-        F.wsp[i] = wp[2 + i];
-        F.bsp[i] = bp[2 + i];
-        F.res[i] = a.layers[2 + i].residual;
-        F.relu[i] = a.layers[2 + i].relu;
-    }
-    F.out = a.out;
-    F.f24 = a.f24;
-    F.tiles_x = ccmi_div_up(a.w, kRW - 2 * F.n_sp);
-    return F;
-}
-
-bool dec_tail_batchable(const DecTailFrame &f)
-{
-    int cm;
-    return f.ups.n_layers >= 2 && ups_ks_ok(f.ups) && f.syn.c_in == f.ups.n_layers && syn_fast(f.syn, &cm);
-}
-
-// launch geometry only: the grids depend on the plane sizes, the synthesis halo and the
-// synthesis input width (template); everything else is per-frame table data
-bool dec_tail_same_group(const DecTailFrame &a, const DecTailFrame &b)
-{
-    if (a.ups.n_layers != b.ups.n_layers || a.windowed != b.windowed) return false;
-    if (a.windowed) {
-        // region decode: the tables carry each frame's true plane sizes and its windows, the
-        // grids cover the group's largest window; one region size (the output grid), any
-        // frame size, any origin
-        if (a.sample != b.sample || a.kind != b.kind) return false;
-        return a.syn.n_layers == b.syn.n_layers && a.syn.c_in == b.syn.c_in && a.roi.rect.h() == b.roi.rect.h() &&
-               a.roi.rect.w() == b.roi.rect.w();
-    }
-    for (int l = 0; l < a.ups.n_layers; ++l)
-        if (a.ups.lh[l] != b.ups.lh[l] || a.ups.lw[l] != b.ups.lw[l]) return false;
-    // tensor outputs: the output grid is sized by the sample count, i.e. by the chroma format too
-    if (a.sample != b.sample || (a.sample >= 0 && a.kind != b.kind)) return false;
-    return a.syn.n_layers == b.syn.n_layers && a.syn.c_in == b.syn.c_in && a.syn.h == b.syn.h && a.syn.w == b.syn.w;
-}
-
-static size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
-
-// table of a group of n frames: [step][frame] DecLevel, [frame] DecSynFused, [frame] DecOut
-size_t dec_tail_table_bytes(int n_layers, int n, bool windowed)
-{
-    const size_t steps = n_layers > 1 ? (size_t)(n_layers - 1) : 0;
-    if (windowed)
-        return al16(sizeof(DecLevelWin) * steps * n) + al16(sizeof(DecSynFusedWin) * (size_t)n) +
-               al16(sizeof(DecOut) * (size_t)n);
-    return al16(sizeof(DecLevel) * steps * n) + al16(sizeof(DecSynFused) * (size_t)n) + al16(sizeof(DecOut) * (size_t)n);
-}
-
-// the window-form tables: [step][frame] DecLevelWin, [frame] DecSynFusedWin, [frame] DecOut
-static void dec_tail_fill_win(const DecTailFrame *const *fr, int n, void *host_tab)
-{
-    const int steps = fr[0]->ups.n_layers - 1;
-    uint8_t *p = static_cast<uint8_t *>(host_tab);
-    DecLevelWin *lv = reinterpret_cast<DecLevelWin *>(p);
-    DecSynFusedWin *sf = reinterpret_cast<DecSynFusedWin *>(p + al16(sizeof(DecLevelWin) * (size_t)steps * n));
-    DecOut *oo = reinterpret_cast<DecOut *>(reinterpret_cast<uint8_t *>(sf) + al16(sizeof(DecSynFusedWin) * (size_t)n));
-    for (int i = 0; i < n; ++i) {
-        DecLevelWin tmp[CCMI_MAX_GRIDS];
-        make_levels_win(*fr[i], tmp);
-        for (int st = 0; st < steps; ++st) lv[(size_t)st * n + i] = tmp[st];
-        const DecRoi &R = fr[i]->roi;
-        DecSynFusedWin &S = sf[i];
-        S = DecSynFusedWin{};
-        S.F = make_syn_fused(fr[i]->syn);
-        S.iy0 = R.lev[0].y0, S.iy1 = R.lev[0].y1 - 1, S.ix0 = R.lev[0].x0, S.ix1 = R.lev[0].x1 - 1;
-        S.ipitch = R.lev[0].w();
-        S.iplane = (int64_t)R.lev[0].h() * R.lev[0].w();
-        S.ry = R.rect.y0, S.rx = R.rect.x0, S.rh = R.rect.h(), S.rw = R.rect.w();
-        // the synthesis output is the region itself, compact: the whole-frame output kernel
-        // converts it as a frame of the region's size (420: the origin is even, so its even
-        // rows and columns are the frame's)
-        const int bd = fr[i]->bitdepth;
-        oo[i] = DecOut{fr[i]->syn.out, S.rh, S.rw, (1 << bd) - 1, fr[i]->kind, bd <= 8 ? 1 : 2, fr[i]->dst};
-    }
-}
-
-void dec_tail_fill(const DecTailFrame *const *fr, int n, void *host_tab)
-{
-    if (fr[0]->windowed) return dec_tail_fill_win(fr, n, host_tab);
-    const int steps = fr[0]->ups.n_layers - 1;
-    uint8_t *p = static_cast<uint8_t *>(host_tab);
-    DecLevel *lv = reinterpret_cast<DecLevel *>(p);
-    DecSynFused *sf = reinterpret_cast<DecSynFused *>(p + al16(sizeof(DecLevel) * (size_t)steps * n));
-    DecOut *oo = reinterpret_cast<DecOut *>(reinterpret_cast<uint8_t *>(sf) + al16(sizeof(DecSynFused) * (size_t)n));
-    for (int i = 0; i < n; ++i) {
-        DecLevel tmp[CCMI_MAX_GRIDS];
-        make_levels(fr[i]->ups, tmp);
-        for (int st = 0; st < steps; ++st) lv[(size_t)st * n + i] = tmp[st];
-        sf[i] = make_syn_fused(fr[i]->syn);
-        const DecSynArgs &sa = fr[i]->syn;
-        const int bd = fr[i]->bitdepth;
-        oo[i] = DecOut{sa.out, sa.h, sa.w, (1 << bd) - 1, fr[i]->kind, bd <= 8 ? 1 : 2, fr[i]->dst};
-    }
-}
-
-// region decode: one launch per stage for a window-form group (dec_tail_same_group); the
-// grids cover the group's largest window of each level
-static int launch_dec_tail_batch_win(const DecTailFrame *const *fr, int n, const void *dev_tab, hipStream_t s)
-{
-    const DecTailFrame &f0 = *fr[0];
-    const int L = f0.ups.n_layers, steps = L - 1;
-    if (f0.sample < 0) return ccmi_set_error(CCMI_ERR_ARG, "dec: a region decode writes tensors only");
-    const uint8_t *p = static_cast<const uint8_t *>(dev_tab);
-    const DecLevelWin *lv = reinterpret_cast<const DecLevelWin *>(p);
-    const DecSynFusedWin *sf = reinterpret_cast<const DecSynFusedWin *>(p + al16(sizeof(DecLevelWin) * (size_t)steps * n));
-    const DecOut *oo =
-        reinterpret_cast<const DecOut *>(reinterpret_cast<const uint8_t *>(sf) + al16(sizeof(DecSynFusedWin) * (size_t)n));
-    for (int st = 0; st < steps; ++st) {
-        const int k = L - 1 - st;
-        int gtx = 1, gty = 1; // tiles from each window's origin rounded down to even
-        for (int i = 0; i < n; ++i) {
-            const DecWindow &d = fr[i]->roi.lev[k - 1];
-            gtx = std::max(gtx, ccmi_div_up(d.x1 - (d.x0 & ~1), kTX));
-            gty = std::max(gty, ccmi_div_up(d.y1 - (d.y0 & ~1), kTY));
-        }
-        hipLaunchKernelGGL(dec_ups_level_win_batch, dim3(gtx * gty, n), dim3(kThreads), 0, s, lv + (size_t)st * n, gtx);
-        CCMI_HIP_CHECK(hipGetLastError());
-    }
-    const int halo = f0.syn.n_layers - 2;
-    const int rh = f0.roi.rect.h(), rw = f0.roi.rect.w();
-    const int gtx = ccmi_div_up(rw, kRW - 2 * halo);
-    const dim3 sg(gtx * ccmi_div_up(rh, kRH - 2 * halo), n);
-    switch (f0.syn.c_in) {
-    case 1: hipLaunchKernelGGL((dec_syn_fused_win_batch<1, 3>), sg, dim3(kThreads), 0, s, sf, gtx); break;
-    case 2: hipLaunchKernelGGL((dec_syn_fused_win_batch<2, 3>), sg, dim3(kThreads), 0, s, sf, gtx); break;
-    case 3: hipLaunchKernelGGL((dec_syn_fused_win_batch<3, 3>), sg, dim3(kThreads), 0, s, sf, gtx); break;
-    case 4: hipLaunchKernelGGL((dec_syn_fused_win_batch<4, 3>), sg, dim3(kThreads), 0, s, sf, gtx); break;
-    case 5: hipLaunchKernelGGL((dec_syn_fused_win_batch<5, 3>), sg, dim3(kThreads), 0, s, sf, gtx); break;
-    case 6: hipLaunchKernelGGL((dec_syn_fused_win_batch<6, 3>), sg, dim3(kThreads), 0, s, sf, gtx); break;
-    case 7: hipLaunchKernelGGL((dec_syn_fused_win_batch<7, 3>), sg, dim3(kThreads), 0, s, sf, gtx); break;
-    default: hipLaunchKernelGGL((dec_syn_fused_win_batch<8, 3>), sg, dim3(kThreads), 0, s, sf, gtx); break;
-    }
-    CCMI_HIP_CHECK(hipGetLastError());
-    const dim3 grid(output_tensor_blocks(rh, rw, f0.kind), n);
-    switch (f0.sample) {
-    case CCMI_SAMPLE_U8: hipLaunchKernelGGL(dec_output_tensor_batch<uint8_t>, grid, dim3(kThreads), 0, s, oo); break;
-    case CCMI_SAMPLE_U16: hipLaunchKernelGGL(dec_output_tensor_batch<uint16_t>, grid, dim3(kThreads), 0, s, oo); break;
-    case CCMI_SAMPLE_F32: hipLaunchKernelGGL(dec_output_tensor_batch<float>, grid, dim3(kThreads), 0, s, oo); break;
-    default: return ccmi_set_error(CCMI_ERR_ARG, "dec: sample type %d", f0.sample);
-    }
-    CCMI_HIP_CHECK(hipGetLastError());
-    return CCMI_OK;
-}
-
-int launch_dec_tail_batch(const DecTailFrame *const *fr, int n, const void *dev_tab, hipStream_t s)
-{
-    if (n < 1 || n > 65535) return ccmi_set_error(CCMI_ERR_ARG, "dec: tail batch of %d frames", n);
-    if (fr[0]->windowed) return launch_dec_tail_batch_win(fr, n, dev_tab, s);
-    const DecTailFrame &f0 = *fr[0];
-    const int L = f0.ups.n_layers, steps = L - 1;
-    const uint8_t *p = static_cast<const uint8_t *>(dev_tab);
-    const DecLevel *lv = reinterpret_cast<const DecLevel *>(p);
-    const DecSynFused *sf = reinterpret_cast<const DecSynFused *>(p + al16(sizeof(DecLevel) * (size_t)steps * n));
-    const DecOut *oo =
-        reinterpret_cast<const DecOut *>(reinterpret_cast<const uint8_t *>(sf) + al16(sizeof(DecSynFused) * (size_t)n));
-    for (int st = 0; st < steps; ++st) {
-        const int k = L - 1 - st;
-        const int hd = f0.ups.lh[k - 1], wd = f0.ups.lw[k - 1];
-        const dim3 grid(ccmi_div_up(wd, kTX) * ccmi_div_up(hd, kTY), n);
-        hipLaunchKernelGGL(dec_ups_level_batch, grid, dim3(kThreads), 0, s, lv + (size_t)st * n);
-        CCMI_HIP_CHECK(hipGetLastError());
-    }
-    const int halo = f0.syn.n_layers - 2;
-    const dim3 sg(ccmi_div_up(f0.syn.w, kRW - 2 * halo) * ccmi_div_up(f0.syn.h, kRH - 2 * halo), n);
-    switch (f0.syn.c_in) {
-    case 1: hipLaunchKernelGGL((dec_syn_fused_batch<1, 3>), sg, dim3(kThreads), 0, s, sf); break;
-    case 2: hipLaunchKernelGGL((dec_syn_fused_batch<2, 3>), sg, dim3(kThreads), 0, s, sf); break;
-    case 3: hipLaunchKernelGGL((dec_syn_fused_batch<3, 3>), sg, dim3(kThreads), 0, s, sf); break;
-    case 4: hipLaunchKernelGGL((dec_syn_fused_batch<4, 3>), sg, dim3(kThreads), 0, s, sf); break;
-    case 5: hipLaunchKernelGGL((dec_syn_fused_batch<5, 3>), sg, dim3(kThreads), 0, s, sf); break;
-    case 6: hipLaunchKernelGGL((dec_syn_fused_batch<6, 3>), sg, dim3(kThreads), 0, s, sf); break;
-    case 7: hipLaunchKernelGGL((dec_syn_fused_batch<7, 3>), sg, dim3(kThreads), 0, s, sf); break;
-    default: hipLaunchKernelGGL((dec_syn_fused_batch<8, 3>), sg, dim3(kThreads), 0, s, sf); break;
-    }
-    CCMI_HIP_CHECK(hipGetLastError());
-    const int64_t plane = (int64_t)f0.syn.h * f0.syn.w;
-    if (f0.sample < 0) {
-        hipLaunchKernelGGL(dec_output_batch, dim3((unsigned)((plane + kThreads - 1) / kThreads), n), dim3(kThreads), 0,
-                           s, oo);
-    } else {
-        const dim3 grid(output_tensor_blocks(f0.syn.h, f0.syn.w, f0.kind), n); // one kind per group
-
-        switch (f0.sample) {
-        case CCMI_SAMPLE_U8: hipLaunchKernelGGL(dec_output_tensor_batch<uint8_t>, grid, dim3(kThreads), 0, s, oo); break;
-        case CCMI_SAMPLE_U16: hipLaunchKernelGGL(dec_output_tensor_batch<uint16_t>, grid, dim3(kThreads), 0, s, oo); break;
-        case CCMI_SAMPLE_F32: hipLaunchKernelGGL(dec_output_tensor_batch<float>, grid, dim3(kThreads), 0, s, oo); break;
-        default: return ccmi_set_error(CCMI_ERR_ARG, "dec: sample type %d", f0.sample);
-        }
-    }
-    CCMI_HIP_CHECK(hipGetLastError());
-    return CCMI_OK;
 }
 
 } // namespace ccmi

@@ -1,10 +1,11 @@
 // dec_host.cpp -- path B host side: .cool parsing, network weight decoding (CABAC
-// Exp-Golomb, tiny), device memory planning and the decode C-ABI entry points.
+// Exp-Golomb, tiny), the execution of a decode plan (decode_run; the plan itself is
+// dec_plan.cpp) and the decode C-ABI entry points.
 //
 // Reference: cc-bitstream.cpp:58-275 (headers, chunking), cc-frame-decoder.cpp:157-353
 // (read_arm / read_ups / read_syn and the Q_STEP_*_SHIFT tables :28-108), ccdecapi.cpp
 // :673-857 (cc_decode_* driver, output formats).  All latent-layer decoding, upsampling,
-// synthesis and output conversion run on the GPU (dec_kernels.hip).
+// synthesis and output conversion run on the GPU (dec_arm.hip, dec_tail.hip).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -15,7 +16,7 @@
 #include <vector>
 
 #include "ccmi_cabac.h"
-#include "dec_internal.h"
+#include "dec_plan.h"
 
 namespace ccmi {
 
@@ -241,93 +242,11 @@ int parse_and_decode_frame(const uint8_t *bs, size_t n, FrameHost &f)
     return decode_frame_weights(f);
 }
 
-
 } // namespace ccmi
 
 using namespace ccmi;
 
 namespace {
-
-enum OutKind { kYuv420 = 0, kYuv444 = 1, kPpm = 2 };
-
-struct OutFmt {
-    int kind, bitdepth;
-    size_t payload, header;
-    char hdr[48];
-};
-
-int out_format(const FrameHost &f, int out_bitdepth, int out_chroma, int as_yuv, OutFmt &o)
-{
-    o.bitdepth = out_bitdepth ? out_bitdepth : f.bitdepth;
-    const int chroma = out_chroma ? out_chroma : (f.frame_data_type == 1 ? 420 : 444);
-    const size_t bps = o.bitdepth <= 8 ? 1 : 2;
-    const size_t npx = (size_t)f.h * f.w;
-    o.header = 0;
-    if (as_yuv) {
-        if (o.bitdepth != 8 && o.bitdepth != 10)
-            return ccmi_set_error(CCMI_ERR_UNSUPPORTED, "YUV output bitdepth must be 8 or 10 (got %d)", o.bitdepth);
-        o.kind = chroma == 420 ? kYuv420 : kYuv444;
-        o.payload = bps * (o.kind == kYuv420 ? npx + 2 * (size_t)(f.h / 2) * (f.w / 2) : 3 * npx);
-    } else {
-        if (o.bitdepth < 1 || o.bitdepth > 16) return ccmi_set_error(CCMI_ERR_ARG, "PPM bitdepth %d", o.bitdepth);
-        o.kind = kPpm;
-        o.header = (size_t)snprintf(o.hdr, sizeof o.hdr, "P6\n%d %d\n%d\n", f.w, f.h, (1 << o.bitdepth) - 1);
-        o.payload = bps * 3 * npx;
-    }
-    return CCMI_OK;
-}
-
-// Where decode_many leaves the decoded frames.  Host bytes (the default): file layout,
-// staged in the workspace and copied to the caller's host buffers.  Device tensors: the
-// output kernel writes planar samples of type `sample` straight to the caller's device
-// pointers; nothing is staged and nothing is downloaded.
-struct Sink {
-    int sample = -1;             // -1 host bytes, else CCMI_SAMPLE_*
-    void *const *dev = nullptr;  // [n] device pointers (NULL: planning only)
-    ccmi_frame_geom *geom = nullptr; // [n], optional: filled by the header pass
-    const ccmi_rect *roi = nullptr;  // [n], optional (device sinks): the region of each frame to decode
-    ccmi_roi_info *info = nullptr;   // [n], optional: what the region decode does, filled by the header pass
-    bool device() const { return sample >= 0; }
-};
-
-// how a stream's decoder tail runs
-enum TailMode {
-    kTailFrame = 0,  // the whole frame (no region, or one that covers the frame)
-    kTailWindow = 1, // region decode on windows (batched tail, fused synthesis)
-    kTailCrop = 2,   // whole-frame per-frame tail, the region cropped by the output kernel
-};
-
-size_t sample_bytes(int sample) { return sample == CCMI_SAMPLE_U8 ? 1 : sample == CCMI_SAMPLE_U16 ? 2 : 4; }
-
-// output of a device sink: planar 420 / 444 samples, no header; payload = bytes at the caller's pointer
-int tensor_format(const FrameHost &f, int out_bitdepth, int out_chroma, int sample, OutFmt &o, size_t *elems,
-                  const DecWindow *rect = nullptr)
-{
-    if (sample != CCMI_SAMPLE_U8 && sample != CCMI_SAMPLE_U16 && sample != CCMI_SAMPLE_F32)
-        return ccmi_set_error(CCMI_ERR_ARG, "decode: unknown sample type %d", sample);
-    if (out_chroma != 0 && out_chroma != 420 && out_chroma != 444)
-        return ccmi_set_error(CCMI_ERR_ARG, "decode: output chroma format %d (0, 420 or 444)", out_chroma);
-    o.bitdepth = out_bitdepth ? out_bitdepth : f.bitdepth;
-    if (o.bitdepth < 1 || o.bitdepth > 16) return ccmi_set_error(CCMI_ERR_ARG, "decode: output bitdepth %d", o.bitdepth);
-    if (sample == CCMI_SAMPLE_U8 && o.bitdepth > 8)
-        return ccmi_set_error(CCMI_ERR_ARG, "decode: %d-bit samples do not fit CCMI_SAMPLE_U8", o.bitdepth);
-    const int chroma = out_chroma ? out_chroma : (f.frame_data_type == 1 ? 420 : 444);
-    const int oh = rect ? rect->h() : f.h, ow = rect ? rect->w() : f.w;
-    const size_t npx = (size_t)oh * ow;
-    o.kind = chroma == 420 ? kYuv420 : kYuv444;
-    o.header = 0;
-    *elems = o.kind == kYuv420 ? npx + 2 * (size_t)(oh / 2) * (ow / 2) : 3 * npx;
-    o.payload = sample_bytes(sample) * *elems;
-    return CCMI_OK;
-}
-
-size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-struct DevPlan {
-    size_t bytes_off[CCMI_MAX_GRIDS];
-    size_t arm_off, ups_off, syn_off, lat_off, ws_off, dense_off, synout_off, synws_off, out_off;
-    size_t lat_elems, ws_elems, dense_elems, synout_elems, synws_elems;
-};
 
 thread_local float g_last_ms[4] = {0, 0, 0, 0};
 thread_local std::vector<uint32_t> g_last_flags; // per stream: OR of its grids' CCMI_ARM_FLAG_* bits
@@ -382,33 +301,18 @@ bool syn_weights_fit24(const FrameHost &f)
     return true;
 }
 
-// the architecture part of a frame's tail arguments (no device pointers): what
-// dec_tail_batchable() looks at, and the true plane sizes
-void tail_arch(const FrameHost &f, DecTailFrame &t)
+// every ARM weight fits 24 signed bits (ArmStreamDesc::flags bit 0); biases sit between
+// weight blocks, checking them too is conservative
+bool arm_weights_fit24(const FrameHost &f)
 {
-    DecUpsArgs &ua = t.ups;
-    ua = DecUpsArgs{};
-    ua.n_layers = f.n_layers;
-    for (int l = 0; l < f.n_layers; ++l) {
-        ua.lh[l] = f.lh[l];
-        ua.lw[l] = f.lw[l];
-    }
-    ua.ups_ks = f.ups_ks;
-    ua.n_ups = f.n_ups;
-    ua.pre_ks = f.pre_ks;
-    ua.n_pre = f.n_pre;
-    DecSynArgs &sa = t.syn;
-    sa = DecSynArgs{};
-    sa.c_in = f.n_layers;
-    sa.h = f.h;
-    sa.w = f.w;
-    sa.n_layers = (int)f.layers.size();
-    for (int l = 0; l < sa.n_layers; ++l) sa.layers[l] = f.layers[l];
+    for (const int32_t v : f.arm)
+        if (v >= (1 << 23) || v < -(1 << 23)) return false;
+    return true;
 }
 
 // CABAC decode of every frame's network weights: host threads over the frames (each
 // stream's weights are an independent few-hundred-symbol decode, ~50-100 us)
-int decode_weights_all(std::vector<FrameHost> &fr)
+int decode_weights_all(std::vector<FramePlan> &fr)
 {
     const int n = (int)fr.size();
     const int T = n >= 32 ? std::max(1, std::min({8, n / 16, (int)std::thread::hardware_concurrency()})) : 1;
@@ -416,7 +320,7 @@ int decode_weights_all(std::vector<FrameHost> &fr)
     std::vector<std::string> msg(n);
     auto work = [&](int t) {
         for (int i = t; i < n; i += T)
-            if ((rc[i] = decode_frame_weights(fr[i])) != CCMI_OK) msg[i] = ccmi_last_error();
+            if ((rc[i] = decode_frame_weights(fr[i].f)) != CCMI_OK) msg[i] = ccmi_last_error();
     };
     if (T == 1) {
         work(0);
@@ -431,229 +335,99 @@ int decode_weights_all(std::vector<FrameHost> &fr)
     return CCMI_OK;
 }
 
-// ws / ws_bytes: caller-owned device workspace (NULL: one hipMalloc per call); need: when
-// not NULL, only the workspace size is computed (headers parsed, nothing decoded or launched).
-// sink: host bytes at outs[i] (as_yuv picks the file layout), or device tensors at sink.dev[i]
-// (outs NULL, as_yuv unused); caps[i] is the capacity in bytes of either.
-int decode_many(const uint8_t *const *streams, const size_t *lens, int n, uint8_t *const *outs, const size_t *caps,
-                size_t *sizes, int out_bitdepth, int out_chroma, int as_yuv, hipStream_t s,
-                int32_t *const *lat_out = nullptr, void *ws = nullptr, size_t ws_bytes = 0, size_t *need = nullptr,
-                const Sink &sink = Sink())
+// ARM + CABAC streams that share one launch: the non-empty latent grids of a chunk's frames
+// with one (d, nh)
+struct ArmGroup {
+    int chunk, d, nh;
+    std::vector<ArmStreamDesc> streams;
+    size_t first; // index of streams[0] in the uploaded descriptor array
+};
+
+// frames of one chunk and one geometry that share one launch per tail stage
+struct TailGroup {
+    int chunk;
+    std::vector<const DecTailFrame *> frames; // table order
+    size_t off;                               // of the group's table, from DecodePlan::tail_off
+};
+
+// State of one decode_run.  The host vectors are what the asynchronous uploads read.
+struct Run {
+    const DecodeRequest &rq;
+    DecodePlan &pl;
+    hipStream_t s;          // the caller's stream
+    uint8_t *dev = nullptr; // workspace base
+    int spin_cap = 0;
+    int K = 1;              // chunks
+    std::vector<int> chunk_of;
+    std::vector<uint8_t> host; // the constant part
+    std::vector<ArmGroup> arm;
+    std::vector<ArmStreamDesc> descs; // every group's streams, in launch order
+    int max_w = 0, max_blocks = 1;
+    std::vector<TailGroup> tails;
+    std::vector<uint8_t> tab; // the tail groups' tables
+    uint32_t *status() const { return reinterpret_cast<uint32_t *>(dev + pl.status_off); }
+};
+
+// the decoded weights' 24-bit facts, and the host image of the constant part
+void stage_constants(Run &r)
 {
-    g_last_flags.clear(); // a call that fails reports no stream, not the previous call's
-    if (n < 1) return ccmi_set_error(CCMI_ERR_ARG, "decode: no streams");
-    std::vector<FrameHost> fr(n);
-    std::vector<OutFmt> of(n);
-    std::vector<DecTailFrame> tail(n);
-    std::vector<int> mode(n, kTailFrame);
-    for (int i = 0; i < n; ++i) {
-        if (!streams[i]) return ccmi_set_error(CCMI_ERR_ARG, "decode: stream %d is NULL", i);
-        if (int rc = parse_frame_header(streams[i], lens[i], fr[i])) {
-            std::string m = ccmi_last_error();
-            return ccmi_set_error(rc, "stream %d: %s", i, m.c_str());
-        }
-        if (sink.device()) {
-            size_t elems = 0;
-            const FrameHost &f = fr[i];
-            DecWindow rect{0, f.h, 0, f.w};
-            if (sink.roi) {
-                const ccmi_rect &q = sink.roi[i];
-                if (q.w < 1 || q.h < 1 || q.x < 0 || q.y < 0 || q.x > f.w - q.w || q.y > f.h - q.h)
-                    return ccmi_set_error(CCMI_ERR_ARG, "stream %d: region x %d y %d w %d h %d outside the %d x %d frame", i,
-                                          q.x, q.y, q.w, q.h, f.w, f.h);
-                rect = DecWindow{q.y, q.y + q.h, q.x, q.x + q.w};
-            }
-            if (int rc = tensor_format(f, out_bitdepth, out_chroma, sink.sample, of[i], &elems, &rect)) return rc;
-            if (of[i].kind == kYuv420 && ((rect.x0 | rect.y0) & 1))
-                return ccmi_set_error(CCMI_ERR_ARG, "stream %d: a 420 region needs an even origin (x %d y %d)", i, rect.x0,
-                                      rect.y0);
-            tail_arch(f, tail[i]);
-            int halo = 0;
-            for (const SynLayerDesc &L : f.layers) halo += (L.ks - 1) / 2;
-            DecRoi &R = tail[i].roi;
-            if (rect.h() == f.h && rect.w() == f.w) {
-                mode[i] = kTailFrame;
-            } else if (f.n_branches == 1 && dec_tail_batchable(tail[i])) {
-                mode[i] = kTailWindow;
-                dec_roi_plan(f.lh, f.lw, f.n_layers, f.ups_ks, f.pre_ks, halo, rect, R);
-            } else {
-                mode[i] = kTailCrop;
-            }
-            if (mode[i] != kTailWindow) { // the whole frame is decoded
-                dec_roi_plan(f.lh, f.lw, f.n_layers, f.ups_ks, f.pre_ks, halo, DecWindow{0, f.h, 0, f.w}, R);
-                R.rect = rect;
-            }
-            tail[i].windowed = mode[i] == kTailWindow;
-            if (sink.geom)
-                sink.geom[i] = ccmi_frame_geom{rect.w(), rect.h(), of[i].bitdepth, of[i].kind == kYuv420 ? 420 : 444,
-                                               f.frame_data_type, elems};
-            if (sink.info) {
-                ccmi_roi_info &I = sink.info[i];
-                I = ccmi_roi_info{};
-                I.n_grids = f.n_layers;
-                for (int l = 0; l < f.n_layers; ++l) I.arm_rows[l] = R.arm_rows[l];
-                I.windowed = f.n_branches == 1 && dec_tail_batchable(tail[i]) ? 1 : 0;
-            }
-            if (sink.dev) {
-                if (!sink.dev[i]) return ccmi_set_error(CCMI_ERR_ARG, "decode: output %d is NULL", i);
-                if (reinterpret_cast<uintptr_t>(sink.dev[i]) % sample_bytes(sink.sample))
-                    return ccmi_set_error(CCMI_ERR_ARG, "decode: output %d is not aligned to its %zu-byte samples", i,
-                                          sample_bytes(sink.sample));
-            }
-        } else {
-            if (int rc = out_format(fr[i], out_bitdepth, out_chroma, as_yuv, of[i])) return rc;
-            for (int l = 0; l < fr[i].n_layers; ++l) tail[i].roi.arm_rows[l] = fr[i].lh[l];
-        }
-        if ((outs || sink.dev) && caps && caps[i] < of[i].header + of[i].payload)
-            return ccmi_set_error(CCMI_ERR_ARG, "stream %d: output buffer of %zu bytes, need %zu", i, caps[i],
-                                  of[i].header + of[i].payload);
-        if (sizes) sizes[i] = of[i].header + of[i].payload;
-    }
-
-    // ---- plan one device allocation: constant part (bytes + weights, uploaded) then scratch
-    std::vector<DevPlan> pl(n);
-    size_t cst = 0;
-    for (int i = 0; i < n; ++i) {
-        FrameHost &f = fr[i];
-        DevPlan &p = pl[i];
-        for (int l = 0; l < f.n_layers; ++l) {
-            p.bytes_off[l] = cst;
-            cst += align_up(f.lat_n[l] + 64, 256);
-        }
-        p.arm_off = cst;
-        cst += align_up(f.arm.size() * 4, 256);
-        p.ups_off = cst;
-        cst += align_up(f.ups.size() * 4, 256);
-        p.syn_off = cst;
-        cst += align_up(f.syn.size() * 4, 256);
-    }
-    size_t tot = align_up(cst, 4096);
-    for (int i = 0; i < n; ++i) {
-        FrameHost &f = fr[i];
-        DevPlan &p = pl[i];
-        // a region decode on windows: the latent planes keep their frame pitch and hold the rows
-        // the ARM decode produces, the pyramid stacks and the synthesis output hold the windows
-        const DecRoi &R = tail[i].roi;
-        const bool win = mode[i] == kTailWindow;
-        p.lat_elems = 0;
-        for (int l = 0; l < f.n_layers; ++l) p.lat_elems += (size_t)R.arm_rows[l] * f.lw[l];
-        p.ws_elems = win ? dec_ups_workspace_elems_win(R, f.n_layers) : dec_ups_workspace_elems(f.lh, f.lw, f.n_layers);
-        p.dense_elems = win ? (size_t)f.n_layers * R.lev[0].h() * R.lev[0].w() : (size_t)f.n_layers * f.h * f.w;
-        p.synout_elems = win ? (size_t)f.layers.back().n_out * R.rect.h() * R.rect.w()
-                             : (size_t)f.layers.back().n_out * f.h * f.w * f.n_branches;
-        DecSynArgs sa{};
-        sa.c_in = f.n_layers;
-        sa.h = f.h;
-        sa.w = f.w;
-        sa.n_layers = (int)f.layers.size();
-        for (int l = 0; l < sa.n_layers; ++l) sa.layers[l] = f.layers[l];
-        p.synws_elems = dec_syn_workspace_elems(sa);
-        p.lat_off = tot;
-        tot += align_up(p.lat_elems * 4, 256);
-        p.ws_off = tot;
-        tot += align_up(p.ws_elems * 4 + 4, 256);
-        p.dense_off = tot;
-        tot += align_up(p.dense_elems * 4, 256);
-        p.synout_off = tot;
-        tot += align_up(p.synout_elems * 4, 256);
-        p.synws_off = tot;
-        tot += align_up(p.synws_elems * 4 + 4, 256);
-        p.out_off = tot;
-        if (!sink.device()) tot += align_up(of[i].payload, 256); // device sinks write to the caller's memory
-    }
-    const size_t desc_off = tot;
-    tot += align_up(sizeof(ArmStreamDesc) * (size_t)n * CCMI_MAX_GRIDS, 256);
-    // batched-tail argument tables: bounded by one single-frame table per frame
-    size_t tail_cap = 0;
-    for (int i = 0; i < n; ++i) tail_cap += dec_tail_table_bytes(fr[i].n_layers, 1, mode[i] == kTailWindow);
-    const size_t tail_off = tot;
-    tot += align_up(tail_cap, 256);
-    // one status word per (frame, latent grid) for the ARM kernels' CCMI_ARM_FLAG_* bits
-    const size_t status_off = tot;
-    const size_t n_status = (size_t)n * CCMI_MAX_GRIDS;
-    tot += align_up(4 * n_status, 256);
-#if defined(CCMI_ARM_STAMPS)
-    const size_t dbg_off = tot;
-    tot += align_up(16 * 8 * (size_t)n * CCMI_MAX_GRIDS, 256);
-    size_t all_count = 0;
-#endif
-
-    if (need) {
-        *need = tot;
-        return CCMI_OK;
-    }
-    if (int rc = decode_weights_all(fr)) return rc;
-    std::vector<uint8_t> host(cst, 0);
-    for (int i = 0; i < n; ++i) {
-        FrameHost &f = fr[i];
-        DevPlan &p = pl[i];
+    r.host.assign(r.pl.cst, 0);
+    for (FramePlan &p : r.pl.fr) {
+        const FrameHost &f = p.f;
+        p.arm24 = arm_weights_fit24(f);
+        p.tail.syn.f24 = syn_weights_fit24(f) ? 1 : 0;
         for (int l = 0; l < f.n_layers; ++l)
-            if (f.lat_n[l]) memcpy(&host[p.bytes_off[l]], f.lat_bytes[l], f.lat_n[l]);
-        memcpy(&host[p.arm_off], f.arm.data(), f.arm.size() * 4);
-        memcpy(&host[p.ups_off], f.ups.data(), f.ups.size() * 4);
-        memcpy(&host[p.syn_off], f.syn.data(), f.syn.size() * 4);
+            if (f.lat_n[l]) memcpy(&r.host[p.bytes_off[l]], f.lat_bytes[l], f.lat_n[l]);
+        memcpy(&r.host[p.arm_off], f.arm.data(), f.arm.size() * 4);
+        memcpy(&r.host[p.ups_off], f.ups.data(), f.ups.size() * 4);
+        memcpy(&r.host[p.syn_off], f.syn.data(), f.syn.size() * 4);
     }
+}
 
-    uint8_t *dev = static_cast<uint8_t *>(ws);
-    if (dev) {
-        if (ws_bytes < tot) return ccmi_set_error(CCMI_ERR_ARG, "decode: workspace of %zu bytes, need %zu", ws_bytes, tot);
-        if (reinterpret_cast<uintptr_t>(dev) % 256)
-            return ccmi_set_error(CCMI_ERR_ARG, "decode: workspace must be 256-byte aligned");
-    } else {
-        CCMI_HIP_CHECK(hipMalloc(&dev, tot));
-    }
-    struct Free {
-        uint8_t *p;
-        ~Free() { if (p) (void)hipFree(p); }
-    } guard{ws ? nullptr : dev};
-    EventSet ev;
-    ev.rec(0, s);
-    CCMI_HIP_CHECK(hipMemcpyAsync(dev, host.data(), cst, hipMemcpyHostToDevice, s));
-    uint32_t *status = reinterpret_cast<uint32_t *>(dev + status_off);
-    CCMI_HIP_CHECK(hipMemsetAsync(status, 0, 4 * n_status, s));
-    const int spin_cap = arm_spin_cap();
-
-    // ---- frames in K chunks by decode cost (coded bytes of their latent layers), cheapest
-    // first.  Each chunk's ARM launch and decoder tail run on a stream of their own, so the
-    // tails of the early chunks overlap the long ARM chains of the later ones: a batch's ARM
-    // stage is the slowest layer-0 chain, and most CUs sit idle once the short streams are done.
-    // K = 2: the caller's stream and one more (GPU_MAX_HW_QUEUES is 4 per process; streams
-    // beyond the hardware queues share one and serialise)
+// Frames in K chunks by decode cost (coded bytes of their latent layers), cheapest first.
+// Each chunk's ARM launch and decoder tail run on a stream of their own, so the tails of the
+// early chunks overlap the long ARM chains of the later ones: a batch's ARM stage is the
+// slowest layer-0 chain, and most CUs sit idle once the short streams are done.
+// K = 2: the caller's stream and one more (GPU_MAX_HW_QUEUES is 4 per process; streams
+// beyond the hardware queues share one and serialise)
 #ifndef CCMI_DEC_CHUNKS
 #define CCMI_DEC_CHUNKS 2
 #endif
-    const int K = n >= 64 ? CCMI_DEC_CHUNKS : 1;
-    std::vector<int> chunk_of(n, 0);
-    if (K > 1) {
-        std::vector<int> order(n);
-        std::vector<size_t> cost(n, 0);
-        for (int i = 0; i < n; ++i) {
-            order[i] = i;
-            for (int l = 0; l < fr[i].n_layers; ++l) cost[i] += fr[i].lat_n[l];
-        }
-        std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cost[a] < cost[b]; });
-        for (int r = 0; r < n; ++r) chunk_of[order[r]] = (int)((int64_t)r * K / n);
-    }
-
-    // ---- ARM + CABAC: every non-empty latent layer of every frame, one launch per (chunk, d, nh)
-    std::vector<ArmStreamDesc> desc;
-    struct Key { int chunk, d, nh; };
-    std::vector<std::pair<Key, std::vector<ArmStreamDesc>>> groups;
-    int max_w = 0, max_blocks = 1;
+void assign_chunks(Run &r)
+{
+    const std::vector<FramePlan> &fr = r.pl.fr;
+    const int n = (int)fr.size();
+    r.K = n >= 64 ? CCMI_DEC_CHUNKS : 1;
+    r.chunk_of.assign(n, 0);
+    if (r.K == 1) return;
+    std::vector<int> order(n);
+    std::vector<size_t> cost(n, 0);
     for (int i = 0; i < n; ++i) {
-        FrameHost &f = fr[i];
-        DevPlan &p = pl[i];
-        int32_t *lat = reinterpret_cast<int32_t *>(dev + p.lat_off);
+        order[i] = i;
+        for (int l = 0; l < fr[i].f.n_layers; ++l) cost[i] += fr[i].f.lat_n[l];
+    }
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return cost[a] < cost[b]; });
+    for (int k = 0; k < n; ++k) r.chunk_of[order[k]] = (int)((int64_t)k * r.K / n);
+}
+
+// ARM + CABAC: every non-empty latent layer of every frame, one launch per (chunk, d, nh);
+// zero layers are cleared here.  Uploads the descriptors in launch order.
+int build_arm_groups(Run &r)
+{
+    for (size_t i = 0; i < r.pl.fr.size(); ++i) {
+        const FramePlan &p = r.pl.fr[i];
+        const FrameHost &f = p.f;
+        int32_t *lat = reinterpret_cast<int32_t *>(r.dev + p.lat_off);
         for (int l = 0; l < f.n_layers; ++l) {
             int32_t *plane = lat;
-            const int rows = tail[i].roi.arm_rows[l]; // == lh[l] unless a region decode stops early
+            const int rows = p.tail.roi.arm_rows[l]; // == lh[l] unless a region decode stops early
             lat += (size_t)rows * f.lw[l];
             if (f.lat_n[l] == 0) { // zero layer (cc-frame-decoder.cpp:479-484)
-                CCMI_HIP_CHECK(hipMemsetAsync(plane, 0, (size_t)rows * f.lw[l] * 4, s));
+                CCMI_HIP_CHECK(hipMemsetAsync(plane, 0, (size_t)rows * f.lw[l] * 4, r.s));
                 continue;
             }
             ArmStreamDesc a{};
-            a.bytes = reinterpret_cast<const uint32_t *>(dev + p.bytes_off[l]);
+            a.bytes = reinterpret_cast<const uint32_t *>(r.dev + p.bytes_off[l]);
             a.nbytes = f.lat_n[l];
             a.h = f.lh[l];
             a.rows = rows;
@@ -661,218 +435,226 @@ int decode_many(const uint8_t *const *streams, const size_t *lens, int n, uint8_
             a.sig_blk = f.sig_blk;
             a.d = f.dim_arm;
             a.nh = f.n_hidden;
-            a.weights = reinterpret_cast<const int32_t *>(dev + p.arm_off);
-            a.flags = 1;
+            a.weights = reinterpret_cast<const int32_t *>(r.dev + p.arm_off);
+            a.flags = p.arm24 ? 1 : 0;
             a.dbg = nullptr;
-            a.status = status + (size_t)i * CCMI_MAX_GRIDS + l;
-            a.spin_cap = spin_cap;
+            a.status = r.status() + i * CCMI_MAX_GRIDS + l;
+            a.spin_cap = r.spin_cap;
 #if defined(CCMI_ARM_STAMPS)
-            a.dbg = reinterpret_cast<uint64_t *>(dev + dbg_off) + 16 * (desc.size() + all_count++);
+            size_t made = 0;
+            for (const ArmGroup &g : r.arm) made += g.streams.size();
+            a.dbg = reinterpret_cast<uint64_t *>(r.dev + r.pl.dbg_off) + 16 * made;
 #endif
-            for (size_t k = 0; k < f.arm.size(); ++k) {
-                // biases sit between weight blocks; checking them too is conservative
-                if (f.arm[k] >= (1 << 23) || f.arm[k] < -(1 << 23)) a.flags = 0;
-            }
             a.out = plane;
-            max_w = std::max(max_w, a.w);
+            r.max_w = std::max(r.max_w, a.w);
             const int blk = std::abs(a.sig_blk);
             if (blk > 0) {
                 int sh = 0;
                 while ((1 << sh) < blk) ++sh;
-                max_blocks = std::max(max_blocks, ((a.h + blk - 1) >> sh) * ((a.w + blk - 1) >> sh));
+                r.max_blocks = std::max(r.max_blocks, ((a.h + blk - 1) >> sh) * ((a.w + blk - 1) >> sh));
             }
-            auto it = std::find_if(groups.begin(), groups.end(), [&](auto &g) {
-                return g.first.chunk == chunk_of[i] && g.first.d == a.d && g.first.nh == a.nh;
-            });
-            if (it == groups.end()) {
-                groups.push_back({Key{chunk_of[i], a.d, a.nh}, {}});
-                it = groups.end() - 1;
+            const int c = r.chunk_of[i];
+            auto it = std::find_if(r.arm.begin(), r.arm.end(),
+                                   [&](const ArmGroup &g) { return g.chunk == c && g.d == a.d && g.nh == a.nh; });
+            if (it == r.arm.end()) {
+                r.arm.push_back(ArmGroup{c, a.d, a.nh, {}, 0});
+                it = r.arm.end() - 1;
             }
-            it->second.push_back(a);
+            it->streams.push_back(a);
         }
     }
-
-    std::vector<ArmStreamDesc> all;
-    std::stable_sort(groups.begin(), groups.end(), [](const auto &x, const auto &y) { return x.first.chunk < y.first.chunk; });
-    for (auto &g : groups) {
+    std::stable_sort(r.arm.begin(), r.arm.end(), [](const ArmGroup &x, const ArmGroup &y) { return x.chunk < y.chunk; });
+    for (ArmGroup &g : r.arm) {
         // longest streams first: they bound the launch
-        std::stable_sort(g.second.begin(), g.second.end(),
+        std::stable_sort(g.streams.begin(), g.streams.end(),
                          [](const ArmStreamDesc &x, const ArmStreamDesc &y) { return x.rows * x.w > y.rows * y.w; });
-        all.insert(all.end(), g.second.begin(), g.second.end());
+        g.first = r.descs.size();
+        r.descs.insert(r.descs.end(), g.streams.begin(), g.streams.end());
     }
-    if (!all.empty())
-        CCMI_HIP_CHECK(hipMemcpyAsync(dev + desc_off, all.data(), all.size() * sizeof(ArmStreamDesc),
-                                      hipMemcpyHostToDevice, s));
+    if (!r.descs.empty())
+        CCMI_HIP_CHECK(hipMemcpyAsync(r.dev + r.pl.desc_off, r.descs.data(), r.descs.size() * sizeof(ArmStreamDesc),
+                                      hipMemcpyHostToDevice, r.s));
+    return CCMI_OK;
+}
 
-    // ---- decoder tail arguments; frames of one geometry with a fused synthesis (single
-    // branch) share one launch per stage
-    for (int i = 0; i < n; ++i) {
-        FrameHost &f = fr[i];
-        DevPlan &p = pl[i];
-        DecTailFrame &t = tail[i];
-        tail_arch(f, t);
-        DecUpsArgs &ua = t.ups;
-        ua.lat = reinterpret_cast<const int32_t *>(dev + p.lat_off);
-        int off = 0;
-        for (int l = 0; l < f.n_layers; ++l) {
-            ua.off[l] = off;
-            off += t.roi.arm_rows[l] * f.lw[l];
-        }
-        ua.kernels = reinterpret_cast<const int32_t *>(dev + p.ups_off);
-        ua.workspace = reinterpret_cast<int32_t *>(dev + p.ws_off);
-        ua.out = reinterpret_cast<int32_t *>(dev + p.dense_off);
-        DecSynArgs &sa = t.syn;
-        sa.in = ua.out;
-        sa.params = reinterpret_cast<const int32_t *>(dev + p.syn_off);
-        sa.out = reinterpret_cast<int32_t *>(dev + p.synout_off);
-        sa.workspace = reinterpret_cast<int32_t *>(dev + p.synws_off);
-        sa.f24 = syn_weights_fit24(f) ? 1 : 0;
-        t.bitdepth = of[i].bitdepth;
-        t.kind = of[i].kind;
-        t.dst = sink.device() ? static_cast<uint8_t *>(sink.dev[i]) : dev + p.out_off;
-        t.sample = sink.sample;
-    }
-    // frames of one geometry share one launch per tail stage (960 class-E frames: 134 ms
-    // against 264 ms with per-frame launches)
-    std::vector<std::vector<int>> tgroups;
-    std::vector<char> batched(n, 0);
-    for (int i = 0; i < n; ++i) {
-        if (fr[i].n_branches != 1 || !dec_tail_batchable(tail[i])) continue;
-        auto it = std::find_if(tgroups.begin(), tgroups.end(), [&](const std::vector<int> &g) {
-            return g.size() < 65535 && chunk_of[g[0]] == chunk_of[i] && dec_tail_same_group(tail[g[0]], tail[i]);
+// Decoder tail: every frame's device pointers; frames of one geometry with a fused synthesis
+// (single branch) share one launch per stage (960 class-E frames: 134 ms against 264 ms with
+// per-frame launches).  Fills and uploads the groups' argument tables.
+int build_tail_groups(Run &r)
+{
+    for (size_t i = 0; i < r.pl.fr.size(); ++i) {
+        FramePlan &p = r.pl.fr[i];
+        DecTailFrame &t = p.tail;
+        t.ups.lat = reinterpret_cast<const int32_t *>(r.dev + p.lat_off);
+        t.ups.kernels = reinterpret_cast<const int32_t *>(r.dev + p.ups_off);
+        t.ups.workspace = reinterpret_cast<int32_t *>(r.dev + p.ws_off);
+        t.ups.out = reinterpret_cast<int32_t *>(r.dev + p.dense_off);
+        t.syn.in = t.ups.out;
+        t.syn.params = reinterpret_cast<const int32_t *>(r.dev + p.syn_off);
+        t.syn.out = reinterpret_cast<int32_t *>(r.dev + p.synout_off);
+        t.syn.workspace = reinterpret_cast<int32_t *>(r.dev + p.synws_off);
+        t.dst = r.rq.device() ? static_cast<uint8_t *>(r.rq.dev[i]) : r.dev + p.out_off;
+        if (!p.batchable) continue;
+        const int c = r.chunk_of[i];
+        auto it = std::find_if(r.tails.begin(), r.tails.end(), [&](const TailGroup &g) {
+            return g.frames.size() < 65535 && g.chunk == c && dec_tail_same_group(*g.frames[0], t);
         });
-        if (it == tgroups.end()) {
-            tgroups.emplace_back();
-            it = tgroups.end() - 1;
+        if (it == r.tails.end()) {
+            r.tails.push_back(TailGroup{c, {}, 0});
+            it = r.tails.end() - 1;
         }
-        it->push_back(i);
-        batched[i] = 1;
+        it->frames.push_back(&t);
     }
-    std::vector<size_t> tg_off(tgroups.size());
-    std::vector<std::vector<const DecTailFrame *>> tg_ptr;
-    std::vector<uint8_t> tab(tail_cap > 0 ? tail_cap : 1);
+    r.tab.resize(r.pl.tail_cap > 0 ? r.pl.tail_cap : 1);
     size_t tpos = 0;
-    for (size_t g = 0; g < tgroups.size(); ++g) {
-        std::vector<const DecTailFrame *> ptr;
-        for (int i : tgroups[g]) ptr.push_back(&tail[i]);
-        tg_off[g] = tpos;
-        dec_tail_fill(ptr.data(), (int)ptr.size(), tab.data() + tpos);
-        tpos += dec_tail_table_bytes(tail[tgroups[g][0]].ups.n_layers, (int)ptr.size(), tail[tgroups[g][0]].windowed);
-        tg_ptr.push_back(std::move(ptr));
+    for (TailGroup &g : r.tails) {
+        const int m = (int)g.frames.size();
+        g.off = tpos;
+        dec_tail_fill(g.frames.data(), m, r.tab.data() + tpos);
+        tpos += dec_tail_table_bytes(g.frames[0]->ups.n_layers, m, g.frames[0]->windowed);
     }
-    if (tpos) CCMI_HIP_CHECK(hipMemcpyAsync(dev + tail_off, tab.data(), tpos, hipMemcpyHostToDevice, s));
-    ev.rec(1, s);
-    // one chunk's ARM launches, then its decoder tail (batched groups, then the rest per frame)
-    auto launch_chunk = [&](int c, hipStream_t cs, hipEvent_t arm_done) -> int {
-        size_t dp = 0;
-        for (auto &g : groups) {
-            if (g.first.chunk == c) {
-                const ArmStreamDesc *dd = reinterpret_cast<const ArmStreamDesc *>(dev + desc_off) + dp;
-                if (int rc = launch_dec_arm(dd, (int)g.second.size(), max_w, max_blocks, g.first.d, g.first.nh, cs))
-                    return rc;
-            }
-            dp += g.second.size();
-        }
-        if (arm_done) CCMI_HIP_CHECK(hipEventRecord(arm_done, cs));
-        for (size_t g = 0; g < tgroups.size(); ++g)
-            if (chunk_of[tgroups[g][0]] == c)
-                if (int rc = launch_dec_tail_batch(tg_ptr[g].data(), (int)tgroups[g].size(), dev + tail_off + tg_off[g], cs))
-                    return rc;
-        for (int i = 0; i < n; ++i) {
-            if (batched[i] || chunk_of[i] != c) continue;
-            FrameHost &f = fr[i];
-            DevPlan &p = pl[i];
-            if (int rc = launch_dec_ups(tail[i].ups, cs)) return rc;
+    if (tpos) CCMI_HIP_CHECK(hipMemcpyAsync(r.dev + r.pl.tail_off, r.tab.data(), tpos, hipMemcpyHostToDevice, r.s));
+    return CCMI_OK;
+}
 
-            const int nout = f.layers.back().n_out;
-            const int64_t plane = (int64_t)f.h * f.w;
-            size_t per_branch = f.syn.size() / f.n_branches;
-            int32_t *synout = reinterpret_cast<int32_t *>(dev + p.synout_off);
-            for (int b = 0; b < f.n_branches; ++b) {
-                DecSynArgs sa = tail[i].syn;
-                sa.params += per_branch * b;
-                sa.out = synout + (size_t)b * nout * plane;
-                if (int rc = launch_dec_syn(sa, cs)) return rc;
-                if (b >= 1) // run_syn (cc-frame-decoder.cpp:1044-1149): blends on 3 planes
-                    if (int rc = launch_dec_blend(synout, synout + (size_t)b * nout * plane, 3 * plane,
-                                                  f.blend[0], f.blend[b], b == 1, cs))
-                        return rc;
-            }
-            if (int rc = mode[i] == kTailCrop
-                             ? launch_dec_output_tensor_roi(synout, f.h, f.w, tail[i].roi.rect, of[i].bitdepth, of[i].kind,
-                                                            sink.sample, tail[i].dst, cs)
-                         : sink.device() ? launch_dec_output_tensor(synout, f.h, f.w, of[i].bitdepth, of[i].kind,
-                                                                    sink.sample, tail[i].dst, cs)
-                                         : launch_dec_output(synout, f.h, f.w, of[i].bitdepth, of[i].kind, tail[i].dst, cs))
+// the per-frame tail of a frame the batched tail does not take: pyramid, synthesis per
+// branch with the blend, output
+int launch_frame_tail(const Run &r, const FramePlan &p, hipStream_t cs)
+{
+    const FrameHost &f = p.f;
+    const DecTailFrame &t = p.tail;
+    if (int rc = launch_dec_ups(t.ups, cs)) return rc;
+    const int nout = f.layers.back().n_out;
+    const int64_t plane = (int64_t)f.h * f.w;
+    const size_t per_branch = f.syn.size() / f.n_branches;
+    int32_t *synout = t.syn.out;
+    for (int b = 0; b < f.n_branches; ++b) {
+        DecSynArgs sa = t.syn;
+        sa.params += per_branch * b;
+        sa.out = synout + (size_t)b * nout * plane;
+        if (int rc = launch_dec_syn(sa, cs)) return rc;
+        if (b >= 1) // run_syn (cc-frame-decoder.cpp:1044-1149): blends on 3 planes
+            if (int rc = launch_dec_blend(synout, synout + (size_t)b * nout * plane, 3 * plane, f.blend[0], f.blend[b],
+                                          b == 1, cs))
                 return rc;
-        }
-        return CCMI_OK;
-    };
-    // the decoded bytes of chunk c: headers on the host, payloads copied back on the chunk's
-    // own stream right after its tail, so one chunk's download overlaps the other chunk's
-    // ARM chains (pinned output buffers make these real DMA copies; pageable ones are staged
-    // by the runtime).  A device sink has nothing to download: its frames are where they belong.
-    auto download_chunk = [&](int c, hipStream_t cs) -> int {
-        for (int i = 0; i < n && outs && !sink.device(); ++i) {
-            if (chunk_of[i] != c) continue;
-            if (of[i].header) memcpy(outs[i], of[i].hdr, of[i].header);
-            CCMI_HIP_CHECK(hipMemcpyAsync(outs[i] + of[i].header, dev + pl[i].out_off, of[i].payload,
-                                          hipMemcpyDeviceToHost, cs));
-        }
-        return CCMI_OK;
-    };
-    // K > 1: streams forked from s after the uploads; each chunk runs ARM -> tail -> download on
-    // its stream, and s waits for every chunk before it returns.  The extra streams and the
-    // events are leased from the process-wide pool (ccmi_api.cpp) for this call: st[c] for
-    // chunks c >= 1 (chunk 0 runs on s), ev[0] fork; per chunk c: [1 + 4c] start, [2 + 4c] ARM
-    // done, [3 + 4c] tail done, [4 + 4c] done.
-    StreamSetLease lease;
-    if (K == 1) {
-        if (int rc = launch_chunk(0, s, ev.ok ? ev.e[2] : nullptr)) return rc;
-        ev.rec(3, s);
-        if (int rc = download_chunk(0, s)) return rc;
-    } else {
-        lease.set = ccmi_streamset_acquire(K, 1 + 4 * K, true);
-        if (!lease.set) return CCMI_ERR_HIP;
-        StreamSet &fk = *lease.set;
-        // an error after some chunks were queued: s still waits for them before the caller can
-        // reuse or free the workspace (the chunks' own streams never outlive it unjoined)
-        int started = 0;
-        auto join = [&]() {
-            for (int c = K - 1; c > K - 1 - started && c >= 1; --c) {
-                (void)hipEventRecord(fk.ev[4 + 4 * c], fk.st[c]);
-                (void)hipStreamWaitEvent(s, fk.ev[4 + 4 * c], 0);
-            }
-        };
-        CCMI_HIP_CHECK(hipEventRecord(fk.ev[0], s));
-        for (int c = K - 1; c >= 0; --c) { // the most expensive chunk first
-            hipStream_t cs = c == 0 ? s : fk.st[c];
-            if (c > 0) {
-                if (hipStreamWaitEvent(cs, fk.ev[0], 0) != hipSuccess) {
-                    join();
-                    return ccmi_set_error(CCMI_ERR_HIP, "decode: stream fork failed");
-                }
-                ++started;
-            }
-            (void)hipEventRecord(fk.ev[1 + 4 * c], cs);
-            int rc = launch_chunk(c, cs, fk.ev[2 + 4 * c]);
-            if (!rc) {
-                (void)hipEventRecord(fk.ev[3 + 4 * c], cs);
-                rc = download_chunk(c, cs);
-            }
-            if (rc) {
-                join();
-                return rc;
-            }
-        }
-        join();
     }
-    ev.rec(4, s);
+    if (p.mode == kTailCrop)
+        return launch_dec_output_tensor_roi(synout, f.h, f.w, t.roi.rect, t.bitdepth, t.kind, t.sample, t.dst, cs);
+    if (r.rq.device()) return launch_dec_output_tensor(synout, f.h, f.w, t.bitdepth, t.kind, t.sample, t.dst, cs);
+    return launch_dec_output(synout, f.h, f.w, t.bitdepth, t.kind, t.dst, cs);
+}
+
+// one chunk's ARM launches, then its decoder tail (batched groups, then the rest per frame)
+int launch_chunk(const Run &r, int c, hipStream_t cs, hipEvent_t arm_done)
+{
+    const ArmStreamDesc *descs = reinterpret_cast<const ArmStreamDesc *>(r.dev + r.pl.desc_off);
+    for (const ArmGroup &g : r.arm)
+        if (g.chunk == c)
+            if (int rc = launch_dec_arm(descs + g.first, (int)g.streams.size(), r.max_w, r.max_blocks, g.d, g.nh, cs))
+                return rc;
+    if (arm_done) CCMI_HIP_CHECK(hipEventRecord(arm_done, cs));
+    for (const TailGroup &g : r.tails)
+        if (g.chunk == c)
+            if (int rc = launch_dec_tail_batch(g.frames.data(), (int)g.frames.size(), r.dev + r.pl.tail_off + g.off, cs))
+                return rc;
+    for (size_t i = 0; i < r.pl.fr.size(); ++i)
+        if (!r.pl.fr[i].batchable && r.chunk_of[i] == c)
+            if (int rc = launch_frame_tail(r, r.pl.fr[i], cs)) return rc;
+    return CCMI_OK;
+}
+
+// The decoded bytes of chunk c: headers on the host, payloads copied back on the chunk's
+// own stream right after its tail, so one chunk's download overlaps the other chunk's
+// ARM chains (pinned output buffers make these real DMA copies; pageable ones are staged
+// by the runtime).  A device sink has nothing to download: its frames are where they belong.
+int download_chunk(const Run &r, int c, hipStream_t cs)
+{
+    if (!r.rq.outs || r.rq.device()) return CCMI_OK;
+    for (size_t i = 0; i < r.pl.fr.size(); ++i) {
+        if (r.chunk_of[i] != c) continue;
+        const FramePlan &p = r.pl.fr[i];
+        if (p.of.header) memcpy(r.rq.outs[i], p.of.hdr, p.of.header);
+        CCMI_HIP_CHECK(hipMemcpyAsync(r.rq.outs[i] + p.of.header, r.dev + p.out_off, p.of.payload, hipMemcpyDeviceToHost, cs));
+    }
+    return CCMI_OK;
+}
+
+// A chunk's events: its start (recorded here only when the chunk streams were forked), ARM
+// done, tail done, and done (what the caller's stream waits for, chunks >= 1).  One chunk:
+// the call's own events, on the caller's stream between [1] uploads done and [4] all done.
+// Forked: the lease's events, [0] fork, then four per chunk.
+struct ChunkEvents {
+    hipEvent_t start, arm_done, tail_done, done;
+};
+
+ChunkEvents chunk_events(const EventSet &ev, const StreamSet *fk, int c)
+{
+    if (fk) return ChunkEvents{fk->ev[1 + 4 * c], fk->ev[2 + 4 * c], fk->ev[3 + 4 * c], fk->ev[4 + 4 * c]};
+    if (!ev.ok) return ChunkEvents{};
+    return ChunkEvents{nullptr, ev.e[2], ev.e[3], nullptr};
+}
+
+// The caller's stream waits for the `started` forked chunks (K-1 downwards).  Also the way
+// out of an error after some chunks were queued: s waits for them before the caller can
+// reuse or free the workspace (the chunks' own streams never outlive it unjoined).
+void join_chunks(const Run &r, const EventSet &ev, const StreamSet *fk, int started)
+{
+    for (int c = r.K - 1; c > r.K - 1 - started && c >= 1; --c) {
+        const ChunkEvents e = chunk_events(ev, fk, c);
+        (void)hipEventRecord(e.done, fk->st[c]);
+        (void)hipStreamWaitEvent(r.s, e.done, 0);
+    }
+}
+
+// Every chunk's ARM -> tail -> download, the most expensive chunk first.  Chunk 0 runs on the
+// caller's stream; chunks >= 1 on streams forked from it after the uploads, leased with their
+// events from the process-wide pool (ccmi_api.cpp) for this call.  One chunk: no lease, no fork.
+int run_chunks(const Run &r, const EventSet &ev, StreamSetLease &lease)
+{
+    const StreamSet *fk = nullptr;
+    if (r.K > 1) {
+        lease.set = ccmi_streamset_acquire(r.K, 1 + 4 * r.K, true);
+        if (!lease.set) return CCMI_ERR_HIP;
+        fk = lease.set;
+        CCMI_HIP_CHECK(hipEventRecord(fk->ev[0], r.s));
+    }
+    int started = 0;
+    for (int c = r.K - 1; c >= 0; --c) {
+        const hipStream_t cs = c == 0 ? r.s : fk->st[c];
+        const ChunkEvents e = chunk_events(ev, fk, c);
+        if (c > 0) {
+            if (hipStreamWaitEvent(cs, fk->ev[0], 0) != hipSuccess) {
+                join_chunks(r, ev, fk, started);
+                return ccmi_set_error(CCMI_ERR_HIP, "decode: stream fork failed");
+            }
+            ++started;
+        }
+        if (e.start) (void)hipEventRecord(e.start, cs);
+        int rc = launch_chunk(r, c, cs, e.arm_done);
+        if (!rc) {
+            if (e.tail_done) (void)hipEventRecord(e.tail_done, cs);
+            rc = download_chunk(r, c, cs);
+        }
+        if (rc) {
+            join_chunks(r, ev, fk, started);
+            return rc;
+        }
+    }
+    join_chunks(r, ev, fk, started);
+    return CCMI_OK;
+}
+
+// latents (when asked for) and the ARM kernels' status words, then the one synchronisation
+int read_back(const Run &r)
+{
+    const DecodePlan &pl = r.pl;
+    const int n = (int)pl.fr.size();
+    int32_t *const *lat_out = r.rq.lat_out;
     for (int i = 0; i < n && lat_out; ++i)
-        CCMI_HIP_CHECK(hipMemcpyAsync(lat_out[i], dev + pl[i].lat_off, pl[i].lat_elems * 4, hipMemcpyDeviceToHost, s));
-    std::vector<uint32_t> st(n_status);
-    CCMI_HIP_CHECK(hipMemcpyAsync(st.data(), status, 4 * n_status, hipMemcpyDeviceToHost, s));
-    CCMI_HIP_CHECK(hipStreamSynchronize(s));
+        CCMI_HIP_CHECK(hipMemcpyAsync(lat_out[i], r.dev + pl.fr[i].lat_off, pl.fr[i].lat_elems * 4, hipMemcpyDeviceToHost, r.s));
+    std::vector<uint32_t> st(pl.n_status());
+    CCMI_HIP_CHECK(hipMemcpyAsync(st.data(), r.status(), 4 * st.size(), hipMemcpyDeviceToHost, r.s));
+    CCMI_HIP_CHECK(hipStreamSynchronize(r.s));
     g_last_flags.assign(n, 0u);
     for (int i = 0; i < n; ++i)
         for (int l = 0; l < CCMI_MAX_GRIDS; ++l) g_last_flags[i] |= st[(size_t)i * CCMI_MAX_GRIDS + l];
@@ -883,45 +665,115 @@ int decode_many(const uint8_t *const *streams, const size_t *lens, int n, uint8_
                 return ccmi_set_error(CCMI_ERR_HIP,
                                       "decode: stream %d, latent grid %d: the ARM decode's wave hand-off gave up "
                                       "after %d polls; output discarded",
-                                      i, l, spin_cap);
+                                      i, l, r.spin_cap);
     for (int i = 0; i < n && lat_out; ++i)
-        for (size_t k = 0; k < pl[i].lat_elems; ++k) lat_out[i][k] >>= kArmPrec;
+        for (size_t k = 0; k < pl.fr[i].lat_elems; ++k) lat_out[i][k] >>= kArmPrec;
 #if defined(CCMI_ARM_STAMPS)
     {
-        std::vector<uint64_t> dbg(16 * all.size());
-        CCMI_HIP_CHECK(hipMemcpy(dbg.data(), dev + dbg_off, dbg.size() * 8, hipMemcpyDeviceToHost));
-        for (size_t j = 0; j < all.size(); ++j) {
-            const size_t k = (size_t)(reinterpret_cast<uint8_t *>(all[j].dbg) - (dev + dbg_off)) / 128;
-            fprintf(stderr, "STAMPS stream %zu (%dx%d):", k, all[j].h, all[j].w);
+        std::vector<uint64_t> dbg(16 * r.descs.size());
+        CCMI_HIP_CHECK(hipMemcpy(dbg.data(), r.dev + pl.dbg_off, dbg.size() * 8, hipMemcpyDeviceToHost));
+        for (size_t j = 0; j < r.descs.size(); ++j) {
+            const size_t k = (size_t)(reinterpret_cast<uint8_t *>(r.descs[j].dbg) - (r.dev + pl.dbg_off)) / 128;
+            fprintf(stderr, "STAMPS stream %zu (%dx%d):", k, r.descs[j].h, r.descs[j].w);
             for (int c = 0; c < 16; ++c) fprintf(stderr, " %llu", (unsigned long long)dbg[16 * k + c]);
             fprintf(stderr, "\n");
         }
     }
 #endif
-    if (ev.ok) {
-        if (K == 1) {
-            for (int k = 0; k < 4; ++k) (void)hipEventElapsedTime(&g_last_ms[k], ev.e[k], ev.e[k + 1]);
-        } else {
-            // overlapped stages: ARM = the longest chunk's ARM (its start to its ARM end, events
-            // of one stream), tail = from the uploads to the last chunk's tail minus that ARM,
-            // download = what is left after the last tail (the part not hidden under kernels)
-            float span = 0.f, arm = 0.f, all = 0.f;
-            (void)hipEventElapsedTime(&g_last_ms[0], ev.e[0], ev.e[1]);
-            (void)hipEventElapsedTime(&all, ev.e[1], ev.e[4]);
-            const StreamSet &fk = *lease.set;
-            for (int c = 0; c < K; ++c) {
-                float t = 0.f;
-                if (hipEventElapsedTime(&t, fk.ev[1 + 4 * c], fk.ev[2 + 4 * c]) == hipSuccess) arm = std::max(arm, t);
-                if (hipEventElapsedTime(&t, ev.e[1], fk.ev[3 + 4 * c]) == hipSuccess) span = std::max(span, t);
-            }
-            g_last_ms[1] = arm;
-            g_last_ms[2] = span - arm;
-            g_last_ms[3] = all - span;
-            (void)hipGetLastError(); // a timing query that failed must not surface in the next call
-        }
-        if (sink.device()) g_last_ms[3] = 0.f; // nothing was downloaded (the status words are not frame data)
-    }
     return CCMI_OK;
+}
+
+// ccmi_decode_last_timing: upload, ARM, tail, download
+void store_timing(const Run &r, const EventSet &ev, const StreamSet *fk)
+{
+    if (!ev.ok) return;
+    if (!fk) {
+        for (int k = 0; k < 4; ++k) (void)hipEventElapsedTime(&g_last_ms[k], ev.e[k], ev.e[k + 1]);
+    } else {
+        // overlapped stages: ARM = the longest chunk's ARM (its start to its ARM end, events
+        // of one stream), tail = from the uploads to the last chunk's tail minus that ARM,
+        // download = what is left after the last tail (the part not hidden under kernels)
+        float span = 0.f, arm = 0.f, all = 0.f;
+        (void)hipEventElapsedTime(&g_last_ms[0], ev.e[0], ev.e[1]);
+        (void)hipEventElapsedTime(&all, ev.e[1], ev.e[4]);
+        for (int c = 0; c < r.K; ++c) {
+            const ChunkEvents e = chunk_events(ev, fk, c);
+            float t = 0.f;
+            if (hipEventElapsedTime(&t, e.start, e.arm_done) == hipSuccess) arm = std::max(arm, t);
+            if (hipEventElapsedTime(&t, ev.e[1], e.tail_done) == hipSuccess) span = std::max(span, t);
+        }
+        g_last_ms[1] = arm;
+        g_last_ms[2] = span - arm;
+        g_last_ms[3] = all - span;
+        (void)hipGetLastError(); // a timing query that failed must not surface in the next call
+    }
+    if (r.rq.device()) g_last_ms[3] = 0.f; // nothing was downloaded (the status words are not frame data)
+}
+
+// Executes a plan on stream s: weight decode, uploads, launches, downloads, status words.
+int decode_run(const DecodeRequest &rq, DecodePlan &pl, hipStream_t s)
+{
+    Run r{rq, pl, s};
+    if (int rc = decode_weights_all(pl.fr)) return rc;
+    stage_constants(r);
+    r.dev = static_cast<uint8_t *>(rq.ws);
+    if (r.dev) {
+        if (rq.ws_bytes < pl.total)
+            return ccmi_set_error(CCMI_ERR_ARG, "decode: workspace of %zu bytes, need %zu", rq.ws_bytes, pl.total);
+        if (reinterpret_cast<uintptr_t>(r.dev) % 256)
+            return ccmi_set_error(CCMI_ERR_ARG, "decode: workspace must be 256-byte aligned");
+    } else {
+        CCMI_HIP_CHECK(hipMalloc(&r.dev, pl.total));
+    }
+    struct Free {
+        uint8_t *p;
+        ~Free() { if (p) (void)hipFree(p); }
+    } guard{rq.ws ? nullptr : r.dev};
+    EventSet ev;
+    StreamSetLease lease;
+    ev.rec(0, s);
+    CCMI_HIP_CHECK(hipMemcpyAsync(r.dev, r.host.data(), pl.cst, hipMemcpyHostToDevice, s));
+    CCMI_HIP_CHECK(hipMemsetAsync(r.status(), 0, 4 * pl.n_status(), s));
+    r.spin_cap = arm_spin_cap();
+    assign_chunks(r);
+    if (int rc = build_arm_groups(r)) return rc;
+    if (int rc = build_tail_groups(r)) return rc;
+    ev.rec(1, s);
+    if (int rc = run_chunks(r, ev, lease)) return rc;
+    ev.rec(4, s);
+    if (int rc = read_back(r)) return rc;
+    store_timing(r, ev, lease.set);
+    return CCMI_OK;
+}
+
+// The thread-local ARM flags are cleared first: a call that fails, or only plans, reports no
+// stream, not the previous call's.
+int plan_only(const DecodeRequest &rq, size_t *workspace_bytes)
+{
+    g_last_flags.clear();
+    DecodePlan pl;
+    if (int rc = decode_plan(rq, pl)) return rc;
+    *workspace_bytes = pl.total;
+    return CCMI_OK;
+}
+
+int decode_many(const DecodeRequest &rq, void *stream)
+{
+    g_last_flags.clear();
+    DecodePlan pl;
+    if (int rc = decode_plan(rq, pl)) return rc;
+    return decode_run(rq, pl, static_cast<hipStream_t>(stream));
+}
+
+DecodeRequest request(const uint8_t *const *streams, const size_t *lens, int n, int out_bitdepth, int out_chroma)
+{
+    DecodeRequest rq;
+    rq.streams = streams;
+    rq.lens = lens;
+    rq.n = n;
+    rq.out_bitdepth = out_bitdepth;
+    rq.out_chroma = out_chroma;
+    return rq;
 }
 
 } // namespace
@@ -959,24 +811,31 @@ extern "C" int ccmi_decode_batch(const uint8_t *const *streams, const size_t *le
                                  int as_yuv, void *stream)
 {
     if (!streams || !lens || !out || !out_caps) return ccmi_set_error(CCMI_ERR_ARG, "decode_batch: null argument");
-    return decode_many(streams, lens, n, out, out_caps, out_sizes, out_bitdepth, out_chroma, as_yuv,
-                       static_cast<hipStream_t>(stream));
+    DecodeRequest rq = request(streams, lens, n, out_bitdepth, out_chroma);
+    rq.as_yuv = as_yuv;
+    rq.outs = out;
+    rq.caps = out_caps;
+    rq.sizes = out_sizes;
+    return decode_many(rq, stream);
 }
 
 extern "C" int ccmi_decode_batch_workspace_bytes(const uint8_t *const *streams, const size_t *lens, int n,
                                                  int out_bitdepth, int out_chroma, int as_yuv, size_t *bytes)
 {
     if (!streams || !lens || !bytes) return ccmi_set_error(CCMI_ERR_ARG, "decode_batch_workspace_bytes: null argument");
-    return decode_many(streams, lens, n, nullptr, nullptr, nullptr, out_bitdepth, out_chroma, as_yuv, nullptr, nullptr,
-                       nullptr, 0, bytes);
+    DecodeRequest rq = request(streams, lens, n, out_bitdepth, out_chroma);
+    rq.as_yuv = as_yuv;
+    return plan_only(rq, bytes);
 }
 
 extern "C" int ccmi_decode_batch_plan(const uint8_t *const *streams, const size_t *lens, int n, int out_bitdepth,
                                       int out_chroma, int as_yuv, size_t *out_sizes, size_t *workspace_bytes)
 {
     if (!streams || !lens || !out_sizes || !workspace_bytes) return ccmi_set_error(CCMI_ERR_ARG, "decode_batch_plan: null argument");
-    return decode_many(streams, lens, n, nullptr, nullptr, out_sizes, out_bitdepth, out_chroma, as_yuv, nullptr, nullptr,
-                       nullptr, 0, workspace_bytes);
+    DecodeRequest rq = request(streams, lens, n, out_bitdepth, out_chroma);
+    rq.as_yuv = as_yuv;
+    rq.sizes = out_sizes;
+    return plan_only(rq, workspace_bytes);
 }
 
 extern "C" int ccmi_decode_batch_ws(const uint8_t *const *streams, const size_t *lens, int n, uint8_t *const *out,
@@ -985,8 +844,14 @@ extern "C" int ccmi_decode_batch_ws(const uint8_t *const *streams, const size_t 
 {
     if (!streams || !lens || !out || !out_caps || !workspace)
         return ccmi_set_error(CCMI_ERR_ARG, "decode_batch_ws: null argument");
-    return decode_many(streams, lens, n, out, out_caps, out_sizes, out_bitdepth, out_chroma, as_yuv,
-                       static_cast<hipStream_t>(stream), nullptr, workspace, workspace_bytes);
+    DecodeRequest rq = request(streams, lens, n, out_bitdepth, out_chroma);
+    rq.as_yuv = as_yuv;
+    rq.outs = out;
+    rq.caps = out_caps;
+    rq.sizes = out_sizes;
+    rq.ws = workspace;
+    rq.ws_bytes = workspace_bytes;
+    return decode_many(rq, stream);
 }
 
 extern "C" int ccmi_decode_batch_dev_plan(const uint8_t *const *streams, const size_t *lens, int n, int out_bitdepth,
@@ -995,12 +860,11 @@ extern "C" int ccmi_decode_batch_dev_plan(const uint8_t *const *streams, const s
 {
     if (!streams || !lens || !geom || !workspace_bytes)
         return ccmi_set_error(CCMI_ERR_ARG, "decode_batch_dev_plan: null argument");
-    Sink sink;
-    sink.sample = sample_type;
-    sink.geom = geom;
     if (sample_type < 0) return ccmi_set_error(CCMI_ERR_ARG, "decode: unknown sample type %d", sample_type);
-    return decode_many(streams, lens, n, nullptr, nullptr, nullptr, out_bitdepth, out_chroma, 0, nullptr, nullptr,
-                       nullptr, 0, workspace_bytes, sink);
+    DecodeRequest rq = request(streams, lens, n, out_bitdepth, out_chroma);
+    rq.sample = sample_type;
+    rq.geom = geom;
+    return plan_only(rq, workspace_bytes);
 }
 
 extern "C" int ccmi_decode_batch_dev(const uint8_t *const *streams, const size_t *lens, int n, void *const *out_dev,
@@ -1009,11 +873,13 @@ extern "C" int ccmi_decode_batch_dev(const uint8_t *const *streams, const size_t
 {
     if (!streams || !lens || !out_dev || !out_caps) return ccmi_set_error(CCMI_ERR_ARG, "decode_batch_dev: null argument");
     if (sample_type < 0) return ccmi_set_error(CCMI_ERR_ARG, "decode: unknown sample type %d", sample_type);
-    Sink sink;
-    sink.sample = sample_type;
-    sink.dev = out_dev;
-    return decode_many(streams, lens, n, nullptr, out_caps, nullptr, out_bitdepth, out_chroma, 0,
-                       static_cast<hipStream_t>(stream), nullptr, workspace, workspace_bytes, nullptr, sink);
+    DecodeRequest rq = request(streams, lens, n, out_bitdepth, out_chroma);
+    rq.sample = sample_type;
+    rq.dev = out_dev;
+    rq.caps = out_caps;
+    rq.ws = workspace;
+    rq.ws_bytes = workspace_bytes;
+    return decode_many(rq, stream);
 }
 
 extern "C" int ccmi_decode_batch_dev_roi_plan(const uint8_t *const *streams, const size_t *lens, int n,
@@ -1023,13 +889,12 @@ extern "C" int ccmi_decode_batch_dev_roi_plan(const uint8_t *const *streams, con
     if (!streams || !lens || !geom || !workspace_bytes)
         return ccmi_set_error(CCMI_ERR_ARG, "decode_batch_dev_roi_plan: null argument");
     if (sample_type < 0) return ccmi_set_error(CCMI_ERR_ARG, "decode: unknown sample type %d", sample_type);
-    Sink sink;
-    sink.sample = sample_type;
-    sink.geom = geom;
-    sink.roi = roi;
-    sink.info = info;
-    return decode_many(streams, lens, n, nullptr, nullptr, nullptr, out_bitdepth, out_chroma, 0, nullptr, nullptr,
-                       nullptr, 0, workspace_bytes, sink);
+    DecodeRequest rq = request(streams, lens, n, out_bitdepth, out_chroma);
+    rq.sample = sample_type;
+    rq.roi = roi;
+    rq.geom = geom;
+    rq.info = info;
+    return plan_only(rq, workspace_bytes);
 }
 
 extern "C" int ccmi_decode_batch_dev_roi(const uint8_t *const *streams, const size_t *lens, int n, const ccmi_rect *roi,
@@ -1040,12 +905,14 @@ extern "C" int ccmi_decode_batch_dev_roi(const uint8_t *const *streams, const si
     if (!streams || !lens || !out_dev || !out_caps)
         return ccmi_set_error(CCMI_ERR_ARG, "decode_batch_dev_roi: null argument");
     if (sample_type < 0) return ccmi_set_error(CCMI_ERR_ARG, "decode: unknown sample type %d", sample_type);
-    Sink sink;
-    sink.sample = sample_type;
-    sink.dev = out_dev;
-    sink.roi = roi;
-    return decode_many(streams, lens, n, nullptr, out_caps, nullptr, out_bitdepth, out_chroma, 0,
-                       static_cast<hipStream_t>(stream), nullptr, workspace, workspace_bytes, nullptr, sink);
+    DecodeRequest rq = request(streams, lens, n, out_bitdepth, out_chroma);
+    rq.sample = sample_type;
+    rq.roi = roi;
+    rq.dev = out_dev;
+    rq.caps = out_caps;
+    rq.ws = workspace;
+    rq.ws_bytes = workspace_bytes;
+    return decode_many(rq, stream);
 }
 
 extern "C" int ccmi_decode_latents(const uint8_t *stream, size_t len, int32_t *out, size_t cap, void *hstream)
@@ -1060,7 +927,12 @@ extern "C" int ccmi_decode_latents(const uint8_t *stream, size_t len, int32_t *o
     if (int rc = ccmi_decode_output_size(stream, len, 0, 0, 1, &osz)) return rc;
     std::vector<uint8_t> tmp(osz);
     uint8_t *op = tmp.data();
-    return decode_many(&stream, &len, 1, &op, &osz, nullptr, 0, 0, 1, static_cast<hipStream_t>(hstream), &out);
+    DecodeRequest rq = request(&stream, &len, 1, 0, 0);
+    rq.as_yuv = 1;
+    rq.outs = &op;
+    rq.caps = &osz;
+    rq.lat_out = &out;
+    return decode_many(rq, hstream);
 }
 
 static bool ends_with(const std::string &a, const char *b)
@@ -1111,7 +983,12 @@ extern "C" int ccmi_decode_file(const char *in_path, const char *out_path, int o
     (void)hipEventCreate(&e0);
     (void)hipEventCreate(&e1);
     (void)hipEventRecord(e0, nullptr);
-    if (decode_many(&sp, &ln, 1, &op, &need, &got, out_bitdepth, out_chroma, as_yuv, nullptr)) return 1;
+    DecodeRequest rq = request(&sp, &ln, 1, out_bitdepth, out_chroma);
+    rq.as_yuv = as_yuv;
+    rq.outs = &op;
+    rq.caps = &need;
+    rq.sizes = &got;
+    if (decode_many(rq, nullptr)) return 1;
     (void)hipEventRecord(e1, nullptr);
     (void)hipEventSynchronize(e1);
     float ms = 0;

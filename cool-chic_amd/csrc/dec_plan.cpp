@@ -1,0 +1,244 @@
+// dec_plan.cpp -- path B: the header pass of a decode call (decode_plan): per-stream
+// validation, output formats, region windows and the layout of the one device workspace.
+// Host arithmetic only: no HIP runtime call in this file.
+#include <stdio.h>
+
+#include <algorithm>
+#include <string>
+
+#include "dec_plan.h"
+
+namespace ccmi {
+
+int out_format(const FrameHost &f, int out_bitdepth, int out_chroma, int as_yuv, OutFmt &o)
+{
+    o.bitdepth = out_bitdepth ? out_bitdepth : f.bitdepth;
+    const int chroma = out_chroma ? out_chroma : (f.frame_data_type == 1 ? 420 : 444);
+    const size_t bps = o.bitdepth <= 8 ? 1 : 2;
+    const size_t npx = (size_t)f.h * f.w;
+    o.header = 0;
+    if (as_yuv) {
+        if (o.bitdepth != 8 && o.bitdepth != 10)
+            return ccmi_set_error(CCMI_ERR_UNSUPPORTED, "YUV output bitdepth must be 8 or 10 (got %d)", o.bitdepth);
+        o.kind = chroma == 420 ? kYuv420 : kYuv444;
+        o.payload = bps * (o.kind == kYuv420 ? npx + 2 * (size_t)(f.h / 2) * (f.w / 2) : 3 * npx);
+    } else {
+        if (o.bitdepth < 1 || o.bitdepth > 16) return ccmi_set_error(CCMI_ERR_ARG, "PPM bitdepth %d", o.bitdepth);
+        o.kind = kPpm;
+        o.header = (size_t)snprintf(o.hdr, sizeof o.hdr, "P6\n%d %d\n%d\n", f.w, f.h, (1 << o.bitdepth) - 1);
+        o.payload = bps * 3 * npx;
+    }
+    return CCMI_OK;
+}
+
+namespace {
+
+size_t sample_bytes(int sample) { return sample == CCMI_SAMPLE_U8 ? 1 : sample == CCMI_SAMPLE_U16 ? 2 : 4; }
+
+// output of a device sink: planar 420 / 444 samples, no header; payload = bytes at the caller's pointer
+int tensor_format(const FrameHost &f, int out_bitdepth, int out_chroma, int sample, OutFmt &o, size_t *elems,
+                  const DecWindow &rect)
+{
+    if (sample != CCMI_SAMPLE_U8 && sample != CCMI_SAMPLE_U16 && sample != CCMI_SAMPLE_F32)
+        return ccmi_set_error(CCMI_ERR_ARG, "decode: unknown sample type %d", sample);
+    if (out_chroma != 0 && out_chroma != 420 && out_chroma != 444)
+        return ccmi_set_error(CCMI_ERR_ARG, "decode: output chroma format %d (0, 420 or 444)", out_chroma);
+    o.bitdepth = out_bitdepth ? out_bitdepth : f.bitdepth;
+    if (o.bitdepth < 1 || o.bitdepth > 16) return ccmi_set_error(CCMI_ERR_ARG, "decode: output bitdepth %d", o.bitdepth);
+    if (sample == CCMI_SAMPLE_U8 && o.bitdepth > 8)
+        return ccmi_set_error(CCMI_ERR_ARG, "decode: %d-bit samples do not fit CCMI_SAMPLE_U8", o.bitdepth);
+    const int chroma = out_chroma ? out_chroma : (f.frame_data_type == 1 ? 420 : 444);
+    const size_t npx = (size_t)rect.h() * rect.w();
+    o.kind = chroma == 420 ? kYuv420 : kYuv444;
+    o.header = 0;
+    *elems = o.kind == kYuv420 ? npx + 2 * (size_t)(rect.h() / 2) * (rect.w() / 2) : 3 * npx;
+    o.payload = sample_bytes(sample) * *elems;
+    return CCMI_OK;
+}
+
+size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// the architecture part of a frame's tail arguments (no device pointers): what
+// dec_tail_batchable() looks at, the true plane sizes and the workspace sizes
+void tail_arch(const FrameHost &f, DecTailFrame &t)
+{
+    DecUpsArgs &ua = t.ups;
+    ua = DecUpsArgs{};
+    ua.n_layers = f.n_layers;
+    for (int l = 0; l < f.n_layers; ++l) {
+        ua.lh[l] = f.lh[l];
+        ua.lw[l] = f.lw[l];
+    }
+    ua.ups_ks = f.ups_ks;
+    ua.n_ups = f.n_ups;
+    ua.pre_ks = f.pre_ks;
+    ua.n_pre = f.n_pre;
+    DecSynArgs &sa = t.syn;
+    sa = DecSynArgs{};
+    sa.c_in = f.n_layers;
+    sa.h = f.h;
+    sa.w = f.w;
+    sa.n_layers = (int)f.layers.size();
+    for (int l = 0; l < sa.n_layers; ++l) sa.layers[l] = f.layers[l];
+}
+
+// A device sink's region, output format and tail mode; fills rq.geom[i] / rq.info[i].
+int plan_tensor_sink(const DecodeRequest &rq, int i, FramePlan &p)
+{
+    const FrameHost &f = p.f;
+    DecTailFrame &t = p.tail;
+    size_t elems = 0;
+    DecWindow rect{0, f.h, 0, f.w};
+    if (rq.roi) {
+        const ccmi_rect &q = rq.roi[i];
+        if (q.w < 1 || q.h < 1 || q.x < 0 || q.y < 0 || q.x > f.w - q.w || q.y > f.h - q.h)
+            return ccmi_set_error(CCMI_ERR_ARG, "stream %d: region x %d y %d w %d h %d outside the %d x %d frame", i, q.x,
+                                  q.y, q.w, q.h, f.w, f.h);
+        rect = DecWindow{q.y, q.y + q.h, q.x, q.x + q.w};
+    }
+    if (int rc = tensor_format(f, rq.out_bitdepth, rq.out_chroma, rq.sample, p.of, &elems, rect)) return rc;
+    if (p.of.kind == kYuv420 && ((rect.x0 | rect.y0) & 1))
+        return ccmi_set_error(CCMI_ERR_ARG, "stream %d: a 420 region needs an even origin (x %d y %d)", i, rect.x0, rect.y0);
+    int halo = 0;
+    for (const SynLayerDesc &L : f.layers) halo += (L.ks - 1) / 2;
+    if (rect.h() == f.h && rect.w() == f.w) {
+        p.mode = kTailFrame;
+    } else if (p.batchable) {
+        p.mode = kTailWindow;
+        dec_roi_plan(f.lh, f.lw, f.n_layers, f.ups_ks, f.pre_ks, halo, rect, t.roi);
+    } else {
+        p.mode = kTailCrop;
+    }
+    if (p.mode != kTailWindow) { // the whole frame is decoded
+        dec_roi_plan(f.lh, f.lw, f.n_layers, f.ups_ks, f.pre_ks, halo, DecWindow{0, f.h, 0, f.w}, t.roi);
+        t.roi.rect = rect;
+    }
+    t.windowed = p.mode == kTailWindow;
+    if (rq.geom)
+        rq.geom[i] = ccmi_frame_geom{rect.w(), rect.h(), p.of.bitdepth, p.of.kind == kYuv420 ? 420 : 444,
+                                     f.frame_data_type, elems};
+    if (rq.info) {
+        ccmi_roi_info &I = rq.info[i];
+        I = ccmi_roi_info{};
+        I.n_grids = f.n_layers;
+        for (int l = 0; l < f.n_layers; ++l) I.arm_rows[l] = t.roi.arm_rows[l];
+        I.windowed = p.batchable ? 1 : 0;
+    }
+    if (rq.dev) {
+        if (!rq.dev[i]) return ccmi_set_error(CCMI_ERR_ARG, "decode: output %d is NULL", i);
+        if (reinterpret_cast<uintptr_t>(rq.dev[i]) % sample_bytes(rq.sample))
+            return ccmi_set_error(CCMI_ERR_ARG, "decode: output %d is not aligned to its %zu-byte samples", i,
+                                  sample_bytes(rq.sample));
+    }
+    return CCMI_OK;
+}
+
+// Stream i: header, sink format, region, capacity -- in this order, which fixes the first
+// error an input reports.
+int plan_frame(const DecodeRequest &rq, int i, FramePlan &p)
+{
+    if (!rq.streams[i]) return ccmi_set_error(CCMI_ERR_ARG, "decode: stream %d is NULL", i);
+    if (int rc = parse_frame_header(rq.streams[i], rq.lens[i], p.f)) {
+        std::string m = ccmi_last_error();
+        return ccmi_set_error(rc, "stream %d: %s", i, m.c_str());
+    }
+    const FrameHost &f = p.f;
+    DecTailFrame &t = p.tail;
+    tail_arch(f, t);
+    p.batchable = f.n_branches == 1 && dec_tail_batchable(t);
+    if (rq.device()) {
+        if (int rc = plan_tensor_sink(rq, i, p)) return rc;
+    } else {
+        if (int rc = out_format(f, rq.out_bitdepth, rq.out_chroma, rq.as_yuv, p.of)) return rc;
+        for (int l = 0; l < f.n_layers; ++l) t.roi.arm_rows[l] = f.lh[l];
+    }
+    for (int l = 0, off = 0; l < f.n_layers; ++l) {
+        t.ups.off[l] = off;
+        off += t.roi.arm_rows[l] * f.lw[l];
+    }
+    t.bitdepth = p.of.bitdepth;
+    t.kind = p.of.kind;
+    t.sample = rq.sample;
+    const size_t bytes = p.of.header + p.of.payload;
+    if ((rq.outs || rq.dev) && rq.caps && rq.caps[i] < bytes)
+        return ccmi_set_error(CCMI_ERR_ARG, "stream %d: output buffer of %zu bytes, need %zu", i, rq.caps[i], bytes);
+    if (rq.sizes) rq.sizes[i] = bytes;
+    return CCMI_OK;
+}
+
+// One device allocation: the constant part (coded bytes + weights, uploaded in one copy),
+// then every frame's scratch, then the call's tables.
+void plan_layout(const DecodeRequest &rq, DecodePlan &pl)
+{
+    size_t cst = 0;
+    for (FramePlan &p : pl.fr) {
+        const FrameHost &f = p.f;
+        for (int l = 0; l < f.n_layers; ++l) {
+            p.bytes_off[l] = cst;
+            cst += align_up(f.lat_n[l] + 64, 256);
+        }
+        p.arm_off = cst;
+        cst += align_up(f.arm.size() * 4, 256);
+        p.ups_off = cst;
+        cst += align_up(f.ups.size() * 4, 256);
+        p.syn_off = cst;
+        cst += align_up(f.syn.size() * 4, 256);
+    }
+    pl.cst = cst;
+    size_t tot = align_up(cst, 4096);
+    for (FramePlan &p : pl.fr) {
+        const FrameHost &f = p.f;
+        // a region decode on windows: the latent planes keep their frame pitch and hold the rows
+        // the ARM decode produces, the pyramid stacks and the synthesis output hold the windows
+        const DecRoi &R = p.tail.roi;
+        const bool win = p.mode == kTailWindow;
+        p.lat_elems = 0;
+        for (int l = 0; l < f.n_layers; ++l) p.lat_elems += (size_t)R.arm_rows[l] * f.lw[l];
+        p.ws_elems = win ? dec_ups_workspace_elems_win(R, f.n_layers) : dec_ups_workspace_elems(f.lh, f.lw, f.n_layers);
+        p.dense_elems = win ? (size_t)f.n_layers * R.lev[0].h() * R.lev[0].w() : (size_t)f.n_layers * f.h * f.w;
+        p.synout_elems = win ? (size_t)f.layers.back().n_out * R.rect.h() * R.rect.w()
+                             : (size_t)f.layers.back().n_out * f.h * f.w * f.n_branches;
+        p.synws_elems = dec_syn_workspace_elems(p.tail.syn);
+        p.lat_off = tot;
+        tot += align_up(p.lat_elems * 4, 256);
+        p.ws_off = tot;
+        tot += align_up(p.ws_elems * 4 + 4, 256);
+        p.dense_off = tot;
+        tot += align_up(p.dense_elems * 4, 256);
+        p.synout_off = tot;
+        tot += align_up(p.synout_elems * 4, 256);
+        p.synws_off = tot;
+        tot += align_up(p.synws_elems * 4 + 4, 256);
+        p.out_off = tot;
+        if (!rq.device()) tot += align_up(p.of.payload, 256); // device sinks write to the caller's memory
+    }
+    pl.desc_off = tot;
+    tot += align_up(sizeof(ArmStreamDesc) * pl.n_status(), 256);
+    // batched-tail argument tables: bounded by one single-frame table per frame
+    pl.tail_cap = 0;
+    for (const FramePlan &p : pl.fr) pl.tail_cap += dec_tail_table_bytes(p.f.n_layers, 1, p.mode == kTailWindow);
+    pl.tail_off = tot;
+    tot += align_up(pl.tail_cap, 256);
+    pl.status_off = tot;
+    tot += align_up(4 * pl.n_status(), 256);
+#if defined(CCMI_ARM_STAMPS)
+    pl.dbg_off = tot;
+    tot += align_up(16 * 8 * pl.n_status(), 256);
+#endif
+    pl.total = tot;
+}
+
+} // namespace
+
+int decode_plan(const DecodeRequest &rq, DecodePlan &pl)
+{
+    if (rq.n < 1) return ccmi_set_error(CCMI_ERR_ARG, "decode: no streams");
+    pl = DecodePlan{};
+    pl.fr.resize(rq.n);
+    for (int i = 0; i < rq.n; ++i)
+        if (int rc = plan_frame(rq, i, pl.fr[i])) return rc;
+    plan_layout(rq, pl);
+    return CCMI_OK;
+}
+
+} // namespace ccmi

@@ -1,0 +1,92 @@
+// dec_plan.h -- path B: what one decode call asks for (DecodeRequest) and what the header
+// pass makes of it (DecodePlan).  decode_plan() is host arithmetic on header fields of
+// untrusted streams and makes no HIP call; decode_run() (dec_host.cpp) executes a plan.
+#pragma once
+
+#include "dec_internal.h"
+
+namespace ccmi {
+
+enum OutKind { kYuv420 = 0, kYuv444 = 1, kPpm = 2 };
+
+struct OutFmt {
+    int kind, bitdepth;
+    size_t payload, header;
+    char hdr[48];
+};
+
+// file layout of a host-byte sink (PPM, or planar YUV when as_yuv)
+int out_format(const FrameHost &f, int out_bitdepth, int out_chroma, int as_yuv, OutFmt &o);
+
+// how a stream's decoder tail runs
+enum TailMode {
+    kTailFrame = 0,  // the whole frame (no region, or one that covers the frame)
+    kTailWindow = 1, // region decode on windows (batched tail, fused synthesis)
+    kTailCrop = 2,   // whole-frame per-frame tail, the region cropped by the output kernel
+};
+
+// One call of the decode driver.  The sink is host bytes (the default): file layout, staged
+// in the workspace and copied to outs[i]; or device tensors (sample >= 0): the output kernel
+// writes planar samples of type `sample` straight to dev[i], nothing is staged and nothing
+// is downloaded.  outs / dev NULL: planning only.
+struct DecodeRequest {
+    const uint8_t *const *streams = nullptr;
+    const size_t *lens = nullptr;
+    int n = 0;
+    int out_bitdepth = 0, out_chroma = 0; // 0: the stream's own
+    // host-byte sink
+    int as_yuv = 0;
+    uint8_t *const *outs = nullptr; // [n] host buffers
+    // device-tensor sink
+    int sample = -1;               // -1 host bytes, else CCMI_SAMPLE_*
+    void *const *dev = nullptr;    // [n] device pointers
+    const ccmi_rect *roi = nullptr; // [n], optional: the region of each frame to decode
+    // either sink
+    const size_t *caps = nullptr;    // [n], optional: capacity in bytes of outs[i] / dev[i]
+    size_t *sizes = nullptr;         // [n], optional: bytes written per stream (filled by the plan)
+    ccmi_frame_geom *geom = nullptr; // [n], optional (device sinks): filled by the plan
+    ccmi_roi_info *info = nullptr;   // [n], optional (device sinks): what the region decode does
+    int32_t *const *lat_out = nullptr; // [n], optional: the decoded latents, to the host
+    // caller-owned device workspace (NULL: one hipMalloc per call)
+    void *ws = nullptr;
+    size_t ws_bytes = 0;
+    bool device() const { return sample >= 0; }
+};
+
+// One stream of a call.  Offsets are bytes from the workspace base.
+struct FramePlan {
+    FrameHost f;
+    OutFmt of;
+    int mode = kTailFrame;
+    bool batchable = false; // single branch and an architecture the batched tail takes
+    bool arm24 = false;     // every ARM weight fits 24 signed bits (decode_run, once they are decoded)
+    // tail arguments: architecture, output format and region (tail.roi) from the plan, device
+    // pointers and syn.f24 from decode_run
+    DecTailFrame tail;
+    // constant part (uploaded): coded bytes per latent grid, then the three networks
+    size_t bytes_off[CCMI_MAX_GRIDS];
+    size_t arm_off, ups_off, syn_off;
+    // scratch
+    size_t lat_off, ws_off, dense_off, synout_off, synws_off, out_off;
+    size_t lat_elems, ws_elems, dense_elems, synout_elems, synws_elems;
+};
+
+struct DecodePlan {
+    std::vector<FramePlan> fr;
+    size_t cst = 0;        // bytes of the constant part
+    size_t total = 0;      // workspace bytes
+    size_t desc_off = 0;   // ArmStreamDesc[n * CCMI_MAX_GRIDS]
+    size_t tail_off = 0;   // batched-tail argument tables, tail_cap bytes
+    size_t tail_cap = 0;
+    size_t status_off = 0; // one word per (frame, latent grid): the ARM kernels' CCMI_ARM_FLAG_* bits
+#if defined(CCMI_ARM_STAMPS)
+    size_t dbg_off = 0;
+#endif
+    size_t n_status() const { return fr.size() * CCMI_MAX_GRIDS; }
+};
+
+// Header parse, argument and region validation, output sizes (rq.sizes / geom / info are
+// filled) and the workspace layout.  No weights are decoded and nothing touches the GPU.
+int decode_plan(const DecodeRequest &rq, DecodePlan &pl);
+
+} // namespace ccmi

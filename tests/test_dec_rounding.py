@@ -1,4 +1,4 @@
-"""Integer identities the path-B latency kernel relies on (dec_kernels.hip,
+"""Integer identities the path-B latency kernel relies on (dec_arm.hip,
 dec_arm_chain_kernel), checked on the CPU in int32 arithmetic with wraparound:
 
 * the reference's symmetric rounding of a /256 (arm_cpu.cpp:94-97, cc-contexts.h:25-29),

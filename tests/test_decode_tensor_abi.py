@@ -69,6 +69,37 @@ def test_dev_plan_geometry_of_every_committed_stream(ccmi_lib):
         assert gf[0].bitdepth == bd and gf[0].elems == 3 * geom[0].height * geom[0].width
 
 
+def test_byte_path_plan_entry_points_agree(ccmi_lib):
+    """One planner behind the byte path's three header-only entry points: for every committed
+    stream ccmi_decode_batch_workspace_bytes and ccmi_decode_batch_plan report the same
+    workspace and the latter's out_sizes[0] is ccmi_decode_output_size, for as_yuv 0 and 1;
+    the two workspace sizes agree for a batch of the first 7 streams too."""
+    import ccmi
+    every = FILES + sorted((ROOT / "tests" / "golden" / "cool_synth").rglob("*.cool"))
+    assert len(every) > len(FILES) > 30
+    ws_bytes = ccmi_lib.ccmi_decode_batch_workspace_bytes
+    ws_bytes.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    ws_bytes.restype = C.c_int
+    byte_plan = ccmi_lib.ccmi_decode_batch_plan
+    byte_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+    byte_plan.restype = C.c_int
+    out_size = ccmi_lib.ccmi_decode_output_size
+    out_size.argtypes = [C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_void_p]
+    out_size.restype = C.c_int
+    data = [f.read_bytes() for f in every]
+    for as_yuv in (0, 1):
+        for batch in [[d] for d in data] + [data[:7]]:
+            n = len(batch)
+            keep, sp, ln = _args(batch)
+            need_a, need_b, sizes, one = C.c_size_t(0), C.c_size_t(0), (C.c_size_t * n)(), C.c_size_t(0)
+            assert ws_bytes(sp, ln, n, 0, 0, as_yuv, C.byref(need_a)) == 0, ccmi.last_error()
+            assert byte_plan(sp, ln, n, 0, 0, as_yuv, sizes, C.byref(need_b)) == 0, ccmi.last_error()
+            assert need_a.value == need_b.value > 0
+            if n == 1:
+                assert out_size(sp[0], ln[0], 0, 0, as_yuv, C.byref(one)) == 0, ccmi.last_error()
+                assert sizes[0] == one.value > 0
+
+
 def test_dev_plan_errors_are_reported(ccmi_lib):
     import ccmi
     data = [FILES[0].read_bytes()]

@@ -8,7 +8,7 @@ stream, another frame size, seeded N(0, 2) integer latents, written by the GPU w
 (21, 37), (19, 64), (34, 66) -- W mod 4 = 1, 0, 2, two odd heights, every plane a few
 samples long, so the output kernel's partial first / last groups and the groups that cross
 from the luma into the chroma planes are a large share of each frame.  One more (21, 37)
-stream has its third synthesis layer turned from 3x3 into 1x1: dec_kernels.hip's syn_fast()
+stream has its third synthesis layer turned from 3x3 into 1x1: dec_tail.hip's syn_fast()
 refuses it, so it is the one stream here that takes the per-frame decoder tail
 (launch_dec_output_tensor); every other stream, committed or generated, alone or in a
 batch, has a fused-synthesis architecture with one branch and takes the batched tail

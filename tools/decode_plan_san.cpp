@@ -1,0 +1,136 @@
+// decode_plan_san.cpp -- stand-alone host program for a sanitizer run of the decoder's planner
+// (decode_plan, dec_plan.cpp) on a machine without a GPU: every header-only entry point over
+// the streams named on the command line, whole, in batches of 7, over a list of regions, and
+// truncated at each length from 0 to the header size plus 8.  Every (truncated) stream sits in
+// a heap block of exactly its length, so a read past its end is reported.  No HIP call is made.
+//
+//   cd cool-chic_amd && hipcc -O1 -g -std=c++17 -fwrapv --offload-arch=gfx950 \
+//       -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
+//       -x hip ../tools/decode_plan_san.cpp csrc/dec_plan.cpp csrc/dec_host.cpp csrc/ccmi_api.cpp \
+//       csrc/dec_arm.hip csrc/dec_tail.hip -o /tmp/decode_plan_san
+//   /tmp/decode_plan_san $(find ../tests/golden/cool ../tests/golden/cool_synth -name '*.cool')
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "../cool-chic_amd/csrc/ccmi_internal.h"
+
+// the float forward path is not linked: ccmi_api.cpp only needs the symbols
+int ccmi_launch_arm_f32(const ccmi_arm_args *, hipStream_t) { return CCMI_ERR_UNSUPPORTED; }
+int ccmi_launch_ups_f32(const ccmi_ups_args *, hipStream_t) { return CCMI_ERR_UNSUPPORTED; }
+int ccmi_launch_syn_f32(const ccmi_syn_args *, hipStream_t) { return CCMI_ERR_UNSUPPORTED; }
+int ccmi_launch_post_f32(const ccmi_post_args *, hipStream_t) { return CCMI_ERR_UNSUPPORTED; }
+
+namespace {
+
+struct Stream {
+    uint8_t *p;
+    size_t n;
+};
+
+Stream exact_copy(const uint8_t *src, size_t n)
+{
+    uint8_t *p = static_cast<uint8_t *>(malloc(n ? n : 1));
+    if (n) memcpy(p, src, n);
+    return Stream{p, n};
+}
+
+long g_calls = 0, g_ok = 0;
+
+void count(int rc)
+{
+    ++g_calls;
+    if (rc == CCMI_OK) ++g_ok;
+}
+
+// every header-only entry point on one batch; rects: one per stream
+void plan_all(const std::vector<Stream> &b, const std::vector<ccmi_rect> &rects, int bd, int chroma)
+{
+    const int n = (int)b.size();
+    std::vector<const uint8_t *> sp(n);
+    std::vector<size_t> ln(n), sizes(n);
+    for (int i = 0; i < n; ++i) sp[i] = b[i].p, ln[i] = b[i].n;
+    std::vector<ccmi_frame_geom> geom(n);
+    std::vector<ccmi_roi_info> info(n);
+    size_t need = 0;
+    for (int yuv = 0; yuv < 2; ++yuv) {
+        count(ccmi_decode_output_size(sp[0], ln[0], bd, chroma, yuv, &need));
+        count(ccmi_decode_batch_workspace_bytes(sp.data(), ln.data(), n, bd, chroma, yuv, &need));
+        count(ccmi_decode_batch_plan(sp.data(), ln.data(), n, bd, chroma, yuv, sizes.data(), &need));
+    }
+    for (int sample = 0; sample < 3; ++sample) {
+        count(ccmi_decode_batch_dev_plan(sp.data(), ln.data(), n, bd, chroma, sample, geom.data(), &need));
+        count(ccmi_decode_batch_dev_roi_plan(sp.data(), ln.data(), n, rects.data(), bd, chroma, sample, geom.data(),
+                                             info.data(), &need));
+        count(ccmi_decode_batch_dev_roi_plan(sp.data(), ln.data(), n, nullptr, bd, chroma, sample, geom.data(), nullptr,
+                                             &need));
+    }
+}
+
+std::vector<ccmi_rect> rects_of(int w, int h)
+{
+    const int a = w / 3 > 0 ? w / 3 : 1, b = h / 3 > 0 ? h / 3 : 1;
+    return {{0, 0, w, h},         {0, 0, 1, 1},         {w - 1, 0, 1, 1},     {0, h - 1, 1, 1},     {w - 1, h - 1, 1, 1},
+            {1, 1, w > 1 ? w - 1 : 1, h > 1 ? h - 1 : 1}, {0, b, a, b},       {a, 0, a, b},         {w - a, b, a, b},
+            {a, h - b, a, b},     {-1, b, a, b},        {a, -1, a, b},        {w - a + 1, b, a, b}, {a, h - b + 1, a, b},
+            {2, 2, 0, 4},         {2 * (w / 4), 2 * (h / 4), a, b},           {0x7fffffff, 0, 1, 1}, {0, 0, 0x7fffffff, 0x7fffffff}};
+}
+
+} // namespace
+
+int main(int argc, char **argv)
+{
+    std::vector<Stream> all;
+    for (int i = 1; i < argc; ++i) {
+        FILE *f = fopen(argv[i], "rb");
+        if (!f) {
+            fprintf(stderr, "cannot open %s\n", argv[i]);
+            return 2;
+        }
+        std::vector<uint8_t> buf;
+        uint8_t tmp[4096];
+        for (size_t k; (k = fread(tmp, 1, sizeof tmp, f)) > 0;) buf.insert(buf.end(), tmp, tmp + k);
+        fclose(f);
+        all.push_back(exact_copy(buf.data(), buf.size()));
+    }
+    if (all.empty()) {
+        fprintf(stderr, "usage: decode_plan_san stream.cool ...\n");
+        return 2;
+    }
+    const int bds[] = {0, 8, 10, 16}, chromas[] = {0, 420, 444};
+    for (size_t i = 0; i < all.size(); ++i) {
+        const Stream &s = all[i];
+        const int h = s.n >= 6 ? (s.p[2] << 8) | s.p[3] : 1, w = s.n >= 6 ? (s.p[4] << 8) | s.p[5] : 1;
+        for (const ccmi_rect &r : rects_of(w, h))
+            for (int bd : bds)
+                for (int ch : chromas) plan_all({s}, {r}, bd, ch);
+        const size_t hdr = s.n >= 11 ? 9 + (((size_t)s.p[9] << 8) | s.p[10]) : s.n;
+        for (size_t cut = 0; cut <= s.n && cut <= hdr + 8; ++cut) {
+            const Stream t = exact_copy(s.p, cut);
+            plan_all({t}, {ccmi_rect{0, 0, w, h}}, 0, 0);
+            plan_all({t}, {ccmi_rect{2, 2, w / 2 > 0 ? w / 2 : 1, h / 2 > 0 ? h / 2 : 1}}, 8, 420);
+            free(t.p);
+        }
+    }
+    for (size_t i = 0; i < all.size(); i += 7) {
+        std::vector<Stream> b(all.begin() + i, all.begin() + std::min(all.size(), i + 7));
+        std::vector<ccmi_rect> rects;
+        for (size_t j = 0; j < b.size(); ++j) {
+            const int h = (b[j].p[2] << 8) | b[j].p[3], w = (b[j].p[4] << 8) | b[j].p[5];
+            rects.push_back(rects_of(w, h)[(i + j) % 10]);
+        }
+        for (int bd : bds)
+            for (int ch : chromas) plan_all(b, rects, bd, ch);
+    }
+    {
+        std::vector<ccmi_rect> rects;
+        for (const Stream &s : all) rects.push_back(ccmi_rect{0, 0, (s.p[4] << 8) | s.p[5], (s.p[2] << 8) | s.p[3]});
+        plan_all(all, rects, 0, 0);
+    }
+    for (Stream &s : all) free(s.p);
+    printf("decode_plan_san: %ld calls, %ld succeeded\n", g_calls, g_ok);
+    return g_ok > 0 ? 0 : 1;
+}
