@@ -28,6 +28,8 @@ EXPORTED = [
     "ccmi_decode_file", "ccmi_decode_batch", "ccmi_decode_output_size", "ccmi_decode_last_timing",
     "ccmi_decode_last_arm_flags", "ccmi_decode_latents", "ccmi_decode_batch_workspace_bytes", "ccmi_decode_batch_plan", "ccmi_decode_batch_ws", "ccmi_decode_weights_i32",
     "ccmi_decode_batch_dev_plan", "ccmi_decode_batch_dev", "ccmi_decode_batch_dev_roi_plan", "ccmi_decode_batch_dev_roi",
+    "ccmi_latents_plan", "ccmi_latents_decode", "ccmi_latents_free", "ccmi_latents_count", "ccmi_latents_values",
+    "ccmi_latents_render_plan", "ccmi_latents_render",
     "ccmi_ups_workspace_bytes_i32", "ccmi_ups_forward_i32", "ccmi_syn_workspace_bytes_i32", "ccmi_syn_forward_i32",
     "ccmi_cool_parse", "ccmi_code_wb", "ccmi_decode_wb", "ccmi_code_latent_layer", "ccmi_arm_forward_i32",
     "ccmi_encode_frame", "ccmi_row_reduce_f32", "ccmi_train_param_count", "ccmi_train_workspace_bytes", "ccmi_train_step",
@@ -159,6 +161,14 @@ def check(rc: int) -> None:
 
 def last_error() -> str:
     return lib().ccmi_last_error().decode(errors="replace")
+
+
+def __getattr__(name):
+    # ccmi.LatentStore: the resident form of decoded streams (ccmi/decode.py), imported on first use
+    if name == "LatentStore":
+        from .decode import LatentStore
+        return LatentStore
+    raise AttributeError(f"module 'ccmi' has no attribute {name!r}")
 
 
 def stream_handle(device=None) -> int:

@@ -257,6 +257,36 @@ def roi_plan(streams: Sequence[bytes], roi, output_bitdepth: int = 0, output_chr
     return [{"arm_rows": [int(v) for v in i.arm_rows[: i.n_grids]], "windowed": bool(i.windowed)} for i in info]
 
 
+def _alloc_outs(geom, sample, stack, dev):
+    """Output tensors of a device-sink call: (the stacked allocation or None, one flat tensor
+    per frame, their pointers, their capacities in bytes)."""
+    import torch
+    tdtype = (torch.uint8, torch.uint16, torch.float32)[sample]
+    n = len(geom)
+    flat = None
+    if stack:
+        g0 = geom[0]
+        if any((g.width, g.height, g.chroma) != (g0.width, g0.height, g0.chroma) for g in geom):
+            raise ValueError("decode_batch_tensors: stack=True needs outputs of one size and chroma format")
+        flat = torch.empty(n, g0.elems, dtype=tdtype, device=dev)
+        outs = [flat[i] for i in range(n)]
+    else:
+        outs = [torch.empty(g.elems, dtype=tdtype, device=dev) for g in geom]
+    op = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
+    cap = (C.c_size_t * n)(*[o.numel() * o.element_size() for o in outs])
+    return flat, outs, op, cap
+
+
+def _shape_outs(flat, outs, geom, stack):
+    from .forward import split_420
+
+    def shaped(t, g):
+        return split_420(t, g.height, g.width) if g.chroma == 420 else t.reshape(*t.shape[:-1], 3, g.height, g.width)
+    if stack:
+        return shaped(flat, geom[0])
+    return [shaped(o, g) for o, g in zip(outs, geom)]
+
+
 def decode_batch_tensors(streams: Sequence[bytes], output_bitdepth: int = 0, output_chroma_format: int = 0,
                          dtype=None, stack: bool = False, workspace=None, stream_handle: int | None = None, roi=None):
     """Decode independent intra .cool streams straight into device tensors
@@ -276,24 +306,13 @@ def decode_batch_tensors(streams: Sequence[bytes], output_bitdepth: int = 0, out
     and y even, chroma [y/2 : y/2 + h/2, x/2 : x/2 + w/2]) and H, W above are the region's, so
     stack=True takes equal-size crops of frames of different sizes."""
     import torch
-    from .forward import split_420
     m = _marshal(streams)
     _, sp, ln = m
     rects = _rects(roi, streams, len(streams))
     sample, geom, need = _plan_dev(m, output_bitdepth, output_chroma_format, dtype, rects)
-    tdtype = (torch.uint8, torch.uint16, torch.float32)[sample]
     n = len(streams)
     dev = torch.device("cuda", torch.cuda.current_device())
-    if stack:
-        g0 = geom[0]
-        if any((g.width, g.height, g.chroma) != (g0.width, g0.height, g0.chroma) for g in geom):
-            raise ValueError("decode_batch_tensors: stack=True needs outputs of one size and chroma format")
-        flat = torch.empty(n, g0.elems, dtype=tdtype, device=dev)
-        outs = [flat[i] for i in range(n)]
-    else:
-        outs = [torch.empty(g.elems, dtype=tdtype, device=dev) for g in geom]
-    op = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
-    cap = (C.c_size_t * n)(*[o.numel() * o.element_size() for o in outs])
+    flat, outs, op, cap = _alloc_outs(geom, sample, stack, dev)
     if stream_handle is None:
         stream_handle = torch.cuda.current_stream(dev).cuda_stream
     if workspace is None:
@@ -305,12 +324,7 @@ def decode_batch_tensors(streams: Sequence[bytes], output_bitdepth: int = 0, out
         check(_bind_dev().ccmi_decode_batch_dev_roi(sp, ln, n, rects, op, cap, sample, output_bitdepth,
                                                     output_chroma_format, workspace.data_ptr(), workspace.numel(),
                                                     stream_handle))
-
-    def shaped(t, g):
-        return split_420(t, g.height, g.width) if g.chroma == 420 else t.reshape(*t.shape[:-1], 3, g.height, g.width)
-    if stack:
-        return shaped(flat, geom[0])
-    return [shaped(o, g) for o, g in zip(outs, geom)]
+    return _shape_outs(flat, outs, geom, stack)
 
 
 def weights_i32(stream: bytes):
@@ -409,6 +423,7 @@ def last_timing() -> dict:
 
 # CCMI_ARM_FLAG_* (include/ccmi.h): what the latent decode of a stream did
 ARM_FLAG_TIMEOUT, ARM_FLAG_Q32, ARM_FLAG_W32, ARM_FLAG_PRE32, ARM_FLAG_BIG = 1, 2, 4, 8, 16
+ARM_FLAG_NARROW = 32  # LatentStore build: a latent does not fit the store's element type
 
 
 def last_arm_flags() -> list[int]:
@@ -422,6 +437,192 @@ def last_arm_flags() -> list[int]:
     return [int(v) for v in out[: n.value]]
 
 
-__all__ = ["last_timing", "last_arm_flags", "decode_latents", "decode_file", "decode_batch", "decode_batch_workspace_bytes", "output_size",
+LATENT_I8, LATENT_I16, LATENT_I32 = 0, 1, 2  # CCMI_LATENT_*
+
+
+def _bind_latents():
+    L = _bind_dev()
+    if not getattr(L, "_ccmi_latents_bound", False):
+        P, I, Z = C.c_void_p, C.c_int, C.c_size_t
+        L.ccmi_latents_plan.argtypes = [P, P, I, I, P, P, P]
+        L.ccmi_latents_decode.argtypes = [P, P, I, I, P, Z, P, Z, P, P]
+        L.ccmi_latents_free.argtypes = [P]
+        L.ccmi_latents_free.restype = None
+        L.ccmi_latents_count.argtypes = [P]
+        L.ccmi_latents_values.argtypes = [P, I, P, Z, P]
+        L.ccmi_latents_render_plan.argtypes = [P, P, I, P, I, I, I, P, P, P]
+        L.ccmi_latents_render.argtypes = [P, P, I, P, P, P, I, I, I, P, Z, P]
+        for f in (L.ccmi_latents_plan, L.ccmi_latents_decode, L.ccmi_latents_count, L.ccmi_latents_values,
+                  L.ccmi_latents_render_plan, L.ccmi_latents_render):
+            f.restype = C.c_int
+        L._ccmi_latents_bound = True
+    return L
+
+
+class LatentStore:
+    """Decode once, render often (ccmi_latents_*): the ARM + CABAC decode of `streams` runs
+    once, and its output -- the integer latents, packed, with the upsampling and synthesis
+    integers -- stays in one device tensor owned by this object.  render() then produces any
+    region of any of the streams, in any output format, at the cost of the decoder tail alone;
+    its result is exactly what decode_batch_tensors returns for the same streams and arguments.
+
+    dtype None: int16 latents, rebuilt as int32 if a stream reports ARM_FLAG_NARROW (a latent
+    outside -32768..32767); torch.int8 / torch.int16 / torch.int32: exactly that type, and a
+    latent that does not fit it is a CcmiError (ERR_UNSUPPORTED; last_arm_flags() shows which
+    streams).  arm_flags: the build's CCMI_ARM_FLAG_* bits per stream.  workspace: a uint8 CUDA tensor for the build (else torch's allocator).  The
+    Python bytes are not referred to after the constructor returns."""
+
+    def __init__(self, streams: Sequence[bytes], dtype=None, workspace=None, stream_handle: int | None = None):
+        import torch
+        self._h = None
+        L = _bind_latents()
+        table = {torch.int8: LATENT_I8, torch.int16: LATENT_I16, torch.int32: LATENT_I32}
+        if dtype is not None and dtype not in table:
+            raise ValueError(f"LatentStore: dtype {dtype} (torch.int8, torch.int16, torch.int32 or None)")
+        m = _marshal(streams)
+        n = len(streams)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        if stream_handle is None:
+            stream_handle = torch.cuda.current_stream(dev).cuda_stream
+        for t in ([torch.int16, torch.int32] if dtype is None else [dtype]):
+            nstore, nws = C.c_size_t(0), C.c_size_t(0)
+            check(L.ccmi_latents_plan(m[1], m[2], n, table[t], C.byref(nstore), None, C.byref(nws)))
+            store = torch.empty(max(nstore.value, 256), dtype=torch.uint8, device=dev)
+            ws = workspace
+            if ws is None:
+                ws = torch.empty(max(nws.value, 256), dtype=torch.uint8, device=dev)
+            h = C.c_void_p(None)
+            rc = L.ccmi_latents_decode(m[1], m[2], n, table[t], store.data_ptr(), store.numel(), ws.data_ptr(),
+                                       ws.numel(), stream_handle, C.byref(h))
+            if rc == 0:
+                break
+            if not (dtype is None and t == torch.int16 and any(f & ARM_FLAG_NARROW for f in last_arm_flags())):
+                check(rc)
+        self._h, self._store, self.dtype, self.nbytes = h, store, t, nstore.value
+        self.arm_flags = last_arm_flags()  # of the build; the planning and render calls clear the thread's record
+        geom, _ = self.render_geometry()
+        self.geometry = [{k: g[k] for k in ("width", "height", "bitdepth", "chroma", "frame_data_type")} for g in geom]
+
+    def __len__(self):
+        return _bind_latents().ccmi_latents_count(self._handle())
+
+    def _handle(self):
+        if self._h is None:
+            raise ValueError("LatentStore: closed")
+        return self._h
+
+    def close(self):
+        """Frees the handle and drops the store tensor."""
+        if getattr(self, "_h", None) is not None:
+            _bind_latents().ccmi_latents_free(self._h)
+            self._h = None
+            self._store = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _frames(self, index, roi):
+        """(m, index array or None, rect array or None)"""
+        n = len(self)
+        idx = list(range(n)) if index is None else [int(i) for i in index]
+        m = len(idx)
+        if m < 1:
+            raise ValueError("LatentStore: no frames")
+        rects = None
+        if roi is not None:
+            one = len(roi) == 4 and all(isinstance(v, int) for v in roi)
+            rois = [tuple(roi)] * m if one else list(roi)
+            if len(rois) != m:
+                raise ValueError(f"roi: one (x, y, w, h), or one entry per frame ({m}), got {len(rois)}")
+            rects = (Rect * m)()
+            for j, r in enumerate(rois):
+                if r is None:  # the whole frame of that stream (an index out of range is the library's error)
+                    g = self.geometry[idx[j]] if 0 <= idx[j] < n else {"width": 1, "height": 1}
+                    r = (0, 0, g["width"], g["height"])
+                if len(r) != 4:
+                    raise ValueError(f"roi[{j}]: (x, y, w, h) expected")
+                rects[j] = Rect(*[int(v) for v in r])
+        return m, (None if index is None else (C.c_int * m)(*idx)), rects
+
+    def _plan(self, index, roi, output_bitdepth, output_chroma_format, dtype, info=None):
+        import torch
+        L = _bind_latents()
+        m, idx, rects = self._frames(index, roi)
+        geom, need = (FrameGeom * m)(), C.c_size_t(0)
+
+        def plan(sample):
+            check(L.ccmi_latents_render_plan(self._handle(), idx, m, rects, output_bitdepth, output_chroma_format, sample,
+                                             geom, info(m) if callable(info) else None, C.byref(need)))
+        if dtype is None:
+            plan(SAMPLE_U16)
+            sample = SAMPLE_U8 if all(g.bitdepth <= 8 for g in geom) else SAMPLE_U16
+        else:
+            table = {torch.uint8: SAMPLE_U8, torch.uint16: SAMPLE_U16, torch.float32: SAMPLE_F32}
+            if dtype not in table:
+                raise ValueError(f"LatentStore: dtype {dtype} (torch.uint8, torch.uint16, torch.float32 or None)")
+            sample = table[dtype]
+        plan(sample)
+        return m, idx, rects, sample, geom, need.value
+
+    def render_geometry(self, index=None, roi=None, output_bitdepth: int = 0, output_chroma_format: int = 0,
+                        dtype=None) -> tuple:
+        """Header-only, like decode_batch_geometry: ([geometry per output frame], render workspace bytes)."""
+        _, _, _, _, geom, need = self._plan(index, roi, output_bitdepth, output_chroma_format, dtype)
+        return [{k: int(getattr(g, k)) for k, _ in FrameGeom._fields_} for g in geom], need
+
+    def roi_plan(self, index, roi, output_bitdepth: int = 0, output_chroma_format: int = 0, dtype=None) -> list:
+        """Like decode.roi_plan, per output frame: arm_rows = the latent rows the tail's planes hold."""
+        box = []
+
+        def info(m):
+            box.append((RoiInfo * m)())
+            return box[-1]
+        self._plan(index, roi, output_bitdepth, output_chroma_format, dtype, info)
+        return [{"arm_rows": [int(v) for v in i.arm_rows[: i.n_grids]], "windowed": bool(i.windowed)} for i in box[-1]]
+
+    def render(self, index=None, roi=None, output_bitdepth: int = 0, output_chroma_format: int = 0, dtype=None,
+               stack: bool = False, workspace=None, stream_handle: int | None = None):
+        """Frame j = stream index[j] of the store (None: every stream in order; repeats and any
+        order allowed), region roi[j] (one (x, y, w, h) for every frame, a sequence with one
+        entry per frame, None entries or None: whole frames).  Returns exactly what
+        decode_batch_tensors returns for those streams: tensors, {'y', 'u', 'v'} dicts, or with
+        stack=True one stacked tensor / dict.  workspace: a uint8 CUDA tensor of at least
+        render_geometry(...)[1] bytes."""
+        import torch
+        m, idx, rects, sample, geom, need = self._plan(index, roi, output_bitdepth, output_chroma_format, dtype)
+        dev = self._store.device
+        flat, outs, op, cap = _alloc_outs(geom, sample, stack, dev)
+        if stream_handle is None:
+            stream_handle = torch.cuda.current_stream(dev).cuda_stream
+        if workspace is None:
+            workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+        check(_bind_latents().ccmi_latents_render(self._handle(), idx, m, rects, op, cap, sample, output_bitdepth,
+                                                  output_chroma_format, workspace.data_ptr(), workspace.numel(),
+                                                  stream_handle))
+        return _shape_outs(flat, outs, geom, stack)
+
+    def latents(self, i: int) -> list:
+        """Stream i's integer latents: one int32 device tensor [h_l, w_l] per grid."""
+        import torch
+        g = self.geometry[i]
+        sizes, h, w = [], g["height"], g["width"]
+        n_grids = len(self.roi_plan([i], None)[0]["arm_rows"])
+        for _ in range(n_grids):
+            sizes.append((h, w))
+            h, w = (h + 1) // 2, (w + 1) // 2
+        flat = torch.empty(sum(a * b for a, b in sizes), dtype=torch.int32, device=self._store.device)
+        check(_bind_latents().ccmi_latents_values(self._handle(), int(i), flat.data_ptr(), flat.numel(),
+                                                  torch.cuda.current_stream(flat.device).cuda_stream))
+        out, p = [], 0
+        for a, b in sizes:
+            out.append(flat[p: p + a * b].view(a, b))
+            p += a * b
+        return out
+
+
+__all__ = ["last_timing", "LatentStore", "last_arm_flags", "decode_latents", "decode_file", "decode_batch", "decode_batch_workspace_bytes", "output_size",
            "decode_batch_tensors", "decode_batch_geometry", "roi_plan",
            "weights_i32", "ups_forward_i32", "syn_forward_i32", "CcmiError"]

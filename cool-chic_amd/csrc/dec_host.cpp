@@ -364,7 +364,17 @@ struct Run {
     std::vector<ArmStreamDesc> descs; // every group's streams, in launch order
     int max_w = 0, max_blocks = 1;
     std::vector<TailGroup> tails;
-    std::vector<uint8_t> tab; // the tail groups' tables
+    std::vector<uint8_t> tab; // the tail groups' tables, then the latent store's job table
+    size_t tab_used = 0;      // bytes of `tab` to upload
+    // latent store: a launch's part of the job table.  Sink: one per chunk, then the copy of the
+    // networks' integers; source: the one unpack.
+    struct LatLaunch {
+        size_t first;
+        int n;
+        uint32_t blocks;
+    };
+    std::vector<LatLaunch> lat;
+    size_t lat_tab() const { return pl.lat_tab_off - pl.tail_off; } // of the job table in `tab`
     uint32_t *status() const { return reinterpret_cast<uint32_t *>(dev + pl.status_off); }
 };
 
@@ -397,7 +407,7 @@ void assign_chunks(Run &r)
 {
     const std::vector<FramePlan> &fr = r.pl.fr;
     const int n = (int)fr.size();
-    r.K = n >= 64 ? CCMI_DEC_CHUNKS : 1;
+    r.K = n >= 64 && !r.rq.src ? CCMI_DEC_CHUNKS : 1; // a render has no ARM chain to hide a tail under
     r.chunk_of.assign(n, 0);
     if (r.K == 1) return;
     std::vector<int> order(n);
@@ -419,9 +429,8 @@ int build_arm_groups(Run &r)
         const FrameHost &f = p.f;
         int32_t *lat = reinterpret_cast<int32_t *>(r.dev + p.lat_off);
         for (int l = 0; l < f.n_layers; ++l) {
-            int32_t *plane = lat;
+            int32_t *plane = lat + p.tail.ups.off[l]; // the planes follow one another (a store build pads them to 16 bytes)
             const int rows = p.tail.roi.arm_rows[l]; // == lh[l] unless a region decode stops early
-            lat += (size_t)rows * f.lw[l];
             if (f.lat_n[l] == 0) { // zero layer (cc-frame-decoder.cpp:479-484)
                 CCMI_HIP_CHECK(hipMemsetAsync(plane, 0, (size_t)rows * f.lw[l] * 4, r.s));
                 continue;
@@ -487,10 +496,15 @@ int build_tail_groups(Run &r)
         DecTailFrame &t = p.tail;
         t.ups.lat = reinterpret_cast<const int32_t *>(r.dev + p.lat_off);
         t.ups.kernels = reinterpret_cast<const int32_t *>(r.dev + p.ups_off);
+        t.syn.params = reinterpret_cast<const int32_t *>(r.dev + p.syn_off);
+        if (r.rq.src) { // the networks' integers stay in the store
+            const LatentStream &S = r.rq.src->s[p.src];
+            t.ups.kernels = reinterpret_cast<const int32_t *>(r.rq.src->store + S.ups_off);
+            t.syn.params = reinterpret_cast<const int32_t *>(r.rq.src->store + S.syn_off);
+        }
         t.ups.workspace = reinterpret_cast<int32_t *>(r.dev + p.ws_off);
         t.ups.out = reinterpret_cast<int32_t *>(r.dev + p.dense_off);
         t.syn.in = t.ups.out;
-        t.syn.params = reinterpret_cast<const int32_t *>(r.dev + p.syn_off);
         t.syn.out = reinterpret_cast<int32_t *>(r.dev + p.synout_off);
         t.syn.workspace = reinterpret_cast<int32_t *>(r.dev + p.synws_off);
         t.dst = r.rq.device() ? static_cast<uint8_t *>(r.rq.dev[i]) : r.dev + p.out_off;
@@ -505,7 +519,7 @@ int build_tail_groups(Run &r)
         }
         it->frames.push_back(&t);
     }
-    r.tab.resize(r.pl.tail_cap > 0 ? r.pl.tail_cap : 1);
+    if (r.tab.size() < r.pl.tail_cap + 1) r.tab.resize(r.pl.tail_cap + 1);
     size_t tpos = 0;
     for (TailGroup &g : r.tails) {
         const int m = (int)g.frames.size();
@@ -513,8 +527,87 @@ int build_tail_groups(Run &r)
         dec_tail_fill(g.frames.data(), m, r.tab.data() + tpos);
         tpos += dec_tail_table_bytes(g.frames[0]->ups.n_layers, m, g.frames[0]->windowed);
     }
-    if (tpos) CCMI_HIP_CHECK(hipMemcpyAsync(r.dev + r.pl.tail_off, r.tab.data(), tpos, hipMemcpyHostToDevice, r.s));
+    r.tab_used = tpos;
     return CCMI_OK;
+}
+
+// Latent-store sink: a pack job per non-empty grid, chunk by chunk, then two copy jobs per
+// stream for the upsampling and synthesis integers (from the uploaded constant part).
+void build_pack_jobs(Run &r)
+{
+    const ccmi_latents &h = *r.rq.lat_store;
+    uint8_t *store = const_cast<uint8_t *>(h.store);
+    DecLatPackJob *jobs = reinterpret_cast<DecLatPackJob *>(r.tab.data() + r.lat_tab());
+    size_t nj = 0;
+    for (int c = 0; c < r.K; ++c) {
+        Run::LatLaunch L{nj, 0, 0};
+        for (size_t i = 0; i < r.pl.fr.size(); ++i) {
+            if (r.chunk_of[i] != c) continue;
+            const FramePlan &p = r.pl.fr[i];
+            for (int l = 0; l < p.f.n_layers; ++l) {
+                if (p.f.lat_n[l] == 0) continue;
+                const uint32_t n = (uint32_t)p.f.lh[l] * (uint32_t)p.f.lw[l];
+                jobs[nj++] = DecLatPackJob{reinterpret_cast<const int32_t *>(r.dev + p.lat_off) + p.tail.ups.off[l],
+                                           store + h.s[i].grid_off[l],
+                                           r.status() + i * CCMI_MAX_GRIDS + l,
+                                           n,
+                                           L.blocks,
+                                           kArmPrec,
+                                           0};
+                L.blocks += dec_lat_pack_blocks(n, h.type);
+                ++L.n;
+            }
+        }
+        r.lat.push_back(L);
+    }
+    Run::LatLaunch N{nj, 0, 0};
+    for (size_t i = 0; i < r.pl.fr.size(); ++i) {
+        const FramePlan &p = r.pl.fr[i];
+        const size_t src[2] = {p.ups_off, p.syn_off}, dst[2] = {h.s[i].ups_off, h.s[i].syn_off};
+        const size_t cnt[2] = {p.f.ups.size(), p.f.syn.size()};
+        for (int k = 0; k < 2; ++k) {
+            if (!cnt[k]) continue;
+            jobs[nj++] = DecLatPackJob{reinterpret_cast<const int32_t *>(r.dev + src[k]), store + dst[k], nullptr,
+                                       (uint32_t)cnt[k], N.blocks, 0, 0};
+            N.blocks += dec_lat_pack_blocks((uint32_t)cnt[k], CCMI_LATENT_I32);
+            ++N.n;
+        }
+    }
+    r.lat.push_back(N);
+    r.tab_used = r.lat_tab() + nj * sizeof(DecLatPackJob);
+}
+
+// Latent-store source: an unpack job per grid of every output frame, over the rectangle of
+// the plane the frame's tail reads (whole planes unless the tail runs on windows).
+void build_unpack_jobs(Run &r)
+{
+    const ccmi_latents &h = *r.rq.src;
+    DecLatUnpackJob *jobs = reinterpret_cast<DecLatUnpackJob *>(r.tab.data() + r.lat_tab());
+    size_t nj = 0;
+    Run::LatLaunch L{0, 0, 0};
+    for (const FramePlan &p : r.pl.fr) {
+        const LatentStream &S = h.s[p.src];
+        for (int l = 0; l < p.f.n_layers; ++l) {
+            const DecWindow &w = p.tail.roi.lat[l];
+            const uint32_t blocks = dec_lat_unpack_blocks(w);
+            if (!blocks) continue;
+            jobs[nj++] = DecLatUnpackJob{p.f.lat_n[l] ? h.store + S.grid_off[l] : nullptr,
+                                         reinterpret_cast<int32_t *>(r.dev + p.lat_off) + p.tail.ups.off[l],
+                                         p.f.lw[l], w.y0, w.y1, w.x0, w.x1, L.blocks, kArmPrec, 0};
+            L.blocks += blocks;
+            ++L.n;
+        }
+    }
+    r.lat.push_back(L);
+    r.tab_used = r.lat_tab() + nj * sizeof(DecLatUnpackJob);
+}
+
+int launch_lat(const Run &r, const Run::LatLaunch &L, int type, hipStream_t cs)
+{
+    const uint8_t *tab = r.dev + r.pl.lat_tab_off;
+    if (r.rq.src)
+        return launch_dec_lat_unpack(reinterpret_cast<const DecLatUnpackJob *>(tab) + L.first, L.n, L.blocks, type, cs);
+    return launch_dec_lat_pack(reinterpret_cast<const DecLatPackJob *>(tab) + L.first, L.n, L.blocks, type, cs);
 }
 
 // the per-frame tail of a frame the batched tail does not take: pyramid, synthesis per
@@ -552,7 +645,12 @@ int launch_chunk(const Run &r, int c, hipStream_t cs, hipEvent_t arm_done)
         if (g.chunk == c)
             if (int rc = launch_dec_arm(descs + g.first, (int)g.streams.size(), r.max_w, r.max_blocks, g.d, g.nh, cs))
                 return rc;
+    // a render's planes come from the store: the unpack stands where the ARM stage does
+    if (r.rq.src)
+        if (int rc = launch_lat(r, r.lat[0], r.rq.src->type, cs)) return rc;
     if (arm_done) CCMI_HIP_CHECK(hipEventRecord(arm_done, cs));
+    if (r.rq.lat_store) // a store build has no tail: the chunk's planes are packed instead
+        return launch_lat(r, r.lat[c], r.rq.lat_store->type, cs);
     for (const TailGroup &g : r.tails)
         if (g.chunk == c)
             if (int rc = launch_dec_tail_batch(g.frames.data(), (int)g.frames.size(), r.dev + r.pl.tail_off + g.off, cs))
@@ -649,6 +747,10 @@ int read_back(const Run &r)
 {
     const DecodePlan &pl = r.pl;
     const int n = (int)pl.fr.size();
+    if (r.rq.src) { // no ARM ran: no status words, and the flag record stays empty
+        CCMI_HIP_CHECK(hipStreamSynchronize(r.s));
+        return CCMI_OK;
+    }
     int32_t *const *lat_out = r.rq.lat_out;
     for (int i = 0; i < n && lat_out; ++i)
         CCMI_HIP_CHECK(hipMemcpyAsync(lat_out[i], r.dev + pl.fr[i].lat_off, pl.fr[i].lat_elems * 4, hipMemcpyDeviceToHost, r.s));
@@ -666,6 +768,15 @@ int read_back(const Run &r)
                                       "decode: stream %d, latent grid %d: the ARM decode's wave hand-off gave up "
                                       "after %d polls; output discarded",
                                       i, l, r.spin_cap);
+    for (int i = 0; i < n && r.rq.lat_store; ++i)
+        for (int l = 0; l < CCMI_MAX_GRIDS; ++l)
+            if (st[(size_t)i * CCMI_MAX_GRIDS + l] & CCMI_ARM_FLAG_NARROW) {
+                static const char *const kName[] = {"int8", "int16", "int32"};
+                return ccmi_set_error(CCMI_ERR_UNSUPPORTED,
+                                      "latents: stream %d, latent grid %d: a latent does not fit %s; build the store "
+                                      "with a wider element type",
+                                      i, l, kName[r.rq.lat_store->type]);
+            }
     for (int i = 0; i < n && lat_out; ++i)
         for (size_t k = 0; k < pl.fr[i].lat_elems; ++k) lat_out[i][k] >>= kArmPrec;
 #if defined(CCMI_ARM_STAMPS)
@@ -714,8 +825,11 @@ void store_timing(const Run &r, const EventSet &ev, const StreamSet *fk)
 int decode_run(const DecodeRequest &rq, DecodePlan &pl, hipStream_t s)
 {
     Run r{rq, pl, s};
-    if (int rc = decode_weights_all(pl.fr)) return rc;
-    stage_constants(r);
+    const bool render = rq.src != nullptr;
+    if (!render) { // a render takes the decoded networks and their 24-bit facts from the handle
+        if (int rc = decode_weights_all(pl.fr)) return rc;
+        stage_constants(r);
+    }
     r.dev = static_cast<uint8_t *>(rq.ws);
     if (r.dev) {
         if (rq.ws_bytes < pl.total)
@@ -732,12 +846,24 @@ int decode_run(const DecodeRequest &rq, DecodePlan &pl, hipStream_t s)
     EventSet ev;
     StreamSetLease lease;
     ev.rec(0, s);
-    CCMI_HIP_CHECK(hipMemcpyAsync(r.dev, r.host.data(), pl.cst, hipMemcpyHostToDevice, s));
-    CCMI_HIP_CHECK(hipMemsetAsync(r.status(), 0, 4 * pl.n_status(), s));
+    if (!render) {
+        CCMI_HIP_CHECK(hipMemcpyAsync(r.dev, r.host.data(), pl.cst, hipMemcpyHostToDevice, s));
+        CCMI_HIP_CHECK(hipMemsetAsync(r.status(), 0, 4 * pl.n_status(), s));
+    }
     r.spin_cap = arm_spin_cap();
     assign_chunks(r);
-    if (int rc = build_arm_groups(r)) return rc;
-    if (int rc = build_tail_groups(r)) return rc;
+    if (!render)
+        if (int rc = build_arm_groups(r)) return rc;
+    // the tables of the call: the tail groups', then the latent store's jobs, in one copy
+    r.tab.assign(r.lat_tab() + pl.lat_tab_cap + 1, 0);
+    if (!rq.lat_store)
+        if (int rc = build_tail_groups(r)) return rc;
+    if (rq.lat_store) build_pack_jobs(r);
+    if (render) build_unpack_jobs(r);
+    if (r.tab_used)
+        CCMI_HIP_CHECK(hipMemcpyAsync(r.dev + pl.tail_off, r.tab.data(), r.tab_used, hipMemcpyHostToDevice, s));
+    if (rq.lat_store) // the networks' integers: constant part -> store, before the chunks fork
+        if (int rc = launch_lat(r, r.lat[r.K], CCMI_LATENT_I32, s)) return rc;
     ev.rec(1, s);
     if (int rc = run_chunks(r, ev, lease)) return rc;
     ev.rec(4, s);
@@ -908,6 +1034,152 @@ extern "C" int ccmi_decode_batch_dev_roi(const uint8_t *const *streams, const si
     DecodeRequest rq = request(streams, lens, n, out_bitdepth, out_chroma);
     rq.sample = sample_type;
     rq.roi = roi;
+    rq.dev = out_dev;
+    rq.caps = out_caps;
+    rq.ws = workspace;
+    rq.ws_bytes = workspace_bytes;
+    return decode_many(rq, stream);
+}
+
+extern "C" int ccmi_latents_plan(const uint8_t *const *streams, const size_t *lens, int n, int latent_type,
+                                 size_t *store_bytes, size_t *store_bytes_each, size_t *workspace_bytes)
+{
+    g_last_flags.clear();
+    if (!streams || !lens || !store_bytes || !workspace_bytes)
+        return ccmi_set_error(CCMI_ERR_ARG, "latents_plan: null argument");
+    ccmi_latents h;
+    DecodeRequest rq = request(streams, lens, n, 0, 0);
+    rq.lat_store = &h;
+    DecodePlan pl;
+    if (int rc = decode_plan(rq, pl)) return rc;
+    if (int rc = latent_store_layout(pl, latent_type, h)) return rc;
+    *store_bytes = h.store_bytes;
+    *workspace_bytes = pl.total;
+    for (int i = 0; i < n && store_bytes_each; ++i) store_bytes_each[i] = h.s[i].bytes;
+    return CCMI_OK;
+}
+
+extern "C" int ccmi_latents_decode(const uint8_t *const *streams, const size_t *lens, int n, int latent_type,
+                                   void *store, size_t store_bytes, void *workspace, size_t workspace_bytes,
+                                   void *stream, ccmi_latents **out)
+{
+    g_last_flags.clear();
+    if (!streams || !lens || !out) return ccmi_set_error(CCMI_ERR_ARG, "latents_decode: null argument");
+    *out = nullptr;
+    ccmi_latents *h = new ccmi_latents;
+    struct Drop {
+        ccmi_latents *p;
+        ~Drop() { delete p; }
+    } drop{h};
+    DecodeRequest rq = request(streams, lens, n, 0, 0);
+    rq.lat_store = h;
+    rq.ws = workspace;
+    rq.ws_bytes = workspace_bytes;
+    DecodePlan pl;
+    if (int rc = decode_plan(rq, pl)) return rc;
+    if (int rc = latent_store_layout(pl, latent_type, *h)) return rc;
+    if (store) {
+        if (store_bytes < h->store_bytes)
+            return ccmi_set_error(CCMI_ERR_ARG, "latents_decode: store of %zu bytes, need %zu", store_bytes, h->store_bytes);
+        if (reinterpret_cast<uintptr_t>(store) % 256)
+            return ccmi_set_error(CCMI_ERR_ARG, "latents_decode: the store must be 256-byte aligned");
+        h->store = static_cast<const uint8_t *>(store);
+        if (int rc = decode_run(rq, pl, static_cast<hipStream_t>(stream))) return rc;
+    } else {
+        // plan-only handle: the networks are decoded on the host, nothing touches the GPU
+        if (int rc = decode_weights_all(pl.fr)) return rc;
+        for (FramePlan &p : pl.fr) p.tail.syn.f24 = syn_weights_fit24(p.f) ? 1 : 0;
+    }
+    for (int i = 0; i < n; ++i) {
+        LatentStream &S = h->s[i];
+        S.f = std::move(pl.fr[i].f);
+        S.f24 = pl.fr[i].tail.syn.f24;
+        // nothing of the caller's streams is referred to from here on
+        for (auto &p : S.f.lat_bytes) p = nullptr;
+        for (auto &p : S.f.wbytes) p = nullptr;
+        S.f.arm.clear();
+        S.f.arm.shrink_to_fit();
+    }
+    drop.p = nullptr;
+    *out = h;
+    return CCMI_OK;
+}
+
+extern "C" void ccmi_latents_free(ccmi_latents *h) { delete h; }
+
+extern "C" int ccmi_latents_count(const ccmi_latents *h) { return h ? (int)h->s.size() : 0; }
+
+extern "C" int ccmi_latents_values(const ccmi_latents *h, int i, int32_t *out_dev, size_t cap_elems, void *stream)
+{
+    if (!h || !out_dev) return ccmi_set_error(CCMI_ERR_ARG, "latents_values: null argument");
+    if (!h->store) return ccmi_set_error(CCMI_ERR_ARG, "latents_values: the handle is plan-only (built without a store)");
+    if (i < 0 || i >= (int)h->s.size())
+        return ccmi_set_error(CCMI_ERR_ARG, "latents_values: stream %d outside the handle's %zu streams", i, h->s.size());
+    const LatentStream &S = h->s[i];
+    const FrameHost &f = S.f;
+    size_t need = 0;
+    for (int l = 0; l < f.n_layers; ++l) need += (size_t)f.lh[l] * f.lw[l];
+    if (cap_elems < need) return ccmi_set_error(CCMI_ERR_ARG, "latents_values: buffer of %zu ints, need %zu", cap_elems, need);
+    DecLatUnpackJob jobs[CCMI_MAX_GRIDS];
+    uint32_t blocks = 0;
+    size_t off = 0;
+    for (int l = 0; l < f.n_layers; ++l) {
+        const DecWindow w{0, f.lh[l], 0, f.lw[l]};
+        jobs[l] = DecLatUnpackJob{f.lat_n[l] ? h->store + S.grid_off[l] : nullptr, out_dev + off, f.lw[l], 0, w.y1, 0, w.x1,
+                                  blocks, 0, 0};
+        blocks += dec_lat_unpack_blocks(w);
+        off += (size_t)f.lh[l] * f.lw[l];
+    }
+    // the job table has to sit in device memory; this call has no workspace argument
+    const hipStream_t s = static_cast<hipStream_t>(stream);
+    void *tab = nullptr;
+    CCMI_HIP_CHECK(hipMalloc(&tab, sizeof jobs));
+    struct Free {
+        void *p;
+        ~Free() { (void)hipFree(p); }
+    } guard{tab};
+    CCMI_HIP_CHECK(hipMemcpyAsync(tab, jobs, sizeof(DecLatUnpackJob) * f.n_layers, hipMemcpyHostToDevice, s));
+    if (int rc = launch_dec_lat_unpack(static_cast<const DecLatUnpackJob *>(tab), f.n_layers, blocks, h->type, s)) return rc;
+    CCMI_HIP_CHECK(hipStreamSynchronize(s));
+    return CCMI_OK;
+}
+
+static int latents_request(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi, int out_bitdepth,
+                           int out_chroma, int sample_type, DecodeRequest &rq)
+{
+    if (!h) return ccmi_set_error(CCMI_ERR_ARG, "render: the handle is NULL (no frame 0)");
+    if (sample_type < 0) return ccmi_set_error(CCMI_ERR_ARG, "decode: unknown sample type %d", sample_type);
+    rq = request(nullptr, nullptr, m, out_bitdepth, out_chroma);
+    rq.src = h;
+    rq.index = index;
+    rq.sample = sample_type;
+    rq.roi = roi;
+    return CCMI_OK;
+}
+
+extern "C" int ccmi_latents_render_plan(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
+                                        int out_bitdepth, int out_chroma, int sample_type, ccmi_frame_geom *geom,
+                                        ccmi_roi_info *info, size_t *workspace_bytes)
+{
+    g_last_flags.clear();
+    DecodeRequest rq;
+    if (int rc = latents_request(h, index, m, roi, out_bitdepth, out_chroma, sample_type, rq)) return rc;
+    if (!geom || !workspace_bytes) return ccmi_set_error(CCMI_ERR_ARG, "latents_render_plan: null argument");
+    rq.geom = geom;
+    rq.info = info;
+    return plan_only(rq, workspace_bytes);
+}
+
+extern "C" int ccmi_latents_render(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
+                                   void *const *out_dev, const size_t *out_caps, int sample_type, int out_bitdepth,
+                                   int out_chroma, void *workspace, size_t workspace_bytes, void *stream)
+{
+    g_last_flags.clear();
+    DecodeRequest rq;
+    if (int rc = latents_request(h, index, m, roi, out_bitdepth, out_chroma, sample_type, rq)) return rc;
+    if (!h->store)
+        return ccmi_set_error(CCMI_ERR_ARG, "render: the handle is plan-only (built without a store): no frame 0 to render");
+    if (!out_dev || !out_caps) return ccmi_set_error(CCMI_ERR_ARG, "latents_render: null argument");
     rq.dev = out_dev;
     rq.caps = out_caps;
     rq.ws = workspace;

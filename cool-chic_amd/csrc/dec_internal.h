@@ -130,11 +130,15 @@ struct DecWindow {
 // What a region decode of one frame computes: rect = the region (level-0 coordinates);
 // lev[k] = the window of pyramid level k the region needs (lev[0]: the synthesis input,
 // the region grown by the 3x3 layers' reach and clipped to the frame); arm_rows[l] = the
-// rows of latent grid l those windows read.  Planned on the host (dec_roi_plan).
+// rows of latent grid l those windows read; lat[l] = the rectangle of grid l they read (grid
+// l < L-1: lev[l] grown by the refine's pre_ks / 2 on every side, clipped to the plane; the
+// coarsest grid: lev[L-1]), which is what a render from a latent store unpacks.  Planned on
+// the host (dec_roi_plan).
 struct DecRoi {
     DecWindow rect;
     DecWindow lev[CCMI_MAX_GRIDS];
     int arm_rows[CCMI_MAX_GRIDS];
+    DecWindow lat[CCMI_MAX_GRIDS];
 };
 // syn_halo: the sum of (ks - 1) / 2 over the synthesis layers
 void dec_roi_plan(const int *lh, const int *lw, int L, int ups_ks, int pre_ks, int syn_halo, const DecWindow &rect,
@@ -168,5 +172,34 @@ size_t dec_tail_table_bytes(int n_layers, int n, bool windowed = false);
 void dec_tail_fill(const DecTailFrame *const *fr, int n, void *host_tab);
 // fr: the group's frames, in table order (a window-form group sizes its grids by their windows)
 int launch_dec_tail_batch(const DecTailFrame *const *fr, int n, const void *dev_tab, hipStream_t s);
+
+// Latent store (dec_latents.hip): the ARM output planes (int32, value << kArmPrec) packed to
+// values of the store's element type (CCMI_LATENT_*), and back.  Both kernels are table-driven:
+// a job owns the blocks [first_block, the next job's first_block) of the launch; the tables
+// live in device memory and are filled on the host.
+struct DecLatPackJob {
+    const int32_t *src;   // 16-byte aligned
+    void *dst;            // 16-byte aligned, n values
+    uint32_t *status;     // the grid's status word: CCMI_ARM_FLAG_NARROW is OR-ed in on a misfit
+    uint32_t n;
+    uint32_t first_block;
+    int shift;            // kArmPrec for latent planes; 0: a plain int32 copy (the networks' integers)
+    int pad_;
+};
+struct DecLatUnpackJob {
+    const void *src;      // the grid's packed values, whole plane, pitch w; NULL: an all-zero grid
+    int32_t *dst;         // plane at pitch w
+    int w;
+    int y0, y1, x0, x1;   // the rectangle to write
+    uint32_t first_block;
+    int shift;            // kArmPrec for the tail's planes; 0: the values themselves
+    int pad_;
+};
+size_t dec_lat_elem_bytes(int type); // 0: not a CCMI_LATENT_* type
+uint32_t dec_lat_pack_blocks(uint32_t n, int type);
+uint32_t dec_lat_unpack_blocks(const DecWindow &r);
+// jobs: device table of n_jobs entries whose first_block counts from 0; n_blocks = their total
+int launch_dec_lat_pack(const DecLatPackJob *jobs, int n_jobs, uint32_t n_blocks, int type, hipStream_t s);
+int launch_dec_lat_unpack(const DecLatUnpackJob *jobs, int n_jobs, uint32_t n_blocks, int type, hipStream_t s);
 
 } // namespace ccmi

@@ -89,16 +89,22 @@ int plan_tensor_sink(const DecodeRequest &rq, int i, FramePlan &p)
     DecTailFrame &t = p.tail;
     size_t elems = 0;
     DecWindow rect{0, f.h, 0, f.w};
+    const char *who = rq.src ? "frame" : "stream"; // a render's outputs are frames of the handle's streams
     if (rq.roi) {
         const ccmi_rect &q = rq.roi[i];
         if (q.w < 1 || q.h < 1 || q.x < 0 || q.y < 0 || q.x > f.w - q.w || q.y > f.h - q.h)
-            return ccmi_set_error(CCMI_ERR_ARG, "stream %d: region x %d y %d w %d h %d outside the %d x %d frame", i, q.x,
-                                  q.y, q.w, q.h, f.w, f.h);
+            return ccmi_set_error(CCMI_ERR_ARG, "%s %d: region x %d y %d w %d h %d outside the %d x %d frame", who, i,
+                                  q.x, q.y, q.w, q.h, f.w, f.h);
         rect = DecWindow{q.y, q.y + q.h, q.x, q.x + q.w};
     }
-    if (int rc = tensor_format(f, rq.out_bitdepth, rq.out_chroma, rq.sample, p.of, &elems, rect)) return rc;
+    if (int rc = tensor_format(f, rq.out_bitdepth, rq.out_chroma, rq.sample, p.of, &elems, rect)) {
+        if (!rq.src) return rc;
+        std::string m = ccmi_last_error();
+        return ccmi_set_error(rc, "frame %d: %s", i, m.c_str());
+    }
     if (p.of.kind == kYuv420 && ((rect.x0 | rect.y0) & 1))
-        return ccmi_set_error(CCMI_ERR_ARG, "stream %d: a 420 region needs an even origin (x %d y %d)", i, rect.x0, rect.y0);
+        return ccmi_set_error(CCMI_ERR_ARG, "%s %d: a 420 region needs an even origin (x %d y %d)", who, i, rect.x0,
+                              rect.y0);
     int halo = 0;
     for (const SynLayerDesc &L : f.layers) halo += (L.ks - 1) / 2;
     if (rect.h() == f.h && rect.w() == f.w) {
@@ -137,31 +143,47 @@ int plan_tensor_sink(const DecodeRequest &rq, int i, FramePlan &p)
 // error an input reports.
 int plan_frame(const DecodeRequest &rq, int i, FramePlan &p)
 {
-    if (!rq.streams[i]) return ccmi_set_error(CCMI_ERR_ARG, "decode: stream %d is NULL", i);
-    if (int rc = parse_frame_header(rq.streams[i], rq.lens[i], p.f)) {
-        std::string m = ccmi_last_error();
-        return ccmi_set_error(rc, "stream %d: %s", i, m.c_str());
+    if (rq.src) { // the header facts and the networks come from the handle: nothing is parsed or decoded
+        const int n_src = (int)rq.src->s.size();
+        p.src = rq.index ? rq.index[i] : i;
+        if (p.src < 0 || p.src >= n_src)
+            return ccmi_set_error(CCMI_ERR_ARG, "frame %d: index %d outside the handle's %d streams", i, p.src, n_src);
+        p.f = rq.src->s[p.src].f;
+    } else {
+        if (!rq.streams[i]) return ccmi_set_error(CCMI_ERR_ARG, "decode: stream %d is NULL", i);
+        if (int rc = parse_frame_header(rq.streams[i], rq.lens[i], p.f)) {
+            std::string m = ccmi_last_error();
+            return ccmi_set_error(rc, "stream %d: %s", i, m.c_str());
+        }
     }
     const FrameHost &f = p.f;
     DecTailFrame &t = p.tail;
     tail_arch(f, t);
+    if (rq.src) t.syn.f24 = rq.src->s[p.src].f24;
     p.batchable = f.n_branches == 1 && dec_tail_batchable(t);
     if (rq.device()) {
         if (int rc = plan_tensor_sink(rq, i, p)) return rc;
+    } else if (rq.lat_store) { // no tail, no output: every latent row
+        for (int l = 0; l < f.n_layers; ++l) t.roi.arm_rows[l] = f.lh[l];
     } else {
         if (int rc = out_format(f, rq.out_bitdepth, rq.out_chroma, rq.as_yuv, p.of)) return rc;
         for (int l = 0; l < f.n_layers; ++l) t.roi.arm_rows[l] = f.lh[l];
     }
+    // the pack kernel loads its sources 16 bytes at a time: a store build starts every plane on 4 values
+    const int plane_align = rq.lat_store ? 4 : 1;
+    p.lat_elems = 0;
     for (int l = 0, off = 0; l < f.n_layers; ++l) {
         t.ups.off[l] = off;
-        off += t.roi.arm_rows[l] * f.lw[l];
+        off += (t.roi.arm_rows[l] * f.lw[l] + plane_align - 1) / plane_align * plane_align;
+        p.lat_elems = (size_t)off;
     }
     t.bitdepth = p.of.bitdepth;
     t.kind = p.of.kind;
     t.sample = rq.sample;
     const size_t bytes = p.of.header + p.of.payload;
     if ((rq.outs || rq.dev) && rq.caps && rq.caps[i] < bytes)
-        return ccmi_set_error(CCMI_ERR_ARG, "stream %d: output buffer of %zu bytes, need %zu", i, rq.caps[i], bytes);
+        return ccmi_set_error(CCMI_ERR_ARG, "%s %d: output buffer of %zu bytes, need %zu", rq.src ? "frame" : "stream", i,
+                              rq.caps[i], bytes);
     if (rq.sizes) rq.sizes[i] = bytes;
     return CCMI_OK;
 }
@@ -170,8 +192,12 @@ int plan_frame(const DecodeRequest &rq, int i, FramePlan &p)
 // then every frame's scratch, then the call's tables.
 void plan_layout(const DecodeRequest &rq, DecodePlan &pl)
 {
+    // A render from a latent store has no constant part (the tail reads the networks from the
+    // store), no ARM descriptors and no status words; a store build has no tail scratch.
+    const bool render = rq.src != nullptr, build = rq.lat_store != nullptr;
     size_t cst = 0;
     for (FramePlan &p : pl.fr) {
+        if (render) break;
         const FrameHost &f = p.f;
         for (int l = 0; l < f.n_layers; ++l) {
             p.bytes_off[l] = cst;
@@ -188,19 +214,18 @@ void plan_layout(const DecodeRequest &rq, DecodePlan &pl)
     size_t tot = align_up(cst, 4096);
     for (FramePlan &p : pl.fr) {
         const FrameHost &f = p.f;
+        p.lat_off = tot;
+        tot += align_up(p.lat_elems * 4, 256);
+        if (build) continue;
         // a region decode on windows: the latent planes keep their frame pitch and hold the rows
         // the ARM decode produces, the pyramid stacks and the synthesis output hold the windows
         const DecRoi &R = p.tail.roi;
         const bool win = p.mode == kTailWindow;
-        p.lat_elems = 0;
-        for (int l = 0; l < f.n_layers; ++l) p.lat_elems += (size_t)R.arm_rows[l] * f.lw[l];
         p.ws_elems = win ? dec_ups_workspace_elems_win(R, f.n_layers) : dec_ups_workspace_elems(f.lh, f.lw, f.n_layers);
         p.dense_elems = win ? (size_t)f.n_layers * R.lev[0].h() * R.lev[0].w() : (size_t)f.n_layers * f.h * f.w;
         p.synout_elems = win ? (size_t)f.layers.back().n_out * R.rect.h() * R.rect.w()
                              : (size_t)f.layers.back().n_out * f.h * f.w * f.n_branches;
         p.synws_elems = dec_syn_workspace_elems(p.tail.syn);
-        p.lat_off = tot;
-        tot += align_up(p.lat_elems * 4, 256);
         p.ws_off = tot;
         tot += align_up(p.ws_elems * 4 + 4, 256);
         p.dense_off = tot;
@@ -213,14 +238,23 @@ void plan_layout(const DecodeRequest &rq, DecodePlan &pl)
         if (!rq.device()) tot += align_up(p.of.payload, 256); // device sinks write to the caller's memory
     }
     pl.desc_off = tot;
-    tot += align_up(sizeof(ArmStreamDesc) * pl.n_status(), 256);
+    if (!render) tot += align_up(sizeof(ArmStreamDesc) * pl.n_status(), 256);
     // batched-tail argument tables: bounded by one single-frame table per frame
     pl.tail_cap = 0;
-    for (const FramePlan &p : pl.fr) pl.tail_cap += dec_tail_table_bytes(p.f.n_layers, 1, p.mode == kTailWindow);
+    for (const FramePlan &p : pl.fr)
+        if (!build) pl.tail_cap += dec_tail_table_bytes(p.f.n_layers, 1, p.mode == kTailWindow);
     pl.tail_off = tot;
     tot += align_up(pl.tail_cap, 256);
+    // the pack / unpack job table follows the tail tables: one host image, one upload.  A build
+    // has a job per grid and two more per stream (the networks' integers), a render one per grid.
+    pl.lat_tab_off = tot;
+    pl.lat_tab_cap = 0;
+    for (const FramePlan &p : pl.fr)
+        pl.lat_tab_cap += build ? sizeof(DecLatPackJob) * (size_t)(p.f.n_layers + 2)
+                                : render ? sizeof(DecLatUnpackJob) * (size_t)p.f.n_layers : 0;
+    tot += align_up(pl.lat_tab_cap, 256);
     pl.status_off = tot;
-    tot += align_up(4 * pl.n_status(), 256);
+    if (!render) tot += align_up(4 * pl.n_status(), 256);
 #if defined(CCMI_ARM_STAMPS)
     pl.dbg_off = tot;
     tot += align_up(16 * 8 * pl.n_status(), 256);
@@ -232,12 +266,41 @@ void plan_layout(const DecodeRequest &rq, DecodePlan &pl)
 
 int decode_plan(const DecodeRequest &rq, DecodePlan &pl)
 {
-    if (rq.n < 1) return ccmi_set_error(CCMI_ERR_ARG, "decode: no streams");
+    if (rq.n < 1) return ccmi_set_error(CCMI_ERR_ARG, rq.src ? "render: no frames (m < 1)" : "decode: no streams");
+    if (rq.src && !rq.index && rq.n != (int)rq.src->s.size())
+        return ccmi_set_error(CCMI_ERR_ARG, "render: %d frames without an index, the handle has %zu streams", rq.n,
+                              rq.src->s.size());
     pl = DecodePlan{};
     pl.fr.resize(rq.n);
     for (int i = 0; i < rq.n; ++i)
         if (int rc = plan_frame(rq, i, pl.fr[i])) return rc;
     plan_layout(rq, pl);
+    return CCMI_OK;
+}
+
+int latent_store_layout(const DecodePlan &pl, int type, ccmi_latents &h)
+{
+    const size_t eb = dec_lat_elem_bytes(type);
+    if (!eb) return ccmi_set_error(CCMI_ERR_ARG, "latents: unknown element type %d", type);
+    h.type = type;
+    h.s.resize(pl.fr.size());
+    size_t pos = 0;
+    for (size_t i = 0; i < pl.fr.size(); ++i) {
+        const FrameHost &f = pl.fr[i].f;
+        LatentStream &S = h.s[i];
+        S.off = pos;
+        S.ups_off = pos;
+        pos += align_up(f.ups.size() * 4, 16);
+        S.syn_off = pos;
+        pos += align_up(f.syn.size() * 4, 16);
+        for (int l = 0; l < f.n_layers; ++l) {
+            S.grid_off[l] = pos;
+            if (f.lat_n[l]) pos += align_up((size_t)f.lh[l] * f.lw[l] * eb, 16);
+        }
+        pos = align_up(pos, 256);
+        S.bytes = pos - S.off;
+    }
+    h.store_bytes = pos;
     return CCMI_OK;
 }
 

@@ -7,6 +7,28 @@
 
 namespace ccmi {
 
+// One stream of a latent store (ccmi_latents): what a render needs of it on the host, and
+// where its parts sit in the device store (bytes from the store's base).
+struct LatentStream {
+    FrameHost f;  // header facts and decoded networks; refers to no coded bytes (pointers cleared, ARM dropped)
+    int f24 = 0;  // DecSynArgs::f24, computed once at the build
+    size_t off = 0, bytes = 0; // the stream's part of the store, 256-byte aligned and rounded
+    size_t ups_off = 0, syn_off = 0;
+    size_t grid_off[CCMI_MAX_GRIDS] = {}; // an empty grid (lat_n == 0) takes no bytes
+};
+
+} // namespace ccmi
+
+// The opaque handle of ccmi.h: immutable once built.
+struct ccmi_latents {
+    int type = 0;                 // CCMI_LATENT_*
+    const uint8_t *store = nullptr; // device; NULL: plan-only
+    size_t store_bytes = 0;
+    std::vector<ccmi::LatentStream> s;
+};
+
+namespace ccmi {
+
 enum OutKind { kYuv420 = 0, kYuv444 = 1, kPpm = 2 };
 
 struct OutFmt {
@@ -28,7 +50,10 @@ enum TailMode {
 // One call of the decode driver.  The sink is host bytes (the default): file layout, staged
 // in the workspace and copied to outs[i]; or device tensors (sample >= 0): the output kernel
 // writes planar samples of type `sample` straight to dev[i], nothing is staged and nothing
-// is downloaded.  outs / dev NULL: planning only.
+// is downloaded; or a latent store (lat_store): no decoder tail at all, the ARM output planes
+// are packed into the store.  outs / dev NULL: planning only.
+// The source is coded streams, or (src) streams of a latent store: frame i is stream index[i]
+// of the handle, the ARM stage is replaced by an unpack of the store, and n counts frames.
 struct DecodeRequest {
     const uint8_t *const *streams = nullptr;
     const size_t *lens = nullptr;
@@ -47,6 +72,11 @@ struct DecodeRequest {
     ccmi_frame_geom *geom = nullptr; // [n], optional (device sinks): filled by the plan
     ccmi_roi_info *info = nullptr;   // [n], optional (device sinks): what the region decode does
     int32_t *const *lat_out = nullptr; // [n], optional: the decoded latents, to the host
+    // latent-store sink: the layout is filled by the plan; lat_store->store NULL: planning only
+    ccmi_latents *lat_store = nullptr;
+    // latent-store source
+    const ccmi_latents *src = nullptr;
+    const int *index = nullptr; // [n], optional: NULL = frame i is stream i (n == the handle's count)
     // caller-owned device workspace (NULL: one hipMalloc per call)
     void *ws = nullptr;
     size_t ws_bytes = 0;
@@ -60,6 +90,7 @@ struct FramePlan {
     int mode = kTailFrame;
     bool batchable = false; // single branch and an architecture the batched tail takes
     bool arm24 = false;     // every ARM weight fits 24 signed bits (decode_run, once they are decoded)
+    int src = -1;           // latent-store source: the handle's stream this frame renders
     // tail arguments: architecture, output format and region (tail.roi) from the plan, device
     // pointers and syn.f24 from decode_run
     DecTailFrame tail;
@@ -79,6 +110,8 @@ struct DecodePlan {
     size_t tail_off = 0;   // batched-tail argument tables, tail_cap bytes
     size_t tail_cap = 0;
     size_t status_off = 0; // one word per (frame, latent grid): the ARM kernels' CCMI_ARM_FLAG_* bits
+    size_t lat_tab_off = 0; // latent-store sink / source: the pack / unpack job table, lat_tab_cap bytes
+    size_t lat_tab_cap = 0;
 #if defined(CCMI_ARM_STAMPS)
     size_t dbg_off = 0;
 #endif
@@ -88,5 +121,10 @@ struct DecodePlan {
 // Header parse, argument and region validation, output sizes (rq.sizes / geom / info are
 // filled) and the workspace layout.  No weights are decoded and nothing touches the GPU.
 int decode_plan(const DecodeRequest &rq, DecodePlan &pl);
+
+// Layout of a latent store for the planned frames' streams at element type `type` (the
+// contract in ccmi.h): fills h.type, h.s[i].off / bytes / ups_off / syn_off / grid_off and
+// h.store_bytes (h.s sized here, the FrameHosts left alone).  Host arithmetic.
+int latent_store_layout(const DecodePlan &pl, int type, ccmi_latents &h);
 
 } // namespace ccmi

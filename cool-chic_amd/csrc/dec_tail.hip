@@ -712,6 +712,16 @@ void dec_roi_plan(const int *lh, const int *lw, int L, int ups_ks, int pre_ks, i
         r.lev[k] = DecWindow{lo(d.y0), hi(d.y1, lh[k]), lo(d.x0), hi(d.x1, lw[k])};
     }
     for (int l = 0; l < L; ++l) r.arm_rows[l] = l == L - 1 ? r.lev[l].y1 : std::min(lh[l], r.lev[l].y1 + pre_ks / 2);
+    // What is read of each latent plane: the refine's taps around lev[l] (its tile loads reach
+    // further, but those lanes' results are discarded); the coarsest plane is the raw source of
+    // the first step, whose reads are clamped to lev[L-1].
+    const int rp = pre_ks / 2;
+    for (int l = 0; l < L; ++l) {
+        const DecWindow &d = r.lev[l];
+        r.lat[l] = l == L - 1 ? d
+                              : DecWindow{std::max(0, d.y0 - rp), std::min(lh[l], d.y1 + rp), std::max(0, d.x0 - rp),
+                                          std::min(lw[l], d.x1 + rp)};
+    }
 }
 
 size_t dec_ups_workspace_elems_win(const DecRoi &r, int L)

@@ -229,6 +229,7 @@ int ccmi_decode_last_timing(float *ms4);
 #define CCMI_ARM_FLAG_W32 4u      /* an ARM weight >= 2^23: every layer in 32-bit products */
 #define CCMI_ARM_FLAG_PRE32 8u    /* chain helper wave: a chunk's contexts left 22 bits (32-bit sums) */
 #define CCMI_ARM_FLAG_BIG 16u     /* spec / one-latent kernels: a |q| >= 2^15, layer 0 in 32-bit */
+#define CCMI_ARM_FLAG_NARROW 32u  /* ccmi_latents_decode: a latent does not fit the store's element type */
 int ccmi_decode_last_arm_flags(uint32_t *flags, int cap, int *n);
 
 /* The integer latents of one intra stream (ARM + CABAC decode on the GPU; values, not
@@ -330,6 +331,75 @@ int ccmi_decode_batch_dev_roi(const uint8_t *const *streams, const size_t *lens,
                               const ccmi_rect *roi /* [n] or NULL */, void *const *out_dev,
                               const size_t *out_caps, int sample_type, int out_bitdepth,
                               int out_chroma, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Decode once, render often: a resident form of decoded streams.  The ARM + CABAC chain is
+ * serial in raster order and its output, the integer latents, does not depend on the region,
+ * the output bitdepth, the chroma format or the sample type.  ccmi_latents_decode() runs that
+ * chain once and keeps the latents (packed to latent_type values) and the upsampling and
+ * synthesis integers in a caller-owned device store; ccmi_latents_render() then produces any
+ * region of any of the streams at the cost of the decoder tail alone.
+ * THE SAMPLES ccmi_latents_render WRITES ARE, ONE FOR ONE, THOSE ccmi_decode_batch_dev_roi
+ * WRITES FOR THE SAME STREAM, REGION AND OUTPUT ARGUMENTS.
+ *
+ * The handle is opaque and no global: it holds no lock, the render calls take it const, and
+ * any number of threads may render from one handle (each with its own workspace and stream).
+ * It lives on the host (parsed headers, decoded networks, the store's layout) and never refers
+ * to `streams` or `workspace` after ccmi_latents_decode returns; the store memory stays the
+ * caller's and must outlive the handle's last render.
+ *
+ * ccmi_latents_plan(): header-only (no CABAC, no GPU): bytes of the device store for these
+ * streams at this element type (store_bytes_each[n] optional) and the workspace the build
+ * needs.  Store layout: stream i starts 256-byte aligned at the sum of store_bytes_each[< i];
+ * it holds the upsampling integers, the synthesis integers, then each latent grid's h_l * w_l
+ * values, every part 16-byte aligned, and store_bytes_each[i] is its size rounded up to 256 (so
+ * store_bytes is the sum).  A grid whose coded substream is empty takes no store bytes and
+ * renders as zeros.  Per stream the store is at most 4 (ups + syn + blend ints) + N sizeof(T) +
+ * 256 (n_grids + 4) bytes, N = the stream's latents.
+ *
+ * ccmi_latents_decode(): store = device memory, 256-byte aligned, >= store_bytes; workspace as
+ * for ccmi_decode_batch_dev (NULL: allocated for the call).  A latent that does not fit the
+ * element type (I8: -128..127, I16: -32768..32767) is never saturated or wrapped: the call
+ * returns CCMI_ERR_UNSUPPORTED naming the first such stream, its grid and the type, creates no
+ * handle, and ccmi_decode_last_arm_flags() shows CCMI_ARM_FLAG_NARROW for exactly the streams
+ * that need a wider type.  The other ARM flags and TIMEOUT (CCMI_ERR_HIP) are reported as by
+ * every decode.  store == NULL: no GPU call is made and the handle is plan-only
+ * (ccmi_latents_render_plan works, ccmi_latents_render and ccmi_latents_values are
+ * CCMI_ERR_ARG).  ccmi_decode_last_timing(): [1] the ARM + CABAC stage, [2] the pack.
+ *
+ * ccmi_latents_values(): stream i's latents as int32 values on the device, grids flattened in
+ * order (the device counterpart of ccmi_decode_latents); cap_elems >= sum_l h_l * w_l.
+ *
+ * ccmi_latents_render_plan() / ccmi_latents_render(): m output frames; frame j is stream
+ * index[j] of the handle (index NULL: m must equal the handle's count and frame j is stream j;
+ * repeats and any order are allowed), region roi[j] (roi NULL, or a rect of 0, 0, W, H: the
+ * whole frame).  geom, info, the sample types, out_caps, the one-sample alignment rule, the 420
+ * even-origin rule and the error for a region outside the frame are those of
+ * ccmi_decode_batch_dev_roi(_plan); info[j].arm_rows are the latent rows the tail's planes hold.
+ * index[j] outside [0, count), m < 1, a NULL handle, and a plan-only handle passed to
+ * ccmi_latents_render are CCMI_ERR_ARG, found before any HIP call, the message naming frame j.
+ * The render workspace holds the tail's scratch and tables only: no coded bytes, no networks
+ * (the tail reads them from the store), no ARM descriptors.  Both GPU calls synchronise
+ * `stream` before they return.  The render calls run no ARM: they clear the ARM flag record
+ * (ccmi_decode_last_arm_flags: *n = 0), and ccmi_decode_last_timing() after a render reports
+ * [0] the table upload, [1] the unpack of the store into the tail's planes, [2] the tail, [3] 0. */
+typedef struct ccmi_latents ccmi_latents;
+enum { CCMI_LATENT_I8 = 0, CCMI_LATENT_I16 = 1, CCMI_LATENT_I32 = 2 };
+int ccmi_latents_plan(const uint8_t *const *streams, const size_t *lens, int n, int latent_type,
+                      size_t *store_bytes, size_t *store_bytes_each /* [n] or NULL */, size_t *workspace_bytes);
+int ccmi_latents_decode(const uint8_t *const *streams, const size_t *lens, int n, int latent_type,
+                        void *store, size_t store_bytes, void *workspace, size_t workspace_bytes,
+                        void *stream, ccmi_latents **out);
+void ccmi_latents_free(ccmi_latents *h); /* host side only; NULL is a no-op */
+int ccmi_latents_count(const ccmi_latents *h);
+int ccmi_latents_values(const ccmi_latents *h, int i, int32_t *out_dev, size_t cap_elems, void *stream);
+int ccmi_latents_render_plan(const ccmi_latents *h, const int *index /* [m] or NULL */, int m,
+                             const ccmi_rect *roi /* [m] or NULL */, int out_bitdepth, int out_chroma,
+                             int sample_type, ccmi_frame_geom *geom /* [m] */, ccmi_roi_info *info /* [m] or NULL */,
+                             size_t *workspace_bytes);
+int ccmi_latents_render(const ccmi_latents *h, const int *index /* [m] or NULL */, int m,
+                        const ccmi_rect *roi /* [m] or NULL */, void *const *out_dev, const size_t *out_caps,
+                        int sample_type, int out_bitdepth, int out_chroma, void *workspace,
+                        size_t workspace_bytes, void *stream);
 
 /* Network weights of a stream's intra frame as the decoder's fixed-point integers
  * (cc-frame-decoder.cpp:201-353, read_arm / read_ups / read_syn):

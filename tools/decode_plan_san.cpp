@@ -1,13 +1,14 @@
 // decode_plan_san.cpp -- stand-alone host program for a sanitizer run of the decoder's planner
-// (decode_plan, dec_plan.cpp) on a machine without a GPU: every header-only entry point over
-// the streams named on the command line, whole, in batches of 7, over a list of regions, and
+// (decode_plan, dec_plan.cpp) on a machine without a GPU: every header-only entry point, the
+// latent store's layout and plan-only handles (ccmi_latents_*, store = NULL) with their render
+// planning included, over the streams named on the command line, whole, in batches of 7, over a list of regions, and
 // truncated at each length from 0 to the header size plus 8.  Every (truncated) stream sits in
 // a heap block of exactly its length, so a read past its end is reported.  No HIP call is made.
 //
 //   cd cool-chic_amd && hipcc -O1 -g -std=c++17 -fwrapv --offload-arch=gfx950 \
 //       -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
 //       -x hip ../tools/decode_plan_san.cpp csrc/dec_plan.cpp csrc/dec_host.cpp csrc/ccmi_api.cpp \
-//       csrc/dec_arm.hip csrc/dec_tail.hip -o /tmp/decode_plan_san
+//       csrc/dec_arm.hip csrc/dec_tail.hip csrc/dec_latents.hip -o /tmp/decode_plan_san
 //   /tmp/decode_plan_san $(find ../tests/golden/cool ../tests/golden/cool_synth -name '*.cool')
 #include <stdio.h>
 #include <stdlib.h>
@@ -68,6 +69,35 @@ void plan_all(const std::vector<Stream> &b, const std::vector<ccmi_rect> &rects,
         count(ccmi_decode_batch_dev_roi_plan(sp.data(), ln.data(), n, nullptr, bd, chroma, sample, geom.data(), nullptr,
                                              &need));
     }
+    // the latent store: layout at every element type, a plan-only handle (no GPU call), and the
+    // render planning over it: in order, through an index with repeats and out-of-range entries
+    std::vector<size_t> each(n);
+    size_t store = 0;
+    for (int type = 0; type < 4; ++type)
+        count(ccmi_latents_plan(sp.data(), ln.data(), n, type, &store, type & 1 ? each.data() : nullptr, &need));
+    ccmi_latents *h = nullptr;
+    count(ccmi_latents_decode(sp.data(), ln.data(), n, CCMI_LATENT_I16, nullptr, 0, nullptr, 0, nullptr, &h));
+    if (!h) return;
+    std::vector<int> idx(n + 2);
+    std::vector<ccmi_rect> rr(n + 2);
+    for (int j = 0; j < n + 2; ++j) idx[j] = (n - 1 - j % n + n) % n, rr[j] = rects[idx[j]];
+    std::vector<ccmi_frame_geom> g2(n + 2);
+    std::vector<ccmi_roi_info> i2(n + 2);
+    for (int sample = 0; sample < 3; ++sample) {
+        count(ccmi_latents_render_plan(h, nullptr, n, rects.data(), bd, chroma, sample, geom.data(), info.data(), &need));
+        count(ccmi_latents_render_plan(h, nullptr, n, nullptr, bd, chroma, sample, geom.data(), nullptr, &need));
+        count(ccmi_latents_render_plan(h, idx.data(), n + 2, rr.data(), bd, chroma, sample, g2.data(), i2.data(), &need));
+    }
+    idx[n] = n;
+    count(ccmi_latents_render_plan(h, idx.data(), n + 2, nullptr, bd, chroma, 1, g2.data(), i2.data(), &need));
+    idx[0] = -1;
+    count(ccmi_latents_render_plan(h, idx.data(), n + 2, nullptr, bd, chroma, 1, g2.data(), i2.data(), &need));
+    count(ccmi_latents_render_plan(h, nullptr, n + 1, nullptr, bd, chroma, 1, g2.data(), nullptr, &need));
+    void *out = nullptr;
+    size_t cap = 0;
+    count(ccmi_latents_render(h, nullptr, n, nullptr, &out, &cap, 1, bd, chroma, nullptr, 0, nullptr)); // plan-only: an error
+    if (ccmi_latents_count(h) != n) abort();
+    ccmi_latents_free(h);
 }
 
 std::vector<ccmi_rect> rects_of(int w, int h)
