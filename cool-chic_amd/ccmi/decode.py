@@ -327,6 +327,140 @@ def decode_batch_tensors(streams: Sequence[bytes], output_bitdepth: int = 0, out
     return _shape_outs(flat, outs, geom, stack)
 
 
+ELEM_F32, ELEM_F16, ELEM_BF16 = 0, 1, 2  # CCMI_ELEM_*
+COLOUR_ASIS, COLOUR_RGB = 0, 1           # CCMI_COLOUR_*
+
+
+class TensorFmt(C.Structure):
+    """ccmi_tensor_fmt: the formatted output of one call."""
+    _fields_ = [("elem", C.c_int), ("colour", C.c_int), ("scale", C.c_float * 3), ("bias", C.c_float * 3),
+                ("stride_c", C.c_int64), ("stride_y", C.c_int64), ("stride_x", C.c_int64), ("mirror", C.c_void_p)]
+
+
+def _bind_fmt():
+    L = _bind_latents()
+    if not getattr(L, "_ccmi_fmt_bound", False):
+        P, I, Z = C.c_void_p, C.c_int, C.c_size_t
+        L.ccmi_decode_batch_dev_fmt_plan.argtypes = [P, P, I, P, I, I, P, P, P, P]
+        L.ccmi_decode_batch_dev_fmt.argtypes = [P, P, I, P, P, P, P, I, I, P, Z, P]
+        L.ccmi_latents_render_fmt_plan.argtypes = [P, P, I, P, I, I, P, P, P, P]
+        L.ccmi_latents_render_fmt.argtypes = [P, P, I, P, P, P, P, I, I, P, Z, P]
+        for f in (L.ccmi_decode_batch_dev_fmt_plan, L.ccmi_decode_batch_dev_fmt, L.ccmi_latents_render_fmt_plan,
+                  L.ccmi_latents_render_fmt):
+            f.restype = C.c_int
+        L._ccmi_fmt_bound = True
+    return L
+
+
+def _model_fmt(n, colour, mean, std, dtype, mirror):
+    """(ccmi_tensor_fmt without strides, what it points to) of a *_model call."""
+    import torch
+    elems = {torch.float32: ELEM_F32, torch.float16: ELEM_F16, torch.bfloat16: ELEM_BF16}
+    colours = {"rgb": COLOUR_RGB, "asis": COLOUR_ASIS}
+    if dtype not in elems:
+        raise ValueError(f"model output: dtype {dtype} (torch.float32, torch.float16 or torch.bfloat16)")
+    if colour not in colours:
+        raise ValueError(f"model output: colour {colour!r} ('rgb' or 'asis')")
+
+    def three(v, default):
+        if v is None:
+            return [default] * 3
+        v = [float(x) for x in v] if hasattr(v, "__len__") else [float(v)] * 3
+        if len(v) != 3:
+            raise ValueError("model output: mean / std take one value per channel")
+        return v
+    mean, std = three(mean, 0.0), three(std, 1.0)
+    fmt = TensorFmt(elem=elems[dtype], colour=colours[colour])
+    for c in range(3):
+        fmt.scale[c] = 1.0 / std[c]       # Python floats, rounded to float32 by the assignment
+        fmt.bias[c] = -mean[c] / std[c]
+    flags = None
+    if mirror is not None:
+        m = [bool(mirror)] * n if isinstance(mirror, (bool, int)) else [bool(v) for v in mirror]
+        if len(m) != n:
+            raise ValueError(f"model output: mirror takes one flag per frame ({n}), got {len(m)}")
+        flags = (C.c_uint8 * n)(*[int(v) for v in m])
+        fmt.mirror = C.cast(flags, C.c_void_p)
+    return fmt, flags
+
+
+def _model_outs(geom, fmt, dtype, channels_last, out, dev):
+    """Destination tensors of a *_model call: fills fmt's strides; returns (result, pointers,
+    capacities in bytes, what they point into)."""
+    import torch
+    n, g0 = len(geom), geom[0]
+    h, w = g0.height, g0.width
+    if any((g.width, g.height) != (w, h) for g in geom):
+        raise ValueError("model output: every region must have one size")
+    if out is None:
+        if channels_last:
+            res = torch.empty(n, h, w, 3, dtype=dtype, device=dev).permute(0, 3, 1, 2)
+        else:
+            res = torch.empty(n, 3, h, w, dtype=dtype, device=dev)
+        frames = [res[i] for i in range(n)]
+    else:
+        frames = res = list(out)
+        if len(frames) != n:
+            raise ValueError(f"model output: out takes one tensor per frame ({n}), got {len(frames)}")
+        for t in frames:
+            if tuple(t.shape) != (3, h, w) or t.dtype != dtype or not t.is_cuda:
+                raise ValueError(f"model output: out tensors must be CUDA {dtype} of shape [3, {h}, {w}], got "
+                                 f"{t.dtype} {tuple(t.shape)} on {t.device}")
+    strides = tuple(int(s) for s in frames[0].stride())
+    if any(tuple(int(s) for s in t.stride()) != strides for t in frames):
+        raise ValueError("model output: out tensors must share one stride set")
+    if strides == (0, 0, 0):  # would read as "planar contiguous" in ccmi_tensor_fmt
+        raise ValueError("model output: out tensors with all-zero strides alias")
+    fmt.stride_c, fmt.stride_y, fmt.stride_x = strides
+    op = (C.c_void_p * n)(*[t.data_ptr() for t in frames])
+    cap = (C.c_size_t * n)()
+    for i, t in enumerate(frames):  # what the tensor's storage holds from its first element on
+        st = t.untyped_storage()
+        cap[i] = max(st.nbytes() - (t.data_ptr() - st.data_ptr()), 0)
+    return res, op, cap, frames
+
+
+def decode_batch_model(streams: Sequence[bytes], roi=None, colour: str = "rgb", mean=None, std=None, dtype=None,
+                       channels_last: bool = False, mirror=None, out=None, output_bitdepth: int = 0,
+                       output_chroma_format: int = 0, workspace=None, stream_handle: int | None = None):
+    """Decode .cool streams into the tensor a model takes (ccmi_decode_batch_dev_fmt): one
+    [n, 3, h, w] tensor of `dtype` (torch.float32, the default, torch.float16 or torch.bfloat16),
+    every channel at full size (420 chroma nearest-upsampled), RGB (colour="rgb": YUV streams go
+    through io.yuv2rgb's matrix and are clamped to [0, 1]; "asis" keeps the stream's planes), then
+    (v - mean) / std per channel as v * float32(1 / std) + float32(-mean / std), written by the
+    decoder's output kernel itself: no float32 frame set and no further pass.  The contract, step
+    by step, is ccmi.h's (ccmi_tensor_fmt).
+
+    roi as for decode_batch_tensors; every region must have one size, and 420 samples need even
+    x, y, w and h (output_chroma_format=444 takes any).  channels_last=True: an [n, h, w, 3]
+    allocation returned as its permuted [n, 3, h, w] view.  mirror: one flag per frame (or one
+    bool): that frame is flipped left to right.  out: a list of n CUDA tensors or views of shape
+    [3, h, w] and one stride set (a tile of a larger canvas, NHWC slices, ...), filled in place
+    and returned instead of a new tensor."""
+    import torch
+    dtype = torch.float32 if dtype is None else dtype
+    n = len(streams)
+    m = _marshal(streams)
+    _, sp, ln = m
+    rects = _rects(roi, streams, n)
+    fmt, keep = _model_fmt(n, colour, mean, std, dtype, mirror)
+    L = _bind_fmt()
+    geom, need = (FrameGeom * n)(), C.c_size_t(0)
+    probe = TensorFmt.from_buffer_copy(fmt)  # planar strides: the geometry does not depend on them
+    check(L.ccmi_decode_batch_dev_fmt_plan(sp, ln, n, rects, output_bitdepth, output_chroma_format, C.byref(probe),
+                                           geom, None, C.byref(need)))
+    dev = torch.device("cuda", torch.cuda.current_device())
+    res, op, cap, frames = _model_outs(geom, fmt, dtype, channels_last, out, dev)
+    if stream_handle is None:
+        stream_handle = torch.cuda.current_stream(dev).cuda_stream
+    if workspace is None:
+        workspace = torch.empty(max(need.value, 256), dtype=torch.uint8, device=dev)
+    check(L.ccmi_decode_batch_dev_fmt(sp, ln, n, rects, op, cap, C.byref(fmt), output_bitdepth, output_chroma_format,
+                                      workspace.data_ptr(), workspace.numel(), stream_handle))
+    del keep, frames
+    return res
+
+
 def weights_i32(stream: bytes):
     """(arm, ups, syn) fixed-point network integers of a stream's intra frame, as the
     decoder uses them (ccmi_decode_weights_i32; cc-frame-decoder.cpp:201-353)."""
@@ -604,6 +738,32 @@ class LatentStore:
                                                   stream_handle))
         return _shape_outs(flat, outs, geom, stack)
 
+    def render_model(self, index=None, roi=None, colour: str = "rgb", mean=None, std=None, dtype=None,
+                     channels_last: bool = False, mirror=None, out=None, output_bitdepth: int = 0,
+                     output_chroma_format: int = 0, workspace=None, stream_handle: int | None = None):
+        """render() into the tensor a model takes (ccmi_latents_render_fmt): frames and regions
+        as for render(), the result and every other argument as for decode_batch_model, whose
+        output for the same streams and arguments it equals bit for bit."""
+        import torch
+        dtype = torch.float32 if dtype is None else dtype
+        L = _bind_fmt()
+        m, idx, rects = self._frames(index, roi)
+        fmt, keep = _model_fmt(m, colour, mean, std, dtype, mirror)
+        geom, need = (FrameGeom * m)(), C.c_size_t(0)
+        probe = TensorFmt.from_buffer_copy(fmt)
+        check(L.ccmi_latents_render_fmt_plan(self._handle(), idx, m, rects, output_bitdepth, output_chroma_format,
+                                             C.byref(probe), geom, None, C.byref(need)))
+        dev = self._store.device
+        res, op, cap, frames = _model_outs(geom, fmt, dtype, channels_last, out, dev)
+        if stream_handle is None:
+            stream_handle = torch.cuda.current_stream(dev).cuda_stream
+        if workspace is None:
+            workspace = torch.empty(max(need.value, 256), dtype=torch.uint8, device=dev)
+        check(L.ccmi_latents_render_fmt(self._handle(), idx, m, rects, op, cap, C.byref(fmt), output_bitdepth,
+                                        output_chroma_format, workspace.data_ptr(), workspace.numel(), stream_handle))
+        del keep, frames
+        return res
+
     def latents(self, i: int) -> list:
         """Stream i's integer latents: one int32 device tensor [h_l, w_l] per grid."""
         import torch
@@ -624,5 +784,5 @@ class LatentStore:
 
 
 __all__ = ["last_timing", "LatentStore", "last_arm_flags", "decode_latents", "decode_file", "decode_batch", "decode_batch_workspace_bytes", "output_size",
-           "decode_batch_tensors", "decode_batch_geometry", "roi_plan",
+           "decode_batch_tensors", "decode_batch_geometry", "roi_plan", "decode_batch_model",
            "weights_i32", "ups_forward_i32", "syn_forward_i32", "CcmiError"]

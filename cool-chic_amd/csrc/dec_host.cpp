@@ -631,6 +631,8 @@ int launch_frame_tail(const Run &r, const FramePlan &p, hipStream_t cs)
                                           b == 1, cs))
                 return rc;
     }
+    if (t.fmt.on) // roi.rect: the region, or the whole frame
+        return launch_dec_output_fmt(synout, f.h, f.w, t.roi.rect, t.bitdepth, t.kind, t.fmt, t.dst, cs);
     if (p.mode == kTailCrop)
         return launch_dec_output_tensor_roi(synout, f.h, f.w, t.roi.rect, t.bitdepth, t.kind, t.sample, t.dst, cs);
     if (r.rq.device()) return launch_dec_output_tensor(synout, f.h, f.w, t.bitdepth, t.kind, t.sample, t.dst, cs);
@@ -1041,6 +1043,41 @@ extern "C" int ccmi_decode_batch_dev_roi(const uint8_t *const *streams, const si
     return decode_many(rq, stream);
 }
 
+// The formatted sink plans as the CCMI_SAMPLE_F32 call it replaces the output kernel of.
+extern "C" int ccmi_decode_batch_dev_fmt_plan(const uint8_t *const *streams, const size_t *lens, int n,
+                                              const ccmi_rect *roi, int out_bitdepth, int out_chroma,
+                                              const ccmi_tensor_fmt *fmt, ccmi_frame_geom *geom, ccmi_roi_info *info,
+                                              size_t *workspace_bytes)
+{
+    if (!streams || !lens || !fmt || !geom || !workspace_bytes)
+        return ccmi_set_error(CCMI_ERR_ARG, "decode_batch_dev_fmt_plan: null argument");
+    DecodeRequest rq = request(streams, lens, n, out_bitdepth, out_chroma);
+    rq.sample = CCMI_SAMPLE_F32;
+    rq.fmt = fmt;
+    rq.roi = roi;
+    rq.geom = geom;
+    rq.info = info;
+    return plan_only(rq, workspace_bytes);
+}
+
+extern "C" int ccmi_decode_batch_dev_fmt(const uint8_t *const *streams, const size_t *lens, int n, const ccmi_rect *roi,
+                                         void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
+                                         int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes,
+                                         void *stream)
+{
+    if (!streams || !lens || !out_dev || !out_caps || !fmt)
+        return ccmi_set_error(CCMI_ERR_ARG, "decode_batch_dev_fmt: null argument");
+    DecodeRequest rq = request(streams, lens, n, out_bitdepth, out_chroma);
+    rq.sample = CCMI_SAMPLE_F32;
+    rq.fmt = fmt;
+    rq.roi = roi;
+    rq.dev = out_dev;
+    rq.caps = out_caps;
+    rq.ws = workspace;
+    rq.ws_bytes = workspace_bytes;
+    return decode_many(rq, stream);
+}
+
 extern "C" int ccmi_latents_plan(const uint8_t *const *streams, const size_t *lens, int n, int latent_type,
                                  size_t *store_bytes, size_t *store_bytes_each, size_t *workspace_bytes)
 {
@@ -1180,6 +1217,39 @@ extern "C" int ccmi_latents_render(const ccmi_latents *h, const int *index, int 
     if (!h->store)
         return ccmi_set_error(CCMI_ERR_ARG, "render: the handle is plan-only (built without a store): no frame 0 to render");
     if (!out_dev || !out_caps) return ccmi_set_error(CCMI_ERR_ARG, "latents_render: null argument");
+    rq.dev = out_dev;
+    rq.caps = out_caps;
+    rq.ws = workspace;
+    rq.ws_bytes = workspace_bytes;
+    return decode_many(rq, stream);
+}
+
+extern "C" int ccmi_latents_render_fmt_plan(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
+                                            int out_bitdepth, int out_chroma, const ccmi_tensor_fmt *fmt,
+                                            ccmi_frame_geom *geom, ccmi_roi_info *info, size_t *workspace_bytes)
+{
+    g_last_flags.clear();
+    DecodeRequest rq;
+    if (int rc = latents_request(h, index, m, roi, out_bitdepth, out_chroma, CCMI_SAMPLE_F32, rq)) return rc;
+    if (!fmt || !geom || !workspace_bytes) return ccmi_set_error(CCMI_ERR_ARG, "latents_render_fmt_plan: null argument");
+    rq.fmt = fmt;
+    rq.geom = geom;
+    rq.info = info;
+    return plan_only(rq, workspace_bytes);
+}
+
+extern "C" int ccmi_latents_render_fmt(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
+                                       void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
+                                       int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes,
+                                       void *stream)
+{
+    g_last_flags.clear();
+    DecodeRequest rq;
+    if (int rc = latents_request(h, index, m, roi, out_bitdepth, out_chroma, CCMI_SAMPLE_F32, rq)) return rc;
+    if (!h->store)
+        return ccmi_set_error(CCMI_ERR_ARG, "render: the handle is plan-only (built without a store): no frame 0 to render");
+    if (!out_dev || !out_caps || !fmt) return ccmi_set_error(CCMI_ERR_ARG, "latents_render_fmt: null argument");
+    rq.fmt = fmt;
     rq.dev = out_dev;
     rq.caps = out_caps;
     rq.ws = workspace;

@@ -149,6 +149,22 @@ size_t dec_ups_workspace_elems_win(const DecRoi &r, int L); // the stacks of lev
 int launch_dec_output_tensor_roi(const int32_t *syn, int h, int w, const DecWindow &rect, int bitdepth, int kind,
                                  int sample, void *dst, hipStream_t s);
 
+// Formatted tensor output (ccmi_tensor_fmt, validated and resolved by the plan): three full-size
+// channels per pixel, colour, affine, element type, strides and mirror applied by the output
+// kernel (dec_output_fmt<T>).  Everything but `matrix` and `mirror` is one value per call.
+struct DecFmt {
+    int on = 0;     // 0: the planar u8 / u16 / f32 tensor output
+    int elem = 0;   // CCMI_ELEM_*
+    int matrix = 0; // this frame takes the YUV -> RGB matrix (CCMI_COLOUR_RGB on a YUV stream)
+    int mirror = 0; // this frame's destination x is reversed
+    float scale[3] = {1.f, 1.f, 1.f}, bias[3] = {0.f, 0.f, 0.f};
+    int64_t stride_c = 0, stride_y = 0, stride_x = 0; // elements, resolved (never all 0)
+};
+// One frame: the region `rect` of the h x w synthesis output (12-bit, [3][h][w]) as the formatted
+// tensor at dst; kind 0 takes planes 1 and 2 at the even row and column (rect's origin even).
+int launch_dec_output_fmt(const int32_t *syn, int h, int w, const DecWindow &rect, int bitdepth, int kind,
+                          const DecFmt &fmt, void *dst, hipStream_t s);
+
 // Batched decoder tail: frames with the same geometry and a fused-synthesis architecture
 // (single branch) share one launch per pyramid step, one synthesis and one output launch
 // (grid.y = frame) instead of ~8 launches per frame.  The per-frame argument tables live
@@ -160,6 +176,7 @@ struct DecTailFrame {
     int bitdepth, kind;
     uint8_t *dst;
     int sample = -1; // -1: file bytes at dst (workspace staging); CCMI_SAMPLE_*: planar tensor at dst (caller's)
+    DecFmt fmt;      // fmt.on: the formatted tensor at dst instead (sample is then CCMI_SAMPLE_F32, unused)
     // region decode on windows: the latent planes keep their frame pitch and hold roi.arm_rows[l]
     // rows, ups.workspace / ups.out / syn.out hold the windows roi.lev[k] / the region, compact
     // (pitch = the window's width); ups.lh / lw and syn.h / w stay the frame's true sizes

@@ -4,7 +4,9 @@
 #include <stdio.h>
 
 #include <algorithm>
+#include <cmath>
 #include <string>
+#include <utility>
 
 #include "dec_plan.h"
 
@@ -53,6 +55,55 @@ int tensor_format(const FrameHost &f, int out_bitdepth, int out_chroma, int samp
     o.header = 0;
     *elems = o.kind == kYuv420 ? npx + 2 * (size_t)(rect.h() / 2) * (rect.w() / 2) : 3 * npx;
     o.payload = sample_bytes(sample) * *elems;
+    return CCMI_OK;
+}
+
+size_t elem_bytes(int elem) { return elem == CCMI_ELEM_F32 ? 4 : 2; }
+
+// A formatted sink (ccmi_tensor_fmt) for the region `rect` of frame i: validates the format
+// against the region and resolves it into d; *span = the elements from the frame's first to its
+// last, + 1.  of = the sample format tensor_format() chose.
+int tensor_fmt(const ccmi_tensor_fmt &m, int i, const FrameHost &f, const OutFmt &of, const DecWindow &rect, DecFmt &d,
+               size_t *span)
+{
+    if (m.elem != CCMI_ELEM_F32 && m.elem != CCMI_ELEM_F16 && m.elem != CCMI_ELEM_BF16)
+        return ccmi_set_error(CCMI_ERR_ARG, "frame %d: unknown element type %d", i, m.elem);
+    if (m.colour != CCMI_COLOUR_ASIS && m.colour != CCMI_COLOUR_RGB)
+        return ccmi_set_error(CCMI_ERR_ARG, "frame %d: unknown colour %d", i, m.colour);
+    for (int c = 0; c < 3; ++c)
+        if (!std::isfinite(m.scale[c]) || !std::isfinite(m.bias[c]))
+            return ccmi_set_error(CCMI_ERR_ARG, "frame %d: scale / bias of channel %d is not finite", i, c);
+    const int w = rect.w(), h = rect.h();
+    if (of.kind == kYuv420 && ((w | h) & 1))
+        return ccmi_set_error(CCMI_ERR_ARG,
+                              "frame %d: a formatted 420 region needs an even size (w %d h %d); out_chroma = 444 takes any",
+                              i, w, h);
+    int64_t sc = m.stride_c, sy = m.stride_y, sx = m.stride_x;
+    if (sc == 0 && sy == 0 && sx == 0) sc = (int64_t)w * h, sy = w, sx = 1;
+    const int64_t big = (int64_t)1 << 40; // times an extent (16-bit frame sizes): every product below fits 64 bits
+    if (sc < 0 || sy < 0 || sx < 0 || sc >= big || sy >= big || sx >= big)
+        return ccmi_set_error(CCMI_ERR_ARG, "frame %d: strides c %lld y %lld x %lld (elements, 0 .. 2^40)", i,
+                              (long long)m.stride_c, (long long)m.stride_y, (long long)m.stride_x);
+    // no two elements of the frame at one address: by ascending stride, each dimension steps over
+    // the whole of the one before it (a dimension of extent 1 never steps)
+    std::pair<int64_t, int64_t> dim[3] = {{sc, 3}, {sy, h}, {sx, w}};
+    std::sort(dim, dim + 3);
+    int64_t reach = 1; // stride x extent of the widest dimension so far
+    for (const auto &[stride, extent] : dim) {
+        if (extent == 1) continue;
+        if (stride < reach)
+            return ccmi_set_error(CCMI_ERR_ARG, "frame %d: strides c %lld y %lld x %lld let elements of the %d x %d frame alias",
+                                  i, (long long)sc, (long long)sy, (long long)sx, w, h);
+        reach = stride * extent;
+    }
+    d = DecFmt{};
+    d.on = 1;
+    d.elem = m.elem;
+    d.matrix = m.colour == CCMI_COLOUR_RGB && f.frame_data_type != 0;
+    d.mirror = m.mirror && m.mirror[i];
+    for (int c = 0; c < 3; ++c) d.scale[c] = m.scale[c], d.bias[c] = m.bias[c];
+    d.stride_c = sc, d.stride_y = sy, d.stride_x = sx;
+    *span = (size_t)(2 * sc + (h - 1) * sy + (w - 1) * sx + 1);
     return CCMI_OK;
 }
 
@@ -105,6 +156,14 @@ int plan_tensor_sink(const DecodeRequest &rq, int i, FramePlan &p)
     if (p.of.kind == kYuv420 && ((rect.x0 | rect.y0) & 1))
         return ccmi_set_error(CCMI_ERR_ARG, "%s %d: a 420 region needs an even origin (x %d y %d)", who, i, rect.x0,
                               rect.y0);
+    size_t unit = sample_bytes(rq.sample); // bytes of one stored element
+    if (rq.fmt) {
+        size_t span = 0;
+        if (int rc = tensor_fmt(*rq.fmt, i, f, p.of, rect, t.fmt, &span)) return rc;
+        unit = elem_bytes(t.fmt.elem);
+        elems = 3 * (size_t)rect.h() * rect.w();
+        p.of.payload = span * unit; // what the caller's buffer must hold
+    }
     int halo = 0;
     for (const SynLayerDesc &L : f.layers) halo += (L.ks - 1) / 2;
     if (rect.h() == f.h && rect.w() == f.w) {
@@ -132,9 +191,8 @@ int plan_tensor_sink(const DecodeRequest &rq, int i, FramePlan &p)
     }
     if (rq.dev) {
         if (!rq.dev[i]) return ccmi_set_error(CCMI_ERR_ARG, "decode: output %d is NULL", i);
-        if (reinterpret_cast<uintptr_t>(rq.dev[i]) % sample_bytes(rq.sample))
-            return ccmi_set_error(CCMI_ERR_ARG, "decode: output %d is not aligned to its %zu-byte samples", i,
-                                  sample_bytes(rq.sample));
+        if (reinterpret_cast<uintptr_t>(rq.dev[i]) % unit)
+            return ccmi_set_error(CCMI_ERR_ARG, "decode: output %d is not aligned to its %zu-byte samples", i, unit);
     }
     return CCMI_OK;
 }

@@ -50,8 +50,9 @@ enum TailMode {
 // One call of the decode driver.  The sink is host bytes (the default): file layout, staged
 // in the workspace and copied to outs[i]; or device tensors (sample >= 0): the output kernel
 // writes planar samples of type `sample` straight to dev[i], nothing is staged and nothing
-// is downloaded; or a latent store (lat_store): no decoder tail at all, the ARM output planes
-// are packed into the store.  outs / dev NULL: planning only.
+// is downloaded (with fmt: the formatted tensor instead); or a latent store (lat_store): no
+// decoder tail at all, the ARM output planes are packed into the store.  outs / dev NULL:
+// planning only.
 // The source is coded streams, or (src) streams of a latent store: frame i is stream index[i]
 // of the handle, the ARM stage is replaced by an unpack of the store, and n counts frames.
 struct DecodeRequest {
@@ -66,6 +67,9 @@ struct DecodeRequest {
     int sample = -1;               // -1 host bytes, else CCMI_SAMPLE_*
     void *const *dev = nullptr;    // [n] device pointers
     const ccmi_rect *roi = nullptr; // [n], optional: the region of each frame to decode
+    // formatted device-tensor sink (ccmi_tensor_fmt): three full-size channels, colour, affine,
+    // element type, strides and mirror; sample is CCMI_SAMPLE_F32 (the workspace is that call's)
+    const ccmi_tensor_fmt *fmt = nullptr;
     // either sink
     const size_t *caps = nullptr;    // [n], optional: capacity in bytes of outs[i] / dev[i]
     size_t *sizes = nullptr;         // [n], optional: bytes written per stream (filled by the plan)

@@ -15,6 +15,8 @@
 //  dec_output       444 -> 420/444 8/10-bit or PPM payload (ccdecapi.cpp:59-240).
 //  dec_output_tensor  the same samples as planar u8 / u16 / f32 device tensors (no file
 //                   layout): one packed store per 4 destination samples, any sample alignment.
+//  dec_output_fmt   the same samples as the formatted tensor of a ccmi_tensor_fmt: three
+//                   full-size channels, YUV -> RGB, scale / bias, f32 / f16 / bf16, strides, mirror.
 #include <stdlib.h>
 
 #include <algorithm>
@@ -643,6 +645,189 @@ unsigned output_tensor_blocks(int h, int w, int kind)
     return (unsigned)((groups + kThreads - 1) / kThreads);
 }
 
+// ------------------------------------------------------------------ formatted output tensors
+// Device sink with a ccmi_tensor_fmt (the contract is in ccmi.h): per region pixel the three
+// samples of output_tensor_body (420: planes 1 and 2 at the even row and column, the nearest x2
+// upsample), normalised, optionally through the YUV -> RGB matrix, scaled and biased, converted
+// to float / half / bfloat16 and stored at dst + c sc + y sy + x' sx.  A thread owns 4
+// consecutive destination pixels x' of one row with all three channels in registers; mirror
+// reads them from x = w - 1 - x'.  The groups of a row start at the naturally aligned address at
+// or below the row's channel-0 element (as output_tensor_body lays them out per frame), so with
+// sx == 1 (NCHW) a full group of an aligned channel is one packed store, and with sc == 1,
+// sx == 3 (NHWC) a full group's 12 elements are three; partial groups, channels whose rows are
+// not aligned alike, and every other stride set take one store per element.
+//
+// Every product and sum below is its own float32 operation: the library is built with the
+// compiler's default contraction, under which a * b + c may become one fused operation -- also
+// through __fmul_rn / __fadd_rn, which are plain inline operators in this toolchain's headers --
+// so the two helpers switch contraction off for their own instruction.
+__device__ __forceinline__ float fmt_mul(float a, float b)
+{
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float fmt_add(float a, float b)
+{
+#pragma clang fp contract(off)
+    return a + b;
+}
+
+struct F16 {
+    _Float16 v;
+};
+struct Bf16 {
+    uint16_t bits;
+};
+template <typename T> struct FmtVec;
+template <> struct FmtVec<float> { using type = float4; };
+template <> struct FmtVec<F16> { using type = uint2; };
+template <> struct FmtVec<Bf16> { using type = uint2; };
+
+template <typename T> __device__ __forceinline__ T fmt_elem(float r);
+template <> __device__ __forceinline__ float fmt_elem<float>(float r) { return r; }
+template <> __device__ __forceinline__ F16 fmt_elem<F16>(float r) { return F16{(_Float16)r}; } // v_cvt_f16_f32, RNE
+template <> __device__ __forceinline__ Bf16 fmt_elem<Bf16>(float r)
+{
+    uint32_t u = __float_as_uint(r);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return Bf16{0x7fc0}; // NaN (a finite scale and bias make none)
+    u += 0x7fffu + ((u >> 16) & 1u); // round to nearest even
+    return Bf16{(uint16_t)(u >> 16)};
+}
+
+// the float32 roundings of yuv2rgb's matrix (ccmi/io.py) and of its offsets / 255: R, G, B
+__device__ constexpr float kFmtA[3] = {(float)-0.000007154783816076815, (float)-0.3441331386566162, (float)1.7720025777816772};
+__device__ constexpr float kFmtB[3] = {(float)1.4019975662231445, (float)-0.7141380310058594, (float)0.00001542569043522235};
+__device__ constexpr float kFmtO[3] = {(float)(-179.45477266423404 / 255.0), (float)(135.45870971679688 / 255.0),
+                                       (float)(-226.8183044444304 / 255.0)};
+
+struct DecFmtCall { // one value per launch
+    float scale[3], bias[3];
+    int64_t sc, sy, sx;
+};
+enum { kFmtMirror = 1, kFmtMatrix = 2 }; // per-frame flags (DecOut::bps of a formatted group)
+
+// groups of 4 destination pixels that cover one row plus the up to 3 lead-in slots
+__host__ __device__ inline int fmt_row_groups(int w) { return (w + 3 + 3) / 4; }
+
+// h x w = the region at (oy, ox) of the synthesis output syn (planes splane apart, pitch spitch;
+// oy, ox even for kind 0)
+template <typename T>
+__device__ __forceinline__ void output_fmt_body(const int32_t *__restrict__ syn, int64_t splane, int spitch, int oy,
+                                                int ox, int h, int w, int maxv, int kind, int flags,
+                                                T *__restrict__ dst, const DecFmtCall &C)
+{
+    const int gpr = fmt_row_groups(w);
+    const int64_t g = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    const int y = (int)(g / gpr);
+    if (y >= h) return;
+    const bool nchw = C.sx == 1, nhwc = !nchw && C.sc == 1 && C.sx == 3;
+    const int64_t row = (int64_t)y * C.sy;
+    // elements from address 0 to (channel 0, y, x' = 0); group k starts mis slots before it, where
+    // the address of its first pixel is a multiple of 4 elements (NHWC: 3 mis == a0 mod 4)
+    const uint64_t a0 = (uint64_t)(reinterpret_cast<uintptr_t>(dst) / sizeof(T)) + (uint64_t)row;
+    const int mis = nchw ? (int)(a0 & 3) : nhwc ? (int)((3 * a0) & 3) : 0;
+    const int d0 = 4 * (int)(g - (int64_t)y * gpr) - mis;
+    if (d0 >= w) return;
+    const float fmax = (float)maxv;
+    auto smp = [maxv, fmax](int32_t v) {
+        int32_t s = (v * maxv + (1 << (kSynPrec - 1))) >> kSynPrec;
+        s = s < 0 ? 0 : (s > maxv ? maxv : s);
+        return __fdiv_rn((float)s, fmax);
+    };
+    const bool mirror = flags & kFmtMirror, matrix = flags & kFmtMatrix;
+    const int32_t *__restrict__ lrow = syn + (int64_t)(oy + y) * spitch + ox;
+    const int32_t *__restrict__ crow = syn + (int64_t)(oy + (kind == 1 ? y : y & ~1)) * spitch + ox;
+    T v[3][4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int d = d0 + k;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c][k] = fmt_elem<T>(0.f);
+        if (d < 0 || d >= w) continue;
+        const int x = mirror ? w - 1 - d : d, xc = kind == 1 ? x : x & ~1;
+        const float p0 = smp(lrow[x]), p1 = smp(crow[splane + xc]), p2 = smp(crow[2 * splane + xc]);
+        float q[3] = {p0, p1, p2};
+        if (matrix) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float t = fmt_add(fmt_add(fmt_add(p0, fmt_mul(kFmtA[c], p1)), fmt_mul(kFmtB[c], p2)), kFmtO[c]);
+                q[c] = fminf(fmaxf(t, 0.f), 1.f);
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c][k] = fmt_elem<T>(fmt_add(fmt_mul(q[c], C.scale[c]), C.bias[c]));
+    }
+    using Vec = typename FmtVec<T>::type;
+    const bool full = d0 >= 0 && d0 + 4 <= w;
+    if (nchw) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            T *p = dst + c * C.sc + row + d0;
+            if (full && reinterpret_cast<uintptr_t>(p) % sizeof(Vec) == 0) {
+                Vec pk;
+                __builtin_memcpy(&pk, v[c], sizeof pk);
+                *reinterpret_cast<Vec *>(p) = pk;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (d0 + k >= 0 && d0 + k < w) p[k] = v[c][k];
+            }
+        }
+    } else if (nhwc && full) { // aligned by the choice of mis
+        T e[12];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) e[3 * k + c] = v[c][k];
+        Vec *p = reinterpret_cast<Vec *>(dst + row + 3 * (int64_t)d0);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            Vec pk;
+            __builtin_memcpy(&pk, e + 4 * j, sizeof pk);
+            p[j] = pk;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (d0 + k < 0 || d0 + k >= w) continue;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) dst[c * C.sc + row + (d0 + k) * C.sx] = v[c][k];
+        }
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_output_fmt(const int32_t *__restrict__ syn, int H, int W, int oy, int ox,
+                                                           int h, int w, int maxv, int kind, int flags,
+                                                           T *__restrict__ dst, DecFmtCall C)
+{
+    output_fmt_body<T>(syn, (int64_t)H * W, W, oy, ox, h, w, maxv, kind, flags, dst, C);
+}
+
+// a tail group: frame blockIdx.y's compact H x W synthesis output (DecOut::bps = its kFmt* flags)
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_output_fmt_batch(const DecOut *__restrict__ Os, DecFmtCall C)
+{
+    const DecOut O = Os[blockIdx.y];
+    output_fmt_body<T>(O.syn, (int64_t)O.H * O.W, O.W, 0, 0, O.H, O.W, O.maxv, O.kind, O.bps, reinterpret_cast<T *>(O.dst),
+                       C);
+}
+
+unsigned output_fmt_blocks(int h, int w)
+{
+    return (unsigned)(((int64_t)h * fmt_row_groups(w) + kThreads - 1) / kThreads);
+}
+
+DecFmtCall fmt_call(const DecFmt &f)
+{
+    DecFmtCall C;
+    for (int c = 0; c < 3; ++c) C.scale[c] = f.scale[c], C.bias[c] = f.bias[c];
+    C.sc = f.stride_c, C.sy = f.stride_y, C.sx = f.stride_x;
+    return C;
+}
+
+int fmt_flags(const DecFmt &f) { return (f.mirror ? kFmtMirror : 0) | (f.matrix ? kFmtMatrix : 0); }
+
 } // namespace
 
 size_t dec_ups_workspace_elems(const int *lh, const int *lw, int L)
@@ -873,6 +1058,20 @@ static int with_sample_type(int sample, Launch &&launch)
     return CCMI_OK;
 }
 
+// launch(T{}) for the element type T of a formatted-output kernel
+template <typename Launch>
+static int with_elem_type(int elem, Launch &&launch)
+{
+    switch (elem) {
+    case CCMI_ELEM_F32: launch(float{}); break;
+    case CCMI_ELEM_F16: launch(F16{}); break;
+    case CCMI_ELEM_BF16: launch(Bf16{}); break;
+    default: return ccmi_set_error(CCMI_ERR_ARG, "dec: element type %d", elem);
+    }
+    CCMI_HIP_CHECK(hipGetLastError());
+    return CCMI_OK;
+}
+
 int launch_dec_syn(const DecSynArgs &a, hipStream_t s)
 {
     int cm;
@@ -959,6 +1158,22 @@ int launch_dec_output_tensor_roi(const int32_t *syn, int h, int w, const DecWind
     });
 }
 
+int launch_dec_output_fmt(const int32_t *syn, int h, int w, const DecWindow &rect, int bitdepth, int kind,
+                          const DecFmt &fmt, void *dst, hipStream_t s)
+{
+    if (kind != 0 && kind != 1) return ccmi_set_error(CCMI_ERR_ARG, "dec: tensor output kind %d", kind);
+    if (rect.y0 < 0 || rect.x0 < 0 || rect.y1 > h || rect.x1 > w || rect.h() < 1 || rect.w() < 1)
+        return ccmi_set_error(CCMI_ERR_ARG, "dec: region outside the frame");
+    if (kind == 0 && ((rect.y0 | rect.x0) & 1)) return ccmi_set_error(CCMI_ERR_ARG, "dec: a 420 region needs an even origin");
+    const dim3 grid(output_fmt_blocks(rect.h(), rect.w()));
+    const int maxv = (1 << bitdepth) - 1;
+    return with_elem_type(fmt.elem, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(dec_output_fmt<T>, grid, dim3(kThreads), 0, s, syn, h, w, rect.y0, rect.x0, rect.h(), rect.w(),
+                           maxv, kind, fmt_flags(fmt), static_cast<T *>(dst), fmt_call(fmt));
+    });
+}
+
 // ------------------------------------------------------------------ batched decoder tail
 bool dec_tail_batchable(const DecTailFrame &f)
 {
@@ -971,6 +1186,9 @@ bool dec_tail_batchable(const DecTailFrame &f)
 bool dec_tail_same_group(const DecTailFrame &a, const DecTailFrame &b)
 {
     if (a.ups.n_layers != b.ups.n_layers || a.windowed != b.windowed) return false;
+    // a formatted output is one kernel per element type; the format is one per call, so the
+    // frames of a call group as they do without it
+    if (a.fmt.on != b.fmt.on || a.fmt.elem != b.fmt.elem) return false;
     if (a.windowed) {
         // region decode: the tables carry each frame's true plane sizes and its windows, the
         // grids cover the group's largest window; one region size (the output grid), any
@@ -1013,7 +1231,8 @@ size_t dec_tail_table_bytes(int n_layers, int n, bool windowed) { return TailTab
 
 static DecOut make_out(const DecTailFrame &f, int h, int w)
 {
-    return DecOut{f.syn.out, h, w, (1 << f.bitdepth) - 1, f.kind, f.bitdepth <= 8 ? 1 : 2, f.dst};
+    return DecOut{f.syn.out, h, w, (1 << f.bitdepth) - 1, f.kind, f.fmt.on ? fmt_flags(f.fmt) : f.bitdepth <= 8 ? 1 : 2,
+                  f.dst};
 }
 
 // the window-form tables
@@ -1063,6 +1282,12 @@ void dec_tail_fill(const DecTailFrame *const *fr, int n, void *host_tab)
 // the tensor output of a group: h x w samples of one kind and sample type per frame
 static int launch_output_tensor_batch(const DecTailFrame &f0, int h, int w, int n, const DecOut *oo, hipStream_t s)
 {
+    if (f0.fmt.on) { // the format but its per-frame flags (in the table) is the call's
+        const dim3 grid(output_fmt_blocks(h, w), n);
+        return with_elem_type(f0.fmt.elem, [&](auto t) {
+            hipLaunchKernelGGL(dec_output_fmt_batch<decltype(t)>, grid, dim3(kThreads), 0, s, oo, fmt_call(f0.fmt));
+        });
+    }
     const dim3 grid(output_tensor_blocks(h, w, f0.kind), n); // one kind per group
     return with_sample_type(f0.sample, [&](auto t) {
         hipLaunchKernelGGL(dec_output_tensor_batch<decltype(t)>, grid, dim3(kThreads), 0, s, oo);

@@ -401,6 +401,65 @@ int ccmi_latents_render(const ccmi_latents *h, const int *index /* [m] or NULL *
                         int sample_type, int out_bitdepth, int out_chroma, void *workspace,
                         size_t workspace_bytes, void *stream);
 
+/* Formatted output: the same decode (coded streams, or a latent store) written as the tensor a
+ * model or a display takes -- three full-size channels, optionally RGB, normalised, fp16 / bf16,
+ * any strides (NCHW, NHWC, a view into the caller's canvas), optionally mirrored -- by one
+ * output kernel that replaces the tensor output kernel: no float32 frame is staged and no extra
+ * pass runs.  For output frame j, region pixel (y, x), channel c:
+ *   1. s_0..s_2: the integer samples of the tensor path at (out_bitdepth, out_chroma).  444: all
+ *      planes at (y, x).  420: plane 0 at (y, x), planes 1 and 2 the 420 plane's sample
+ *      (y >> 1, x >> 1), i.e. the nearest-neighbour x2 upsample; the region's x, y, w AND h must
+ *      be even (a whole frame too), else CCMI_ERR_ARG -- ask for out_chroma = 444 instead;
+ *   2. p_k = (float)s_k / (float)(2^bitdepth - 1), one correctly rounded division (CCMI_SAMPLE_F32);
+ *   3. CCMI_COLOUR_ASIS, or an RGB stream (frame_data_type 0): q = p.  CCMI_COLOUR_RGB on a YUV
+ *      stream: q_c = clamp(((p_0 + a_c p_1) + b_c p_2) + o_c, 0, 1), every product and sum one
+ *      float32 operation in this order; (a_c, b_c) are the float32 roundings of the BT.709-style
+ *      matrix the reference's yuv2rgb uses and o_c of its offset / 255;
+ *   4. r_c = q_c * scale[c] + bias[c], two float32 operations (no fused multiply-add);
+ *   5. r_c to `elem`, round to nearest even;
+ *   6. stored at out_dev[j] + c stride_c + y stride_y + x' stride_x (elements), x' = w - 1 - x
+ *      when mirror[j] is non-zero, else x.
+ * Strides all 0 mean planar contiguous (w h, w, 1).  Checked by the plan, before any GPU work,
+ * CCMI_ERR_ARG naming the frame and nothing written: an unknown elem / colour, a non-finite scale
+ * or bias, a negative stride, strides that let two elements of a frame share an address (sorted
+ * by stride, each must be >= the previous stride times the previous extent), out_caps[j] below
+ * (2 stride_c + (h - 1) stride_y + (w - 1) stride_x + 1) sizeof(elem), out_dev[j] not aligned to
+ * one element, and the 420 evenness rule.  geom[j].width / height are the region's, elems is
+ * 3 w h, chroma the format the samples were taken at.  The workspace is that of the same call
+ * with CCMI_SAMPLE_F32.  Everything else (roi, index, info, workspace, the stream
+ * synchronisation, timing and ARM flags) is as for ccmi_decode_batch_dev_roi(_plan) and
+ * ccmi_latents_render(_plan), whose argument lists these follow with fmt in place of sample_type.
+ * With unit stride_x (NCHW) or stride_c = 1, stride_x = 3 (NHWC) the kernel writes packed 8 / 16
+ * byte stores wherever the destination is aligned; other strides take one store per element.
+ * Measured (profiles/decode_model_ab.txt): 960 class-E streams from a latent store, 256 x 256
+ * regions, RGB, ImageNet mean / std, bf16, NCHW: 11.1 ms per call (tail 8.2 ms) against 13.5 ms
+ * for the CCMI_SAMPLE_F32 render (tail 8.0 ms) followed by the same steps as torch operations,
+ * equal in every element; peak allocation above store and workspace 360 MiB against 3720 MiB. */
+enum { CCMI_ELEM_F32 = 0, CCMI_ELEM_F16 = 1, CCMI_ELEM_BF16 = 2 };
+enum { CCMI_COLOUR_ASIS = 0, CCMI_COLOUR_RGB = 1 };
+typedef struct ccmi_tensor_fmt {
+    int elem, colour;
+    float scale[3], bias[3];
+    int64_t stride_c, stride_y, stride_x; /* elements; all 0 = planar contiguous [3][h][w] */
+    const uint8_t *mirror;                /* host, [n] or NULL */
+} ccmi_tensor_fmt;
+int ccmi_decode_batch_dev_fmt_plan(const uint8_t *const *streams, const size_t *lens, int n,
+                                   const ccmi_rect *roi /* [n] or NULL */, int out_bitdepth,
+                                   int out_chroma, const ccmi_tensor_fmt *fmt, ccmi_frame_geom *geom /* [n] */,
+                                   ccmi_roi_info *info /* [n] or NULL */, size_t *workspace_bytes);
+int ccmi_decode_batch_dev_fmt(const uint8_t *const *streams, const size_t *lens, int n,
+                              const ccmi_rect *roi /* [n] or NULL */, void *const *out_dev,
+                              const size_t *out_caps, const ccmi_tensor_fmt *fmt, int out_bitdepth,
+                              int out_chroma, void *workspace, size_t workspace_bytes, void *stream);
+int ccmi_latents_render_fmt_plan(const ccmi_latents *h, const int *index /* [m] or NULL */, int m,
+                                 const ccmi_rect *roi /* [m] or NULL */, int out_bitdepth, int out_chroma,
+                                 const ccmi_tensor_fmt *fmt, ccmi_frame_geom *geom /* [m] */,
+                                 ccmi_roi_info *info /* [m] or NULL */, size_t *workspace_bytes);
+int ccmi_latents_render_fmt(const ccmi_latents *h, const int *index /* [m] or NULL */, int m,
+                            const ccmi_rect *roi /* [m] or NULL */, void *const *out_dev, const size_t *out_caps,
+                            const ccmi_tensor_fmt *fmt, int out_bitdepth, int out_chroma, void *workspace,
+                            size_t workspace_bytes, void *stream);
+
 /* Network weights of a stream's intra frame as the decoder's fixed-point integers
  * (cc-frame-decoder.cpp:201-353, read_arm / read_ups / read_syn):
  *   arm: per hidden layer W[d][d] (out, in) then b[d]; then W_out[2][d], b_out[2]

@@ -1,7 +1,8 @@
 // decode_plan_san.cpp -- stand-alone host program for a sanitizer run of the decoder's planner
 // (decode_plan, dec_plan.cpp) on a machine without a GPU: every header-only entry point, the
 // latent store's layout and plan-only handles (ccmi_latents_*, store = NULL) with their render
-// planning included, over the streams named on the command line, whole, in batches of 7, over a list of regions, and
+// planning included, the formatted sinks (ccmi_tensor_fmt: element types, stride sets, a mirror
+// array of exactly n bytes, and the run entry point with capacities it must reject), over the streams named on the command line, whole, in batches of 7, over a list of regions, and
 // truncated at each length from 0 to the header size plus 8.  Every (truncated) stream sits in
 // a heap block of exactly its length, so a read past its end is reported.  No HIP call is made.
 //
@@ -69,15 +70,59 @@ void plan_all(const std::vector<Stream> &b, const std::vector<ccmi_rect> &rects,
         count(ccmi_decode_batch_dev_roi_plan(sp.data(), ln.data(), n, nullptr, bd, chroma, sample, geom.data(), nullptr,
                                              &need));
     }
+    // the formatted sink: every element type (one unknown), stride sets that are planar, NHWC,
+    // padded, aliasing and negative; the mirror flags sit in a heap block of exactly n bytes
+    uint8_t *mir = static_cast<uint8_t *>(malloc(n));
+    for (int i = 0; i < n; ++i) mir[i] = (uint8_t)(i & 1);
+    const int64_t strides[][3] = {{0, 0, 0}, {1, 3 * 4096, 3}, {1 << 24, 4100, 1}, {1, 1, 1}, {7, -1, 1}, {0, 16, 1}};
+    std::vector<ccmi_tensor_fmt> fmts;
+    for (int elem = 0; elem < 4; ++elem)
+        for (const auto &st : strides) {
+            ccmi_tensor_fmt f{};
+            f.elem = elem, f.colour = elem & 1;
+            for (int c = 0; c < 3; ++c) f.scale[c] = 4.f + c, f.bias[c] = -1.f;
+            f.stride_c = st[0], f.stride_y = st[1], f.stride_x = st[2];
+            f.mirror = elem == 2 ? nullptr : mir;
+            fmts.push_back(f);
+        }
+    fmts.back().scale[1] = 1.f / 0.f; // non-finite
+    fmts[0].colour = 2;               // unknown
+    for (const ccmi_tensor_fmt &f : fmts) {
+        count(ccmi_decode_batch_dev_fmt_plan(sp.data(), ln.data(), n, rects.data(), bd, chroma, &f, geom.data(), info.data(),
+                                             &need));
+        count(ccmi_decode_batch_dev_fmt_plan(sp.data(), ln.data(), n, nullptr, bd, chroma, &f, geom.data(), nullptr, &need));
+    }
+    {
+        // the run entry point with capacities one byte short of what its own plan asks (or 0 when
+        // the plan fails): rejected before any GPU work, the made-up pointers are never used
+        ccmi_tensor_fmt f = fmts[1];
+        f.colour = CCMI_COLOUR_RGB;
+        std::vector<void *> outs(n, reinterpret_cast<void *>(uintptr_t(1) << 40));
+        std::vector<size_t> caps(n, 0);
+        if (ccmi_decode_batch_dev_fmt_plan(sp.data(), ln.data(), n, rects.data(), bd, chroma, &f, geom.data(), nullptr, &need) ==
+            CCMI_OK)
+            for (int i = 0; i < n; ++i)
+                caps[i] = (2 * (size_t)f.stride_c + (size_t)(geom[i].height - 1) * f.stride_y +
+                           (size_t)(geom[i].width - 1) * f.stride_x + 1) * 4 - 1;
+        const int rc = ccmi_decode_batch_dev_fmt(sp.data(), ln.data(), n, rects.data(), outs.data(), caps.data(), &f, bd, chroma,
+                                                 nullptr, 0, nullptr);
+        if (rc == CCMI_OK) abort();
+        count(rc);
+    }
     // the latent store: layout at every element type, a plan-only handle (no GPU call), and the
     // render planning over it: in order, through an index with repeats and out-of-range entries
+    void *out0 = nullptr;
+    size_t cap0 = 0;
     std::vector<size_t> each(n);
     size_t store = 0;
     for (int type = 0; type < 4; ++type)
         count(ccmi_latents_plan(sp.data(), ln.data(), n, type, &store, type & 1 ? each.data() : nullptr, &need));
     ccmi_latents *h = nullptr;
     count(ccmi_latents_decode(sp.data(), ln.data(), n, CCMI_LATENT_I16, nullptr, 0, nullptr, 0, nullptr, &h));
-    if (!h) return;
+    if (!h) {
+        free(mir);
+        return;
+    }
     std::vector<int> idx(n + 2);
     std::vector<ccmi_rect> rr(n + 2);
     for (int j = 0; j < n + 2; ++j) idx[j] = (n - 1 - j % n + n) % n, rr[j] = rects[idx[j]];
@@ -93,11 +138,17 @@ void plan_all(const std::vector<Stream> &b, const std::vector<ccmi_rect> &rects,
     idx[0] = -1;
     count(ccmi_latents_render_plan(h, idx.data(), n + 2, nullptr, bd, chroma, 1, g2.data(), i2.data(), &need));
     count(ccmi_latents_render_plan(h, nullptr, n + 1, nullptr, bd, chroma, 1, g2.data(), nullptr, &need));
+    for (const ccmi_tensor_fmt &f : fmts) { // the mirror array has n entries: frames in order only
+        count(ccmi_latents_render_fmt_plan(h, nullptr, n, rects.data(), bd, chroma, &f, geom.data(), info.data(), &need));
+        count(ccmi_latents_render_fmt_plan(h, nullptr, n, nullptr, bd, chroma, &f, geom.data(), nullptr, &need));
+    }
+    count(ccmi_latents_render_fmt(h, nullptr, n, nullptr, &out0, &cap0, &fmts[1], bd, chroma, nullptr, 0, nullptr)); // plan-only
     void *out = nullptr;
     size_t cap = 0;
     count(ccmi_latents_render(h, nullptr, n, nullptr, &out, &cap, 1, bd, chroma, nullptr, 0, nullptr)); // plan-only: an error
     if (ccmi_latents_count(h) != n) abort();
     ccmi_latents_free(h);
+    free(mir);
 }
 
 std::vector<ccmi_rect> rects_of(int w, int h)
