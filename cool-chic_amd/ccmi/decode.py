@@ -352,6 +352,45 @@ def _bind_fmt():
     return L
 
 
+FILTER_TRIANGLE = 0  # CCMI_FILTER_*
+
+
+class Resample(C.Structure):
+    """ccmi_resample: the output size of a resampling call."""
+    _fields_ = [("out_w", C.c_int), ("out_h", C.c_int), ("filter", C.c_int)]
+
+
+def _bind_rs():
+    L = _bind_fmt()
+    if not getattr(L, "_ccmi_rs_bound", False):
+        P, I, Z = C.c_void_p, C.c_int, C.c_size_t
+        L.ccmi_decode_batch_dev_rs_plan.argtypes = [P, P, I, P, I, I, P, P, P, P, P]
+        L.ccmi_decode_batch_dev_rs.argtypes = [P, P, I, P, P, P, P, P, I, I, P, Z, P]
+        L.ccmi_latents_render_rs_plan.argtypes = [P, P, I, P, I, I, P, P, P, P, P]
+        L.ccmi_latents_render_rs.argtypes = [P, P, I, P, P, P, P, P, I, I, P, Z, P]
+        L.ccmi_decode_last_tail_groups.argtypes = [P, P]
+        for f in (L.ccmi_decode_batch_dev_rs_plan, L.ccmi_decode_batch_dev_rs, L.ccmi_latents_render_rs_plan,
+                  L.ccmi_latents_render_rs, L.ccmi_decode_last_tail_groups):
+            f.restype = C.c_int
+        L._ccmi_rs_bound = True
+    return L
+
+
+def _resample(size):
+    """size=(out_h, out_w) of a *_model call -> ccmi_resample (the library checks the range)."""
+    if len(size) != 2:
+        raise ValueError(f"model output: size takes (out_h, out_w), got {size!r}")
+    return Resample(out_w=int(size[1]), out_h=int(size[0]), filter=FILTER_TRIANGLE)
+
+
+def last_tail_groups() -> tuple:
+    """(batched tail groups, per-frame tails) this thread's last decode or render call launched
+    (ccmi_decode_last_tail_groups): frames that share a group share one launch per tail stage."""
+    batched, per_frame = C.c_int(0), C.c_int(0)
+    check(_bind_rs().ccmi_decode_last_tail_groups(C.byref(batched), C.byref(per_frame)))
+    return batched.value, per_frame.value
+
+
 def _model_fmt(n, colour, mean, std, dtype, mirror):
     """(ccmi_tensor_fmt without strides, what it points to) of a *_model call."""
     import torch
@@ -391,7 +430,8 @@ def _model_outs(geom, fmt, dtype, channels_last, out, dev):
     n, g0 = len(geom), geom[0]
     h, w = g0.height, g0.width
     if any((g.width, g.height) != (w, h) for g in geom):
-        raise ValueError("model output: every region must have one size")
+        raise ValueError("model output: every region must have one size, since the frames form one [n, 3, h, w] "
+                         "tensor; size=(out_h, out_w) resamples regions of different sizes to one")
     if out is None:
         if channels_last:
             res = torch.empty(n, h, w, 3, dtype=dtype, device=dev).permute(0, 3, 1, 2)
@@ -422,7 +462,7 @@ def _model_outs(geom, fmt, dtype, channels_last, out, dev):
 
 def decode_batch_model(streams: Sequence[bytes], roi=None, colour: str = "rgb", mean=None, std=None, dtype=None,
                        channels_last: bool = False, mirror=None, out=None, output_bitdepth: int = 0,
-                       output_chroma_format: int = 0, workspace=None, stream_handle: int | None = None):
+                       output_chroma_format: int = 0, workspace=None, stream_handle: int | None = None, size=None):
     """Decode .cool streams into the tensor a model takes (ccmi_decode_batch_dev_fmt): one
     [n, 3, h, w] tensor of `dtype` (torch.float32, the default, torch.float16 or torch.bfloat16),
     every channel at full size (420 chroma nearest-upsampled), RGB (colour="rgb": YUV streams go
@@ -436,7 +476,13 @@ def decode_batch_model(streams: Sequence[bytes], roi=None, colour: str = "rgb", 
     allocation returned as its permuted [n, 3, h, w] view.  mirror: one flag per frame (or one
     bool): that frame is flipped left to right.  out: a list of n CUDA tensors or views of shape
     [3, h, w] and one stride set (a tile of a larger canvas, NHWC slices, ...), filled in place
-    and returned instead of a new tensor."""
+    and returned instead of a new tensor.
+
+    size=(out_h, out_w) (ccmi_decode_batch_dev_rs): every region, of any size, is resampled to
+    that size by the antialiased triangle filter of interpolate(mode="bilinear", antialias=True)
+    between the colour step and the normalisation, in the same output stage (the contract's
+    steps 3a-3c); h, w above are then out_h, out_w, the regions may differ in size, and frames
+    of one architecture share their launches whatever their regions (last_tail_groups())."""
     import torch
     dtype = torch.float32 if dtype is None else dtype
     n = len(streams)
@@ -444,19 +490,21 @@ def decode_batch_model(streams: Sequence[bytes], roi=None, colour: str = "rgb", 
     _, sp, ln = m
     rects = _rects(roi, streams, n)
     fmt, keep = _model_fmt(n, colour, mean, std, dtype, mirror)
-    L = _bind_fmt()
+    L = _bind_fmt() if size is None else _bind_rs()
+    rs = () if size is None else (C.byref(_resample(size)),)
+    plan, run = ((L.ccmi_decode_batch_dev_fmt_plan, L.ccmi_decode_batch_dev_fmt) if size is None else
+                 (L.ccmi_decode_batch_dev_rs_plan, L.ccmi_decode_batch_dev_rs))
     geom, need = (FrameGeom * n)(), C.c_size_t(0)
     probe = TensorFmt.from_buffer_copy(fmt)  # planar strides: the geometry does not depend on them
-    check(L.ccmi_decode_batch_dev_fmt_plan(sp, ln, n, rects, output_bitdepth, output_chroma_format, C.byref(probe),
-                                           geom, None, C.byref(need)))
+    check(plan(sp, ln, n, rects, output_bitdepth, output_chroma_format, C.byref(probe), *rs, geom, None, C.byref(need)))
     dev = torch.device("cuda", torch.cuda.current_device())
     res, op, cap, frames = _model_outs(geom, fmt, dtype, channels_last, out, dev)
     if stream_handle is None:
         stream_handle = torch.cuda.current_stream(dev).cuda_stream
     if workspace is None:
         workspace = torch.empty(max(need.value, 256), dtype=torch.uint8, device=dev)
-    check(L.ccmi_decode_batch_dev_fmt(sp, ln, n, rects, op, cap, C.byref(fmt), output_bitdepth, output_chroma_format,
-                                      workspace.data_ptr(), workspace.numel(), stream_handle))
+    check(run(sp, ln, n, rects, op, cap, C.byref(fmt), *rs, output_bitdepth, output_chroma_format,
+              workspace.data_ptr(), workspace.numel(), stream_handle))
     del keep, frames
     return res
 
@@ -740,29 +788,48 @@ class LatentStore:
 
     def render_model(self, index=None, roi=None, colour: str = "rgb", mean=None, std=None, dtype=None,
                      channels_last: bool = False, mirror=None, out=None, output_bitdepth: int = 0,
-                     output_chroma_format: int = 0, workspace=None, stream_handle: int | None = None):
-        """render() into the tensor a model takes (ccmi_latents_render_fmt): frames and regions
-        as for render(), the result and every other argument as for decode_batch_model, whose
-        output for the same streams and arguments it equals bit for bit."""
+                     output_chroma_format: int = 0, workspace=None, stream_handle: int | None = None, size=None):
+        """render() into the tensor a model takes (ccmi_latents_render_fmt; with size
+        ccmi_latents_render_rs): frames and regions as for render(), the result and every other
+        argument as for decode_batch_model, whose output for the same streams and arguments it
+        equals bit for bit.  workspace with a size: at least what render_model_workspace_bytes()
+        reports (the resample's intermediate is not part of render_geometry()'s figure)."""
         import torch
         dtype = torch.float32 if dtype is None else dtype
-        L = _bind_fmt()
         m, idx, rects = self._frames(index, roi)
         fmt, keep = _model_fmt(m, colour, mean, std, dtype, mirror)
+        L = _bind_fmt() if size is None else _bind_rs()
+        rs = () if size is None else (C.byref(_resample(size)),)
+        plan, run = ((L.ccmi_latents_render_fmt_plan, L.ccmi_latents_render_fmt) if size is None else
+                     (L.ccmi_latents_render_rs_plan, L.ccmi_latents_render_rs))
         geom, need = (FrameGeom * m)(), C.c_size_t(0)
         probe = TensorFmt.from_buffer_copy(fmt)
-        check(L.ccmi_latents_render_fmt_plan(self._handle(), idx, m, rects, output_bitdepth, output_chroma_format,
-                                             C.byref(probe), geom, None, C.byref(need)))
+        check(plan(self._handle(), idx, m, rects, output_bitdepth, output_chroma_format, C.byref(probe), *rs, geom, None,
+                   C.byref(need)))
         dev = self._store.device
         res, op, cap, frames = _model_outs(geom, fmt, dtype, channels_last, out, dev)
         if stream_handle is None:
             stream_handle = torch.cuda.current_stream(dev).cuda_stream
         if workspace is None:
             workspace = torch.empty(max(need.value, 256), dtype=torch.uint8, device=dev)
-        check(L.ccmi_latents_render_fmt(self._handle(), idx, m, rects, op, cap, C.byref(fmt), output_bitdepth,
-                                        output_chroma_format, workspace.data_ptr(), workspace.numel(), stream_handle))
+        check(run(self._handle(), idx, m, rects, op, cap, C.byref(fmt), *rs, output_bitdepth, output_chroma_format,
+                  workspace.data_ptr(), workspace.numel(), stream_handle))
         del keep, frames
         return res
+
+    def render_model_workspace_bytes(self, index=None, roi=None, size=None, output_bitdepth: int = 0,
+                                     output_chroma_format: int = 0) -> int:
+        """Header-only: the workspace render_model needs for these frames, regions and size
+        (ccmi_latents_render_rs_plan; the element type, colour and strides do not change it)."""
+        m, idx, rects = self._frames(index, roi)
+        fmt = TensorFmt(elem=ELEM_F32, colour=COLOUR_ASIS)
+        for c in range(3):
+            fmt.scale[c] = 1.0
+        rs = None if size is None else C.byref(_resample(size))
+        geom, need = (FrameGeom * m)(), C.c_size_t(0)
+        check(_bind_rs().ccmi_latents_render_rs_plan(self._handle(), idx, m, rects, output_bitdepth, output_chroma_format,
+                                                     C.byref(fmt), rs, geom, None, C.byref(need)))
+        return need.value
 
     def latents(self, i: int) -> list:
         """Stream i's integer latents: one int32 device tensor [h_l, w_l] per grid."""
@@ -784,5 +851,5 @@ class LatentStore:
 
 
 __all__ = ["last_timing", "LatentStore", "last_arm_flags", "decode_latents", "decode_file", "decode_batch", "decode_batch_workspace_bytes", "output_size",
-           "decode_batch_tensors", "decode_batch_geometry", "roi_plan", "decode_batch_model",
+           "decode_batch_tensors", "decode_batch_geometry", "roi_plan", "decode_batch_model", "last_tail_groups",
            "weights_i32", "ups_forward_i32", "syn_forward_i32", "CcmiError"]

@@ -250,6 +250,15 @@ namespace {
 
 thread_local float g_last_ms[4] = {0, 0, 0, 0};
 thread_local std::vector<uint32_t> g_last_flags; // per stream: OR of its grids' CCMI_ARM_FLAG_* bits
+thread_local int g_last_tails[2] = {0, 0};       // batched tail groups, per-frame tails of the last call
+
+// what every decode, render and planning call clears first: a call that fails, or only plans,
+// reports nothing, not the previous call's
+void clear_last()
+{
+    g_last_flags.clear();
+    g_last_tails[0] = g_last_tails[1] = 0;
+}
 
 // polls per two-wave wait of the chain kernel before it gives up (ArmStreamDesc::spin_cap)
 int arm_spin_cap()
@@ -508,6 +517,7 @@ int build_tail_groups(Run &r)
         t.syn.out = reinterpret_cast<int32_t *>(r.dev + p.synout_off);
         t.syn.workspace = reinterpret_cast<int32_t *>(r.dev + p.synws_off);
         t.dst = r.rq.device() ? static_cast<uint8_t *>(r.rq.dev[i]) : r.dev + p.out_off;
+        t.rs_tmp = p.rs_elems ? reinterpret_cast<float *>(r.dev + p.rs_off) : nullptr;
         if (!p.batchable) continue;
         const int c = r.chunk_of[i];
         auto it = std::find_if(r.tails.begin(), r.tails.end(), [&](const TailGroup &g) {
@@ -525,7 +535,7 @@ int build_tail_groups(Run &r)
         const int m = (int)g.frames.size();
         g.off = tpos;
         dec_tail_fill(g.frames.data(), m, r.tab.data() + tpos);
-        tpos += dec_tail_table_bytes(g.frames[0]->ups.n_layers, m, g.frames[0]->windowed);
+        tpos += dec_tail_table_bytes(g.frames[0]->ups.n_layers, m, g.frames[0]->windowed, g.frames[0]->fmt.rs != 0);
     }
     r.tab_used = tpos;
     return CCMI_OK;
@@ -631,6 +641,8 @@ int launch_frame_tail(const Run &r, const FramePlan &p, hipStream_t cs)
                                           b == 1, cs))
                 return rc;
     }
+    if (t.fmt.rs)
+        return launch_dec_resample(synout, f.h, f.w, t.roi.rect, t.bitdepth, t.kind, t.fmt, t.rs_tmp, t.dst, cs);
     if (t.fmt.on) // roi.rect: the region, or the whole frame
         return launch_dec_output_fmt(synout, f.h, f.w, t.roi.rect, t.bitdepth, t.kind, t.fmt, t.dst, cs);
     if (p.mode == kTailCrop)
@@ -868,6 +880,10 @@ int decode_run(const DecodeRequest &rq, DecodePlan &pl, hipStream_t s)
         if (int rc = launch_lat(r, r.lat[r.K], CCMI_LATENT_I32, s)) return rc;
     ev.rec(1, s);
     if (int rc = run_chunks(r, ev, lease)) return rc;
+    if (!rq.lat_store) { // what launch_chunk ran: every group, and a tail of its own per other frame
+        g_last_tails[0] = (int)r.tails.size();
+        for (const FramePlan &p : pl.fr) g_last_tails[1] += p.batchable ? 0 : 1;
+    }
     ev.rec(4, s);
     if (int rc = read_back(r)) return rc;
     store_timing(r, ev, lease.set);
@@ -878,7 +894,7 @@ int decode_run(const DecodeRequest &rq, DecodePlan &pl, hipStream_t s)
 // stream, not the previous call's.
 int plan_only(const DecodeRequest &rq, size_t *workspace_bytes)
 {
-    g_last_flags.clear();
+    clear_last();
     DecodePlan pl;
     if (int rc = decode_plan(rq, pl)) return rc;
     *workspace_bytes = pl.total;
@@ -887,7 +903,7 @@ int plan_only(const DecodeRequest &rq, size_t *workspace_bytes)
 
 int decode_many(const DecodeRequest &rq, void *stream)
 {
-    g_last_flags.clear();
+    clear_last();
     DecodePlan pl;
     if (int rc = decode_plan(rq, pl)) return rc;
     return decode_run(rq, pl, static_cast<hipStream_t>(stream));
@@ -1081,7 +1097,7 @@ extern "C" int ccmi_decode_batch_dev_fmt(const uint8_t *const *streams, const si
 extern "C" int ccmi_latents_plan(const uint8_t *const *streams, const size_t *lens, int n, int latent_type,
                                  size_t *store_bytes, size_t *store_bytes_each, size_t *workspace_bytes)
 {
-    g_last_flags.clear();
+    clear_last();
     if (!streams || !lens || !store_bytes || !workspace_bytes)
         return ccmi_set_error(CCMI_ERR_ARG, "latents_plan: null argument");
     ccmi_latents h;
@@ -1100,7 +1116,7 @@ extern "C" int ccmi_latents_decode(const uint8_t *const *streams, const size_t *
                                    void *store, size_t store_bytes, void *workspace, size_t workspace_bytes,
                                    void *stream, ccmi_latents **out)
 {
-    g_last_flags.clear();
+    clear_last();
     if (!streams || !lens || !out) return ccmi_set_error(CCMI_ERR_ARG, "latents_decode: null argument");
     *out = nullptr;
     ccmi_latents *h = new ccmi_latents;
@@ -1198,7 +1214,7 @@ extern "C" int ccmi_latents_render_plan(const ccmi_latents *h, const int *index,
                                         int out_bitdepth, int out_chroma, int sample_type, ccmi_frame_geom *geom,
                                         ccmi_roi_info *info, size_t *workspace_bytes)
 {
-    g_last_flags.clear();
+    clear_last();
     DecodeRequest rq;
     if (int rc = latents_request(h, index, m, roi, out_bitdepth, out_chroma, sample_type, rq)) return rc;
     if (!geom || !workspace_bytes) return ccmi_set_error(CCMI_ERR_ARG, "latents_render_plan: null argument");
@@ -1211,7 +1227,7 @@ extern "C" int ccmi_latents_render(const ccmi_latents *h, const int *index, int 
                                    void *const *out_dev, const size_t *out_caps, int sample_type, int out_bitdepth,
                                    int out_chroma, void *workspace, size_t workspace_bytes, void *stream)
 {
-    g_last_flags.clear();
+    clear_last();
     DecodeRequest rq;
     if (int rc = latents_request(h, index, m, roi, out_bitdepth, out_chroma, sample_type, rq)) return rc;
     if (!h->store)
@@ -1228,7 +1244,7 @@ extern "C" int ccmi_latents_render_fmt_plan(const ccmi_latents *h, const int *in
                                             int out_bitdepth, int out_chroma, const ccmi_tensor_fmt *fmt,
                                             ccmi_frame_geom *geom, ccmi_roi_info *info, size_t *workspace_bytes)
 {
-    g_last_flags.clear();
+    clear_last();
     DecodeRequest rq;
     if (int rc = latents_request(h, index, m, roi, out_bitdepth, out_chroma, CCMI_SAMPLE_F32, rq)) return rc;
     if (!fmt || !geom || !workspace_bytes) return ccmi_set_error(CCMI_ERR_ARG, "latents_render_fmt_plan: null argument");
@@ -1243,7 +1259,7 @@ extern "C" int ccmi_latents_render_fmt(const ccmi_latents *h, const int *index, 
                                        int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes,
                                        void *stream)
 {
-    g_last_flags.clear();
+    clear_last();
     DecodeRequest rq;
     if (int rc = latents_request(h, index, m, roi, out_bitdepth, out_chroma, CCMI_SAMPLE_F32, rq)) return rc;
     if (!h->store)
@@ -1255,6 +1271,98 @@ extern "C" int ccmi_latents_render_fmt(const ccmi_latents *h, const int *index, 
     rq.ws = workspace;
     rq.ws_bytes = workspace_bytes;
     return decode_many(rq, stream);
+}
+
+// The resampling sink: the formatted call with a ccmi_resample next to the format (rs NULL: that
+// call itself).
+extern "C" int ccmi_decode_batch_dev_rs_plan(const uint8_t *const *streams, const size_t *lens, int n,
+                                             const ccmi_rect *roi, int out_bitdepth, int out_chroma,
+                                             const ccmi_tensor_fmt *fmt, const ccmi_resample *rs, ccmi_frame_geom *geom,
+                                             ccmi_roi_info *info, size_t *workspace_bytes)
+{
+    if (!rs)
+        return ccmi_decode_batch_dev_fmt_plan(streams, lens, n, roi, out_bitdepth, out_chroma, fmt, geom, info, workspace_bytes);
+    if (!streams || !lens || !fmt || !geom || !workspace_bytes)
+        return ccmi_set_error(CCMI_ERR_ARG, "decode_batch_dev_rs_plan: null argument");
+    DecodeRequest rq = request(streams, lens, n, out_bitdepth, out_chroma);
+    rq.sample = CCMI_SAMPLE_F32;
+    rq.fmt = fmt;
+    rq.rs = rs;
+    rq.roi = roi;
+    rq.geom = geom;
+    rq.info = info;
+    return plan_only(rq, workspace_bytes);
+}
+
+extern "C" int ccmi_decode_batch_dev_rs(const uint8_t *const *streams, const size_t *lens, int n, const ccmi_rect *roi,
+                                        void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
+                                        const ccmi_resample *rs, int out_bitdepth, int out_chroma, void *workspace,
+                                        size_t workspace_bytes, void *stream)
+{
+    if (!rs)
+        return ccmi_decode_batch_dev_fmt(streams, lens, n, roi, out_dev, out_caps, fmt, out_bitdepth, out_chroma, workspace,
+                                         workspace_bytes, stream);
+    if (!streams || !lens || !out_dev || !out_caps || !fmt)
+        return ccmi_set_error(CCMI_ERR_ARG, "decode_batch_dev_rs: null argument");
+    DecodeRequest rq = request(streams, lens, n, out_bitdepth, out_chroma);
+    rq.sample = CCMI_SAMPLE_F32;
+    rq.fmt = fmt;
+    rq.rs = rs;
+    rq.roi = roi;
+    rq.dev = out_dev;
+    rq.caps = out_caps;
+    rq.ws = workspace;
+    rq.ws_bytes = workspace_bytes;
+    return decode_many(rq, stream);
+}
+
+extern "C" int ccmi_latents_render_rs_plan(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
+                                           int out_bitdepth, int out_chroma, const ccmi_tensor_fmt *fmt,
+                                           const ccmi_resample *rs, ccmi_frame_geom *geom, ccmi_roi_info *info,
+                                           size_t *workspace_bytes)
+{
+    if (!rs)
+        return ccmi_latents_render_fmt_plan(h, index, m, roi, out_bitdepth, out_chroma, fmt, geom, info, workspace_bytes);
+    clear_last();
+    DecodeRequest rq;
+    if (int rc = latents_request(h, index, m, roi, out_bitdepth, out_chroma, CCMI_SAMPLE_F32, rq)) return rc;
+    if (!fmt || !geom || !workspace_bytes) return ccmi_set_error(CCMI_ERR_ARG, "latents_render_rs_plan: null argument");
+    rq.fmt = fmt;
+    rq.rs = rs;
+    rq.geom = geom;
+    rq.info = info;
+    return plan_only(rq, workspace_bytes);
+}
+
+extern "C" int ccmi_latents_render_rs(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
+                                      void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
+                                      const ccmi_resample *rs, int out_bitdepth, int out_chroma, void *workspace,
+                                      size_t workspace_bytes, void *stream)
+{
+    if (!rs)
+        return ccmi_latents_render_fmt(h, index, m, roi, out_dev, out_caps, fmt, out_bitdepth, out_chroma, workspace,
+                                       workspace_bytes, stream);
+    clear_last();
+    DecodeRequest rq;
+    if (int rc = latents_request(h, index, m, roi, out_bitdepth, out_chroma, CCMI_SAMPLE_F32, rq)) return rc;
+    if (!h->store)
+        return ccmi_set_error(CCMI_ERR_ARG, "render: the handle is plan-only (built without a store): no frame 0 to render");
+    if (!out_dev || !out_caps || !fmt) return ccmi_set_error(CCMI_ERR_ARG, "latents_render_rs: null argument");
+    rq.fmt = fmt;
+    rq.rs = rs;
+    rq.dev = out_dev;
+    rq.caps = out_caps;
+    rq.ws = workspace;
+    rq.ws_bytes = workspace_bytes;
+    return decode_many(rq, stream);
+}
+
+extern "C" int ccmi_decode_last_tail_groups(int *batched, int *per_frame)
+{
+    if (!batched || !per_frame) return ccmi_set_error(CCMI_ERR_ARG, "decode_last_tail_groups: null argument");
+    *batched = g_last_tails[0];
+    *per_frame = g_last_tails[1];
+    return CCMI_OK;
 }
 
 extern "C" int ccmi_decode_latents(const uint8_t *stream, size_t len, int32_t *out, size_t cap, void *hstream)

@@ -159,11 +159,21 @@ struct DecFmt {
     int mirror = 0; // this frame's destination x is reversed
     float scale[3] = {1.f, 1.f, 1.f}, bias[3] = {0.f, 0.f, 0.f};
     int64_t stride_c = 0, stride_y = 0, stride_x = 0; // elements, resolved (never all 0)
+    // ccmi_resample (one per call): the region, of any size, is resampled to out_h x out_w between
+    // the colour step and scale / bias (dec_resample_h, dec_resample_v<T>); strides and mirror
+    // then refer to the output size
+    int rs = 0;
+    int out_h = 0, out_w = 0;
 };
 // One frame: the region `rect` of the h x w synthesis output (12-bit, [3][h][w]) as the formatted
 // tensor at dst; kind 0 takes planes 1 and 2 at the even row and column (rect's origin even).
 int launch_dec_output_fmt(const int32_t *syn, int h, int w, const DecWindow &rect, int bitdepth, int kind,
                           const DecFmt &fmt, void *dst, hipStream_t s);
+// The same with fmt.rs: the region is resampled to fmt.out_h x fmt.out_w on the way.  tmp holds the
+// horizontal pass, dec_resample_tmp_elems() floats.
+size_t dec_resample_tmp_elems(int region_h, int out_w);
+int launch_dec_resample(const int32_t *syn, int h, int w, const DecWindow &rect, int bitdepth, int kind,
+                        const DecFmt &fmt, float *tmp, void *dst, hipStream_t s);
 
 // Batched decoder tail: frames with the same geometry and a fused-synthesis architecture
 // (single branch) share one launch per pyramid step, one synthesis and one output launch
@@ -177,6 +187,7 @@ struct DecTailFrame {
     uint8_t *dst;
     int sample = -1; // -1: file bytes at dst (workspace staging); CCMI_SAMPLE_*: planar tensor at dst (caller's)
     DecFmt fmt;      // fmt.on: the formatted tensor at dst instead (sample is then CCMI_SAMPLE_F32, unused)
+    float *rs_tmp = nullptr; // fmt.rs: the frame's horizontal-pass intermediate, [3][region h][out_w]
     // region decode on windows: the latent planes keep their frame pitch and hold roi.arm_rows[l]
     // rows, ups.workspace / ups.out / syn.out hold the windows roi.lev[k] / the region, compact
     // (pitch = the window's width); ups.lh / lw and syn.h / w stay the frame's true sizes
@@ -185,7 +196,7 @@ struct DecTailFrame {
 };
 bool dec_tail_batchable(const DecTailFrame &f);
 bool dec_tail_same_group(const DecTailFrame &a, const DecTailFrame &b);
-size_t dec_tail_table_bytes(int n_layers, int n, bool windowed = false);
+size_t dec_tail_table_bytes(int n_layers, int n, bool windowed = false, bool resample = false);
 void dec_tail_fill(const DecTailFrame *const *fr, int n, void *host_tab);
 // fr: the group's frames, in table order (a window-form group sizes its grids by their windows)
 int launch_dec_tail_batch(const DecTailFrame *const *fr, int n, const void *dev_tab, hipStream_t s);

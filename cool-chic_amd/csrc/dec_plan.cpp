@@ -60,11 +60,14 @@ int tensor_format(const FrameHost &f, int out_bitdepth, int out_chroma, int samp
 
 size_t elem_bytes(int elem) { return elem == CCMI_ELEM_F32 ? 4 : 2; }
 
+constexpr int kMaxResample = 16384; // region and output extents of a resample: its integer weights fit int32
+
 // A formatted sink (ccmi_tensor_fmt) for the region `rect` of frame i: validates the format
 // against the region and resolves it into d; *span = the elements from the frame's first to its
-// last, + 1.  of = the sample format tensor_format() chose.
-int tensor_fmt(const ccmi_tensor_fmt &m, int i, const FrameHost &f, const OutFmt &of, const DecWindow &rect, DecFmt &d,
-               size_t *span)
+// last, + 1.  of = the sample format tensor_format() chose.  rs (optional): the region is
+// resampled, so the frame the strides describe is rs->out_h x rs->out_w.
+int tensor_fmt(const ccmi_tensor_fmt &m, const ccmi_resample *rs, int i, const FrameHost &f, const OutFmt &of,
+               const DecWindow &rect, DecFmt &d, size_t *span)
 {
     if (m.elem != CCMI_ELEM_F32 && m.elem != CCMI_ELEM_F16 && m.elem != CCMI_ELEM_BF16)
         return ccmi_set_error(CCMI_ERR_ARG, "frame %d: unknown element type %d", i, m.elem);
@@ -73,11 +76,20 @@ int tensor_fmt(const ccmi_tensor_fmt &m, int i, const FrameHost &f, const OutFmt
     for (int c = 0; c < 3; ++c)
         if (!std::isfinite(m.scale[c]) || !std::isfinite(m.bias[c]))
             return ccmi_set_error(CCMI_ERR_ARG, "frame %d: scale / bias of channel %d is not finite", i, c);
-    const int w = rect.w(), h = rect.h();
-    if (of.kind == kYuv420 && ((w | h) & 1))
+    if (of.kind == kYuv420 && ((rect.w() | rect.h()) & 1))
         return ccmi_set_error(CCMI_ERR_ARG,
                               "frame %d: a formatted 420 region needs an even size (w %d h %d); out_chroma = 444 takes any",
-                              i, w, h);
+                              i, rect.w(), rect.h());
+    if (rs) {
+        if (rs->filter != CCMI_FILTER_TRIANGLE) return ccmi_set_error(CCMI_ERR_ARG, "frame %d: unknown filter %d", i, rs->filter);
+        if (rs->out_w < 1 || rs->out_w > kMaxResample || rs->out_h < 1 || rs->out_h > kMaxResample)
+            return ccmi_set_error(CCMI_ERR_ARG, "frame %d: output size w %d h %d (1 .. %d)", i, rs->out_w, rs->out_h,
+                                  kMaxResample);
+        if (rect.w() > kMaxResample || rect.h() > kMaxResample)
+            return ccmi_set_error(CCMI_ERR_ARG, "frame %d: a resampled region is at most %d a side (w %d h %d)", i,
+                                  kMaxResample, rect.w(), rect.h());
+    }
+    const int w = rs ? rs->out_w : rect.w(), h = rs ? rs->out_h : rect.h(); // of the stored frame
     int64_t sc = m.stride_c, sy = m.stride_y, sx = m.stride_x;
     if (sc == 0 && sy == 0 && sx == 0) sc = (int64_t)w * h, sy = w, sx = 1;
     const int64_t big = (int64_t)1 << 40; // times an extent (16-bit frame sizes): every product below fits 64 bits
@@ -103,6 +115,7 @@ int tensor_fmt(const ccmi_tensor_fmt &m, int i, const FrameHost &f, const OutFmt
     d.mirror = m.mirror && m.mirror[i];
     for (int c = 0; c < 3; ++c) d.scale[c] = m.scale[c], d.bias[c] = m.bias[c];
     d.stride_c = sc, d.stride_y = sy, d.stride_x = sx;
+    if (rs) d.rs = 1, d.out_h = h, d.out_w = w;
     *span = (size_t)(2 * sc + (h - 1) * sy + (w - 1) * sx + 1);
     return CCMI_OK;
 }
@@ -157,11 +170,17 @@ int plan_tensor_sink(const DecodeRequest &rq, int i, FramePlan &p)
         return ccmi_set_error(CCMI_ERR_ARG, "%s %d: a 420 region needs an even origin (x %d y %d)", who, i, rect.x0,
                               rect.y0);
     size_t unit = sample_bytes(rq.sample); // bytes of one stored element
+    int out_w = rect.w(), out_h = rect.h();  // of the stored frame: the region, unless it is resampled
     if (rq.fmt) {
         size_t span = 0;
-        if (int rc = tensor_fmt(*rq.fmt, i, f, p.of, rect, t.fmt, &span)) return rc;
+        if (int rc = tensor_fmt(*rq.fmt, rq.rs, i, f, p.of, rect, t.fmt, &span)) return rc;
         unit = elem_bytes(t.fmt.elem);
         elems = 3 * (size_t)rect.h() * rect.w();
+        if (t.fmt.rs) {
+            out_w = t.fmt.out_w, out_h = t.fmt.out_h;
+            elems = 3 * (size_t)out_h * out_w;
+            p.rs_elems = dec_resample_tmp_elems(rect.h(), out_w);
+        }
         p.of.payload = span * unit; // what the caller's buffer must hold
     }
     int halo = 0;
@@ -180,7 +199,7 @@ int plan_tensor_sink(const DecodeRequest &rq, int i, FramePlan &p)
     }
     t.windowed = p.mode == kTailWindow;
     if (rq.geom)
-        rq.geom[i] = ccmi_frame_geom{rect.w(), rect.h(), p.of.bitdepth, p.of.kind == kYuv420 ? 420 : 444,
+        rq.geom[i] = ccmi_frame_geom{out_w, out_h, p.of.bitdepth, p.of.kind == kYuv420 ? 420 : 444,
                                      f.frame_data_type, elems};
     if (rq.info) {
         ccmi_roi_info &I = rq.info[i];
@@ -292,6 +311,10 @@ void plan_layout(const DecodeRequest &rq, DecodePlan &pl)
         tot += align_up(p.synout_elems * 4, 256);
         p.synws_off = tot;
         tot += align_up(p.synws_elems * 4 + 4, 256);
+        if (p.rs_elems) {
+            p.rs_off = tot;
+            tot += align_up(p.rs_elems * 4, 256);
+        }
         p.out_off = tot;
         if (!rq.device()) tot += align_up(p.of.payload, 256); // device sinks write to the caller's memory
     }
@@ -300,7 +323,7 @@ void plan_layout(const DecodeRequest &rq, DecodePlan &pl)
     // batched-tail argument tables: bounded by one single-frame table per frame
     pl.tail_cap = 0;
     for (const FramePlan &p : pl.fr)
-        if (!build) pl.tail_cap += dec_tail_table_bytes(p.f.n_layers, 1, p.mode == kTailWindow);
+        if (!build) pl.tail_cap += dec_tail_table_bytes(p.f.n_layers, 1, p.mode == kTailWindow, p.tail.fmt.rs != 0);
     pl.tail_off = tot;
     tot += align_up(pl.tail_cap, 256);
     // the pack / unpack job table follows the tail tables: one host image, one upload.  A build

@@ -70,6 +70,8 @@ struct DecodeRequest {
     // formatted device-tensor sink (ccmi_tensor_fmt): three full-size channels, colour, affine,
     // element type, strides and mirror; sample is CCMI_SAMPLE_F32 (the workspace is that call's)
     const ccmi_tensor_fmt *fmt = nullptr;
+    // with fmt, optional: every frame's region is resampled to one output size (ccmi_resample)
+    const ccmi_resample *rs = nullptr;
     // either sink
     const size_t *caps = nullptr;    // [n], optional: capacity in bytes of outs[i] / dev[i]
     size_t *sizes = nullptr;         // [n], optional: bytes written per stream (filled by the plan)
@@ -104,6 +106,7 @@ struct FramePlan {
     // scratch
     size_t lat_off, ws_off, dense_off, synout_off, synws_off, out_off;
     size_t lat_elems, ws_elems, dense_elems, synout_elems, synws_elems;
+    size_t rs_off = 0, rs_elems = 0; // a resample's horizontal-pass intermediate (float32); none without one
 };
 
 struct DecodePlan {

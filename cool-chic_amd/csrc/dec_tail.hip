@@ -17,6 +17,8 @@
 //                   layout): one packed store per 4 destination samples, any sample alignment.
 //  dec_output_fmt   the same samples as the formatted tensor of a ccmi_tensor_fmt: three
 //                   full-size channels, YUV -> RGB, scale / bias, f32 / f16 / bf16, strides, mirror.
+//  dec_resample_h, dec_resample_v  the formatted tensor with a ccmi_resample: the region through an
+//                   antialiased triangle filter to the output size, horizontal then vertical pass.
 #include <stdlib.h>
 
 #include <algorithm>
@@ -828,6 +830,233 @@ DecFmtCall fmt_call(const DecFmt &f)
 
 int fmt_flags(const DecFmt &f) { return (f.mirror ? kFmtMirror : 0) | (f.matrix ? kFmtMatrix : 0); }
 
+// ------------------------------------------------------------------ resampled formatted output
+// The formatted sink with a ccmi_resample (steps 3a-3c of the contract in ccmi.h): the region,
+// h x w, goes through an antialiased triangle filter to oh x ow between the colour step and
+// scale / bias.  Two launches:
+//   dec_resample_h     thread = (region row y, output column i), three channels: q per tap from
+//                      the synthesis output, t[c][y][i] (float32, [3][h][ow]) to the workspace;
+//   dec_resample_v<T>  thread = (output row, 4 destination pixels), as the formatted output stage:
+//                      the vertical pass over t (loads coalesced along the row), then scale / bias,
+//                      element conversion and the stores of fmt_store.  mirror reads column
+//                      ow - 1 - x'.
+// The three helpers restate output_fmt_body's pixel, group and store steps for the resampling
+// kernels; that body keeps its own copy so that the kernels built from it stay as they are.
+
+// steps 1-3 of the contract for one pixel: lrow / crow point at the pixel's luma row and at the
+// row its chroma is taken from, x / xc are its luma and chroma columns
+__device__ __forceinline__ void fmt_pixel(const int32_t *__restrict__ lrow, const int32_t *__restrict__ crow,
+                                          int64_t splane, int x, int xc, int maxv, float fmax, bool matrix, float (&q)[3])
+{
+    auto smp = [maxv, fmax](int32_t v) {
+        int32_t s = (v * maxv + (1 << (kSynPrec - 1))) >> kSynPrec;
+        s = s < 0 ? 0 : (s > maxv ? maxv : s);
+        return __fdiv_rn((float)s, fmax);
+    };
+    const float p0 = smp(lrow[x]), p1 = smp(crow[splane + xc]), p2 = smp(crow[2 * splane + xc]);
+    q[0] = p0, q[1] = p1, q[2] = p2;
+    if (matrix) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float t = fmt_add(fmt_add(fmt_add(p0, fmt_mul(kFmtA[c], p1)), fmt_mul(kFmtB[c], p2)), kFmtO[c]);
+            q[c] = fminf(fmaxf(t, 0.f), 1.f);
+        }
+    }
+}
+
+// step 6 for a thread's 4 destination pixels d0 .. d0 + 3 of the row at `row` elements (w pixels
+// wide): the packed stores where the layout and the alignment allow them
+template <typename T>
+__device__ __forceinline__ void fmt_store(const T (&v)[3][4], T *__restrict__ dst, const DecFmtCall &C, int64_t row,
+                                          int d0, int w, bool nchw, bool nhwc)
+{
+    using Vec = typename FmtVec<T>::type;
+    const bool full = d0 >= 0 && d0 + 4 <= w;
+    if (nchw) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            T *p = dst + c * C.sc + row + d0;
+            if (full && reinterpret_cast<uintptr_t>(p) % sizeof(Vec) == 0) {
+                Vec pk;
+                __builtin_memcpy(&pk, v[c], sizeof pk);
+                *reinterpret_cast<Vec *>(p) = pk;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (d0 + k >= 0 && d0 + k < w) p[k] = v[c][k];
+            }
+        }
+    } else if (nhwc && full) { // aligned by the choice of mis
+        T e[12];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) e[3 * k + c] = v[c][k];
+        Vec *p = reinterpret_cast<Vec *>(dst + row + 3 * (int64_t)d0);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            Vec pk;
+            __builtin_memcpy(&pk, e + 4 * j, sizeof pk);
+            p[j] = pk;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (d0 + k < 0 || d0 + k >= w) continue;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) dst[c * C.sc + row + (d0 + k) * C.sx] = v[c][k];
+        }
+    }
+}
+
+// the thread's row y and first destination pixel d0 of a w-wide row (see above); false: no work
+template <typename T>
+__device__ __forceinline__ bool fmt_group(const T *dst, const DecFmtCall &C, int h, int w, int &y, int &d0, int64_t &row,
+                                          bool &nchw, bool &nhwc)
+{
+    const int gpr = fmt_row_groups(w);
+    const int64_t g = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    y = (int)(g / gpr);
+    if (y >= h) return false;
+    nchw = C.sx == 1, nhwc = !nchw && C.sc == 1 && C.sx == 3;
+    row = (int64_t)y * C.sy;
+    // elements from address 0 to (channel 0, y, x' = 0); group k starts mis slots before it, where
+    // the address of its first pixel is a multiple of 4 elements (NHWC: 3 mis == a0 mod 4)
+    const uint64_t a0 = (uint64_t)(reinterpret_cast<uintptr_t>(dst) / sizeof(T)) + (uint64_t)row;
+    const int mis = nchw ? (int)(a0 & 3) : nhwc ? (int)((3 * a0) & 3) : 0;
+    d0 = 4 * (int)(g - (int64_t)y * gpr) - mis;
+    return d0 < w;
+}
+
+// The weights are recomputed per thread from integers: RsTaps holds the run j0 .. j1 of output
+// index i and what u(i, j) = 2D - |(2j + 1) O - (2i + 1) I| needs; everything fits int32 for
+// I, O <= 16384 (the plan's bound).
+struct RsTaps {
+    int j0, j1, c, O, D2;
+    float fU;
+    __device__ __forceinline__ int u(int j) const { return D2 - abs((2 * j + 1) * O - c); }
+    __device__ __forceinline__ float w(int j) const { return __fdiv_rn((float)u(j), fU); }
+};
+
+__device__ __forceinline__ RsTaps rs_taps(int i, int I, int O)
+{
+    RsTaps t;
+    t.O = O;
+    t.D2 = 2 * max(I, O);
+    t.c = (2 * i + 1) * I;
+    // u > 0: (c - 2D - O) / 2O < j < (c + 2D - O) / 2O, clipped to the region
+    const int a = t.c - t.D2 - O, b = t.c + t.D2 - O; // b >= 1
+    t.j0 = a >= 0 ? a / (2 * O) + 1 : 0;
+    t.j1 = min((b - 1) / (2 * O), I - 1);
+    int U = 0;
+    for (int j = t.j0; j <= t.j1; ++j) U += t.u(j);
+    t.fU = (float)U;
+    return t;
+}
+
+// one frame of a resampling group: DecOut as for dec_output_fmt_batch (H x W = the region, compact)
+struct DecOutRs {
+    DecOut o;
+    float *tmp;
+};
+
+// h x w = the region at (oy, ox) of the synthesis output, as for output_fmt_body
+__device__ __forceinline__ void resample_h_body(const int32_t *__restrict__ syn, int64_t splane, int spitch, int oy, int ox,
+                                                int h, int w, int ow, int maxv, int kind, int flags,
+                                                float *__restrict__ tmp)
+{
+    const int64_t g = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    const int y = (int)(g / ow);
+    if (y >= h) return;
+    const int i = (int)(g - (int64_t)y * ow);
+    const RsTaps T = rs_taps(i, w, ow);
+    const float fmax = (float)maxv;
+    const bool matrix = flags & kFmtMatrix;
+    const int32_t *__restrict__ lrow = syn + (int64_t)(oy + y) * spitch + ox;
+    const int32_t *__restrict__ crow = syn + (int64_t)(oy + (kind == 1 ? y : y & ~1)) * spitch + ox;
+    float acc[3] = {0.f, 0.f, 0.f};
+    for (int j = T.j0; j <= T.j1; ++j) {
+        const float wj = T.w(j);
+        float q[3];
+        fmt_pixel(lrow, crow, splane, j, kind == 1 ? j : j & ~1, maxv, fmax, matrix, q);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[c] = fmt_add(acc[c], fmt_mul(wj, q[c]));
+    }
+    const int64_t tplane = (int64_t)h * ow;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) tmp[c * tplane + g] = acc[c];
+}
+
+// tmp = [3][h][ow] of resample_h_body; the frame at dst is oh x ow
+template <typename T>
+__device__ __forceinline__ void resample_v_body(const float *__restrict__ tmp, int h, int oh, int ow, int flags,
+                                                T *__restrict__ dst, const DecFmtCall &C)
+{
+    int y, d0;
+    int64_t row;
+    bool nchw, nhwc;
+    if (!fmt_group<T>(dst, C, oh, ow, y, d0, row, nchw, nhwc)) return;
+    const RsTaps R = rs_taps(y, h, oh);
+    const bool mirror = flags & kFmtMirror;
+    // element indices of tmp fit 32 bits (3 h ow <= 3 * 2^28): one base and 32-bit offsets
+    const unsigned tplane = (unsigned)h * (unsigned)ow;
+    unsigned x[4];
+    float acc[3][4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int d = min(max(d0 + k, 0), ow - 1); // the surplus slots of a partial group are never stored
+        x[k] = (unsigned)(mirror ? ow - 1 - d : d);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[c][k] = 0.f;
+    }
+    for (int j = R.j0; j <= R.j1; ++j) {
+        const float wj = R.w(j);
+        const unsigned r0 = (unsigned)j * (unsigned)ow;
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc[c][k] = fmt_add(acc[c][k], fmt_mul(wj, tmp[c * tplane + r0 + x[k]]));
+    }
+    T v[3][4];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[c][k] = fmt_elem<T>(fmt_add(fmt_mul(acc[c][k], C.scale[c]), C.bias[c]));
+    fmt_store<T>(v, dst, C, row, d0, ow, nchw, nhwc);
+}
+
+__global__ __launch_bounds__(kThreads) void dec_resample_h(const int32_t *__restrict__ syn, int H, int W, int oy, int ox,
+                                                           int h, int w, int ow, int maxv, int kind, int flags,
+                                                           float *__restrict__ tmp)
+{
+    resample_h_body(syn, (int64_t)H * W, W, oy, ox, h, w, ow, maxv, kind, flags, tmp);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_resample_v(const float *__restrict__ tmp, int h, int oh, int ow, int flags,
+                                                           T *__restrict__ dst, DecFmtCall C)
+{
+    resample_v_body<T>(tmp, h, oh, ow, flags, dst, C);
+}
+
+// a tail group: frame blockIdx.y's compact region; the grid covers the group's largest region
+__global__ __launch_bounds__(kThreads) void dec_resample_h_batch(const DecOutRs *__restrict__ Os, int ow)
+{
+    const DecOutRs R = Os[blockIdx.y];
+    const DecOut &O = R.o;
+    resample_h_body(O.syn, (int64_t)O.H * O.W, O.W, 0, 0, O.H, O.W, ow, O.maxv, O.kind, O.bps, R.tmp);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_resample_v_batch(const DecOutRs *__restrict__ Os, int oh, int ow,
+                                                                 DecFmtCall C)
+{
+    const DecOutRs R = Os[blockIdx.y];
+    resample_v_body<T>(R.tmp, R.o.H, oh, ow, R.o.bps, reinterpret_cast<T *>(R.o.dst), C);
+}
+
+unsigned resample_h_blocks(int h, int ow) { return (unsigned)(((int64_t)h * ow + kThreads - 1) / kThreads); }
+
 } // namespace
 
 size_t dec_ups_workspace_elems(const int *lh, const int *lw, int L)
@@ -1174,6 +1403,28 @@ int launch_dec_output_fmt(const int32_t *syn, int h, int w, const DecWindow &rec
     });
 }
 
+size_t dec_resample_tmp_elems(int region_h, int out_w) { return 3 * (size_t)region_h * out_w; }
+
+int launch_dec_resample(const int32_t *syn, int h, int w, const DecWindow &rect, int bitdepth, int kind,
+                        const DecFmt &fmt, float *tmp, void *dst, hipStream_t s)
+{
+    if (kind != 0 && kind != 1) return ccmi_set_error(CCMI_ERR_ARG, "dec: tensor output kind %d", kind);
+    if (rect.y0 < 0 || rect.x0 < 0 || rect.y1 > h || rect.x1 > w || rect.h() < 1 || rect.w() < 1)
+        return ccmi_set_error(CCMI_ERR_ARG, "dec: region outside the frame");
+    if (kind == 0 && ((rect.y0 | rect.x0) & 1)) return ccmi_set_error(CCMI_ERR_ARG, "dec: a 420 region needs an even origin");
+    if (!fmt.rs || fmt.out_h < 1 || fmt.out_w < 1 || !tmp) return ccmi_set_error(CCMI_ERR_ARG, "dec: resample without a size");
+    const int maxv = (1 << bitdepth) - 1;
+    hipLaunchKernelGGL(dec_resample_h, dim3(resample_h_blocks(rect.h(), fmt.out_w)), dim3(kThreads), 0, s, syn, h, w,
+                       rect.y0, rect.x0, rect.h(), rect.w(), fmt.out_w, maxv, kind, fmt_flags(fmt), tmp);
+    CCMI_HIP_CHECK(hipGetLastError());
+    const dim3 grid(output_fmt_blocks(fmt.out_h, fmt.out_w));
+    return with_elem_type(fmt.elem, [&](auto t) {
+        using T = decltype(t);
+        hipLaunchKernelGGL(dec_resample_v<T>, grid, dim3(kThreads), 0, s, tmp, rect.h(), fmt.out_h, fmt.out_w,
+                           fmt_flags(fmt), static_cast<T *>(dst), fmt_call(fmt));
+    });
+}
+
 // ------------------------------------------------------------------ batched decoder tail
 bool dec_tail_batchable(const DecTailFrame &f)
 {
@@ -1189,13 +1440,15 @@ bool dec_tail_same_group(const DecTailFrame &a, const DecTailFrame &b)
     // a formatted output is one kernel per element type; the format is one per call, so the
     // frames of a call group as they do without it
     if (a.fmt.on != b.fmt.on || a.fmt.elem != b.fmt.elem) return false;
+    if (a.fmt.rs != b.fmt.rs || a.fmt.out_h != b.fmt.out_h || a.fmt.out_w != b.fmt.out_w) return false;
     if (a.windowed) {
         // region decode: the tables carry each frame's true plane sizes and its windows, the
         // grids cover the group's largest window; one region size (the output grid), any
-        // frame size, any origin
+        // frame size, any origin.  A resample's output grid is the output size (above): its
+        // regions may differ, and the synthesis and horizontal-pass grids cover the largest
         if (a.sample != b.sample || a.kind != b.kind) return false;
-        return a.syn.n_layers == b.syn.n_layers && a.syn.c_in == b.syn.c_in && a.roi.rect.h() == b.roi.rect.h() &&
-               a.roi.rect.w() == b.roi.rect.w();
+        if (a.syn.n_layers != b.syn.n_layers || a.syn.c_in != b.syn.c_in) return false;
+        return a.fmt.rs || (a.roi.rect.h() == b.roi.rect.h() && a.roi.rect.w() == b.roi.rect.w());
     }
     for (int l = 0; l < a.ups.n_layers; ++l)
         if (a.ups.lh[l] != b.ups.lh[l] || a.ups.lw[l] != b.ups.lw[l]) return false;
@@ -1208,18 +1461,19 @@ static size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 // Byte layout of the argument table of a group of n frames: [step][frame] pyramid levels, then
 // [frame] synthesis arguments, then [frame] DecOut, each section 16-byte aligned.  A window-form
-// group holds DecLevelWin / DecSynFusedWin, the others DecLevel / DecSynFused.
+// group holds DecLevelWin / DecSynFusedWin, the others DecLevel / DecSynFused; a resampling
+// group holds DecOutRs for DecOut.
 struct TailTable {
     size_t syn, out, bytes; // section offsets (the levels are at 0) and the total size
-    TailTable(int steps, int n, bool windowed)
+    TailTable(int steps, int n, bool windowed, bool resample)
     {
         const size_t st = steps > 0 ? (size_t)steps : 0;
         syn = al16((windowed ? sizeof(DecLevelWin) : sizeof(DecLevel)) * st * n);
         out = syn + al16((windowed ? sizeof(DecSynFusedWin) : sizeof(DecSynFused)) * (size_t)n);
-        bytes = out + al16(sizeof(DecOut) * (size_t)n);
+        bytes = out + al16((resample ? sizeof(DecOutRs) : sizeof(DecOut)) * (size_t)n);
     }
     // the group of `fr[0]`
-    TailTable(const DecTailFrame &f0, int n) : TailTable(f0.ups.n_layers - 1, n, f0.windowed) {}
+    TailTable(const DecTailFrame &f0, int n) : TailTable(f0.ups.n_layers - 1, n, f0.windowed, f0.fmt.rs != 0) {}
     template <typename T> T *at(void *tab, size_t off) const { return reinterpret_cast<T *>(static_cast<uint8_t *>(tab) + off); }
     template <typename T> const T *at(const void *tab, size_t off) const
     {
@@ -1227,12 +1481,22 @@ struct TailTable {
     }
 };
 
-size_t dec_tail_table_bytes(int n_layers, int n, bool windowed) { return TailTable(n_layers - 1, n, windowed).bytes; }
+size_t dec_tail_table_bytes(int n_layers, int n, bool windowed, bool resample)
+{
+    return TailTable(n_layers - 1, n, windowed, resample).bytes;
+}
 
 static DecOut make_out(const DecTailFrame &f, int h, int w)
 {
     return DecOut{f.syn.out, h, w, (1 << f.bitdepth) - 1, f.kind, f.fmt.on ? fmt_flags(f.fmt) : f.bitdepth <= 8 ? 1 : 2,
                   f.dst};
+}
+
+// entry i of a group's output section
+static void put_out(const TailTable &T, void *host_tab, int i, const DecTailFrame &f, int h, int w)
+{
+    if (f.fmt.rs) T.at<DecOutRs>(host_tab, T.out)[i] = DecOutRs{make_out(f, h, w), f.rs_tmp};
+    else T.at<DecOut>(host_tab, T.out)[i] = make_out(f, h, w);
 }
 
 // the window-form tables
@@ -1242,7 +1506,6 @@ static void dec_tail_fill_win(const DecTailFrame *const *fr, int n, void *host_t
     const TailTable T(*fr[0], n);
     DecLevelWin *lv = T.at<DecLevelWin>(host_tab, 0);
     DecSynFusedWin *sf = T.at<DecSynFusedWin>(host_tab, T.syn);
-    DecOut *oo = T.at<DecOut>(host_tab, T.out);
     for (int i = 0; i < n; ++i) {
         DecLevelWin tmp[CCMI_MAX_GRIDS];
         make_levels_win(*fr[i], tmp);
@@ -1258,7 +1521,7 @@ static void dec_tail_fill_win(const DecTailFrame *const *fr, int n, void *host_t
         // the synthesis output is the region itself, compact: the whole-frame output kernel
         // converts it as a frame of the region's size (420: the origin is even, so its even
         // rows and columns are the frame's)
-        oo[i] = make_out(*fr[i], S.rh, S.rw);
+        put_out(T, host_tab, i, *fr[i], S.rh, S.rw);
     }
 }
 
@@ -1269,19 +1532,28 @@ void dec_tail_fill(const DecTailFrame *const *fr, int n, void *host_tab)
     const TailTable T(*fr[0], n);
     DecLevel *lv = T.at<DecLevel>(host_tab, 0);
     DecSynFused *sf = T.at<DecSynFused>(host_tab, T.syn);
-    DecOut *oo = T.at<DecOut>(host_tab, T.out);
     for (int i = 0; i < n; ++i) {
         DecLevel tmp[CCMI_MAX_GRIDS];
         make_levels(fr[i]->ups, tmp);
         for (int st = 0; st < steps; ++st) lv[(size_t)st * n + i] = tmp[st];
         sf[i] = make_syn_fused(fr[i]->syn);
-        oo[i] = make_out(*fr[i], fr[i]->syn.h, fr[i]->syn.w);
+        put_out(T, host_tab, i, *fr[i], fr[i]->syn.h, fr[i]->syn.w);
     }
 }
 
 // the tensor output of a group: h x w samples of one kind and sample type per frame
 static int launch_output_tensor_batch(const DecTailFrame &f0, int h, int w, int n, const DecOut *oo, hipStream_t s)
 {
+    if (f0.fmt.rs) { // the section holds DecOutRs; h = the group's tallest region
+        const DecOutRs *rr = reinterpret_cast<const DecOutRs *>(oo);
+        const int oh = f0.fmt.out_h, ow = f0.fmt.out_w;
+        hipLaunchKernelGGL(dec_resample_h_batch, dim3(resample_h_blocks(h, ow), n), dim3(kThreads), 0, s, rr, ow);
+        CCMI_HIP_CHECK(hipGetLastError());
+        const dim3 grid(output_fmt_blocks(oh, ow), n);
+        return with_elem_type(f0.fmt.elem, [&](auto t) {
+            hipLaunchKernelGGL(dec_resample_v_batch<decltype(t)>, grid, dim3(kThreads), 0, s, rr, oh, ow, fmt_call(f0.fmt));
+        });
+    }
     if (f0.fmt.on) { // the format but its per-frame flags (in the table) is the call's
         const dim3 grid(output_fmt_blocks(h, w), n);
         return with_elem_type(f0.fmt.elem, [&](auto t) {
@@ -1316,7 +1588,11 @@ static int launch_dec_tail_batch_win(const DecTailFrame *const *fr, int n, const
         CCMI_HIP_CHECK(hipGetLastError());
     }
     const int halo = f0.syn.n_layers - 2;
-    const int rh = f0.roi.rect.h(), rw = f0.roi.rect.w();
+    int rh = 1, rw = 1; // one region size per group, but a resampling group's: the largest
+    for (int i = 0; i < n; ++i) {
+        rh = std::max(rh, fr[i]->roi.rect.h());
+        rw = std::max(rw, fr[i]->roi.rect.w());
+    }
     const int gtx = ccmi_div_up(rw, kRW - 2 * halo);
     const dim3 sg(gtx * ccmi_div_up(rh, kRH - 2 * halo), n);
     with_syn_cin(f0.syn.c_in, [&](auto cin) {

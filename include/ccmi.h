@@ -460,6 +460,59 @@ int ccmi_latents_render_fmt(const ccmi_latents *h, const int *index /* [m] or NU
                             const ccmi_tensor_fmt *fmt, int out_bitdepth, int out_chroma, void *workspace,
                             size_t workspace_bytes, void *stream);
 
+/* Resampled formatted output: the formatted sink with an output size.  Every frame's region, of
+ * any size, is resampled to out_h x out_w by an antialiased triangle filter -- the filter of
+ * interpolate(mode="bilinear", antialias=True, align_corners=False) and of PIL's BILINEAR --
+ * between steps 3 and 4 of the ccmi_tensor_fmt contract, in the decoder's output stage: crop,
+ * resize, colour, normalisation, element type, layout and mirror in one call, and frames of
+ * different region sizes share the tail's launches.  rs == NULL is the _fmt call itself.
+ * Steps 1-3 give q_c(y, x) over the region, h x w.  Then
+ *   3a. weights, per axis: region extent I, output extent O, D = max(I, O).  For output index i
+ *       and source index j in [0, I): u(i, j) = max(0, 2 D - |(2 j + 1) O - (2 i + 1) I|), an
+ *       integer.  The taps of i are the j with u > 0, a contiguous run, clipped to the REGION (the
+ *       region is the image being resized: the result equals crop-then-resize).  U(i) = sum_j
+ *       u(i, j); w(i, j) = (float)u / (float)U, conversions to nearest even, one correctly
+ *       rounded float32 division.  With I == O the only tap is j = i with w = 1: that pass is the
+ *       identity, bit for bit;
+ *   3b. horizontal pass, per region row y: t_c(y, i) = sum_j w_x(i, j) q_c(y, j), evaluated from 0
+ *       over j ascending, every product and every sum its own float32 operation (no fused
+ *       multiply-add);
+ *   3c. vertical pass: r'_c(i, k) = sum_y w_y(i, y) t_c(y, k), evaluated the same way over y
+ *       ascending.
+ * Steps 4-6 apply to r' at the output size; the mirror is x' = out_w - 1 - x.
+ * Checked by the plan before any GPU work, CCMI_ERR_ARG naming the frame and nothing written:
+ * out_w or out_h outside [1, 16384], a region side above 16384 (the weights' integers then fit
+ * 32 bits), an unknown filter.  The strides, their aliasing check and out_caps refer to the
+ * out_h x out_w frame; geom[j].width / height are out_w / out_h and elems is 3 out_w out_h.  The
+ * 420 rule stays on the region (x, y, w and h even); the output size may be anything.
+ * ccmi_roi_info is unchanged.  The workspace grows by the float32 intermediate t, [3][h][out_w]
+ * per frame.  Streams with a fused synthesis of one architecture share one batched tail whatever
+ * their region sizes (whole-frame requests: one per frame size, as ever); the others run their
+ * per-frame tail.  ccmi_decode_last_tail_groups(): how many batched tail groups and how many
+ * per-frame tails this thread's last decode or render call launched (0, 0 after a call that
+ * failed or only planned, and after ccmi_latents_decode, which runs no tail). */
+enum { CCMI_FILTER_TRIANGLE = 0 };
+typedef struct ccmi_resample { int out_w, out_h, filter; } ccmi_resample;
+int ccmi_decode_batch_dev_rs_plan(const uint8_t *const *streams, const size_t *lens, int n,
+                                  const ccmi_rect *roi /* [n] or NULL */, int out_bitdepth, int out_chroma,
+                                  const ccmi_tensor_fmt *fmt, const ccmi_resample *rs /* or NULL */,
+                                  ccmi_frame_geom *geom /* [n] */, ccmi_roi_info *info /* [n] or NULL */,
+                                  size_t *workspace_bytes);
+int ccmi_decode_batch_dev_rs(const uint8_t *const *streams, const size_t *lens, int n,
+                             const ccmi_rect *roi /* [n] or NULL */, void *const *out_dev, const size_t *out_caps,
+                             const ccmi_tensor_fmt *fmt, const ccmi_resample *rs /* or NULL */, int out_bitdepth,
+                             int out_chroma, void *workspace, size_t workspace_bytes, void *stream);
+int ccmi_latents_render_rs_plan(const ccmi_latents *h, const int *index /* [m] or NULL */, int m,
+                                const ccmi_rect *roi /* [m] or NULL */, int out_bitdepth, int out_chroma,
+                                const ccmi_tensor_fmt *fmt, const ccmi_resample *rs /* or NULL */,
+                                ccmi_frame_geom *geom /* [m] */, ccmi_roi_info *info /* [m] or NULL */,
+                                size_t *workspace_bytes);
+int ccmi_latents_render_rs(const ccmi_latents *h, const int *index /* [m] or NULL */, int m,
+                           const ccmi_rect *roi /* [m] or NULL */, void *const *out_dev, const size_t *out_caps,
+                           const ccmi_tensor_fmt *fmt, const ccmi_resample *rs /* or NULL */, int out_bitdepth,
+                           int out_chroma, void *workspace, size_t workspace_bytes, void *stream);
+int ccmi_decode_last_tail_groups(int *batched, int *per_frame);
+
 /* Network weights of a stream's intra frame as the decoder's fixed-point integers
  * (cc-frame-decoder.cpp:201-353, read_arm / read_ups / read_syn):
  *   arm: per hidden layer W[d][d] (out, in) then b[d]; then W_out[2][d], b_out[2]

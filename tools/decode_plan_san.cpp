@@ -2,7 +2,8 @@
 // (decode_plan, dec_plan.cpp) on a machine without a GPU: every header-only entry point, the
 // latent store's layout and plan-only handles (ccmi_latents_*, store = NULL) with their render
 // planning included, the formatted sinks (ccmi_tensor_fmt: element types, stride sets, a mirror
-// array of exactly n bytes, and the run entry point with capacities it must reject), over the streams named on the command line, whole, in batches of 7, over a list of regions, and
+// array of exactly n bytes, and the run entry point with capacities it must reject), the resampling
+// sinks (ccmi_resample: output sizes in and out of range, an unknown filter), over the streams named on the command line, whole, in batches of 7, over a list of regions, and
 // truncated at each length from 0 to the header size plus 8.  Every (truncated) stream sits in
 // a heap block of exactly its length, so a read past its end is reported.  No HIP call is made.
 //
@@ -92,6 +93,34 @@ void plan_all(const std::vector<Stream> &b, const std::vector<ccmi_rect> &rects,
                                              &need));
         count(ccmi_decode_batch_dev_fmt_plan(sp.data(), ln.data(), n, nullptr, bd, chroma, &f, geom.data(), nullptr, &need));
     }
+    // the resampling sink: output sizes in and out of range, an unknown filter, over the first
+    // stride sets of every element type; rs NULL is the formatted plan itself
+    const ccmi_resample sizes_rs[] = {{224, 224, 0}, {1, 1, 0}, {16384, 3, 0}, {7, 16384, 0}, {0, 8, 0},
+                                      {8, -1, 0},    {16385, 8, 0}, {0x7fffffff, 0x7fffffff, 0}, {8, 8, 1}};
+    for (const ccmi_resample &rs : sizes_rs)
+        for (size_t k = 0; k < fmts.size(); k += 5) {
+            count(ccmi_decode_batch_dev_rs_plan(sp.data(), ln.data(), n, rects.data(), bd, chroma, &fmts[k], &rs, geom.data(),
+                                                info.data(), &need));
+            count(ccmi_decode_batch_dev_rs_plan(sp.data(), ln.data(), n, nullptr, bd, chroma, &fmts[k], &rs, geom.data(),
+                                                nullptr, &need));
+        }
+    count(ccmi_decode_batch_dev_rs_plan(sp.data(), ln.data(), n, rects.data(), bd, chroma, &fmts[1], nullptr, geom.data(),
+                                        info.data(), &need));
+    {
+        // the run entry point with capacities one byte short of what its own plan asks for the
+        // output size: rejected before any GPU work
+        ccmi_tensor_fmt f = fmts[0];
+        f.colour = CCMI_COLOUR_RGB;
+        const ccmi_resample rs{9, 5, CCMI_FILTER_TRIANGLE};
+        std::vector<void *> outs(n, reinterpret_cast<void *>(uintptr_t(1) << 40));
+        std::vector<size_t> caps(n, 3 * 9 * 5 * 4 - 1);
+        const int rc = ccmi_decode_batch_dev_rs(sp.data(), ln.data(), n, rects.data(), outs.data(), caps.data(), &f, &rs, bd,
+                                                chroma, nullptr, 0, nullptr);
+        if (rc == CCMI_OK) abort();
+        count(rc);
+        int batched = -1, per_frame = -1;
+        if (ccmi_decode_last_tail_groups(&batched, &per_frame) != CCMI_OK || batched != 0 || per_frame != 0) abort();
+    }
     {
         // the run entry point with capacities one byte short of what its own plan asks (or 0 when
         // the plan fails): rejected before any GPU work, the made-up pointers are never used
@@ -143,6 +172,13 @@ void plan_all(const std::vector<Stream> &b, const std::vector<ccmi_rect> &rects,
         count(ccmi_latents_render_fmt_plan(h, nullptr, n, nullptr, bd, chroma, &f, geom.data(), nullptr, &need));
     }
     count(ccmi_latents_render_fmt(h, nullptr, n, nullptr, &out0, &cap0, &fmts[1], bd, chroma, nullptr, 0, nullptr)); // plan-only
+    for (const ccmi_resample &rs : sizes_rs) {
+        count(ccmi_latents_render_rs_plan(h, nullptr, n, rects.data(), bd, chroma, &fmts[1], &rs, geom.data(), info.data(), &need));
+        count(ccmi_latents_render_rs_plan(h, nullptr, n, nullptr, bd, chroma, &fmts[13], &rs, geom.data(), nullptr, &need));
+    }
+    count(ccmi_latents_render_rs_plan(h, nullptr, n, nullptr, bd, chroma, &fmts[1], nullptr, geom.data(), nullptr, &need));
+    count(ccmi_latents_render_rs(h, nullptr, n, nullptr, &out0, &cap0, &fmts[1], &sizes_rs[0], bd, chroma, nullptr, 0,
+                                 nullptr)); // plan-only
     void *out = nullptr;
     size_t cap = 0;
     count(ccmi_latents_render(h, nullptr, n, nullptr, &out, &cap, 1, bd, chroma, nullptr, 0, nullptr)); // plan-only: an error
