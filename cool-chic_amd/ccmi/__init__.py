@@ -30,6 +30,8 @@ EXPORTED = [
     "ccmi_decode_batch_dev_plan", "ccmi_decode_batch_dev", "ccmi_decode_batch_dev_roi_plan", "ccmi_decode_batch_dev_roi",
     "ccmi_latents_plan", "ccmi_latents_decode", "ccmi_latents_free", "ccmi_latents_count", "ccmi_latents_values",
     "ccmi_latents_render_plan", "ccmi_latents_render",
+    "ccmi_latents_compact_plan", "ccmi_latents_compact_measure", "ccmi_latents_compact", "ccmi_latents_concat",
+    "ccmi_latents_stream_info",
     "ccmi_decode_batch_dev_fmt_plan", "ccmi_decode_batch_dev_fmt", "ccmi_latents_render_fmt_plan", "ccmi_latents_render_fmt",
     "ccmi_decode_batch_dev_rs_plan", "ccmi_decode_batch_dev_rs", "ccmi_latents_render_rs_plan", "ccmi_latents_render_rs",
     "ccmi_decode_last_tail_groups",

@@ -619,7 +619,7 @@ def last_arm_flags() -> list[int]:
     return [int(v) for v in out[: n.value]]
 
 
-LATENT_I8, LATENT_I16, LATENT_I32 = 0, 1, 2  # CCMI_LATENT_*
+LATENT_I8, LATENT_I16, LATENT_I32, LATENT_SEG = 0, 1, 2, 3  # CCMI_LATENT_*; SEG by LatentStore.compact() only
 
 
 def _bind_latents():
@@ -634,8 +634,15 @@ def _bind_latents():
         L.ccmi_latents_values.argtypes = [P, I, P, Z, P]
         L.ccmi_latents_render_plan.argtypes = [P, P, I, P, I, I, I, P, P, P]
         L.ccmi_latents_render.argtypes = [P, P, I, P, P, P, I, I, I, P, Z, P]
+        L.ccmi_latents_compact_plan.argtypes = [P, P, P]
+        L.ccmi_latents_compact_measure.argtypes = [P, P, Z, P, P, P]
+        L.ccmi_latents_compact.argtypes = [P, P, Z, P, Z, P, P]
+        L.ccmi_latents_concat.argtypes = [P, I, P]
+        L.ccmi_latents_stream_info.argtypes = [P, I, P, P]
         for f in (L.ccmi_latents_plan, L.ccmi_latents_decode, L.ccmi_latents_count, L.ccmi_latents_values,
-                  L.ccmi_latents_render_plan, L.ccmi_latents_render):
+                  L.ccmi_latents_render_plan, L.ccmi_latents_render, L.ccmi_latents_compact_plan,
+                  L.ccmi_latents_compact_measure, L.ccmi_latents_compact, L.ccmi_latents_concat,
+                  L.ccmi_latents_stream_info):
             f.restype = C.c_int
         L._ccmi_latents_bound = True
     return L
@@ -652,7 +659,13 @@ class LatentStore:
     outside -32768..32767); torch.int8 / torch.int16 / torch.int32: exactly that type, and a
     latent that does not fit it is a CcmiError (ERR_UNSUPPORTED; last_arm_flags() shows which
     streams).  arm_flags: the build's CCMI_ARM_FLAG_* bits per stream.  workspace: a uint8 CUDA tensor for the build (else torch's allocator).  The
-    Python bytes are not referred to after the constructor returns."""
+    Python bytes are not referred to after the constructor returns.
+
+    compact() makes a store of the same streams with per-segment bit widths (dtype "seg", several
+    times smaller), LatentStore.concat() one store object over the streams of several (a set built
+    chunk by chunk, of any mix of types); both render exactly as the stores they were made from.
+    nbytes, stream_nbytes and stream_dtypes: the store bytes, in all and per stream, and each
+    stream's type."""
 
     def __init__(self, streams: Sequence[bytes], dtype=None, workspace=None, stream_handle: int | None = None):
         import torch
@@ -680,10 +693,64 @@ class LatentStore:
                 break
             if not (dtype is None and t == torch.int16 and any(f & ARM_FLAG_NARROW for f in last_arm_flags())):
                 check(rc)
-        self._h, self._store, self.dtype, self.nbytes = h, store, t, nstore.value
-        self.arm_flags = last_arm_flags()  # of the build; the planning and render calls clear the thread's record
+        flags = last_arm_flags()  # of the build; the planning and render calls clear the thread's record
+        self._adopt(h, [store], flags)
+
+    def _adopt(self, h, stores, arm_flags):
+        """Takes the handle h over the device tensors `stores`; the facts come from the handle."""
+        import torch
+        L = _bind_latents()
+        self._h, self._stores, self._store, self.arm_flags = h, list(stores), stores[0], arm_flags
+        names = {LATENT_I8: torch.int8, LATENT_I16: torch.int16, LATENT_I32: torch.int32, LATENT_SEG: "seg"}
+        self.stream_nbytes, self.stream_dtypes = [], []
+        for i in range(len(self)):
+            t, nb = C.c_int(0), C.c_size_t(0)
+            check(L.ccmi_latents_stream_info(h, i, C.byref(t), C.byref(nb)))
+            self.stream_nbytes.append(nb.value)
+            self.stream_dtypes.append(names[t.value])
+        self.nbytes = sum(self.stream_nbytes)
+        self.dtype = self.stream_dtypes[0] if len(set(self.stream_dtypes)) == 1 else "mixed"
         geom, _ = self.render_geometry()
         self.geometry = [{k: g[k] for k in ("width", "height", "bitdepth", "chroma", "frame_data_type")} for g in geom]
+
+    def compact(self, workspace=None, stream_handle: int | None = None) -> "LatentStore":
+        """A new store of the same streams in the segmented form (ccmi_latents_compact: runs of 64
+        latents at the narrowest of 0, 2, 4, 8, 16, 32 bits), measured, allocated exactly and
+        packed on the GPU.  This store is untouched and may be closed; the new one renders the
+        same samples.  workspace: a uint8 CUDA tensor (else torch's allocator)."""
+        import torch
+        L = _bind_latents()
+        dev = self._store.device
+        if stream_handle is None:
+            stream_handle = torch.cuda.current_stream(dev).cuda_stream
+        bound, nws, exact = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        check(L.ccmi_latents_compact_plan(self._handle(), C.byref(bound), C.byref(nws)))
+        ws = workspace
+        if ws is None:
+            ws = torch.empty(max(nws.value, 256), dtype=torch.uint8, device=dev)
+        check(L.ccmi_latents_compact_measure(self._handle(), ws.data_ptr(), ws.numel(), stream_handle, C.byref(exact), None))
+        store = torch.empty(max(exact.value, 256), dtype=torch.uint8, device=dev)
+        h = C.c_void_p(None)
+        check(L.ccmi_latents_compact(self._handle(), store.data_ptr(), store.numel(), ws.data_ptr(), ws.numel(),
+                                     stream_handle, C.byref(h)))
+        out = LatentStore.__new__(LatentStore)
+        out._adopt(h, [store], list(self.arm_flags))
+        return out
+
+    @classmethod
+    def concat(cls, stores) -> "LatentStore":
+        """One store object over the streams of `stores`, in order (ccmi_latents_concat): host
+        only, nothing is copied.  The parts may be closed afterwards: the new object keeps their
+        device tensors alive.  dtype is the parts' common type, or "mixed"."""
+        stores = list(stores)
+        if not stores:
+            raise ValueError("LatentStore.concat: no stores")
+        parts = (C.c_void_p * len(stores))(*[s._handle() for s in stores])
+        h = C.c_void_p(None)
+        check(_bind_latents().ccmi_latents_concat(parts, len(stores), C.byref(h)))
+        out = cls.__new__(cls)
+        out._adopt(h, [t for s in stores for t in s._stores], [f for s in stores for f in s.arm_flags])
+        return out
 
     def __len__(self):
         return _bind_latents().ccmi_latents_count(self._handle())
@@ -699,6 +766,7 @@ class LatentStore:
             _bind_latents().ccmi_latents_free(self._h)
             self._h = None
             self._store = None
+            self._stores = []
 
     def __del__(self):
         try:

@@ -376,11 +376,12 @@ struct Run {
     std::vector<uint8_t> tab; // the tail groups' tables, then the latent store's job table
     size_t tab_used = 0;      // bytes of `tab` to upload
     // latent store: a launch's part of the job table.  Sink: one per chunk, then the copy of the
-    // networks' integers; source: the one unpack.
+    // networks' integers; source: one unpack per storage type among the frames' streams.
     struct LatLaunch {
         size_t first;
         int n;
         uint32_t blocks;
+        int type; // CCMI_LATENT_*
     };
     std::vector<LatLaunch> lat;
     size_t lat_tab() const { return pl.lat_tab_off - pl.tail_off; } // of the job table in `tab`
@@ -508,8 +509,8 @@ int build_tail_groups(Run &r)
         t.syn.params = reinterpret_cast<const int32_t *>(r.dev + p.syn_off);
         if (r.rq.src) { // the networks' integers stay in the store
             const LatentStream &S = r.rq.src->s[p.src];
-            t.ups.kernels = reinterpret_cast<const int32_t *>(r.rq.src->store + S.ups_off);
-            t.syn.params = reinterpret_cast<const int32_t *>(r.rq.src->store + S.syn_off);
+            t.ups.kernels = reinterpret_cast<const int32_t *>(S.base + S.ups_off);
+            t.syn.params = reinterpret_cast<const int32_t *>(S.base + S.syn_off);
         }
         t.ups.workspace = reinterpret_cast<int32_t *>(r.dev + p.ws_off);
         t.ups.out = reinterpret_cast<int32_t *>(r.dev + p.dense_off);
@@ -546,11 +547,12 @@ int build_tail_groups(Run &r)
 void build_pack_jobs(Run &r)
 {
     const ccmi_latents &h = *r.rq.lat_store;
-    uint8_t *store = const_cast<uint8_t *>(h.store);
+    uint8_t *store = const_cast<uint8_t *>(h.s[0].base); // a build has one store and one type
+    const int type = h.s[0].type;
     DecLatPackJob *jobs = reinterpret_cast<DecLatPackJob *>(r.tab.data() + r.lat_tab());
     size_t nj = 0;
     for (int c = 0; c < r.K; ++c) {
-        Run::LatLaunch L{nj, 0, 0};
+        Run::LatLaunch L{nj, 0, 0, type};
         for (size_t i = 0; i < r.pl.fr.size(); ++i) {
             if (r.chunk_of[i] != c) continue;
             const FramePlan &p = r.pl.fr[i];
@@ -564,13 +566,13 @@ void build_pack_jobs(Run &r)
                                            L.blocks,
                                            kArmPrec,
                                            0};
-                L.blocks += dec_lat_pack_blocks(n, h.type);
+                L.blocks += dec_lat_pack_blocks(n, type);
                 ++L.n;
             }
         }
         r.lat.push_back(L);
     }
-    Run::LatLaunch N{nj, 0, 0};
+    Run::LatLaunch N{nj, 0, 0, CCMI_LATENT_I32};
     for (size_t i = 0; i < r.pl.fr.size(); ++i) {
         const FramePlan &p = r.pl.fr[i];
         const size_t src[2] = {p.ups_off, p.syn_off}, dst[2] = {h.s[i].ups_off, h.s[i].syn_off};
@@ -588,36 +590,41 @@ void build_pack_jobs(Run &r)
 }
 
 // Latent-store source: an unpack job per grid of every output frame, over the rectangle of
-// the plane the frame's tail reads (whole planes unless the tail runs on windows).
+// the plane the frame's tail reads (whole planes unless the tail runs on windows).  The jobs of
+// one storage type follow each other and share a launch: a handle over stores of several types
+// (ccmi_latents_concat) costs one launch per type present, whatever the order of the frames.
 void build_unpack_jobs(Run &r)
 {
     const ccmi_latents &h = *r.rq.src;
     DecLatUnpackJob *jobs = reinterpret_cast<DecLatUnpackJob *>(r.tab.data() + r.lat_tab());
     size_t nj = 0;
-    Run::LatLaunch L{0, 0, 0};
-    for (const FramePlan &p : r.pl.fr) {
-        const LatentStream &S = h.s[p.src];
-        for (int l = 0; l < p.f.n_layers; ++l) {
-            const DecWindow &w = p.tail.roi.lat[l];
-            const uint32_t blocks = dec_lat_unpack_blocks(w);
-            if (!blocks) continue;
-            jobs[nj++] = DecLatUnpackJob{p.f.lat_n[l] ? h.store + S.grid_off[l] : nullptr,
-                                         reinterpret_cast<int32_t *>(r.dev + p.lat_off) + p.tail.ups.off[l],
-                                         p.f.lw[l], w.y0, w.y1, w.x0, w.x1, L.blocks, kArmPrec, 0};
-            L.blocks += blocks;
-            ++L.n;
+    for (int type = CCMI_LATENT_I8; type <= CCMI_LATENT_SEG; ++type) {
+        Run::LatLaunch L{nj, 0, 0, type};
+        for (const FramePlan &p : r.pl.fr) {
+            const LatentStream &S = h.s[p.src];
+            if (S.type != type) continue;
+            for (int l = 0; l < p.f.n_layers; ++l) {
+                const DecWindow &w = p.tail.roi.lat[l];
+                const uint32_t blocks = dec_lat_unpack_blocks(w);
+                if (!blocks) continue;
+                jobs[nj++] = DecLatUnpackJob{p.f.lat_n[l] ? S.base + S.grid_off[l] : nullptr,
+                                             reinterpret_cast<int32_t *>(r.dev + p.lat_off) + p.tail.ups.off[l],
+                                             p.f.lw[l], w.y0, w.y1, w.x0, w.x1, L.blocks, kArmPrec, p.f.lh[l]};
+                L.blocks += blocks;
+                ++L.n;
+            }
         }
+        if (L.n) r.lat.push_back(L);
     }
-    r.lat.push_back(L);
     r.tab_used = r.lat_tab() + nj * sizeof(DecLatUnpackJob);
 }
 
-int launch_lat(const Run &r, const Run::LatLaunch &L, int type, hipStream_t cs)
+int launch_lat(const Run &r, const Run::LatLaunch &L, hipStream_t cs)
 {
     const uint8_t *tab = r.dev + r.pl.lat_tab_off;
     if (r.rq.src)
-        return launch_dec_lat_unpack(reinterpret_cast<const DecLatUnpackJob *>(tab) + L.first, L.n, L.blocks, type, cs);
-    return launch_dec_lat_pack(reinterpret_cast<const DecLatPackJob *>(tab) + L.first, L.n, L.blocks, type, cs);
+        return launch_dec_lat_unpack(reinterpret_cast<const DecLatUnpackJob *>(tab) + L.first, L.n, L.blocks, L.type, cs);
+    return launch_dec_lat_pack(reinterpret_cast<const DecLatPackJob *>(tab) + L.first, L.n, L.blocks, L.type, cs);
 }
 
 // the per-frame tail of a frame the batched tail does not take: pyramid, synthesis per
@@ -661,10 +668,11 @@ int launch_chunk(const Run &r, int c, hipStream_t cs, hipEvent_t arm_done)
                 return rc;
     // a render's planes come from the store: the unpack stands where the ARM stage does
     if (r.rq.src)
-        if (int rc = launch_lat(r, r.lat[0], r.rq.src->type, cs)) return rc;
+        for (const Run::LatLaunch &L : r.lat)
+            if (int rc = launch_lat(r, L, cs)) return rc;
     if (arm_done) CCMI_HIP_CHECK(hipEventRecord(arm_done, cs));
     if (r.rq.lat_store) // a store build has no tail: the chunk's planes are packed instead
-        return launch_lat(r, r.lat[c], r.rq.lat_store->type, cs);
+        return launch_lat(r, r.lat[c], cs);
     for (const TailGroup &g : r.tails)
         if (g.chunk == c)
             if (int rc = launch_dec_tail_batch(g.frames.data(), (int)g.frames.size(), r.dev + r.pl.tail_off + g.off, cs))
@@ -789,7 +797,7 @@ int read_back(const Run &r)
                 return ccmi_set_error(CCMI_ERR_UNSUPPORTED,
                                       "latents: stream %d, latent grid %d: a latent does not fit %s; build the store "
                                       "with a wider element type",
-                                      i, l, kName[r.rq.lat_store->type]);
+                                      i, l, kName[r.rq.lat_store->s[0].type]);
             }
     for (int i = 0; i < n && lat_out; ++i)
         for (size_t k = 0; k < pl.fr[i].lat_elems; ++k) lat_out[i][k] >>= kArmPrec;
@@ -877,7 +885,7 @@ int decode_run(const DecodeRequest &rq, DecodePlan &pl, hipStream_t s)
     if (r.tab_used)
         CCMI_HIP_CHECK(hipMemcpyAsync(r.dev + pl.tail_off, r.tab.data(), r.tab_used, hipMemcpyHostToDevice, s));
     if (rq.lat_store) // the networks' integers: constant part -> store, before the chunks fork
-        if (int rc = launch_lat(r, r.lat[r.K], CCMI_LATENT_I32, s)) return rc;
+        if (int rc = launch_lat(r, r.lat[r.K], s)) return rc;
     ev.rec(1, s);
     if (int rc = run_chunks(r, ev, lease)) return rc;
     if (!rq.lat_store) { // what launch_chunk ran: every group, and a tail of its own per other frame
@@ -1136,7 +1144,8 @@ extern "C" int ccmi_latents_decode(const uint8_t *const *streams, const size_t *
             return ccmi_set_error(CCMI_ERR_ARG, "latents_decode: store of %zu bytes, need %zu", store_bytes, h->store_bytes);
         if (reinterpret_cast<uintptr_t>(store) % 256)
             return ccmi_set_error(CCMI_ERR_ARG, "latents_decode: the store must be 256-byte aligned");
-        h->store = static_cast<const uint8_t *>(store);
+        h->resident = true;
+        for (LatentStream &S : h->s) S.base = static_cast<const uint8_t *>(store);
         if (int rc = decode_run(rq, pl, static_cast<hipStream_t>(stream))) return rc;
     } else {
         // plan-only handle: the networks are decoded on the host, nothing touches the GPU
@@ -1165,7 +1174,7 @@ extern "C" int ccmi_latents_count(const ccmi_latents *h) { return h ? (int)h->s.
 extern "C" int ccmi_latents_values(const ccmi_latents *h, int i, int32_t *out_dev, size_t cap_elems, void *stream)
 {
     if (!h || !out_dev) return ccmi_set_error(CCMI_ERR_ARG, "latents_values: null argument");
-    if (!h->store) return ccmi_set_error(CCMI_ERR_ARG, "latents_values: the handle is plan-only (built without a store)");
+    if (!h->resident) return ccmi_set_error(CCMI_ERR_ARG, "latents_values: the handle is plan-only (built without a store)");
     if (i < 0 || i >= (int)h->s.size())
         return ccmi_set_error(CCMI_ERR_ARG, "latents_values: stream %d outside the handle's %zu streams", i, h->s.size());
     const LatentStream &S = h->s[i];
@@ -1178,8 +1187,8 @@ extern "C" int ccmi_latents_values(const ccmi_latents *h, int i, int32_t *out_de
     size_t off = 0;
     for (int l = 0; l < f.n_layers; ++l) {
         const DecWindow w{0, f.lh[l], 0, f.lw[l]};
-        jobs[l] = DecLatUnpackJob{f.lat_n[l] ? h->store + S.grid_off[l] : nullptr, out_dev + off, f.lw[l], 0, w.y1, 0, w.x1,
-                                  blocks, 0, 0};
+        jobs[l] = DecLatUnpackJob{f.lat_n[l] ? S.base + S.grid_off[l] : nullptr, out_dev + off, f.lw[l], 0, w.y1, 0, w.x1,
+                                  blocks, 0, f.lh[l]};
         blocks += dec_lat_unpack_blocks(w);
         off += (size_t)f.lh[l] * f.lw[l];
     }
@@ -1192,7 +1201,7 @@ extern "C" int ccmi_latents_values(const ccmi_latents *h, int i, int32_t *out_de
         ~Free() { (void)hipFree(p); }
     } guard{tab};
     CCMI_HIP_CHECK(hipMemcpyAsync(tab, jobs, sizeof(DecLatUnpackJob) * f.n_layers, hipMemcpyHostToDevice, s));
-    if (int rc = launch_dec_lat_unpack(static_cast<const DecLatUnpackJob *>(tab), f.n_layers, blocks, h->type, s)) return rc;
+    if (int rc = launch_dec_lat_unpack(static_cast<const DecLatUnpackJob *>(tab), f.n_layers, blocks, S.type, s)) return rc;
     CCMI_HIP_CHECK(hipStreamSynchronize(s));
     return CCMI_OK;
 }
@@ -1230,7 +1239,7 @@ extern "C" int ccmi_latents_render(const ccmi_latents *h, const int *index, int 
     clear_last();
     DecodeRequest rq;
     if (int rc = latents_request(h, index, m, roi, out_bitdepth, out_chroma, sample_type, rq)) return rc;
-    if (!h->store)
+    if (!h->resident)
         return ccmi_set_error(CCMI_ERR_ARG, "render: the handle is plan-only (built without a store): no frame 0 to render");
     if (!out_dev || !out_caps) return ccmi_set_error(CCMI_ERR_ARG, "latents_render: null argument");
     rq.dev = out_dev;
@@ -1262,7 +1271,7 @@ extern "C" int ccmi_latents_render_fmt(const ccmi_latents *h, const int *index, 
     clear_last();
     DecodeRequest rq;
     if (int rc = latents_request(h, index, m, roi, out_bitdepth, out_chroma, CCMI_SAMPLE_F32, rq)) return rc;
-    if (!h->store)
+    if (!h->resident)
         return ccmi_set_error(CCMI_ERR_ARG, "render: the handle is plan-only (built without a store): no frame 0 to render");
     if (!out_dev || !out_caps || !fmt) return ccmi_set_error(CCMI_ERR_ARG, "latents_render_fmt: null argument");
     rq.fmt = fmt;
@@ -1345,7 +1354,7 @@ extern "C" int ccmi_latents_render_rs(const ccmi_latents *h, const int *index, i
     clear_last();
     DecodeRequest rq;
     if (int rc = latents_request(h, index, m, roi, out_bitdepth, out_chroma, CCMI_SAMPLE_F32, rq)) return rc;
-    if (!h->store)
+    if (!h->resident)
         return ccmi_set_error(CCMI_ERR_ARG, "render: the handle is plan-only (built without a store): no frame 0 to render");
     if (!out_dev || !out_caps || !fmt) return ccmi_set_error(CCMI_ERR_ARG, "latents_render_rs: null argument");
     rq.fmt = fmt;

@@ -221,13 +221,43 @@ struct DecLatUnpackJob {
     int y0, y1, x0, x1;   // the rectangle to write
     uint32_t first_block;
     int shift;            // kArmPrec for the tail's planes; 0: the values themselves
-    int pad_;
+    int h;                // the plane's rows (CCMI_LATENT_SEG: the payload follows the h * nseg descriptors)
 };
-size_t dec_lat_elem_bytes(int type); // 0: not a CCMI_LATENT_* type
+size_t dec_lat_elem_bytes(int type); // 0: not one of CCMI_LATENT_I8 / I16 / I32
 uint32_t dec_lat_pack_blocks(uint32_t n, int type);
 uint32_t dec_lat_unpack_blocks(const DecWindow &r);
 // jobs: device table of n_jobs entries whose first_block counts from 0; n_blocks = their total
 int launch_dec_lat_pack(const DecLatPackJob *jobs, int n_jobs, uint32_t n_blocks, int type, hipStream_t s);
+// type CCMI_LATENT_SEG: dec_lat_unpack_seg, src = the grid's descriptor table
 int launch_dec_lat_unpack(const DecLatUnpackJob *jobs, int n_jobs, uint32_t n_blocks, int type, hipStream_t s);
+
+// Segmented form (CCMI_LATENT_SEG, the contract in ccmi.h): a grid is rows of segments of
+// kSegLen values, each at the narrowest of six widths; a descriptor table, then the payload.
+// Compaction of a built store runs three table-driven kernels, one job per non-empty grid, one
+// wave per segment: the width pass writes the segment's code to the job's words of the
+// workspace, the scan (one block per grid) turns them into descriptors in place and writes the
+// grid's payload words to totals[job], the pack writes descriptors and payload to the new store.
+constexpr int kSegLen = 64;
+constexpr uint32_t kSegOffMax = (1u << 29) - 1;   // a descriptor's word offset has 29 bits
+constexpr uint32_t kSegTotalBad = 0xFFFFFFFFu;    // totals[job]: a segment's offset does not fit
+struct DecLatSegJob {
+    const void *src;      // the source grid's values (elem bytes each), whole plane, pitch w
+    uint32_t *desc;       // workspace, h * nseg words: width codes, then descriptors
+    uint32_t *desc_out;   // pack: the new store's descriptor table
+    uint32_t *payload;    // pack: the new store's payload words
+    int w, h, nseg;
+    int elem;             // 1, 2 or 4 bytes per source value
+    uint32_t first_seg;   // of the launch's segments, this grid's first
+    uint32_t pad_;
+};
+inline uint32_t dec_lat_seg_per_row(int w) { return (uint32_t)((w + kSegLen - 1) / kSegLen); }
+inline size_t dec_lat_seg_table_bytes(int h, int w) // the descriptor table, 16-byte aligned
+{
+    return ((size_t)h * dec_lat_seg_per_row(w) * 4 + 15) & ~(size_t)15;
+}
+// jobs: device table ordered by first_seg, n_segs = their total
+int launch_dec_lat_seg_width(const DecLatSegJob *jobs, int n_jobs, uint32_t n_segs, hipStream_t s);
+int launch_dec_lat_seg_scan(const DecLatSegJob *jobs, int n_jobs, uint32_t *totals, hipStream_t s);
+int launch_dec_lat_seg_pack(const DecLatSegJob *jobs, int n_jobs, uint32_t n_segs, hipStream_t s);
 
 } // namespace ccmi

@@ -1,4 +1,4 @@
-// dec_latents.hip -- path B: the latent store's two kernels (gfx950).
+// dec_latents.hip -- path B: the latent store's kernels (gfx950).
 //
 // dec_lat_pack<T>: the ARM + CABAC stage's output planes (int32, value << kArmPrec) -> the
 // store's T values (int8 / int16 / int32), one launch per chunk of a build.  A latent that does
@@ -12,6 +12,11 @@
 // Both are memory-bound copies driven by a job table in device memory (DecLatPackJob /
 // DecLatUnpackJob): a job owns a whole number of blocks, a block finds its job by a binary
 // search over the jobs' first blocks (uniform per block: scalar loads).
+//
+// The segmented form (CCMI_LATENT_SEG, the contract in ccmi.h) is made from a built store by
+// dec_lat_seg_width / dec_lat_seg_scan / dec_lat_seg_pack (DecLatSegJob, one wave per segment of
+// 64 values, a wave finds its job by the same search over the jobs' first segments) and read by
+// dec_lat_unpack_seg, which takes dec_lat_unpack's jobs and writes the same rectangle.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -108,6 +113,179 @@ __global__ __launch_bounds__(kThreads) void dec_lat_unpack(const DecLatUnpackJob
     }
 }
 
+// ---- the segmented form ----
+constexpr int kSegWaves = kThreads / kSegLen;
+constexpr int kScanPerThread = 4;
+
+// a wave's segment: its job, its place in the grid, its values
+struct SegAt {
+    uint32_t q;  // the segment's index in its grid, row-major
+    int c;       // its values: kSegLen, fewer for a row's last segment
+    int32_t v;   // this lane's value; 0 for lanes >= c
+};
+
+__device__ __forceinline__ int seg_values(int w, uint32_t s) { return min(kSegLen, w - kSegLen * (int)s); }
+// words of a segment of c values at width code k (0, 2, 4, 8, 16, 32 bits)
+__device__ __forceinline__ uint32_t seg_words(uint32_t k, int c) { return k ? (((uint32_t)c << k) + 31u) >> 5 : 0u; }
+
+__device__ __forceinline__ DecLatSegJob seg_job(const DecLatSegJob *__restrict__ jobs, int n_jobs, uint32_t seg)
+{
+    int lo = 0, hi = n_jobs - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (jobs[mid].first_seg <= seg) lo = mid;
+        else hi = mid - 1;
+    }
+    return jobs[lo];
+}
+
+__device__ __forceinline__ SegAt seg_load(const DecLatSegJob &J, uint32_t seg, int lane)
+{
+    SegAt a;
+    a.q = seg - J.first_seg;
+    const uint32_t r = a.q / (uint32_t)J.nseg, s = a.q - r * (uint32_t)J.nseg;
+    a.c = seg_values(J.w, s);
+    a.v = 0;
+    if (lane < a.c) {
+        const size_t at = (size_t)r * J.w + (size_t)s * kSegLen + lane;
+        a.v = J.elem == 1   ? (int32_t) static_cast<const int8_t *>(J.src)[at]
+              : J.elem == 2 ? (int32_t) static_cast<const int16_t *>(J.src)[at]
+                            : static_cast<const int32_t *>(J.src)[at];
+    }
+    return a;
+}
+
+// Width pass: the smallest code whose range holds every value of the segment.  The five range
+// tests are nested, so the number of non-empty ballots is the code: no reduction.
+__global__ __launch_bounds__(kThreads) void dec_lat_seg_width(const DecLatSegJob *__restrict__ jobs, int n_jobs,
+                                                              uint32_t n_segs)
+{
+    const uint32_t seg = blockIdx.x * kSegWaves + (threadIdx.x >> 6);
+    if (seg >= n_segs) return; // the whole wave
+    const int lane = threadIdx.x & 63;
+    const DecLatSegJob J = seg_job(jobs, n_jobs, seg);
+    const SegAt a = seg_load(J, seg, lane);
+    const int32_t v = a.v;
+    const uint32_t k = (__ballot(v != 0) != 0ull) + (__ballot(v < -2 || v > 1) != 0ull) +
+                       (__ballot(v < -8 || v > 7) != 0ull) + (__ballot(v < -128 || v > 127) != 0ull) +
+                       (__ballot(v < -32768 || v > 32767) != 0ull);
+    if (lane == 0) J.desc[a.q] = k;
+}
+
+// Scan: one block per grid.  Exclusive scan of the segments' word counts in (r, s) order, a
+// thread on kScanPerThread consecutive segments, the block looping over the grid with a carry;
+// the codes become descriptors in place.
+__global__ __launch_bounds__(kThreads) void dec_lat_seg_scan(const DecLatSegJob *__restrict__ jobs,
+                                                             uint32_t *__restrict__ totals)
+{
+    __shared__ uint32_t wave_sum[kSegWaves];
+    const DecLatSegJob J = jobs[blockIdx.x];
+    const uint32_t n = (uint32_t)J.h * (uint32_t)J.nseg;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint64_t carry = 0;
+    int over = 0;
+    for (uint32_t base = 0; base < n; base += kThreads * kScanPerThread) {
+        const uint32_t i0 = base + threadIdx.x * kScanPerThread;
+        uint32_t k[kScanPerThread], wd[kScanPerThread], sum = 0;
+#pragma unroll
+        for (int t = 0; t < kScanPerThread; ++t) {
+            const uint32_t i = i0 + t;
+            k[t] = 0;
+            wd[t] = 0;
+            if (i < n) {
+                k[t] = J.desc[i];
+                wd[t] = seg_words(k[t], seg_values(J.w, i % (uint32_t)J.nseg));
+            }
+            sum += wd[t];
+        }
+        uint32_t inc = sum; // inclusive over the wave
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t up = __shfl_up(inc, d);
+            if (lane >= d) inc += up;
+        }
+        if (lane == 63) wave_sum[wave] = inc;
+        __syncthreads();
+        uint32_t before = 0, all = 0;
+#pragma unroll
+        for (int wv = 0; wv < kSegWaves; ++wv) {
+            const uint32_t ws = wave_sum[wv];
+            before += wv < wave ? ws : 0u;
+            all += ws;
+        }
+        __syncthreads(); // wave_sum is rewritten by the next round
+        uint64_t off = carry + before + (inc - sum);
+#pragma unroll
+        for (int t = 0; t < kScanPerThread; ++t) {
+            const uint32_t i = i0 + t;
+            if (i < n) {
+                over |= off > (uint64_t)kSegOffMax;
+                J.desc[i] = ((uint32_t)off << 3) | k[t];
+                off += wd[t];
+            }
+        }
+        carry += all;
+    }
+    over = __syncthreads_or(over);
+    if (threadIdx.x == 0) totals[blockIdx.x] = over || carry >= (uint64_t)kSegTotalBad ? kSegTotalBad : (uint32_t)carry;
+}
+
+// Pack: lane j's field goes to bit (j b) % 32 of word (j b) / 32; the 32 / b lanes of a word are
+// OR-combined by an xor butterfly and the first of them stores it: 2 b consecutive words per
+// full segment.  Lanes past the segment's values carry 0, so the last word's trailing bits are 0.
+__global__ __launch_bounds__(kThreads) void dec_lat_seg_pack(const DecLatSegJob *__restrict__ jobs, int n_jobs,
+                                                             uint32_t n_segs)
+{
+    const uint32_t seg = blockIdx.x * kSegWaves + (threadIdx.x >> 6);
+    if (seg >= n_segs) return; // the whole wave
+    const int lane = threadIdx.x & 63;
+    const DecLatSegJob J = seg_job(jobs, n_jobs, seg);
+    const SegAt a = seg_load(J, seg, lane);
+    const uint32_t d = J.desc[a.q], k = d & 7u, off = d >> 3;
+    if (lane == 0) J.desc_out[a.q] = d;
+    if (k == 0) return; // wave-uniform: an all-zero segment has no words
+    const int per_word = 32 >> k; // lanes per word: 16, 8, 4, 2, 1
+    uint32_t x = (uint32_t)a.v;
+    if (k < 5) x = (x & ((1u << (1u << k)) - 1u)) << (((uint32_t)lane << k) & 31u);
+#pragma unroll
+    for (int m = 1; m < 16; m <<= 1)
+        if (m < per_word) x |= (uint32_t)__shfl_xor((int)x, m); // per_word is wave-uniform
+    const uint32_t word = (uint32_t)lane >> (5 - k);
+    if ((lane & (per_word - 1)) == 0 && word < seg_words(k, a.c)) J.payload[off + word] = x;
+}
+
+// dec_lat_unpack for the segmented form: the same jobs (src = the grid's descriptor table, the
+// payload behind it), the same rectangle, the same 4 samples per thread.  A field never crosses
+// a word (every width divides 32): one descriptor load, one word load, a signed extract.
+__global__ __launch_bounds__(kThreads) void dec_lat_unpack_seg(const DecLatUnpackJob *__restrict__ jobs, int n_jobs)
+{
+    const DecLatUnpackJob J = jobs[find_job(jobs, n_jobs, blockIdx.x)];
+    const uint32_t rw = (uint32_t)(J.x1 - J.x0);
+    const uint64_t total = (uint64_t)(uint32_t)(J.y1 - J.y0) * rw;
+    const uint64_t base = (uint64_t)(blockIdx.x - J.first_block) * (kThreads * kUnpackPerThread);
+    const uint32_t nseg = ((uint32_t)J.w + kSegLen - 1) / kSegLen;
+    const uint32_t *desc = static_cast<const uint32_t *>(J.src);
+    const uint32_t *payload = desc + (((size_t)J.h * nseg + 3) & ~(size_t)3);
+#pragma unroll
+    for (int t = 0; t < kUnpackPerThread; ++t) {
+        const uint64_t i = base + (uint64_t)t * kThreads + threadIdx.x;
+        if (i < total) {
+            const uint32_t r = (uint32_t)(i / rw), c = (uint32_t)(i - (uint64_t)r * rw);
+            const uint32_t y = (uint32_t)J.y0 + r, x = (uint32_t)J.x0 + c;
+            int32_t v = 0;
+            if (desc) {
+                const uint32_t d = desc[(size_t)y * nseg + (x >> 6)], k = d & 7u;
+                if (k) {
+                    const uint32_t b = 1u << k, bit = (x & 63u) << k;
+                    const uint32_t word = payload[(size_t)(d >> 3) + (bit >> 5)];
+                    v = (int32_t)(word << (32u - b - (bit & 31u))) >> (32u - b);
+                }
+            }
+            J.dst[(int64_t)y * J.w + x] = (int32_t)((uint32_t)v << J.shift);
+        }
+    }
+}
+
 template <typename Launch>
 int with_latent_type(int type, Launch &&launch)
 {
@@ -152,10 +330,41 @@ int launch_dec_lat_pack(const DecLatPackJob *jobs, int n_jobs, uint32_t n_blocks
 int launch_dec_lat_unpack(const DecLatUnpackJob *jobs, int n_jobs, uint32_t n_blocks, int type, hipStream_t s)
 {
     if (n_jobs < 1 || n_blocks < 1) return CCMI_OK;
+    if (type == CCMI_LATENT_SEG) {
+        hipLaunchKernelGGL(dec_lat_unpack_seg, dim3(n_blocks), dim3(kThreads), 0, s, jobs, n_jobs);
+        CCMI_HIP_CHECK(hipGetLastError());
+        return CCMI_OK;
+    }
     if (int rc = with_latent_type(type, [&](auto t) {
             hipLaunchKernelGGL(dec_lat_unpack<decltype(t)>, dim3(n_blocks), dim3(kThreads), 0, s, jobs, n_jobs);
         }))
         return rc;
+    CCMI_HIP_CHECK(hipGetLastError());
+    return CCMI_OK;
+}
+
+int launch_dec_lat_seg_width(const DecLatSegJob *jobs, int n_jobs, uint32_t n_segs, hipStream_t s)
+{
+    if (n_jobs < 1 || n_segs < 1) return CCMI_OK;
+    hipLaunchKernelGGL(dec_lat_seg_width, dim3((n_segs + kSegWaves - 1) / kSegWaves), dim3(kThreads), 0, s, jobs, n_jobs,
+                       n_segs);
+    CCMI_HIP_CHECK(hipGetLastError());
+    return CCMI_OK;
+}
+
+int launch_dec_lat_seg_scan(const DecLatSegJob *jobs, int n_jobs, uint32_t *totals, hipStream_t s)
+{
+    if (n_jobs < 1) return CCMI_OK;
+    hipLaunchKernelGGL(dec_lat_seg_scan, dim3(n_jobs), dim3(kThreads), 0, s, jobs, totals);
+    CCMI_HIP_CHECK(hipGetLastError());
+    return CCMI_OK;
+}
+
+int launch_dec_lat_seg_pack(const DecLatSegJob *jobs, int n_jobs, uint32_t n_segs, hipStream_t s)
+{
+    if (n_jobs < 1 || n_segs < 1) return CCMI_OK;
+    hipLaunchKernelGGL(dec_lat_seg_pack, dim3((n_segs + kSegWaves - 1) / kSegWaves), dim3(kThreads), 0, s, jobs, n_jobs,
+                       n_segs);
     CCMI_HIP_CHECK(hipGetLastError());
     return CCMI_OK;
 }

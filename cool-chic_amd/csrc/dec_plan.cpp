@@ -361,14 +361,18 @@ int decode_plan(const DecodeRequest &rq, DecodePlan &pl)
 
 int latent_store_layout(const DecodePlan &pl, int type, ccmi_latents &h)
 {
+    if (type == CCMI_LATENT_SEG)
+        return ccmi_set_error(CCMI_ERR_ARG,
+                              "latents: a CCMI_LATENT_SEG store has a data-dependent size and is not built from streams: "
+                              "build an I8 / I16 / I32 store, then ccmi_latents_compact_measure / ccmi_latents_compact");
     const size_t eb = dec_lat_elem_bytes(type);
     if (!eb) return ccmi_set_error(CCMI_ERR_ARG, "latents: unknown element type %d", type);
-    h.type = type;
     h.s.resize(pl.fr.size());
     size_t pos = 0;
     for (size_t i = 0; i < pl.fr.size(); ++i) {
         const FrameHost &f = pl.fr[i].f;
         LatentStream &S = h.s[i];
+        S.type = type;
         S.off = pos;
         S.ups_off = pos;
         pos += align_up(f.ups.size() * 4, 16);

@@ -7,23 +7,28 @@
 
 namespace ccmi {
 
-// One stream of a latent store (ccmi_latents): what a render needs of it on the host, and
-// where its parts sit in the device store (bytes from the store's base).
+// One stream of a latent store (ccmi_latents): what a render needs of it on the host, the form
+// of its latents, and where its parts sit in its device store (bytes from `base`: a handle made
+// by ccmi_latents_concat spans several stores).
 struct LatentStream {
     FrameHost f;  // header facts and decoded networks; refers to no coded bytes (pointers cleared, ARM dropped)
     int f24 = 0;  // DecSynArgs::f24, computed once at the build
+    int type = 0; // CCMI_LATENT_*
+    const uint8_t *base = nullptr; // device: the store this stream sits in; NULL: plan-only
     size_t off = 0, bytes = 0; // the stream's part of the store, 256-byte aligned and rounded
     size_t ups_off = 0, syn_off = 0;
-    size_t grid_off[CCMI_MAX_GRIDS] = {}; // an empty grid (lat_n == 0) takes no bytes
+    // an empty grid (lat_n == 0) takes no bytes; CCMI_LATENT_SEG: the descriptor table, the payload
+    // dec_lat_seg_table_bytes() behind it
+    size_t grid_off[CCMI_MAX_GRIDS] = {};
 };
 
 } // namespace ccmi
 
-// The opaque handle of ccmi.h: immutable once built.
+// The opaque handle of ccmi.h: immutable once built.  Type and store are per stream; every
+// stream of a handle is resident, or none is (plan-only).
 struct ccmi_latents {
-    int type = 0;                 // CCMI_LATENT_*
-    const uint8_t *store = nullptr; // device; NULL: plan-only
-    size_t store_bytes = 0;
+    bool resident = false;
+    size_t store_bytes = 0; // the sum of the streams' bytes
     std::vector<ccmi::LatentStream> s;
 };
 
@@ -78,7 +83,7 @@ struct DecodeRequest {
     ccmi_frame_geom *geom = nullptr; // [n], optional (device sinks): filled by the plan
     ccmi_roi_info *info = nullptr;   // [n], optional (device sinks): what the region decode does
     int32_t *const *lat_out = nullptr; // [n], optional: the decoded latents, to the host
-    // latent-store sink: the layout is filled by the plan; lat_store->store NULL: planning only
+    // latent-store sink: the layout is filled by the plan; !lat_store->resident: planning only
     ccmi_latents *lat_store = nullptr;
     // latent-store source
     const ccmi_latents *src = nullptr;
@@ -130,7 +135,7 @@ struct DecodePlan {
 int decode_plan(const DecodeRequest &rq, DecodePlan &pl);
 
 // Layout of a latent store for the planned frames' streams at element type `type` (the
-// contract in ccmi.h): fills h.type, h.s[i].off / bytes / ups_off / syn_off / grid_off and
+// contract in ccmi.h): fills h.s[i].type / off / bytes / ups_off / syn_off / grid_off and
 // h.store_bytes (h.s sized here, the FrameHosts left alone).  Host arithmetic.
 int latent_store_layout(const DecodePlan &pl, int type, ccmi_latents &h);
 

@@ -383,7 +383,7 @@ int ccmi_decode_batch_dev_roi(const uint8_t *const *streams, const size_t *lens,
  * (ccmi_decode_last_arm_flags: *n = 0), and ccmi_decode_last_timing() after a render reports
  * [0] the table upload, [1] the unpack of the store into the tail's planes, [2] the tail, [3] 0. */
 typedef struct ccmi_latents ccmi_latents;
-enum { CCMI_LATENT_I8 = 0, CCMI_LATENT_I16 = 1, CCMI_LATENT_I32 = 2 };
+enum { CCMI_LATENT_I8 = 0, CCMI_LATENT_I16 = 1, CCMI_LATENT_I32 = 2, CCMI_LATENT_SEG = 3 /* by compaction only */ };
 int ccmi_latents_plan(const uint8_t *const *streams, const size_t *lens, int n, int latent_type,
                       size_t *store_bytes, size_t *store_bytes_each /* [n] or NULL */, size_t *workspace_bytes);
 int ccmi_latents_decode(const uint8_t *const *streams, const size_t *lens, int n, int latent_type,
@@ -400,6 +400,64 @@ int ccmi_latents_render(const ccmi_latents *h, const int *index /* [m] or NULL *
                         const ccmi_rect *roi /* [m] or NULL */, void *const *out_dev, const size_t *out_caps,
                         int sample_type, int out_bitdepth, int out_chroma, void *workspace,
                         size_t workspace_bytes, void *stream);
+
+/* Compact stores and one handle over many stores.
+ *
+ * CCMI_LATENT_SEG: per-segment bit widths.  A stream's part of the store is laid out as for the
+ * other types (256-byte aligned; upsampling integers, synthesis integers, then the grids; every
+ * part 16-byte aligned; the size rounded up to 256; an empty grid takes no bytes and renders as
+ * zeros); only the form of a non-empty grid l (h_l x w_l) differs: a descriptor table, then a
+ * payload, each 16-byte aligned.
+ *   Segments: nseg = ceil(w_l / 64); segment (r, s) covers columns [64 s, min(64 s + 64, w_l)) of
+ *   row r: c values.
+ *   Width code k in 0..5 stands for b = 0, 2, 4, 8, 16, 32 bits; a segment's k is the smallest
+ *   code with every value in [-2^(b-1), 2^(b-1) - 1]; b = 0: every value is 0.
+ *   Payload: segment (r, s) takes ceil(c b / 32) 32-bit words; segments follow each other in
+ *   (r, s) row-major order without gaps, off(r, s) = the words before it.  Value j is the two's-
+ *   complement field at bits [j b, (j + 1) b) of the segment's words read as one little-endian bit
+ *   string (bit t is bit t % 32 of word t / 32); the last word's trailing bits are 0.
+ *   Descriptors: desc[r nseg + s] = (off << 3) | k, uint32, h_l nseg of them.  off must fit 29
+ *   bits: a grid where it does not is CCMI_ERR_UNSUPPORTED naming stream and grid.
+ * The form is a function of the latents alone: compactions of the same streams from I8, I16 and
+ * I32 stores give the same descriptor tables and payloads, byte for byte.
+ *
+ * A SEG store has a data-dependent size, so it is not built from coded streams
+ * (ccmi_latents_plan / ccmi_latents_decode with CCMI_LATENT_SEG: CCMI_ERR_ARG) but from a built
+ * I8 / I16 / I32 handle, which may be freed afterwards with its store:
+ * ccmi_latents_compact_plan(): host arithmetic, works on a plan-only handle too: the size of the
+ *   compact store if every segment took 32 bits, and the workspace of the two calls below.
+ * ccmi_latents_compact_measure(): the width pass and the offset scan on the GPU; the exact store
+ *   size and (optional) the per-stream sizes, 256-byte multiples whose sum it is.
+ * ccmi_latents_compact(): stateless (derives the widths again), writes the store (device, 256-byte
+ *   aligned) and creates the handle.  store_bytes below the exact size: CCMI_ERR_ARG naming the
+ *   size needed, nothing written to `store`, no handle.
+ * workspace NULL: allocated for the call.  The new handle never refers to src, its store or the
+ * workspace.  Both GPU calls synchronise `stream` before they return.  A NULL src, a plan-only src
+ * where the GPU is needed, and a src with a CCMI_LATENT_SEG stream are CCMI_ERR_ARG before any
+ * HIP call.
+ *
+ * ccmi_latents_concat(): host only.  The new handle's streams are those of parts[0], then
+ * parts[1], ..., each with its own type (I8 / I16 / I32 / SEG may mix) and its own device
+ * location.  The parts may be freed afterwards; their store memory stays the caller's and must
+ * outlive the new handle's last render.  Plan-only parts give a plan-only handle; mixing plan-only
+ * and resident parts, n_parts < 1, a NULL entry and more than INT_MAX streams are CCMI_ERR_ARG.
+ * Every ccmi_latents_render* call, its plan and ccmi_latents_values take such a handle: frames
+ * are planned and grouped exactly as if the streams sat in one store
+ * (ccmi_decode_last_tail_groups reports the same counts), the run launches one unpack per
+ * storage type present, and render plans and workspaces do not depend on the storage type.
+ * ccmi_latents_stream_info(): stream i's CCMI_LATENT_* type and its bytes in its store (either
+ * pointer may be NULL).
+ * Measured (profiles/decode_compact_ab.txt): 274 kB per 720p stream against 2.21 MB at int16, 934 kB
+ * per 1080p stream against 5.53 MB; 960 class-E streams measure in 12.5 ms and compact in 25 ms;
+ * the 256 x 256 render_model call takes 11.0-11.2 ms from the int16 store, its compaction and a
+ * concat of 8 compacted chunks alike (the unpack 0.28-0.29 ms against 0.27 ms). */
+int ccmi_latents_compact_plan(const ccmi_latents *src, size_t *store_bytes_max, size_t *workspace_bytes);
+int ccmi_latents_compact_measure(const ccmi_latents *src, void *workspace, size_t workspace_bytes, void *stream,
+                                 size_t *store_bytes, size_t *store_bytes_each /* [count] or NULL */);
+int ccmi_latents_compact(const ccmi_latents *src, void *store, size_t store_bytes, void *workspace,
+                         size_t workspace_bytes, void *stream, ccmi_latents **out);
+int ccmi_latents_concat(const ccmi_latents *const *parts, int n_parts, ccmi_latents **out);
+int ccmi_latents_stream_info(const ccmi_latents *h, int i, int *latent_type, size_t *store_bytes);
 
 /* Formatted output: the same decode (coded streams, or a latent store) written as the tensor a
  * model or a display takes -- three full-size channels, optionally RGB, normalised, fp16 / bf16,
