@@ -20,25 +20,62 @@ class SynI32Args(C.Structure):
                 ("workspace", C.c_void_p), ("workspace_bytes", C.c_size_t)]
 
 
+_P, _I, _Z = C.c_void_p, C.c_int, C.c_size_t
+# every decoder prototype this module calls: name -> argument types (the result is an int but for _RESTYPES)
+_PROTOS = {
+    "ccmi_decode_weights_i32": [_P, _Z, _P, _Z, _P, _Z, _P, _Z, _P],
+    "ccmi_ups_workspace_bytes_i32": [_I, _P, _P],
+    "ccmi_ups_forward_i32": [C.POINTER(UpsI32Args), _P],
+    "ccmi_syn_workspace_bytes_i32": [C.POINTER(SynI32Args)],
+    "ccmi_syn_forward_i32": [C.POINTER(SynI32Args), _P],
+    "ccmi_decode_latents": [_P, _Z, _P, _Z, _P],
+    "ccmi_decode_batch_workspace_bytes": [_P, _P, _I, _I, _I, _I, _P],
+    "ccmi_decode_batch_ws": [_P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _Z, _P],
+    "ccmi_decode_batch_plan": [_P, _P, _I, _I, _I, _I, _P, _P],
+    "ccmi_decode_batch_dev_plan": [_P, _P, _I, _I, _I, _I, _P, _P],
+    "ccmi_decode_batch_dev": [_P, _P, _I, _P, _P, _I, _I, _I, _P, _Z, _P],
+    "ccmi_decode_batch_dev_roi_plan": [_P, _P, _I, _P, _I, _I, _I, _P, _P, _P],
+    "ccmi_decode_batch_dev_roi": [_P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _Z, _P],
+    "ccmi_decode_batch_dev_fmt_plan": [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P],
+    "ccmi_decode_batch_dev_fmt": [_P, _P, _I, _P, _P, _P, _P, _I, _I, _P, _Z, _P],
+    "ccmi_decode_batch_dev_rs_plan": [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P],
+    "ccmi_decode_batch_dev_rs": [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _P, _Z, _P],
+    "ccmi_decode_last_tail_groups": [_P, _P],
+    "ccmi_latents_plan": [_P, _P, _I, _I, _P, _P, _P],
+    "ccmi_latents_decode": [_P, _P, _I, _I, _P, _Z, _P, _Z, _P, _P],
+    "ccmi_latents_free": [_P],
+    "ccmi_latents_count": [_P],
+    "ccmi_latents_values": [_P, _I, _P, _Z, _P],
+    "ccmi_latents_render_plan": [_P, _P, _I, _P, _I, _I, _I, _P, _P, _P],
+    "ccmi_latents_render": [_P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _Z, _P],
+    "ccmi_latents_render_fmt_plan": [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P],
+    "ccmi_latents_render_fmt": [_P, _P, _I, _P, _P, _P, _P, _I, _I, _P, _Z, _P],
+    "ccmi_latents_render_rs_plan": [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P],
+    "ccmi_latents_render_rs": [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _P, _Z, _P],
+    "ccmi_latents_compact_plan": [_P, _P, _P],
+    "ccmi_latents_compact_measure": [_P, _P, _Z, _P, _P, _P],
+    "ccmi_latents_compact": [_P, _P, _Z, _P, _Z, _P, _P],
+    "ccmi_latents_concat": [_P, _I, _P],
+    "ccmi_latents_stream_info": [_P, _I, _P, _P],
+}
+_RESTYPES = {"ccmi_ups_workspace_bytes_i32": _Z, "ccmi_syn_workspace_bytes_i32": _Z, "ccmi_latents_free": None}
+
+
 def _bind():
+    """The library with every prototype of _PROTOS declared that it has: older builds, loaded
+    for A/B runs, lack the newer entry points."""
     L = lib()
     if not getattr(L, "_ccmi_dec_bound", False):
-        L.ccmi_decode_weights_i32.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t,
-                                              C.c_void_p, C.c_size_t, C.c_void_p]
-        L.ccmi_ups_workspace_bytes_i32.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
-        L.ccmi_ups_workspace_bytes_i32.restype = C.c_size_t
-        L.ccmi_ups_forward_i32.argtypes = [C.POINTER(UpsI32Args), C.c_void_p]
-        L.ccmi_syn_workspace_bytes_i32.argtypes = [C.POINTER(SynI32Args)]
-        L.ccmi_syn_workspace_bytes_i32.restype = C.c_size_t
-        L.ccmi_syn_forward_i32.argtypes = [C.POINTER(SynI32Args), C.c_void_p]
-        L.ccmi_decode_batch_workspace_bytes.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                        C.c_void_p]
-        L.ccmi_decode_batch_ws.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int,
-                                           C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.ccmi_decode_batch_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
-                                             C.c_void_p]
+        for name, argtypes in _PROTOS.items():
+            if hasattr(L, name):
+                f = getattr(L, name)
+                f.argtypes, f.restype = argtypes, _RESTYPES.get(name, C.c_int)
         L._ccmi_dec_bound = True
     return L
+
+
+# the names the tests reach the bound library by, from when each sink had a binder of its own
+_bind_dev = _bind_latents = _bind_fmt = _bind_rs = _bind
 
 
 def decode_file(inp: str, out: str = "", output_bitdepth: int = 0, output_chroma_format: int = 0,
@@ -80,6 +117,29 @@ class _PinnedPool:
 _POOL = _PinnedPool()
 
 
+def _marshal(streams, who="decode_batch_tensors"):
+    """(what keeps them alive, pointer array, length array) of the streams; who names the caller
+    that refuses an empty list itself (None: the library does)."""
+    n = len(streams)
+    if n < 1 and who:
+        raise ValueError(f"{who}: no streams")
+    bufs = [C.create_string_buffer(s, len(s)) for s in streams]
+    sp = (C.c_void_p * n)(*[C.cast(b, C.c_void_p) for b in bufs])
+    ln = (C.c_size_t * n)(*[len(s) for s in streams])
+    return bufs, sp, ln
+
+
+def _stream_ws(dev, stream_handle, workspace, need):
+    """The caller's stream and workspace, or the defaults: torch's current stream of dev and
+    `need` bytes from its caching allocator."""
+    import torch
+    if stream_handle is None:
+        stream_handle = torch.cuda.current_stream(dev).cuda_stream
+    if workspace is None:
+        workspace = torch.empty(max(int(need), 256), dtype=torch.uint8, device=dev)
+    return stream_handle, workspace
+
+
 def decode_batch(streams: Sequence[bytes], output_bitdepth: int = 0, output_chroma_format: int = 0,
                  as_yuv: bool = True, stream_handle: int | None = None, workspace=None, views: bool = False) -> list:
     """Decode independent intra .cool streams in one batched launch sequence; returns the
@@ -93,11 +153,7 @@ def decode_batch(streams: Sequence[bytes], output_bitdepth: int = 0, output_chro
     valid until the next call on this thread), otherwise bytes."""
     import torch
     n = len(streams)
-    if n < 1:
-        raise ValueError("decode_batch: no streams")
-    bufs = [C.create_string_buffer(s, len(s)) for s in streams]
-    sp = (C.c_void_p * n)(*[C.cast(b, C.c_void_p) for b in bufs])
-    ln = (C.c_size_t * n)(*[len(s) for s in streams])
+    keep, sp, ln = _marshal(streams, "decode_batch")
     cap = (C.c_size_t * n)()
     need = C.c_size_t(0)
     L = _bind()
@@ -110,11 +166,8 @@ def decode_batch(streams: Sequence[bytes], output_bitdepth: int = 0, output_chro
     base = pool.data_ptr()
     op = (C.c_void_p * n)(*[base + o for o in offs])
     got = (C.c_size_t * n)()
-    dev = torch.device("cuda", torch.cuda.current_device())
-    if stream_handle is None:
-        stream_handle = torch.cuda.current_stream(dev).cuda_stream
-    if workspace is None:
-        workspace = torch.empty(max(int(need.value), 256), dtype=torch.uint8, device=dev)
+    stream_handle, workspace = _stream_ws(torch.device("cuda", torch.cuda.current_device()), stream_handle, workspace,
+                                          need.value)
     check(L.ccmi_decode_batch_ws(sp, ln, n, op, cap, got, output_bitdepth, output_chroma_format, int(as_yuv),
                                  workspace.data_ptr(), workspace.numel(), stream_handle))
     mv = memoryview(pool.numpy())
@@ -125,13 +178,10 @@ def decode_batch(streams: Sequence[bytes], output_bitdepth: int = 0, output_chro
 
 def decode_batch_workspace_bytes(streams: Sequence[bytes], output_bitdepth: int = 0, output_chroma_format: int = 0,
                                  as_yuv: bool = True) -> int:
-    n = len(streams)
-    bufs = [C.create_string_buffer(s, len(s)) for s in streams]
-    sp = (C.c_void_p * n)(*[C.cast(b, C.c_void_p) for b in bufs])
-    ln = (C.c_size_t * n)(*[len(s) for s in streams])
+    keep, sp, ln = _marshal(streams, None)
     out = C.c_size_t(0)
-    check(_bind().ccmi_decode_batch_workspace_bytes(sp, ln, n, output_bitdepth, output_chroma_format, int(as_yuv),
-                                                    C.byref(out)))
+    check(_bind().ccmi_decode_batch_workspace_bytes(sp, ln, len(streams), output_bitdepth, output_chroma_format,
+                                                    int(as_yuv), C.byref(out)))
     return out.value
 
 
@@ -154,84 +204,67 @@ class RoiInfo(C.Structure):
 SAMPLE_U8, SAMPLE_U16, SAMPLE_F32 = 0, 1, 2  # CCMI_SAMPLE_*
 
 
-def _bind_dev():
-    L = _bind()
-    if not getattr(L, "_ccmi_dec_dev_bound", False):
-        L.ccmi_decode_batch_dev_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
-                                                 C.c_void_p, C.c_void_p]
-        L.ccmi_decode_batch_dev_plan.restype = C.c_int
-        L.ccmi_decode_batch_dev.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int,
-                                            C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]
-        L.ccmi_decode_batch_dev.restype = C.c_int
-        if hasattr(L, "ccmi_decode_batch_dev_roi"):  # absent from older builds loaded for A/B runs
-            L.ccmi_decode_batch_dev_roi_plan.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                                         C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-            L.ccmi_decode_batch_dev_roi_plan.restype = C.c_int
-            L.ccmi_decode_batch_dev_roi.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
-                                                    C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_size_t,
-                                                    C.c_void_p]
-            L.ccmi_decode_batch_dev_roi.restype = C.c_int
-        L._ccmi_dec_dev_bound = True
-    return L
-
-
-def _marshal(streams):
-    n = len(streams)
-    if n < 1:
-        raise ValueError("decode_batch_tensors: no streams")
-    bufs = [C.create_string_buffer(s, len(s)) for s in streams]
-    sp = (C.c_void_p * n)(*[C.cast(b, C.c_void_p) for b in bufs])
-    ln = (C.c_size_t * n)(*[len(s) for s in streams])
-    return bufs, sp, ln
-
-
-def _rects(roi, streams, n):
-    """roi argument -> ccmi_rect array, or None for whole frames.  One (x, y, w, h) for every
-    stream, or a sequence with one entry per stream; an entry None is that stream's whole frame
-    (its size read from the stream's GOP header)."""
+def _roi_rects(roi, n, whole, noun):
+    """roi argument -> ccmi_rect array of n entries, or None for whole frames.  One (x, y, w, h)
+    for every stream / frame (the noun), or a sequence with one entry per; an entry None is
+    whole(i), that entry's whole frame."""
     if roi is None:
         return None
     one = len(roi) == 4 and all(isinstance(v, int) for v in roi)
     rois = [tuple(roi)] * n if one else list(roi)
     if len(rois) != n:
-        raise ValueError(f"roi: one (x, y, w, h), or one entry per stream ({n}), got {len(rois)}")
+        raise ValueError(f"roi: one (x, y, w, h), or one entry per {noun} ({n}), got {len(rois)}")
     arr = (Rect * n)()
     for i, r in enumerate(rois):
         if r is None:
-            s = streams[i]
-            if len(s) < 6:
-                raise ValueError(f"stream {i}: truncated GOP header")
-            r = (0, 0, int.from_bytes(s[4:6], "big"), int.from_bytes(s[2:4], "big"))
+            r = whole(i)
         if len(r) != 4:
             raise ValueError(f"roi[{i}]: (x, y, w, h) expected")
         arr[i] = Rect(*[int(v) for v in r])
     return arr
 
 
+def _rects(roi, streams, n):
+    """_roi_rects of streams: a whole frame's size is read from the stream's GOP header."""
+    def whole(i):
+        s = streams[i]
+        if len(s) < 6:
+            raise ValueError(f"stream {i}: truncated GOP header")
+        return 0, 0, int.from_bytes(s[4:6], "big"), int.from_bytes(s[2:4], "big")
+    return _roi_rects(roi, n, whole, "stream")
+
+
+def _pick_sample(plan, geom, dtype, who):
+    """Runs plan(sample type), which fills geom, with the sample type of dtype, and returns the
+    type.  dtype None: planned at U16 first (any bitdepth: learns every output bitdepth), then U8
+    when every output fits it."""
+    import torch
+    if dtype is None:
+        plan(SAMPLE_U16)
+        sample = SAMPLE_U8 if all(g.bitdepth <= 8 for g in geom) else SAMPLE_U16
+    else:
+        table = {torch.uint8: SAMPLE_U8, torch.uint16: SAMPLE_U16, torch.float32: SAMPLE_F32}
+        if dtype not in table:
+            raise ValueError(f"{who}: dtype {dtype} (torch.uint8, torch.uint16, torch.float32 or None)")
+        sample = table[dtype]
+    plan(sample)
+    return sample
+
+
 def _plan_dev(m, output_bitdepth, output_chroma_format, dtype, rects=None, info=None):
     """(sample type, ccmi_frame_geom array, workspace bytes) of marshalled streams."""
-    import torch
     n = len(m[0])
     geom = (FrameGeom * n)()
     need = C.c_size_t(0)
 
     def plan(sample):
         if rects is None and info is None:
-            check(_bind_dev().ccmi_decode_batch_dev_plan(m[1], m[2], n, output_bitdepth, output_chroma_format, sample,
-                                                         geom, C.byref(need)))
+            check(_bind().ccmi_decode_batch_dev_plan(m[1], m[2], n, output_bitdepth, output_chroma_format, sample,
+                                                     geom, C.byref(need)))
         else:
-            check(_bind_dev().ccmi_decode_batch_dev_roi_plan(m[1], m[2], n, rects, output_bitdepth,
-                                                             output_chroma_format, sample, geom, info, C.byref(need)))
-    if dtype is None:
-        plan(SAMPLE_U16)  # any bitdepth: learns every stream's output bitdepth
-        sample = SAMPLE_U8 if all(g.bitdepth <= 8 for g in geom) else SAMPLE_U16
-    else:
-        table = {torch.uint8: SAMPLE_U8, torch.uint16: SAMPLE_U16, torch.float32: SAMPLE_F32}
-        if dtype not in table:
-            raise ValueError(f"decode_batch_tensors: dtype {dtype} (torch.uint8, torch.uint16, torch.float32 or None)")
-        sample = table[dtype]
-    plan(sample)
-    return sample, geom, need.value
+            check(_bind().ccmi_decode_batch_dev_roi_plan(m[1], m[2], n, rects, output_bitdepth,
+                                                         output_chroma_format, sample, geom, info, C.byref(need)))
+    return _pick_sample(plan, geom, dtype, "decode_batch_tensors"), geom, need.value
 
 
 def decode_batch_geometry(streams: Sequence[bytes], output_bitdepth: int = 0, output_chroma_format: int = 0,
@@ -313,17 +346,14 @@ def decode_batch_tensors(streams: Sequence[bytes], output_bitdepth: int = 0, out
     n = len(streams)
     dev = torch.device("cuda", torch.cuda.current_device())
     flat, outs, op, cap = _alloc_outs(geom, sample, stack, dev)
-    if stream_handle is None:
-        stream_handle = torch.cuda.current_stream(dev).cuda_stream
-    if workspace is None:
-        workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
+    stream_handle, workspace = _stream_ws(dev, stream_handle, workspace, need)
     if rects is None:
-        check(_bind_dev().ccmi_decode_batch_dev(sp, ln, n, op, cap, sample, output_bitdepth, output_chroma_format,
-                                                workspace.data_ptr(), workspace.numel(), stream_handle))
+        check(_bind().ccmi_decode_batch_dev(sp, ln, n, op, cap, sample, output_bitdepth, output_chroma_format,
+                                            workspace.data_ptr(), workspace.numel(), stream_handle))
     else:
-        check(_bind_dev().ccmi_decode_batch_dev_roi(sp, ln, n, rects, op, cap, sample, output_bitdepth,
-                                                    output_chroma_format, workspace.data_ptr(), workspace.numel(),
-                                                    stream_handle))
+        check(_bind().ccmi_decode_batch_dev_roi(sp, ln, n, rects, op, cap, sample, output_bitdepth,
+                                                output_chroma_format, workspace.data_ptr(), workspace.numel(),
+                                                stream_handle))
     return _shape_outs(flat, outs, geom, stack)
 
 
@@ -337,43 +367,12 @@ class TensorFmt(C.Structure):
                 ("stride_c", C.c_int64), ("stride_y", C.c_int64), ("stride_x", C.c_int64), ("mirror", C.c_void_p)]
 
 
-def _bind_fmt():
-    L = _bind_latents()
-    if not getattr(L, "_ccmi_fmt_bound", False):
-        P, I, Z = C.c_void_p, C.c_int, C.c_size_t
-        L.ccmi_decode_batch_dev_fmt_plan.argtypes = [P, P, I, P, I, I, P, P, P, P]
-        L.ccmi_decode_batch_dev_fmt.argtypes = [P, P, I, P, P, P, P, I, I, P, Z, P]
-        L.ccmi_latents_render_fmt_plan.argtypes = [P, P, I, P, I, I, P, P, P, P]
-        L.ccmi_latents_render_fmt.argtypes = [P, P, I, P, P, P, P, I, I, P, Z, P]
-        for f in (L.ccmi_decode_batch_dev_fmt_plan, L.ccmi_decode_batch_dev_fmt, L.ccmi_latents_render_fmt_plan,
-                  L.ccmi_latents_render_fmt):
-            f.restype = C.c_int
-        L._ccmi_fmt_bound = True
-    return L
-
-
 FILTER_TRIANGLE = 0  # CCMI_FILTER_*
 
 
 class Resample(C.Structure):
     """ccmi_resample: the output size of a resampling call."""
     _fields_ = [("out_w", C.c_int), ("out_h", C.c_int), ("filter", C.c_int)]
-
-
-def _bind_rs():
-    L = _bind_fmt()
-    if not getattr(L, "_ccmi_rs_bound", False):
-        P, I, Z = C.c_void_p, C.c_int, C.c_size_t
-        L.ccmi_decode_batch_dev_rs_plan.argtypes = [P, P, I, P, I, I, P, P, P, P, P]
-        L.ccmi_decode_batch_dev_rs.argtypes = [P, P, I, P, P, P, P, P, I, I, P, Z, P]
-        L.ccmi_latents_render_rs_plan.argtypes = [P, P, I, P, I, I, P, P, P, P, P]
-        L.ccmi_latents_render_rs.argtypes = [P, P, I, P, P, P, P, P, I, I, P, Z, P]
-        L.ccmi_decode_last_tail_groups.argtypes = [P, P]
-        for f in (L.ccmi_decode_batch_dev_rs_plan, L.ccmi_decode_batch_dev_rs, L.ccmi_latents_render_rs_plan,
-                  L.ccmi_latents_render_rs, L.ccmi_decode_last_tail_groups):
-            f.restype = C.c_int
-        L._ccmi_rs_bound = True
-    return L
 
 
 def _resample(size):
@@ -387,7 +386,7 @@ def last_tail_groups() -> tuple:
     """(batched tail groups, per-frame tails) this thread's last decode or render call launched
     (ccmi_decode_last_tail_groups): frames that share a group share one launch per tail stage."""
     batched, per_frame = C.c_int(0), C.c_int(0)
-    check(_bind_rs().ccmi_decode_last_tail_groups(C.byref(batched), C.byref(per_frame)))
+    check(_bind().ccmi_decode_last_tail_groups(C.byref(batched), C.byref(per_frame)))
     return batched.value, per_frame.value
 
 
@@ -460,6 +459,33 @@ def _model_outs(geom, fmt, dtype, channels_last, out, dev):
     return res, op, cap, frames
 
 
+def _plan_model(plan, head, n, rects, fmt, rs, output_bitdepth, output_chroma_format):
+    """(ccmi_frame_geom array, workspace bytes) of a formatted call: plan is the source's *_rs_plan
+    entry point (rs None: exactly the *_fmt_plan call), head its first two arguments."""
+    geom, need = (FrameGeom * n)(), C.c_size_t(0)
+    probe = TensorFmt.from_buffer_copy(fmt)  # planar strides: the geometry does not depend on them
+    check(plan(*head, n, rects, output_bitdepth, output_chroma_format, C.byref(probe), rs, geom, None, C.byref(need)))
+    return geom, need.value
+
+
+def _run_model(plan, run, head, n, rects, dev, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth,
+               output_chroma_format, workspace, stream_handle, size):
+    """The body of decode_batch_model and LatentStore.render_model: plan / run are the source's
+    *_rs_plan / *_rs entry points, head their first two arguments; dev None: the current device."""
+    import torch
+    dtype = torch.float32 if dtype is None else dtype
+    fmt, keep = _model_fmt(n, colour, mean, std, dtype, mirror)
+    rs = None if size is None else C.byref(_resample(size))
+    geom, need = _plan_model(plan, head, n, rects, fmt, rs, output_bitdepth, output_chroma_format)
+    dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else dev
+    res, op, cap, frames = _model_outs(geom, fmt, dtype, channels_last, out, dev)
+    stream_handle, workspace = _stream_ws(dev, stream_handle, workspace, need)
+    check(run(*head, n, rects, op, cap, C.byref(fmt), rs, output_bitdepth, output_chroma_format,
+              workspace.data_ptr(), workspace.numel(), stream_handle))
+    del keep, frames
+    return res
+
+
 def decode_batch_model(streams: Sequence[bytes], roi=None, colour: str = "rgb", mean=None, std=None, dtype=None,
                        channels_last: bool = False, mirror=None, out=None, output_bitdepth: int = 0,
                        output_chroma_format: int = 0, workspace=None, stream_handle: int | None = None, size=None):
@@ -483,30 +509,12 @@ def decode_batch_model(streams: Sequence[bytes], roi=None, colour: str = "rgb", 
     between the colour step and the normalisation, in the same output stage (the contract's
     steps 3a-3c); h, w above are then out_h, out_w, the regions may differ in size, and frames
     of one architecture share their launches whatever their regions (last_tail_groups())."""
-    import torch
-    dtype = torch.float32 if dtype is None else dtype
     n = len(streams)
-    m = _marshal(streams)
-    _, sp, ln = m
-    rects = _rects(roi, streams, n)
-    fmt, keep = _model_fmt(n, colour, mean, std, dtype, mirror)
-    L = _bind_fmt() if size is None else _bind_rs()
-    rs = () if size is None else (C.byref(_resample(size)),)
-    plan, run = ((L.ccmi_decode_batch_dev_fmt_plan, L.ccmi_decode_batch_dev_fmt) if size is None else
-                 (L.ccmi_decode_batch_dev_rs_plan, L.ccmi_decode_batch_dev_rs))
-    geom, need = (FrameGeom * n)(), C.c_size_t(0)
-    probe = TensorFmt.from_buffer_copy(fmt)  # planar strides: the geometry does not depend on them
-    check(plan(sp, ln, n, rects, output_bitdepth, output_chroma_format, C.byref(probe), *rs, geom, None, C.byref(need)))
-    dev = torch.device("cuda", torch.cuda.current_device())
-    res, op, cap, frames = _model_outs(geom, fmt, dtype, channels_last, out, dev)
-    if stream_handle is None:
-        stream_handle = torch.cuda.current_stream(dev).cuda_stream
-    if workspace is None:
-        workspace = torch.empty(max(need.value, 256), dtype=torch.uint8, device=dev)
-    check(run(sp, ln, n, rects, op, cap, C.byref(fmt), *rs, output_bitdepth, output_chroma_format,
-              workspace.data_ptr(), workspace.numel(), stream_handle))
-    del keep, frames
-    return res
+    keep, sp, ln = _marshal(streams)
+    L = _bind()
+    return _run_model(L.ccmi_decode_batch_dev_rs_plan, L.ccmi_decode_batch_dev_rs, (sp, ln), n, _rects(roi, streams, n),
+                      None, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth, output_chroma_format,
+                      workspace, stream_handle, size)
 
 
 def weights_i32(stream: bytes):
@@ -582,9 +590,7 @@ def decode_latents(stream: bytes, stream_handle: int | None = None) -> list:
     n = sum(h * w for h, w in fr.grid_sizes)
     out = np.zeros(n, dtype=np.int32)
     buf = C.create_string_buffer(stream, len(stream))
-    L = lib()
-    L.ccmi_decode_latents.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p]
-    L.ccmi_decode_latents.restype = C.c_int
+    L = _bind()
     if stream_handle is None:
         import torch
         stream_handle = torch.cuda.current_stream().cuda_stream
@@ -622,32 +628,6 @@ def last_arm_flags() -> list[int]:
 LATENT_I8, LATENT_I16, LATENT_I32, LATENT_SEG = 0, 1, 2, 3  # CCMI_LATENT_*; SEG by LatentStore.compact() only
 
 
-def _bind_latents():
-    L = _bind_dev()
-    if not getattr(L, "_ccmi_latents_bound", False):
-        P, I, Z = C.c_void_p, C.c_int, C.c_size_t
-        L.ccmi_latents_plan.argtypes = [P, P, I, I, P, P, P]
-        L.ccmi_latents_decode.argtypes = [P, P, I, I, P, Z, P, Z, P, P]
-        L.ccmi_latents_free.argtypes = [P]
-        L.ccmi_latents_free.restype = None
-        L.ccmi_latents_count.argtypes = [P]
-        L.ccmi_latents_values.argtypes = [P, I, P, Z, P]
-        L.ccmi_latents_render_plan.argtypes = [P, P, I, P, I, I, I, P, P, P]
-        L.ccmi_latents_render.argtypes = [P, P, I, P, P, P, I, I, I, P, Z, P]
-        L.ccmi_latents_compact_plan.argtypes = [P, P, P]
-        L.ccmi_latents_compact_measure.argtypes = [P, P, Z, P, P, P]
-        L.ccmi_latents_compact.argtypes = [P, P, Z, P, Z, P, P]
-        L.ccmi_latents_concat.argtypes = [P, I, P]
-        L.ccmi_latents_stream_info.argtypes = [P, I, P, P]
-        for f in (L.ccmi_latents_plan, L.ccmi_latents_decode, L.ccmi_latents_count, L.ccmi_latents_values,
-                  L.ccmi_latents_render_plan, L.ccmi_latents_render, L.ccmi_latents_compact_plan,
-                  L.ccmi_latents_compact_measure, L.ccmi_latents_compact, L.ccmi_latents_concat,
-                  L.ccmi_latents_stream_info):
-            f.restype = C.c_int
-        L._ccmi_latents_bound = True
-    return L
-
-
 class LatentStore:
     """Decode once, render often (ccmi_latents_*): the ARM + CABAC decode of `streams` runs
     once, and its output -- the integer latents, packed, with the upsampling and synthesis
@@ -670,22 +650,18 @@ class LatentStore:
     def __init__(self, streams: Sequence[bytes], dtype=None, workspace=None, stream_handle: int | None = None):
         import torch
         self._h = None
-        L = _bind_latents()
+        L = _bind()
         table = {torch.int8: LATENT_I8, torch.int16: LATENT_I16, torch.int32: LATENT_I32}
         if dtype is not None and dtype not in table:
             raise ValueError(f"LatentStore: dtype {dtype} (torch.int8, torch.int16, torch.int32 or None)")
         m = _marshal(streams)
         n = len(streams)
         dev = torch.device("cuda", torch.cuda.current_device())
-        if stream_handle is None:
-            stream_handle = torch.cuda.current_stream(dev).cuda_stream
         for t in ([torch.int16, torch.int32] if dtype is None else [dtype]):
             nstore, nws = C.c_size_t(0), C.c_size_t(0)
             check(L.ccmi_latents_plan(m[1], m[2], n, table[t], C.byref(nstore), None, C.byref(nws)))
             store = torch.empty(max(nstore.value, 256), dtype=torch.uint8, device=dev)
-            ws = workspace
-            if ws is None:
-                ws = torch.empty(max(nws.value, 256), dtype=torch.uint8, device=dev)
+            stream_handle, ws = _stream_ws(dev, stream_handle, workspace, nws.value)
             h = C.c_void_p(None)
             rc = L.ccmi_latents_decode(m[1], m[2], n, table[t], store.data_ptr(), store.numel(), ws.data_ptr(),
                                        ws.numel(), stream_handle, C.byref(h))
@@ -699,7 +675,7 @@ class LatentStore:
     def _adopt(self, h, stores, arm_flags):
         """Takes the handle h over the device tensors `stores`; the facts come from the handle."""
         import torch
-        L = _bind_latents()
+        L = _bind()
         self._h, self._stores, self._store, self.arm_flags = h, list(stores), stores[0], arm_flags
         names = {LATENT_I8: torch.int8, LATENT_I16: torch.int16, LATENT_I32: torch.int32, LATENT_SEG: "seg"}
         self.stream_nbytes, self.stream_dtypes = [], []
@@ -719,15 +695,11 @@ class LatentStore:
         packed on the GPU.  This store is untouched and may be closed; the new one renders the
         same samples.  workspace: a uint8 CUDA tensor (else torch's allocator)."""
         import torch
-        L = _bind_latents()
+        L = _bind()
         dev = self._store.device
-        if stream_handle is None:
-            stream_handle = torch.cuda.current_stream(dev).cuda_stream
         bound, nws, exact = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
         check(L.ccmi_latents_compact_plan(self._handle(), C.byref(bound), C.byref(nws)))
-        ws = workspace
-        if ws is None:
-            ws = torch.empty(max(nws.value, 256), dtype=torch.uint8, device=dev)
+        stream_handle, ws = _stream_ws(dev, stream_handle, workspace, nws.value)
         check(L.ccmi_latents_compact_measure(self._handle(), ws.data_ptr(), ws.numel(), stream_handle, C.byref(exact), None))
         store = torch.empty(max(exact.value, 256), dtype=torch.uint8, device=dev)
         h = C.c_void_p(None)
@@ -747,13 +719,13 @@ class LatentStore:
             raise ValueError("LatentStore.concat: no stores")
         parts = (C.c_void_p * len(stores))(*[s._handle() for s in stores])
         h = C.c_void_p(None)
-        check(_bind_latents().ccmi_latents_concat(parts, len(stores), C.byref(h)))
+        check(_bind().ccmi_latents_concat(parts, len(stores), C.byref(h)))
         out = cls.__new__(cls)
         out._adopt(h, [t for s in stores for t in s._stores], [f for s in stores for f in s.arm_flags])
         return out
 
     def __len__(self):
-        return _bind_latents().ccmi_latents_count(self._handle())
+        return _bind().ccmi_latents_count(self._handle())
 
     def _handle(self):
         if self._h is None:
@@ -763,7 +735,7 @@ class LatentStore:
     def close(self):
         """Frees the handle and drops the store tensor."""
         if getattr(self, "_h", None) is not None:
-            _bind_latents().ccmi_latents_free(self._h)
+            _bind().ccmi_latents_free(self._h)
             self._h = None
             self._store = None
             self._stores = []
@@ -781,40 +753,22 @@ class LatentStore:
         m = len(idx)
         if m < 1:
             raise ValueError("LatentStore: no frames")
-        rects = None
-        if roi is not None:
-            one = len(roi) == 4 and all(isinstance(v, int) for v in roi)
-            rois = [tuple(roi)] * m if one else list(roi)
-            if len(rois) != m:
-                raise ValueError(f"roi: one (x, y, w, h), or one entry per frame ({m}), got {len(rois)}")
-            rects = (Rect * m)()
-            for j, r in enumerate(rois):
-                if r is None:  # the whole frame of that stream (an index out of range is the library's error)
-                    g = self.geometry[idx[j]] if 0 <= idx[j] < n else {"width": 1, "height": 1}
-                    r = (0, 0, g["width"], g["height"])
-                if len(r) != 4:
-                    raise ValueError(f"roi[{j}]: (x, y, w, h) expected")
-                rects[j] = Rect(*[int(v) for v in r])
+
+        def whole(j):  # of that frame's stream (an index out of range is the library's error)
+            g = self.geometry[idx[j]] if 0 <= idx[j] < n else {"width": 1, "height": 1}
+            return 0, 0, g["width"], g["height"]
+        rects = _roi_rects(roi, m, whole, "frame")
         return m, (None if index is None else (C.c_int * m)(*idx)), rects
 
     def _plan(self, index, roi, output_bitdepth, output_chroma_format, dtype, info=None):
-        import torch
-        L = _bind_latents()
+        L = _bind()
         m, idx, rects = self._frames(index, roi)
         geom, need = (FrameGeom * m)(), C.c_size_t(0)
 
         def plan(sample):
             check(L.ccmi_latents_render_plan(self._handle(), idx, m, rects, output_bitdepth, output_chroma_format, sample,
                                              geom, info(m) if callable(info) else None, C.byref(need)))
-        if dtype is None:
-            plan(SAMPLE_U16)
-            sample = SAMPLE_U8 if all(g.bitdepth <= 8 for g in geom) else SAMPLE_U16
-        else:
-            table = {torch.uint8: SAMPLE_U8, torch.uint16: SAMPLE_U16, torch.float32: SAMPLE_F32}
-            if dtype not in table:
-                raise ValueError(f"LatentStore: dtype {dtype} (torch.uint8, torch.uint16, torch.float32 or None)")
-            sample = table[dtype]
-        plan(sample)
+        sample = _pick_sample(plan, geom, dtype, "LatentStore")
         return m, idx, rects, sample, geom, need.value
 
     def render_geometry(self, index=None, roi=None, output_bitdepth: int = 0, output_chroma_format: int = 0,
@@ -841,17 +795,12 @@ class LatentStore:
         decode_batch_tensors returns for those streams: tensors, {'y', 'u', 'v'} dicts, or with
         stack=True one stacked tensor / dict.  workspace: a uint8 CUDA tensor of at least
         render_geometry(...)[1] bytes."""
-        import torch
         m, idx, rects, sample, geom, need = self._plan(index, roi, output_bitdepth, output_chroma_format, dtype)
         dev = self._store.device
         flat, outs, op, cap = _alloc_outs(geom, sample, stack, dev)
-        if stream_handle is None:
-            stream_handle = torch.cuda.current_stream(dev).cuda_stream
-        if workspace is None:
-            workspace = torch.empty(max(need, 256), dtype=torch.uint8, device=dev)
-        check(_bind_latents().ccmi_latents_render(self._handle(), idx, m, rects, op, cap, sample, output_bitdepth,
-                                                  output_chroma_format, workspace.data_ptr(), workspace.numel(),
-                                                  stream_handle))
+        stream_handle, workspace = _stream_ws(dev, stream_handle, workspace, need)
+        check(_bind().ccmi_latents_render(self._handle(), idx, m, rects, op, cap, sample, output_bitdepth,
+                                          output_chroma_format, workspace.data_ptr(), workspace.numel(), stream_handle))
         return _shape_outs(flat, outs, geom, stack)
 
     def render_model(self, index=None, roi=None, colour: str = "rgb", mean=None, std=None, dtype=None,
@@ -862,28 +811,11 @@ class LatentStore:
         argument as for decode_batch_model, whose output for the same streams and arguments it
         equals bit for bit.  workspace with a size: at least what render_model_workspace_bytes()
         reports (the resample's intermediate is not part of render_geometry()'s figure)."""
-        import torch
-        dtype = torch.float32 if dtype is None else dtype
         m, idx, rects = self._frames(index, roi)
-        fmt, keep = _model_fmt(m, colour, mean, std, dtype, mirror)
-        L = _bind_fmt() if size is None else _bind_rs()
-        rs = () if size is None else (C.byref(_resample(size)),)
-        plan, run = ((L.ccmi_latents_render_fmt_plan, L.ccmi_latents_render_fmt) if size is None else
-                     (L.ccmi_latents_render_rs_plan, L.ccmi_latents_render_rs))
-        geom, need = (FrameGeom * m)(), C.c_size_t(0)
-        probe = TensorFmt.from_buffer_copy(fmt)
-        check(plan(self._handle(), idx, m, rects, output_bitdepth, output_chroma_format, C.byref(probe), *rs, geom, None,
-                   C.byref(need)))
-        dev = self._store.device
-        res, op, cap, frames = _model_outs(geom, fmt, dtype, channels_last, out, dev)
-        if stream_handle is None:
-            stream_handle = torch.cuda.current_stream(dev).cuda_stream
-        if workspace is None:
-            workspace = torch.empty(max(need.value, 256), dtype=torch.uint8, device=dev)
-        check(run(self._handle(), idx, m, rects, op, cap, C.byref(fmt), *rs, output_bitdepth, output_chroma_format,
-                  workspace.data_ptr(), workspace.numel(), stream_handle))
-        del keep, frames
-        return res
+        L = _bind()
+        return _run_model(L.ccmi_latents_render_rs_plan, L.ccmi_latents_render_rs, (self._handle(), idx), m, rects,
+                          self._store.device, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth,
+                          output_chroma_format, workspace, stream_handle, size)
 
     def render_model_workspace_bytes(self, index=None, roi=None, size=None, output_bitdepth: int = 0,
                                      output_chroma_format: int = 0) -> int:
@@ -894,10 +826,8 @@ class LatentStore:
         for c in range(3):
             fmt.scale[c] = 1.0
         rs = None if size is None else C.byref(_resample(size))
-        geom, need = (FrameGeom * m)(), C.c_size_t(0)
-        check(_bind_rs().ccmi_latents_render_rs_plan(self._handle(), idx, m, rects, output_bitdepth, output_chroma_format,
-                                                     C.byref(fmt), rs, geom, None, C.byref(need)))
-        return need.value
+        return _plan_model(_bind().ccmi_latents_render_rs_plan, (self._handle(), idx), m, rects, fmt, rs, output_bitdepth,
+                           output_chroma_format)[1]
 
     def latents(self, i: int) -> list:
         """Stream i's integer latents: one int32 device tensor [h_l, w_l] per grid."""
@@ -909,8 +839,8 @@ class LatentStore:
             sizes.append((h, w))
             h, w = (h + 1) // 2, (w + 1) // 2
         flat = torch.empty(sum(a * b for a, b in sizes), dtype=torch.int32, device=self._store.device)
-        check(_bind_latents().ccmi_latents_values(self._handle(), int(i), flat.data_ptr(), flat.numel(),
-                                                  torch.cuda.current_stream(flat.device).cuda_stream))
+        check(_bind().ccmi_latents_values(self._handle(), int(i), flat.data_ptr(), flat.numel(),
+                                          torch.cuda.current_stream(flat.device).cuda_stream))
         out, p = [], 0
         for a, b in sizes:
             out.append(flat[p: p + a * b].view(a, b))

@@ -1006,27 +1006,74 @@ extern "C" int ccmi_decode_batch_ws(const uint8_t *const *streams, const size_t 
     return decode_many(rq, stream);
 }
 
-extern "C" int ccmi_decode_batch_dev_plan(const uint8_t *const *streams, const size_t *lens, int n, int out_bitdepth,
-                                          int out_chroma, int sample_type, ccmi_frame_geom *geom,
-                                          size_t *workspace_bytes)
+// ------------------------------------------------------------------ device sinks
+// Sixteen entry points over one table: the source is the caller's streams or a latent store, the
+// sink plain samples (sample_type; with or without a region) or formatted ones (fmt, forced to
+// CCMI_SAMPLE_F32, the call whose output kernel the format replaces; with or without a resample),
+// and each comes as a plan and as a run.  `who` is the entry point's name for the error text,
+// `missing` its own null-argument check beyond the source's.
+struct Sink {
+    const ccmi_rect *roi;
+    int sample;
+    const ccmi_tensor_fmt *fmt;
+    const ccmi_resample *rs;
+};
+
+static Sink samples(const ccmi_rect *roi, int sample_type) { return Sink{roi, sample_type, nullptr, nullptr}; }
+
+static Sink formatted(const ccmi_rect *roi, const ccmi_tensor_fmt *fmt, const ccmi_resample *rs)
 {
-    if (!streams || !lens || !geom || !workspace_bytes)
-        return ccmi_set_error(CCMI_ERR_ARG, "decode_batch_dev_plan: null argument");
-    if (sample_type < 0) return ccmi_set_error(CCMI_ERR_ARG, "decode: unknown sample type %d", sample_type);
-    DecodeRequest rq = request(streams, lens, n, out_bitdepth, out_chroma);
-    rq.sample = sample_type;
+    return Sink{roi, CCMI_SAMPLE_F32, fmt, rs};
+}
+
+static void set_sink(DecodeRequest &rq, const Sink &k)
+{
+    rq.sample = k.sample;
+    rq.roi = k.roi;
+    rq.fmt = k.fmt;
+    rq.rs = k.rs;
+}
+
+// streams as the source: null arguments, then the sample type, then the plan's own errors
+static int stream_request(const char *who, const uint8_t *const *streams, const size_t *lens, int n, const Sink &k,
+                          int out_bitdepth, int out_chroma, bool missing, DecodeRequest &rq)
+{
+    clear_last();
+    if (!streams || !lens || missing) return ccmi_set_error(CCMI_ERR_ARG, "%s: null argument", who);
+    if (k.sample < 0) return ccmi_set_error(CCMI_ERR_ARG, "decode: unknown sample type %d", k.sample);
+    rq = request(streams, lens, n, out_bitdepth, out_chroma);
+    set_sink(rq, k);
+    return CCMI_OK;
+}
+
+// a latent store as the source: the handle and the sample type, then (a run) a plan-only handle,
+// then null arguments, then the plan's own errors
+static int latents_request(const char *who, const ccmi_latents *h, const int *index, int m, const Sink &k,
+                           int out_bitdepth, int out_chroma, bool run, bool missing, DecodeRequest &rq)
+{
+    clear_last();
+    if (!h) return ccmi_set_error(CCMI_ERR_ARG, "render: the handle is NULL (no frame 0)");
+    if (k.sample < 0) return ccmi_set_error(CCMI_ERR_ARG, "decode: unknown sample type %d", k.sample);
+    if (run && !h->resident)
+        return ccmi_set_error(CCMI_ERR_ARG, "render: the handle is plan-only (built without a store): no frame 0 to render");
+    if (missing) return ccmi_set_error(CCMI_ERR_ARG, "%s: null argument", who);
+    rq = request(nullptr, nullptr, m, out_bitdepth, out_chroma);
+    rq.src = h;
+    rq.index = index;
+    set_sink(rq, k);
+    return CCMI_OK;
+}
+
+static int sink_plan(DecodeRequest &rq, ccmi_frame_geom *geom, ccmi_roi_info *info, size_t *workspace_bytes)
+{
     rq.geom = geom;
+    rq.info = info;
     return plan_only(rq, workspace_bytes);
 }
 
-extern "C" int ccmi_decode_batch_dev(const uint8_t *const *streams, const size_t *lens, int n, void *const *out_dev,
-                                     const size_t *out_caps, int sample_type, int out_bitdepth, int out_chroma,
-                                     void *workspace, size_t workspace_bytes, void *stream)
+static int sink_run(DecodeRequest &rq, void *const *out_dev, const size_t *out_caps, void *workspace,
+                    size_t workspace_bytes, void *stream)
 {
-    if (!streams || !lens || !out_dev || !out_caps) return ccmi_set_error(CCMI_ERR_ARG, "decode_batch_dev: null argument");
-    if (sample_type < 0) return ccmi_set_error(CCMI_ERR_ARG, "decode: unknown sample type %d", sample_type);
-    DecodeRequest rq = request(streams, lens, n, out_bitdepth, out_chroma);
-    rq.sample = sample_type;
     rq.dev = out_dev;
     rq.caps = out_caps;
     rq.ws = workspace;
@@ -1034,19 +1081,37 @@ extern "C" int ccmi_decode_batch_dev(const uint8_t *const *streams, const size_t
     return decode_many(rq, stream);
 }
 
+extern "C" int ccmi_decode_batch_dev_plan(const uint8_t *const *streams, const size_t *lens, int n, int out_bitdepth,
+                                          int out_chroma, int sample_type, ccmi_frame_geom *geom,
+                                          size_t *workspace_bytes)
+{
+    DecodeRequest rq;
+    if (int rc = stream_request("decode_batch_dev_plan", streams, lens, n, samples(nullptr, sample_type), out_bitdepth,
+                                out_chroma, !geom || !workspace_bytes, rq))
+        return rc;
+    return sink_plan(rq, geom, nullptr, workspace_bytes);
+}
+
+extern "C" int ccmi_decode_batch_dev(const uint8_t *const *streams, const size_t *lens, int n, void *const *out_dev,
+                                     const size_t *out_caps, int sample_type, int out_bitdepth, int out_chroma,
+                                     void *workspace, size_t workspace_bytes, void *stream)
+{
+    DecodeRequest rq;
+    if (int rc = stream_request("decode_batch_dev", streams, lens, n, samples(nullptr, sample_type), out_bitdepth,
+                                out_chroma, !out_dev || !out_caps, rq))
+        return rc;
+    return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
+}
+
 extern "C" int ccmi_decode_batch_dev_roi_plan(const uint8_t *const *streams, const size_t *lens, int n,
                                               const ccmi_rect *roi, int out_bitdepth, int out_chroma, int sample_type,
                                               ccmi_frame_geom *geom, ccmi_roi_info *info, size_t *workspace_bytes)
 {
-    if (!streams || !lens || !geom || !workspace_bytes)
-        return ccmi_set_error(CCMI_ERR_ARG, "decode_batch_dev_roi_plan: null argument");
-    if (sample_type < 0) return ccmi_set_error(CCMI_ERR_ARG, "decode: unknown sample type %d", sample_type);
-    DecodeRequest rq = request(streams, lens, n, out_bitdepth, out_chroma);
-    rq.sample = sample_type;
-    rq.roi = roi;
-    rq.geom = geom;
-    rq.info = info;
-    return plan_only(rq, workspace_bytes);
+    DecodeRequest rq;
+    if (int rc = stream_request("decode_batch_dev_roi_plan", streams, lens, n, samples(roi, sample_type), out_bitdepth,
+                                out_chroma, !geom || !workspace_bytes, rq))
+        return rc;
+    return sink_plan(rq, geom, info, workspace_bytes);
 }
 
 extern "C" int ccmi_decode_batch_dev_roi(const uint8_t *const *streams, const size_t *lens, int n, const ccmi_rect *roi,
@@ -1054,34 +1119,46 @@ extern "C" int ccmi_decode_batch_dev_roi(const uint8_t *const *streams, const si
                                          int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes,
                                          void *stream)
 {
-    if (!streams || !lens || !out_dev || !out_caps)
-        return ccmi_set_error(CCMI_ERR_ARG, "decode_batch_dev_roi: null argument");
-    if (sample_type < 0) return ccmi_set_error(CCMI_ERR_ARG, "decode: unknown sample type %d", sample_type);
-    DecodeRequest rq = request(streams, lens, n, out_bitdepth, out_chroma);
-    rq.sample = sample_type;
-    rq.roi = roi;
-    rq.dev = out_dev;
-    rq.caps = out_caps;
-    rq.ws = workspace;
-    rq.ws_bytes = workspace_bytes;
-    return decode_many(rq, stream);
+    DecodeRequest rq;
+    if (int rc = stream_request("decode_batch_dev_roi", streams, lens, n, samples(roi, sample_type), out_bitdepth,
+                                out_chroma, !out_dev || !out_caps, rq))
+        return rc;
+    return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
 }
 
-// The formatted sink plans as the CCMI_SAMPLE_F32 call it replaces the output kernel of.
+// The resampling sink is the formatted call with a ccmi_resample next to the format; rs NULL is
+// that call itself, under its own name.
+extern "C" int ccmi_decode_batch_dev_rs_plan(const uint8_t *const *streams, const size_t *lens, int n,
+                                             const ccmi_rect *roi, int out_bitdepth, int out_chroma,
+                                             const ccmi_tensor_fmt *fmt, const ccmi_resample *rs, ccmi_frame_geom *geom,
+                                             ccmi_roi_info *info, size_t *workspace_bytes)
+{
+    DecodeRequest rq;
+    if (int rc = stream_request(rs ? "decode_batch_dev_rs_plan" : "decode_batch_dev_fmt_plan", streams, lens, n,
+                                formatted(roi, fmt, rs), out_bitdepth, out_chroma, !fmt || !geom || !workspace_bytes, rq))
+        return rc;
+    return sink_plan(rq, geom, info, workspace_bytes);
+}
+
+extern "C" int ccmi_decode_batch_dev_rs(const uint8_t *const *streams, const size_t *lens, int n, const ccmi_rect *roi,
+                                        void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
+                                        const ccmi_resample *rs, int out_bitdepth, int out_chroma, void *workspace,
+                                        size_t workspace_bytes, void *stream)
+{
+    DecodeRequest rq;
+    if (int rc = stream_request(rs ? "decode_batch_dev_rs" : "decode_batch_dev_fmt", streams, lens, n,
+                                formatted(roi, fmt, rs), out_bitdepth, out_chroma, !out_dev || !out_caps || !fmt, rq))
+        return rc;
+    return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
+}
+
 extern "C" int ccmi_decode_batch_dev_fmt_plan(const uint8_t *const *streams, const size_t *lens, int n,
                                               const ccmi_rect *roi, int out_bitdepth, int out_chroma,
                                               const ccmi_tensor_fmt *fmt, ccmi_frame_geom *geom, ccmi_roi_info *info,
                                               size_t *workspace_bytes)
 {
-    if (!streams || !lens || !fmt || !geom || !workspace_bytes)
-        return ccmi_set_error(CCMI_ERR_ARG, "decode_batch_dev_fmt_plan: null argument");
-    DecodeRequest rq = request(streams, lens, n, out_bitdepth, out_chroma);
-    rq.sample = CCMI_SAMPLE_F32;
-    rq.fmt = fmt;
-    rq.roi = roi;
-    rq.geom = geom;
-    rq.info = info;
-    return plan_only(rq, workspace_bytes);
+    return ccmi_decode_batch_dev_rs_plan(streams, lens, n, roi, out_bitdepth, out_chroma, fmt, nullptr, geom, info,
+                                         workspace_bytes);
 }
 
 extern "C" int ccmi_decode_batch_dev_fmt(const uint8_t *const *streams, const size_t *lens, int n, const ccmi_rect *roi,
@@ -1089,17 +1166,8 @@ extern "C" int ccmi_decode_batch_dev_fmt(const uint8_t *const *streams, const si
                                          int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes,
                                          void *stream)
 {
-    if (!streams || !lens || !out_dev || !out_caps || !fmt)
-        return ccmi_set_error(CCMI_ERR_ARG, "decode_batch_dev_fmt: null argument");
-    DecodeRequest rq = request(streams, lens, n, out_bitdepth, out_chroma);
-    rq.sample = CCMI_SAMPLE_F32;
-    rq.fmt = fmt;
-    rq.roi = roi;
-    rq.dev = out_dev;
-    rq.caps = out_caps;
-    rq.ws = workspace;
-    rq.ws_bytes = workspace_bytes;
-    return decode_many(rq, stream);
+    return ccmi_decode_batch_dev_rs(streams, lens, n, roi, out_dev, out_caps, fmt, nullptr, out_bitdepth, out_chroma,
+                                    workspace, workspace_bytes, stream);
 }
 
 extern "C" int ccmi_latents_plan(const uint8_t *const *streams, const size_t *lens, int n, int latent_type,
@@ -1206,123 +1274,26 @@ extern "C" int ccmi_latents_values(const ccmi_latents *h, int i, int32_t *out_de
     return CCMI_OK;
 }
 
-static int latents_request(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi, int out_bitdepth,
-                           int out_chroma, int sample_type, DecodeRequest &rq)
-{
-    if (!h) return ccmi_set_error(CCMI_ERR_ARG, "render: the handle is NULL (no frame 0)");
-    if (sample_type < 0) return ccmi_set_error(CCMI_ERR_ARG, "decode: unknown sample type %d", sample_type);
-    rq = request(nullptr, nullptr, m, out_bitdepth, out_chroma);
-    rq.src = h;
-    rq.index = index;
-    rq.sample = sample_type;
-    rq.roi = roi;
-    return CCMI_OK;
-}
-
 extern "C" int ccmi_latents_render_plan(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
                                         int out_bitdepth, int out_chroma, int sample_type, ccmi_frame_geom *geom,
                                         ccmi_roi_info *info, size_t *workspace_bytes)
 {
-    clear_last();
     DecodeRequest rq;
-    if (int rc = latents_request(h, index, m, roi, out_bitdepth, out_chroma, sample_type, rq)) return rc;
-    if (!geom || !workspace_bytes) return ccmi_set_error(CCMI_ERR_ARG, "latents_render_plan: null argument");
-    rq.geom = geom;
-    rq.info = info;
-    return plan_only(rq, workspace_bytes);
+    if (int rc = latents_request("latents_render_plan", h, index, m, samples(roi, sample_type), out_bitdepth, out_chroma,
+                                 false, !geom || !workspace_bytes, rq))
+        return rc;
+    return sink_plan(rq, geom, info, workspace_bytes);
 }
 
 extern "C" int ccmi_latents_render(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
                                    void *const *out_dev, const size_t *out_caps, int sample_type, int out_bitdepth,
                                    int out_chroma, void *workspace, size_t workspace_bytes, void *stream)
 {
-    clear_last();
     DecodeRequest rq;
-    if (int rc = latents_request(h, index, m, roi, out_bitdepth, out_chroma, sample_type, rq)) return rc;
-    if (!h->resident)
-        return ccmi_set_error(CCMI_ERR_ARG, "render: the handle is plan-only (built without a store): no frame 0 to render");
-    if (!out_dev || !out_caps) return ccmi_set_error(CCMI_ERR_ARG, "latents_render: null argument");
-    rq.dev = out_dev;
-    rq.caps = out_caps;
-    rq.ws = workspace;
-    rq.ws_bytes = workspace_bytes;
-    return decode_many(rq, stream);
-}
-
-extern "C" int ccmi_latents_render_fmt_plan(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
-                                            int out_bitdepth, int out_chroma, const ccmi_tensor_fmt *fmt,
-                                            ccmi_frame_geom *geom, ccmi_roi_info *info, size_t *workspace_bytes)
-{
-    clear_last();
-    DecodeRequest rq;
-    if (int rc = latents_request(h, index, m, roi, out_bitdepth, out_chroma, CCMI_SAMPLE_F32, rq)) return rc;
-    if (!fmt || !geom || !workspace_bytes) return ccmi_set_error(CCMI_ERR_ARG, "latents_render_fmt_plan: null argument");
-    rq.fmt = fmt;
-    rq.geom = geom;
-    rq.info = info;
-    return plan_only(rq, workspace_bytes);
-}
-
-extern "C" int ccmi_latents_render_fmt(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
-                                       void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
-                                       int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes,
-                                       void *stream)
-{
-    clear_last();
-    DecodeRequest rq;
-    if (int rc = latents_request(h, index, m, roi, out_bitdepth, out_chroma, CCMI_SAMPLE_F32, rq)) return rc;
-    if (!h->resident)
-        return ccmi_set_error(CCMI_ERR_ARG, "render: the handle is plan-only (built without a store): no frame 0 to render");
-    if (!out_dev || !out_caps || !fmt) return ccmi_set_error(CCMI_ERR_ARG, "latents_render_fmt: null argument");
-    rq.fmt = fmt;
-    rq.dev = out_dev;
-    rq.caps = out_caps;
-    rq.ws = workspace;
-    rq.ws_bytes = workspace_bytes;
-    return decode_many(rq, stream);
-}
-
-// The resampling sink: the formatted call with a ccmi_resample next to the format (rs NULL: that
-// call itself).
-extern "C" int ccmi_decode_batch_dev_rs_plan(const uint8_t *const *streams, const size_t *lens, int n,
-                                             const ccmi_rect *roi, int out_bitdepth, int out_chroma,
-                                             const ccmi_tensor_fmt *fmt, const ccmi_resample *rs, ccmi_frame_geom *geom,
-                                             ccmi_roi_info *info, size_t *workspace_bytes)
-{
-    if (!rs)
-        return ccmi_decode_batch_dev_fmt_plan(streams, lens, n, roi, out_bitdepth, out_chroma, fmt, geom, info, workspace_bytes);
-    if (!streams || !lens || !fmt || !geom || !workspace_bytes)
-        return ccmi_set_error(CCMI_ERR_ARG, "decode_batch_dev_rs_plan: null argument");
-    DecodeRequest rq = request(streams, lens, n, out_bitdepth, out_chroma);
-    rq.sample = CCMI_SAMPLE_F32;
-    rq.fmt = fmt;
-    rq.rs = rs;
-    rq.roi = roi;
-    rq.geom = geom;
-    rq.info = info;
-    return plan_only(rq, workspace_bytes);
-}
-
-extern "C" int ccmi_decode_batch_dev_rs(const uint8_t *const *streams, const size_t *lens, int n, const ccmi_rect *roi,
-                                        void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
-                                        const ccmi_resample *rs, int out_bitdepth, int out_chroma, void *workspace,
-                                        size_t workspace_bytes, void *stream)
-{
-    if (!rs)
-        return ccmi_decode_batch_dev_fmt(streams, lens, n, roi, out_dev, out_caps, fmt, out_bitdepth, out_chroma, workspace,
-                                         workspace_bytes, stream);
-    if (!streams || !lens || !out_dev || !out_caps || !fmt)
-        return ccmi_set_error(CCMI_ERR_ARG, "decode_batch_dev_rs: null argument");
-    DecodeRequest rq = request(streams, lens, n, out_bitdepth, out_chroma);
-    rq.sample = CCMI_SAMPLE_F32;
-    rq.fmt = fmt;
-    rq.rs = rs;
-    rq.roi = roi;
-    rq.dev = out_dev;
-    rq.caps = out_caps;
-    rq.ws = workspace;
-    rq.ws_bytes = workspace_bytes;
-    return decode_many(rq, stream);
+    if (int rc = latents_request("latents_render", h, index, m, samples(roi, sample_type), out_bitdepth, out_chroma, true,
+                                 !out_dev || !out_caps, rq))
+        return rc;
+    return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
 }
 
 extern "C" int ccmi_latents_render_rs_plan(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
@@ -1330,17 +1301,12 @@ extern "C" int ccmi_latents_render_rs_plan(const ccmi_latents *h, const int *ind
                                            const ccmi_resample *rs, ccmi_frame_geom *geom, ccmi_roi_info *info,
                                            size_t *workspace_bytes)
 {
-    if (!rs)
-        return ccmi_latents_render_fmt_plan(h, index, m, roi, out_bitdepth, out_chroma, fmt, geom, info, workspace_bytes);
-    clear_last();
     DecodeRequest rq;
-    if (int rc = latents_request(h, index, m, roi, out_bitdepth, out_chroma, CCMI_SAMPLE_F32, rq)) return rc;
-    if (!fmt || !geom || !workspace_bytes) return ccmi_set_error(CCMI_ERR_ARG, "latents_render_rs_plan: null argument");
-    rq.fmt = fmt;
-    rq.rs = rs;
-    rq.geom = geom;
-    rq.info = info;
-    return plan_only(rq, workspace_bytes);
+    if (int rc = latents_request(rs ? "latents_render_rs_plan" : "latents_render_fmt_plan", h, index, m,
+                                 formatted(roi, fmt, rs), out_bitdepth, out_chroma, false,
+                                 !fmt || !geom || !workspace_bytes, rq))
+        return rc;
+    return sink_plan(rq, geom, info, workspace_bytes);
 }
 
 extern "C" int ccmi_latents_render_rs(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
@@ -1348,22 +1314,28 @@ extern "C" int ccmi_latents_render_rs(const ccmi_latents *h, const int *index, i
                                       const ccmi_resample *rs, int out_bitdepth, int out_chroma, void *workspace,
                                       size_t workspace_bytes, void *stream)
 {
-    if (!rs)
-        return ccmi_latents_render_fmt(h, index, m, roi, out_dev, out_caps, fmt, out_bitdepth, out_chroma, workspace,
-                                       workspace_bytes, stream);
-    clear_last();
     DecodeRequest rq;
-    if (int rc = latents_request(h, index, m, roi, out_bitdepth, out_chroma, CCMI_SAMPLE_F32, rq)) return rc;
-    if (!h->resident)
-        return ccmi_set_error(CCMI_ERR_ARG, "render: the handle is plan-only (built without a store): no frame 0 to render");
-    if (!out_dev || !out_caps || !fmt) return ccmi_set_error(CCMI_ERR_ARG, "latents_render_rs: null argument");
-    rq.fmt = fmt;
-    rq.rs = rs;
-    rq.dev = out_dev;
-    rq.caps = out_caps;
-    rq.ws = workspace;
-    rq.ws_bytes = workspace_bytes;
-    return decode_many(rq, stream);
+    if (int rc = latents_request(rs ? "latents_render_rs" : "latents_render_fmt", h, index, m, formatted(roi, fmt, rs),
+                                 out_bitdepth, out_chroma, true, !out_dev || !out_caps || !fmt, rq))
+        return rc;
+    return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ccmi_latents_render_fmt_plan(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
+                                            int out_bitdepth, int out_chroma, const ccmi_tensor_fmt *fmt,
+                                            ccmi_frame_geom *geom, ccmi_roi_info *info, size_t *workspace_bytes)
+{
+    return ccmi_latents_render_rs_plan(h, index, m, roi, out_bitdepth, out_chroma, fmt, nullptr, geom, info,
+                                       workspace_bytes);
+}
+
+extern "C" int ccmi_latents_render_fmt(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
+                                       void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
+                                       int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes,
+                                       void *stream)
+{
+    return ccmi_latents_render_rs(h, index, m, roi, out_dev, out_caps, fmt, nullptr, out_bitdepth, out_chroma, workspace,
+                                  workspace_bytes, stream);
 }
 
 extern "C" int ccmi_decode_last_tail_groups(int *batched, int *per_frame)

@@ -711,138 +711,6 @@ enum { kFmtMirror = 1, kFmtMatrix = 2 }; // per-frame flags (DecOut::bps of a fo
 // groups of 4 destination pixels that cover one row plus the up to 3 lead-in slots
 __host__ __device__ inline int fmt_row_groups(int w) { return (w + 3 + 3) / 4; }
 
-// h x w = the region at (oy, ox) of the synthesis output syn (planes splane apart, pitch spitch;
-// oy, ox even for kind 0)
-template <typename T>
-__device__ __forceinline__ void output_fmt_body(const int32_t *__restrict__ syn, int64_t splane, int spitch, int oy,
-                                                int ox, int h, int w, int maxv, int kind, int flags,
-                                                T *__restrict__ dst, const DecFmtCall &C)
-{
-    const int gpr = fmt_row_groups(w);
-    const int64_t g = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    const int y = (int)(g / gpr);
-    if (y >= h) return;
-    const bool nchw = C.sx == 1, nhwc = !nchw && C.sc == 1 && C.sx == 3;
-    const int64_t row = (int64_t)y * C.sy;
-    // elements from address 0 to (channel 0, y, x' = 0); group k starts mis slots before it, where
-    // the address of its first pixel is a multiple of 4 elements (NHWC: 3 mis == a0 mod 4)
-    const uint64_t a0 = (uint64_t)(reinterpret_cast<uintptr_t>(dst) / sizeof(T)) + (uint64_t)row;
-    const int mis = nchw ? (int)(a0 & 3) : nhwc ? (int)((3 * a0) & 3) : 0;
-    const int d0 = 4 * (int)(g - (int64_t)y * gpr) - mis;
-    if (d0 >= w) return;
-    const float fmax = (float)maxv;
-    auto smp = [maxv, fmax](int32_t v) {
-        int32_t s = (v * maxv + (1 << (kSynPrec - 1))) >> kSynPrec;
-        s = s < 0 ? 0 : (s > maxv ? maxv : s);
-        return __fdiv_rn((float)s, fmax);
-    };
-    const bool mirror = flags & kFmtMirror, matrix = flags & kFmtMatrix;
-    const int32_t *__restrict__ lrow = syn + (int64_t)(oy + y) * spitch + ox;
-    const int32_t *__restrict__ crow = syn + (int64_t)(oy + (kind == 1 ? y : y & ~1)) * spitch + ox;
-    T v[3][4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const int d = d0 + k;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) v[c][k] = fmt_elem<T>(0.f);
-        if (d < 0 || d >= w) continue;
-        const int x = mirror ? w - 1 - d : d, xc = kind == 1 ? x : x & ~1;
-        const float p0 = smp(lrow[x]), p1 = smp(crow[splane + xc]), p2 = smp(crow[2 * splane + xc]);
-        float q[3] = {p0, p1, p2};
-        if (matrix) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float t = fmt_add(fmt_add(fmt_add(p0, fmt_mul(kFmtA[c], p1)), fmt_mul(kFmtB[c], p2)), kFmtO[c]);
-                q[c] = fminf(fmaxf(t, 0.f), 1.f);
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) v[c][k] = fmt_elem<T>(fmt_add(fmt_mul(q[c], C.scale[c]), C.bias[c]));
-    }
-    using Vec = typename FmtVec<T>::type;
-    const bool full = d0 >= 0 && d0 + 4 <= w;
-    if (nchw) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            T *p = dst + c * C.sc + row + d0;
-            if (full && reinterpret_cast<uintptr_t>(p) % sizeof(Vec) == 0) {
-                Vec pk;
-                __builtin_memcpy(&pk, v[c], sizeof pk);
-                *reinterpret_cast<Vec *>(p) = pk;
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (d0 + k >= 0 && d0 + k < w) p[k] = v[c][k];
-            }
-        }
-    } else if (nhwc && full) { // aligned by the choice of mis
-        T e[12];
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) e[3 * k + c] = v[c][k];
-        Vec *p = reinterpret_cast<Vec *>(dst + row + 3 * (int64_t)d0);
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            Vec pk;
-            __builtin_memcpy(&pk, e + 4 * j, sizeof pk);
-            p[j] = pk;
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (d0 + k < 0 || d0 + k >= w) continue;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) dst[c * C.sc + row + (d0 + k) * C.sx] = v[c][k];
-        }
-    }
-}
-
-template <typename T>
-__global__ __launch_bounds__(kThreads) void dec_output_fmt(const int32_t *__restrict__ syn, int H, int W, int oy, int ox,
-                                                           int h, int w, int maxv, int kind, int flags,
-                                                           T *__restrict__ dst, DecFmtCall C)
-{
-    output_fmt_body<T>(syn, (int64_t)H * W, W, oy, ox, h, w, maxv, kind, flags, dst, C);
-}
-
-// a tail group: frame blockIdx.y's compact H x W synthesis output (DecOut::bps = its kFmt* flags)
-template <typename T>
-__global__ __launch_bounds__(kThreads) void dec_output_fmt_batch(const DecOut *__restrict__ Os, DecFmtCall C)
-{
-    const DecOut O = Os[blockIdx.y];
-    output_fmt_body<T>(O.syn, (int64_t)O.H * O.W, O.W, 0, 0, O.H, O.W, O.maxv, O.kind, O.bps, reinterpret_cast<T *>(O.dst),
-                       C);
-}
-
-unsigned output_fmt_blocks(int h, int w)
-{
-    return (unsigned)(((int64_t)h * fmt_row_groups(w) + kThreads - 1) / kThreads);
-}
-
-DecFmtCall fmt_call(const DecFmt &f)
-{
-    DecFmtCall C;
-    for (int c = 0; c < 3; ++c) C.scale[c] = f.scale[c], C.bias[c] = f.bias[c];
-    C.sc = f.stride_c, C.sy = f.stride_y, C.sx = f.stride_x;
-    return C;
-}
-
-int fmt_flags(const DecFmt &f) { return (f.mirror ? kFmtMirror : 0) | (f.matrix ? kFmtMatrix : 0); }
-
-// ------------------------------------------------------------------ resampled formatted output
-// The formatted sink with a ccmi_resample (steps 3a-3c of the contract in ccmi.h): the region,
-// h x w, goes through an antialiased triangle filter to oh x ow between the colour step and
-// scale / bias.  Two launches:
-//   dec_resample_h     thread = (region row y, output column i), three channels: q per tap from
-//                      the synthesis output, t[c][y][i] (float32, [3][h][ow]) to the workspace;
-//   dec_resample_v<T>  thread = (output row, 4 destination pixels), as the formatted output stage:
-//                      the vertical pass over t (loads coalesced along the row), then scale / bias,
-//                      element conversion and the stores of fmt_store.  mirror reads column
-//                      ow - 1 - x'.
-// The three helpers restate output_fmt_body's pixel, group and store steps for the resampling
-// kernels; that body keeps its own copy so that the kernels built from it stay as they are.
-
 // steps 1-3 of the contract for one pixel: lrow / crow point at the pixel's luma row and at the
 // row its chroma is taken from, x / xc are its luma and chroma columns
 __device__ __forceinline__ void fmt_pixel(const int32_t *__restrict__ lrow, const int32_t *__restrict__ crow,
@@ -927,6 +795,80 @@ __device__ __forceinline__ bool fmt_group(const T *dst, const DecFmtCall &C, int
     d0 = 4 * (int)(g - (int64_t)y * gpr) - mis;
     return d0 < w;
 }
+
+// h x w = the region at (oy, ox) of the synthesis output syn (planes splane apart, pitch spitch;
+// oy, ox even for kind 0)
+template <typename T>
+__device__ __forceinline__ void output_fmt_body(const int32_t *__restrict__ syn, int64_t splane, int spitch, int oy,
+                                                int ox, int h, int w, int maxv, int kind, int flags,
+                                                T *__restrict__ dst, const DecFmtCall &C)
+{
+    int y, d0;
+    int64_t row;
+    bool nchw, nhwc;
+    if (!fmt_group<T>(dst, C, h, w, y, d0, row, nchw, nhwc)) return;
+    const float fmax = (float)maxv;
+    const bool mirror = flags & kFmtMirror, matrix = flags & kFmtMatrix;
+    const int32_t *__restrict__ lrow = syn + (int64_t)(oy + y) * spitch + ox;
+    const int32_t *__restrict__ crow = syn + (int64_t)(oy + (kind == 1 ? y : y & ~1)) * spitch + ox;
+    T v[3][4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int d = d0 + k;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c][k] = fmt_elem<T>(0.f);
+        if (d < 0 || d >= w) continue;
+        const int x = mirror ? w - 1 - d : d;
+        float q[3];
+        fmt_pixel(lrow, crow, splane, x, kind == 1 ? x : x & ~1, maxv, fmax, matrix, q);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c][k] = fmt_elem<T>(fmt_add(fmt_mul(q[c], C.scale[c]), C.bias[c]));
+    }
+    fmt_store<T>(v, dst, C, row, d0, w, nchw, nhwc);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_output_fmt(const int32_t *__restrict__ syn, int H, int W, int oy, int ox,
+                                                           int h, int w, int maxv, int kind, int flags,
+                                                           T *__restrict__ dst, DecFmtCall C)
+{
+    output_fmt_body<T>(syn, (int64_t)H * W, W, oy, ox, h, w, maxv, kind, flags, dst, C);
+}
+
+// a tail group: frame blockIdx.y's compact H x W synthesis output (DecOut::bps = its kFmt* flags)
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_output_fmt_batch(const DecOut *__restrict__ Os, DecFmtCall C)
+{
+    const DecOut O = Os[blockIdx.y];
+    output_fmt_body<T>(O.syn, (int64_t)O.H * O.W, O.W, 0, 0, O.H, O.W, O.maxv, O.kind, O.bps, reinterpret_cast<T *>(O.dst),
+                       C);
+}
+
+unsigned output_fmt_blocks(int h, int w)
+{
+    return (unsigned)(((int64_t)h * fmt_row_groups(w) + kThreads - 1) / kThreads);
+}
+
+DecFmtCall fmt_call(const DecFmt &f)
+{
+    DecFmtCall C;
+    for (int c = 0; c < 3; ++c) C.scale[c] = f.scale[c], C.bias[c] = f.bias[c];
+    C.sc = f.stride_c, C.sy = f.stride_y, C.sx = f.stride_x;
+    return C;
+}
+
+int fmt_flags(const DecFmt &f) { return (f.mirror ? kFmtMirror : 0) | (f.matrix ? kFmtMatrix : 0); }
+
+// ------------------------------------------------------------------ resampled formatted output
+// The formatted sink with a ccmi_resample (steps 3a-3c of the contract in ccmi.h): the region,
+// h x w, goes through an antialiased triangle filter to oh x ow between the colour step and
+// scale / bias.  Two launches:
+//   dec_resample_h     thread = (region row y, output column i), three channels: q per tap from
+//                      the synthesis output, t[c][y][i] (float32, [3][h][ow]) to the workspace;
+//   dec_resample_v<T>  thread = (output row, 4 destination pixels), as the formatted output stage:
+//                      the vertical pass over t (loads coalesced along the row), then scale / bias,
+//                      element conversion and the stores of fmt_store.  mirror reads column
+//                      ow - 1 - x'.
 
 // The weights are recomputed per thread from integers: RsTaps holds the run j0 .. j1 of output
 // index i and what u(i, j) = 2D - |(2j + 1) O - (2i + 1) I| needs; everything fits int32 for
@@ -1372,12 +1314,22 @@ int launch_dec_output_tensor(const int32_t *syn, int h, int w, int bitdepth, int
     });
 }
 
-int launch_dec_output_tensor_roi(const int32_t *syn, int h, int w, const DecWindow &rect, int bitdepth, int kind,
-                                 int sample, void *dst, hipStream_t s)
+// what the cropping launchers ask of a region of an h x w frame: a known kind, inside the frame, not
+// empty and, where the kernel reads 420 chroma at the even row and column, an even origin
+static int check_region(const DecWindow &rect, int h, int w, int kind, bool even_origin)
 {
     if (kind != 0 && kind != 1) return ccmi_set_error(CCMI_ERR_ARG, "dec: tensor output kind %d", kind);
     if (rect.y0 < 0 || rect.x0 < 0 || rect.y1 > h || rect.x1 > w || rect.h() < 1 || rect.w() < 1)
         return ccmi_set_error(CCMI_ERR_ARG, "dec: region outside the frame");
+    if (even_origin && kind == 0 && ((rect.y0 | rect.x0) & 1))
+        return ccmi_set_error(CCMI_ERR_ARG, "dec: a 420 region needs an even origin");
+    return CCMI_OK;
+}
+
+int launch_dec_output_tensor_roi(const int32_t *syn, int h, int w, const DecWindow &rect, int bitdepth, int kind,
+                                 int sample, void *dst, hipStream_t s)
+{
+    if (int rc = check_region(rect, h, w, kind, false)) return rc;
     const dim3 grid(output_tensor_blocks(rect.h(), rect.w(), kind));
     const int maxv = (1 << bitdepth) - 1;
     return with_sample_type(sample, [&](auto t) {
@@ -1390,10 +1342,7 @@ int launch_dec_output_tensor_roi(const int32_t *syn, int h, int w, const DecWind
 int launch_dec_output_fmt(const int32_t *syn, int h, int w, const DecWindow &rect, int bitdepth, int kind,
                           const DecFmt &fmt, void *dst, hipStream_t s)
 {
-    if (kind != 0 && kind != 1) return ccmi_set_error(CCMI_ERR_ARG, "dec: tensor output kind %d", kind);
-    if (rect.y0 < 0 || rect.x0 < 0 || rect.y1 > h || rect.x1 > w || rect.h() < 1 || rect.w() < 1)
-        return ccmi_set_error(CCMI_ERR_ARG, "dec: region outside the frame");
-    if (kind == 0 && ((rect.y0 | rect.x0) & 1)) return ccmi_set_error(CCMI_ERR_ARG, "dec: a 420 region needs an even origin");
+    if (int rc = check_region(rect, h, w, kind, true)) return rc;
     const dim3 grid(output_fmt_blocks(rect.h(), rect.w()));
     const int maxv = (1 << bitdepth) - 1;
     return with_elem_type(fmt.elem, [&](auto t) {
@@ -1408,10 +1357,7 @@ size_t dec_resample_tmp_elems(int region_h, int out_w) { return 3 * (size_t)regi
 int launch_dec_resample(const int32_t *syn, int h, int w, const DecWindow &rect, int bitdepth, int kind,
                         const DecFmt &fmt, float *tmp, void *dst, hipStream_t s)
 {
-    if (kind != 0 && kind != 1) return ccmi_set_error(CCMI_ERR_ARG, "dec: tensor output kind %d", kind);
-    if (rect.y0 < 0 || rect.x0 < 0 || rect.y1 > h || rect.x1 > w || rect.h() < 1 || rect.w() < 1)
-        return ccmi_set_error(CCMI_ERR_ARG, "dec: region outside the frame");
-    if (kind == 0 && ((rect.y0 | rect.x0) & 1)) return ccmi_set_error(CCMI_ERR_ARG, "dec: a 420 region needs an even origin");
+    if (int rc = check_region(rect, h, w, kind, true)) return rc;
     if (!fmt.rs || fmt.out_h < 1 || fmt.out_w < 1 || !tmp) return ccmi_set_error(CCMI_ERR_ARG, "dec: resample without a size");
     const int maxv = (1 << bitdepth) - 1;
     hipLaunchKernelGGL(dec_resample_h, dim3(resample_h_blocks(rect.h(), fmt.out_w)), dim3(kThreads), 0, s, syn, h, w,

@@ -4,47 +4,17 @@ built libccmi.so in the form of tests/test_decode_fmt_resources.py (no GPU neede
 stage keeps 4 pixels x 3 channels of accumulators per thread in registers; no kernel may use
 scratch or spill."""
 import re
-import shutil
-import subprocess
-from pathlib import Path
 
-import pytest
+from kernel_meta import LIB, metadata
 
-ROOT = Path(__file__).resolve().parents[1]
-LIB = ROOT / "cool-chic_amd" / "lib" / "libccmi.so"
-LLVM = Path("/opt/rocm/lib/llvm/bin")
 PLAIN = ("dec_resample_h(", "dec_resample_h_batch(")
 TYPED = ("dec_resample_v<", "dec_resample_v_batch<")
 TYPES = ("float", "F16", "Bf16")
 MAX_VGPRS = 64  # 8 waves per SIMD
 
 
-def _metadata(tmp_path):
-    objdump, readelf = LLVM / "llvm-objdump", LLVM / "llvm-readelf"
-    if not (LIB.exists() and objdump.exists() and readelf.exists()):
-        pytest.skip("libccmi.so or the ROCm llvm tools are absent")
-    lib = tmp_path / "libccmi.so"
-    shutil.copy(LIB, lib)
-    subprocess.run([str(objdump), "--offloading", str(lib)], cwd=tmp_path, check=True, capture_output=True)
-    text = "".join(subprocess.run([str(readelf), "--notes", str(f)], capture_output=True, text=True).stdout
-                   for f in sorted(tmp_path.glob("libccmi.so.*gfx950")))
-    out, name = {}, None
-    for line in text.splitlines():
-        m = re.match(r"\s+\.name:\s+(\S+)", line)
-        if m:
-            name = m.group(1)
-            out[name] = {}
-            continue
-        m = re.match(r"\s+\.(vgpr_count|vgpr_spill_count|sgpr_spill_count|private_segment_fixed_size):\s+(\d+)", line)
-        if m and name:
-            out[name][m.group(1)] = int(m.group(2))
-    names = list(out)
-    dem = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.splitlines()
-    return {d: out[n] for n, d in zip(names, dem)}
-
-
 def test_resampling_kernels_use_no_scratch(tmp_path):
-    meta = _metadata(tmp_path)
+    meta = metadata(LIB, tmp_path)
     wanted = [(form, None) for form in PLAIN] + [(form, t) for form in TYPED for t in TYPES]
     lines = []
     for form, t in wanted:

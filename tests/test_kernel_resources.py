@@ -4,16 +4,7 @@ crossing a VGPR step halves or thirds the waves a SIMD can hold (512 VGPRs per l
 <= 128 -> 4 waves, <= 168 -> 3, <= 256 -> 2), which the bench only shows at round end.
 Round 2 lost 30 % of the headline this way (an opt-in MFMA head compiled into the default
 fused kernel took it from 108 to 133 VGPRs)."""
-import re
-import shutil
-import subprocess
-from pathlib import Path
-
-import pytest
-
-ROOT = Path(__file__).resolve().parents[1]
-LIB = ROOT / "cool-chic_amd" / "lib" / "libccmi.so"
-LLVM = Path("/opt/rocm/lib/llvm/bin")
+from kernel_meta import LIB, metadata
 
 # demangled-name prefix -> (max VGPRs, max VGPR spills, scratch bytes allowed)
 BUDGET = {
@@ -60,32 +51,8 @@ BUDGET = {
 }
 
 
-def _metadata(tmp_path):
-    objdump, readelf = LLVM / "llvm-objdump", LLVM / "llvm-readelf"
-    if not (LIB.exists() and objdump.exists() and readelf.exists()):
-        pytest.skip("libccmi.so or the ROCm llvm tools are absent")
-    lib = tmp_path / "libccmi.so"
-    shutil.copy(LIB, lib)
-    subprocess.run([str(objdump), "--offloading", str(lib)], cwd=tmp_path, check=True, capture_output=True)
-    text = "".join(subprocess.run([str(readelf), "--notes", str(f)], capture_output=True, text=True).stdout
-                   for f in sorted(tmp_path.glob("libccmi.so.*gfx950")))
-    out, name = {}, None
-    for line in text.splitlines():
-        m = re.match(r"\s+\.name:\s+(\S+)", line)
-        if m:
-            name = m.group(1)
-            out[name] = {}
-            continue
-        m = re.match(r"\s+\.(vgpr_count|vgpr_spill_count|private_segment_fixed_size):\s+(\d+)", line)
-        if m and name:
-            out[name][m.group(1)] = int(m.group(2))
-    names = list(out)
-    dem = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.splitlines()
-    return {d: out[n] for n, d in zip(names, dem)}
-
-
 def test_hot_kernel_register_budgets(tmp_path):
-    meta = _metadata(tmp_path)
+    meta = metadata(LIB, tmp_path)
     assert len(meta) > 50
     lines = []
     for key, (vmax, spills, scratch) in BUDGET.items():

@@ -72,7 +72,7 @@ def run_set(cls, copies, reps, warmup):
     desc = encode.parse(streams[0]).desc
     H, W, n = desc.h, desc.w, len(streams)
     rois = _rois(n, H, W)
-    L = decode._bind_latents()
+    L = decode._bind()
     keep, sp, ln = decode._marshal(streams)
     planned = {}
     for name, t in (("int8", decode.LATENT_I8), ("int16", decode.LATENT_I16)):

@@ -48,7 +48,7 @@ def _stat(v):
 
 def store_sizes(streams):
     """Header-only: bytes of the store at each element type, and the build workspace."""
-    L = decode._bind_latents()
+    L = decode._bind()
     keep, sp, ln = decode._marshal(streams)
     out = {}
     for name, t in (("int8", 0), ("int16", 1), ("int32", 2)):

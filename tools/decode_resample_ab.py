@@ -19,7 +19,8 @@ follows the contract's float32 order, torch's interpolate its own, so they diffe
 
 --mode regress: the unchanged call, store.render_model(256 x 256 regions, no size), through the
 C ABI of two libraries in one process, alternating: --parent (a libccmi.so built from the parent
-commit) and the tree's own.  Each library builds its own store and workspace.  The rule is that of
+commit) and the tree's own, in the element type of --dtype (bfloat16, float32 or float16).  Each
+library builds its own store and workspace.  The rule is that of
 profiles/decode_split_ab.txt, per run of this tool: reference = the lowest of the parent's
 per-block medians, allowance = their spread; the new library's median of block medians must not
 exceed reference + allowance.  The repetitions are split into three blocks per library for this.
@@ -150,7 +151,7 @@ class Geom(C.Structure):
 class RawStore:
     """A latent store and the unchanged formatted render through the C ABI of one libccmi.so."""
 
-    def __init__(self, path, streams, rects):
+    def __init__(self, path, streams, rects, dtype):
         P, I, Z = C.c_void_p, C.c_int, C.c_size_t
         self.L = L = C.CDLL(str(path))
         L.ccmi_last_error.restype = C.c_char_p
@@ -172,15 +173,16 @@ class RawStore:
                                       ws.numel(), self.stream, C.byref(self.h)))
         del ws
         self.rects = (decode.Rect * n)(*[decode.Rect(*r) for r in rects])
-        self.fmt = decode.TensorFmt(elem=decode.ELEM_BF16, colour=decode.COLOUR_RGB)
+        elem = {torch.bfloat16: decode.ELEM_BF16, torch.float32: decode.ELEM_F32, torch.float16: decode.ELEM_F16}[dtype]
+        self.fmt = decode.TensorFmt(elem=elem, colour=decode.COLOUR_RGB)
         for c in range(3):
             self.fmt.scale[c], self.fmt.bias[c] = 1.0 / STD[c], -MEAN[c] / STD[c]
         geom, need = (Geom * n)(), C.c_size_t(0)
         self.ok(L.ccmi_latents_render_fmt_plan(self.h, None, n, self.rects, 0, 0, C.byref(self.fmt), geom, None, C.byref(need)))
         self.ws = torch.empty(max(need.value, 256), dtype=torch.uint8, device="cuda")
-        self.out = torch.empty(n, 3, SIDE, SIDE, dtype=torch.bfloat16, device="cuda")
+        self.out = torch.empty(n, 3, SIDE, SIDE, dtype=dtype, device="cuda")
         self.op = (C.c_void_p * n)(*[self.out[i].data_ptr() for i in range(n)])
-        self.cap = (C.c_size_t * n)(*[3 * SIDE * SIDE * 2] * n)
+        self.cap = (C.c_size_t * n)(*[3 * SIDE * SIDE * self.out.element_size()] * n)
 
     def ok(self, rc):
         if rc:
@@ -202,7 +204,8 @@ def mode_regress(a, streams):
     rects = [(2 * int(rng.integers(0, (W - SIDE) // 2 + 1)), 2 * int(rng.integers(0, (H - SIDE) // 2 + 1)), SIDE, SIDE)
              for _ in range(n)]
     import ccmi
-    libs = {"parent": RawStore(a.parent, streams, rects), "new": RawStore(ccmi.LIB_PATH, streams, rects)}
+    dtype = getattr(torch, a.dtype)
+    libs = {"parent": RawStore(a.parent, streams, rects, dtype), "new": RawStore(ccmi.LIB_PATH, streams, rects, dtype)}
     blocks = 3
     reps = blocks * a.reps
     rec = {k: [] for k in libs}
@@ -214,13 +217,14 @@ def mode_regress(a, streams):
             torch.cuda.synchronize()
             if it >= a.warmup:
                 rec[k].append(1e3 * (time.perf_counter() - t0))
-    same = bool((libs["parent"].out.view(torch.int16) == libs["new"].out.view(torch.int16)).all())
+    bits = torch.int32 if dtype == torch.float32 else torch.int16
+    same = bool((libs["parent"].out.view(bits) == libs["new"].out.view(bits)).all())
     med = {k: [statistics.median(v[b * a.reps:(b + 1) * a.reps]) for b in range(blocks)] for k, v in rec.items()}
     ref, spread = min(med["parent"]), max(med["parent"]) - min(med["parent"])
     new = statistics.median(med["new"])
     lines = ["regression check: the unchanged render_model (no size), parent library against this tree's, one process, alternating",
              f"device: {torch.cuda.get_device_name(0)}; {n} class-E frames, {SIDE}x{SIDE} regions at random even origins, RGB, "
-             f"ImageNet mean / std, bf16, NCHW; {blocks} blocks of {a.reps} alternating repetitions after {a.warmup} warm-up rounds; "
+             f"ImageNet mean / std, {a.dtype}, NCHW; {blocks} blocks of {a.reps} alternating repetitions after {a.warmup} warm-up rounds; "
              "wall ms per call",
              "  parent block medians " + ", ".join(f"{v:.3f}" for v in med["parent"]) + f"  (reference {ref:.3f}, spread {spread:.3f})",
              "  new block medians    " + ", ".join(f"{v:.3f}" for v in med["new"]) +
@@ -236,6 +240,8 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--mode", choices=("resample", "regress"), default="resample")
     ap.add_argument("--parent", default="", help="--mode regress: a libccmi.so built from the parent commit")
+    ap.add_argument("--dtype", choices=("bfloat16", "float32", "float16"), default="bfloat16",
+                    help="--mode regress: the element type of the rendered tensor")
     ap.add_argument("--copies", type=int, default=64)
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=2)
