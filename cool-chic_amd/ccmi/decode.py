@@ -41,6 +41,10 @@ _PROTOS = {
     "ccmi_decode_batch_dev_rs_plan": [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P],
     "ccmi_decode_batch_dev_rs": [_P, _P, _I, _P, _P, _P, _P, _P, _I, _I, _P, _Z, _P],
     "ccmi_decode_last_tail_groups": [_P, _P],
+    "ccmi_decode_batch_dev_warp_plan": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P],
+    "ccmi_decode_batch_dev_warp": [_P, _P, _I, _P, _P, _P, _P, _I, _I, _P, _Z, _P],
+    "ccmi_latents_render_warp_plan": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P],
+    "ccmi_latents_render_warp": [_P, _P, _I, _P, _P, _P, _P, _I, _I, _P, _Z, _P],
     "ccmi_latents_plan": [_P, _P, _I, _I, _P, _P, _P],
     "ccmi_latents_decode": [_P, _P, _I, _I, _P, _Z, _P, _Z, _P, _P],
     "ccmi_latents_free": [_P],
@@ -382,6 +386,62 @@ def _resample(size):
     return Resample(out_w=int(size[1]), out_h=int(size[0]), filter=FILTER_TRIANGLE)
 
 
+PAD_FILL, PAD_EDGE = 0, 1  # CCMI_PAD_*
+
+
+class Warp(C.Structure):
+    """ccmi_warp: the output size, the padding and the per-frame matrices of a warping call."""
+    _fields_ = [("out_w", C.c_int), ("out_h", C.c_int), ("pad", C.c_int), ("fill", C.c_float * 3),
+                ("matrix", C.c_void_p)]
+
+
+def _warp(affine, n, size, roi, pad, fill):
+    """affine= / pad= / fill= of a *_model call -> (ccmi_warp, what it points to), or (None, None)
+    without affine.  The library checks the values; the shapes are checked here."""
+    import numpy as np
+    if affine is None:
+        return None, None
+    if size is None:
+        raise ValueError("model output: affine needs size=(out_h, out_w)")
+    if roi is not None:
+        raise ValueError("model output: affine excludes roi (the matrix says where the output lies in the frame)")
+    if len(size) != 2:
+        raise ValueError(f"model output: size takes (out_h, out_w), got {size!r}")
+    pads = {"fill": PAD_FILL, "edge": PAD_EDGE}
+    if pad not in pads:
+        raise ValueError(f"model output: pad {pad!r} ('fill' or 'edge')")
+    a = affine.detach().cpu().numpy() if hasattr(affine, "detach") else np.asarray(affine)
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.shape == (2, 3):
+        a = np.ascontiguousarray(np.broadcast_to(a, (n, 2, 3)))
+    if a.shape != (n, 2, 3):
+        raise ValueError(f"model output: affine takes [{n}, 2, 3] or one [2, 3], got {list(a.shape)}")
+    f = [float(v) for v in fill] if hasattr(fill, "__len__") else [float(fill)] * 3
+    if len(f) != 3:
+        raise ValueError("model output: fill takes one value, or one per channel")
+    w = Warp(out_w=int(size[1]), out_h=int(size[0]), pad=pads[pad], matrix=a.ctypes.data)
+    for c in range(3):
+        w.fill[c] = f[c]
+    return w, a
+
+
+def affine_matrix(size, centre, angle: float = 0.0, scale: float = 1.0, flip: bool = False):
+    """The [2, 3] float32 matrix (affine= of the *_model calls) of a rotated, scaled and optionally
+    flipped view: the size = (out_h, out_w) output is centred on centre = (cx, cy) of the frame
+    (pixels; pixel (y, x) covers [x, x + 1) x [y, y + 1)), turned by `angle` radians and showing
+    out / scale frame pixels a side.  For output row i, column k:
+        dx = k + 0.5 - out_w / 2, negated if flip;   dy = i + 0.5 - out_h / 2;
+        xs = cx + (cos(angle) dx - sin(angle) dy) / scale;
+        ys = cy + (sin(angle) dx + cos(angle) dy) / scale."""
+    import math
+    import numpy as np
+    oh, ow = size
+    cx, cy = centre
+    c, s, f = math.cos(angle), math.sin(angle), -1.0 if flip else 1.0
+    return np.array([[f * c / scale, -s / scale, cx + (-f * c * ow / 2 + s * oh / 2) / scale],
+                     [f * s / scale, c / scale, cy + (-f * s * ow / 2 - c * oh / 2) / scale]], dtype=np.float32)
+
+
 def last_tail_groups() -> tuple:
     """(batched tail groups, per-frame tails) this thread's last decode or render call launched
     (ccmi_decode_last_tail_groups): frames that share a group share one launch per tail stage."""
@@ -459,36 +519,49 @@ def _model_outs(geom, fmt, dtype, channels_last, out, dev):
     return res, op, cap, frames
 
 
-def _plan_model(plan, head, n, rects, fmt, rs, output_bitdepth, output_chroma_format):
+def _plan_model(plan, head, n, rects, fmt, rs, output_bitdepth, output_chroma_format, warp=None, info=None,
+                window=None):
     """(ccmi_frame_geom array, workspace bytes) of a formatted call: plan is the source's *_rs_plan
-    entry point (rs None: exactly the *_fmt_plan call), head its first two arguments."""
+    entry point (rs None: exactly the *_fmt_plan call), head its first two arguments.  With warp
+    (a ccmi_warp) plan is the *_warp_plan entry point, which takes no regions; info / window: its
+    optional per-frame outputs."""
     geom, need = (FrameGeom * n)(), C.c_size_t(0)
     probe = TensorFmt.from_buffer_copy(fmt)  # planar strides: the geometry does not depend on them
-    check(plan(*head, n, rects, output_bitdepth, output_chroma_format, C.byref(probe), rs, geom, None, C.byref(need)))
+    if warp is not None:
+        check(plan(*head, n, output_bitdepth, output_chroma_format, C.byref(probe), C.byref(warp), geom, info, window,
+                   C.byref(need)))
+    else:
+        check(plan(*head, n, rects, output_bitdepth, output_chroma_format, C.byref(probe), rs, geom, info, C.byref(need)))
     return geom, need.value
 
 
 def _run_model(plan, run, head, n, rects, dev, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth,
-               output_chroma_format, workspace, stream_handle, size):
+               output_chroma_format, workspace, stream_handle, size, warp=None):
     """The body of decode_batch_model and LatentStore.render_model: plan / run are the source's
-    *_rs_plan / *_rs entry points, head their first two arguments; dev None: the current device."""
+    *_rs_plan / *_rs entry points, or with warp (a ccmi_warp, which carries the size) its
+    *_warp_plan / *_warp ones; head their first two arguments; dev None: the current device."""
     import torch
     dtype = torch.float32 if dtype is None else dtype
     fmt, keep = _model_fmt(n, colour, mean, std, dtype, mirror)
-    rs = None if size is None else C.byref(_resample(size))
-    geom, need = _plan_model(plan, head, n, rects, fmt, rs, output_bitdepth, output_chroma_format)
+    rs = None if size is None or warp is not None else C.byref(_resample(size))
+    geom, need = _plan_model(plan, head, n, rects, fmt, rs, output_bitdepth, output_chroma_format, warp)
     dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else dev
     res, op, cap, frames = _model_outs(geom, fmt, dtype, channels_last, out, dev)
     stream_handle, workspace = _stream_ws(dev, stream_handle, workspace, need)
-    check(run(*head, n, rects, op, cap, C.byref(fmt), rs, output_bitdepth, output_chroma_format,
-              workspace.data_ptr(), workspace.numel(), stream_handle))
+    if warp is not None:
+        check(run(*head, n, op, cap, C.byref(fmt), C.byref(warp), output_bitdepth, output_chroma_format,
+                  workspace.data_ptr(), workspace.numel(), stream_handle))
+    else:
+        check(run(*head, n, rects, op, cap, C.byref(fmt), rs, output_bitdepth, output_chroma_format,
+                  workspace.data_ptr(), workspace.numel(), stream_handle))
     del keep, frames
     return res
 
 
 def decode_batch_model(streams: Sequence[bytes], roi=None, colour: str = "rgb", mean=None, std=None, dtype=None,
                        channels_last: bool = False, mirror=None, out=None, output_bitdepth: int = 0,
-                       output_chroma_format: int = 0, workspace=None, stream_handle: int | None = None, size=None):
+                       output_chroma_format: int = 0, workspace=None, stream_handle: int | None = None, size=None,
+                       affine=None, pad: str = "fill", fill=0.0):
     """Decode .cool streams into the tensor a model takes (ccmi_decode_batch_dev_fmt): one
     [n, 3, h, w] tensor of `dtype` (torch.float32, the default, torch.float16 or torch.bfloat16),
     every channel at full size (420 chroma nearest-upsampled), RGB (colour="rgb": YUV streams go
@@ -508,10 +581,25 @@ def decode_batch_model(streams: Sequence[bytes], roi=None, colour: str = "rgb", 
     that size by the antialiased triangle filter of interpolate(mode="bilinear", antialias=True)
     between the colour step and the normalisation, in the same output stage (the contract's
     steps 3a-3c); h, w above are then out_h, out_w, the regions may differ in size, and frames
-    of one architecture share their launches whatever their regions (last_tail_groups())."""
+    of one architecture share their launches whatever their regions (last_tail_groups()).
+
+    affine= (ccmi_decode_batch_dev_warp; needs size, excludes roi): [n, 2, 3], or one [2, 3] for
+    every frame, as an array, a nested list or a CPU tensor (affine_matrix() makes one).  Every
+    output pixel (i, k) is a bilinear sample of the whole frame at xs = m00 (k + 0.5) +
+    m01 (i + 0.5) + m02, ys = m10 (k + 0.5) + m11 (i + 0.5) + m12 (pixels; grid_sample with
+    align_corners=False, not antialiased), between the colour step and the normalisation: rotation,
+    scale, shear and translation in the same output stage.  pad="fill": a tap outside the frame is
+    `fill` (one value or one per channel, in [0, 1] colour units, before the normalisation);
+    pad="edge": the nearest frame pixel.  The library decodes only the window of each frame its
+    matrix reaches."""
     n = len(streams)
     keep, sp, ln = _marshal(streams)
     L = _bind()
+    warp, keep_w = _warp(affine, n, size, roi, pad, fill)
+    if warp is not None:
+        return _run_model(L.ccmi_decode_batch_dev_warp_plan, L.ccmi_decode_batch_dev_warp, (sp, ln), n, None, None,
+                          colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth, output_chroma_format,
+                          workspace, stream_handle, size, warp)
     return _run_model(L.ccmi_decode_batch_dev_rs_plan, L.ccmi_decode_batch_dev_rs, (sp, ln), n, _rects(roi, streams, n),
                       None, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth, output_chroma_format,
                       workspace, stream_handle, size)
@@ -805,26 +893,56 @@ class LatentStore:
 
     def render_model(self, index=None, roi=None, colour: str = "rgb", mean=None, std=None, dtype=None,
                      channels_last: bool = False, mirror=None, out=None, output_bitdepth: int = 0,
-                     output_chroma_format: int = 0, workspace=None, stream_handle: int | None = None, size=None):
+                     output_chroma_format: int = 0, workspace=None, stream_handle: int | None = None, size=None,
+                     affine=None, pad: str = "fill", fill=0.0):
         """render() into the tensor a model takes (ccmi_latents_render_fmt; with size
-        ccmi_latents_render_rs): frames and regions as for render(), the result and every other
-        argument as for decode_batch_model, whose output for the same streams and arguments it
-        equals bit for bit.  workspace with a size: at least what render_model_workspace_bytes()
-        reports (the resample's intermediate is not part of render_geometry()'s figure)."""
-        m, idx, rects = self._frames(index, roi)
+        ccmi_latents_render_rs; with affine ccmi_latents_render_warp): frames and regions as for
+        render(), the result and every other argument as for decode_batch_model, whose output for
+        the same streams and arguments it equals bit for bit.  workspace with a size or an affine:
+        at least what render_model_workspace_bytes() reports (the resample's intermediate and a
+        warp's windows are not part of render_geometry()'s figure)."""
+        m, idx, rects = self._frames(index, None if affine is not None else roi)
         L = _bind()
+        warp, keep_w = _warp(affine, m, size, roi, pad, fill)
+        if warp is not None:
+            return _run_model(L.ccmi_latents_render_warp_plan, L.ccmi_latents_render_warp, (self._handle(), idx), m,
+                              None, self._store.device, colour, mean, std, dtype, channels_last, mirror, out,
+                              output_bitdepth, output_chroma_format, workspace, stream_handle, size, warp)
         return _run_model(L.ccmi_latents_render_rs_plan, L.ccmi_latents_render_rs, (self._handle(), idx), m, rects,
                           self._store.device, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth,
                           output_chroma_format, workspace, stream_handle, size)
 
-    def render_model_workspace_bytes(self, index=None, roi=None, size=None, output_bitdepth: int = 0,
-                                     output_chroma_format: int = 0) -> int:
-        """Header-only: the workspace render_model needs for these frames, regions and size
-        (ccmi_latents_render_rs_plan; the element type, colour and strides do not change it)."""
-        m, idx, rects = self._frames(index, roi)
+    def warp_plan(self, index, affine, size, pad: str = "fill", fill=0.0, output_bitdepth: int = 0,
+                  output_chroma_format: int = 0) -> list:
+        """What render_model(affine=...) will do, per output frame (ccmi_latents_render_warp_plan,
+        header-only), like roi_plan: {'window': (x, y, w, h), the rectangle of the frame the tail
+        renders for that frame's matrix, 'windowed', 'arm_rows'}."""
+        m, idx, _ = self._frames(index, None)
+        warp, keep_w = _warp(affine, m, size, None, pad, fill)
+        if warp is None:
+            raise ValueError("LatentStore.warp_plan: affine is None")
         fmt = TensorFmt(elem=ELEM_F32, colour=COLOUR_ASIS)
         for c in range(3):
             fmt.scale[c] = 1.0
+        info, window = (RoiInfo * m)(), (Rect * m)()
+        _plan_model(_bind().ccmi_latents_render_warp_plan, (self._handle(), idx), m, None, fmt, None, output_bitdepth,
+                    output_chroma_format, warp, info, window)
+        return [{"window": (r.x, r.y, r.w, r.h), "windowed": bool(i.windowed),
+                 "arm_rows": [int(v) for v in i.arm_rows[: i.n_grids]]} for i, r in zip(info, window)]
+
+    def render_model_workspace_bytes(self, index=None, roi=None, size=None, output_bitdepth: int = 0,
+                                     output_chroma_format: int = 0, affine=None, pad: str = "fill", fill=0.0) -> int:
+        """Header-only: the workspace render_model needs for these frames, regions and size, or
+        these frames, matrices and size (ccmi_latents_render_rs_plan / _warp_plan; the element type,
+        colour and strides do not change it)."""
+        m, idx, rects = self._frames(index, None if affine is not None else roi)
+        fmt = TensorFmt(elem=ELEM_F32, colour=COLOUR_ASIS)
+        for c in range(3):
+            fmt.scale[c] = 1.0
+        warp, keep_w = _warp(affine, m, size, roi, pad, fill)
+        if warp is not None:
+            return _plan_model(_bind().ccmi_latents_render_warp_plan, (self._handle(), idx), m, None, fmt, None,
+                               output_bitdepth, output_chroma_format, warp)[1]
         rs = None if size is None else C.byref(_resample(size))
         return _plan_model(_bind().ccmi_latents_render_rs_plan, (self._handle(), idx), m, rects, fmt, rs, output_bitdepth,
                            output_chroma_format)[1]
@@ -850,4 +968,5 @@ class LatentStore:
 
 __all__ = ["last_timing", "LatentStore", "last_arm_flags", "decode_latents", "decode_file", "decode_batch", "decode_batch_workspace_bytes", "output_size",
            "decode_batch_tensors", "decode_batch_geometry", "roi_plan", "decode_batch_model", "last_tail_groups",
+           "affine_matrix",
            "weights_i32", "ups_forward_i32", "syn_forward_i32", "CcmiError"]

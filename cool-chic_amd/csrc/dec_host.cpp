@@ -536,7 +536,7 @@ int build_tail_groups(Run &r)
         const int m = (int)g.frames.size();
         g.off = tpos;
         dec_tail_fill(g.frames.data(), m, r.tab.data() + tpos);
-        tpos += dec_tail_table_bytes(g.frames[0]->ups.n_layers, m, g.frames[0]->windowed, g.frames[0]->fmt.rs != 0);
+        tpos += dec_tail_table_bytes(g.frames[0]->ups.n_layers, m, g.frames[0]->windowed, dec_out_form(g.frames[0]->fmt));
     }
     r.tab_used = tpos;
     return CCMI_OK;
@@ -648,6 +648,8 @@ int launch_frame_tail(const Run &r, const FramePlan &p, hipStream_t cs)
                                           b == 1, cs))
                 return rc;
     }
+    if (t.fmt.warp) // the whole frame is decoded: the kernel samples it where the matrix points
+        return launch_dec_warp(synout, f.h, f.w, t.bitdepth, t.kind, t.fmt, t.dst, cs);
     if (t.fmt.rs)
         return launch_dec_resample(synout, f.h, f.w, t.roi.rect, t.bitdepth, t.kind, t.fmt, t.rs_tmp, t.dst, cs);
     if (t.fmt.on) // roi.rect: the region, or the whole frame
@@ -1007,9 +1009,10 @@ extern "C" int ccmi_decode_batch_ws(const uint8_t *const *streams, const size_t 
 }
 
 // ------------------------------------------------------------------ device sinks
-// Sixteen entry points over one table: the source is the caller's streams or a latent store, the
+// Twenty entry points over one table: the source is the caller's streams or a latent store, the
 // sink plain samples (sample_type; with or without a region) or formatted ones (fmt, forced to
-// CCMI_SAMPLE_F32, the call whose output kernel the format replaces; with or without a resample),
+// CCMI_SAMPLE_F32, the call whose output kernel the format replaces; with or without a resample,
+// or with a warp, which takes no region),
 // and each comes as a plan and as a run.  `who` is the entry point's name for the error text,
 // `missing` its own null-argument check beyond the source's.
 struct Sink {
@@ -1017,13 +1020,19 @@ struct Sink {
     int sample;
     const ccmi_tensor_fmt *fmt;
     const ccmi_resample *rs;
+    const ccmi_warp *warp;
 };
 
-static Sink samples(const ccmi_rect *roi, int sample_type) { return Sink{roi, sample_type, nullptr, nullptr}; }
+static Sink samples(const ccmi_rect *roi, int sample_type) { return Sink{roi, sample_type, nullptr, nullptr, nullptr}; }
 
 static Sink formatted(const ccmi_rect *roi, const ccmi_tensor_fmt *fmt, const ccmi_resample *rs)
 {
-    return Sink{roi, CCMI_SAMPLE_F32, fmt, rs};
+    return Sink{roi, CCMI_SAMPLE_F32, fmt, rs, nullptr};
+}
+
+static Sink warped(const ccmi_tensor_fmt *fmt, const ccmi_warp *warp)
+{
+    return Sink{nullptr, CCMI_SAMPLE_F32, fmt, nullptr, warp};
 }
 
 static void set_sink(DecodeRequest &rq, const Sink &k)
@@ -1032,6 +1041,7 @@ static void set_sink(DecodeRequest &rq, const Sink &k)
     rq.roi = k.roi;
     rq.fmt = k.fmt;
     rq.rs = k.rs;
+    rq.warp = k.warp;
 }
 
 // streams as the source: null arguments, then the sample type, then the plan's own errors
@@ -1148,6 +1158,32 @@ extern "C" int ccmi_decode_batch_dev_rs(const uint8_t *const *streams, const siz
     DecodeRequest rq;
     if (int rc = stream_request(rs ? "decode_batch_dev_rs" : "decode_batch_dev_fmt", streams, lens, n,
                                 formatted(roi, fmt, rs), out_bitdepth, out_chroma, !out_dev || !out_caps || !fmt, rq))
+        return rc;
+    return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
+}
+
+// The warping sink: the formatted call with a ccmi_warp in place of the regions.
+extern "C" int ccmi_decode_batch_dev_warp_plan(const uint8_t *const *streams, const size_t *lens, int n,
+                                               int out_bitdepth, int out_chroma, const ccmi_tensor_fmt *fmt,
+                                               const ccmi_warp *warp, ccmi_frame_geom *geom, ccmi_roi_info *info,
+                                               ccmi_rect *window, size_t *workspace_bytes)
+{
+    DecodeRequest rq;
+    if (int rc = stream_request("decode_batch_dev_warp_plan (frame 0)", streams, lens, n, warped(fmt, warp), out_bitdepth,
+                                out_chroma, !fmt || !warp || !warp->matrix || !geom || !workspace_bytes, rq))
+        return rc;
+    rq.window = window;
+    return sink_plan(rq, geom, info, workspace_bytes);
+}
+
+extern "C" int ccmi_decode_batch_dev_warp(const uint8_t *const *streams, const size_t *lens, int n,
+                                          void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
+                                          const ccmi_warp *warp, int out_bitdepth, int out_chroma, void *workspace,
+                                          size_t workspace_bytes, void *stream)
+{
+    DecodeRequest rq;
+    if (int rc = stream_request("decode_batch_dev_warp (frame 0)", streams, lens, n, warped(fmt, warp), out_bitdepth,
+                                out_chroma, !out_dev || !out_caps || !fmt || !warp || !warp->matrix, rq))
         return rc;
     return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
 }
@@ -1317,6 +1353,31 @@ extern "C" int ccmi_latents_render_rs(const ccmi_latents *h, const int *index, i
     DecodeRequest rq;
     if (int rc = latents_request(rs ? "latents_render_rs" : "latents_render_fmt", h, index, m, formatted(roi, fmt, rs),
                                  out_bitdepth, out_chroma, true, !out_dev || !out_caps || !fmt, rq))
+        return rc;
+    return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ccmi_latents_render_warp_plan(const ccmi_latents *h, const int *index, int m, int out_bitdepth,
+                                             int out_chroma, const ccmi_tensor_fmt *fmt, const ccmi_warp *warp,
+                                             ccmi_frame_geom *geom, ccmi_roi_info *info, ccmi_rect *window,
+                                             size_t *workspace_bytes)
+{
+    DecodeRequest rq;
+    if (int rc = latents_request("latents_render_warp_plan (frame 0)", h, index, m, warped(fmt, warp), out_bitdepth,
+                                 out_chroma, false, !fmt || !warp || !warp->matrix || !geom || !workspace_bytes, rq))
+        return rc;
+    rq.window = window;
+    return sink_plan(rq, geom, info, workspace_bytes);
+}
+
+extern "C" int ccmi_latents_render_warp(const ccmi_latents *h, const int *index, int m, void *const *out_dev,
+                                        const size_t *out_caps, const ccmi_tensor_fmt *fmt, const ccmi_warp *warp,
+                                        int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes,
+                                        void *stream)
+{
+    DecodeRequest rq;
+    if (int rc = latents_request("latents_render_warp (frame 0)", h, index, m, warped(fmt, warp), out_bitdepth, out_chroma,
+                                 true, !out_dev || !out_caps || !fmt || !warp || !warp->matrix, rq))
         return rc;
     return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
 }

@@ -164,7 +164,17 @@ struct DecFmt {
     // then refer to the output size
     int rs = 0;
     int out_h = 0, out_w = 0;
+    // ccmi_warp: every out_h x out_w output pixel is a bilinear sample of the whole frame at the
+    // position this frame's matrix m gives (dec_warp<T>), between the same two steps; pad and
+    // fill are one per call.  Never together with rs
+    int warp = 0;
+    int pad = 0;
+    float fill[3] = {0.f, 0.f, 0.f};
+    float m[6] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f};
 };
+// the form of a tail group's output section: DecOut, or its resample / warp extension
+enum { kOutPlain = 0, kOutRs = 1, kOutWarp = 2 };
+inline int dec_out_form(const DecFmt &f) { return f.rs ? kOutRs : f.warp ? kOutWarp : kOutPlain; }
 // One frame: the region `rect` of the h x w synthesis output (12-bit, [3][h][w]) as the formatted
 // tensor at dst; kind 0 takes planes 1 and 2 at the even row and column (rect's origin even).
 int launch_dec_output_fmt(const int32_t *syn, int h, int w, const DecWindow &rect, int bitdepth, int kind,
@@ -174,6 +184,10 @@ int launch_dec_output_fmt(const int32_t *syn, int h, int w, const DecWindow &rec
 size_t dec_resample_tmp_elems(int region_h, int out_w);
 int launch_dec_resample(const int32_t *syn, int h, int w, const DecWindow &rect, int bitdepth, int kind,
                         const DecFmt &fmt, float *tmp, void *dst, hipStream_t s);
+// The same with fmt.warp: the fmt.out_h x fmt.out_w frame at dst samples the whole h x w synthesis
+// output through fmt.m (kind 0: h and w even).
+int launch_dec_warp(const int32_t *syn, int h, int w, int bitdepth, int kind, const DecFmt &fmt, void *dst,
+                    hipStream_t s);
 
 // Batched decoder tail: frames with the same geometry and a fused-synthesis architecture
 // (single branch) share one launch per pyramid step, one synthesis and one output launch
@@ -196,7 +210,7 @@ struct DecTailFrame {
 };
 bool dec_tail_batchable(const DecTailFrame &f);
 bool dec_tail_same_group(const DecTailFrame &a, const DecTailFrame &b);
-size_t dec_tail_table_bytes(int n_layers, int n, bool windowed = false, bool resample = false);
+size_t dec_tail_table_bytes(int n_layers, int n, bool windowed = false, int out_form = kOutPlain);
 void dec_tail_fill(const DecTailFrame *const *fr, int n, void *host_tab);
 // fr: the group's frames, in table order (a window-form group sizes its grids by their windows)
 int launch_dec_tail_batch(const DecTailFrame *const *fr, int n, const void *dev_tab, hipStream_t s);

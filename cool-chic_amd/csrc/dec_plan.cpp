@@ -62,12 +62,66 @@ size_t elem_bytes(int elem) { return elem == CCMI_ELEM_F32 ? 4 : 2; }
 
 constexpr int kMaxResample = 16384; // region and output extents of a resample: its integer weights fit int32
 
+constexpr double kMaxWarpReach = 4194304.0; // 2^22: the bound on a warp's float32 positions
+
+// A warp (ccmi_warp) of frame i: the checks that need no header.  After them every position of
+// the output grid is finite and within 2^22 of the origin, so the window below is plain arithmetic.
+int warp_check(const ccmi_warp &wp, int i)
+{
+    if (wp.out_w < 1 || wp.out_w > kMaxResample || wp.out_h < 1 || wp.out_h > kMaxResample)
+        return ccmi_set_error(CCMI_ERR_ARG, "frame %d: output size w %d h %d (1 .. %d)", i, wp.out_w, wp.out_h,
+                              kMaxResample);
+    if (wp.pad != CCMI_PAD_FILL && wp.pad != CCMI_PAD_EDGE)
+        return ccmi_set_error(CCMI_ERR_ARG, "frame %d: unknown pad %d", i, wp.pad);
+    const float *m = wp.matrix + 6 * (size_t)i;
+    for (int k = 0; k < 6; ++k)
+        if (!std::isfinite(m[k])) return ccmi_set_error(CCMI_ERR_ARG, "frame %d: matrix entry %d is not finite", i, k);
+    for (int c = 0; c < 3; ++c)
+        if (!std::isfinite(wp.fill[c]))
+            return ccmi_set_error(CCMI_ERR_ARG, "frame %d: fill of channel %d is not finite", i, c);
+    for (int r = 0; r < 2; ++r) {
+        const double reach = std::fabs((double)m[3 * r]) * wp.out_w + std::fabs((double)m[3 * r + 1]) * wp.out_h +
+                             std::fabs((double)m[3 * r + 2]);
+        if (reach > kMaxWarpReach)
+            return ccmi_set_error(CCMI_ERR_ARG,
+                                  "frame %d: matrix row %d reaches %.9g pixels (|m0| out_w + |m1| out_h + |m2| <= 2^22)", i, r,
+                                  reach);
+    }
+    return CCMI_OK;
+}
+
+// The window of an h x w frame a checked warp samples (the rule is in ccmi.h): the bounding box of
+// the taps in double, grown by one pixel, each end clamped into the frame; even = grown to even
+// x, y, w, h (h and w even).
+DecWindow warp_window(const ccmi_warp &wp, int i, int h, int w, bool even)
+{
+    const float *m = wp.matrix + 6 * (size_t)i;
+    const double cx[2] = {0.5, wp.out_w - 0.5}, cy[2] = {0.5, wp.out_h - 0.5};
+    int end[2][2]; // [axis: x, y][first, last]
+    for (int r = 0; r < 2; ++r) {
+        double lo = 0, hi = 0;
+        for (int a = 0; a < 2; ++a)
+            for (int b = 0; b < 2; ++b) {
+                const double v = (double)m[3 * r] * cx[a] + (double)m[3 * r + 1] * cy[b] + (double)m[3 * r + 2];
+                if ((a | b) == 0 || v < lo) lo = v;
+                if ((a | b) == 0 || v > hi) hi = v;
+            }
+        const double last = (r == 0 ? w : h) - 1;
+        end[r][0] = (int)std::min(std::max(std::floor(lo - 0.5) - 1, 0.0), last);
+        end[r][1] = (int)std::min(std::max(std::floor(hi - 0.5) + 2, 0.0), last);
+    }
+    DecWindow win{end[1][0], end[1][1] + 1, end[0][0], end[0][1] + 1};
+    if (even) win = DecWindow{win.y0 & ~1, (win.y1 + 1) & ~1, win.x0 & ~1, (win.x1 + 1) & ~1};
+    return win;
+}
+
 // A formatted sink (ccmi_tensor_fmt) for the region `rect` of frame i: validates the format
 // against the region and resolves it into d; *span = the elements from the frame's first to its
 // last, + 1.  of = the sample format tensor_format() chose.  rs (optional): the region is
-// resampled, so the frame the strides describe is rs->out_h x rs->out_w.
-int tensor_fmt(const ccmi_tensor_fmt &m, const ccmi_resample *rs, int i, const FrameHost &f, const OutFmt &of,
-               const DecWindow &rect, DecFmt &d, size_t *span)
+// resampled, so the frame the strides describe is rs->out_h x rs->out_w; wp (optional, checked):
+// the region is the window a warp samples, the frame wp->out_h x wp->out_w.
+int tensor_fmt(const ccmi_tensor_fmt &m, const ccmi_resample *rs, const ccmi_warp *wp, int i, const FrameHost &f,
+               const OutFmt &of, const DecWindow &rect, DecFmt &d, size_t *span)
 {
     if (m.elem != CCMI_ELEM_F32 && m.elem != CCMI_ELEM_F16 && m.elem != CCMI_ELEM_BF16)
         return ccmi_set_error(CCMI_ERR_ARG, "frame %d: unknown element type %d", i, m.elem);
@@ -89,7 +143,8 @@ int tensor_fmt(const ccmi_tensor_fmt &m, const ccmi_resample *rs, int i, const F
             return ccmi_set_error(CCMI_ERR_ARG, "frame %d: a resampled region is at most %d a side (w %d h %d)", i,
                                   kMaxResample, rect.w(), rect.h());
     }
-    const int w = rs ? rs->out_w : rect.w(), h = rs ? rs->out_h : rect.h(); // of the stored frame
+    // of the stored frame
+    const int w = rs ? rs->out_w : wp ? wp->out_w : rect.w(), h = rs ? rs->out_h : wp ? wp->out_h : rect.h();
     int64_t sc = m.stride_c, sy = m.stride_y, sx = m.stride_x;
     if (sc == 0 && sy == 0 && sx == 0) sc = (int64_t)w * h, sy = w, sx = 1;
     const int64_t big = (int64_t)1 << 40; // times an extent (16-bit frame sizes): every product below fits 64 bits
@@ -116,6 +171,11 @@ int tensor_fmt(const ccmi_tensor_fmt &m, const ccmi_resample *rs, int i, const F
     for (int c = 0; c < 3; ++c) d.scale[c] = m.scale[c], d.bias[c] = m.bias[c];
     d.stride_c = sc, d.stride_y = sy, d.stride_x = sx;
     if (rs) d.rs = 1, d.out_h = h, d.out_w = w;
+    if (wp) {
+        d.warp = 1, d.out_h = h, d.out_w = w, d.pad = wp->pad;
+        for (int c = 0; c < 3; ++c) d.fill[c] = wp->fill[c];
+        for (int k = 0; k < 6; ++k) d.m[k] = wp->matrix[6 * (size_t)i + k];
+    }
     *span = (size_t)(2 * sc + (h - 1) * sy + (w - 1) * sx + 1);
     return CCMI_OK;
 }
@@ -161,11 +221,23 @@ int plan_tensor_sink(const DecodeRequest &rq, int i, FramePlan &p)
                                   q.x, q.y, q.w, q.h, f.w, f.h);
         rect = DecWindow{q.y, q.y + q.h, q.x, q.x + q.w};
     }
+    if (rq.warp) { // the region is the window the matrix reaches
+        if (int rc = warp_check(*rq.warp, i)) return rc;
+        rect = warp_window(*rq.warp, i, f.h, f.w, false);
+    }
     if (int rc = tensor_format(f, rq.out_bitdepth, rq.out_chroma, rq.sample, p.of, &elems, rect)) {
         if (!rq.src) return rc;
         std::string m = ccmi_last_error();
         return ccmi_set_error(rc, "frame %d: %s", i, m.c_str());
     }
+    if (rq.warp && p.of.kind == kYuv420) {
+        if ((f.w | f.h) & 1)
+            return ccmi_set_error(
+                CCMI_ERR_ARG, "frame %d: a warp of 420 samples needs an even frame size (w %d h %d); out_chroma = 444 takes any",
+                i, f.w, f.h);
+        rect = warp_window(*rq.warp, i, f.h, f.w, true);
+    }
+    if (rq.window) rq.window[i] = ccmi_rect{rect.x0, rect.y0, rect.w(), rect.h()};
     if (p.of.kind == kYuv420 && ((rect.x0 | rect.y0) & 1))
         return ccmi_set_error(CCMI_ERR_ARG, "%s %d: a 420 region needs an even origin (x %d y %d)", who, i, rect.x0,
                               rect.y0);
@@ -173,13 +245,17 @@ int plan_tensor_sink(const DecodeRequest &rq, int i, FramePlan &p)
     int out_w = rect.w(), out_h = rect.h();  // of the stored frame: the region, unless it is resampled
     if (rq.fmt) {
         size_t span = 0;
-        if (int rc = tensor_fmt(*rq.fmt, rq.rs, i, f, p.of, rect, t.fmt, &span)) return rc;
+        if (int rc = tensor_fmt(*rq.fmt, rq.rs, rq.warp, i, f, p.of, rect, t.fmt, &span)) return rc;
         unit = elem_bytes(t.fmt.elem);
         elems = 3 * (size_t)rect.h() * rect.w();
         if (t.fmt.rs) {
             out_w = t.fmt.out_w, out_h = t.fmt.out_h;
             elems = 3 * (size_t)out_h * out_w;
             p.rs_elems = dec_resample_tmp_elems(rect.h(), out_w);
+        }
+        if (t.fmt.warp) {
+            out_w = t.fmt.out_w, out_h = t.fmt.out_h;
+            elems = 3 * (size_t)out_h * out_w;
         }
         p.of.payload = span * unit; // what the caller's buffer must hold
     }
@@ -323,7 +399,7 @@ void plan_layout(const DecodeRequest &rq, DecodePlan &pl)
     // batched-tail argument tables: bounded by one single-frame table per frame
     pl.tail_cap = 0;
     for (const FramePlan &p : pl.fr)
-        if (!build) pl.tail_cap += dec_tail_table_bytes(p.f.n_layers, 1, p.mode == kTailWindow, p.tail.fmt.rs != 0);
+        if (!build) pl.tail_cap += dec_tail_table_bytes(p.f.n_layers, 1, p.mode == kTailWindow, dec_out_form(p.tail.fmt));
     pl.tail_off = tot;
     tot += align_up(pl.tail_cap, 256);
     // the pack / unpack job table follows the tail tables: one host image, one upload.  A build

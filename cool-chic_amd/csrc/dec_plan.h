@@ -77,6 +77,10 @@ struct DecodeRequest {
     const ccmi_tensor_fmt *fmt = nullptr;
     // with fmt, optional: every frame's region is resampled to one output size (ccmi_resample)
     const ccmi_resample *rs = nullptr;
+    // with fmt, instead of roi and rs: every output pixel samples the whole frame through the
+    // frame's matrix (ccmi_warp); the plan derives each frame's region, its window, from the matrix
+    const ccmi_warp *warp = nullptr;
+    ccmi_rect *window = nullptr; // [n], optional: the windows, filled by the plan
     // either sink
     const size_t *caps = nullptr;    // [n], optional: capacity in bytes of outs[i] / dev[i]
     size_t *sizes = nullptr;         // [n], optional: bytes written per stream (filled by the plan)

@@ -19,6 +19,8 @@
 //                   full-size channels, YUV -> RGB, scale / bias, f32 / f16 / bf16, strides, mirror.
 //  dec_resample_h, dec_resample_v  the formatted tensor with a ccmi_resample: the region through an
 //                   antialiased triangle filter to the output size, horizontal then vertical pass.
+//  dec_warp         the formatted tensor with a ccmi_warp: every output pixel a bilinear sample of
+//                   the frame at the position the frame's 2 x 3 matrix gives, fill or edge padding.
 #include <stdlib.h>
 
 #include <algorithm>
@@ -999,6 +1001,116 @@ __global__ __launch_bounds__(kThreads) void dec_resample_v_batch(const DecOutRs 
 
 unsigned resample_h_blocks(int h, int ow) { return (unsigned)(((int64_t)h * ow + kThreads - 1) / kThreads); }
 
+// ------------------------------------------------------------------ warped formatted output
+// The formatted sink with a ccmi_warp (steps 3a-3d of its contract in ccmi.h): every pixel of the
+// oh x ow frame at dst is a bilinear sample of q over the WHOLE frame, fh x fw, at the position
+// the frame's 2 x 3 matrix gives, between the colour step and scale / bias.  One launch, a thread
+// = (output row, 4 destination pixels) as in the formatted output stage; the pixels go one at a
+// time, so 12 tap values are live and not 48.  Each pixel gathers 4 taps x 3 channels through
+// fmt_pixel (the colour step per tap).
+// The synthesis output holds the window the plan derived from the matrix, h x w at (oy, ox) of
+// the frame, compact (the per-frame tail: the whole frame at 0, 0).  A tap is tested and clamped
+// against the FRAME, as the contract has it, then addressed relative to the window and clamped to
+// it as well: the window holds every in-frame tap, so that clamp changes nothing unless the plan
+// is wrong, and then it shows as a wrong value and never as a read outside the workspace.
+struct DecWarpCall { // one value per launch
+    int oh, ow, pad;
+    float fill[3];
+};
+
+// one frame of a warping group: DecOut as for dec_output_fmt_batch (H x W = the window, compact)
+struct DecOutWarp {
+    DecOut o;
+    float m[6];
+    int oy, ox, fh, fw; // the window's origin in the frame, and the frame
+};
+
+template <typename T>
+__device__ __forceinline__ void warp_body(const int32_t *__restrict__ syn, int h, int w, int oy, int ox, int fh, int fw,
+                                          const float (&m)[6], int maxv, int kind, int flags, T *__restrict__ dst,
+                                          const DecFmtCall &C, const DecWarpCall &Wc)
+{
+    int y, d0;
+    int64_t row;
+    bool nchw, nhwc;
+    if (!fmt_group<T>(dst, C, Wc.oh, Wc.ow, y, d0, row, nchw, nhwc)) return;
+    const float fmax = (float)maxv;
+    const bool mirror = flags & kFmtMirror, matrix = flags & kFmtMatrix;
+    const int64_t splane = (int64_t)h * w;
+    const float cy = (float)y + 0.5f;
+    const float xr = fmt_mul(m[1], cy), yr = fmt_mul(m[4], cy); // the row's share of the position
+    T v[3][4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int d = d0 + k;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c][k] = fmt_elem<T>(0.f);
+        if (d < 0 || d >= Wc.ow) continue;
+        const float cx = (float)(mirror ? Wc.ow - 1 - d : d) + 0.5f;
+        const float xs = fmt_add(fmt_add(fmt_mul(m[0], cx), xr), m[2]);
+        const float ys = fmt_add(fmt_add(fmt_mul(m[3], cx), yr), m[5]);
+        const float u = xs - 0.5f, vv = ys - 0.5f;
+        const float uf = floorf(u), vf = floorf(vv); // |u|, |v| <= 2^22 + 1: exact in an int
+        const float fx = u - uf, fy = vv - vf;
+        const int x0 = (int)uf, y0 = (int)vf;
+        const float gx = 1.f - fx, gy = 1.f - fy;
+        float line[2][3]; // top, bot
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            const int yy = y0 + a;
+            const bool yin = yy >= 0 && yy < fh;
+            const int ry = min(max(min(max(yy, 0), fh - 1) - oy, 0), h - 1);
+            const int32_t *__restrict__ lrow = syn + (int64_t)ry * w;
+            const int32_t *__restrict__ crow = syn + (int64_t)(kind == 1 ? ry : ry & ~1) * w;
+            float t[2][3];
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                const int xx = x0 + b;
+                const bool in = yin && xx >= 0 && xx < fw;
+                const int rx = min(max(min(max(xx, 0), fw - 1) - ox, 0), w - 1);
+                fmt_pixel(lrow, crow, splane, rx, kind == 1 ? rx : rx & ~1, maxv, fmax, matrix, t[b]);
+                if (!in && Wc.pad == CCMI_PAD_FILL) {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) t[b][c] = Wc.fill[c];
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) line[a][c] = fmt_add(fmt_mul(t[0][c], gx), fmt_mul(t[1][c], fx));
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float r = fmt_add(fmt_mul(line[0][c], gy), fmt_mul(line[1][c], fy));
+            v[c][k] = fmt_elem<T>(fmt_add(fmt_mul(r, C.scale[c]), C.bias[c]));
+        }
+    }
+    fmt_store<T>(v, dst, C, row, d0, Wc.ow, nchw, nhwc);
+}
+
+// one frame (DecOut::bps = its kFmt* flags): the per-frame tail's, A.o = the whole synthesis output
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_warp(DecOutWarp A, DecFmtCall C, DecWarpCall Wc)
+{
+    warp_body<T>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind, A.o.bps,
+                 reinterpret_cast<T *>(A.o.dst), C, Wc);
+}
+
+// a tail group: frame blockIdx.y's compact window
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_warp_batch(const DecOutWarp *__restrict__ Os, DecFmtCall C, DecWarpCall Wc)
+{
+    const DecOutWarp A = Os[blockIdx.y];
+    warp_body<T>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind, A.o.bps,
+                 reinterpret_cast<T *>(A.o.dst), C, Wc);
+}
+
+DecWarpCall warp_call(const DecFmt &f)
+{
+    DecWarpCall Wc;
+    Wc.oh = f.out_h, Wc.ow = f.out_w, Wc.pad = f.pad;
+    for (int c = 0; c < 3; ++c) Wc.fill[c] = f.fill[c];
+    return Wc;
+}
+
 } // namespace
 
 size_t dec_ups_workspace_elems(const int *lh, const int *lw, int L)
@@ -1371,6 +1483,26 @@ int launch_dec_resample(const int32_t *syn, int h, int w, const DecWindow &rect,
     });
 }
 
+static DecOutWarp make_out_warp(const DecOut &o, const DecFmt &fmt, int oy, int ox, int fh, int fw)
+{
+    DecOutWarp A{o, {}, oy, ox, fh, fw};
+    for (int k = 0; k < 6; ++k) A.m[k] = fmt.m[k];
+    return A;
+}
+
+int launch_dec_warp(const int32_t *syn, int h, int w, int bitdepth, int kind, const DecFmt &fmt, void *dst, hipStream_t s)
+{
+    if (int rc = check_region(DecWindow{0, h, 0, w}, h, w, kind, true)) return rc;
+    if (!fmt.warp || fmt.out_h < 1 || fmt.out_w < 1) return ccmi_set_error(CCMI_ERR_ARG, "dec: warp without a size");
+    if (kind == 0 && ((h | w) & 1)) return ccmi_set_error(CCMI_ERR_ARG, "dec: a 420 warp needs an even frame size");
+    const DecOut o{syn, h, w, (1 << bitdepth) - 1, kind, fmt_flags(fmt), static_cast<uint8_t *>(dst)};
+    const DecOutWarp A = make_out_warp(o, fmt, 0, 0, h, w);
+    const dim3 grid(output_fmt_blocks(fmt.out_h, fmt.out_w));
+    return with_elem_type(fmt.elem, [&](auto t) {
+        hipLaunchKernelGGL(dec_warp<decltype(t)>, grid, dim3(kThreads), 0, s, A, fmt_call(fmt), warp_call(fmt));
+    });
+}
+
 // ------------------------------------------------------------------ batched decoder tail
 bool dec_tail_batchable(const DecTailFrame &f)
 {
@@ -1386,15 +1518,17 @@ bool dec_tail_same_group(const DecTailFrame &a, const DecTailFrame &b)
     // a formatted output is one kernel per element type; the format is one per call, so the
     // frames of a call group as they do without it
     if (a.fmt.on != b.fmt.on || a.fmt.elem != b.fmt.elem) return false;
-    if (a.fmt.rs != b.fmt.rs || a.fmt.out_h != b.fmt.out_h || a.fmt.out_w != b.fmt.out_w) return false;
+    if (a.fmt.rs != b.fmt.rs || a.fmt.warp != b.fmt.warp || a.fmt.out_h != b.fmt.out_h || a.fmt.out_w != b.fmt.out_w)
+        return false;
     if (a.windowed) {
         // region decode: the tables carry each frame's true plane sizes and its windows, the
         // grids cover the group's largest window; one region size (the output grid), any
         // frame size, any origin.  A resample's output grid is the output size (above): its
-        // regions may differ, and the synthesis and horizontal-pass grids cover the largest
+        // regions may differ, and the synthesis and horizontal-pass grids cover the largest; a
+        // warp's likewise, its regions being the windows its matrices reach
         if (a.sample != b.sample || a.kind != b.kind) return false;
         if (a.syn.n_layers != b.syn.n_layers || a.syn.c_in != b.syn.c_in) return false;
-        return a.fmt.rs || (a.roi.rect.h() == b.roi.rect.h() && a.roi.rect.w() == b.roi.rect.w());
+        return a.fmt.rs || a.fmt.warp || (a.roi.rect.h() == b.roi.rect.h() && a.roi.rect.w() == b.roi.rect.w());
     }
     for (int l = 0; l < a.ups.n_layers; ++l)
         if (a.ups.lh[l] != b.ups.lh[l] || a.ups.lw[l] != b.ups.lw[l]) return false;
@@ -1408,18 +1542,21 @@ static size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
 // Byte layout of the argument table of a group of n frames: [step][frame] pyramid levels, then
 // [frame] synthesis arguments, then [frame] DecOut, each section 16-byte aligned.  A window-form
 // group holds DecLevelWin / DecSynFusedWin, the others DecLevel / DecSynFused; a resampling
-// group holds DecOutRs for DecOut.
+// group holds DecOutRs for DecOut, a warping group DecOutWarp (out_form: kOut*).
 struct TailTable {
     size_t syn, out, bytes; // section offsets (the levels are at 0) and the total size
-    TailTable(int steps, int n, bool windowed, bool resample)
+    TailTable(int steps, int n, bool windowed, int out_form)
     {
         const size_t st = steps > 0 ? (size_t)steps : 0;
         syn = al16((windowed ? sizeof(DecLevelWin) : sizeof(DecLevel)) * st * n);
         out = syn + al16((windowed ? sizeof(DecSynFusedWin) : sizeof(DecSynFused)) * (size_t)n);
-        bytes = out + al16((resample ? sizeof(DecOutRs) : sizeof(DecOut)) * (size_t)n);
+        const size_t entry = out_form == kOutRs     ? sizeof(DecOutRs)
+                             : out_form == kOutWarp ? sizeof(DecOutWarp)
+                                                    : sizeof(DecOut);
+        bytes = out + al16(entry * (size_t)n);
     }
     // the group of `fr[0]`
-    TailTable(const DecTailFrame &f0, int n) : TailTable(f0.ups.n_layers - 1, n, f0.windowed, f0.fmt.rs != 0) {}
+    TailTable(const DecTailFrame &f0, int n) : TailTable(f0.ups.n_layers - 1, n, f0.windowed, dec_out_form(f0.fmt)) {}
     template <typename T> T *at(void *tab, size_t off) const { return reinterpret_cast<T *>(static_cast<uint8_t *>(tab) + off); }
     template <typename T> const T *at(const void *tab, size_t off) const
     {
@@ -1427,9 +1564,9 @@ struct TailTable {
     }
 };
 
-size_t dec_tail_table_bytes(int n_layers, int n, bool windowed, bool resample)
+size_t dec_tail_table_bytes(int n_layers, int n, bool windowed, int out_form)
 {
-    return TailTable(n_layers - 1, n, windowed, resample).bytes;
+    return TailTable(n_layers - 1, n, windowed, out_form).bytes;
 }
 
 static DecOut make_out(const DecTailFrame &f, int h, int w)
@@ -1438,10 +1575,12 @@ static DecOut make_out(const DecTailFrame &f, int h, int w)
                   f.dst};
 }
 
-// entry i of a group's output section
-static void put_out(const TailTable &T, void *host_tab, int i, const DecTailFrame &f, int h, int w)
+// entry i of a group's output section: the h x w synthesis output sits at (oy, ox) of its frame
+static void put_out(const TailTable &T, void *host_tab, int i, const DecTailFrame &f, int h, int w, int oy = 0, int ox = 0)
 {
-    if (f.fmt.rs) T.at<DecOutRs>(host_tab, T.out)[i] = DecOutRs{make_out(f, h, w), f.rs_tmp};
+    if (f.fmt.warp)
+        T.at<DecOutWarp>(host_tab, T.out)[i] = make_out_warp(make_out(f, h, w), f.fmt, oy, ox, f.syn.h, f.syn.w);
+    else if (f.fmt.rs) T.at<DecOutRs>(host_tab, T.out)[i] = DecOutRs{make_out(f, h, w), f.rs_tmp};
     else T.at<DecOut>(host_tab, T.out)[i] = make_out(f, h, w);
 }
 
@@ -1467,7 +1606,7 @@ static void dec_tail_fill_win(const DecTailFrame *const *fr, int n, void *host_t
         // the synthesis output is the region itself, compact: the whole-frame output kernel
         // converts it as a frame of the region's size (420: the origin is even, so its even
         // rows and columns are the frame's)
-        put_out(T, host_tab, i, *fr[i], S.rh, S.rw);
+        put_out(T, host_tab, i, *fr[i], S.rh, S.rw, S.ry, S.rx);
     }
 }
 
@@ -1498,6 +1637,13 @@ static int launch_output_tensor_batch(const DecTailFrame &f0, int h, int w, int 
         const dim3 grid(output_fmt_blocks(oh, ow), n);
         return with_elem_type(f0.fmt.elem, [&](auto t) {
             hipLaunchKernelGGL(dec_resample_v_batch<decltype(t)>, grid, dim3(kThreads), 0, s, rr, oh, ow, fmt_call(f0.fmt));
+        });
+    }
+    if (f0.fmt.warp) { // the section holds DecOutWarp; the grid is the output size
+        const dim3 grid(output_fmt_blocks(f0.fmt.out_h, f0.fmt.out_w), n);
+        return with_elem_type(f0.fmt.elem, [&](auto t) {
+            hipLaunchKernelGGL(dec_warp_batch<decltype(t)>, grid, dim3(kThreads), 0, s,
+                               reinterpret_cast<const DecOutWarp *>(oo), fmt_call(f0.fmt), warp_call(f0.fmt));
         });
     }
     if (f0.fmt.on) { // the format but its per-frame flags (in the table) is the call's

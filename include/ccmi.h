@@ -571,6 +571,70 @@ int ccmi_latents_render_rs(const ccmi_latents *h, const int *index /* [m] or NUL
                            int out_chroma, void *workspace, size_t workspace_bytes, void *stream);
 int ccmi_decode_last_tail_groups(int *batched, int *per_frame);
 
+/* Warped formatted output: the formatted sink with an output size and one 2 x 3 matrix per frame.
+ * Every output frame is out_h x out_w and every output pixel a bilinear sample of the decoded
+ * frame at the position the frame's matrix gives -- rotation, scale, shear, translation, flip:
+ * grid_sample(mode="bilinear", align_corners=False) with the grid in pixels -- between steps 3 and
+ * 4 of the ccmi_tensor_fmt contract, in the decoder's output stage.  There is no roi: steps 1-3
+ * define q_c(y, x) over the WHOLE frame, H x W, and the library derives the window of the frame it
+ * has to decode.  For output row i, column k, every product, sum and difference one float32
+ * operation in the order written (no fused multiply-add):
+ *   3a. cx = (float)k + 0.5f, cy = (float)i + 0.5f;
+ *       xs = ((m00 cx) + (m01 cy)) + m02, ys = ((m10 cx) + (m11 cy)) + m12: frame coordinates in
+ *       pixels, pixel (y, x) covering [x, x + 1) x [y, y + 1);
+ *   3b. u = xs - 0.5f, x0 = floor(u), fx = u - (float)x0; v, y0, fy alike from ys;
+ *   3c. tap T_c(a, b), a, b in {0, 1}: q_c(y0 + a, x0 + b) where that lies in [0, H) x [0, W);
+ *       otherwise fill[c] (CCMI_PAD_FILL), or q_c at the indices clamped to the frame
+ *       (CCMI_PAD_EDGE);
+ *   3d. top = (T(0,0) (1 - fx)) + (T(0,1) fx), bot alike from T(1, .), r' = (top (1 - fy)) + (bot fy).
+ * Steps 4-6 apply to r' at the output size; mirror[j] is x' = out_w - 1 - x, as with a resample.
+ * So an integer translation (m = 1 0 x / 0 1 y) is the crop at (x, y) bit for bit, and m00 = -1 a
+ * flip, bit for bit.  There is no antialiasing (this is grid_sample, not
+ * interpolate(antialias=True)): pure downscaling belongs to ccmi_resample.
+ * Checked by the plan before any GPU work, CCMI_ERR_ARG naming the frame and nothing written: warp
+ * or matrix NULL, out_w or out_h outside [1, 16384], an unknown pad, a non-finite matrix entry or
+ * fill, |m00| out_w + |m01| out_h + |m02| > 2^22 or the same sum of the second row (the bound on
+ * every float32 intermediate: the position is then within 3 2^-24 2^22 = 0.75 pixel of exact
+ * arithmetic and x0 fits an int), and a 420 sample format on a frame with an odd size.  The
+ * strides, their aliasing check and out_caps refer to the out_h x out_w frame; geom[j].width /
+ * height are out_w / out_h and elems is 3 out_w out_h.
+ * window[j] (the _plan calls, optional) is the rectangle of the frame the tail renders for frame
+ * j, computed in double from the float32 matrix: xs, ys at the four corner pixel centres (the map
+ * is linear: the extremes); columns floor(min xs - 0.5) - 1 .. floor(max xs - 0.5) + 2 and rows
+ * alike -- the taps' bounding box grown by one pixel for the float32 rounding --, each end CLAMPED
+ * into the frame (never empty; it holds the edge pixels CCMI_PAD_EDGE needs even when the whole
+ * output lies outside the frame), grown to even x, y, w, h for a 420 sample format.  It is a
+ * superset of the in-frame taps and no part of the bitwise contract.  The workspace is that of the
+ * _fmt call with roi = window (no intermediate); a window equal to the frame runs the whole-frame
+ * tail, a stream without a fused synthesis its per-frame tail on the whole frame.  Streams with a
+ * fused synthesis of one architecture share one batched tail whatever their matrices.  The
+ * argument lists follow the _rs calls without roi; everything else (index, info, the stream
+ * synchronisation, timing, ARM flags, ccmi_decode_last_tail_groups) is as for them.
+ * Measured (profiles/decode_warp_ab.txt): 960 class-E streams from an int16 store, rotation +-30
+ * degrees, scale 0.5-1.5, random centres, 224 x 224 bf16 RGB normalised: 14.8-14.9 ms per call (tail
+ * 11.3 ms) in one tail group, against 194-209 ms for the CCMI_ELEM_F32 render of the same windows per
+ * window size (737 groups) followed by torch's grid_sample; workspace 6.6 GiB. */
+enum { CCMI_PAD_FILL = 0, CCMI_PAD_EDGE = 1 };
+typedef struct ccmi_warp {
+    int out_w, out_h, pad;
+    float fill[3];        /* CCMI_PAD_FILL: value of a tap outside the frame, in q units (after step 3) */
+    const float *matrix;  /* host, [n][6]: m00 m01 m02 m10 m11 m12 of frame j */
+} ccmi_warp;
+int ccmi_decode_batch_dev_warp_plan(const uint8_t *const *streams, const size_t *lens, int n, int out_bitdepth,
+                                    int out_chroma, const ccmi_tensor_fmt *fmt, const ccmi_warp *warp,
+                                    ccmi_frame_geom *geom /* [n] */, ccmi_roi_info *info /* [n] or NULL */,
+                                    ccmi_rect window[] /* [n] or NULL */, size_t *workspace_bytes);
+int ccmi_decode_batch_dev_warp(const uint8_t *const *streams, const size_t *lens, int n, void *const *out_dev,
+                               const size_t *out_caps, const ccmi_tensor_fmt *fmt, const ccmi_warp *warp,
+                               int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes, void *stream);
+int ccmi_latents_render_warp_plan(const ccmi_latents *h, const int *index /* [m] or NULL */, int m, int out_bitdepth,
+                                  int out_chroma, const ccmi_tensor_fmt *fmt, const ccmi_warp *warp,
+                                  ccmi_frame_geom *geom /* [m] */, ccmi_roi_info *info /* [m] or NULL */,
+                                  ccmi_rect window[] /* [m] or NULL */, size_t *workspace_bytes);
+int ccmi_latents_render_warp(const ccmi_latents *h, const int *index /* [m] or NULL */, int m, void *const *out_dev,
+                             const size_t *out_caps, const ccmi_tensor_fmt *fmt, const ccmi_warp *warp,
+                             int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Network weights of a stream's intra frame as the decoder's fixed-point integers
  * (cc-frame-decoder.cpp:201-353, read_arm / read_ups / read_syn):
  *   arm: per hidden layer W[d][d] (out, in) then b[d]; then W_out[2][d], b_out[2]

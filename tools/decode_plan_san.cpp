@@ -3,7 +3,10 @@
 // latent store's layout and plan-only handles (ccmi_latents_*, store = NULL) with their render
 // planning included, the formatted sinks (ccmi_tensor_fmt: element types, stride sets, a mirror
 // array of exactly n bytes, and the run entry point with capacities it must reject), the resampling
-// sinks (ccmi_resample: output sizes in and out of range, an unknown filter), over the streams named on the command line, whole, in batches of 7, over a list of regions, and
+// sinks (ccmi_resample: output sizes in and out of range, an unknown filter), the warping sinks
+// (ccmi_warp: sizes in and out of range, non-finite entries, the 2^22 bound, matrices that put the
+// output wholly outside the frame, singular matrices; the matrices sit in a heap block of exactly
+// 6 n floats and the windows in one of exactly n rects), over the streams named on the command line, whole, in batches of 7, over a list of regions, and
 // truncated at each length from 0 to the header size plus 8.  Every (truncated) stream sits in
 // a heap block of exactly its length, so a read past its end is reported.  No HIP call is made.
 //
@@ -138,6 +141,56 @@ void plan_all(const std::vector<Stream> &b, const std::vector<ccmi_rect> &rects,
         if (rc == CCMI_OK) abort();
         count(rc);
     }
+    // the warping sink: one matrix set per case, the same matrix for every frame
+    const float inf = 1.f / 0.f, top = 4194304.f;
+    const float mats[][6] = {{1, 0, 0, 0, 1, 0},          {1, 0, 3, 0, 1, 5},           {-1, 0, 64, 0, 1, 2},
+                             {0.866f, -0.5f, 40, 0.5f, 0.866f, -20},                   {0.01f, 0, 7.5f, 0, 0.01f, 7.5f},
+                             {1, 0, 1e6f, 0, 1, 1e6f},    {1, 0, -1e6f, 0, 1, -1e6f},   {0, 0, 5.25f, 0, 0, 9.75f},
+                             {0, 0, 0, 0, 0, 0},          {1, 1, 0, 1, 1, 0},           {0, 0, top, 0, 0, -top},
+                             {0, 0, 4194304.5f, 0, 1, 0}, {1, 0, 0, 300000, 0, 0},      {inf, 0, 0, 0, 1, 0},
+                             {1, 0, 0, 0, 1, -inf},       {0.f / 0.f, 0, 0, 0, 1, 0},  {3e38f, 3e38f, 3e38f, 1, 1, 1}};
+    const ccmi_warp sizes_wp[] = {{224, 224, CCMI_PAD_FILL, {0.5f, 0.5f, 0.5f}, nullptr}, {1, 1, CCMI_PAD_EDGE, {0, 0, 0}, nullptr},
+                                  {16384, 3, CCMI_PAD_EDGE, {0, 0, 0}, nullptr},         {7, 16384, CCMI_PAD_FILL, {0, 1, 0}, nullptr},
+                                  {0, 8, 0, {0, 0, 0}, nullptr},                         {8, 16385, 0, {0, 0, 0}, nullptr},
+                                  {0x7fffffff, 0x7fffffff, 1, {0, 0, 0}, nullptr},       {8, 8, 2, {0, 0, 0}, nullptr},
+                                  {8, 8, 0, {0, inf, 0}, nullptr},                       {8, 8, 1, {0.f / 0.f, 0, 0}, nullptr}};
+    float *mat = static_cast<float *>(malloc(sizeof(float) * 6 * n));
+    ccmi_rect *win = static_cast<ccmi_rect *>(malloc(sizeof(ccmi_rect) * n));
+    for (const auto &m : mats) {
+        for (int i = 0; i < n; ++i) memcpy(mat + 6 * i, m, sizeof m);
+        for (ccmi_warp wp : sizes_wp) {
+            wp.matrix = mat;
+            for (size_t k = 1; k < fmts.size(); k += 6) {
+                const int rc = ccmi_decode_batch_dev_warp_plan(sp.data(), ln.data(), n, bd, chroma, &fmts[k], &wp, geom.data(),
+                                                               info.data(), win, &need);
+                count(rc);
+                if (rc == CCMI_OK) // the window is never empty and lies in the frame the header names
+                    for (int i = 0; i < n; ++i)
+                        if (win[i].w < 1 || win[i].h < 1 || win[i].x < 0 || win[i].y < 0 || geom[i].width != wp.out_w) abort();
+                count(ccmi_decode_batch_dev_warp_plan(sp.data(), ln.data(), n, bd, chroma, &fmts[k], &wp, geom.data(), nullptr,
+                                                      nullptr, &need));
+            }
+        }
+    }
+    {
+        // NULL warp / matrix, and the run entry point with capacities one byte short: rejected
+        // before any GPU work, the made-up pointers are never used
+        ccmi_warp wp = sizes_wp[1];
+        count(ccmi_decode_batch_dev_warp_plan(sp.data(), ln.data(), n, bd, chroma, &fmts[1], &wp, geom.data(), nullptr, win, &need));
+        count(ccmi_decode_batch_dev_warp_plan(sp.data(), ln.data(), n, bd, chroma, &fmts[1], nullptr, geom.data(), nullptr, win,
+                                              &need));
+        memcpy(mat, mats[3], sizeof mats[3]);
+        for (int i = 1; i < n; ++i) memcpy(mat + 6 * i, mats[1], sizeof mats[1]);
+        wp = ccmi_warp{9, 5, CCMI_PAD_EDGE, {0, 0, 0}, mat};
+        ccmi_tensor_fmt f = fmts[0];
+        f.colour = CCMI_COLOUR_RGB;
+        std::vector<void *> outs(n, reinterpret_cast<void *>(uintptr_t(1) << 40));
+        std::vector<size_t> caps(n, 3 * 9 * 5 * 4 - 1);
+        const int rc = ccmi_decode_batch_dev_warp(sp.data(), ln.data(), n, outs.data(), caps.data(), &f, &wp, bd, chroma, nullptr,
+                                                  0, nullptr);
+        if (rc == CCMI_OK) abort();
+        count(rc);
+    }
     // the latent store: layout at every element type, a plan-only handle (no GPU call), and the
     // render planning over it: in order, through an index with repeats and out-of-range entries
     void *out0 = nullptr;
@@ -150,6 +203,8 @@ void plan_all(const std::vector<Stream> &b, const std::vector<ccmi_rect> &rects,
     count(ccmi_latents_decode(sp.data(), ln.data(), n, CCMI_LATENT_I16, nullptr, 0, nullptr, 0, nullptr, &h));
     if (!h) {
         free(mir);
+        free(mat);
+        free(win);
         return;
     }
     std::vector<int> idx(n + 2);
@@ -179,12 +234,28 @@ void plan_all(const std::vector<Stream> &b, const std::vector<ccmi_rect> &rects,
     count(ccmi_latents_render_rs_plan(h, nullptr, n, nullptr, bd, chroma, &fmts[1], nullptr, geom.data(), nullptr, &need));
     count(ccmi_latents_render_rs(h, nullptr, n, nullptr, &out0, &cap0, &fmts[1], &sizes_rs[0], bd, chroma, nullptr, 0,
                                  nullptr)); // plan-only
+    for (const auto &m : mats) { // the matrix block has n entries: frames in order only
+        for (int i = 0; i < n; ++i) memcpy(mat + 6 * i, m, sizeof m);
+        for (ccmi_warp wp : sizes_wp) {
+            wp.matrix = mat;
+            count(ccmi_latents_render_warp_plan(h, nullptr, n, bd, chroma, &fmts[1], &wp, geom.data(), info.data(), win, &need));
+            count(ccmi_latents_render_warp_plan(h, idx.data() + 1, n, bd, chroma, &fmts[13], &wp, geom.data(), nullptr, nullptr,
+                                                &need));
+        }
+    }
+    {
+        ccmi_warp wp = sizes_wp[0];
+        wp.matrix = mat;
+        count(ccmi_latents_render_warp(h, nullptr, n, &out0, &cap0, &fmts[1], &wp, bd, chroma, nullptr, 0, nullptr)); // plan-only
+    }
     void *out = nullptr;
     size_t cap = 0;
     count(ccmi_latents_render(h, nullptr, n, nullptr, &out, &cap, 1, bd, chroma, nullptr, 0, nullptr)); // plan-only: an error
     if (ccmi_latents_count(h) != n) abort();
     ccmi_latents_free(h);
     free(mir);
+    free(mat);
+    free(win);
 }
 
 std::vector<ccmi_rect> rects_of(int w, int h)
