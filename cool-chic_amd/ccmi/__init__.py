@@ -25,6 +25,7 @@ EXPORTED = [
     "ccmi_last_error", "ccmi_version", "ccmi_device_count",
     "ccmi_arm_forward_f32", "ccmi_arm_context_f32", "ccmi_arm_mlp_f32", "ccmi_ups_workspace_bytes", "ccmi_ups_forward_f32",
     "ccmi_syn_workspace_bytes", "ccmi_syn_forward_f32", "ccmi_post_f32", "ccmi_decode_forward_f32",
+    "ccmi_fused_run_plan",
     "ccmi_decode_file", "ccmi_decode_batch", "ccmi_decode_output_size", "ccmi_decode_last_timing",
     "ccmi_decode_last_arm_flags", "ccmi_decode_latents", "ccmi_decode_batch_workspace_bytes", "ccmi_decode_batch_plan", "ccmi_decode_batch_ws", "ccmi_decode_weights_i32",
     "ccmi_decode_batch_dev_plan", "ccmi_decode_batch_dev", "ccmi_decode_batch_dev_roi_plan", "ccmi_decode_batch_dev_roi",
@@ -153,6 +154,10 @@ def lib() -> C.CDLL:
     L.ccmi_decode_output_size.restype = C.c_int
     L.ccmi_decode_last_timing.argtypes = [C.POINTER(C.c_float)]
     L.ccmi_decode_last_timing.restype = C.c_int
+    if hasattr(L, "ccmi_fused_run_plan"):  # absent from older builds loaded for A/B runs
+        L.ccmi_fused_run_plan.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int,
+                                          C.POINTER(C.c_int)]
+        L.ccmi_fused_run_plan.restype = C.c_int
     if hasattr(L, "ccmi_decode_last_arm_flags"):  # absent from older builds loaded for A/B runs
         L.ccmi_decode_last_arm_flags.argtypes = [C.POINTER(C.c_uint32), C.c_int, C.POINTER(C.c_int)]
         L.ccmi_decode_last_arm_flags.restype = C.c_int

@@ -173,12 +173,15 @@ def post_forward(x: torch.Tensor, bitdepth: int = 8, yuv420: bool = False) -> to
 
 def decode_forward(latent: torch.Tensor, sizes, ups_params: torch.Tensor, ups_k: int, n_ups: int, pre_k: int,
                    n_pre: int, layers, syn_params: torch.Tensor, gain: float = 16.0, quantize: bool = True,
-                   bitdepth: int = 8, yuv420: bool = False, head: int = 0, fold: bool = False) -> torch.Tensor:
+                   bitdepth: int = 8, yuv420: bool = False, head: int = 0, fold: bool = False,
+                   walk: bool = True) -> torch.Tensor:
     """Fused upsampling -> synthesis -> post (ccmi_decode_forward_f32): latent [B, N] ->
     post-processed frames (layout of post_forward), or with bitdepth=0 the raw synthesis
     output [B, C_out, H, W].  head: ccmi.HEAD_* (the 1x1 head on the VALU or on f32 MFMA).
     fold=True also evaluates the level-2 -> 1 upsampling step inside the fused kernel (stages
     bit 3, opt-in: the same values bit for bit, measured slower).
+    walk=False gives every workgroup of the fused kernel a single window instead of a run of
+    them (stages bit 4: the same values bit for bit, every window pays the vertical halo).
     Raises CcmiError(ERR_UNSUPPORTED) for architectures without a fused kernel (use
     ups_forward / syn_forward / post_forward)."""
     squeeze = latent.dim() == 1
@@ -215,11 +218,24 @@ def decode_forward(latent: torch.Tensor, sizes, ups_params: torch.Tensor, ups_k:
                   B, L, H, W, syn_stride)
     y.in_ = None
     a = DecodeArgs(ups=u, syn=y, bitdepth=int(bitdepth), yuv420=int(bool(yuv420)), out=ptr(out), out_stride=n,
-                   head=int(head), stages=8 if fold else 0)
+                   head=int(head), stages=(8 if fold else 0) | (0 if walk else 16))
     check(lib().ccmi_decode_forward_f32(a, stream_handle(latent.device)))
     if bitdepth == 0 or not yuv420:
         out = out.view(B, n_out, H, W)
     return out[0] if squeeze else out
+
+
+def fused_run_plan(h: int, n_sp: int, cap: int = 0):
+    """Rows of an h-row frame by run of the fused kernel (ccmi_fused_run_plan, host only):
+    (cap applied, [(first output row, windows)] per run).  cap < 1: the library's default."""
+    import ctypes as C
+    cap_used = C.c_int(0)
+    n = lib().ccmi_fused_run_plan(h, n_sp, cap, None, None, 0, C.byref(cap_used))
+    if n < 0:
+        raise ValueError(f"run plan: h={h} n_sp={n_sp}")
+    start, wins = (C.c_int * n)(), (C.c_int * n)()
+    lib().ccmi_fused_run_plan(h, n_sp, cap, start, wins, n, None)
+    return cap_used.value, list(zip(start, wins))
 
 
 def split_420(flat: torch.Tensor, H: int, W: int) -> dict:

@@ -44,7 +44,8 @@ struct FusedArgs {
     int hid;             // hidden width of a 2-layer head
     int head_mfma;       // 2-layer head on the f32 MFMA form (fwd_syn.hip, CCMI_HEAD_MFMA)
     int head_generic;    // never the unrolled 48-wide head (CCMI_HEAD_GENERIC, a test form)
-    int ntiles;          // windows per frame (the fused kernel's 1-D grid is ntiles x batch)
+    int ntiles;          // runs per frame (the fused kernel's 1-D grid is ntiles x batch)
+    int run_base, run_extra; // a strip's run i walks run_base + (i < run_extra) windows (RunPlan)
     int w0_off, b0_off, relu0;
     int w1_off, b1_off, relu1;
     int n_sp;            // 3x3 layers after the head
@@ -63,6 +64,33 @@ struct Plan {
     int hid, cmid;
     FusedArgs fa;
 };
+
+// Run plan of the fused kernel: a workgroup walks a run of consecutive windows (rh head rows
+// each) down one column strip.  With h 3x3 layers a run of n windows emits rh n - 2 h rows
+// (only its first window pays the vertical halo), run i starts at the row where run i - 1
+// ended and the last run is clipped at H.  R caps the windows of one run (h = 0: 1, there is
+// no halo to save).  The windows are dealt as evenly as possible, longer runs first: run i
+// holds base + (i < extra) of them.
+#ifndef CCMI_FUSED_RUN
+#define CCMI_FUSED_RUN 6
+#endif
+struct RunPlan {
+    int n_runs, base, extra;
+};
+inline RunPlan fused_run_plan(int H, int h, int R, int rh)
+{
+    if (h == 0 || R < 1) R = 1;
+    const int per = rh * R - 2 * h; // rows a full-length run emits
+    const int n_runs = (H + per - 1) / per;
+    const int windows = (H + 2 * h * n_runs + rh - 1) / rh;
+    return RunPlan{n_runs, windows / n_runs, windows % n_runs};
+}
+inline int run_windows(const RunPlan &p, int i) { return p.base + (i < p.extra ? 1 : 0); }
+// first output row of run i
+inline int run_start(const RunPlan &p, int i, int h, int rh)
+{
+    return rh * (i * p.base + (i < p.extra ? i : p.extra)) - 2 * h * i;
+}
 
 // Offsets of each layer's weights / biases in a frame's parameter block.
 void layer_offsets(const ccmi_syn_args *a, int *w_off, int *b_off, int *cin_of, int64_t *total);

@@ -8,14 +8,18 @@
 //
 // Fast path (every architecture made of a 1x1 "MLP" head followed by 3x3 layers with
 // <= 4 channels -- all the reference presets: hop, mop, lop, ...): ONE fused kernel per
-// launch.  A workgroup owns a 32 x 64 pixel window.  Pass 0 evaluates the per-pixel MLP
-// (c_in -> hid -> c_mid, weights from LDS records) on the whole window (output tile plus a
-// halo of one pixel per 3x3 layer) and keeps its c_mid outputs in registers; each 3x3 layer
-// then shrinks the valid region by one pixel, in registers (the horizontal taps across lanes
-// by DPP, the vertical ones from the thread's own rows and its neighbours' edge rows through
-// LDS); the last layer writes to HBM.  Replicate padding is reproduced by evaluating halo
-// pixels at the clamped image coordinate.  HBM traffic: c_in planes read once (+ halo),
-// c_out planes written once.
+// launch.  A workgroup walks a run of consecutive 32 x 64 pixel windows down one column strip
+// (fwd_common.h fused_run_plan: at most CCMI_FUSED_RUN windows).  Per window, pass 0 evaluates
+// the per-pixel MLP (c_in -> hid -> c_mid, weights from LDS records) on the whole window and
+// keeps its c_mid outputs in registers; each 3x3 layer then works in registers (the horizontal
+// taps across lanes by DPP, the vertical ones from the thread's own rows and the last two rows
+// of the thread above through LDS) and writes its output one row up, so that a window needs
+// nothing from below: the two rows above its first come from the run's previous window (a
+// small carry area in LDS).  Only a run's first window pays the vertical halo (its top two
+// rows per 3x3 layer are not stored); columns lose one pixel per 3x3 layer on either side in
+// every window.  The last layer writes to HBM.  Replicate padding is reproduced by evaluating
+// pixels outside the image at the clamped image coordinate.  HBM traffic: c_in planes read
+// once (+ halo), c_out planes written once.
 //
 // Any other architecture runs the generic per-layer kernel (one launch per layer,
 // ping-pong through the caller's workspace).
@@ -32,10 +36,12 @@ constexpr int kThreads = 256;
 
 
 // Fused head + 3x3 tail.  The workgroup's working region is a fixed 32 x 64 window
-// (2048 pixels, 512 threads, 4 per thread): the output tile is the window minus a halo
-// of one pixel per 3x3 layer.  All stages share the window's coordinate frame (pitch
-// 64); stage t is valid on rows/cols [t, 32-t) x [t, 64-t).  Thread (c = tid & 63,
-// g = tid >> 6) owns column c of the 4 consecutive rows 4g .. 4g+3 in every stage.
+// (2048 pixels, 512 threads, 4 per thread), moved down by 32 rows per iteration of the run.
+// Thread (c = tid & 63, g = tid >> 6) owns column c and the register rows 4g .. 4g+3; with the
+// window's head rows at image rows oy .. oy+31, register row r of stage t (the output of t
+// 3x3 layers) holds image row oy + r - t.  Stage t is valid on columns [t, 64-t); on rows it
+// is valid everywhere except above row oy + t in a run's first window (no carry yet).  So
+// after n_sp layers a run's first window stores 32 - 2 n_sp rows and every later one 32.
 //  * head: packed fp32 (v_pk_fma_f32) over pixel pairs, weight records broadcast from LDS,
 //    hidden activations consumed as they are produced (never stored);
 //  * 3x3 layers: in registers (see "3x3 layers, replicate padding" below).  Pixels outside
@@ -51,7 +57,6 @@ constexpr int kThreads = 256;
 #endif
 constexpr int kFThreads = CCMI_FUSED_THREADS;
 constexpr int kRW = 64, kRH = CCMI_FUSED_RH;
-constexpr int kPlane = kRW * (kRH + 2); // LDS plane: window rows -1 .. kRH (guard rows)
 constexpr int kRowsPerThread = kRH / (kFThreads / kRW); // 4
 constexpr int kNW = kFThreads / 64;                     // waves per workgroup (8)
 
@@ -72,7 +77,17 @@ constexpr int kNW = kFThreads / 64;                     // waves per workgroup (
 // 32-bit byte offsets from a wave-uniform base (a frame's planes stay below 4 GB, checked at
 // launch): the address is SGPR base + zero-extended VGPR offset, no 64-bit VALU arithmetic
 __device__ __forceinline__ float *at(float *base, uint32_t i) { return (float *)((char *)base + i * 4u); }
-__device__ __forceinline__ float ldu(const float *base, uint32_t byte) { return *(const float *)((const char *)base + byte); }
+__device__ __forceinline__ float ldu(const float *base, uint64_t byte) { return *(const float *)((const char *)base + byte); }
+// A 32-bit byte offset as the 64-bit register pair ldu() adds to its base, made in this window
+// and opaque: z is a zero the compiler cannot fold (a thread index >> 31).  From a plain zero
+// extension the compiler keeps one loop-invariant zero register for the upper halves, holds it
+// across the whole window loop and spills it there.
+__device__ __forceinline__ uint64_t off64(uint32_t byte, uint32_t z)
+{
+    uint64_t o = ((uint64_t)z << 32) | byte;
+    asm volatile("" : "+v"(o));
+    return o;
+}
 
 __device__ __forceinline__ void store_out(const FusedArgs &A, float *out, int64_t plane, int m, int gy, int gx, float v,
                                           const float *lut8)
@@ -118,6 +133,17 @@ __device__ __forceinline__ void rows_transpose4(const float (&v)[4], float (&t)[
     t[3] = __uint_as_float(b[1]);
 }
 
+// The kernarg segment through a pointer the compiler cannot see through: arguments read
+// through it are loaded after this point (scalar loads), not held in SGPRs from further up.
+// Only for code inlined into a kernel.
+typedef const __attribute__((address_space(4))) char *kernarg_ptr;
+__device__ __forceinline__ kernarg_ptr fresh_kernargs()
+{
+    kernarg_ptr p = (kernarg_ptr)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return p;
+}
+
 #if defined(CCMI_ARM_STAMPS)
 // diagnostic build (make stamps): per-phase cycle totals of the fused kernel, wave 0 of
 // every workgroup; read with ccmi_debug_fused_stamps()
@@ -144,6 +170,9 @@ constexpr int kTW = kRW + 7 - 1 + 2;              // raw latent tile pitch (70 u
 // gathers are done: 52 KB of LDS for the 7-grid hop decoder, three resident workgroups per CU
 // (measured: one workgroup per CU instead of two costs +41 %, tools/occ_probe.sh).
 constexpr int fused_groups(int cin, bool ups) { return ups && cin - 1 >= 4 ? 2 : 1; }
+// carry rows of a run: per 3x3 layer, the last two rows of the window's bottom wave, kept for
+// the top wave of the run's next window ([layer][2 rows][CMID][column])
+constexpr int fused_carry_floats(int cmid) { return kMaxSp * 2 * cmid * kRW; }
 constexpr int fused_lds_floats(int cin, int cmid, bool ups)
 {
     const int C = ups ? cin - 1 : 0, GC = (C + fused_groups(cin, ups) - 1) / fused_groups(cin, ups);
@@ -153,7 +182,7 @@ constexpr int fused_lds_floats(int cin, int cmid, bool ups)
     const int b0 = xr > raw ? xr : raw;
     int b1 = xr > stage ? xr : stage;
     b1 = b1 > kMaxHid * 16 + 256 ? b1 : kMaxHid * 16 + 256; // head records (+ the MFMA head's weight table)
-    return b0 + b1 + 256; // + the 8-bit quotient table
+    return b0 + b1 + fused_carry_floats(cmid) + 256; // + the runs' carry rows + the 8-bit quotient table
 }
 // waves per SIMD the register allocation must allow: 3 workgroups of 8 waves on 4 SIMDs when
 // the LDS fits three (<= 160 KB / 3), else 2
@@ -174,7 +203,7 @@ constexpr int fused_wpe(int cin, int cmid, bool ups, bool mh = false)
 // arguments): the level-1 values phase A needs are computed from the level-2 stack and the
 // level-1 latent instead of read from a level-1 stack in HBM (see "fold" below)
 template <int CIN, int CMID, bool UPS, bool MH = false, int HID = 0, bool FOLD = false>
-__global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused_wpe(CIN, CMID, UPS, MH)))) void syn_fused_kernel(FusedArgs A, LevelArgs U, LevelArgs U2)
+__global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused_wpe(CIN, CMID, UPS, MH)))) void syn_fused_kernel(FusedArgs Ak, LevelArgs Uk, LevelArgs U2k)
 {
     static_assert(!FOLD || (UPS && CIN >= 3), "the fold needs the fused level-1 -> 0 step and a level-2 stack");
     constexpr int NR = kRowsPerThread;
@@ -191,6 +220,7 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
     float *s_hs = s_pool + kBuf0;              // [GC][kHsRows][kRW]   (UPS only)
     float *s_hr = s_hs + GC * kHsRows * kRW;   // [kHrRows][kRW]       (UPS only)
     float *s_lut8 = s_pool + kTot - 256;
+    float *s_carry = s_lut8 - fused_carry_floats(CMID); // [kMaxSp][2][CMID][kRW]
 #if defined(CCMI_ARM_STAMPS)
     unsigned long long t_prev = __builtin_amdgcn_s_memtime();
 #endif
@@ -206,26 +236,54 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
     constexpr bool kPadRec = CIN + 1 + CMID <= 12;
     auto hr = [](int f) constexpr { return kPadRec ? f + f / 3 : f; };
 
-    // XCD-aware window order (raster order, frame after frame, a contiguous run per XCD):
-    // vertically adjacent windows re-read each other's halo rows from one L2
+    // XCD-aware order of the runs (raster order, frame after frame, a contiguous stretch per
+    // XCD): neighbouring strips re-read each other's halo columns from one L2
     const int wt = xcd_order(blockIdx.x, gridDim.x);
-    const int b = wt / A.ntiles, tile = wt - b * A.ntiles;
+    const int b0 = wt / Ak.ntiles, tile = wt - b0 * Ak.ntiles;
+    // the work item is a run: nwin consecutive windows of one column strip, the first one's
+    // head rows starting halo rows above the run's first output row (fused_run_plan)
+    const int ri = tile / Ak.tiles_x;
+    const int nwin = Ak.run_base + (ri < Ak.run_extra ? 1 : 0);
+    const int y0 = kRH * (ri * Ak.run_base + min(ri, Ak.run_extra)) - 2 * Ak.n_sp * ri;
+    const int x0 = (tile - ri * Ak.tiles_x) * (kRW - 2 * Ak.n_sp);
+    const int oy0 = y0 - Ak.n_sp, ox0 = x0 - Ak.n_sp; // global coords of the first window's (0,0)
+    // per-run table in LDS: the 8-bit output quotients (own area)
+    if (Ak.qmax == 255.f) s_lut8[threadIdx.x & 255] = (float)(threadIdx.x & 255) / 255.f;
+    // The walk.  The trip count is a function of the work item alone (scalar), every barrier
+    // below is reached by all waves in every iteration, and nothing leaves the loop early.
+#pragma clang loop unroll(disable)
+    for (int win = 0; win < nwin; ++win) {
+    // Loop-invariant values must not be hoisted out of this loop: held across a whole window
+    // they cost the kernel its 6 waves per SIMD.  So the thread index is an opaque copy per
+    // use (values derived from it, lane masks and LDS addresses, were hoisted and spilled),
+    auto tixf = []() __attribute__((always_inline)) {
+        int t = threadIdx.x;
+        asm volatile("" : "+v"(t));
+        return t;
+    };
+    // and the kernel's arguments are re-read from the kernarg segment in every window, through
+    // a pointer the compiler cannot see through (hoisted, they filled the SGPRs and the spilled
+    // ones took vector registers).
+    const auto kargs = fresh_kernargs();
+    constexpr size_t kOffU = (sizeof(FusedArgs) + alignof(LevelArgs) - 1) / alignof(LevelArgs) * alignof(LevelArgs);
+    constexpr size_t kOffU2 = (kOffU + sizeof(LevelArgs) + alignof(LevelArgs) - 1) / alignof(LevelArgs) * alignof(LevelArgs);
+    const FusedArgs &A = *(const FusedArgs *)kargs;
+    const LevelArgs &U = *(const LevelArgs *)(kargs + kOffU);
+    const LevelArgs &U2 = *(const LevelArgs *)(kargs + kOffU2);
     const int halo = A.n_sp;
-    const int TX = kRW - 2 * halo, TY = kRH - 2 * halo;
-    const int y0 = (tile / A.tiles_x) * TY;
-    const int x0 = (tile % A.tiles_x) * TX;
-    const int oy = y0 - halo, ox = x0 - halo; // global coords of window (0,0)
+    // (the frame and the strip's column likewise: what the compiler derives from them is a few
+    // scalar instructions per window, hoisted it occupies SGPRs across the loop)
+    int b = b0, ox = ox0;
+    asm volatile("" : "+s"(b), "+s"(ox));
+    const int oy = oy0 + kRH * win; // image row of this window's head row 0
     const cfloat_ptr prm = (cfloat_ptr)(size_t)(A.params + (int64_t)b * A.pstride);
     const float *in = A.in + (int64_t)b * A.in_stride;
     float *out = A.out + (int64_t)b * A.out_stride;
     const int64_t plane = (int64_t)A.H * A.W;
-    // lane-derived indices; re-derived after the head (below) so that they are not live
-    // across it: held there they were the kernel's 5 spilled VGPRs (scratch traffic
-    // in every wave)
-    int c = threadIdx.x & (kRW - 1);
-    int rb = (threadIdx.x >> 6) * NR; // first window row of this thread
-    int gx = ox + c;
-    int cxg = clampi(gx, A.W - 1);
+    // lane-derived indices; re-derived at the top of every window and after the head (below) so
+    // that they are not live across the head or the loop's back edge: held across the head
+    // they were the kernel's 5 spilled VGPRs (scratch traffic in every wave)
+    int c, rb, gx, cxg; // column, first window row of this thread, image column, clamped
     auto reidx = [&]() {
         int t = threadIdx.x;
         asm volatile("" : "+v"(t)); // an opaque copy: the compiler cannot reuse the old values
@@ -236,10 +294,8 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
     };
 
     const float *lut8 = A.qmax == 255.f ? s_lut8 : nullptr;
-    // per-frame tables in LDS: the 8-bit output quotients (own area, staged at once) and the
-    // head's weight records (region 1: before anything else without fused upsampling, after
-    // the gathers with it)
-    if (lut8) s_lut8[threadIdx.x & 255] = (float)(threadIdx.x & 255) / 255.f;
+    // per-frame table in LDS: the head's weight records (region 1: before anything else
+    // without fused upsampling, after the gathers with it)
     // the records (L2-resident: every workgroup of a frame reads the same ones) are fetched
     // into two registers before the last upsampling group, so their latency hides behind its
     // passes, and staged once region 1 is free
@@ -249,7 +305,7 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
     constexpr float kW0Scale = kScaledRelu ? 0x1p-32f : 1.f, kW1Scale = kScaledRelu ? 0x1p32f : 1.f;
     float hv[kHeadRegs];
     auto load_head = [&]() {
-        const int tid = threadIdx.x;
+        const int tid = tixf();
 #pragma unroll
         for (int k = 0; k < kHeadRegs; ++k) {
             const int i = tid + k * kFThreads, j = i >> 4, f = i & 15;
@@ -265,7 +321,7 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
         }
     };
     auto stage_head = [&]() {
-        const int tid = threadIdx.x;
+        const int tid = tixf();
 #pragma unroll
         for (int k = 0; k < kHeadRegs; ++k) {
             const int i = tid + k * kFThreads, j = i >> 4, f = i & 15;
@@ -283,6 +339,7 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
             }
         }
     };
+    reidx();
     if constexpr (!UPS) {
         load_head();
         stage_head();
@@ -297,8 +354,11 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
     // channel for 4 pixels, offsets fixed by the parity of the window's first row
     const bool interior = oy >= 0 && oy + kRH <= A.H;
     if constexpr (UPS) {
+        // the level's taps, re-read per window through the constant address space (scalar loads
+        // even behind the previous window's stores): held in SGPRs across the head and the 3x3
+        // layers they cost the kernel its 6 waves per SIMD
         float wu[8], wr[7];
-        const float *uprm = U.params + (int64_t)b * U.pstride;
+        const cfloat_ptr uprm = (cfloat_ptr)(size_t)(U.params + (int64_t)b * U.pstride);
 #pragma unroll
         for (int k = 0; k < 8; ++k) wu[k] = uprm[U.up_off + k];
 #pragma unroll
@@ -309,8 +369,8 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
         // Row addresses are wave-uniform (scalar), so a load costs no VALU index math, and a
         // wave's horizontal passes read back only rows it wrote itself -- a wave-level fence
         // instead of a workgroup barrier between the raw tiles and the horizontal passes.
-        const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-        const int lane = threadIdx.x & 63;
+        const int wv = __builtin_amdgcn_readfirstlane((int)(tixf() >> 6));
+        const int lane = tixf() & 63;
         constexpr int kSR = GC * kHsRows, kSU = (kSR + kNW - 1) / kNW; // a group's source rows, per wave
         constexpr int kLU = (kHrRows + kNW - 1) / kNW;         // latent rows per wave
         static_assert(kSW <= 64 && kTW <= 128 && kTW > 64 && kHsRows >= kNW, "lane = raw column, one row wrap per step");
@@ -325,7 +385,8 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
         {
             const int splane = U.hs * U.ws;
             // lanes past the tile re-read the last column (same cache lines, no extra fetch)
-            const uint32_t scol = 4u * (uint32_t)clampi(ibase + (lane < kSW ? lane : kSW - 1), U.ws - 1);
+            const uint32_t zhi = (uint32_t)tixf() >> 31; // 0
+            const uint64_t scol = off64(4u * (uint32_t)clampi(ibase + (lane < kSW ? lane : kSW - 1), U.ws - 1), zhi);
 #pragma unroll
             for (int G = 0; G < NG; ++G)
 #pragma unroll
@@ -346,12 +407,12 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
                     }
                 }
             // latent tile: zero outside the image (the refine's zero padding)
-            uint32_t tx[2];
+            uint64_t tx[2];
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
                 const int X = Xa - 3 + (lane + 64 * h < kTW ? lane + 64 * h : kTW - 1);
                 tin[h] = X >= 0 && X < U.wd;
-                tx[h] = 4u * (uint32_t)clampi(X, U.wd - 1);
+                tx[h] = off64(4u * (uint32_t)clampi(X, U.wd - 1), zhi);
             }
 #pragma unroll
             for (int u = 0; u < kLU; ++u) {
@@ -386,18 +447,18 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
             float *f_ref = f_lat + kFLR * kFLP;          // [kFLR][kFP]   refine, horizontal
             float *f_src = f_ref + kFLR * kFP;           // [C2][kF2R][kF2P]
             float *f_h2 = f_src + C2 * kF2R * kF2P;      // [C2][kF2R][kFP] transposed conv, horizontal
-            static_assert(kFLR * kFLP + kFLR * kFP + C2 * kF2R * (kF2P + kFP) <= kTot - 256, "fold tiles fit before the LUT");
+            static_assert(kFLR * kFLP + kFLR * kFP + C2 * kF2R * (kF2P + kFP) <= kTot - 256 - fused_carry_floats(CMID), "fold tiles fit before the carry rows");
             const int hs1 = U.hs, ws1 = U.ws, hs2 = U2.hs, ws2 = U2.ws;
             const int R0 = clampi(jbase, hs1 - 1), R1 = clampi(jbase + kHsRows - 1, hs1 - 1);
             const int C0 = clampi(ibase, ws1 - 1);
             const int r2 = (R0 >> 1) + FT::D0, c2 = (C0 >> 1) + FT::D0; // level-2 origin of the tile
-            const float *uprm2 = U2.params + (int64_t)b * U2.pstride;
+            const cfloat_ptr uprm2 = (cfloat_ptr)(size_t)(U2.params + (int64_t)b * U2.pstride);
             float wu2[8], wr2[7];
 #pragma unroll
             for (int k = 0; k < 8; ++k) wu2[k] = uprm2[U2.up_off + k];
 #pragma unroll
             for (int k = 0; k < 7; ++k) wr2[k] = uprm2[U2.pre_off + k];
-            const int tid = threadIdx.x;
+            const int tid = tixf();
             // F1: every load in flight before the first LDS store
             {
                 const float *l1 = U2.ref_src + (int64_t)b * U2.ref_stride;
@@ -683,6 +744,7 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
     f2 img[NR / 2][CMID];
     // ------------------------ pass 0: per-pixel 1x1 head ------------------------
     {
+        const FusedArgs &A = *(const FusedArgs *)fresh_kernargs(); // (re-read: see the top of the loop)
         const cfloat_ptr w0 = prm + A.w0_off, b0 = prm + A.b0_off;
         const cfloat_ptr b1 = prm + A.b1_off;
         float o[NR][CMID];
@@ -698,7 +760,7 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
             // from the accumulators; per window row, four 16-pixel groups per wave
             static_assert(HID % 16 == 0 && HID <= kMaxHid && CIN + 1 <= 8 && CMID <= 4, "f32-MFMA head shape");
             constexpr int NT = HID / 16;
-            const int lane = threadIdx.x & 63, lr = lane & 15, lg = lane >> 4;
+            const int lane = tixf() & 63, lr = lane & 15, lg = lane >> 4;
             __syncthreads(); // s_head / s_w1p staged
             float a1[NT][2]; // A[m = lr][k = lg] of K-step s: W0[16 mt + lr][4 s + lg] (channel c_in: the bias)
 #pragma unroll
@@ -868,7 +930,7 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
         }
         FSTAMP(3);
         reidx();
-        if (halo == 0) {
+        if (halo == 0) { // head-only decoders: single-window runs, stored here (wave-uniform)
 #pragma unroll
             for (int p = 0; p < NR; ++p) {
                 const int gy = oy + rb + p;
@@ -876,7 +938,6 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
 #pragma unroll
                     for (int m = 0; m < CMID; ++m) store_out(A, out, plane, m, gy, gx, o[p][m], lut8);
             }
-            return;
         }
 #pragma unroll
         for (int q = 0; q < NR / 2; ++q)
@@ -886,31 +947,38 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
 
     // ------------------------ 3x3 layers, replicate padding ------------------------
     // Register form: a stage's image stays in the registers of the thread that computed it
-    // (lane = window column, the thread's 4 rows); only each thread's first and last row go
-    // through LDS, for the threads above and below (one wave each: a wave is 4 whole window
-    // rows).  The horizontal taps never touch LDS: for output channel m the thread forms the
+    // (lane = window column, the thread's 4 rows).  Skewed rows: a thread holding input rows
+    // r .. r+3 produces output rows r-1 .. r+2 from its own rows and the last two rows of the
+    // thread above (one wave up: a wave is 4 whole window rows), so only each thread's last two
+    // rows go through LDS and nothing is needed from below.  The top wave takes those two rows
+    // from the carry area, where the bottom wave left them in the run's previous window.  The
+    // horizontal taps never touch LDS: for output channel m the thread forms the
     // three column partial sums S_dx = sum_{k,dy} w[m][k][dy][dx] x_k(row + dy - 1) of its own
     // column, and out(c) = S_1(c) + S_0(c - 1) + S_2(c + 1), the neighbours' sums read across
     // lanes by DPP (v_add_f32 wave_shr:1 / wave_shl:1).  (The LDS form read 3 x 3 x CMID
     // neighbours per pixel from an LDS image and was LDS-bandwidth bound: 120 ds_read per
     // thread and layer.)  Replicate padding: every stage is evaluated at all window pixels,
     // and a value outside the image stands for the nearest image pixel --
-    //  * rows (wave-uniform): a thread reading rows rb-1 .. rb+4 replaces those outside the
+    //  * rows (wave-uniform): a thread reading rows r-2 .. r+3 replaces those outside the
     //    image by the nearest in-image row among them (the only rows an in-image output
-    //    reads: the edge row itself is the thread's own or its neighbour's);
+    //    reads: the edge row itself is the thread's own or one of the two from above);
     //  * columns: the head is evaluated at clamped columns, and each 3x3 layer's output at
     //    lanes outside the image is replaced by the edge lane's (v_readlane), so the next
     //    layer's column sums there are the edge column's.
-    // Window rows 0 / kRH-1 and columns 0 / kRW-1 read garbage neighbours (other window or
-    // DPP zero fill); they are outside every later stage's valid band [t, kRW - t).
-    // Halo rows exchange buffers, double-buffered by layer parity: [top, bottom][CMID][thread].
+    // Columns 0 / kRW-1 read garbage neighbours (DPP zero fill); they are outside every later
+    // stage's valid band [t, kRW - t).  In a run's first window the carry rows are garbage:
+    // stage t is valid from row t of that window on, and the 2 n_sp top rows of its last stage
+    // (labels oy - n_sp .. oy + n_sp - 1) are not stored.
+    // Exchange buffers, double-buffered by layer parity: [last two rows][CMID][thread].
+    if (halo != 0) {
+    const FusedArgs &A = *(const FusedArgs *)fresh_kernargs(); // (re-read: see the top of the loop)
     float *xb0 = s_pool, *xb1 = s_pool + kBuf0;
     auto publish = [&](float *xb) __attribute__((always_inline)) {
-        const int tid = threadIdx.x;
+        const int tid = tixf();
 #pragma unroll
         for (int m = 0; m < CMID; ++m) {
-            xb[m * kFThreads + tid] = img[0][m].x;                      // row rb
-            xb[(CMID + m) * kFThreads + tid] = img[NR / 2 - 1][m].y;   // row rb + 3
+            xb[m * kFThreads + tid] = img[NR / 2 - 1][m].x;            // the thread's row NR - 2
+            xb[(CMID + m) * kFThreads + tid] = img[NR / 2 - 1][m].y;   // and row NR - 1
         }
     };
     auto shr1 = [](float v) __attribute__((always_inline)) { // lane c <- lane c - 1 (0 at lane 0)
@@ -919,31 +987,55 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
     auto shl1 = [](float v) __attribute__((always_inline)) { // lane c <- lane c + 1 (0 at lane 63)
         return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x130, 0xf, 0xf, true));
     };
-    const bool rows_inner = oy > 0 && oy + kRH < A.H;          // rows -1 .. kRH all in the image
+    // every row any stage touches (oy - n_sp - 1 .. oy + kRH - 1) in the image
+    const bool rows_inner = oy - halo - 1 >= 0 && oy + kRH <= A.H;
     const bool cols_inner = ox >= 0 && ox + kRW <= A.W;        // every lane an image column
-    // one 3x3 layer: img (stage s input) -> img (stage s output); the non-last layers publish
-    // their output's halo rows into xout
+    // one 3x3 layer: img (stage s input) -> img (stage s output, one row up); the non-last
+    // layers publish their output's last two rows into xout
     auto layer = [&](auto LAST, int s, const float *xin, float *xout) __attribute__((always_inline)) {
         constexpr bool last = decltype(LAST)::value;
+        const int tid = tixf();
+        const int wrow = __builtin_amdgcn_readfirstlane(tid >> 6) * NR; // rb, wave-uniform
+        float *cr = s_carry + s * (2 * CMID * kRW) + (tid & (kRW - 1)); // this layer's carry rows, own column
+        // the thread's input rows r-2 .. r+3 (r = oy + rb - s) of every input channel: v[0], v[1]
+        // from the thread above, or for the top wave from the carry of the run's previous
+        // window -- read before the barrier, because the bottom wave overwrites it after it
+        float v[NR + 2][CMID];
+        if (wrow == 0) {
+#pragma unroll
+            for (int m = 0; m < CMID; ++m) {
+                v[0][m] = cr[m * kRW];
+                v[1][m] = cr[(CMID + m) * kRW];
+            }
+        }
         __syncthreads(); // xin published by every wave (and the previous reads of xout done)
         const cfloat_ptr wt = prm + A.sp[s].w_off;
         const cfloat_ptr bs = prm + A.sp[s].b_off;
         const f2 lo = f2(A.sp[s].relu ? 0.f : -INFINITY);
         const f2 rsd = f2(A.sp[s].residual ? 1.f : 0.f);
-        const int tid = threadIdx.x;
-        const int wrow = __builtin_amdgcn_readfirstlane(tid >> 6) * NR; // rb, wave-uniform
-        const int tup = wrow > 0 ? tid - 64 : tid, tdn = wrow + NR < kRH ? tid + 64 : tid;
-        // rows rb-1 .. rb+4 of every input channel
-        float v[NR + 2][CMID];
+        if (wrow != 0) {
 #pragma unroll
-        for (int m = 0; m < CMID; ++m) {
-            v[0][m] = xin[(CMID + m) * kFThreads + tup];
-            v[NR + 1][m] = xin[m * kFThreads + tdn];
+            for (int m = 0; m < CMID; ++m) {
+                v[0][m] = xin[m * kFThreads + tid - kRW];
+                v[1][m] = xin[(CMID + m) * kFThreads + tid - kRW];
+            }
+        }
 #pragma unroll
-            for (int p = 0; p < NR; ++p) v[p + 1][m] = (p & 1) ? img[p / 2][m].y : img[p / 2][m].x;
+        for (int m = 0; m < CMID; ++m)
+#pragma unroll
+            for (int p = 0; p < NR; ++p) v[p + 2][m] = (p & 1) ? img[p / 2][m].y : img[p / 2][m].x;
+        if (wrow == kRH - NR) {
+            // the bottom wave's last two rows are rows -2, -1 of the next window (the top wave
+            // has read the previous ones before the barrier above; the next read is behind the
+            // barrier that closes this window)
+#pragma unroll
+            for (int m = 0; m < CMID; ++m) {
+                cr[m * kRW] = v[NR][m];
+                cr[(CMID + m) * kRW] = v[NR + 1][m];
+            }
         }
         if (!rows_inner) {
-            const int gy0 = oy + wrow - 1; // image row of v[0]
+            const int gy0 = oy + wrow - 2 - s; // image row of v[0]
 #pragma unroll
             for (int i = 1; i < NR + 2; ++i)
                 if (gy0 + i >= A.H)
@@ -955,7 +1047,8 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
 #pragma unroll
                     for (int m = 0; m < CMID; ++m) v[i][m] = v[i + 1][m];
         }
-        // packed row pairs: P[r][k] = {row rb - 1 + r, row rb + r}, r = 0 .. NR
+        // packed row pairs: P[r][k] = {v[r], v[r + 1]}, r = 0 .. NR; output row pair q (the
+        // thread's rows 2q, 2q + 1 of the next stage) is centred on P[2q + 1]
         f2 P[NR + 1][CMID];
 #pragma unroll
         for (int r = 0; r <= NR; ++r)
@@ -989,7 +1082,7 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
                 f2 acc;
                 acc.x = (S[1][q].x + shr1(S[0][q].x)) + shl1(S[2][q].x);
                 acc.y = (S[1][q].y + shr1(S[0][q].y)) + shl1(S[2][q].y);
-                // residual: the input at the centre (row pair 2q + 1 = rows rb + 2q, rb + 2q + 1)
+                // residual: the input at the centre (row pair 2q + 1 = v[2q + 1], v[2q + 2])
                 nxt[q][m] = __builtin_elementwise_max(__builtin_elementwise_fma(rsd, P[2 * q + 1][m], acc), lo);
             }
         }
@@ -1048,8 +1141,10 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
             constexpr int fmt = tab ? md - 2 : md;
 #pragma unroll
             for (int p = 0; p < NR; ++p) {
-                const int r = rb + p, gy = oy + r;
-                if (!(col_ok && r >= t && r < kRH - t && gy < A.H)) continue;
+                // register row r holds image row oy + r - t (one row up per layer); a run's
+                // first window has no valid rows above its row 2 t
+                const int r = rb + p, gy = oy + r - t;
+                if (!(col_ok && (win > 0 || r >= 2 * t) && gy < A.H)) continue;
                 const uint32_t px = (uint32_t)(gy * A.W + gx);
                 const bool cy_ok = fmt == 2 && cx_ok && !(gy & 1) && (gy >> 1) < (A.H >> 1);
                 const uint32_t cpx = (uint32_t)((gy >> 1) * (int)cw + (gx >> 1));
@@ -1073,7 +1168,12 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
         } else if (A.yuv420) emit(std::integral_constant<int, 2>{});
         else emit(std::integral_constant<int, 1>{});
     }
+    } // halo != 0
     FSTAMP(4);
+    // the next window's phase A overwrites regions 0 / 1 (this window's exchange buffers and
+    // head records); the carry rows were written before this barrier
+    __syncthreads();
+    } // the run's windows
 }
 
 // Generic layer: any ks (odd), any channel counts; replicate padding.
@@ -1168,6 +1268,16 @@ bool launch_fused_mfma_head(dim3 grid, hipStream_t s, const FusedArgs &fa, const
 // the folded form (level 2 -> 1 in the kernel): the headline decoder only (7 grids, 48-wide
 // VALU head, 3-channel tail)
 bool fold_eligible(const FusedArgs &fa, int cmid) { return cmid == 3 && unrolled_head(fa) && !fa.head_mfma; }
+
+// the fused kernel's grid for one frame: column strips x runs of at most cap windows
+void set_runs(FusedArgs &f, int cap)
+{
+    const RunPlan rp = fused_run_plan(f.H, f.n_sp, cap, kRH);
+    f.tiles_x = ccmi_div_up(f.W, kRW - 2 * f.n_sp);
+    f.ntiles = f.tiles_x * rp.n_runs;
+    f.run_base = rp.base;
+    f.run_extra = rp.extra;
+}
 
 } // namespace
 
@@ -1270,9 +1380,7 @@ int ccmi_launch_syn_f32(const ccmi_syn_args *a, hipStream_t s)
         P.fa.pstride = a->param_stride;
         P.fa.out = a->out;
         P.fa.out_stride = a->out_stride;
-        const int halo = P.fa.n_sp;
-        P.fa.tiles_x = ccmi_div_up(a->w, kRW - 2 * halo);
-        P.fa.ntiles = P.fa.tiles_x * ccmi_div_up(a->h, kRH - 2 * halo);
+        set_runs(P.fa, CCMI_FUSED_RUN);
         dim3 grid((unsigned)(P.fa.ntiles * a->batch));
         if (P.cmid == 3) launch_fused<3, false>(grid, s, P.fa, LevelArgs{});
         else launch_fused<4, false>(grid, s, P.fa, LevelArgs{});
@@ -1359,9 +1467,8 @@ extern "C" int ccmi_decode_forward_f32(const ccmi_decode_args *a, void *stream)
     P.fa.out_stride = a->out_stride;
     P.fa.qmax = a->bitdepth > 0 ? (float)((1 << a->bitdepth) - 1) : 0.f;
     P.fa.yuv420 = a->yuv420;
-    const int halo = P.fa.n_sp;
-    P.fa.tiles_x = ccmi_div_up(y.w, kRW - 2 * halo);
-    P.fa.ntiles = P.fa.tiles_x * ccmi_div_up(y.h, kRH - 2 * halo);
+    // stages bit 4: single-window runs (the geometry without the walk), for A/B runs and tests
+    set_runs(P.fa, (stages & 16) ? 1 : CCMI_FUSED_RUN);
     dim3 grid((unsigned)(P.fa.ntiles * y.batch));
     if (fold) {
         hipLaunchKernelGGL((syn_fused_kernel<7, 3, true, false, 48, true>), grid, dim3(kFThreads), 0, s, P.fa, last, prev);
@@ -1372,6 +1479,21 @@ extern "C" int ccmi_decode_forward_f32(const ccmi_decode_args *a, void *stream)
     }
     CCMI_HIP_CHECK(hipGetLastError());
     return CCMI_OK;
+}
+
+extern "C" int ccmi_fused_run_plan(int h, int n_sp, int cap, int *start, int *windows, int max_runs, int *cap_used)
+{
+    if (h < 1 || n_sp < 0 || 2 * n_sp >= kRH || max_runs < 0 || (max_runs > 0 && (!start || !windows)))
+        return ccmi_set_error(CCMI_ERR_ARG, "run plan: h=%d n_sp=%d max_runs=%d", h, n_sp, max_runs), -1;
+    if (cap < 1) cap = CCMI_FUSED_RUN;
+    if (n_sp == 0) cap = 1;
+    if (cap_used) *cap_used = cap;
+    const RunPlan rp = fused_run_plan(h, n_sp, cap, kRH);
+    for (int i = 0; i < rp.n_runs && i < max_runs; ++i) {
+        start[i] = run_start(rp, i, n_sp, kRH);
+        windows[i] = run_windows(rp, i);
+    }
+    return rp.n_runs;
 }
 
 #if defined(CCMI_ARM_STAMPS)

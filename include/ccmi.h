@@ -178,7 +178,10 @@ typedef struct ccmi_decode_args {
                                lets a caller time the two apart.  bit 3 (opt-in, the 7-grid
                                48-wide-head decoders): the fused kernel also evaluates the
                                level-2 -> 1 step and the pyramid stops at level 2 (same values
-                               bit for bit; measured slower) */
+                               bit for bit; measured slower).  bit 4: the
+                               fused kernel's runs hold one window each (cap 1 of
+                               ccmi_fused_run_plan: every window pays the vertical halo; same
+                               values bit for bit, for A/B runs and tests) */
     int head;               /* synthesis 1x1 head arithmetic, CCMI_HEAD_*: both are fp32 (the
                                MFMA form's products are exact f32 fmas, summed in another
                                order); MFMA needs 7 inputs, 48 hidden units and >= 1 3x3 layer
@@ -189,6 +192,15 @@ typedef struct ccmi_decode_args {
 } ccmi_decode_args;
 enum { CCMI_HEAD_DEFAULT = 0, CCMI_HEAD_VALU = 1, CCMI_HEAD_MFMA = 2, CCMI_HEAD_GENERIC = 3 };
 int ccmi_decode_forward_f32(const ccmi_decode_args *args, void *stream);
+
+/* Host only (no device call): how the fused kernel splits the h rows of a frame into runs.
+ * A workgroup walks a run of consecutive 32-row windows down a column strip; with n_sp 3x3
+ * layers a run of n windows emits 32 n - 2 n_sp rows.  cap is the most windows a run may
+ * hold (< 1: the library's built default; n_sp == 0: always 1).  Returns the number of runs
+ * (-1 on a bad argument) and fills the first output row and the window count of the first
+ * max_runs of them; run i ends where run i + 1 starts, the last one at h.  cap_used (may be
+ * NULL) receives the cap applied. */
+int ccmi_fused_run_plan(int h, int n_sp, int cap, int *start, int *windows, int max_runs, int *cap_used);
 
 /* ------------------------------------------------------------------------- */
 /* Path B: fixed-point .cool decoder, bit-exact with coolchic/cpp.             */
