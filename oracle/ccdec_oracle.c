@@ -629,7 +629,7 @@ static inline int32_t syn_act(int32_t s, int relu)
 static void syn_fused(const int32_t *w0, const int32_t *b0, const int32_t *w1, const int32_t *b1,
                       int nin, int nhid, int nout, const int32_t *in, int32_t *out, size_t npx)
 {
-    int32_t hid[256], v[64];
+    int32_t hid[CCO_MAX_HID], v[64];
     for (size_t p = 0; p < npx; p++) {
         for (int i = 0; i < nin; i++) v[i] = in[(size_t)i * npx + p];
         for (int j = 0; j < nhid; j++) {
@@ -727,6 +727,85 @@ static int run_syn(const hdr_t *h, const nets_t *nn, cco_frame *f)
         free(r);
     }
     f->syn_out = acc;
+    return 0;
+}
+
+/* ------------------------------------------------------------------------- */
+/* The two tail stages on caller arrays (tests: architectures no stream holds) */
+/* ------------------------------------------------------------------------- */
+
+/* run_ups on raw arrays: lat = the grids one after another (value << ARM_PREC), kernels = n_ups
+ * full (mirrored) ups_ks-tap kernels, then n_pre pre_ks-tap ones; out = n_grids x lh[0] x lw[0]. */
+int cco_ups_forward(int n_grids, const int *lh, const int *lw, const int32_t *lat, int ups_ks, int n_ups,
+                    int pre_ks, int n_pre, const int32_t *kernels, int32_t *out)
+{
+    if (n_grids < 1 || n_grids > CCO_MAX_LAYERS || ups_ks < 2 || ups_ks > 16 || pre_ks < 1 || pre_ks > 16 ||
+        n_ups < 1 || n_ups > CCO_MAX_LAYERS || n_pre < 1 || n_pre > CCO_MAX_LAYERS)
+        return 1;
+    hdr_t h;
+    memset(&h, 0, sizeof(h));
+    h.n_ups = n_ups; h.ups_ks = ups_ks; h.n_pre = n_pre; h.pre_ks = pre_ks;
+    nets_t *nn = (nets_t *)calloc(1, sizeof(nets_t));
+    for (int l = 0; l < n_ups; l++) memcpy(nn->ups[l], kernels + (size_t)l * ups_ks, sizeof(int32_t) * (size_t)ups_ks);
+    kernels += (size_t)n_ups * ups_ks;
+    for (int l = 0; l < n_pre; l++) memcpy(nn->pre[l], kernels + (size_t)l * pre_ks, sizeof(int32_t) * (size_t)pre_ks);
+    cco_frame f;
+    memset(&f, 0, sizeof(f));
+    f.h = lh[0]; f.w = lw[0]; f.n_layers = n_grids;
+    int zero[CCO_MAX_LAYERS] = {0};
+    for (int l = 0; l < n_grids; l++) {
+        f.lh[l] = lh[l]; f.lw[l] = lw[l];
+        f.lat[l] = (int32_t *)lat; /* read only */
+        lat += (size_t)lh[l] * lw[l];
+    }
+    f.syn_in = out;
+    run_ups(&h, nn, &f, zero);
+    free(nn);
+    return 0;
+}
+
+/* One synthesis branch on raw arrays, layer by layer as run_branch: layers = n_layers x
+ * (n_out, ks, residual, relu), params = per layer the weights, then the biases;
+ * out = n_out of the last layer x h x w.  The hidden width may go up to CCO_MAX_HID. */
+int cco_syn_forward(int c_in, int h, int w, int n_layers, const int *layers, const int32_t *params, const int32_t *in,
+                    int32_t *out)
+{
+    if (c_in < 1 || c_in > 64 || n_layers < 1 || n_layers > 16 || h < 1 || w < 1) return 1;
+    size_t npx = (size_t)h * w;
+    int maxp = c_in;
+    const int32_t *wp[16], *bp[16];
+    for (int l = 0, c = c_in; l < n_layers; l++) {
+        int n_out = layers[4 * l], ks = layers[4 * l + 1];
+        if (n_out < 1 || n_out > CCO_MAX_HID || ks < 1 || !(ks & 1)) return 1;
+        wp[l] = params;
+        params += (size_t)n_out * c * ks * ks;
+        bp[l] = params;
+        params += n_out;
+        c = n_out;
+        if (n_out > maxp) maxp = n_out;
+    }
+    int fuse = n_layers >= 2 && layers[1] == 1 && layers[5] == 1;
+    int32_t *A = (int32_t *)malloc(sizeof(int32_t) * npx * (size_t)maxp);
+    int32_t *B = (int32_t *)malloc(sizeof(int32_t) * npx * (size_t)maxp);
+    memcpy(A, in, sizeof(int32_t) * npx * (size_t)c_in);
+    int nin = c_in;
+    for (int l = 0; l < n_layers; l++) {
+        const int *L = layers + 4 * l;
+        if (l == 0 && fuse) {
+            if (L[4] > 64) { free(A); free(B); return 1; }
+            syn_fused(wp[0], bp[0], wp[1], bp[1], nin, L[0], L[4], A, B, npx);
+            nin = L[4];
+            l++;
+        } else {
+            if (L[2] && L[0] > nin) { free(A); free(B); return 1; }
+            syn_conv(wp[l], bp[l], L[1], nin, L[0], L[2], L[3], A, h, w, B);
+            nin = L[0];
+        }
+        int32_t *t = A; A = B; B = t;
+    }
+    memcpy(out, A, sizeof(int32_t) * npx * (size_t)nin);
+    free(A);
+    free(B);
     return 0;
 }
 

@@ -19,6 +19,7 @@ extern "C" {
 #endif
 
 #define CCO_MAX_LAYERS 8
+#define CCO_MAX_HID 1024 /* widest hidden layer of the stage wrappers; streams stay within 256 */
 
 typedef struct cco_frame {
     int h, w;                 /* image size */
@@ -42,6 +43,17 @@ void cco_frame_free(cco_frame *f);
  * (flat-block latents included), as encode.py:510-560 computes them with ArmInt before
  * cc_code_latent_layer_bac.  mu[l], log_scale[l]: caller arrays of lh[l] * lw[l]. */
 int cco_arm_params(const uint8_t *bs, size_t n, const cco_frame *f, int32_t **mu, int32_t **log_scale);
+
+/* The decoder's two tail stages on caller arrays, by the same loops the frame decode runs
+ * (ups_refine / ups_up2, syn_fused / syn_conv): the reference for the GPU's stage entry points
+ * on inputs no stream carries.  lat: the grids one after another, value << 8; kernels: n_ups
+ * full ups_ks-tap kernels, then n_pre pre_ks-tap ones; out: n_grids x lh[0] x lw[0].
+ * layers: n_layers x (n_out, ks, residual, relu); params: per layer weights, then biases;
+ * in: c_in x h x w; out: last n_out x h x w.  0 on success. */
+int cco_ups_forward(int n_grids, const int *lh, const int *lw, const int32_t *lat, int ups_ks, int n_ups,
+                    int pre_ks, int n_pre, const int32_t *kernels, int32_t *out);
+int cco_syn_forward(int c_in, int h, int w, int n_layers, const int *layers, const int32_t *params, const int32_t *in,
+                    int32_t *out);
 
 /* Output conversions, as the reference CLI writes them
  * (ccdecapi.cpp:59-128 ppm_out, :132-180 convert_444_420_8b, 444 raw). */
