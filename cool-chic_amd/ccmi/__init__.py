@@ -33,6 +33,8 @@ EXPORTED = [
     "ccmi_latents_render_plan", "ccmi_latents_render",
     "ccmi_latents_compact_plan", "ccmi_latents_compact_measure", "ccmi_latents_compact", "ccmi_latents_concat",
     "ccmi_latents_stream_info",
+    "ccmi_latents_file_head", "ccmi_latents_export_plan", "ccmi_latents_export", "ccmi_latents_import_plan",
+    "ccmi_latents_import",
     "ccmi_decode_batch_dev_fmt_plan", "ccmi_decode_batch_dev_fmt", "ccmi_latents_render_fmt_plan", "ccmi_latents_render_fmt",
     "ccmi_decode_batch_dev_rs_plan", "ccmi_decode_batch_dev_rs", "ccmi_latents_render_rs_plan", "ccmi_latents_render_rs",
     "ccmi_decode_last_tail_groups",

@@ -5,7 +5,7 @@ from __future__ import annotations
 import ctypes as C
 from typing import Sequence
 
-from . import MAX_GRIDS, MAX_SYN_LAYERS, CcmiError, SynLayer, check, lib
+from . import ERR_IO, MAX_GRIDS, MAX_SYN_LAYERS, CcmiError, SynLayer, check, lib
 
 
 class UpsI32Args(C.Structure):
@@ -61,6 +61,11 @@ _PROTOS = {
     "ccmi_latents_compact": [_P, _P, _Z, _P, _Z, _P, _P],
     "ccmi_latents_concat": [_P, _I, _P],
     "ccmi_latents_stream_info": [_P, _I, _P, _P],
+    "ccmi_latents_file_head": [_P, _Z, _P, _P, _P],
+    "ccmi_latents_export_plan": [_P, _P, _I, _P, _P, _P],
+    "ccmi_latents_export": [_P, _P, _I, _P, _P, _Z, _P, _Z, _P],
+    "ccmi_latents_import_plan": [_P, _Z, _I, _I, _P, _P, _P, _P],
+    "ccmi_latents_import": [_P, _Z, _I, _I, _P, _Z, _P, _Z, _P, _Z, _P, _P, _P],
 }
 _RESTYPES = {"ccmi_ups_workspace_bytes_i32": _Z, "ccmi_syn_workspace_bytes_i32": _Z, "ccmi_latents_free": None}
 
@@ -811,6 +816,104 @@ class LatentStore:
         out = cls.__new__(cls)
         out._adopt(h, [t for s in stores for t in s._stores], [f for s in stores for f in s.arm_flags])
         return out
+
+    def save(self, path, index=None, workspace=None, stream_handle: int | None = None) -> int:
+        """Writes streams `index` of this store (None: all, in order; repeats and any order allowed)
+        as a latent file (ccmi_latents_export; the file form is in include/ccmi.h): any store, a
+        concat of mixed types included.  The file is a function of the streams alone, byte for
+        byte.  arm_flags travel with the streams.  Written under a temporary name in the same
+        directory, then renamed.  Returns the file's bytes."""
+        import os
+        import torch
+        L = _bind()
+        idx = None if index is None else [int(i) for i in index]
+        m = len(self) if idx is None else len(idx)
+        arr = None if idx is None else (C.c_int * max(m, 1))(*idx)
+        nmeta, nfile, nws = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+        check(L.ccmi_latents_export_plan(self._handle(), arr, m, C.byref(nmeta), C.byref(nfile), C.byref(nws)))
+        src = range(m) if idx is None else idx
+        flags = (C.c_uint32 * m)(*[int(self.arm_flags[i]) if i < len(self.arm_flags) else 0 for i in src])
+        host = torch.empty(nfile.value, dtype=torch.uint8, pin_memory=True)
+        stream_handle, ws = _stream_ws(self._store.device, stream_handle, workspace, nws.value)
+        check(L.ccmi_latents_export(self._handle(), arr, m, flags, host.data_ptr(), host.numel(), ws.data_ptr(),
+                                    ws.numel(), stream_handle))
+        path = os.fspath(path)
+        tmp = "%s.tmp.%d" % (path, os.getpid())
+        try:
+            with open(tmp, "wb") as f:
+                f.write(memoryview(host.numpy()))
+            os.replace(tmp, path)
+        except BaseException:
+            if os.path.exists(tmp):
+                os.unlink(tmp)
+            raise
+        return nfile.value
+
+    @staticmethod
+    def _read_meta(f):
+        """(stream count, META bytes, file bytes) of the open latent file f."""
+        L = _bind()
+        head = f.read(64)
+        n, nmeta, nfile = C.c_int(0), C.c_size_t(0), C.c_size_t(0)
+        check(L.ccmi_latents_file_head(head, len(head), C.byref(n), C.byref(nmeta), C.byref(nfile)))
+        f.seek(0)
+        return n.value, f.read(nmeta.value), nfile.value
+
+    @classmethod
+    def load(cls, path, first: int = 0, count=None, workspace=None, stream_handle: int | None = None) -> "LatentStore":
+        """Streams [first, first + count) (count None: to the end) of a latent file as a store
+        (ccmi_latents_import).  Only META and those streams' part of the file are read, so a rank's
+        shard of a big file costs that shard's I/O.  The file is untrusted input: it is validated on
+        the host, checksummed and its descriptor tables verified on the GPU before the store exists;
+        a CcmiError (ERR_BITSTREAM) names the stream.  Loaded stores compact(), concat(), render and
+        latents() like any other: LatentStore.concat([LatentStore.load(p) for p in chunks]) reopens a
+        data set built chunk by chunk."""
+        import torch
+        L = _bind()
+        with open(path, "rb") as f:
+            n, meta, _ = cls._read_meta(f)
+            cnt = -1 if count is None else int(count)
+            off, nbytes, nws = C.c_size_t(0), C.c_size_t(0), C.c_size_t(0)
+            check(L.ccmi_latents_import_plan(meta, len(meta), int(first), cnt, C.byref(off), C.byref(nbytes), None,
+                                             C.byref(nws)))
+            host = torch.empty(max(nbytes.value, 1), dtype=torch.uint8, pin_memory=True)
+            view = memoryview(host.numpy())[: nbytes.value]
+            f.seek(off.value)
+            got = 0
+            while got < nbytes.value:
+                k = f.readinto(view[got:])
+                if not k:
+                    raise CcmiError(ERR_IO, f"LatentStore.load: {path} ends {nbytes.value - got} bytes short of its DATA")
+                got += k
+        m = n - int(first) if count is None else int(count)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        store = torch.empty(max(nbytes.value, 256), dtype=torch.uint8, device=dev)
+        stream_handle, ws = _stream_ws(dev, stream_handle, workspace, nws.value)
+        flags, h = (C.c_uint32 * max(m, 1))(), C.c_void_p(None)
+        check(L.ccmi_latents_import(meta, len(meta), int(first), cnt, host.data_ptr(), nbytes.value, store.data_ptr(),
+                                    store.numel(), ws.data_ptr(), ws.numel(), stream_handle, flags, C.byref(h)))
+        out = cls.__new__(cls)
+        out._adopt(h, [store], [int(v) for v in flags[:m]])
+        return out
+
+    @staticmethod
+    def file_info(path) -> dict:
+        """What a latent file holds, from META alone (no GPU): {'n_streams', 'meta_bytes',
+        'file_bytes', 'streams': [{'width', 'height', 'bitdepth', 'chroma', 'frame_data_type',
+        'dtype', 'nbytes', 'arm_flags'}]}."""
+        L = _bind()
+        with open(path, "rb") as f:
+            n, meta, nfile = LatentStore._read_meta(f)
+        flags, h = (C.c_uint32 * n)(), C.c_void_p(None)
+        check(L.ccmi_latents_import(meta, len(meta), 0, -1, None, 0, None, 0, None, 0, None, flags, C.byref(h)))
+        st = LatentStore.__new__(LatentStore)
+        st._adopt(h, [None], [int(v) for v in flags])  # plan-only: no store behind it
+        try:
+            streams = [dict(g, dtype=t, nbytes=nb, arm_flags=fl)
+                       for g, t, nb, fl in zip(st.geometry, st.stream_dtypes, st.stream_nbytes, st.arm_flags)]
+        finally:
+            st.close()
+        return {"n_streams": n, "meta_bytes": len(meta), "file_bytes": nfile, "streams": streams}
 
     def __len__(self):
         return _bind().ccmi_latents_count(self._handle())

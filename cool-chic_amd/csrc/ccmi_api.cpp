@@ -68,7 +68,7 @@ void ccmi_streamset_release(StreamSet *set)
 
 extern "C" const char *ccmi_last_error(void) { return g_err; }
 
-extern "C" int ccmi_version(void) { return 100; }
+extern "C" int ccmi_version(void) { return 101; }
 
 extern "C" int ccmi_device_count(void)
 {

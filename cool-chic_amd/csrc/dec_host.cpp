@@ -1399,6 +1399,18 @@ extern "C" int ccmi_latents_render_fmt(const ccmi_latents *h, const int *index, 
                                   workspace_bytes, stream);
 }
 
+namespace ccmi {
+
+bool dec_syn_weights_fit24(const FrameHost &f) { return syn_weights_fit24(f); }
+
+void dec_set_last_call(const float ms[4])
+{
+    clear_last();
+    for (int k = 0; k < 4; ++k) g_last_ms[k] = ms[k];
+}
+
+} // namespace ccmi
+
 extern "C" int ccmi_decode_last_tail_groups(int *batched, int *per_frame)
 {
     if (!batched || !per_frame) return ccmi_set_error(CCMI_ERR_ARG, "decode_last_tail_groups: null argument");

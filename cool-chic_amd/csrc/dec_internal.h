@@ -274,4 +274,37 @@ int launch_dec_lat_seg_width(const DecLatSegJob *jobs, int n_jobs, uint32_t n_se
 int launch_dec_lat_seg_scan(const DecLatSegJob *jobs, int n_jobs, uint32_t *totals, hipStream_t s);
 int launch_dec_lat_seg_pack(const DecLatSegJob *jobs, int n_jobs, uint32_t n_segs, hipStream_t s);
 
+// Latent-store files (dec_store_file.cpp, the contract in ccmi.h).  Three more table-driven
+// kernels: the gather copies a defined byte range of a store to its place in the DATA image
+// (src and dst 16-byte aligned, n of any size), the checksum adds a range's two sums to
+// sum[0..1] (zeroed by the host; integer sums, so the order of the blocks does not matter), the
+// verify (one block per non-empty SEG grid) checks an untrusted descriptor table against the
+// payload size its record states and writes the grid's status word (0, or kSegBad* bits).
+struct DecLatGatherJob {
+    const uint8_t *src;
+    uint8_t *dst;
+    uint64_t n;           // bytes
+    uint32_t first_block;
+    uint32_t pad_;
+};
+struct DecLatSumJob {
+    const uint32_t *src;  // 16-byte aligned
+    unsigned long long *sum;
+    uint64_t n_words;
+    uint32_t first_block;
+    uint32_t pad_;
+};
+struct DecLatVerifyJob {
+    const uint32_t *desc; // the grid's h * nseg descriptors
+    uint32_t *status;
+    int w, h, nseg;
+    uint32_t seg_words;   // the payload words the record states
+};
+enum { kSegBadCode = 1, kSegBadOffset = 2, kSegBadTotal = 4 };
+uint32_t dec_lat_gather_blocks(uint64_t n_bytes);
+uint32_t dec_lat_sum_blocks(uint64_t n_words);
+int launch_dec_lat_file_gather(const DecLatGatherJob *jobs, int n_jobs, uint32_t n_blocks, hipStream_t s);
+int launch_dec_lat_file_sum(const DecLatSumJob *jobs, int n_jobs, uint32_t n_blocks, hipStream_t s);
+int launch_dec_lat_seg_verify(const DecLatVerifyJob *jobs, int n_jobs, hipStream_t s);
+
 } // namespace ccmi

@@ -17,6 +17,10 @@
 // dec_lat_seg_width / dec_lat_seg_scan / dec_lat_seg_pack (DecLatSegJob, one wave per segment of
 // 64 values, a wave finds its job by the same search over the jobs' first segments) and read by
 // dec_lat_unpack_seg, which takes dec_lat_unpack's jobs and writes the same rectangle.
+//
+// Latent-store files (dec_store_file.cpp): dec_lat_file_gather copies the defined byte ranges of
+// stores into a zeroed DATA image, dec_lat_file_sum takes a range's two checksums, and
+// dec_lat_seg_verify proves an imported descriptor table safe before any handle refers to it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -286,6 +290,137 @@ __global__ __launch_bounds__(kThreads) void dec_lat_unpack_seg(const DecLatUnpac
     }
 }
 
+// ---- latent-store files ----
+constexpr int kFileGroups = 4;                        // 16-byte groups per thread
+constexpr int kFileBlock = kThreads * kFileGroups;    // groups per block: 16 KiB
+
+// Gather: a block copies kFileBlock consecutive 16-byte groups of its job's range, consecutive
+// lanes on consecutive groups; the range's last group may be partial: byte stores.
+__global__ __launch_bounds__(kThreads) void dec_lat_file_gather(const DecLatGatherJob *__restrict__ jobs, int n_jobs)
+{
+    const DecLatGatherJob J = jobs[find_job(jobs, n_jobs, blockIdx.x)];
+    const uint64_t g0 = (uint64_t)(blockIdx.x - J.first_block) * kFileBlock;
+#pragma unroll
+    for (int t = 0; t < kFileGroups; ++t) {
+        const uint64_t b = (g0 + (uint64_t)t * kThreads + threadIdx.x) * 16;
+        if (b + 16 <= J.n) {
+            *reinterpret_cast<uint4 *>(J.dst + b) = *reinterpret_cast<const uint4 *>(J.src + b);
+        } else if (b < J.n) {
+            for (uint64_t k = b; k < J.n; ++k) J.dst[k] = J.src[k];
+        }
+    }
+}
+
+// Checksum: sum[0] += sum of w_i, sum[1] += sum of (i + 1) w_i (mod 2^64) over the block's words;
+// a wave reduces by shuffles, the block through LDS, one atomic pair per block.
+__global__ __launch_bounds__(kThreads) void dec_lat_file_sum(const DecLatSumJob *__restrict__ jobs, int n_jobs)
+{
+    __shared__ unsigned long long part[2][kSegWaves];
+    const DecLatSumJob J = jobs[find_job(jobs, n_jobs, blockIdx.x)];
+    const uint64_t g0 = (uint64_t)(blockIdx.x - J.first_block) * kFileBlock;
+    unsigned long long s0 = 0, s1 = 0;
+#pragma unroll
+    for (int t = 0; t < kFileGroups; ++t) {
+        const uint64_t g = g0 + (uint64_t)t * kThreads + threadIdx.x, i = 4 * g;
+        if (i + 4 <= J.n_words) {
+            const uint4 v = reinterpret_cast<const uint4 *>(J.src)[g];
+            s0 += (unsigned long long)v.x + v.y + v.z + v.w;
+            s1 += (i + 1) * v.x + (i + 2) * v.y + (i + 3) * v.z + (i + 4) * v.w;
+        } else {
+            for (uint64_t k = i; k < J.n_words; ++k) {
+                const uint32_t v = J.src[k];
+                s0 += v;
+                s1 += (k + 1) * v;
+            }
+        }
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        s0 += __shfl_down(s0, d);
+        s1 += __shfl_down(s1, d);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        part[0][wave] = s0;
+        part[1][wave] = s1;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        unsigned long long a = 0;
+#pragma unroll
+        for (int wv = 0; wv < kSegWaves; ++wv) a += part[threadIdx.x][wv];
+        atomicAdd(J.sum + threadIdx.x, a);
+    }
+}
+
+// Verify: one block per non-empty SEG grid of an imported (untrusted) store, shaped like
+// dec_lat_seg_scan.  The table's extent, h * nseg words, follows from the header the host has
+// validated against the part's size, so the reads here are in bounds whatever the table holds.
+// Checked: every width code k <= 5; every offset equals the exclusive prefix sum of the word
+// counts seg_words(k, c) of the segments before it; the sum over all segments equals the
+// record's seg_words, which is what the layout reserved for the payload.
+// What follows for dec_lat_unpack_seg: it reads payload[off + (bit >> 5)] with
+// bit = (x & 63) << k < c << k, so (bit >> 5) < seg_words(k, c) = words; off + words is the next
+// segment's offset or, for the last one, the total, and offsets do not decrease: off + words <=
+// seg_words for every segment.  No render can read outside the grid's payload.  (That k is the
+// smallest code that fits and that trailing bits are 0 is not checked: neither moves a read.)
+__global__ __launch_bounds__(kThreads) void dec_lat_seg_verify(const DecLatVerifyJob *__restrict__ jobs)
+{
+    __shared__ uint32_t wave_sum[kSegWaves];
+    const DecLatVerifyJob J = jobs[blockIdx.x];
+    const uint32_t n = (uint32_t)J.h * (uint32_t)J.nseg;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint64_t carry = 0;
+    int bad = 0;
+    for (uint32_t base = 0; base < n; base += kThreads * kScanPerThread) {
+        const uint32_t i0 = base + threadIdx.x * kScanPerThread;
+        uint32_t off[kScanPerThread], wd[kScanPerThread], sum = 0;
+#pragma unroll
+        for (int t = 0; t < kScanPerThread; ++t) {
+            const uint32_t i = i0 + t;
+            off[t] = 0;
+            wd[t] = 0;
+            if (i < n) {
+                const uint32_t d = J.desc[i], k = d & 7u;
+                if (k > 5u) bad |= kSegBadCode;
+                off[t] = d >> 3;
+                wd[t] = seg_words(min(k, 5u), seg_values(J.w, i % (uint32_t)J.nseg));
+            }
+            sum += wd[t];
+        }
+        uint32_t inc = sum; // inclusive over the wave
+#pragma unroll
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t up = __shfl_up(inc, d);
+            if (lane >= d) inc += up;
+        }
+        if (lane == 63) wave_sum[wave] = inc;
+        __syncthreads();
+        uint32_t before = 0, all = 0;
+#pragma unroll
+        for (int wv = 0; wv < kSegWaves; ++wv) {
+            const uint32_t ws = wave_sum[wv];
+            before += wv < wave ? ws : 0u;
+            all += ws;
+        }
+        __syncthreads(); // wave_sum is rewritten by the next round
+        uint64_t want = carry + before + (inc - sum);
+#pragma unroll
+        for (int t = 0; t < kScanPerThread; ++t) {
+            if (i0 + t < n) {
+                if ((uint64_t)off[t] != want) bad |= kSegBadOffset;
+                want += wd[t];
+            }
+        }
+        carry += all;
+    }
+    if (carry != (uint64_t)J.seg_words) bad |= kSegBadTotal; // uniform over the block
+    int flags = 0;
+#pragma unroll
+    for (int bit = 1; bit <= kSegBadTotal; bit <<= 1) flags |= __syncthreads_or(bad & bit) ? bit : 0;
+    if (threadIdx.x == 0) *J.status = (uint32_t)flags;
+}
+
 template <typename Launch>
 int with_latent_type(int type, Launch &&launch)
 {
@@ -339,6 +474,37 @@ int launch_dec_lat_unpack(const DecLatUnpackJob *jobs, int n_jobs, uint32_t n_bl
             hipLaunchKernelGGL(dec_lat_unpack<decltype(t)>, dim3(n_blocks), dim3(kThreads), 0, s, jobs, n_jobs);
         }))
         return rc;
+    CCMI_HIP_CHECK(hipGetLastError());
+    return CCMI_OK;
+}
+
+uint32_t dec_lat_gather_blocks(uint64_t n_bytes)
+{
+    return (uint32_t)((n_bytes + 16ull * kFileBlock - 1) / (16ull * kFileBlock));
+}
+
+uint32_t dec_lat_sum_blocks(uint64_t n_words) { return (uint32_t)((n_words + 4ull * kFileBlock - 1) / (4ull * kFileBlock)); }
+
+int launch_dec_lat_file_gather(const DecLatGatherJob *jobs, int n_jobs, uint32_t n_blocks, hipStream_t s)
+{
+    if (n_jobs < 1 || n_blocks < 1) return CCMI_OK;
+    hipLaunchKernelGGL(dec_lat_file_gather, dim3(n_blocks), dim3(kThreads), 0, s, jobs, n_jobs);
+    CCMI_HIP_CHECK(hipGetLastError());
+    return CCMI_OK;
+}
+
+int launch_dec_lat_file_sum(const DecLatSumJob *jobs, int n_jobs, uint32_t n_blocks, hipStream_t s)
+{
+    if (n_jobs < 1 || n_blocks < 1) return CCMI_OK;
+    hipLaunchKernelGGL(dec_lat_file_sum, dim3(n_blocks), dim3(kThreads), 0, s, jobs, n_jobs);
+    CCMI_HIP_CHECK(hipGetLastError());
+    return CCMI_OK;
+}
+
+int launch_dec_lat_seg_verify(const DecLatVerifyJob *jobs, int n_jobs, hipStream_t s)
+{
+    if (n_jobs < 1) return CCMI_OK;
+    hipLaunchKernelGGL(dec_lat_seg_verify, dim3(n_jobs), dim3(kThreads), 0, s, jobs);
     CCMI_HIP_CHECK(hipGetLastError());
     return CCMI_OK;
 }

@@ -20,6 +20,9 @@ struct LatentStream {
     // an empty grid (lat_n == 0) takes no bytes; CCMI_LATENT_SEG: the descriptor table, the payload
     // dec_lat_seg_table_bytes() behind it
     size_t grid_off[CCMI_MAX_GRIDS] = {};
+    // CCMI_LATENT_SEG: the payload words of each non-empty grid (the compaction's scan, or a
+    // file's record); grid_off differences do not give the last grid's, the part being rounded
+    uint32_t seg_words[CCMI_MAX_GRIDS] = {};
 };
 
 } // namespace ccmi
@@ -142,5 +145,11 @@ int decode_plan(const DecodeRequest &rq, DecodePlan &pl);
 // contract in ccmi.h): fills h.s[i].type / off / bytes / ups_off / syn_off / grid_off and
 // h.store_bytes (h.s sized here, the FrameHosts left alone).  Host arithmetic.
 int latent_store_layout(const DecodePlan &pl, int type, ccmi_latents &h);
+
+// For the calls that make a handle without a decode (dec_store_file.cpp): DecSynArgs::f24 of
+// decoded synthesis integers, as the build computes it; and the thread's record of the last
+// call (ARM flags and tail groups cleared, ccmi_decode_last_timing's four figures set).
+bool dec_syn_weights_fit24(const FrameHost &f);
+void dec_set_last_call(const float ms[4]);
 
 } // namespace ccmi

@@ -79,6 +79,7 @@ void seg_store_layout(const ccmi_latents &src, const CompactPlan &cp, const uint
             S.grid_off[l] = pos;
             if (!f.lat_n[l]) continue;
             const size_t payload = words ? (size_t)words[g] : (size_t)f.lh[l] * f.lw[l];
+            S.seg_words[l] = (uint32_t)std::min<size_t>(payload, 0xFFFFFFFFu); // what an export writes
             pos += dec_lat_seg_table_bytes(f.lh[l], f.lw[l]) + align_up(payload * 4, 16);
             ++g;
         }

@@ -471,6 +471,85 @@ int ccmi_latents_compact(const ccmi_latents *src, void *store, size_t store_byte
 int ccmi_latents_concat(const ccmi_latents *const *parts, int n_parts, ccmi_latents **out);
 int ccmi_latents_stream_info(const ccmi_latents *h, int i, int *latent_type, size_t *store_bytes);
 
+/* Latent stores as files: export of any resident handle, verified import.
+ *
+ * THE FILE FORM.  Everything is little-endian.
+ *   FILE = HEAD (64 bytes) | INDEX | zero padding to a multiple of 256 | DATA;  META = HEAD | INDEX.
+ * HEAD: bytes 0-7 the magic "CCMILAT1"; 8 u32 version = 1; 12 u32 n_streams >= 1; 16 u64 index_bytes;
+ *   24 u64 data_off = (64 + index_bytes) rounded up to 256; 32 u64 data_bytes; 40 u64[2] index_sum (the
+ *   checksum below over the INDEX bytes); 56 u64 0.
+ * INDEX: one record per stream, each a multiple of 8 bytes (one zero u32 of padding where needed),
+ *   the fields in this order:
+ *     u32 record_bytes; u32 latent_type (CCMI_LATENT_*); u64 part_bytes (this stream's part of DATA, a
+ *     multiple of 256); u64[2] part_sum (the checksum over the part); u32 user_flags;
+ *     14 i32: h, w, bitdepth, frame_data_type, intra_period, dim_arm, n_hidden, n_ups, ups_ks, n_pre,
+ *       pre_ks, n_branches, sig_blk, n_layers (the .cool header's fields; n_layers = the latent grids);
+ *     u32 the count of synthesis layers, then per layer 4 i32: n_out, ks, residual, relu;
+ *     per grid u32 lat_n (the grid's coded bytes in its .cool stream; 0: an empty grid);
+ *     per grid u32 seg_words: the grid's payload words of a CCMI_LATENT_SEG stream; 0 for the other
+ *       types and for an empty grid;
+ *     u32 the count of blend integers (n_branches if n_branches > 1, else 0), then the integers (i32).
+ *   The upsampling and synthesis integers are not in the INDEX: a reader takes them from DATA.
+ * DATA: the streams' parts one behind the other, stream i's at data_off + the part_bytes before it.
+ *   A part is, byte for byte, the stream's part of a store of its type as defined above (upsampling
+ *   integers: n_ups ups_ks + n_pre pre_ks int32; synthesis integers: per branch and layer n_out c_in
+ *   ks ks + n_out int32, c_in = n_layers for the first layer, else the layer before's n_out; then the
+ *   non-empty grids; every part 16-byte aligned; SEG: descriptor table, then seg_words payload words;
+ *   the size rounded up to 256), and every byte the store contract leaves undefined (alignment
+ *   padding, the tail) is 0.  No offset inside a part is stored: writer and reader derive the layout
+ *   from the record, and part_bytes must equal the derived size.
+ * Checksum of a byte range read as u32 words w_0 .. w_(n-1) (a range that is no multiple of 4 bytes
+ *   zero-extended): sum[0] = sum of w_i, sum[1] = sum of (i + 1) w_i, both mod 2^64.  It guards
+ *   against accidental corruption; memory safety does not rest on it.
+ * A file is a function of the latents, the networks and the header facts alone: exports of the same
+ * streams are identical byte for byte whatever sat in the stores' padding and whichever of I8 / I16 /
+ * I32 a SEG store was compacted from.
+ *
+ * ccmi_latents_file_head(): the head's checks alone; meta_bytes = 64 + index_bytes, file_bytes =
+ *   data_off + data_bytes (any of the three outputs may be NULL).
+ * ccmi_latents_export_plan(): host arithmetic, works on a plan-only handle.  The file holds streams
+ *   index[0..m) of the handle (NULL: every stream in order, m = the count; repeats and any order are
+ *   allowed, so a file can be a re-sharding of a handle).
+ * ccmi_latents_export(): any resident handle, a concat of mixed types over several stores included;
+ *   a plan-only handle is CCMI_ERR_ARG before any HIP call.  `file` is host memory of file_bytes;
+ *   workspace (device, 256-byte aligned; NULL: allocated for the call) holds the DATA image, which is
+ *   cleared, gathered and checksummed on the device and downloaded in one copy.  The handle and its
+ *   stores are only read: renders may run from them meanwhile.  user_flags[j] travels with stream j.
+ * ccmi_latents_import_plan(): validates META; for streams [first, first + count) (count < 0: to the
+ *   end) the range FILE[data_off, data_off + data_bytes) that holds their parts, their store bytes
+ *   (store_bytes_each[i] = part_bytes; the store takes data_bytes) and the import's workspace.
+ * ccmi_latents_import(): store == NULL and data == NULL: no HIP call, a plan-only handle from META
+ *   alone (its networks' integers are zeros).  Otherwise: META is validated on the host; `data` (host)
+ *   is copied to `store` (device, 256-byte aligned), which then is that DATA range byte for byte; the
+ *   parts' checksums are taken on the device; every descriptor table of a SEG stream is verified on
+ *   the device: every width code <= 5, every offset the exclusive prefix sum of the word counts of
+ *   the segments before it, the total equal to seg_words.  After that off + words <= seg_words holds
+ *   for every segment, so no render can read outside a grid's payload whatever the file held.  (That
+ *   a code is the smallest that fits and that trailing bits are 0 is not checked: neither affects
+ *   safety, only whether a re-export is canonical.)  The upsampling and synthesis integers are read
+ *   from `data`.  Only then the handle is created.  The call writes exactly data_bytes of `store`,
+ *   synchronises `stream`, clears the ARM flag record and the tail groups;
+ *   ccmi_decode_last_timing() reports [0] the upload, [1] checksums + verify.
+ *   Errors create no handle and name the stream (and grid).  CCMI_ERR_BITSTREAM: a malformed or
+ *   inconsistent META (every header field is held to the .cool header's limits; a stream's upsampling
+ *   and synthesis integers may number 2^22 at most; seg_words <= min(h_l w_l, 2^29 + 63)), a checksum
+ *   mismatch, a descriptor fault.  CCMI_ERR_ARG, before any HIP call: a NULL pointer, first / count
+ *   outside the file, data_bytes or store_bytes too short, a store not 256-byte aligned, a workspace
+ *   too small or misaligned, store and data not both NULL or both set. */
+int ccmi_latents_file_head(const void *head, size_t head_bytes /* >= 64 */, int *n_streams, size_t *meta_bytes,
+                           size_t *file_bytes);
+int ccmi_latents_export_plan(const ccmi_latents *h, const int *index /* [m] or NULL */, int m, size_t *meta_bytes,
+                             size_t *file_bytes, size_t *workspace_bytes);
+int ccmi_latents_export(const ccmi_latents *h, const int *index, int m, const uint32_t *user_flags /* [m] or NULL */,
+                        void *file /* host */, size_t file_bytes, void *workspace, size_t workspace_bytes, void *stream);
+int ccmi_latents_import_plan(const void *meta, size_t meta_bytes, int first, int count /* < 0: to the end */,
+                             size_t *data_off, size_t *data_bytes, size_t *store_bytes_each /* [count] or NULL */,
+                             size_t *workspace_bytes);
+int ccmi_latents_import(const void *meta, size_t meta_bytes, int first, int count,
+                        const void *data /* host: FILE[data_off, data_off + data_bytes) of import_plan */, size_t data_bytes,
+                        void *store, size_t store_bytes, void *workspace, size_t workspace_bytes, void *stream,
+                        uint32_t *user_flags /* [count] or NULL */, ccmi_latents **out);
+
 /* Formatted output: the same decode (coded streams, or a latent store) written as the tensor a
  * model or a display takes -- three full-size channels, optionally RGB, normalised, fp16 / bf16,
  * any strides (NCHW, NHWC, a view into the caller's canvas), optionally mirrored -- by one
