@@ -45,6 +45,10 @@ _PROTOS = {
     "ccmi_decode_batch_dev_warp": [_P, _P, _I, _P, _P, _P, _P, _I, _I, _P, _Z, _P],
     "ccmi_latents_render_warp_plan": [_P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P],
     "ccmi_latents_render_warp": [_P, _P, _I, _P, _P, _P, _P, _I, _I, _P, _Z, _P],
+    "ccmi_decode_batch_dev_col_plan": [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "ccmi_decode_batch_dev_col": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _Z, _P],
+    "ccmi_latents_render_col_plan": [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "ccmi_latents_render_col": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _Z, _P],
     "ccmi_latents_plan": [_P, _P, _I, _I, _P, _P, _P],
     "ccmi_latents_decode": [_P, _P, _I, _I, _P, _Z, _P, _Z, _P, _P],
     "ccmi_latents_free": [_P],
@@ -447,6 +451,125 @@ def affine_matrix(size, centre, angle: float = 0.0, scale: float = 1.0, flip: bo
                      [f * s / scale, c / scale, cy + (-f * s * ow / 2 - c * oh / 2) / scale]], dtype=np.float32)
 
 
+COL_BRIGHTNESS, COL_SATURATION, COL_CONTRAST, COL_MATRIX = 0, 1, 2, 3  # CCMI_COL_*
+COL_MAX_OPS = 8
+_COL_NAMES = {"brightness": COL_BRIGHTNESS, "saturation": COL_SATURATION, "contrast": COL_CONTRAST, "matrix": COL_MATRIX}
+
+
+class ColourOp(C.Structure):
+    """ccmi_colour_op: one photometric operation (v[0] the factor, or the 3 x 4 matrix row-major)."""
+    _fields_ = [("op", C.c_int), ("v", C.c_float * 12)]
+
+
+class Colour(C.Structure):
+    """ccmi_colour: the per-frame op counts and the flat op array of a colouring call."""
+    _fields_ = [("count", C.c_void_p), ("ops", C.c_void_p)]
+
+
+def _colour(colour_ops, n):
+    """colour_ops= of a *_model call -> (ccmi_colour, what it points to), or (None, None) without ops.
+    One list of (op, value) tuples for every frame, or one such list per frame; op is 'brightness',
+    'saturation', 'contrast' or 'matrix' (or a COL_* code), value the factor, or the matrix as 12
+    numbers or [3][4].  The library checks the values; the shapes are checked here."""
+    import numpy as np
+    if colour_ops is None:
+        return None, None
+    ops = list(colour_ops)
+    if not ops:
+        return None, None
+    if isinstance(ops[0], tuple) and len(ops[0]) == 2 and isinstance(ops[0][0], (str, int)):
+        ops = [ops] * n  # one list for all frames
+    if len(ops) != n:
+        raise ValueError(f"model output: colour_ops takes one op list, or one per frame ({n}), got {len(ops)}")
+    counts = np.fromiter((len(f) for f in ops), dtype=np.int32, count=n)
+    # ccmi_colour_op as a packed record (52 bytes): filled row by row, no per-element ctypes stores
+    flat = np.zeros(max(int(counts.sum()), 1), dtype=np.dtype([("op", "<i4"), ("v", "<f4", (12,))]))
+    codes, at_f, fs, at_m, ms = [], [], [], [], []  # gathered in one pass, stored in bulk
+    for f in ops:
+        for op, value in f:
+            code = _COL_NAMES.get(op) if isinstance(op, str) else int(op)
+            if code is None:
+                raise ValueError(f"model output: colour op {op!r} ({', '.join(_COL_NAMES)})")
+            if code == COL_MATRIX:
+                at_m.append(len(codes))
+                ms.append(value)
+            else:
+                at_f.append(len(codes))
+                fs.append(value)
+            codes.append(code)
+    if codes:
+        flat["op"] = codes
+    if fs:
+        fs = np.asarray(fs, dtype=np.float32)
+        if fs.ndim != 1:
+            raise ValueError("model output: a brightness / saturation / contrast op takes one factor")
+        flat["v"][at_f, 0] = fs
+    if ms:
+        try:
+            ms = np.asarray(ms, dtype=np.float32).reshape(len(at_m), 12)
+        except ValueError:
+            raise ValueError("model output: a matrix colour op takes a 3 x 4 matrix (12 values)") from None
+        flat["v"][at_m] = ms
+    return Colour(count=counts.ctypes.data, ops=flat.ctypes.data), (counts, flat)
+
+
+# RGB -> YIQ (NTSC); rows 1 and 2 sum to 0, so a grey pixel has no chroma and every rotation keeps it
+_YIQ = ((0.299, 0.587, 0.114), (0.595716, -0.274453, -0.321263), (0.211456, -0.522591, 0.311135))
+
+
+def hue_matrix(h: float):
+    """The [3, 4] float32 matrix of a 'matrix' colour op that turns the hue by h turns: RGB -> YIQ,
+    a rotation of the (I, Q) plane by 2 pi h, YIQ -> RGB, composed in float64 and rounded once.  Luma
+    and greys are kept; the result is clamped to [0, 1] per channel by the op.  It is NOT
+    torchvision's adjust_hue, which shifts H of HSV."""
+    import math
+    import numpy as np
+    t = np.array(_YIQ, dtype=np.float64)
+    c, s = math.cos(2 * math.pi * h), math.sin(2 * math.pi * h)
+    r = np.array([[1, 0, 0], [0, c, -s], [0, s, c]], dtype=np.float64)
+    m = np.zeros((3, 4), dtype=np.float64)
+    m[:, :3] = np.linalg.inv(t) @ r @ t
+    return m.astype(np.float32)
+
+
+def grey_matrix():
+    """The [3, 4] float32 matrix of a 'matrix' colour op that sets every channel to the grey
+    0.2989 R + 0.587 G + 0.114 B (RandomGrayscale with three output channels)."""
+    import numpy as np
+    return np.array([[0.2989, 0.587, 0.114, 0.0]] * 3, dtype=np.float32)
+
+
+def colour_jitter(n: int, brightness: float = 0.0, contrast: float = 0.0, saturation: float = 0.0, hue: float = 0.0,
+                  grey_p: float = 0.0, generator=None) -> list:
+    """n op lists (colour_ops= of the *_model calls) drawn as torchvision's ColorJitter draws them:
+    brightness / contrast / saturation = b gives a factor in U[max(0, 1 - b), 1 + b], hue = h a turn
+    in U[-h, h] (hue_matrix), an argument of 0 leaves its op out, and every frame applies its ops in
+    a random order of its own.  grey_p: with that probability a frame ends with grey_matrix()
+    (RandomGrayscale).  generator: a torch.Generator (CPU); the same seed gives the same lists."""
+    import torch
+    kinds = [(name, float(b)) for name, b in (("brightness", brightness), ("contrast", contrast),
+                                              ("saturation", saturation), ("hue", hue)) if b]
+    for name, b in kinds:
+        if b < 0 or (name == "hue" and b > 0.5):
+            raise ValueError(f"colour_jitter: {name} = {b}")
+    out = []
+    for _ in range(n):
+        u = torch.rand(len(kinds) + 1, generator=generator, dtype=torch.float64).tolist()
+        order = torch.randperm(len(kinds), generator=generator).tolist() if kinds else []
+        ops = []
+        for k in order:
+            name, b = kinds[k]
+            if name == "hue":
+                ops.append(("matrix", hue_matrix(-b + 2 * b * u[k])))
+            else:
+                lo = max(0.0, 1.0 - b)
+                ops.append((name, lo + (1.0 + b - lo) * u[k]))
+        if grey_p and u[-1] < grey_p:
+            ops.append(("matrix", grey_matrix()))
+        out.append(ops)
+    return out
+
+
 def last_tail_groups() -> tuple:
     """(batched tail groups, per-frame tails) this thread's last decode or render call launched
     (ccmi_decode_last_tail_groups): frames that share a group share one launch per tail stage."""
@@ -525,14 +648,19 @@ def _model_outs(geom, fmt, dtype, channels_last, out, dev):
 
 
 def _plan_model(plan, head, n, rects, fmt, rs, output_bitdepth, output_chroma_format, warp=None, info=None,
-                window=None):
+                window=None, col=None):
     """(ccmi_frame_geom array, workspace bytes) of a formatted call: plan is the source's *_rs_plan
     entry point (rs None: exactly the *_fmt_plan call), head its first two arguments.  With warp
     (a ccmi_warp) plan is the *_warp_plan entry point, which takes no regions; info / window: its
-    optional per-frame outputs."""
+    optional per-frame outputs.  With col (a ccmi_colour) plan is the *_col_plan entry point, which
+    takes all of them."""
     geom, need = (FrameGeom * n)(), C.c_size_t(0)
     probe = TensorFmt.from_buffer_copy(fmt)  # planar strides: the geometry does not depend on them
-    if warp is not None:
+    if col is not None:
+        check(plan(*head, n, None if warp is not None else rects, output_bitdepth, output_chroma_format, C.byref(probe),
+                   None if warp is not None else rs, None if warp is None else C.byref(warp), C.byref(col), geom, info,
+                   window, C.byref(need)))
+    elif warp is not None:
         check(plan(*head, n, output_bitdepth, output_chroma_format, C.byref(probe), C.byref(warp), geom, info, window,
                    C.byref(need)))
     else:
@@ -541,19 +669,24 @@ def _plan_model(plan, head, n, rects, fmt, rs, output_bitdepth, output_chroma_fo
 
 
 def _run_model(plan, run, head, n, rects, dev, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth,
-               output_chroma_format, workspace, stream_handle, size, warp=None):
+               output_chroma_format, workspace, stream_handle, size, warp=None, col=None):
     """The body of decode_batch_model and LatentStore.render_model: plan / run are the source's
     *_rs_plan / *_rs entry points, or with warp (a ccmi_warp, which carries the size) its
-    *_warp_plan / *_warp ones; head their first two arguments; dev None: the current device."""
+    *_warp_plan / *_warp ones, or with col (a ccmi_colour) its *_col_plan / *_col ones; head their
+    first two arguments; dev None: the current device."""
     import torch
     dtype = torch.float32 if dtype is None else dtype
     fmt, keep = _model_fmt(n, colour, mean, std, dtype, mirror)
     rs = None if size is None or warp is not None else C.byref(_resample(size))
-    geom, need = _plan_model(plan, head, n, rects, fmt, rs, output_bitdepth, output_chroma_format, warp)
+    geom, need = _plan_model(plan, head, n, rects, fmt, rs, output_bitdepth, output_chroma_format, warp, col=col)
     dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else dev
     res, op, cap, frames = _model_outs(geom, fmt, dtype, channels_last, out, dev)
     stream_handle, workspace = _stream_ws(dev, stream_handle, workspace, need)
-    if warp is not None:
+    if col is not None:
+        check(run(*head, n, None if warp is not None else rects, op, cap, C.byref(fmt), None if warp is not None else rs,
+                  None if warp is None else C.byref(warp), C.byref(col), output_bitdepth, output_chroma_format,
+                  workspace.data_ptr(), workspace.numel(), stream_handle))
+    elif warp is not None:
         check(run(*head, n, op, cap, C.byref(fmt), C.byref(warp), output_bitdepth, output_chroma_format,
                   workspace.data_ptr(), workspace.numel(), stream_handle))
     else:
@@ -566,7 +699,7 @@ def _run_model(plan, run, head, n, rects, dev, colour, mean, std, dtype, channel
 def decode_batch_model(streams: Sequence[bytes], roi=None, colour: str = "rgb", mean=None, std=None, dtype=None,
                        channels_last: bool = False, mirror=None, out=None, output_bitdepth: int = 0,
                        output_chroma_format: int = 0, workspace=None, stream_handle: int | None = None, size=None,
-                       affine=None, pad: str = "fill", fill=0.0):
+                       affine=None, pad: str = "fill", fill=0.0, colour_ops=None):
     """Decode .cool streams into the tensor a model takes (ccmi_decode_batch_dev_fmt): one
     [n, 3, h, w] tensor of `dtype` (torch.float32, the default, torch.float16 or torch.bfloat16),
     every channel at full size (420 chroma nearest-upsampled), RGB (colour="rgb": YUV streams go
@@ -596,11 +729,26 @@ def decode_batch_model(streams: Sequence[bytes], roi=None, colour: str = "rgb", 
     scale, shear and translation in the same output stage.  pad="fill": a tap outside the frame is
     `fill` (one value or one per channel, in [0, 1] colour units, before the normalisation);
     pad="edge": the nearest frame pixel.  The library decodes only the window of each frame its
-    matrix reaches."""
+    matrix reaches.
+
+    colour_ops= (ccmi_decode_batch_dev_col; with or without roi, size and affine): one list of
+    (op, value) tuples for every frame, or one list per frame, of at most 8 ops each, applied in
+    the list's order to the three channels of every output pixel after the geometry and before the
+    normalisation (the contract's step 3z): ('brightness', f), ('saturation', f), ('contrast', f)
+    with f >= 0 (at most one contrast op per frame: it blends with the frame's mean grey, which a
+    statistics pass of the output stage sums in fixed point), ('matrix', M) with M a [3, 4] matrix
+    (hue_matrix(), grey_matrix()).  Every op clamps to [0, 1].  colour_jitter() draws such lists.
+    Frames with different ops, or none, share the tail's launches.  None or []: the call without."""
     n = len(streams)
     keep, sp, ln = _marshal(streams)
     L = _bind()
     warp, keep_w = _warp(affine, n, size, roi, pad, fill)
+    col, keep_c = _colour(colour_ops, n)
+    if col is not None:
+        return _run_model(L.ccmi_decode_batch_dev_col_plan, L.ccmi_decode_batch_dev_col, (sp, ln), n,
+                          None if warp is not None else _rects(roi, streams, n), None, colour, mean, std, dtype,
+                          channels_last, mirror, out, output_bitdepth, output_chroma_format, workspace, stream_handle, size,
+                          warp, col)
     if warp is not None:
         return _run_model(L.ccmi_decode_batch_dev_warp_plan, L.ccmi_decode_batch_dev_warp, (sp, ln), n, None, None,
                           colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth, output_chroma_format,
@@ -997,16 +1145,22 @@ class LatentStore:
     def render_model(self, index=None, roi=None, colour: str = "rgb", mean=None, std=None, dtype=None,
                      channels_last: bool = False, mirror=None, out=None, output_bitdepth: int = 0,
                      output_chroma_format: int = 0, workspace=None, stream_handle: int | None = None, size=None,
-                     affine=None, pad: str = "fill", fill=0.0):
+                     affine=None, pad: str = "fill", fill=0.0, colour_ops=None):
         """render() into the tensor a model takes (ccmi_latents_render_fmt; with size
         ccmi_latents_render_rs; with affine ccmi_latents_render_warp): frames and regions as for
         render(), the result and every other argument as for decode_batch_model, whose output for
         the same streams and arguments it equals bit for bit.  workspace with a size or an affine:
         at least what render_model_workspace_bytes() reports (the resample's intermediate and a
-        warp's windows are not part of render_geometry()'s figure)."""
+        warp's windows are not part of render_geometry()'s figure).  With colour_ops
+        ccmi_latents_render_col: render_model_workspace_bytes() takes the same argument."""
         m, idx, rects = self._frames(index, None if affine is not None else roi)
         L = _bind()
         warp, keep_w = _warp(affine, m, size, roi, pad, fill)
+        col, keep_c = _colour(colour_ops, m)
+        if col is not None:
+            return _run_model(L.ccmi_latents_render_col_plan, L.ccmi_latents_render_col, (self._handle(), idx), m, rects,
+                              self._store.device, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth,
+                              output_chroma_format, workspace, stream_handle, size, warp, col)
         if warp is not None:
             return _run_model(L.ccmi_latents_render_warp_plan, L.ccmi_latents_render_warp, (self._handle(), idx), m,
                               None, self._store.device, colour, mean, std, dtype, channels_last, mirror, out,
@@ -1034,15 +1188,22 @@ class LatentStore:
                  "arm_rows": [int(v) for v in i.arm_rows[: i.n_grids]]} for i, r in zip(info, window)]
 
     def render_model_workspace_bytes(self, index=None, roi=None, size=None, output_bitdepth: int = 0,
-                                     output_chroma_format: int = 0, affine=None, pad: str = "fill", fill=0.0) -> int:
+                                     output_chroma_format: int = 0, affine=None, pad: str = "fill", fill=0.0,
+                                     colour_ops=None) -> int:
         """Header-only: the workspace render_model needs for these frames, regions and size, or
         these frames, matrices and size (ccmi_latents_render_rs_plan / _warp_plan; the element type,
-        colour and strides do not change it)."""
+        colour and strides do not change it), and these colour ops (ccmi_latents_render_col_plan:
+        the op tables and the contrast ops' accumulators)."""
         m, idx, rects = self._frames(index, None if affine is not None else roi)
         fmt = TensorFmt(elem=ELEM_F32, colour=COLOUR_ASIS)
         for c in range(3):
             fmt.scale[c] = 1.0
         warp, keep_w = _warp(affine, m, size, roi, pad, fill)
+        col, keep_c = _colour(colour_ops, m)
+        if col is not None:
+            rs = None if size is None or warp is not None else C.byref(_resample(size))
+            return _plan_model(_bind().ccmi_latents_render_col_plan, (self._handle(), idx), m, rects, fmt, rs,
+                               output_bitdepth, output_chroma_format, warp, col=col)[1]
         if warp is not None:
             return _plan_model(_bind().ccmi_latents_render_warp_plan, (self._handle(), idx), m, None, fmt, None,
                                output_bitdepth, output_chroma_format, warp)[1]
@@ -1071,5 +1232,5 @@ class LatentStore:
 
 __all__ = ["last_timing", "LatentStore", "last_arm_flags", "decode_latents", "decode_file", "decode_batch", "decode_batch_workspace_bytes", "output_size",
            "decode_batch_tensors", "decode_batch_geometry", "roi_plan", "decode_batch_model", "last_tail_groups",
-           "affine_matrix",
+           "affine_matrix", "hue_matrix", "grey_matrix", "colour_jitter",
            "weights_i32", "ups_forward_i32", "syn_forward_i32", "CcmiError"]

@@ -519,6 +519,8 @@ int build_tail_groups(Run &r)
         t.syn.workspace = reinterpret_cast<int32_t *>(r.dev + p.synws_off);
         t.dst = r.rq.device() ? static_cast<uint8_t *>(r.rq.dev[i]) : r.dev + p.out_off;
         t.rs_tmp = p.rs_elems ? reinterpret_cast<float *>(r.dev + p.rs_off) : nullptr;
+        if (t.fmt.col && r.pl.cols[i].contrast >= 0)
+            r.pl.cols[i].acc = reinterpret_cast<unsigned long long *>(r.dev + r.pl.col_off) + i;
         if (!p.batchable) continue;
         const int c = r.chunk_of[i];
         auto it = std::find_if(r.tails.begin(), r.tails.end(), [&](const TailGroup &g) {
@@ -536,7 +538,8 @@ int build_tail_groups(Run &r)
         const int m = (int)g.frames.size();
         g.off = tpos;
         dec_tail_fill(g.frames.data(), m, r.tab.data() + tpos);
-        tpos += dec_tail_table_bytes(g.frames[0]->ups.n_layers, m, g.frames[0]->windowed, dec_out_form(g.frames[0]->fmt));
+        tpos += dec_tail_table_bytes(g.frames[0]->ups.n_layers, m, g.frames[0]->windowed, dec_out_form(g.frames[0]->fmt),
+                                     g.frames[0]->fmt.col != 0);
     }
     r.tab_used = tpos;
     return CCMI_OK;
@@ -649,11 +652,11 @@ int launch_frame_tail(const Run &r, const FramePlan &p, hipStream_t cs)
                 return rc;
     }
     if (t.fmt.warp) // the whole frame is decoded: the kernel samples it where the matrix points
-        return launch_dec_warp(synout, f.h, f.w, t.bitdepth, t.kind, t.fmt, t.dst, cs);
+        return launch_dec_warp(synout, f.h, f.w, t.bitdepth, t.kind, t.fmt, t.dst, cs, t.col);
     if (t.fmt.rs)
-        return launch_dec_resample(synout, f.h, f.w, t.roi.rect, t.bitdepth, t.kind, t.fmt, t.rs_tmp, t.dst, cs);
+        return launch_dec_resample(synout, f.h, f.w, t.roi.rect, t.bitdepth, t.kind, t.fmt, t.rs_tmp, t.dst, cs, t.col);
     if (t.fmt.on) // roi.rect: the region, or the whole frame
-        return launch_dec_output_fmt(synout, f.h, f.w, t.roi.rect, t.bitdepth, t.kind, t.fmt, t.dst, cs);
+        return launch_dec_output_fmt(synout, f.h, f.w, t.roi.rect, t.bitdepth, t.kind, t.fmt, t.dst, cs, t.col);
     if (p.mode == kTailCrop)
         return launch_dec_output_tensor_roi(synout, f.h, f.w, t.roi.rect, t.bitdepth, t.kind, t.sample, t.dst, cs);
     if (r.rq.device()) return launch_dec_output_tensor(synout, f.h, f.w, t.bitdepth, t.kind, t.sample, t.dst, cs);
@@ -888,6 +891,8 @@ int decode_run(const DecodeRequest &rq, DecodePlan &pl, hipStream_t s)
         CCMI_HIP_CHECK(hipMemcpyAsync(r.dev + pl.tail_off, r.tab.data(), r.tab_used, hipMemcpyHostToDevice, s));
     if (rq.lat_store) // the networks' integers: constant part -> store, before the chunks fork
         if (int rc = launch_lat(r, r.lat[r.K], s)) return rc;
+    if (pl.col_stat) // the contrast ops' accumulators, cleared in stream before any chunk's statistics pass
+        CCMI_HIP_CHECK(hipMemsetAsync(r.dev + pl.col_off, 0, sizeof(unsigned long long) * pl.fr.size(), s));
     ev.rec(1, s);
     if (int rc = run_chunks(r, ev, lease)) return rc;
     if (!rq.lat_store) { // what launch_chunk ran: every group, and a tail of its own per other frame
@@ -1009,7 +1014,7 @@ extern "C" int ccmi_decode_batch_ws(const uint8_t *const *streams, const size_t 
 }
 
 // ------------------------------------------------------------------ device sinks
-// Twenty entry points over one table: the source is the caller's streams or a latent store, the
+// Twenty-four entry points over one table: the source is the caller's streams or a latent store, the
 // sink plain samples (sample_type; with or without a region) or formatted ones (fmt, forced to
 // CCMI_SAMPLE_F32, the call whose output kernel the format replaces; with or without a resample,
 // or with a warp, which takes no region),
@@ -1021,18 +1026,26 @@ struct Sink {
     const ccmi_tensor_fmt *fmt;
     const ccmi_resample *rs;
     const ccmi_warp *warp;
+    const ccmi_colour *colour;
 };
 
-static Sink samples(const ccmi_rect *roi, int sample_type) { return Sink{roi, sample_type, nullptr, nullptr, nullptr}; }
+static Sink samples(const ccmi_rect *roi, int sample_type) { return Sink{roi, sample_type, nullptr, nullptr, nullptr, nullptr}; }
 
 static Sink formatted(const ccmi_rect *roi, const ccmi_tensor_fmt *fmt, const ccmi_resample *rs)
 {
-    return Sink{roi, CCMI_SAMPLE_F32, fmt, rs, nullptr};
+    return Sink{roi, CCMI_SAMPLE_F32, fmt, rs, nullptr, nullptr};
 }
 
 static Sink warped(const ccmi_tensor_fmt *fmt, const ccmi_warp *warp)
 {
-    return Sink{nullptr, CCMI_SAMPLE_F32, fmt, nullptr, warp};
+    return Sink{nullptr, CCMI_SAMPLE_F32, fmt, nullptr, warp, nullptr};
+}
+
+// the superset: a resample or a warp or neither, and colour ops; what may not go together is the plan's to refuse
+static Sink coloured(const ccmi_rect *roi, const ccmi_tensor_fmt *fmt, const ccmi_resample *rs, const ccmi_warp *warp,
+                     const ccmi_colour *colour)
+{
+    return Sink{roi, CCMI_SAMPLE_F32, fmt, rs, warp, colour};
 }
 
 static void set_sink(DecodeRequest &rq, const Sink &k)
@@ -1042,6 +1055,7 @@ static void set_sink(DecodeRequest &rq, const Sink &k)
     rq.fmt = k.fmt;
     rq.rs = k.rs;
     rq.warp = k.warp;
+    rq.colour = k.colour;
 }
 
 // streams as the source: null arguments, then the sample type, then the plan's own errors
@@ -1184,6 +1198,35 @@ extern "C" int ccmi_decode_batch_dev_warp(const uint8_t *const *streams, const s
     DecodeRequest rq;
     if (int rc = stream_request("decode_batch_dev_warp (frame 0)", streams, lens, n, warped(fmt, warp), out_bitdepth,
                                 out_chroma, !out_dev || !out_caps || !fmt || !warp || !warp->matrix, rq))
+        return rc;
+    return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
+}
+
+// The colouring sink: the superset of the three above with a ccmi_colour (colour NULL: that call itself).
+extern "C" int ccmi_decode_batch_dev_col_plan(const uint8_t *const *streams, const size_t *lens, int n,
+                                              const ccmi_rect *roi, int out_bitdepth, int out_chroma,
+                                              const ccmi_tensor_fmt *fmt, const ccmi_resample *rs, const ccmi_warp *warp,
+                                              const ccmi_colour *colour, ccmi_frame_geom *geom, ccmi_roi_info *info,
+                                              ccmi_rect *window, size_t *workspace_bytes)
+{
+    DecodeRequest rq;
+    if (int rc = stream_request("decode_batch_dev_col_plan (frame 0)", streams, lens, n, coloured(roi, fmt, rs, warp, colour),
+                                out_bitdepth, out_chroma,
+                                !fmt || (warp && !warp->matrix) || (window && !warp) || !geom || !workspace_bytes, rq))
+        return rc;
+    rq.window = window;
+    return sink_plan(rq, geom, info, workspace_bytes);
+}
+
+extern "C" int ccmi_decode_batch_dev_col(const uint8_t *const *streams, const size_t *lens, int n, const ccmi_rect *roi,
+                                         void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
+                                         const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
+                                         int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes,
+                                         void *stream)
+{
+    DecodeRequest rq;
+    if (int rc = stream_request("decode_batch_dev_col (frame 0)", streams, lens, n, coloured(roi, fmt, rs, warp, colour),
+                                out_bitdepth, out_chroma, !out_dev || !out_caps || !fmt || (warp && !warp->matrix), rq))
         return rc;
     return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
 }
@@ -1378,6 +1421,34 @@ extern "C" int ccmi_latents_render_warp(const ccmi_latents *h, const int *index,
     DecodeRequest rq;
     if (int rc = latents_request("latents_render_warp (frame 0)", h, index, m, warped(fmt, warp), out_bitdepth, out_chroma,
                                  true, !out_dev || !out_caps || !fmt || !warp || !warp->matrix, rq))
+        return rc;
+    return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ccmi_latents_render_col_plan(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
+                                            int out_bitdepth, int out_chroma, const ccmi_tensor_fmt *fmt,
+                                            const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
+                                            ccmi_frame_geom *geom, ccmi_roi_info *info, ccmi_rect *window,
+                                            size_t *workspace_bytes)
+{
+    DecodeRequest rq;
+    if (int rc = latents_request("latents_render_col_plan (frame 0)", h, index, m, coloured(roi, fmt, rs, warp, colour),
+                                 out_bitdepth, out_chroma, false,
+                                 !fmt || (warp && !warp->matrix) || (window && !warp) || !geom || !workspace_bytes, rq))
+        return rc;
+    rq.window = window;
+    return sink_plan(rq, geom, info, workspace_bytes);
+}
+
+extern "C" int ccmi_latents_render_col(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
+                                       void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
+                                       const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
+                                       int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes,
+                                       void *stream)
+{
+    DecodeRequest rq;
+    if (int rc = latents_request("latents_render_col (frame 0)", h, index, m, coloured(roi, fmt, rs, warp, colour),
+                                 out_bitdepth, out_chroma, true, !out_dev || !out_caps || !fmt || (warp && !warp->matrix), rq))
         return rc;
     return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
 }

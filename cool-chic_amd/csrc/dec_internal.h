@@ -171,23 +171,43 @@ struct DecFmt {
     int pad = 0;
     float fill[3] = {0.f, 0.f, 0.f};
     float m[6] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f};
+    // ccmi_colour with at least one op in the call (one value per call): the colour forms of the
+    // output kernels run, each frame with its own DecCol (DecTailFrame::col), after any of the above
+    int col = 0;
 };
+// ccmi_colour of one frame (step 3z of the contract in ccmi.h), validated and resolved by the plan:
+// the op table the colour forms of the output kernels read from the tail's argument tables.
+struct DecColOp {
+    int op;      // CCMI_COL_*
+    float v[12]; // v[0] = f and, SATURATION / CONTRAST, v[1] = 1 - f (float32, computed once here); MATRIX: M
+};
+struct DecCol {
+    int n = 0;         // ops
+    int contrast = -1; // the index of the frame's contrast op, or -1
+    // device: the frame's S_j in the workspace (decode_run), cleared in stream and summed by the
+    // statistics pass before the output kernel reads it; unused without a contrast op
+    unsigned long long *acc = nullptr;
+    DecColOp ops[CCMI_COL_MAX_OPS] = {};
+};
+
 // the form of a tail group's output section: DecOut, or its resample / warp extension
 enum { kOutPlain = 0, kOutRs = 1, kOutWarp = 2 };
 inline int dec_out_form(const DecFmt &f) { return f.rs ? kOutRs : f.warp ? kOutWarp : kOutPlain; }
 // One frame: the region `rect` of the h x w synthesis output (12-bit, [3][h][w]) as the formatted
 // tensor at dst; kind 0 takes planes 1 and 2 at the even row and column (rect's origin even).
+// fmt.col (here and below): col is the frame's op table and the colour form of the kernel runs,
+// after the statistics pass when the frame has a contrast op (col->acc: cleared by the caller, in stream).
 int launch_dec_output_fmt(const int32_t *syn, int h, int w, const DecWindow &rect, int bitdepth, int kind,
-                          const DecFmt &fmt, void *dst, hipStream_t s);
+                          const DecFmt &fmt, void *dst, hipStream_t s, const DecCol *col = nullptr);
 // The same with fmt.rs: the region is resampled to fmt.out_h x fmt.out_w on the way.  tmp holds the
 // horizontal pass, dec_resample_tmp_elems() floats.
 size_t dec_resample_tmp_elems(int region_h, int out_w);
 int launch_dec_resample(const int32_t *syn, int h, int w, const DecWindow &rect, int bitdepth, int kind,
-                        const DecFmt &fmt, float *tmp, void *dst, hipStream_t s);
+                        const DecFmt &fmt, float *tmp, void *dst, hipStream_t s, const DecCol *col = nullptr);
 // The same with fmt.warp: the fmt.out_h x fmt.out_w frame at dst samples the whole h x w synthesis
 // output through fmt.m (kind 0: h and w even).
 int launch_dec_warp(const int32_t *syn, int h, int w, int bitdepth, int kind, const DecFmt &fmt, void *dst,
-                    hipStream_t s);
+                    hipStream_t s, const DecCol *col = nullptr);
 
 // Batched decoder tail: frames with the same geometry and a fused-synthesis architecture
 // (single branch) share one launch per pyramid step, one synthesis and one output launch
@@ -202,6 +222,7 @@ struct DecTailFrame {
     int sample = -1; // -1: file bytes at dst (workspace staging); CCMI_SAMPLE_*: planar tensor at dst (caller's)
     DecFmt fmt;      // fmt.on: the formatted tensor at dst instead (sample is then CCMI_SAMPLE_F32, unused)
     float *rs_tmp = nullptr; // fmt.rs: the frame's horizontal-pass intermediate, [3][region h][out_w]
+    const DecCol *col = nullptr; // fmt.col: the frame's colour ops (n == 0: none), in DecodePlan::cols
     // region decode on windows: the latent planes keep their frame pitch and hold roi.arm_rows[l]
     // rows, ups.workspace / ups.out / syn.out hold the windows roi.lev[k] / the region, compact
     // (pitch = the window's width); ups.lh / lw and syn.h / w stay the frame's true sizes
@@ -210,7 +231,8 @@ struct DecTailFrame {
 };
 bool dec_tail_batchable(const DecTailFrame &f);
 bool dec_tail_same_group(const DecTailFrame &a, const DecTailFrame &b);
-size_t dec_tail_table_bytes(int n_layers, int n, bool windowed = false, int out_form = kOutPlain);
+// col: the group's frames carry a DecCol each, a fourth section of the table
+size_t dec_tail_table_bytes(int n_layers, int n, bool windowed = false, int out_form = kOutPlain, bool col = false);
 void dec_tail_fill(const DecTailFrame *const *fr, int n, void *host_tab);
 // fr: the group's frames, in table order (a window-form group sizes its grids by their windows)
 int launch_dec_tail_batch(const DecTailFrame *const *fr, int n, const void *dev_tab, hipStream_t s);

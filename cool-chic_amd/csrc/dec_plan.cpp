@@ -182,6 +182,47 @@ int tensor_fmt(const ccmi_tensor_fmt &m, const ccmi_resample *rs, const ccmi_war
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
+// ccmi_colour of frame i, whose ops start at `first` of the flat array: validated and resolved into d
+// (1 - f in float32 here, once; a factor of -0 becomes +0).
+int colour_ops(const ccmi_colour &cl, int i, size_t first, DecCol &d)
+{
+    const int n = cl.count[i];
+    if (n < 0 || n > CCMI_COL_MAX_OPS)
+        return ccmi_set_error(CCMI_ERR_ARG, "frame %d: %d colour ops (0 .. %d)", i, n, CCMI_COL_MAX_OPS);
+    d = DecCol{};
+    d.n = n;
+    for (int k = 0; k < n; ++k) {
+        const ccmi_colour_op &op = cl.ops[first + k];
+        DecColOp &o = d.ops[k];
+        o.op = op.op;
+        switch (op.op) {
+        case CCMI_COL_MATRIX:
+            for (int e = 0; e < 12; ++e) {
+                if (!std::isfinite(op.v[e]))
+                    return ccmi_set_error(CCMI_ERR_ARG, "frame %d: colour op %d: matrix entry %d is not finite", i, k, e);
+                o.v[e] = op.v[e];
+            }
+            break;
+        case CCMI_COL_CONTRAST:
+            if (d.contrast >= 0)
+                return ccmi_set_error(CCMI_ERR_ARG, "frame %d: colour ops %d and %d are both contrast ops (at most one)", i,
+                                      d.contrast, k);
+            d.contrast = k;
+            [[fallthrough]];
+        case CCMI_COL_BRIGHTNESS:
+        case CCMI_COL_SATURATION:
+            if (!std::isfinite(op.v[0]) || op.v[0] < 0.f)
+                return ccmi_set_error(CCMI_ERR_ARG, "frame %d: colour op %d: factor %g (finite, >= 0)", i, k, (double)op.v[0]);
+            o.v[0] = op.v[0] + 0.f;
+            o.v[1] = 1.f - o.v[0];
+            break;
+        default:
+            return ccmi_set_error(CCMI_ERR_ARG, "frame %d: colour op %d: unknown op %d", i, k, op.op);
+        }
+    }
+    return CCMI_OK;
+}
+
 // the architecture part of a frame's tail arguments (no device pointers): what
 // dec_tail_batchable() looks at, the true plane sizes and the workspace sizes
 void tail_arch(const FrameHost &f, DecTailFrame &t)
@@ -399,7 +440,8 @@ void plan_layout(const DecodeRequest &rq, DecodePlan &pl)
     // batched-tail argument tables: bounded by one single-frame table per frame
     pl.tail_cap = 0;
     for (const FramePlan &p : pl.fr)
-        if (!build) pl.tail_cap += dec_tail_table_bytes(p.f.n_layers, 1, p.mode == kTailWindow, dec_out_form(p.tail.fmt));
+        if (!build)
+            pl.tail_cap += dec_tail_table_bytes(p.f.n_layers, 1, p.mode == kTailWindow, dec_out_form(p.tail.fmt), pl.col);
     pl.tail_off = tot;
     tot += align_up(pl.tail_cap, 256);
     // the pack / unpack job table follows the tail tables: one host image, one upload.  A build
@@ -410,6 +452,8 @@ void plan_layout(const DecodeRequest &rq, DecodePlan &pl)
         pl.lat_tab_cap += build ? sizeof(DecLatPackJob) * (size_t)(p.f.n_layers + 2)
                                 : render ? sizeof(DecLatUnpackJob) * (size_t)p.f.n_layers : 0;
     tot += align_up(pl.lat_tab_cap, 256);
+    pl.col_off = tot;
+    if (pl.col) tot += align_up(sizeof(unsigned long long) * pl.fr.size(), 256);
     pl.status_off = tot;
     if (!render) tot += align_up(4 * pl.n_status(), 256);
 #if defined(CCMI_ARM_STAMPS)
@@ -427,10 +471,32 @@ int decode_plan(const DecodeRequest &rq, DecodePlan &pl)
     if (rq.src && !rq.index && rq.n != (int)rq.src->s.size())
         return ccmi_set_error(CCMI_ERR_ARG, "render: %d frames without an index, the handle has %zu streams", rq.n,
                               rq.src->s.size());
+    if (rq.rs && rq.warp)
+        return ccmi_set_error(CCMI_ERR_ARG, "frame 0: a resample and a warp are both given (a call takes one geometry)");
+    if (rq.warp && rq.roi)
+        return ccmi_set_error(CCMI_ERR_ARG, "frame 0: a warp takes no roi (the matrix says where the output lies)");
     pl = DecodePlan{};
     pl.fr.resize(rq.n);
-    for (int i = 0; i < rq.n; ++i)
+    if (rq.colour) { // every frame's ops first: whether any frame has one decides the form of the whole call
+        if (!rq.fmt || !rq.colour->count)
+            return ccmi_set_error(CCMI_ERR_ARG, "frame 0: colour without %s", rq.fmt ? "its counts" : "a format");
+        size_t first = 0;
+        pl.cols.resize(rq.n);
+        for (int i = 0; i < rq.n; ++i) {
+            if (rq.colour->count[i] > 0 && !rq.colour->ops) return ccmi_set_error(CCMI_ERR_ARG, "frame %d: colour ops are NULL", i);
+            DecCol &d = pl.cols[i];
+            if (int rc = colour_ops(*rq.colour, i, first, d)) return rc;
+            first += (size_t)d.n;
+            pl.col = pl.col || d.n > 0;
+            pl.col_stat = pl.col_stat || d.contrast >= 0;
+        }
+    }
+    if (!pl.col) pl.cols.clear(); // no op in any frame: the call without colour
+    for (int i = 0; i < rq.n; ++i) {
         if (int rc = plan_frame(rq, i, pl.fr[i])) return rc;
+        pl.fr[i].tail.fmt.col = pl.col ? 1 : 0;
+        pl.fr[i].tail.col = pl.col ? &pl.cols[i] : nullptr;
+    }
     plan_layout(rq, pl);
     return CCMI_OK;
 }

@@ -84,6 +84,9 @@ struct DecodeRequest {
     // frame's matrix (ccmi_warp); the plan derives each frame's region, its window, from the matrix
     const ccmi_warp *warp = nullptr;
     ccmi_rect *window = nullptr; // [n], optional: the windows, filled by the plan
+    // with fmt, optional: every frame's own list of colour ops between the geometry and scale / bias
+    // (ccmi_colour); with an op in any frame the call runs the colour forms of the output kernels
+    const ccmi_colour *colour = nullptr;
     // either sink
     const size_t *caps = nullptr;    // [n], optional: capacity in bytes of outs[i] / dev[i]
     size_t *sizes = nullptr;         // [n], optional: bytes written per stream (filled by the plan)
@@ -131,6 +134,10 @@ struct DecodePlan {
     size_t status_off = 0; // one word per (frame, latent grid): the ARM kernels' CCMI_ARM_FLAG_* bits
     size_t lat_tab_off = 0; // latent-store sink / source: the pack / unpack job table, lat_tab_cap bytes
     size_t lat_tab_cap = 0;
+    bool col = false;      // a frame has colour ops (DecFmt::col of every frame)
+    std::vector<DecCol> cols; // col: every frame's ops (DecTailFrame::col points here); empty otherwise
+    bool col_stat = false; // a frame has a contrast op: the accumulators are cleared before the tails run
+    size_t col_off = 0;    // col: one 64-bit accumulator per frame (S_j of its contrast op)
 #if defined(CCMI_ARM_STAMPS)
     size_t dbg_off = 0;
 #endif

@@ -734,6 +734,83 @@ __device__ __forceinline__ void fmt_pixel(const int32_t *__restrict__ lrow, cons
     }
 }
 
+// ---- the colour stage (step 3z of the contract in ccmi.h, ccmi_colour)
+// The three output bodies below take a mode: kColNone is the body as it always was (the kernels
+// without colour instantiate it, and nothing of the stage is compiled into them); kColWrite puts
+// the pixel through its frame's ops between the geometry and scale / bias; kColStat is the
+// statistics pass of the frames with a contrast op: the same pixels through the ops that precede
+// the contrast op, their integer grey terms summed per thread, per wave and, by one 64-bit atomic
+// add per wave, per frame.  Nothing is stored in that mode and no thread leaves before the wave's
+// reduction.  The pass evaluates the geometry a second time and stages nothing: what it would stage
+// is three float32 per output pixel written and read again, more traffic than the taps it re-reads
+// from a synthesis output that the stage before has just left in the cache.
+// The op table is one DecCol per frame in the tail's argument tables, or the kernel's own argument
+// (the per-frame tail): uniform per block, so the loop over the ops branches on scalars.
+enum { kColNone = 0, kColWrite = 1, kColStat = 2 };
+
+__device__ __forceinline__ float col_clamp(float t) { return fminf(fmaxf(t, 0.f), 1.f); }
+
+__device__ __forceinline__ float col_grey(const float (&x)[3])
+{
+    return fmt_add(fmt_add(fmt_mul(0.2989f, x[0]), fmt_mul(0.587f, x[1])), fmt_mul(0.114f, x[2]));
+}
+
+// ops [first, last) of the frame on one pixel; mean = m_j (read by a contrast op only)
+__device__ __forceinline__ void col_ops(const DecCol &K, int first, int last, float mean, float (&x)[3])
+{
+    for (int i = first; i < last; ++i) {
+        const DecColOp &P = K.ops[i];
+        if (P.op == CCMI_COL_MATRIX) {
+            float y[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                y[c] = col_clamp(fmt_add(
+                    fmt_add(fmt_add(fmt_mul(P.v[4 * c], x[0]), fmt_mul(P.v[4 * c + 1], x[1])), fmt_mul(P.v[4 * c + 2], x[2])),
+                    P.v[4 * c + 3]));
+#pragma unroll
+            for (int c = 0; c < 3; ++c) x[c] = y[c];
+        } else if (P.op == CCMI_COL_BRIGHTNESS) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) x[c] = col_clamp(fmt_mul(P.v[0], x[c]));
+        } else { // towards the pixel's grey (saturation) or the frame's mean grey (contrast)
+            const float b = fmt_mul(P.v[1], P.op == CCMI_COL_SATURATION ? col_grey(x) : mean);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) x[c] = col_clamp(fmt_add(fmt_mul(P.v[0], x[c]), b));
+        }
+    }
+}
+
+// kColWrite: m_j of a frame of npix output pixels from the sum the statistics pass left
+__device__ __forceinline__ float col_mean(const DecCol &K, int npix)
+{
+    if (K.contrast < 0) return 0.f;
+    const float m = (float)((double)*K.acc / ((double)npix * 65535.0));
+    return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(m))); // one value per block: kept in a scalar
+}
+
+// kColStat: one pixel's term of S_j, at most 65535
+__device__ __forceinline__ uint32_t col_term(const DecCol &K, float (&x)[3])
+{
+    col_ops(K, 0, K.contrast, 0.f, x);
+    return (uint32_t)rintf(fmt_mul(col_clamp(col_grey(x)), 65535.0f));
+}
+
+// kColStat: the thread's sum (4 pixels) -> the wave's (at most 2^24) -> the frame's; every lane of
+// the wave arrives here.  Integer additions: the order of the waves does not show in the sum.
+__device__ __forceinline__ void col_accumulate(const DecCol &K, uint32_t sum)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    if ((threadIdx.x & 63) == 0 && sum) atomicAdd(K.acc, (unsigned long long)sum);
+}
+
+// the format of a statistics pass: its groups of 4 pixels start at pixel 0 of every row
+__device__ __forceinline__ DecFmtCall col_stat_call()
+{
+    DecFmtCall C{};
+    return C;
+}
+
 // step 6 for a thread's 4 destination pixels d0 .. d0 + 3 of the row at `row` elements (w pixels
 // wide): the packed stores where the layout and the alignment allow them
 template <typename T>
@@ -800,15 +877,18 @@ __device__ __forceinline__ bool fmt_group(const T *dst, const DecFmtCall &C, int
 
 // h x w = the region at (oy, ox) of the synthesis output syn (planes splane apart, pitch spitch;
 // oy, ox even for kind 0)
-template <typename T>
-__device__ __forceinline__ void output_fmt_body(const int32_t *__restrict__ syn, int64_t splane, int spitch, int oy,
-                                                int ox, int h, int w, int maxv, int kind, int flags,
-                                                T *__restrict__ dst, const DecFmtCall &C)
+template <typename T, int COL = kColNone>
+__device__ __forceinline__ uint32_t output_fmt_body(const int32_t *__restrict__ syn, int64_t splane, int spitch, int oy,
+                                                    int ox, int h, int w, int maxv, int kind, int flags,
+                                                    T *__restrict__ dst, const DecFmtCall &C, const DecCol *K = nullptr)
 {
     int y, d0;
     int64_t row;
     bool nchw, nhwc;
-    if (!fmt_group<T>(dst, C, h, w, y, d0, row, nchw, nhwc)) return;
+    if (!fmt_group<T>(dst, C, h, w, y, d0, row, nchw, nhwc)) return 0;
+    float mean = 0.f;
+    uint32_t sum = 0;
+    if constexpr (COL == kColWrite) mean = col_mean(*K, h * w);
     const float fmax = (float)maxv;
     const bool mirror = flags & kFmtMirror, matrix = flags & kFmtMatrix;
     const int32_t *__restrict__ lrow = syn + (int64_t)(oy + y) * spitch + ox;
@@ -823,10 +903,16 @@ __device__ __forceinline__ void output_fmt_body(const int32_t *__restrict__ syn,
         const int x = mirror ? w - 1 - d : d;
         float q[3];
         fmt_pixel(lrow, crow, splane, x, kind == 1 ? x : x & ~1, maxv, fmax, matrix, q);
+        if constexpr (COL == kColStat) {
+            sum += col_term(*K, q);
+            continue;
+        }
+        if constexpr (COL == kColWrite) col_ops(*K, 0, K->n, mean, q);
 #pragma unroll
         for (int c = 0; c < 3; ++c) v[c][k] = fmt_elem<T>(fmt_add(fmt_mul(q[c], C.scale[c]), C.bias[c]));
     }
-    fmt_store<T>(v, dst, C, row, d0, w, nchw, nhwc);
+    if constexpr (COL != kColStat) fmt_store<T>(v, dst, C, row, d0, w, nchw, nhwc);
+    return sum;
 }
 
 template <typename T>
@@ -837,6 +923,22 @@ __global__ __launch_bounds__(kThreads) void dec_output_fmt(const int32_t *__rest
     output_fmt_body<T>(syn, (int64_t)H * W, W, oy, ox, h, w, maxv, kind, flags, dst, C);
 }
 
+// the colour forms (ccmi_colour): K = the frame's ops; the statistics pass of a frame with a contrast op
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_output_fmt_col(const int32_t *__restrict__ syn, int H, int W, int oy, int ox,
+                                                               int h, int w, int maxv, int kind, int flags,
+                                                               T *__restrict__ dst, DecFmtCall C, DecCol K)
+{
+    output_fmt_body<T, kColWrite>(syn, (int64_t)H * W, W, oy, ox, h, w, maxv, kind, flags, dst, C, &K);
+}
+
+__global__ __launch_bounds__(kThreads) void dec_output_fmt_stat(const int32_t *__restrict__ syn, int H, int W, int oy, int ox,
+                                                                int h, int w, int maxv, int kind, int flags, DecCol K)
+{
+    col_accumulate(K, output_fmt_body<float, kColStat>(syn, (int64_t)H * W, W, oy, ox, h, w, maxv, kind, flags, nullptr,
+                                                       col_stat_call(), &K));
+}
+
 // a tail group: frame blockIdx.y's compact H x W synthesis output (DecOut::bps = its kFmt* flags)
 template <typename T>
 __global__ __launch_bounds__(kThreads) void dec_output_fmt_batch(const DecOut *__restrict__ Os, DecFmtCall C)
@@ -844,6 +946,27 @@ __global__ __launch_bounds__(kThreads) void dec_output_fmt_batch(const DecOut *_
     const DecOut O = Os[blockIdx.y];
     output_fmt_body<T>(O.syn, (int64_t)O.H * O.W, O.W, 0, 0, O.H, O.W, O.maxv, O.kind, O.bps, reinterpret_cast<T *>(O.dst),
                        C);
+}
+
+// the colour forms of a tail group: Ks = the group's op tables, one per frame
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_output_fmt_col_batch(const DecOut *__restrict__ Os, DecFmtCall C,
+                                                                     const DecCol *__restrict__ Ks)
+{
+    const DecOut O = Os[blockIdx.y];
+    output_fmt_body<T, kColWrite>(O.syn, (int64_t)O.H * O.W, O.W, 0, 0, O.H, O.W, O.maxv, O.kind, O.bps,
+                                  reinterpret_cast<T *>(O.dst), C, Ks + blockIdx.y);
+}
+
+// only the frames with a contrast op take part
+__global__ __launch_bounds__(kThreads) void dec_output_fmt_stat_batch(const DecOut *__restrict__ Os,
+                                                                      const DecCol *__restrict__ Ks)
+{
+    const DecCol &K = Ks[blockIdx.y];
+    if (K.contrast < 0) return;
+    const DecOut O = Os[blockIdx.y];
+    col_accumulate(K, output_fmt_body<float, kColStat>(O.syn, (int64_t)O.H * O.W, O.W, 0, 0, O.H, O.W, O.maxv, O.kind, O.bps,
+                                                       nullptr, col_stat_call(), &K));
 }
 
 unsigned output_fmt_blocks(int h, int w)
@@ -932,14 +1055,14 @@ __device__ __forceinline__ void resample_h_body(const int32_t *__restrict__ syn,
 }
 
 // tmp = [3][h][ow] of resample_h_body; the frame at dst is oh x ow
-template <typename T>
-__device__ __forceinline__ void resample_v_body(const float *__restrict__ tmp, int h, int oh, int ow, int flags,
-                                                T *__restrict__ dst, const DecFmtCall &C)
+template <typename T, int COL = kColNone>
+__device__ __forceinline__ uint32_t resample_v_body(const float *__restrict__ tmp, int h, int oh, int ow, int flags,
+                                                    T *__restrict__ dst, const DecFmtCall &C, const DecCol *K = nullptr)
 {
     int y, d0;
     int64_t row;
     bool nchw, nhwc;
-    if (!fmt_group<T>(dst, C, oh, ow, y, d0, row, nchw, nhwc)) return;
+    if (!fmt_group<T>(dst, C, oh, ow, y, d0, row, nchw, nhwc)) return 0;
     const RsTaps R = rs_taps(y, h, oh);
     const bool mirror = flags & kFmtMirror;
     // element indices of tmp fit 32 bits (3 h ow <= 3 * 2^28): one base and 32-bit offsets
@@ -961,12 +1084,29 @@ __device__ __forceinline__ void resample_v_body(const float *__restrict__ tmp, i
 #pragma unroll
             for (int k = 0; k < 4; ++k) acc[c][k] = fmt_add(acc[c][k], fmt_mul(wj, tmp[c * tplane + r0 + x[k]]));
     }
+    if constexpr (COL != kColNone) {
+        const float mean = COL == kColWrite ? col_mean(*K, oh * ow) : 0.f;
+        uint32_t sum = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float q[3] = {acc[0][k], acc[1][k], acc[2][k]};
+            if constexpr (COL == kColStat) {
+                if (d0 + k >= 0 && d0 + k < ow) sum += col_term(*K, q); // a surplus slot repeats a pixel
+            } else {
+                col_ops(*K, 0, K->n, mean, q);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) acc[c][k] = q[c];
+            }
+        }
+        if constexpr (COL == kColStat) return sum;
+    }
     T v[3][4];
 #pragma unroll
     for (int c = 0; c < 3; ++c)
 #pragma unroll
         for (int k = 0; k < 4; ++k) v[c][k] = fmt_elem<T>(fmt_add(fmt_mul(acc[c][k], C.scale[c]), C.bias[c]));
     fmt_store<T>(v, dst, C, row, d0, ow, nchw, nhwc);
+    return 0;
 }
 
 __global__ __launch_bounds__(kThreads) void dec_resample_h(const int32_t *__restrict__ syn, int H, int W, int oy, int ox,
@@ -983,6 +1123,19 @@ __global__ __launch_bounds__(kThreads) void dec_resample_v(const float *__restri
     resample_v_body<T>(tmp, h, oh, ow, flags, dst, C);
 }
 
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_resample_v_col(const float *__restrict__ tmp, int h, int oh, int ow,
+                                                               int flags, T *__restrict__ dst, DecFmtCall C, DecCol K)
+{
+    resample_v_body<T, kColWrite>(tmp, h, oh, ow, flags, dst, C, &K);
+}
+
+__global__ __launch_bounds__(kThreads) void dec_resample_v_stat(const float *__restrict__ tmp, int h, int oh, int ow,
+                                                                int flags, DecCol K)
+{
+    col_accumulate(K, resample_v_body<float, kColStat>(tmp, h, oh, ow, flags, nullptr, col_stat_call(), &K));
+}
+
 // a tail group: frame blockIdx.y's compact region; the grid covers the group's largest region
 __global__ __launch_bounds__(kThreads) void dec_resample_h_batch(const DecOutRs *__restrict__ Os, int ow)
 {
@@ -997,6 +1150,23 @@ __global__ __launch_bounds__(kThreads) void dec_resample_v_batch(const DecOutRs 
 {
     const DecOutRs R = Os[blockIdx.y];
     resample_v_body<T>(R.tmp, R.o.H, oh, ow, R.o.bps, reinterpret_cast<T *>(R.o.dst), C);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_resample_v_col_batch(const DecOutRs *__restrict__ Os, int oh, int ow,
+                                                                     DecFmtCall C, const DecCol *__restrict__ Ks)
+{
+    const DecOutRs R = Os[blockIdx.y];
+    resample_v_body<T, kColWrite>(R.tmp, R.o.H, oh, ow, R.o.bps, reinterpret_cast<T *>(R.o.dst), C, Ks + blockIdx.y);
+}
+
+__global__ __launch_bounds__(kThreads) void dec_resample_v_stat_batch(const DecOutRs *__restrict__ Os, int oh, int ow,
+                                                                      const DecCol *__restrict__ Ks)
+{
+    const DecCol &K = Ks[blockIdx.y];
+    if (K.contrast < 0) return;
+    const DecOutRs R = Os[blockIdx.y];
+    col_accumulate(K, resample_v_body<float, kColStat>(R.tmp, R.o.H, oh, ow, R.o.bps, nullptr, col_stat_call(), &K));
 }
 
 unsigned resample_h_blocks(int h, int ow) { return (unsigned)(((int64_t)h * ow + kThreads - 1) / kThreads); }
@@ -1025,15 +1195,18 @@ struct DecOutWarp {
     int oy, ox, fh, fw; // the window's origin in the frame, and the frame
 };
 
-template <typename T>
-__device__ __forceinline__ void warp_body(const int32_t *__restrict__ syn, int h, int w, int oy, int ox, int fh, int fw,
-                                          const float (&m)[6], int maxv, int kind, int flags, T *__restrict__ dst,
-                                          const DecFmtCall &C, const DecWarpCall &Wc)
+template <typename T, int COL = kColNone>
+__device__ __forceinline__ uint32_t warp_body(const int32_t *__restrict__ syn, int h, int w, int oy, int ox, int fh, int fw,
+                                              const float (&m)[6], int maxv, int kind, int flags, T *__restrict__ dst,
+                                              const DecFmtCall &C, const DecWarpCall &Wc, const DecCol *K = nullptr)
 {
     int y, d0;
     int64_t row;
     bool nchw, nhwc;
-    if (!fmt_group<T>(dst, C, Wc.oh, Wc.ow, y, d0, row, nchw, nhwc)) return;
+    if (!fmt_group<T>(dst, C, Wc.oh, Wc.ow, y, d0, row, nchw, nhwc)) return 0;
+    float mean = 0.f;
+    uint32_t sum = 0;
+    if constexpr (COL == kColWrite) mean = col_mean(*K, Wc.oh * Wc.ow);
     const float fmax = (float)maxv;
     const bool mirror = flags & kFmtMirror, matrix = flags & kFmtMatrix;
     const int64_t splane = (int64_t)h * w;
@@ -1077,13 +1250,27 @@ __device__ __forceinline__ void warp_body(const int32_t *__restrict__ syn, int h
 #pragma unroll
             for (int c = 0; c < 3; ++c) line[a][c] = fmt_add(fmt_mul(t[0][c], gx), fmt_mul(t[1][c], fx));
         }
+        if constexpr (COL == kColNone) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float r = fmt_add(fmt_mul(line[0][c], gy), fmt_mul(line[1][c], fy));
-            v[c][k] = fmt_elem<T>(fmt_add(fmt_mul(r, C.scale[c]), C.bias[c]));
+            for (int c = 0; c < 3; ++c) {
+                const float r = fmt_add(fmt_mul(line[0][c], gy), fmt_mul(line[1][c], fy));
+                v[c][k] = fmt_elem<T>(fmt_add(fmt_mul(r, C.scale[c]), C.bias[c]));
+            }
+        } else {
+            float r[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) r[c] = fmt_add(fmt_mul(line[0][c], gy), fmt_mul(line[1][c], fy));
+            if constexpr (COL == kColStat) {
+                sum += col_term(*K, r);
+            } else {
+                col_ops(*K, 0, K->n, mean, r);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) v[c][k] = fmt_elem<T>(fmt_add(fmt_mul(r[c], C.scale[c]), C.bias[c]));
+            }
         }
     }
-    fmt_store<T>(v, dst, C, row, d0, Wc.ow, nchw, nhwc);
+    if constexpr (COL != kColStat) fmt_store<T>(v, dst, C, row, d0, Wc.ow, nchw, nhwc);
+    return sum;
 }
 
 // one frame (DecOut::bps = its kFmt* flags): the per-frame tail's, A.o = the whole synthesis output
@@ -1101,6 +1288,38 @@ __global__ __launch_bounds__(kThreads) void dec_warp_batch(const DecOutWarp *__r
     const DecOutWarp A = Os[blockIdx.y];
     warp_body<T>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind, A.o.bps,
                  reinterpret_cast<T *>(A.o.dst), C, Wc);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_warp_col(DecOutWarp A, DecFmtCall C, DecWarpCall Wc, DecCol K)
+{
+    warp_body<T, kColWrite>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind, A.o.bps,
+                            reinterpret_cast<T *>(A.o.dst), C, Wc, &K);
+}
+
+__global__ __launch_bounds__(kThreads) void dec_warp_stat(DecOutWarp A, DecWarpCall Wc, DecCol K)
+{
+    col_accumulate(K, warp_body<float, kColStat>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind,
+                                                 A.o.bps, nullptr, col_stat_call(), Wc, &K));
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_warp_col_batch(const DecOutWarp *__restrict__ Os, DecFmtCall C, DecWarpCall Wc,
+                                                               const DecCol *__restrict__ Ks)
+{
+    const DecOutWarp A = Os[blockIdx.y];
+    warp_body<T, kColWrite>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind, A.o.bps,
+                            reinterpret_cast<T *>(A.o.dst), C, Wc, Ks + blockIdx.y);
+}
+
+__global__ __launch_bounds__(kThreads) void dec_warp_stat_batch(const DecOutWarp *__restrict__ Os, DecWarpCall Wc,
+                                                                const DecCol *__restrict__ Ks)
+{
+    const DecCol &K = Ks[blockIdx.y];
+    if (K.contrast < 0) return;
+    const DecOutWarp A = Os[blockIdx.y];
+    col_accumulate(K, warp_body<float, kColStat>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind,
+                                                 A.o.bps, nullptr, col_stat_call(), Wc, &K));
 }
 
 DecWarpCall warp_call(const DecFmt &f)
@@ -1451,12 +1670,33 @@ int launch_dec_output_tensor_roi(const int32_t *syn, int h, int w, const DecWind
     });
 }
 
+// a per-frame tail's colour form needs the frame's op table (and a contrast op its accumulator)
+static int col_frame(const DecFmt &fmt, const DecCol *col)
+{
+    if (fmt.col && (!col || (col->contrast >= 0 && !col->acc)))
+        return ccmi_set_error(CCMI_ERR_ARG, "dec: colour without its op table");
+    return CCMI_OK;
+}
+
 int launch_dec_output_fmt(const int32_t *syn, int h, int w, const DecWindow &rect, int bitdepth, int kind,
-                          const DecFmt &fmt, void *dst, hipStream_t s)
+                          const DecFmt &fmt, void *dst, hipStream_t s, const DecCol *col)
 {
     if (int rc = check_region(rect, h, w, kind, true)) return rc;
+    if (int rc = col_frame(fmt, col)) return rc;
     const dim3 grid(output_fmt_blocks(rect.h(), rect.w()));
     const int maxv = (1 << bitdepth) - 1;
+    if (fmt.col) {
+        if (col->contrast >= 0) {
+            hipLaunchKernelGGL(dec_output_fmt_stat, grid, dim3(kThreads), 0, s, syn, h, w, rect.y0, rect.x0, rect.h(), rect.w(),
+                               maxv, kind, fmt_flags(fmt), *col);
+            CCMI_HIP_CHECK(hipGetLastError());
+        }
+        return with_elem_type(fmt.elem, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL(dec_output_fmt_col<T>, grid, dim3(kThreads), 0, s, syn, h, w, rect.y0, rect.x0, rect.h(),
+                               rect.w(), maxv, kind, fmt_flags(fmt), static_cast<T *>(dst), fmt_call(fmt), *col);
+        });
+    }
     return with_elem_type(fmt.elem, [&](auto t) {
         using T = decltype(t);
         hipLaunchKernelGGL(dec_output_fmt<T>, grid, dim3(kThreads), 0, s, syn, h, w, rect.y0, rect.x0, rect.h(), rect.w(),
@@ -1467,15 +1707,28 @@ int launch_dec_output_fmt(const int32_t *syn, int h, int w, const DecWindow &rec
 size_t dec_resample_tmp_elems(int region_h, int out_w) { return 3 * (size_t)region_h * out_w; }
 
 int launch_dec_resample(const int32_t *syn, int h, int w, const DecWindow &rect, int bitdepth, int kind,
-                        const DecFmt &fmt, float *tmp, void *dst, hipStream_t s)
+                        const DecFmt &fmt, float *tmp, void *dst, hipStream_t s, const DecCol *col)
 {
     if (int rc = check_region(rect, h, w, kind, true)) return rc;
     if (!fmt.rs || fmt.out_h < 1 || fmt.out_w < 1 || !tmp) return ccmi_set_error(CCMI_ERR_ARG, "dec: resample without a size");
+    if (int rc = col_frame(fmt, col)) return rc;
     const int maxv = (1 << bitdepth) - 1;
     hipLaunchKernelGGL(dec_resample_h, dim3(resample_h_blocks(rect.h(), fmt.out_w)), dim3(kThreads), 0, s, syn, h, w,
                        rect.y0, rect.x0, rect.h(), rect.w(), fmt.out_w, maxv, kind, fmt_flags(fmt), tmp);
     CCMI_HIP_CHECK(hipGetLastError());
     const dim3 grid(output_fmt_blocks(fmt.out_h, fmt.out_w));
+    if (fmt.col) {
+        if (col->contrast >= 0) {
+            hipLaunchKernelGGL(dec_resample_v_stat, grid, dim3(kThreads), 0, s, tmp, rect.h(), fmt.out_h, fmt.out_w,
+                               fmt_flags(fmt), *col);
+            CCMI_HIP_CHECK(hipGetLastError());
+        }
+        return with_elem_type(fmt.elem, [&](auto t) {
+            using T = decltype(t);
+            hipLaunchKernelGGL(dec_resample_v_col<T>, grid, dim3(kThreads), 0, s, tmp, rect.h(), fmt.out_h, fmt.out_w,
+                               fmt_flags(fmt), static_cast<T *>(dst), fmt_call(fmt), *col);
+        });
+    }
     return with_elem_type(fmt.elem, [&](auto t) {
         using T = decltype(t);
         hipLaunchKernelGGL(dec_resample_v<T>, grid, dim3(kThreads), 0, s, tmp, rect.h(), fmt.out_h, fmt.out_w,
@@ -1490,7 +1743,8 @@ static DecOutWarp make_out_warp(const DecOut &o, const DecFmt &fmt, int oy, int 
     return A;
 }
 
-int launch_dec_warp(const int32_t *syn, int h, int w, int bitdepth, int kind, const DecFmt &fmt, void *dst, hipStream_t s)
+int launch_dec_warp(const int32_t *syn, int h, int w, int bitdepth, int kind, const DecFmt &fmt, void *dst, hipStream_t s,
+                    const DecCol *col)
 {
     if (int rc = check_region(DecWindow{0, h, 0, w}, h, w, kind, true)) return rc;
     if (!fmt.warp || fmt.out_h < 1 || fmt.out_w < 1) return ccmi_set_error(CCMI_ERR_ARG, "dec: warp without a size");
@@ -1498,6 +1752,16 @@ int launch_dec_warp(const int32_t *syn, int h, int w, int bitdepth, int kind, co
     const DecOut o{syn, h, w, (1 << bitdepth) - 1, kind, fmt_flags(fmt), static_cast<uint8_t *>(dst)};
     const DecOutWarp A = make_out_warp(o, fmt, 0, 0, h, w);
     const dim3 grid(output_fmt_blocks(fmt.out_h, fmt.out_w));
+    if (int rc = col_frame(fmt, col)) return rc;
+    if (fmt.col) {
+        if (col->contrast >= 0) {
+            hipLaunchKernelGGL(dec_warp_stat, grid, dim3(kThreads), 0, s, A, warp_call(fmt), *col);
+            CCMI_HIP_CHECK(hipGetLastError());
+        }
+        return with_elem_type(fmt.elem, [&](auto t) {
+            hipLaunchKernelGGL(dec_warp_col<decltype(t)>, grid, dim3(kThreads), 0, s, A, fmt_call(fmt), warp_call(fmt), *col);
+        });
+    }
     return with_elem_type(fmt.elem, [&](auto t) {
         hipLaunchKernelGGL(dec_warp<decltype(t)>, grid, dim3(kThreads), 0, s, A, fmt_call(fmt), warp_call(fmt));
     });
@@ -1520,6 +1784,7 @@ bool dec_tail_same_group(const DecTailFrame &a, const DecTailFrame &b)
     if (a.fmt.on != b.fmt.on || a.fmt.elem != b.fmt.elem) return false;
     if (a.fmt.rs != b.fmt.rs || a.fmt.warp != b.fmt.warp || a.fmt.out_h != b.fmt.out_h || a.fmt.out_w != b.fmt.out_w)
         return false;
+    if (a.fmt.col != b.fmt.col) return false; // one per call too: the frames' ops are table data
     if (a.windowed) {
         // region decode: the tables carry each frame's true plane sizes and its windows, the
         // grids cover the group's largest window; one region size (the output grid), any
@@ -1542,10 +1807,11 @@ static size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
 // Byte layout of the argument table of a group of n frames: [step][frame] pyramid levels, then
 // [frame] synthesis arguments, then [frame] DecOut, each section 16-byte aligned.  A window-form
 // group holds DecLevelWin / DecSynFusedWin, the others DecLevel / DecSynFused; a resampling
-// group holds DecOutRs for DecOut, a warping group DecOutWarp (out_form: kOut*).
+// group holds DecOutRs for DecOut, a warping group DecOutWarp (out_form: kOut*); a group of a
+// call with colour ops ends with [frame] DecCol.
 struct TailTable {
-    size_t syn, out, bytes; // section offsets (the levels are at 0) and the total size
-    TailTable(int steps, int n, bool windowed, int out_form)
+    size_t syn, out, col, bytes; // section offsets (the levels are at 0) and the total size
+    TailTable(int steps, int n, bool windowed, int out_form, bool colour)
     {
         const size_t st = steps > 0 ? (size_t)steps : 0;
         syn = al16((windowed ? sizeof(DecLevelWin) : sizeof(DecLevel)) * st * n);
@@ -1553,10 +1819,14 @@ struct TailTable {
         const size_t entry = out_form == kOutRs     ? sizeof(DecOutRs)
                              : out_form == kOutWarp ? sizeof(DecOutWarp)
                                                     : sizeof(DecOut);
-        bytes = out + al16(entry * (size_t)n);
+        col = out + al16(entry * (size_t)n);
+        bytes = col + (colour ? al16(sizeof(DecCol) * (size_t)n) : 0);
     }
     // the group of `fr[0]`
-    TailTable(const DecTailFrame &f0, int n) : TailTable(f0.ups.n_layers - 1, n, f0.windowed, dec_out_form(f0.fmt)) {}
+    TailTable(const DecTailFrame &f0, int n)
+        : TailTable(f0.ups.n_layers - 1, n, f0.windowed, dec_out_form(f0.fmt), f0.fmt.col != 0)
+    {
+    }
     template <typename T> T *at(void *tab, size_t off) const { return reinterpret_cast<T *>(static_cast<uint8_t *>(tab) + off); }
     template <typename T> const T *at(const void *tab, size_t off) const
     {
@@ -1564,9 +1834,9 @@ struct TailTable {
     }
 };
 
-size_t dec_tail_table_bytes(int n_layers, int n, bool windowed, int out_form)
+size_t dec_tail_table_bytes(int n_layers, int n, bool windowed, int out_form, bool col)
 {
-    return TailTable(n_layers - 1, n, windowed, out_form).bytes;
+    return TailTable(n_layers - 1, n, windowed, out_form, col).bytes;
 }
 
 static DecOut make_out(const DecTailFrame &f, int h, int w)
@@ -1582,6 +1852,7 @@ static void put_out(const TailTable &T, void *host_tab, int i, const DecTailFram
         T.at<DecOutWarp>(host_tab, T.out)[i] = make_out_warp(make_out(f, h, w), f.fmt, oy, ox, f.syn.h, f.syn.w);
     else if (f.fmt.rs) T.at<DecOutRs>(host_tab, T.out)[i] = DecOutRs{make_out(f, h, w), f.rs_tmp};
     else T.at<DecOut>(host_tab, T.out)[i] = make_out(f, h, w);
+    if (f.fmt.col) T.at<DecCol>(host_tab, T.col)[i] = *f.col;
 }
 
 // the window-form tables
@@ -1627,8 +1898,38 @@ void dec_tail_fill(const DecTailFrame *const *fr, int n, void *host_tab)
 }
 
 // the tensor output of a group: h x w samples of one kind and sample type per frame
-static int launch_output_tensor_batch(const DecTailFrame &f0, int h, int w, int n, const DecOut *oo, hipStream_t s)
+static int launch_output_tensor_batch(const DecTailFrame &f0, int h, int w, int n, const DecOut *oo, hipStream_t s,
+                                      const DecCol *kk = nullptr, bool stat = false)
 {
+    if (f0.fmt.col) { // kk = the group's op tables; stat: a frame has a contrast op
+        const dim3 grid(output_fmt_blocks(f0.fmt.rs || f0.fmt.warp ? f0.fmt.out_h : h, f0.fmt.rs || f0.fmt.warp ? f0.fmt.out_w : w),
+                        n);
+        const DecFmtCall C = fmt_call(f0.fmt);
+        if (f0.fmt.rs) {
+            const DecOutRs *rr = reinterpret_cast<const DecOutRs *>(oo);
+            const int oh = f0.fmt.out_h, ow = f0.fmt.out_w;
+            hipLaunchKernelGGL(dec_resample_h_batch, dim3(resample_h_blocks(h, ow), n), dim3(kThreads), 0, s, rr, ow);
+            CCMI_HIP_CHECK(hipGetLastError());
+            if (stat) hipLaunchKernelGGL(dec_resample_v_stat_batch, grid, dim3(kThreads), 0, s, rr, oh, ow, kk);
+            CCMI_HIP_CHECK(hipGetLastError());
+            return with_elem_type(f0.fmt.elem, [&](auto t) {
+                hipLaunchKernelGGL(dec_resample_v_col_batch<decltype(t)>, grid, dim3(kThreads), 0, s, rr, oh, ow, C, kk);
+            });
+        }
+        if (f0.fmt.warp) {
+            const DecOutWarp *ww = reinterpret_cast<const DecOutWarp *>(oo);
+            if (stat) hipLaunchKernelGGL(dec_warp_stat_batch, grid, dim3(kThreads), 0, s, ww, warp_call(f0.fmt), kk);
+            CCMI_HIP_CHECK(hipGetLastError());
+            return with_elem_type(f0.fmt.elem, [&](auto t) {
+                hipLaunchKernelGGL(dec_warp_col_batch<decltype(t)>, grid, dim3(kThreads), 0, s, ww, C, warp_call(f0.fmt), kk);
+            });
+        }
+        if (stat) hipLaunchKernelGGL(dec_output_fmt_stat_batch, grid, dim3(kThreads), 0, s, oo, kk);
+        CCMI_HIP_CHECK(hipGetLastError());
+        return with_elem_type(f0.fmt.elem, [&](auto t) {
+            hipLaunchKernelGGL(dec_output_fmt_col_batch<decltype(t)>, grid, dim3(kThreads), 0, s, oo, C, kk);
+        });
+    }
     if (f0.fmt.rs) { // the section holds DecOutRs; h = the group's tallest region
         const DecOutRs *rr = reinterpret_cast<const DecOutRs *>(oo);
         const int oh = f0.fmt.out_h, ow = f0.fmt.out_w;
@@ -1656,6 +1957,14 @@ static int launch_output_tensor_batch(const DecTailFrame &f0, int h, int w, int 
     return with_sample_type(f0.sample, [&](auto t) {
         hipLaunchKernelGGL(dec_output_tensor_batch<decltype(t)>, grid, dim3(kThreads), 0, s, oo);
     });
+}
+
+// a frame of the group has a contrast op: the group runs its statistics pass
+static bool col_group_stat(const DecTailFrame *const *fr, int n)
+{
+    for (int i = 0; i < n; ++i)
+        if (fr[i]->fmt.col && fr[i]->col->contrast >= 0) return true;
+    return false;
 }
 
 // region decode: one launch per stage for a window-form group (dec_tail_same_group); the
@@ -1691,7 +2000,8 @@ static int launch_dec_tail_batch_win(const DecTailFrame *const *fr, int n, const
         hipLaunchKernelGGL((dec_syn_fused_win_batch<decltype(cin)::value, 3>), sg, dim3(kThreads), 0, s, sf, gtx);
     });
     CCMI_HIP_CHECK(hipGetLastError());
-    return launch_output_tensor_batch(f0, rh, rw, n, T.at<DecOut>(dev_tab, T.out), s);
+    return launch_output_tensor_batch(f0, rh, rw, n, T.at<DecOut>(dev_tab, T.out), s, T.at<DecCol>(dev_tab, T.col),
+                                      col_group_stat(fr, n));
 }
 
 int launch_dec_tail_batch(const DecTailFrame *const *fr, int n, const void *dev_tab, hipStream_t s)
@@ -1717,7 +2027,8 @@ int launch_dec_tail_batch(const DecTailFrame *const *fr, int n, const void *dev_
         hipLaunchKernelGGL((dec_syn_fused_batch<decltype(cin)::value, 3>), sg, dim3(kThreads), 0, s, sf);
     });
     CCMI_HIP_CHECK(hipGetLastError());
-    if (f0.sample >= 0) return launch_output_tensor_batch(f0, f0.syn.h, f0.syn.w, n, oo, s);
+    if (f0.sample >= 0)
+        return launch_output_tensor_batch(f0, f0.syn.h, f0.syn.w, n, oo, s, T.at<DecCol>(dev_tab, T.col), col_group_stat(fr, n));
     const int64_t plane = (int64_t)f0.syn.h * f0.syn.w;
     hipLaunchKernelGGL(dec_output_batch, dim3((unsigned)((plane + kThreads - 1) / kThreads), n), dim3(kThreads), 0, s, oo);
     CCMI_HIP_CHECK(hipGetLastError());

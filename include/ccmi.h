@@ -726,6 +726,85 @@ int ccmi_latents_render_warp(const ccmi_latents *h, const int *index /* [m] or N
                              const size_t *out_caps, const ccmi_tensor_fmt *fmt, const ccmi_warp *warp,
                              int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Coloured formatted output: the formatted sink with a per-frame list of photometric operations --
+ * brightness, saturation, contrast and a 3 x 4 colour matrix, the ColorJitter / RandomGrayscale half
+ * of the usual augmentation recipe -- applied in the decoder's output stage, after the geometry
+ * (step 3 of ccmi_tensor_fmt, step 3c of ccmi_resample, step 3d of ccmi_warp) and before step 4
+ * (scale / bias):
+ *   3z. x_0..x_2 = the three channels of output pixel (i, k) of frame j, at the output size.  Frame
+ *       j's ops, count[j] <= CCMI_COL_MAX_OPS of them, are applied in the frame's own order; every
+ *       product, sum and difference is one float32 operation in the order written (no fused
+ *       multiply-add), clamp is to [0, 1]:
+ *       CCMI_COL_BRIGHTNESS f (v[0], f >= 0):  x_c = clamp(f x_c);
+ *       CCMI_COL_SATURATION f (v[0], f >= 0):  g = ((0.2989f x_0) + (0.587f x_1)) + (0.114f x_2),
+ *           x_c = clamp((f x_c) + ((1 - f) g)); 1 - f is computed once on the host in float32;
+ *       CCMI_COL_CONTRAST f (v[0], f >= 0; at most one per frame):  x_c = clamp((f x_c) + ((1 - f) m_j)),
+ *           m_j the frame's mean grey in fixed point, which makes it independent of the order of
+ *           summation: S_j = the sum over all out_h out_w output pixels of frame j of
+ *           (uint64) rintf(clamp(g) 65535.0f), g the grey above of the pixel as it stands after the ops
+ *           that precede the contrast op; m_j = (float)((double)S_j / ((double)(out_h out_w) 65535.0)).
+ *           In a warp, pixels that come from `fill` count like any others.  The library sums integers
+ *           (one 64-bit atomic add per wave into a per-frame accumulator of the workspace, cleared in
+ *           stream), so a frame gives the same bits alone or in any batch, call after call;
+ *       CCMI_COL_MATRIX M (v[0..11], row-major 3 x 4):
+ *           x'_c = clamp((((M_c0 x_0) + (M_c1 x_1)) + (M_c2 x_2)) + M_c3), all three from the old x.
+ *           Hue as a rotation of the chroma plane of YIQ, greyscale, channel permutations, inversion.
+ *           It is NOT torchvision's HSV hue shift: a rotation in YIQ keeps luma and clips at the gamut.
+ * The ops act on the three channels whatever they are (CCMI_COLOUR_ASIS on a YUV stream included);
+ * the grey weights and the helpers' matrices are meant for RGB.  Steps 4-6 apply to the result.
+ * A frame without ops, and a call with colour NULL, give the bits of the call without colour.
+ *
+ * One superset pair per source: fmt, then rs OR warp OR neither (rs and warp both NULL: the _fmt
+ * call), then colour or NULL.  With a warp there is no roi (roi must be NULL) and `window` is filled
+ * as by the _warp plan; without one `window` must be NULL.  colour NULL, or every count 0: exactly
+ * the _rs / _warp call, plan and workspace included.  Otherwise the workspace grows by the op table
+ * (one entry per frame in the tail's argument tables) and the accumulators (8 bytes per frame, rounded
+ * to 256 for the call); frames with and without ops, in any orders, share the tail's launches
+ * (ccmi_decode_last_tail_groups is what the call without colour reports), and the frames that have a
+ * contrast op take part in one more pass per group, which evaluates the same pixels up to the
+ * contrast op and adds up S_j.
+ * Checked by the plan before any GPU work, CCMI_ERR_ARG naming the frame and nothing written: rs and
+ * warp both given, a roi with a warp, count or ops NULL, a count outside [0, CCMI_COL_MAX_OPS], an
+ * unknown op, two contrast ops in one frame, a negative or non-finite factor, a non-finite matrix
+ * entry; and everything the _rs / _warp plan checks.
+ * Measured (profiles/decode_colour_ab.txt): 960 class-E streams from an int16 store, RandomResizedCrop to
+ * 224 x 224, four ops per frame in random orders (every frame with a contrast op), bf16 RGB normalised:
+ * 50.2-51.7 ms per call (tail 45.2 ms) against 48.7-49.8 ms (tail 44.5 ms) for the call without ops and
+ * 57.7-59.4 ms for the float32 render followed by the same ops as torch operations; peak allocation above
+ * store and workspace 276 MiB against 1654 MiB. */
+enum { CCMI_COL_BRIGHTNESS = 0, CCMI_COL_SATURATION = 1, CCMI_COL_CONTRAST = 2, CCMI_COL_MATRIX = 3 };
+enum { CCMI_COL_MAX_OPS = 8 };
+typedef struct ccmi_colour_op {
+    int op;      /* CCMI_COL_* */
+    float v[12]; /* v[0] = the factor f; CCMI_COL_MATRIX: M, row-major 3 x 4 */
+} ccmi_colour_op;
+typedef struct ccmi_colour {
+    const int *count;          /* host, [n]: ops of frame j */
+    const ccmi_colour_op *ops; /* host, flat: frame j's ops follow frame j - 1's */
+} ccmi_colour;
+int ccmi_decode_batch_dev_col_plan(const uint8_t *const *streams, const size_t *lens, int n,
+                                   const ccmi_rect *roi /* [n] or NULL */, int out_bitdepth, int out_chroma,
+                                   const ccmi_tensor_fmt *fmt, const ccmi_resample *rs /* or NULL */,
+                                   const ccmi_warp *warp /* or NULL */, const ccmi_colour *colour /* or NULL */,
+                                   ccmi_frame_geom *geom /* [n] */, ccmi_roi_info *info /* [n] or NULL */,
+                                   ccmi_rect window[] /* [n] or NULL; warp only */, size_t *workspace_bytes);
+int ccmi_decode_batch_dev_col(const uint8_t *const *streams, const size_t *lens, int n,
+                              const ccmi_rect *roi /* [n] or NULL */, void *const *out_dev, const size_t *out_caps,
+                              const ccmi_tensor_fmt *fmt, const ccmi_resample *rs /* or NULL */,
+                              const ccmi_warp *warp /* or NULL */, const ccmi_colour *colour /* or NULL */,
+                              int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes, void *stream);
+int ccmi_latents_render_col_plan(const ccmi_latents *h, const int *index /* [m] or NULL */, int m,
+                                 const ccmi_rect *roi /* [m] or NULL */, int out_bitdepth, int out_chroma,
+                                 const ccmi_tensor_fmt *fmt, const ccmi_resample *rs /* or NULL */,
+                                 const ccmi_warp *warp /* or NULL */, const ccmi_colour *colour /* or NULL */,
+                                 ccmi_frame_geom *geom /* [m] */, ccmi_roi_info *info /* [m] or NULL */,
+                                 ccmi_rect window[] /* [m] or NULL; warp only */, size_t *workspace_bytes);
+int ccmi_latents_render_col(const ccmi_latents *h, const int *index /* [m] or NULL */, int m,
+                            const ccmi_rect *roi /* [m] or NULL */, void *const *out_dev, const size_t *out_caps,
+                            const ccmi_tensor_fmt *fmt, const ccmi_resample *rs /* or NULL */,
+                            const ccmi_warp *warp /* or NULL */, const ccmi_colour *colour /* or NULL */,
+                            int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Network weights of a stream's intra frame as the decoder's fixed-point integers
  * (cc-frame-decoder.cpp:201-353, read_arm / read_ups / read_syn):
  *   arm: per hidden layer W[d][d] (out, in) then b[d]; then W_out[2][d], b_out[2]

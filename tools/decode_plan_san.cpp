@@ -3,7 +3,8 @@
 // latent store's layout and plan-only handles (ccmi_latents_*, store = NULL) with their render
 // planning included, the formatted sinks (ccmi_tensor_fmt: element types, stride sets, a mirror
 // array of exactly n bytes, and the run entry point with capacities it must reject), the resampling
-// sinks (ccmi_resample: output sizes in and out of range, an unknown filter), the warping sinks
+// sinks (ccmi_resample: output sizes in and out of range, an unknown filter), the colouring sinks
+// (ccmi_colour: counts and ops in heap blocks of exactly their sizes, every plan error), the warping sinks
 // (ccmi_warp: sizes in and out of range, non-finite entries, the 2^22 bound, matrices that put the
 // output wholly outside the frame, singular matrices; the matrices sit in a heap block of exactly
 // 6 n floats and the windows in one of exactly n rects), over the streams named on the command line, whole, in batches of 7, over a list of regions, and
@@ -190,6 +191,57 @@ void plan_all(const std::vector<Stream> &b, const std::vector<ccmi_rect> &rects,
                                                   0, nullptr);
         if (rc == CCMI_OK) abort();
         count(rc);
+    }
+    {
+        // the colouring sink: the counts sit in a heap block of exactly n ints and the ops in one of
+        // exactly their sum, so a read past either is reported.  Frame i of a case takes the case's
+        // first (i % (len + 1)) ops; cases: every kind, 8 ops, 9 ops, an unknown op, two contrast ops,
+        // a negative and two non-finite factors, a non-finite matrix entry; each with a region, with
+        // a resample, with a warp, and with both (refused)
+        const float nan = 0.f / 0.f;
+        const ccmi_colour_op B{CCMI_COL_BRIGHTNESS, {1.25f}}, S{CCMI_COL_SATURATION, {0.5f}}, K{CCMI_COL_CONTRAST, {1.5f}},
+            M{CCMI_COL_MATRIX, {0, 0, 1, 0, 0, 1, 0, 0, 1, 0, 0, 0}}, U{7, {1.f}}, N{CCMI_COL_BRIGHTNESS, {-0.5f}},
+            I{CCMI_COL_SATURATION, {inf}}, Q{CCMI_COL_CONTRAST, {nan}}, X{CCMI_COL_MATRIX, {1, 0, 0, 0, 0, nan, 0, 0, 0, 0, 1, 0}};
+        const std::vector<std::vector<ccmi_colour_op>> cases = {
+            {B, S, K, M}, {M, M, M, M, K, S, B, B}, {B, B, B, B, B, B, B, B, B}, {B, U}, {K, B, K}, {S, N}, {I}, {M, Q}, {X}, {}};
+        const ccmi_resample rs{9, 5, CCMI_FILTER_TRIANGLE};
+        for (int i = 0; i < n; ++i) memcpy(mat + 6 * i, mats[3], sizeof mats[3]);
+        ccmi_warp wp{9, 5, CCMI_PAD_FILL, {0.1f, 0.2f, 0.3f}, mat};
+        for (const auto &cs : cases) {
+            int *cnt = static_cast<int *>(malloc(sizeof(int) * n));
+            size_t tot = 0;
+            for (int i = 0; i < n; ++i) tot += (size_t)(cnt[i] = (int)((size_t)i % (cs.size() + 1)));
+            if (n == 1) tot = (size_t)(cnt[0] = (int)cs.size());
+            ccmi_colour_op *ops = static_cast<ccmi_colour_op *>(malloc(tot ? sizeof(ccmi_colour_op) * tot : 1));
+            for (size_t k = 0, i = 0; (int)i < n; ++i)
+                for (int e = 0; e < cnt[i]; ++e) ops[k++] = cs[(size_t)e];
+            const ccmi_colour col{cnt, ops};
+            const ccmi_tensor_fmt &f = fmts[1];
+            count(ccmi_decode_batch_dev_col_plan(sp.data(), ln.data(), n, rects.data(), bd, chroma, &f, nullptr, nullptr, &col,
+                                                 geom.data(), info.data(), nullptr, &need));
+            count(ccmi_decode_batch_dev_col_plan(sp.data(), ln.data(), n, rects.data(), bd, chroma, &f, &rs, nullptr, &col,
+                                                 geom.data(), nullptr, nullptr, &need));
+            count(ccmi_decode_batch_dev_col_plan(sp.data(), ln.data(), n, nullptr, bd, chroma, &f, nullptr, &wp, &col, geom.data(),
+                                                 info.data(), win, &need));
+            int rc = ccmi_decode_batch_dev_col_plan(sp.data(), ln.data(), n, nullptr, bd, chroma, &f, &rs, &wp, &col, geom.data(),
+                                                    nullptr, nullptr, &need);
+            if (rc == CCMI_OK) abort();
+            count(rc);
+            // the run entry point with capacities one byte short: rejected before any GPU work
+            std::vector<void *> outs(n, reinterpret_cast<void *>(uintptr_t(1) << 40));
+            std::vector<size_t> caps(n, 3 * 9 * 5 * 4 - 1);
+            ccmi_tensor_fmt g = fmts[0];
+            g.colour = CCMI_COLOUR_RGB;
+            rc = ccmi_decode_batch_dev_col(sp.data(), ln.data(), n, rects.data(), outs.data(), caps.data(), &g, &rs, nullptr, &col,
+                                           bd, chroma, nullptr, 0, nullptr);
+            if (rc == CCMI_OK) abort();
+            count(rc);
+            free(ops);
+            free(cnt);
+        }
+        const ccmi_colour nocount{nullptr, nullptr};
+        count(ccmi_decode_batch_dev_col_plan(sp.data(), ln.data(), n, rects.data(), bd, chroma, &fmts[1], nullptr, nullptr, &nocount,
+                                             geom.data(), nullptr, nullptr, &need));
     }
     // the latent store: layout at every element type, a plan-only handle (no GPU call), and the
     // render planning over it: in order, through an index with repeats and out-of-range entries
