@@ -651,16 +651,7 @@ int launch_frame_tail(const Run &r, const FramePlan &p, hipStream_t cs)
                                           b == 1, cs))
                 return rc;
     }
-    if (t.fmt.warp) // the whole frame is decoded: the kernel samples it where the matrix points
-        return launch_dec_warp(synout, f.h, f.w, t.bitdepth, t.kind, t.fmt, t.dst, cs, t.col);
-    if (t.fmt.rs)
-        return launch_dec_resample(synout, f.h, f.w, t.roi.rect, t.bitdepth, t.kind, t.fmt, t.rs_tmp, t.dst, cs, t.col);
-    if (t.fmt.on) // roi.rect: the region, or the whole frame
-        return launch_dec_output_fmt(synout, f.h, f.w, t.roi.rect, t.bitdepth, t.kind, t.fmt, t.dst, cs, t.col);
-    if (p.mode == kTailCrop)
-        return launch_dec_output_tensor_roi(synout, f.h, f.w, t.roi.rect, t.bitdepth, t.kind, t.sample, t.dst, cs);
-    if (r.rq.device()) return launch_dec_output_tensor(synout, f.h, f.w, t.bitdepth, t.kind, t.sample, t.dst, cs);
-    return launch_dec_output(synout, f.h, f.w, t.bitdepth, t.kind, t.dst, cs);
+    return launch_dec_out_frame(t, synout, f.h, f.w, p.mode == kTailCrop, r.rq.device(), cs);
 }
 
 // one chunk's ARM launches, then its decoder tail (batched groups, then the rest per frame)

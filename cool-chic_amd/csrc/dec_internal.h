@@ -113,14 +113,6 @@ int launch_dec_syn(const DecSynArgs &a, hipStream_t s);
 int launch_dec_blend(int32_t *acc, const int32_t *x, int64_t n, int32_t b_acc, int32_t b_x, int first,
                      hipStream_t s);
 
-// Output conversion (ccdecapi.cpp:59-240): syn output (12-bit) -> file bytes.
-// kind: 0 yuv420, 1 yuv444, 2 ppm payload (interleaved RGB).  bps = 1 or 2 bytes/sample.
-int launch_dec_output(const int32_t *syn, int h, int w, int bitdepth, int kind, uint8_t *dst, hipStream_t s);
-// The same samples as a planar device tensor (ccmi_decode_batch_dev): kind 0 Y[H][W] U V
-// [H/2][W/2], kind 1 [3][H][W]; sample = CCMI_SAMPLE_*; dst needs one sample's alignment only.
-int launch_dec_output_tensor(const int32_t *syn, int h, int w, int bitdepth, int kind, int sample, void *dst,
-                             hipStream_t s);
-
 // A rectangle of one pyramid level, [y0, y1) x [x0, x1) in that level's coordinates.
 struct DecWindow {
     int y0, y1, x0, x1;
@@ -144,14 +136,10 @@ struct DecRoi {
 void dec_roi_plan(const int *lh, const int *lw, int L, int ups_ks, int pre_ks, int syn_halo, const DecWindow &rect,
                   DecRoi &r);
 size_t dec_ups_workspace_elems_win(const DecRoi &r, int L); // the stacks of levels 1..L-2, windows only
-// Whole-frame synthesis output (12-bit, [3][H][W]) -> the planar tensor of the region `rect`
-// (the per-frame tail of a region decode crops here).
-int launch_dec_output_tensor_roi(const int32_t *syn, int h, int w, const DecWindow &rect, int bitdepth, int kind,
-                                 int sample, void *dst, hipStream_t s);
 
 // Formatted tensor output (ccmi_tensor_fmt, validated and resolved by the plan): three full-size
 // channels per pixel, colour, affine, element type, strides and mirror applied by the output
-// kernel (dec_output_fmt<T>).  Everything but `matrix` and `mirror` is one value per call.
+// kernel (dec_output_fmt<T>, dec_out.hip).  Everything but `matrix` and `mirror` is one value per call.
 struct DecFmt {
     int on = 0;     // 0: the planar u8 / u16 / f32 tensor output
     int elem = 0;   // CCMI_ELEM_*
@@ -190,24 +178,11 @@ struct DecCol {
     DecColOp ops[CCMI_COL_MAX_OPS] = {};
 };
 
-// the form of a tail group's output section: DecOut, or its resample / warp extension
+// the form of a tail group's output section: the plain entry, or its resample / warp extension
 enum { kOutPlain = 0, kOutRs = 1, kOutWarp = 2 };
 inline int dec_out_form(const DecFmt &f) { return f.rs ? kOutRs : f.warp ? kOutWarp : kOutPlain; }
-// One frame: the region `rect` of the h x w synthesis output (12-bit, [3][h][w]) as the formatted
-// tensor at dst; kind 0 takes planes 1 and 2 at the even row and column (rect's origin even).
-// fmt.col (here and below): col is the frame's op table and the colour form of the kernel runs,
-// after the statistics pass when the frame has a contrast op (col->acc: cleared by the caller, in stream).
-int launch_dec_output_fmt(const int32_t *syn, int h, int w, const DecWindow &rect, int bitdepth, int kind,
-                          const DecFmt &fmt, void *dst, hipStream_t s, const DecCol *col = nullptr);
-// The same with fmt.rs: the region is resampled to fmt.out_h x fmt.out_w on the way.  tmp holds the
-// horizontal pass, dec_resample_tmp_elems() floats.
+// a resample's horizontal pass (DecTailFrame::rs_tmp), in floats
 size_t dec_resample_tmp_elems(int region_h, int out_w);
-int launch_dec_resample(const int32_t *syn, int h, int w, const DecWindow &rect, int bitdepth, int kind,
-                        const DecFmt &fmt, float *tmp, void *dst, hipStream_t s, const DecCol *col = nullptr);
-// The same with fmt.warp: the fmt.out_h x fmt.out_w frame at dst samples the whole h x w synthesis
-// output through fmt.m (kind 0: h and w even).
-int launch_dec_warp(const int32_t *syn, int h, int w, int bitdepth, int kind, const DecFmt &fmt, void *dst,
-                    hipStream_t s, const DecCol *col = nullptr);
 
 // Batched decoder tail: frames with the same geometry and a fused-synthesis architecture
 // (single branch) share one launch per pyramid step, one synthesis and one output launch
@@ -236,6 +211,27 @@ size_t dec_tail_table_bytes(int n_layers, int n, bool windowed = false, int out_
 void dec_tail_fill(const DecTailFrame *const *fr, int n, void *host_tab);
 // fr: the group's frames, in table order (a window-form group sizes its grids by their windows)
 int launch_dec_tail_batch(const DecTailFrame *const *fr, int n, const void *dev_tab, hipStream_t s);
+
+// The output stage (dec_out.hip), all the tail knows of it: synthesis output (12-bit, [3][h][w])
+// to file bytes (sample < 0; ccdecapi.cpp:59-240; kind 0 yuv420, 1 yuv444, 2 ppm payload), to the
+// planar tensor (kind 0 Y[H][W] U V [H/2][W/2], kind 1 [3][H][W]; dst needs one sample's
+// alignment only) or, with fmt.on, to the formatted tensor -- resampled (fmt.rs), warped
+// (fmt.warp) and through the frame's colour ops (fmt.col, after the statistics pass where a
+// frame has a contrast op; DecCol::acc is cleared by the caller, in stream) on the way.
+// A tail group's output section holds one entry per frame, of its out_form's size ...
+size_t dec_out_entry_bytes(int out_form);
+// ... and dec_out_fill writes entry i of it (host side), and of the colour section with fmt.col,
+// for the frame's h x w synthesis output that sits at (oy, ox) of its frame.
+void dec_out_fill(void *out_sec, void *col_sec, int i, const DecTailFrame &f, int h, int w, int oy, int ox);
+// The output stage of a group of n frames like f0, from the uploaded sections: h x w is the
+// synthesis output (a window-form group's: the largest region); stat: a frame has a contrast op.
+int launch_dec_out_group(const DecTailFrame &f0, int h, int w, int n, const void *out_sec, const DecCol *col_sec,
+                         bool stat, hipStream_t s);
+// The output stage of one frame (the per-frame tail) from its whole-frame h x w synthesis output.
+// Formatted: the region f.roi.rect (kind 0: an even origin), a warp the whole frame (kind 0: h and
+// w even).  Planar: crop takes f.roi.rect, else device the whole frame; neither: file bytes.
+int launch_dec_out_frame(const DecTailFrame &f, const int32_t *synout, int h, int w, bool crop, bool device,
+                         hipStream_t s);
 
 // Latent store (dec_latents.hip): the ARM output planes (int32, value << kArmPrec) packed to
 // values of the store's element type (CCMI_LATENT_*), and back.  Both kernels are table-driven:

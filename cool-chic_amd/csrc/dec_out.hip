@@ -1,0 +1,1110 @@
+// dec_out.hip -- path B: the output stage of the bit-exact fixed-point .cool decoder: the 12-bit
+// synthesis output of dec_tail.hip to file bytes, planar tensors or the formatted tensor, every
+// sink as a single-frame kernel (the per-frame tail) and a _batch kernel (a tail group).
+//
+//  dec_output       444 -> 420/444 8/10-bit or PPM payload (ccdecapi.cpp:59-240).
+//  dec_output_tensor  the same samples as planar u8 / u16 / f32 device tensors (no file
+//                   layout): one packed store per 4 destination samples, any sample alignment.
+//  dec_output_fmt   the same samples as the formatted tensor of a ccmi_tensor_fmt: three
+//                   full-size channels, YUV -> RGB, scale / bias, f32 / f16 / bf16, strides, mirror.
+//  dec_resample_h, dec_resample_v  the formatted tensor with a ccmi_resample: the region through an
+//                   antialiased triangle filter to the output size, horizontal then vertical pass.
+//  dec_warp         the formatted tensor with a ccmi_warp: every output pixel a bilinear sample of
+//                   the frame at the position the frame's 2 x 3 matrix gives, fill or edge padding.
+//  *_col, *_stat    the colour forms of the three formatted kernels (ccmi_colour) and their
+//                   statistics pass.
+//
+// The tail sees four functions (dec_internal.h): the size and the filling of an entry of a group's
+// output section, launch_dec_out_group and launch_dec_out_frame.  Both launchers choose the
+// geometry, hand its grid, its three kernel forms and their arguments to launch_fmt_forms, which
+// is the only place that knows the colour protocol and the element types.  A new formatted sink is
+// one more branch in each launcher; a new element type one more case of with_elem_type.
+#include <stdlib.h>
+
+#include "dec_device.h"
+#include "dec_internal.h"
+
+namespace ccmi {
+namespace {
+
+constexpr int kThreads = 256;
+
+// a 12-bit synthesis value as a sample in 0 .. maxv: the rounding and the clamp of ccdecapi.cpp
+__device__ __forceinline__ int32_t smp(int32_t v, int maxv)
+{
+    const int32_t s = (v * maxv + (1 << (kSynPrec - 1))) >> kSynPrec;
+    return s < 0 ? 0 : (s > maxv ? maxv : s);
+}
+
+// ------------------------------------------------------------------ output bytes
+struct DecOut {
+    const int32_t *syn;
+    int H, W, maxv, kind;
+    int bps_or_flags; // the byte output: bytes per sample; a formatted group: the frame's kFmt* flags; else unused
+    uint8_t *dst;
+};
+
+__device__ __forceinline__ void output_body(const int32_t *__restrict__ syn, int H, int W, int maxv, int kind, int bps,
+                                            uint8_t *__restrict__ dst);
+
+__global__ __launch_bounds__(kThreads) void dec_output_kernel(const int32_t *__restrict__ syn, int H, int W, int maxv,
+                                                              int kind, int bps, uint8_t *__restrict__ dst)
+{
+    output_body(syn, H, W, maxv, kind, bps, dst);
+}
+
+__global__ __launch_bounds__(kThreads) void dec_output_batch(const DecOut *__restrict__ Os)
+{
+    const DecOut O = Os[blockIdx.y];
+    output_body(O.syn, O.H, O.W, O.maxv, O.kind, O.bps_or_flags, O.dst);
+}
+
+__device__ __forceinline__ void output_body(const int32_t *__restrict__ syn, int H, int W, int maxv, int kind, int bps,
+                                            uint8_t *__restrict__ dst)
+{
+    const int64_t plane = (int64_t)H * W;
+    const int64_t p = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    if (p >= plane) return;
+    auto put = [&](int64_t idx, int32_t s, bool big_endian) {
+        if (bps == 1) dst[idx] = (uint8_t)s;
+        else if (big_endian) { dst[2 * idx] = (uint8_t)(s >> 8); dst[2 * idx + 1] = (uint8_t)s; }
+        else { dst[2 * idx] = (uint8_t)s; dst[2 * idx + 1] = (uint8_t)(s >> 8); }
+    };
+    const int y = (int)(p / W), x = (int)(p - (int64_t)y * W);
+    if (kind == 2) { // PPM: interleaved RGB, 16-bit big endian
+        for (int c = 0; c < 3; ++c) put(3 * p + c, smp(syn[c * plane + p], maxv), true);
+        return;
+    }
+    put(p, smp(syn[p], maxv), false);
+    if (kind == 1) {
+        put(plane + p, smp(syn[plane + p], maxv), false);
+        put(2 * plane + p, smp(syn[2 * plane + p], maxv), false);
+    } else if (!(y & 1) && !(x & 1) && (y >> 1) < H / 2 && (x >> 1) < W / 2) {
+        const int64_t cp = (int64_t)(H / 2) * (W / 2), ci = (int64_t)(y >> 1) * (W / 2) + (x >> 1);
+        put(plane + ci, smp(syn[plane + p], maxv), false);
+        put(plane + cp + ci, smp(syn[2 * plane + p], maxv), false);
+    }
+}
+
+// ------------------------------------------------------------------ output tensors
+// Device sink: the same samples as output_body (smp(), same 420 subsampling) in planar
+// tensor layout, never interleaved.  Both layouts are ONE flat array of samples:
+//   444: [3][H][W], sample j is smp(syn[j]);
+//   420: Y[H][W] then U, V [H/2][W/2], contiguous: j < HW as above, the rest a stride-2 gather.
+// A thread owns one naturally aligned group of 4 destination samples (one 32 / 64 / 128-bit
+// store for u8 / u16 / f32).  dst only has the alignment of one sample, so the groups are
+// laid out from the aligned address at or below dst: the first and the last group of a frame
+// are partial and take scalar stores, every other group one packed store -- the chroma
+// samples too, which the byte path writes one byte per thread.  DecOut::bps_or_flags is unused here
+// (the sample type is the template argument).
+template <typename T> struct OutVec;
+template <> struct OutVec<uint8_t> { using type = uint32_t; };
+template <> struct OutVec<uint16_t> { using type = uint2; };
+template <> struct OutVec<float> { using type = float4; };
+
+template <typename T> __device__ __forceinline__ T out_sample(int32_t s, float fmax);
+template <> __device__ __forceinline__ uint8_t out_sample<uint8_t>(int32_t s, float) { return (uint8_t)s; }
+template <> __device__ __forceinline__ uint16_t out_sample<uint16_t>(int32_t s, float) { return (uint16_t)s; }
+// one correctly rounded division: what torch's u.to(float32) / maxv computes
+template <> __device__ __forceinline__ float out_sample<float>(int32_t s, float fmax) { return __fdiv_rn((float)s, fmax); }
+
+// CROP (the per-frame tail of a region decode): H x W is the region, whose sample (y, x) of
+// plane c is syn[c * splane + (oy + y) * spitch + ox + x] of the whole-frame synthesis output
+// (oy, ox even for 420, so the chroma's even rows and columns are the frame's).
+template <typename T, bool CROP>
+__device__ __forceinline__ void output_tensor_body(const int32_t *__restrict__ syn, int H, int W, int maxv, int kind,
+                                                   T *__restrict__ dst, int64_t splane = 0, int spitch = 0, int oy = 0,
+                                                   int ox = 0)
+{
+    const int64_t plane = (int64_t)H * W;
+    auto direct_at = [&](int64_t j) { // flat sample j of the [.][H][W] prefix
+        if (!CROP) return j;
+        const int64_t c = j / plane, rem = j - c * plane;
+        const int y = (int)(rem / W), x = (int)(rem - (int64_t)y * W);
+        return c * splane + (int64_t)(oy + y) * spitch + ox + x;
+    };
+    const int ch = H / 2, cw = W / 2;
+    const int64_t cp = (int64_t)ch * cw;
+    const int64_t elems = kind == 1 ? 3 * plane : plane + 2 * cp;
+    const int64_t direct = kind == 1 ? elems : plane; // samples below this index read syn[j]
+    const int mis = (int)((reinterpret_cast<uintptr_t>(dst) / sizeof(T)) & 3); // samples past the aligned address
+    const int64_t j0 = ((int64_t)blockIdx.x * kThreads + threadIdx.x) * 4 - mis;
+    if (j0 >= elems) return;
+    const float fmax = (float)maxv;
+    T v[4];
+    if (j0 >= 0 && j0 + 4 <= direct) { // the common case: 4 samples of the flat prefix
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = out_sample<T>(smp(syn[direct_at(j0 + k)], maxv), fmax);
+    } else {
+        // a group that is partial, crosses into the chroma planes or lies in them: one
+        // division for its first chroma sample, the others step along the row
+        int64_t c = 0;
+        int cy = 0, cx = 0;
+        const int64_t jc = (j0 > direct ? j0 : direct) - direct; // first chroma index of the group
+        if (kind != 1 && cp > 0) {
+            c = jc / cp;
+            const int64_t ci = jc - c * cp;
+            cy = (int)(ci / cw);
+            cx = (int)(ci - (int64_t)cy * cw);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int64_t j = j0 + k;
+            v[k] = T(0);
+            if (j < 0 || j >= elems) continue;
+            if (j < direct) {
+                v[k] = out_sample<T>(smp(syn[direct_at(j)], maxv), fmax);
+                continue;
+            }
+            v[k] = out_sample<T>(smp(syn[CROP ? (1 + c) * splane + (int64_t)(oy + 2 * cy) * spitch + ox + 2 * cx
+                                              : (1 + c) * plane + (int64_t)(2 * cy) * W + 2 * cx],
+                                     maxv),
+                                 fmax);
+            if (++cx == cw) {
+                cx = 0;
+                if (++cy == ch) {
+                    cy = 0;
+                    ++c;
+                }
+            }
+        }
+    }
+    if (j0 >= 0 && j0 + 4 <= elems) {
+        typename OutVec<T>::type pk;
+        __builtin_memcpy(&pk, v, sizeof pk);
+        *reinterpret_cast<typename OutVec<T>::type *>(dst + j0) = pk;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (j0 + k >= 0 && j0 + k < elems) dst[j0 + k] = v[k];
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_output_tensor(const int32_t *__restrict__ syn, int H, int W, int maxv,
+                                                              int kind, T *__restrict__ dst)
+{
+    output_tensor_body<T, false>(syn, H, W, maxv, kind, dst);
+}
+
+// h x w = the region at (oy, ox) of the H x W frame
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_output_tensor_crop(const int32_t *__restrict__ syn, int H, int W, int oy,
+                                                                   int ox, int h, int w, int maxv, int kind,
+                                                                   T *__restrict__ dst)
+{
+    output_tensor_body<T, true>(syn, h, w, maxv, kind, dst, (int64_t)H * W, W, oy, ox);
+}
+
+template <typename T> __global__ __launch_bounds__(kThreads) void dec_output_tensor_batch(const DecOut *__restrict__ Os)
+{
+    const DecOut O = Os[blockIdx.y];
+    output_tensor_body<T, false>(O.syn, O.H, O.W, O.maxv, O.kind, reinterpret_cast<T *>(O.dst));
+}
+
+// blocks that cover the samples of one frame plus the up to 3 lead-in slots of an unaligned dst
+unsigned output_tensor_blocks(int h, int w, int kind)
+{
+    const int64_t plane = (int64_t)h * w;
+    const int64_t elems = kind == 1 ? 3 * plane : plane + 2 * (int64_t)(h / 2) * (w / 2);
+    const int64_t groups = (elems + 3 + 3) / 4;
+    return (unsigned)((groups + kThreads - 1) / kThreads);
+}
+
+// ------------------------------------------------------------------ formatted output tensors
+// Device sink with a ccmi_tensor_fmt (the contract is in ccmi.h): per region pixel the three
+// samples of output_tensor_body (420: planes 1 and 2 at the even row and column, the nearest x2
+// upsample), normalised, optionally through the YUV -> RGB matrix, scaled and biased, converted
+// to float / half / bfloat16 and stored at dst + c sc + y sy + x' sx.  A thread owns 4
+// consecutive destination pixels x' of one row with all three channels in registers; mirror
+// reads them from x = w - 1 - x'.  The groups of a row start at the naturally aligned address at
+// or below the row's channel-0 element (as output_tensor_body lays them out per frame), so with
+// sx == 1 (NCHW) a full group of an aligned channel is one packed store, and with sc == 1,
+// sx == 3 (NHWC) a full group's 12 elements are three; partial groups, channels whose rows are
+// not aligned alike, and every other stride set take one store per element.
+//
+// Every product and sum below is its own float32 operation: the library is built with the
+// compiler's default contraction, under which a * b + c may become one fused operation -- also
+// through __fmul_rn / __fadd_rn, which are plain inline operators in this toolchain's headers --
+// so the two helpers switch contraction off for their own instruction.
+__device__ __forceinline__ float fmt_mul(float a, float b)
+{
+#pragma clang fp contract(off)
+    return a * b;
+}
+__device__ __forceinline__ float fmt_add(float a, float b)
+{
+#pragma clang fp contract(off)
+    return a + b;
+}
+
+struct F16 {
+    _Float16 v;
+};
+struct Bf16 {
+    uint16_t bits;
+};
+template <typename T> struct FmtVec;
+template <> struct FmtVec<float> { using type = float4; };
+template <> struct FmtVec<F16> { using type = uint2; };
+template <> struct FmtVec<Bf16> { using type = uint2; };
+
+template <typename T> __device__ __forceinline__ T fmt_elem(float r);
+template <> __device__ __forceinline__ float fmt_elem<float>(float r) { return r; }
+template <> __device__ __forceinline__ F16 fmt_elem<F16>(float r) { return F16{(_Float16)r}; } // v_cvt_f16_f32, RNE
+template <> __device__ __forceinline__ Bf16 fmt_elem<Bf16>(float r)
+{
+    uint32_t u = __float_as_uint(r);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return Bf16{0x7fc0}; // NaN (a finite scale and bias make none)
+    u += 0x7fffu + ((u >> 16) & 1u); // round to nearest even
+    return Bf16{(uint16_t)(u >> 16)};
+}
+
+// the float32 roundings of yuv2rgb's matrix (ccmi/io.py) and of its offsets / 255: R, G, B
+__device__ constexpr float kFmtA[3] = {(float)-0.000007154783816076815, (float)-0.3441331386566162, (float)1.7720025777816772};
+__device__ constexpr float kFmtB[3] = {(float)1.4019975662231445, (float)-0.7141380310058594, (float)0.00001542569043522235};
+__device__ constexpr float kFmtO[3] = {(float)(-179.45477266423404 / 255.0), (float)(135.45870971679688 / 255.0),
+                                       (float)(-226.8183044444304 / 255.0)};
+
+struct DecFmtCall { // one value per launch
+    float scale[3], bias[3];
+    int64_t sc, sy, sx;
+};
+enum { kFmtMirror = 1, kFmtMatrix = 2 }; // per-frame flags (DecOut::bps_or_flags of a formatted group)
+
+// groups of 4 destination pixels that cover one row plus the up to 3 lead-in slots
+__host__ __device__ inline int fmt_row_groups(int w) { return (w + 3 + 3) / 4; }
+
+// steps 1-3 of the contract for one pixel: lrow / crow point at the pixel's luma row and at the
+// row its chroma is taken from, x / xc are its luma and chroma columns
+__device__ __forceinline__ void fmt_pixel(const int32_t *__restrict__ lrow, const int32_t *__restrict__ crow,
+                                          int64_t splane, int x, int xc, int maxv, float fmax, bool matrix, float (&q)[3])
+{
+    auto unit = [maxv, fmax](int32_t v) { return __fdiv_rn((float)smp(v, maxv), fmax); };
+    const float p0 = unit(lrow[x]), p1 = unit(crow[splane + xc]), p2 = unit(crow[2 * splane + xc]);
+    q[0] = p0, q[1] = p1, q[2] = p2;
+    if (matrix) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float t = fmt_add(fmt_add(fmt_add(p0, fmt_mul(kFmtA[c], p1)), fmt_mul(kFmtB[c], p2)), kFmtO[c]);
+            q[c] = fminf(fmaxf(t, 0.f), 1.f);
+        }
+    }
+}
+
+// ---- the colour stage (step 3z of the contract in ccmi.h, ccmi_colour)
+// The three output bodies below take a mode: kColNone is the body as it always was (the kernels
+// without colour instantiate it, and nothing of the stage is compiled into them); kColWrite puts
+// the pixel through its frame's ops between the geometry and scale / bias; kColStat is the
+// statistics pass of the frames with a contrast op: the same pixels through the ops that precede
+// the contrast op, their integer grey terms summed per thread, per wave and, by one 64-bit atomic
+// add per wave, per frame.  Nothing is stored in that mode and no thread leaves before the wave's
+// reduction.  The pass evaluates the geometry a second time and stages nothing: what it would stage
+// is three float32 per output pixel written and read again, more traffic than the taps it re-reads
+// from a synthesis output that the stage before has just left in the cache.
+// The op table is one DecCol per frame in the tail's argument tables, or the kernel's own argument
+// (the per-frame tail): uniform per block, so the loop over the ops branches on scalars.
+enum { kColNone = 0, kColWrite = 1, kColStat = 2 };
+
+__device__ __forceinline__ float col_clamp(float t) { return fminf(fmaxf(t, 0.f), 1.f); }
+
+__device__ __forceinline__ float col_grey(const float (&x)[3])
+{
+    return fmt_add(fmt_add(fmt_mul(0.2989f, x[0]), fmt_mul(0.587f, x[1])), fmt_mul(0.114f, x[2]));
+}
+
+// ops [first, last) of the frame on one pixel; mean = m_j (read by a contrast op only)
+__device__ __forceinline__ void col_ops(const DecCol &K, int first, int last, float mean, float (&x)[3])
+{
+    for (int i = first; i < last; ++i) {
+        const DecColOp &P = K.ops[i];
+        if (P.op == CCMI_COL_MATRIX) {
+            float y[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                y[c] = col_clamp(fmt_add(
+                    fmt_add(fmt_add(fmt_mul(P.v[4 * c], x[0]), fmt_mul(P.v[4 * c + 1], x[1])), fmt_mul(P.v[4 * c + 2], x[2])),
+                    P.v[4 * c + 3]));
+#pragma unroll
+            for (int c = 0; c < 3; ++c) x[c] = y[c];
+        } else if (P.op == CCMI_COL_BRIGHTNESS) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) x[c] = col_clamp(fmt_mul(P.v[0], x[c]));
+        } else { // towards the pixel's grey (saturation) or the frame's mean grey (contrast)
+            const float b = fmt_mul(P.v[1], P.op == CCMI_COL_SATURATION ? col_grey(x) : mean);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) x[c] = col_clamp(fmt_add(fmt_mul(P.v[0], x[c]), b));
+        }
+    }
+}
+
+// kColWrite: m_j of a frame of npix output pixels from the sum the statistics pass left
+__device__ __forceinline__ float col_mean(const DecCol &K, int npix)
+{
+    if (K.contrast < 0) return 0.f;
+    const float m = (float)((double)*K.acc / ((double)npix * 65535.0));
+    return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(m))); // one value per block: kept in a scalar
+}
+
+// kColStat: one pixel's term of S_j, at most 65535
+__device__ __forceinline__ uint32_t col_term(const DecCol &K, float (&x)[3])
+{
+    col_ops(K, 0, K.contrast, 0.f, x);
+    return (uint32_t)rintf(fmt_mul(col_clamp(col_grey(x)), 65535.0f));
+}
+
+// kColStat: the thread's sum (4 pixels) -> the wave's (at most 2^24) -> the frame's; every lane of
+// the wave arrives here.  Integer additions: the order of the waves does not show in the sum.
+__device__ __forceinline__ void col_accumulate(const DecCol &K, uint32_t sum)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o);
+    if ((threadIdx.x & 63) == 0 && sum) atomicAdd(K.acc, (unsigned long long)sum);
+}
+
+// the format of a statistics pass: its groups of 4 pixels start at pixel 0 of every row
+__device__ __forceinline__ DecFmtCall col_stat_call()
+{
+    DecFmtCall C{};
+    return C;
+}
+
+// step 6 for a thread's 4 destination pixels d0 .. d0 + 3 of the row at `row` elements (w pixels
+// wide): the packed stores where the layout and the alignment allow them
+template <typename T>
+__device__ __forceinline__ void fmt_store(const T (&v)[3][4], T *__restrict__ dst, const DecFmtCall &C, int64_t row,
+                                          int d0, int w, bool nchw, bool nhwc)
+{
+    using Vec = typename FmtVec<T>::type;
+    const bool full = d0 >= 0 && d0 + 4 <= w;
+    if (nchw) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            T *p = dst + c * C.sc + row + d0;
+            if (full && reinterpret_cast<uintptr_t>(p) % sizeof(Vec) == 0) {
+                Vec pk;
+                __builtin_memcpy(&pk, v[c], sizeof pk);
+                *reinterpret_cast<Vec *>(p) = pk;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (d0 + k >= 0 && d0 + k < w) p[k] = v[c][k];
+            }
+        }
+    } else if (nhwc && full) { // aligned by the choice of mis
+        T e[12];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) e[3 * k + c] = v[c][k];
+        Vec *p = reinterpret_cast<Vec *>(dst + row + 3 * (int64_t)d0);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            Vec pk;
+            __builtin_memcpy(&pk, e + 4 * j, sizeof pk);
+            p[j] = pk;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (d0 + k < 0 || d0 + k >= w) continue;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) dst[c * C.sc + row + (d0 + k) * C.sx] = v[c][k];
+        }
+    }
+}
+
+// the thread's row y and first destination pixel d0 of a w-wide row (see above); false: no work
+template <typename T>
+__device__ __forceinline__ bool fmt_group(const T *dst, const DecFmtCall &C, int h, int w, int &y, int &d0, int64_t &row,
+                                          bool &nchw, bool &nhwc)
+{
+    const int gpr = fmt_row_groups(w);
+    const int64_t g = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    y = (int)(g / gpr);
+    if (y >= h) return false;
+    nchw = C.sx == 1, nhwc = !nchw && C.sc == 1 && C.sx == 3;
+    row = (int64_t)y * C.sy;
+    // elements from address 0 to (channel 0, y, x' = 0); group k starts mis slots before it, where
+    // the address of its first pixel is a multiple of 4 elements (NHWC: 3 mis == a0 mod 4)
+    const uint64_t a0 = (uint64_t)(reinterpret_cast<uintptr_t>(dst) / sizeof(T)) + (uint64_t)row;
+    const int mis = nchw ? (int)(a0 & 3) : nhwc ? (int)((3 * a0) & 3) : 0;
+    d0 = 4 * (int)(g - (int64_t)y * gpr) - mis;
+    return d0 < w;
+}
+
+// h x w = the region at (oy, ox) of the synthesis output syn (planes splane apart, pitch spitch;
+// oy, ox even for kind 0)
+template <typename T, int COL = kColNone>
+__device__ __forceinline__ uint32_t output_fmt_body(const int32_t *__restrict__ syn, int64_t splane, int spitch, int oy,
+                                                    int ox, int h, int w, int maxv, int kind, int flags,
+                                                    T *__restrict__ dst, const DecFmtCall &C, const DecCol *K = nullptr)
+{
+    int y, d0;
+    int64_t row;
+    bool nchw, nhwc;
+    if (!fmt_group<T>(dst, C, h, w, y, d0, row, nchw, nhwc)) return 0;
+    float mean = 0.f;
+    uint32_t sum = 0;
+    if constexpr (COL == kColWrite) mean = col_mean(*K, h * w);
+    const float fmax = (float)maxv;
+    const bool mirror = flags & kFmtMirror, matrix = flags & kFmtMatrix;
+    const int32_t *__restrict__ lrow = syn + (int64_t)(oy + y) * spitch + ox;
+    const int32_t *__restrict__ crow = syn + (int64_t)(oy + (kind == 1 ? y : y & ~1)) * spitch + ox;
+    T v[3][4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int d = d0 + k;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c][k] = fmt_elem<T>(0.f);
+        if (d < 0 || d >= w) continue;
+        const int x = mirror ? w - 1 - d : d;
+        float q[3];
+        fmt_pixel(lrow, crow, splane, x, kind == 1 ? x : x & ~1, maxv, fmax, matrix, q);
+        if constexpr (COL == kColStat) {
+            sum += col_term(*K, q);
+            continue;
+        }
+        if constexpr (COL == kColWrite) col_ops(*K, 0, K->n, mean, q);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c][k] = fmt_elem<T>(fmt_add(fmt_mul(q[c], C.scale[c]), C.bias[c]));
+    }
+    if constexpr (COL != kColStat) fmt_store<T>(v, dst, C, row, d0, w, nchw, nhwc);
+    return sum;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_output_fmt(const int32_t *__restrict__ syn, int H, int W, int oy, int ox,
+                                                           int h, int w, int maxv, int kind, int flags,
+                                                           T *__restrict__ dst, DecFmtCall C)
+{
+    output_fmt_body<T>(syn, (int64_t)H * W, W, oy, ox, h, w, maxv, kind, flags, dst, C);
+}
+
+// the colour forms (ccmi_colour): K = the frame's ops; the statistics pass of a frame with a contrast op
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_output_fmt_col(const int32_t *__restrict__ syn, int H, int W, int oy, int ox,
+                                                               int h, int w, int maxv, int kind, int flags,
+                                                               T *__restrict__ dst, DecFmtCall C, DecCol K)
+{
+    output_fmt_body<T, kColWrite>(syn, (int64_t)H * W, W, oy, ox, h, w, maxv, kind, flags, dst, C, &K);
+}
+
+__global__ __launch_bounds__(kThreads) void dec_output_fmt_stat(const int32_t *__restrict__ syn, int H, int W, int oy, int ox,
+                                                                int h, int w, int maxv, int kind, int flags, DecCol K)
+{
+    col_accumulate(K, output_fmt_body<float, kColStat>(syn, (int64_t)H * W, W, oy, ox, h, w, maxv, kind, flags, nullptr,
+                                                       col_stat_call(), &K));
+}
+
+// a tail group: frame blockIdx.y's compact H x W synthesis output (DecOut::bps_or_flags = its kFmt* flags)
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_output_fmt_batch(const DecOut *__restrict__ Os, DecFmtCall C)
+{
+    const DecOut O = Os[blockIdx.y];
+    output_fmt_body<T>(O.syn, (int64_t)O.H * O.W, O.W, 0, 0, O.H, O.W, O.maxv, O.kind, O.bps_or_flags, reinterpret_cast<T *>(O.dst),
+                       C);
+}
+
+// the colour forms of a tail group: Ks = the group's op tables, one per frame
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_output_fmt_col_batch(const DecOut *__restrict__ Os, DecFmtCall C,
+                                                                     const DecCol *__restrict__ Ks)
+{
+    const DecOut O = Os[blockIdx.y];
+    output_fmt_body<T, kColWrite>(O.syn, (int64_t)O.H * O.W, O.W, 0, 0, O.H, O.W, O.maxv, O.kind, O.bps_or_flags,
+                                  reinterpret_cast<T *>(O.dst), C, Ks + blockIdx.y);
+}
+
+// only the frames with a contrast op take part
+__global__ __launch_bounds__(kThreads) void dec_output_fmt_stat_batch(const DecOut *__restrict__ Os,
+                                                                      const DecCol *__restrict__ Ks)
+{
+    const DecCol &K = Ks[blockIdx.y];
+    if (K.contrast < 0) return;
+    const DecOut O = Os[blockIdx.y];
+    col_accumulate(K, output_fmt_body<float, kColStat>(O.syn, (int64_t)O.H * O.W, O.W, 0, 0, O.H, O.W, O.maxv, O.kind, O.bps_or_flags,
+                                                       nullptr, col_stat_call(), &K));
+}
+
+unsigned output_fmt_blocks(int h, int w)
+{
+    return (unsigned)(((int64_t)h * fmt_row_groups(w) + kThreads - 1) / kThreads);
+}
+
+DecFmtCall fmt_call(const DecFmt &f)
+{
+    DecFmtCall C;
+    for (int c = 0; c < 3; ++c) C.scale[c] = f.scale[c], C.bias[c] = f.bias[c];
+    C.sc = f.stride_c, C.sy = f.stride_y, C.sx = f.stride_x;
+    return C;
+}
+
+int fmt_flags(const DecFmt &f) { return (f.mirror ? kFmtMirror : 0) | (f.matrix ? kFmtMatrix : 0); }
+
+// ------------------------------------------------------------------ resampled formatted output
+// The formatted sink with a ccmi_resample (steps 3a-3c of the contract in ccmi.h): the region,
+// h x w, goes through an antialiased triangle filter to oh x ow between the colour step and
+// scale / bias.  Two launches:
+//   dec_resample_h     thread = (region row y, output column i), three channels: q per tap from
+//                      the synthesis output, t[c][y][i] (float32, [3][h][ow]) to the workspace;
+//   dec_resample_v<T>  thread = (output row, 4 destination pixels), as the formatted output stage:
+//                      the vertical pass over t (loads coalesced along the row), then scale / bias,
+//                      element conversion and the stores of fmt_store.  mirror reads column
+//                      ow - 1 - x'.
+
+// The weights are recomputed per thread from integers: RsTaps holds the run j0 .. j1 of output
+// index i and what u(i, j) = 2D - |(2j + 1) O - (2i + 1) I| needs; everything fits int32 for
+// I, O <= 16384 (the plan's bound).
+struct RsTaps {
+    int j0, j1, c, O, D2;
+    float fU;
+    __device__ __forceinline__ int u(int j) const { return D2 - abs((2 * j + 1) * O - c); }
+    __device__ __forceinline__ float w(int j) const { return __fdiv_rn((float)u(j), fU); }
+};
+
+__device__ __forceinline__ RsTaps rs_taps(int i, int I, int O)
+{
+    RsTaps t;
+    t.O = O;
+    t.D2 = 2 * max(I, O);
+    t.c = (2 * i + 1) * I;
+    // u > 0: (c - 2D - O) / 2O < j < (c + 2D - O) / 2O, clipped to the region
+    const int a = t.c - t.D2 - O, b = t.c + t.D2 - O; // b >= 1
+    t.j0 = a >= 0 ? a / (2 * O) + 1 : 0;
+    t.j1 = min((b - 1) / (2 * O), I - 1);
+    int U = 0;
+    for (int j = t.j0; j <= t.j1; ++j) U += t.u(j);
+    t.fU = (float)U;
+    return t;
+}
+
+// one frame of a resampling group: DecOut as for dec_output_fmt_batch (H x W = the region, compact)
+struct DecOutRs {
+    DecOut o;
+    float *tmp;
+};
+
+// h x w = the region at (oy, ox) of the synthesis output, as for output_fmt_body
+__device__ __forceinline__ void resample_h_body(const int32_t *__restrict__ syn, int64_t splane, int spitch, int oy, int ox,
+                                                int h, int w, int ow, int maxv, int kind, int flags,
+                                                float *__restrict__ tmp)
+{
+    const int64_t g = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+    const int y = (int)(g / ow);
+    if (y >= h) return;
+    const int i = (int)(g - (int64_t)y * ow);
+    const RsTaps T = rs_taps(i, w, ow);
+    const float fmax = (float)maxv;
+    const bool matrix = flags & kFmtMatrix;
+    const int32_t *__restrict__ lrow = syn + (int64_t)(oy + y) * spitch + ox;
+    const int32_t *__restrict__ crow = syn + (int64_t)(oy + (kind == 1 ? y : y & ~1)) * spitch + ox;
+    float acc[3] = {0.f, 0.f, 0.f};
+    for (int j = T.j0; j <= T.j1; ++j) {
+        const float wj = T.w(j);
+        float q[3];
+        fmt_pixel(lrow, crow, splane, j, kind == 1 ? j : j & ~1, maxv, fmax, matrix, q);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[c] = fmt_add(acc[c], fmt_mul(wj, q[c]));
+    }
+    const int64_t tplane = (int64_t)h * ow;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) tmp[c * tplane + g] = acc[c];
+}
+
+// tmp = [3][h][ow] of resample_h_body; the frame at dst is oh x ow
+template <typename T, int COL = kColNone>
+__device__ __forceinline__ uint32_t resample_v_body(const float *__restrict__ tmp, int h, int oh, int ow, int flags,
+                                                    T *__restrict__ dst, const DecFmtCall &C, const DecCol *K = nullptr)
+{
+    int y, d0;
+    int64_t row;
+    bool nchw, nhwc;
+    if (!fmt_group<T>(dst, C, oh, ow, y, d0, row, nchw, nhwc)) return 0;
+    const RsTaps R = rs_taps(y, h, oh);
+    const bool mirror = flags & kFmtMirror;
+    // element indices of tmp fit 32 bits (3 h ow <= 3 * 2^28): one base and 32-bit offsets
+    const unsigned tplane = (unsigned)h * (unsigned)ow;
+    unsigned x[4];
+    float acc[3][4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int d = min(max(d0 + k, 0), ow - 1); // the surplus slots of a partial group are never stored
+        x[k] = (unsigned)(mirror ? ow - 1 - d : d);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) acc[c][k] = 0.f;
+    }
+    for (int j = R.j0; j <= R.j1; ++j) {
+        const float wj = R.w(j);
+        const unsigned r0 = (unsigned)j * (unsigned)ow;
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc[c][k] = fmt_add(acc[c][k], fmt_mul(wj, tmp[c * tplane + r0 + x[k]]));
+    }
+    if constexpr (COL != kColNone) {
+        const float mean = COL == kColWrite ? col_mean(*K, oh * ow) : 0.f;
+        uint32_t sum = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float q[3] = {acc[0][k], acc[1][k], acc[2][k]};
+            if constexpr (COL == kColStat) {
+                if (d0 + k >= 0 && d0 + k < ow) sum += col_term(*K, q); // a surplus slot repeats a pixel
+            } else {
+                col_ops(*K, 0, K->n, mean, q);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) acc[c][k] = q[c];
+            }
+        }
+        if constexpr (COL == kColStat) return sum;
+    }
+    T v[3][4];
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[c][k] = fmt_elem<T>(fmt_add(fmt_mul(acc[c][k], C.scale[c]), C.bias[c]));
+    fmt_store<T>(v, dst, C, row, d0, ow, nchw, nhwc);
+    return 0;
+}
+
+__global__ __launch_bounds__(kThreads) void dec_resample_h(const int32_t *__restrict__ syn, int H, int W, int oy, int ox,
+                                                           int h, int w, int ow, int maxv, int kind, int flags,
+                                                           float *__restrict__ tmp)
+{
+    resample_h_body(syn, (int64_t)H * W, W, oy, ox, h, w, ow, maxv, kind, flags, tmp);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_resample_v(const float *__restrict__ tmp, int h, int oh, int ow, int flags,
+                                                           T *__restrict__ dst, DecFmtCall C)
+{
+    resample_v_body<T>(tmp, h, oh, ow, flags, dst, C);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_resample_v_col(const float *__restrict__ tmp, int h, int oh, int ow,
+                                                               int flags, T *__restrict__ dst, DecFmtCall C, DecCol K)
+{
+    resample_v_body<T, kColWrite>(tmp, h, oh, ow, flags, dst, C, &K);
+}
+
+__global__ __launch_bounds__(kThreads) void dec_resample_v_stat(const float *__restrict__ tmp, int h, int oh, int ow,
+                                                                int flags, DecCol K)
+{
+    col_accumulate(K, resample_v_body<float, kColStat>(tmp, h, oh, ow, flags, nullptr, col_stat_call(), &K));
+}
+
+// a tail group: frame blockIdx.y's compact region; the grid covers the group's largest region
+__global__ __launch_bounds__(kThreads) void dec_resample_h_batch(const DecOutRs *__restrict__ Os, int ow)
+{
+    const DecOutRs R = Os[blockIdx.y];
+    const DecOut &O = R.o;
+    resample_h_body(O.syn, (int64_t)O.H * O.W, O.W, 0, 0, O.H, O.W, ow, O.maxv, O.kind, O.bps_or_flags, R.tmp);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_resample_v_batch(const DecOutRs *__restrict__ Os, int oh, int ow,
+                                                                 DecFmtCall C)
+{
+    const DecOutRs R = Os[blockIdx.y];
+    resample_v_body<T>(R.tmp, R.o.H, oh, ow, R.o.bps_or_flags, reinterpret_cast<T *>(R.o.dst), C);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_resample_v_col_batch(const DecOutRs *__restrict__ Os, int oh, int ow,
+                                                                     DecFmtCall C, const DecCol *__restrict__ Ks)
+{
+    const DecOutRs R = Os[blockIdx.y];
+    resample_v_body<T, kColWrite>(R.tmp, R.o.H, oh, ow, R.o.bps_or_flags, reinterpret_cast<T *>(R.o.dst), C, Ks + blockIdx.y);
+}
+
+__global__ __launch_bounds__(kThreads) void dec_resample_v_stat_batch(const DecOutRs *__restrict__ Os, int oh, int ow,
+                                                                      const DecCol *__restrict__ Ks)
+{
+    const DecCol &K = Ks[blockIdx.y];
+    if (K.contrast < 0) return;
+    const DecOutRs R = Os[blockIdx.y];
+    col_accumulate(K, resample_v_body<float, kColStat>(R.tmp, R.o.H, oh, ow, R.o.bps_or_flags, nullptr, col_stat_call(), &K));
+}
+
+unsigned resample_h_blocks(int h, int ow) { return (unsigned)(((int64_t)h * ow + kThreads - 1) / kThreads); }
+
+// ------------------------------------------------------------------ warped formatted output
+// The formatted sink with a ccmi_warp (steps 3a-3d of its contract in ccmi.h): every pixel of the
+// oh x ow frame at dst is a bilinear sample of q over the WHOLE frame, fh x fw, at the position
+// the frame's 2 x 3 matrix gives, between the colour step and scale / bias.  One launch, a thread
+// = (output row, 4 destination pixels) as in the formatted output stage; the pixels go one at a
+// time, so 12 tap values are live and not 48.  Each pixel gathers 4 taps x 3 channels through
+// fmt_pixel (the colour step per tap).
+// The synthesis output holds the window the plan derived from the matrix, h x w at (oy, ox) of
+// the frame, compact (the per-frame tail: the whole frame at 0, 0).  A tap is tested and clamped
+// against the FRAME, as the contract has it, then addressed relative to the window and clamped to
+// it as well: the window holds every in-frame tap, so that clamp changes nothing unless the plan
+// is wrong, and then it shows as a wrong value and never as a read outside the workspace.
+struct DecWarpCall { // one value per launch
+    int oh, ow, pad;
+    float fill[3];
+};
+
+// one frame of a warping group: DecOut as for dec_output_fmt_batch (H x W = the window, compact)
+struct DecOutWarp {
+    DecOut o;
+    float m[6];
+    int oy, ox, fh, fw; // the window's origin in the frame, and the frame
+};
+
+template <typename T, int COL = kColNone>
+__device__ __forceinline__ uint32_t warp_body(const int32_t *__restrict__ syn, int h, int w, int oy, int ox, int fh, int fw,
+                                              const float (&m)[6], int maxv, int kind, int flags, T *__restrict__ dst,
+                                              const DecFmtCall &C, const DecWarpCall &Wc, const DecCol *K = nullptr)
+{
+    int y, d0;
+    int64_t row;
+    bool nchw, nhwc;
+    if (!fmt_group<T>(dst, C, Wc.oh, Wc.ow, y, d0, row, nchw, nhwc)) return 0;
+    float mean = 0.f;
+    uint32_t sum = 0;
+    if constexpr (COL == kColWrite) mean = col_mean(*K, Wc.oh * Wc.ow);
+    const float fmax = (float)maxv;
+    const bool mirror = flags & kFmtMirror, matrix = flags & kFmtMatrix;
+    const int64_t splane = (int64_t)h * w;
+    const float cy = (float)y + 0.5f;
+    const float xr = fmt_mul(m[1], cy), yr = fmt_mul(m[4], cy); // the row's share of the position
+    T v[3][4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int d = d0 + k;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c][k] = fmt_elem<T>(0.f);
+        if (d < 0 || d >= Wc.ow) continue;
+        const float cx = (float)(mirror ? Wc.ow - 1 - d : d) + 0.5f;
+        const float xs = fmt_add(fmt_add(fmt_mul(m[0], cx), xr), m[2]);
+        const float ys = fmt_add(fmt_add(fmt_mul(m[3], cx), yr), m[5]);
+        const float u = xs - 0.5f, vv = ys - 0.5f;
+        const float uf = floorf(u), vf = floorf(vv); // |u|, |v| <= 2^22 + 1: exact in an int
+        const float fx = u - uf, fy = vv - vf;
+        const int x0 = (int)uf, y0 = (int)vf;
+        const float gx = 1.f - fx, gy = 1.f - fy;
+        float line[2][3]; // top, bot
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+            const int yy = y0 + a;
+            const bool yin = yy >= 0 && yy < fh;
+            const int ry = min(max(min(max(yy, 0), fh - 1) - oy, 0), h - 1);
+            const int32_t *__restrict__ lrow = syn + (int64_t)ry * w;
+            const int32_t *__restrict__ crow = syn + (int64_t)(kind == 1 ? ry : ry & ~1) * w;
+            float t[2][3];
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                const int xx = x0 + b;
+                const bool in = yin && xx >= 0 && xx < fw;
+                const int rx = min(max(min(max(xx, 0), fw - 1) - ox, 0), w - 1);
+                fmt_pixel(lrow, crow, splane, rx, kind == 1 ? rx : rx & ~1, maxv, fmax, matrix, t[b]);
+                if (!in && Wc.pad == CCMI_PAD_FILL) {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) t[b][c] = Wc.fill[c];
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) line[a][c] = fmt_add(fmt_mul(t[0][c], gx), fmt_mul(t[1][c], fx));
+        }
+        if constexpr (COL == kColNone) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const float r = fmt_add(fmt_mul(line[0][c], gy), fmt_mul(line[1][c], fy));
+                v[c][k] = fmt_elem<T>(fmt_add(fmt_mul(r, C.scale[c]), C.bias[c]));
+            }
+        } else {
+            float r[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) r[c] = fmt_add(fmt_mul(line[0][c], gy), fmt_mul(line[1][c], fy));
+            if constexpr (COL == kColStat) {
+                sum += col_term(*K, r);
+            } else {
+                col_ops(*K, 0, K->n, mean, r);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) v[c][k] = fmt_elem<T>(fmt_add(fmt_mul(r[c], C.scale[c]), C.bias[c]));
+            }
+        }
+    }
+    if constexpr (COL != kColStat) fmt_store<T>(v, dst, C, row, d0, Wc.ow, nchw, nhwc);
+    return sum;
+}
+
+// one frame (DecOut::bps_or_flags = its kFmt* flags): the per-frame tail's, A.o = the whole synthesis output
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_warp(DecOutWarp A, DecFmtCall C, DecWarpCall Wc)
+{
+    warp_body<T>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind, A.o.bps_or_flags,
+                 reinterpret_cast<T *>(A.o.dst), C, Wc);
+}
+
+// a tail group: frame blockIdx.y's compact window
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_warp_batch(const DecOutWarp *__restrict__ Os, DecFmtCall C, DecWarpCall Wc)
+{
+    const DecOutWarp A = Os[blockIdx.y];
+    warp_body<T>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind, A.o.bps_or_flags,
+                 reinterpret_cast<T *>(A.o.dst), C, Wc);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_warp_col(DecOutWarp A, DecFmtCall C, DecWarpCall Wc, DecCol K)
+{
+    warp_body<T, kColWrite>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind, A.o.bps_or_flags,
+                            reinterpret_cast<T *>(A.o.dst), C, Wc, &K);
+}
+
+__global__ __launch_bounds__(kThreads) void dec_warp_stat(DecOutWarp A, DecWarpCall Wc, DecCol K)
+{
+    col_accumulate(K, warp_body<float, kColStat>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind,
+                                                 A.o.bps_or_flags, nullptr, col_stat_call(), Wc, &K));
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_warp_col_batch(const DecOutWarp *__restrict__ Os, DecFmtCall C, DecWarpCall Wc,
+                                                               const DecCol *__restrict__ Ks)
+{
+    const DecOutWarp A = Os[blockIdx.y];
+    warp_body<T, kColWrite>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind, A.o.bps_or_flags,
+                            reinterpret_cast<T *>(A.o.dst), C, Wc, Ks + blockIdx.y);
+}
+
+__global__ __launch_bounds__(kThreads) void dec_warp_stat_batch(const DecOutWarp *__restrict__ Os, DecWarpCall Wc,
+                                                                const DecCol *__restrict__ Ks)
+{
+    const DecCol &K = Ks[blockIdx.y];
+    if (K.contrast < 0) return;
+    const DecOutWarp A = Os[blockIdx.y];
+    col_accumulate(K, warp_body<float, kColStat>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind,
+                                                 A.o.bps_or_flags, nullptr, col_stat_call(), Wc, &K));
+}
+
+DecWarpCall warp_call(const DecFmt &f)
+{
+    DecWarpCall Wc;
+    Wc.oh = f.out_h, Wc.ow = f.out_w, Wc.pad = f.pad;
+    for (int c = 0; c < 3; ++c) Wc.fill[c] = f.fill[c];
+    return Wc;
+}
+
+} // namespace
+
+// one launch of blocks of kThreads
+template <typename Kernel, typename... A>
+static void launch(Kernel kernel, dim3 grid, hipStream_t s, const A &...a)
+{
+    hipLaunchKernelGGL(kernel, grid, dim3(kThreads), 0, s, a...);
+}
+
+// launch(T{}) for the sample type T of a tensor-output kernel
+template <typename Launch>
+static int with_sample_type(int sample, Launch &&launch)
+{
+    switch (sample) {
+    case CCMI_SAMPLE_U8: launch(uint8_t{}); break;
+    case CCMI_SAMPLE_U16: launch(uint16_t{}); break;
+    case CCMI_SAMPLE_F32: launch(float{}); break;
+    default: return ccmi_set_error(CCMI_ERR_ARG, "dec: sample type %d", sample);
+    }
+    CCMI_HIP_CHECK(hipGetLastError());
+    return CCMI_OK;
+}
+
+// launch(T{}) for the element type T of a formatted-output kernel
+template <typename Launch>
+static int with_elem_type(int elem, Launch &&launch)
+{
+    switch (elem) {
+    case CCMI_ELEM_F32: launch(float{}); break;
+    case CCMI_ELEM_F16: launch(F16{}); break;
+    case CCMI_ELEM_BF16: launch(Bf16{}); break;
+    default: return ccmi_set_error(CCMI_ERR_ARG, "dec: element type %d", elem);
+    }
+    CCMI_HIP_CHECK(hipGetLastError());
+    return CCMI_OK;
+}
+
+// dst as the kernel's element type: as(t, dst) inside a with_*_type launch
+template <typename T> static T *as(T, void *p) { return static_cast<T *>(p); }
+
+// The colour protocol of the formatted sinks, for all three geometries and both launchers.  A
+// geometry hands in its three kernel forms, each a launch on its output grid: a call without
+// colour ops runs the plain form; a call with them the statistics pass, if a frame has a contrast
+// op (stat), and then the colour form.  The plain and the colour form take the element type as T{}.
+template <typename Stat, typename Col, typename Plain>
+static int launch_fmt_forms(const DecFmt &fmt, bool stat, Stat &&stat_form, Col &&col_form, Plain &&plain_form)
+{
+    if (!fmt.col) return with_elem_type(fmt.elem, plain_form);
+    if (stat) {
+        stat_form();
+        CCMI_HIP_CHECK(hipGetLastError());
+    }
+    return with_elem_type(fmt.elem, col_form);
+}
+
+// the output grid of a formatted sink, n frames: a resample's and a warp's cover the output size,
+// the plain one's the h x w region
+static dim3 fmt_grid(const DecFmt &fmt, int h, int w, int n)
+{
+    const bool sized = fmt.rs || fmt.warp;
+    return dim3(output_fmt_blocks(sized ? fmt.out_h : h, sized ? fmt.out_w : w), n);
+}
+
+// what the cropping launchers ask of a region of an h x w frame: a known kind, inside the frame, not
+// empty and, where the kernel reads 420 chroma at the even row and column, an even origin
+static int check_region(const DecWindow &rect, int h, int w, int kind, bool even_origin)
+{
+    if (kind != 0 && kind != 1) return ccmi_set_error(CCMI_ERR_ARG, "dec: tensor output kind %d", kind);
+    if (rect.y0 < 0 || rect.x0 < 0 || rect.y1 > h || rect.x1 > w || rect.h() < 1 || rect.w() < 1)
+        return ccmi_set_error(CCMI_ERR_ARG, "dec: region outside the frame");
+    if (even_origin && kind == 0 && ((rect.y0 | rect.x0) & 1))
+        return ccmi_set_error(CCMI_ERR_ARG, "dec: a 420 region needs an even origin");
+    return CCMI_OK;
+}
+
+// a per-frame tail's colour form needs the frame's op table (and a contrast op its accumulator)
+static int col_frame(const DecFmt &fmt, const DecCol *col)
+{
+    if (fmt.col && (!col || (col->contrast >= 0 && !col->acc)))
+        return ccmi_set_error(CCMI_ERR_ARG, "dec: colour without its op table");
+    return CCMI_OK;
+}
+
+size_t dec_resample_tmp_elems(int region_h, int out_w) { return 3 * (size_t)region_h * out_w; }
+
+static DecOutWarp make_out_warp(const DecOut &o, const DecFmt &fmt, int oy, int ox, int fh, int fw)
+{
+    DecOutWarp A{o, {}, oy, ox, fh, fw};
+    for (int k = 0; k < 6; ++k) A.m[k] = fmt.m[k];
+    return A;
+}
+
+static unsigned output_blocks(int h, int w) { return (unsigned)(((int64_t)h * w + kThreads - 1) / kThreads); }
+
+int launch_dec_out_frame(const DecTailFrame &f, const int32_t *syn, int h, int w, bool crop, bool device, hipStream_t s)
+{
+    const DecFmt &fmt = f.fmt;
+    const DecWindow &rect = f.roi.rect;
+    const int kind = f.kind, maxv = (1 << f.bitdepth) - 1;
+    void *dst = f.dst;
+    if (!fmt.on) {
+        if (crop) {
+            if (int rc = check_region(rect, h, w, kind, false)) return rc;
+            const dim3 grid(output_tensor_blocks(rect.h(), rect.w(), kind));
+            return with_sample_type(f.sample, [&](auto t) {
+                launch(dec_output_tensor_crop<decltype(t)>, grid, s, syn, h, w, rect.y0, rect.x0, rect.h(), rect.w(), maxv,
+                       kind, as(t, dst));
+            });
+        }
+        if (device) {
+            if (kind != 0 && kind != 1) return ccmi_set_error(CCMI_ERR_ARG, "dec: tensor output kind %d", kind);
+            const dim3 grid(output_tensor_blocks(h, w, kind));
+            return with_sample_type(f.sample, [&](auto t) {
+                launch(dec_output_tensor<decltype(t)>, grid, s, syn, h, w, maxv, kind, as(t, dst));
+            });
+        }
+        launch(dec_output_kernel, dim3(output_blocks(h, w)), s, syn, h, w, maxv, kind, f.bitdepth <= 8 ? 1 : 2, f.dst);
+        CCMI_HIP_CHECK(hipGetLastError());
+        return CCMI_OK;
+    }
+    // the formatted sinks: a warp samples the whole frame, the others read roi.rect (the region, or the whole frame)
+    if (int rc = check_region(fmt.warp ? DecWindow{0, h, 0, w} : rect, h, w, kind, true)) return rc;
+    if (fmt.warp) {
+        if (fmt.out_h < 1 || fmt.out_w < 1) return ccmi_set_error(CCMI_ERR_ARG, "dec: warp without a size");
+        if (kind == 0 && ((h | w) & 1)) return ccmi_set_error(CCMI_ERR_ARG, "dec: a 420 warp needs an even frame size");
+    } else if (fmt.rs && (fmt.out_h < 1 || fmt.out_w < 1 || !f.rs_tmp)) {
+        return ccmi_set_error(CCMI_ERR_ARG, "dec: resample without a size");
+    }
+    if (int rc = col_frame(fmt, f.col)) return rc;
+    const DecCol *K = f.col; // the colour forms take the frame's op table by value
+    const bool stat = fmt.col && K->contrast >= 0;
+    const dim3 grid = fmt_grid(fmt, rect.h(), rect.w(), 1);
+    const int flags = fmt_flags(fmt), rh = rect.h(), rw = rect.w(), oh = fmt.out_h, ow = fmt.out_w;
+    const DecFmtCall C = fmt_call(fmt);
+    if (fmt.warp) {
+        const DecOutWarp A = make_out_warp(DecOut{syn, h, w, maxv, kind, flags, f.dst}, fmt, 0, 0, h, w);
+        const DecWarpCall Wc = warp_call(fmt);
+        return launch_fmt_forms(
+            fmt, stat, [&] { launch(dec_warp_stat, grid, s, A, Wc, *K); },
+            [&](auto t) { launch(dec_warp_col<decltype(t)>, grid, s, A, C, Wc, *K); },
+            [&](auto t) { launch(dec_warp<decltype(t)>, grid, s, A, C, Wc); });
+    }
+    if (fmt.rs) { // rs_tmp holds the horizontal pass
+        float *tmp = f.rs_tmp;
+        launch(dec_resample_h, dim3(resample_h_blocks(rh, ow)), s, syn, h, w, rect.y0, rect.x0, rh, rw, ow, maxv, kind, flags, tmp);
+        CCMI_HIP_CHECK(hipGetLastError());
+        return launch_fmt_forms(
+            fmt, stat, [&] { launch(dec_resample_v_stat, grid, s, tmp, rh, oh, ow, flags, *K); },
+            [&](auto t) { launch(dec_resample_v_col<decltype(t)>, grid, s, tmp, rh, oh, ow, flags, as(t, dst), C, *K); },
+            [&](auto t) { launch(dec_resample_v<decltype(t)>, grid, s, tmp, rh, oh, ow, flags, as(t, dst), C); });
+    }
+    return launch_fmt_forms(
+        fmt, stat, [&] { launch(dec_output_fmt_stat, grid, s, syn, h, w, rect.y0, rect.x0, rh, rw, maxv, kind, flags, *K); },
+        [&](auto t) {
+            launch(dec_output_fmt_col<decltype(t)>, grid, s, syn, h, w, rect.y0, rect.x0, rh, rw, maxv, kind, flags, as(t, dst), C, *K);
+        },
+        [&](auto t) {
+            launch(dec_output_fmt<decltype(t)>, grid, s, syn, h, w, rect.y0, rect.x0, rh, rw, maxv, kind, flags, as(t, dst), C);
+        });
+}
+
+// ------------------------------------------------------------------ a tail group's output section
+size_t dec_out_entry_bytes(int out_form)
+{
+    return out_form == kOutRs ? sizeof(DecOutRs) : out_form == kOutWarp ? sizeof(DecOutWarp) : sizeof(DecOut);
+}
+
+void dec_out_fill(void *out_sec, void *col_sec, int i, const DecTailFrame &f, int h, int w, int oy, int ox)
+{
+    const DecOut o{f.syn.out, h, w, (1 << f.bitdepth) - 1, f.kind, f.fmt.on ? fmt_flags(f.fmt) : f.bitdepth <= 8 ? 1 : 2,
+                   f.dst};
+    if (f.fmt.warp) static_cast<DecOutWarp *>(out_sec)[i] = make_out_warp(o, f.fmt, oy, ox, f.syn.h, f.syn.w);
+    else if (f.fmt.rs) static_cast<DecOutRs *>(out_sec)[i] = DecOutRs{o, f.rs_tmp};
+    else static_cast<DecOut *>(out_sec)[i] = o;
+    if (f.fmt.col) static_cast<DecCol *>(col_sec)[i] = *f.col;
+}
+
+int launch_dec_out_group(const DecTailFrame &f0, int h, int w, int n, const void *out_sec, const DecCol *kk, bool stat,
+                         hipStream_t s)
+{
+    const DecFmt &fmt = f0.fmt;
+    if (!fmt.on) {
+        const DecOut *oo = static_cast<const DecOut *>(out_sec);
+        if (f0.sample < 0) { // file bytes
+            launch(dec_output_batch, dim3(output_blocks(h, w), n), s, oo);
+            CCMI_HIP_CHECK(hipGetLastError());
+            return CCMI_OK;
+        }
+        const dim3 grid(output_tensor_blocks(h, w, f0.kind), n); // one kind per group
+        return with_sample_type(f0.sample, [&](auto t) { launch(dec_output_tensor_batch<decltype(t)>, grid, s, oo); });
+    }
+    // the format but its per-frame flags (in the table) is the call's
+    const dim3 grid = fmt_grid(fmt, h, w, n);
+    const DecFmtCall C = fmt_call(fmt);
+    if (fmt.warp) { // the section holds DecOutWarp
+        const DecOutWarp *ww = static_cast<const DecOutWarp *>(out_sec);
+        const DecWarpCall Wc = warp_call(fmt);
+        return launch_fmt_forms(
+            fmt, stat, [&] { launch(dec_warp_stat_batch, grid, s, ww, Wc, kk); },
+            [&](auto t) { launch(dec_warp_col_batch<decltype(t)>, grid, s, ww, C, Wc, kk); },
+            [&](auto t) { launch(dec_warp_batch<decltype(t)>, grid, s, ww, C, Wc); });
+    }
+    if (fmt.rs) { // the section holds DecOutRs; h = the group's tallest region
+        const DecOutRs *rr = static_cast<const DecOutRs *>(out_sec);
+        const int oh = fmt.out_h, ow = fmt.out_w;
+        launch(dec_resample_h_batch, dim3(resample_h_blocks(h, ow), n), s, rr, ow);
+        CCMI_HIP_CHECK(hipGetLastError());
+        return launch_fmt_forms(
+            fmt, stat, [&] { launch(dec_resample_v_stat_batch, grid, s, rr, oh, ow, kk); },
+            [&](auto t) { launch(dec_resample_v_col_batch<decltype(t)>, grid, s, rr, oh, ow, C, kk); },
+            [&](auto t) { launch(dec_resample_v_batch<decltype(t)>, grid, s, rr, oh, ow, C); });
+    }
+    const DecOut *oo = static_cast<const DecOut *>(out_sec);
+    return launch_fmt_forms(
+        fmt, stat, [&] { launch(dec_output_fmt_stat_batch, grid, s, oo, kk); },
+        [&](auto t) { launch(dec_output_fmt_col_batch<decltype(t)>, grid, s, oo, C, kk); },
+        [&](auto t) { launch(dec_output_fmt_batch<decltype(t)>, grid, s, oo, C); });
+}
+
+} // namespace ccmi

@@ -10,7 +10,7 @@ samples long, so the output kernel's partial first / last groups and the groups 
 from the luma into the chroma planes are a large share of each frame.  One more (21, 37)
 stream has its third synthesis layer turned from 3x3 into 1x1: dec_tail.hip's syn_fast()
 refuses it, so it is the one stream here that takes the per-frame decoder tail
-(launch_dec_output_tensor); every other stream, committed or generated, alone or in a
+(dec_output_tensor, dec_out.hip); every other stream, committed or generated, alone or in a
 batch, has a fused-synthesis architecture with one branch and takes the batched tail
 (dec_output_tensor_batch, a group per geometry and chunk, dec_host.cpp)."""
 import ctypes as C

@@ -14,7 +14,7 @@
 //   cd cool-chic_amd && hipcc -O1 -g -std=c++17 -fwrapv --offload-arch=gfx950 \
 //       -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
 //       -x hip ../tools/decode_plan_san.cpp csrc/dec_plan.cpp csrc/dec_host.cpp csrc/ccmi_api.cpp \
-//       csrc/dec_arm.hip csrc/dec_tail.hip csrc/dec_latents.hip -o /tmp/decode_plan_san
+//       csrc/dec_arm.hip csrc/dec_tail.hip csrc/dec_out.hip csrc/dec_latents.hip -o /tmp/decode_plan_san
 //   /tmp/decode_plan_san $(find ../tests/golden/cool ../tests/golden/cool_synth -name '*.cool')
 #include <stdio.h>
 #include <stdlib.h>

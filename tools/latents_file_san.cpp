@@ -13,8 +13,8 @@
 //   cd cool-chic_amd && hipcc -O1 -g -std=c++17 -fwrapv --offload-arch=gfx950 \
 //       -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
 //       -x hip ../tools/latents_file_san.cpp csrc/dec_store_file.cpp csrc/dec_store.cpp csrc/dec_plan.cpp \
-//       csrc/dec_host.cpp csrc/ccmi_api.cpp csrc/dec_arm.hip csrc/dec_tail.hip csrc/dec_latents.hip \
-//       -o /tmp/latents_file_san
+//       csrc/dec_host.cpp csrc/ccmi_api.cpp csrc/dec_arm.hip csrc/dec_tail.hip csrc/dec_out.hip \
+//       csrc/dec_latents.hip -o /tmp/latents_file_san
 //   /tmp/latents_file_san ../tests/golden/latent_meta/*.meta
 #include <stdio.h>
 #include <stdlib.h>
