@@ -58,8 +58,10 @@ def _as_batch(params: torch.Tensor, B: int):
 
 
 def arm_forward(latent: torch.Tensor, sizes, params: torch.Tensor, dim_arm: int, n_hidden: int,
-                gain: float = 16.0, quantize: bool = True, want=("mu", "scale", "log_scale", "rate")) -> dict:
-    """latent [B, N] (or [N]) flat grids; params [B, P] (or [P]).  Returns dict of [B, N] tensors."""
+                gain: float = 16.0, quantize: bool = True, want=("mu", "scale", "log_scale", "rate"),
+                form: int = 0) -> dict:
+    """latent [B, N] (or [N]) flat grids; params [B, P] (or [P]).  Returns dict of [B, N] tensors.
+    form: the kernel form (ccmi.ARM_FORM_*); every form gives the same bits."""
     squeeze = latent.dim() == 1
     latent = latent.unsqueeze(0) if squeeze else latent
     B, N = latent.shape
@@ -77,7 +79,10 @@ def arm_forward(latent: torch.Tensor, sizes, params: torch.Tensor, dim_arm: int,
                 quantize=int(bool(quantize)), dim_arm=dim_arm, n_hidden=n_hidden, params=ptr(params),
                 param_stride=pstride, mu=ptr(outs.get("mu")), scale=ptr(outs.get("scale")),
                 log_scale=ptr(outs.get("log_scale")), rate=ptr(outs.get("rate")), out_stride=N, batch=B)
-    check(lib().ccmi_arm_forward_f32(a, stream_handle(latent.device)))
+    if form:
+        check(lib().ccmi_arm_forward_f32_form(a, stream_handle(latent.device), int(form)))
+    else:
+        check(lib().ccmi_arm_forward_f32(a, stream_handle(latent.device)))
     if squeeze:
         outs = {k: v[0] for k, v in outs.items()}
     return outs

@@ -66,6 +66,40 @@ void ccmi_streamset_release(StreamSet *set)
     g_pool.push_back(set);
 }
 
+// Packed-weight buffers of the ARM's pairs form, one per (device, stream).  A buffer too small
+// for a later call stays where it is (a captured graph may hold its address) and a larger one
+// is added in front of it; none is freed (the runtime may be gone at process exit).
+struct ArmPackBuf {
+    int device;
+    hipStream_t stream;
+    float *ptr;
+    size_t bytes;
+};
+static std::mutex g_pack_mu;
+static std::vector<ArmPackBuf> g_pack; // newest first per key
+
+int ccmi_arm_pack_buffer(size_t bytes, hipStream_t s, float **out)
+{
+    *out = nullptr;
+    int dev = 0;
+    CCMI_HIP_CHECK(hipGetDevice(&dev));
+    std::lock_guard<std::mutex> lk(g_pack_mu);
+    for (const ArmPackBuf &b : g_pack)
+        if (b.device == dev && b.stream == s && b.bytes >= bytes) {
+            *out = b.ptr;
+            return CCMI_OK;
+        }
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    CCMI_HIP_CHECK(hipStreamIsCapturing(s, &cap));
+    if (cap != hipStreamCaptureStatusNone) return CCMI_OK;
+    const size_t want = (bytes + 65535) & ~(size_t)65535;
+    float *p = nullptr;
+    CCMI_HIP_CHECK(hipMalloc(reinterpret_cast<void **>(&p), want));
+    g_pack.insert(g_pack.begin(), ArmPackBuf{dev, s, p, want});
+    *out = p;
+    return CCMI_OK;
+}
+
 extern "C" const char *ccmi_last_error(void) { return g_err; }
 
 extern "C" int ccmi_version(void) { return 101; }
@@ -87,6 +121,12 @@ static int check_grids(int n, const int *h, const int *w, const char *who)
 
 extern "C" int ccmi_arm_forward_f32(const ccmi_arm_args *a, void *stream)
 {
+    return ccmi_arm_forward_f32_form(a, stream, CCMI_ARM_FORM_DEFAULT);
+}
+
+extern "C" int ccmi_arm_forward_f32_form(const ccmi_arm_args *a, void *stream, int form)
+{
+    if (form < CCMI_ARM_FORM_DEFAULT || form > CCMI_ARM_FORM_PAIRS) return ccmi_set_error(CCMI_ERR_ARG, "arm: unknown form %d", form);
     if (!a || !a->latent || !a->params) return ccmi_set_error(CCMI_ERR_ARG, "arm: null argument");
     if (int rc = check_grids(a->n_grids, a->h, a->w, "arm")) return rc;
     if (a->batch < 1) return ccmi_set_error(CCMI_ERR_ARG, "arm: batch must be >= 1");
@@ -94,7 +134,7 @@ extern "C" int ccmi_arm_forward_f32(const ccmi_arm_args *a, void *stream)
     const int64_t need = (int64_t)a->n_hidden * (a->dim_arm * a->dim_arm + a->dim_arm) + 2 * a->dim_arm + 2;
     if (a->param_stride != 0 && a->param_stride < need) return ccmi_set_error(CCMI_ERR_ARG, "arm: param_stride < %lld", (long long)need);
     if (!a->rate && !a->mu && !a->scale && !a->log_scale) return ccmi_set_error(CCMI_ERR_ARG, "arm: no output requested");
-    return ccmi_launch_arm_f32(a, static_cast<hipStream_t>(stream));
+    return ccmi_launch_arm_f32(a, static_cast<hipStream_t>(stream), form);
 }
 
 extern "C" int ccmi_ups_forward_f32(const ccmi_ups_args *a, void *stream)

@@ -35,10 +35,15 @@ int ccmi_set_error(int code, const char *fmt, ...);
 static inline int ccmi_div_up(int a, int b) { return (a + b - 1) / b; }
 
 // Stage launchers (return CCMI_OK or an error code; never exit()).
-int ccmi_launch_arm_f32(const ccmi_arm_args *a, hipStream_t s);
+int ccmi_launch_arm_f32(const ccmi_arm_args *a, hipStream_t s, int form);
 int ccmi_launch_ups_f32(const ccmi_ups_args *a, hipStream_t s);
 int ccmi_launch_syn_f32(const ccmi_syn_args *a, hipStream_t s);
 int ccmi_launch_post_f32(const ccmi_post_args *a, hipStream_t s);
+
+// The packed-weight buffer of the ARM's pairs form for stream s of the current device (contract:
+// ccmi.h, ccmi_arm_forward_f32_form).  *out = a device buffer of >= bytes, or nullptr (with
+// CCMI_OK) when none exists and s is capturing, so none may be allocated.
+int ccmi_arm_pack_buffer(size_t bytes, hipStream_t s, float **out);
 
 // Process-wide pool of side streams and events, one set per concurrent user and device
 // (train.hip's ARM side stream, dec_host.cpp's chunk streams).  A set is leased for one call

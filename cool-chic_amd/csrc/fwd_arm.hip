@@ -15,6 +15,11 @@
 // scalar loads) feeds one v_pk_fma_f32 (two FMAs).  NL = 4 (two pairs per weight) was
 // measured 13 % slower: 132 VGPRs, 3 waves per SIMD instead of 7.  LDS reads are lane-consecutive (conflict-free).  Grids of all resolutions
 // share one launch through a tile prefix table (no per-grid launches).
+//
+// Two forms of the MLP, bit for bit the same (ccmi_arm_forward_f32_form): the row form above
+// (arm_fwd_kernel, every dim_arm, reads the caller's parameters) and the pairs form
+// (arm_fwd_pairs_kernel, dim_arm 8 and 16, the default): a packed register is two output units
+// of one latent, the weights come from a transposed copy written by arm_pack_kernel.
 #include <stdlib.h>
 
 #include <algorithm>
@@ -39,6 +44,9 @@ constexpr int kHalo = 4;
 constexpr int kLW = kTX + 2 * kHalo;          // 72
 constexpr int kLH = kTY + kHalo;              // 12
 
+
+// scaled ReLU of the pairs form: activations travel times 2^-32
+constexpr float kArmDown = 0x1p-32f, kArmUp = 0x1p+32f;
 
 struct ArmGeom {
     int n;
@@ -78,31 +86,36 @@ __device__ __forceinline__ float laplace_cdf(float x, float mu, float inv_scale)
     return 0.5f - 0.5f * sg * (__expf(-fabsf(s) * inv_scale) - 1.f);
 }
 
-// NH >= 0: the hidden-layer count fixed at compile time (the layer loop unrolled, so the
-// next layer's scalar weight loads can be scheduled under the current layer's FMAs)
-template <int D, int NH = -1>
-__global__ __launch_bounds__(kThreads) void arm_fwd_kernel(
-    const float *__restrict__ lat, int64_t lat_stride, ArmGeom g, float gain, int quantize, int nh,
-    const float *__restrict__ params, int64_t pstride, float *__restrict__ o_mu, float *__restrict__ o_scale,
-    float *__restrict__ o_log_scale, float *__restrict__ o_rate, int64_t ostride)
-{
-    __shared__ float tile[kLH][kLW];
+// The tile a workgroup owns: grid l of frame b, rows y0.., columns x0.. of its H x W latents.
+struct ArmTile {
+    int b, l, H, W, y0, x0;
+};
 
+// Finds the workgroup's tile and stages it, quantised, with its causal halo in LDS.  SC: the
+// quantised values are stored times 2^-32 (arm_fwd_pairs_kernel's scaled ReLU).
+template <bool SC = false>
+__device__ __forceinline__ ArmTile arm_stage_tile(float (&tile)[kLH][kLW], const float *__restrict__ lat,
+                                                  int64_t lat_stride, const ArmGeom &g, float gain, int quantize)
+{
     // XCD-aware tile order (ccmi_fwd::xcd_order): vertically adjacent tiles, which share the
     // 4 causal halo rows, meet in one L2
     const int wt = ccmi_fwd::xcd_order(blockIdx.x, gridDim.x);
     const int ntl = g.tile_start[g.n];
-    const int b = wt / ntl;
-    const int t = wt - b * ntl;
+    ArmTile T;
+    T.b = wt / ntl;
+    const int t = wt - T.b * ntl;
     int l = 0;
 #pragma unroll
     for (int k = 1; k < CCMI_MAX_GRIDS; ++k)
         if (k < g.n && t >= g.tile_start[k]) l = k;
     const int lt = t - g.tile_start[l];
-    const int H = g.h[l], W = g.w[l];
-    const int y0 = (lt / g.tiles_x[l]) * kTY;
-    const int x0 = (lt % g.tiles_x[l]) * kTX;
-    const float *src = lat + (int64_t)b * lat_stride + g.off[l];
+    T.l = l;
+    T.H = g.h[l];
+    T.W = g.w[l];
+    T.y0 = (lt / g.tiles_x[l]) * kTY;
+    T.x0 = (lt % g.tiles_x[l]) * kTX;
+    const int H = T.H, W = T.W, y0 = T.y0, x0 = T.x0;
+    const float *src = lat + (int64_t)T.b * lat_stride + g.off[l];
 
     // fixed trip count, unrolled: every load of the thread is in flight before the first
     // LDS store waits on one
@@ -119,12 +132,52 @@ __global__ __launch_bounds__(kThreads) void arm_fwd_kernel(
 #pragma unroll
         for (int u = 0; u < NU; ++u) {
             const int i = threadIdx.x + u * kThreads;
-            if (i < kLH * kLW) tile[i / kLW][i % kLW] = quantize ? rintf(gain * lv[u]) : lv[u];
+            if constexpr (SC) {
+                if (i < kLH * kLW) tile[i / kLW][i % kLW] = rintf(gain * lv[u]) * kArmDown;
+            } else {
+                if (i < kLH * kLW) tile[i / kLW][i % kLW] = quantize ? rintf(gain * lv[u]) : lv[u];
+            }
         }
     }
     __syncthreads();
+    return T;
+}
 
-    const cfloat_ptr p = (cfloat_ptr)(size_t)(params + (int64_t)b * pstride);
+// Scale, rate and the stores of the thread's latent n (row cy0 + n * kRowsPerPass of the tile)
+// from its mu mn and log-scale lsn; q is the latent's own quantised value.
+__device__ __forceinline__ void arm_emit(const ArmTile &T, const ArmGeom &g, int n, float mn, float lsn, float q,
+                                         float *__restrict__ o_mu, float *__restrict__ o_scale,
+                                         float *__restrict__ o_log_scale, float *__restrict__ o_rate, int64_t ostride)
+{
+    const int y = T.y0 + threadIdx.x / kTX + n * kRowsPerPass, x = T.x0 + threadIdx.x % kTX;
+    if (y < T.H && x < T.W) {
+        // v_exp_f32 / v_log_f32 directly (the clamped exponent and p in [2^-16, 1] are far
+        // from the ranges the library forms guard; errors well inside the rate tolerance)
+        const float sc = __expf(fminf(fmaxf(lsn - 4.f, -4.6f), 5.0f));
+        const int64_t idx = (int64_t)T.b * ostride + g.off[T.l] + y * T.W + x;
+        if (o_mu) o_mu[idx] = mn;
+        if (o_scale) o_scale[idx] = sc;
+        if (o_log_scale) o_log_scale[idx] = lsn;
+        if (o_rate) {
+            const float is = __builtin_amdgcn_rcpf(sc);
+            const float pr = fmaxf(laplace_cdf(q + 0.5f, mn, is) - laplace_cdf(q - 0.5f, mn, is), 1.52587890625e-05f);
+            o_rate[idx] = -__log2f(pr);
+        }
+    }
+}
+
+// NH >= 0: the hidden-layer count fixed at compile time (the layer loop unrolled, so the
+// next layer's scalar weight loads can be scheduled under the current layer's FMAs)
+template <int D, int NH = -1>
+__global__ __launch_bounds__(kThreads) void arm_fwd_kernel(
+    const float *__restrict__ lat, int64_t lat_stride, ArmGeom g, float gain, int quantize, int nh,
+    const float *__restrict__ params, int64_t pstride, float *__restrict__ o_mu, float *__restrict__ o_scale,
+    float *__restrict__ o_log_scale, float *__restrict__ o_rate, int64_t ostride)
+{
+    __shared__ float tile[kLH][kLW];
+    const ArmTile T = arm_stage_tile(tile, lat, lat_stride, g, gain, quantize);
+
+    const cfloat_ptr p = (cfloat_ptr)(size_t)(params + (int64_t)T.b * pstride);
     const int cx = threadIdx.x % kTX;
     const int cy0 = threadIdx.x / kTX;
 
@@ -189,24 +242,183 @@ __global__ __launch_bounds__(kThreads) void arm_fwd_kernel(
         }
     }
 #pragma unroll
+    for (int n = 0; n < kNL; ++n)
+        arm_emit(T, g, n, (n & 1) ? m[n >> 1].y : m[n >> 1].x, (n & 1) ? ls[n >> 1].y : ls[n >> 1].x,
+                 tile[cy0 + n * kRowsPerPass + kHalo][cx + kHalo], o_mu, o_scale, o_log_scale, o_rate, ostride);
+}
+
+// The transposed copy of every frame's ARM parameters the pairs form reads (layout:
+// fwd_common.h, arm_pack_src).  One workgroup per frame.
+__global__ __launch_bounds__(kThreads) void arm_pack_kernel(const float *__restrict__ params, int64_t pstride, int d,
+                                                            int nh, float *__restrict__ out, int ostride)
+{
+    const float *p = params + (int64_t)blockIdx.x * pstride;
+    float *o = out + (int64_t)blockIdx.x * ostride;
+    for (int t = threadIdx.x; t < ostride; t += kThreads) {
+        const int s = ccmi_fwd::arm_pack_src(d, nh, t);
+        o[t] = s >= 0 ? p[s] : 0.f;
+    }
+}
+
+template <int D>
+using arm_row = float __attribute__((ext_vector_type(D)));
+
+// One row of D packed weights, `at` floats into the frame's block, as one scalar load with the
+// offset in an SGPR.  The offset is made opaque so that the load stays where it is written:
+// left to itself the compiler hoists every row load of an unrolled layer to its top and
+// spills the SGPRs through VGPR lanes.
+template <int D>
+__device__ __forceinline__ arm_row<D> arm_load_row(cfloat_ptr base, unsigned at, const arm_row<D> *landed = nullptr)
+{
+    // scalar loads return out of order, so every wait is for all of them: the wait for the row
+    // in use (`landed`, issued a row of FMAs ago) goes in front of this load, not behind it
+    if (landed) asm volatile("" ::"s"((*landed)[0]));
+    unsigned off = at * (unsigned)sizeof(float);
+    asm volatile("" : "+s"(off));
+    const arm_row<D> r =
+        *(const __attribute__((address_space(4))) arm_row<D> *)((const __attribute__((address_space(4))) char *)base + off);
+    // and the scheduler may not sink the load below the FMAs that follow it: it is issued
+    // here and waited for at its first use, a row of FMAs later
+    __builtin_amdgcn_sched_barrier(0);
+    return r;
+}
+
+// Keeps the row loads one row ahead of the FMAs: no FMA of a later row (and so no load of the
+// row after it) moves above this point.
+template <int N>
+__device__ __forceinline__ void arm_fence(f2 (&o)[kNL][N])
+{
+    static_assert(N == 4 || N == 8, "accumulator pairs per latent");
+#pragma unroll
     for (int n = 0; n < kNL; ++n) {
-        const int y = y0 + cy0 + n * kRowsPerPass, x = x0 + cx;
-        const float mn = (n & 1) ? m[n >> 1].y : m[n >> 1].x, lsn = (n & 1) ? ls[n >> 1].y : ls[n >> 1].x;
-        if (y < H && x < W) {
-            // v_exp_f32 / v_log_f32 directly (the clamped exponent and p in [2^-16, 1] are far
-            // from the ranges the library forms guard; errors well inside the rate tolerance)
-            const float sc = __expf(fminf(fmaxf(lsn - 4.f, -4.6f), 5.0f));
-            const float q = tile[cy0 + n * kRowsPerPass + kHalo][cx + kHalo];
-            const int64_t idx = (int64_t)b * ostride + g.off[l] + y * W + x;
-            if (o_mu) o_mu[idx] = mn;
-            if (o_scale) o_scale[idx] = sc;
-            if (o_log_scale) o_log_scale[idx] = lsn;
-            if (o_rate) {
-                const float is = __builtin_amdgcn_rcpf(sc);
-                const float pr = fmaxf(laplace_cdf(q + 0.5f, mn, is) - laplace_cdf(q - 0.5f, mn, is), 1.52587890625e-05f);
-                o_rate[idx] = -__log2f(pr);
+        if constexpr (N == 8)
+            asm volatile("" : "+v"(o[n][0]), "+v"(o[n][1]), "+v"(o[n][2]), "+v"(o[n][3]), "+v"(o[n][4]), "+v"(o[n][5]),
+                         "+v"(o[n][6]), "+v"(o[n][7]));
+        else
+            asm volatile("" : "+v"(o[n][0]), "+v"(o[n][1]), "+v"(o[n][2]), "+v"(o[n][3]));
+    }
+}
+
+// The pairs form of arm_fwd_kernel: same tile, same arithmetic, bit for bit, other packing.
+// A packed register holds two neighbouring output units (j, j + 1) of ONE latent, so the weight
+// operand of a v_pk_fma_f32 is the pair (W[j][i], W[j + 1][i]): with the transposed copy of
+// arm_pack_kernel an aligned SGPR pair straight out of the row's scalar load, where the row
+// form moves every odd-indexed weight into a scratch pair first.  The activation a_i is one
+// half of a VGPR pair, selected by op_sel.  A layer is D / 2 independent accumulator chains
+// per latent walked over i; each output is still (a_j + b_j) and then the products for
+// i = 0 .. D-1 in order.  The rows are consumed in the order they are stored (layer: bias
+// row first, then rows 0 .. D-1; then the output block in two halves), each loaded while the
+// one before it is used.
+//
+// SC (quantize = 1 only), the scaled ReLU: the tile is staged as q 2^-32, the accumulators start
+// at b 2^-32 + a' (one v_pk_fma_f32 where the unscaled form has a v_pk_add_f32), so a
+// pre-activation arrives as h 2^-32 and max(h, 0) is the clamp-to-[0, 1] modifier of the layer's
+// last fma: no v_max_f32 per unit and latent (gfx950 has no packed f32 max).  mu, log_scale
+// and the latent's own value are multiplied back by 2^32 at the end.  Nothing is rescaled on
+// the scalar unit: the weights are used as they are.  A power-of-two scaling commutes with
+// every rounding of the chain, so the bits are the unscaled form's, under the conditions
+// written at the fused head's unit() (fwd_syn.hip, "Scaled ReLU"): every bias, activation and
+// partial sum is 0 or at least 2^-94 in magnitude, and no pre-activation exceeds 2^32.
+template <int D, int NH = -1, bool SC = false>
+__global__ __launch_bounds__(kThreads) void arm_fwd_pairs_kernel(
+    const float *__restrict__ lat, int64_t lat_stride, ArmGeom g, float gain, int quantize, int nh,
+    const float *__restrict__ packed, int pkstride, float *__restrict__ o_mu, float *__restrict__ o_scale,
+    float *__restrict__ o_log_scale, float *__restrict__ o_rate, int64_t ostride)
+{
+    static_assert(kNL == 2 && (D == 8 || D == 16), "pairs form: two latents per thread, dim_arm 8 or 16");
+    constexpr int RS = ccmi_fwd::arm_pack_row(D), LS = ccmi_fwd::arm_pack_layer(D), HP = D / 2;
+    __shared__ float tile[kLH][kLW];
+    const ArmTile T = arm_stage_tile<SC>(tile, lat, lat_stride, g, gain, quantize);
+
+    const cfloat_ptr P = (cfloat_ptr)(size_t)(packed + (int64_t)T.b * pkstride);
+    const int cx = threadIdx.x % kTX;
+    const int cy0 = threadIdx.x / kTX;
+    if constexpr (NH >= 0) nh = NH;
+
+    // a[n][jp] = activations (2 jp, 2 jp + 1) of latent n (row cy0 + n * kRowsPerPass)
+    f2 a[kNL][HP];
+#pragma unroll
+    for (int i = 0; i < D; ++i) {
+        int dy, dx;
+        ctx_offset<D>(i, dy, dx);
+#pragma unroll
+        for (int n = 0; n < kNL; ++n) a[n][i >> 1][i & 1] = tile[cy0 + n * kRowsPerPass + kHalo + dy][cx + kHalo + dx];
+    }
+
+    const unsigned Wo = nh * LS;
+    const f2 bo = *(const __attribute__((address_space(4))) f2 *)(P + Wo + 2 * D);
+    arm_row<D> cur = arm_load_row<D>(P, nh > 0 ? D * RS : 0);
+#pragma unroll
+    for (int layer = 0; layer < nh; ++layer) {
+        const unsigned Wl = layer * LS;
+        // F.linear(x) + x, then ReLU: the accumulators start at bias + residual
+        f2 o[kNL][HP];
+        arm_row<D> nxt = arm_load_row<D>(P, Wl, &cur);
+#pragma unroll
+        for (int n = 0; n < kNL; ++n)
+#pragma unroll
+            for (int jp = 0; jp < HP; ++jp) {
+                const f2 bp = f2{cur[2 * jp], cur[2 * jp + 1]};
+                o[n][jp] = SC ? __builtin_elementwise_fma(bp, f2(kArmDown), a[n][jp]) : a[n][jp] + bp;
             }
+        arm_fence(o);
+        cur = nxt;
+#pragma unroll
+        for (int i = 0; i < D; ++i) {
+            // after the last row: the next layer's bias row, or the first half of the output block
+            nxt = arm_load_row<D>(P, i + 1 < D ? Wl + (i + 1) * RS : layer + 1 < nh ? Wl + LS + D * RS : Wl + LS, &cur);
+#pragma unroll
+            for (int n = 0; n < kNL; ++n) {
+                const f2 ai = f2(a[n][i >> 1][i & 1]);
+#pragma unroll
+                for (int jp = 0; jp < HP; ++jp) {
+                    const f2 wp = f2{cur[2 * jp], cur[2 * jp + 1]};
+                    if constexpr (SC && (D & 1) == 0) {
+                        if (i == D - 1) { // the odd half of the last activation pair, clamped to [0, 1]
+                            asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[0,1,0] op_sel_hi:[1,1,1] clamp"
+                                : "=v"(o[n][jp])
+                                : "s"(wp), "v"(a[n][HP - 1]), "v"(o[n][jp]));
+                            continue;
+                        }
+                    }
+                    o[n][jp] = __builtin_elementwise_fma(wp, ai, o[n][jp]);
+                }
+            }
+            // not after the last row: the ReLU would get a canonicalising v_max in front of it
+            if (i + 1 < D) arm_fence(o);
+            cur = nxt;
         }
+#pragma unroll
+        for (int n = 0; n < kNL; ++n)
+#pragma unroll
+            for (int jp = 0; jp < HP; ++jp) a[n][jp] = SC ? o[n][jp] : __builtin_elementwise_max(o[n][jp], f2(0.f));
+    }
+
+    // output layer: one pair (mu, log_scale) per latent; cur holds WoT[0 .. D/2)
+    f2 ml[kNL];
+#pragma unroll
+    for (int n = 0; n < kNL; ++n) ml[n] = SC ? bo * kArmDown : bo;
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        arm_row<D> nxt = cur;
+        if (half == 0) nxt = arm_load_row<D>(P, Wo + D, &cur);
+#pragma unroll
+        for (int k = 0; k < HP; ++k) {
+            const int i = half * HP + k;
+#pragma unroll
+            for (int n = 0; n < kNL; ++n)
+                ml[n] = __builtin_elementwise_fma(f2{cur[2 * k], cur[2 * k + 1]}, f2(a[n][i >> 1][i & 1]), ml[n]);
+        }
+        cur = nxt;
+    }
+#pragma unroll
+    for (int n = 0; n < kNL; ++n) {
+        float q = tile[cy0 + n * kRowsPerPass + kHalo][cx + kHalo];
+        if constexpr (SC) {
+            ml[n] *= kArmUp;
+            q *= kArmUp;
+        }
+        arm_emit(T, g, n, ml[n].x, ml[n].y, q, o_mu, o_scale, o_log_scale, o_rate, ostride);
     }
 }
 
@@ -302,7 +514,18 @@ extern "C" int ccmi_arm_mlp_f32(const float *ctx, int64_t m, int dim_arm, int n_
     return CCMI_OK;
 }
 
-int ccmi_launch_arm_f32(const ccmi_arm_args *a, hipStream_t s)
+extern "C" int ccmi_arm_pack_host(const float *params, int dim_arm, int n_hidden, float *out)
+{
+    if (!params || !out || dim_arm < 1 || n_hidden < 0) return -1;
+    const int n = ccmi_fwd::arm_pack_stride(dim_arm, n_hidden);
+    for (int t = 0; t < n; ++t) {
+        const int s = ccmi_fwd::arm_pack_src(dim_arm, n_hidden, t);
+        out[t] = s >= 0 ? params[s] : 0.f;
+    }
+    return n;
+}
+
+int ccmi_launch_arm_f32(const ccmi_arm_args *a, hipStream_t s, int form)
 {
     ArmGeom g{};
     g.n = a->n_grids;
@@ -320,6 +543,44 @@ int ccmi_launch_arm_f32(const ccmi_arm_args *a, hipStream_t s)
     if ((a->latent_stride != 0 && a->latent_stride < off) || a->out_stride < off)
         return ccmi_set_error(CCMI_ERR_ARG, "arm: stride smaller than the %d latents of a frame", off);
     dim3 grid((unsigned)(tiles * a->batch));
+
+    // pairs form (dim_arm 8 and 16): pack the weights on this stream, then the kernel that reads
+    // the copy.  Without a buffer (none may be allocated while the stream captures) form 0 runs
+    // the row form below.
+    const bool has_pairs = a->dim_arm == 8 || a->dim_arm == 16;
+    if (form == CCMI_ARM_FORM_PAIRS && !has_pairs)
+        return ccmi_set_error(CCMI_ERR_UNSUPPORTED, "arm: the pairs form needs dim_arm 8 or 16 (got %d)", a->dim_arm);
+    if (form != CCMI_ARM_FORM_ROWS && has_pairs) {
+        const int pks = ccmi_fwd::arm_pack_stride(a->dim_arm, a->n_hidden);
+        const int frames = a->param_stride ? a->batch : 1; // stride 0: one model shared by all frames
+        float *pk = nullptr;
+        if (int rc = ccmi_arm_pack_buffer((size_t)frames * pks * sizeof(float), s, &pk)) return rc;
+        if (!pk && form == CCMI_ARM_FORM_PAIRS)
+            return ccmi_set_error(CCMI_ERR_UNSUPPORTED, "arm: no packed-weight buffer for this stream while it captures");
+        if (pk) {
+            hipLaunchKernelGGL(arm_pack_kernel, dim3(frames), dim3(kThreads), 0, s, a->params, a->param_stride, a->dim_arm,
+                               a->n_hidden, pk, pks);
+#define CCMI_ARM_PAIRS(DD, NN)                                                                                        \
+    do {                                                                                                              \
+        auto kern = a->quantize ? arm_fwd_pairs_kernel<DD, NN, true> : arm_fwd_pairs_kernel<DD, NN, false>;          \
+        hipLaunchKernelGGL(kern, grid, dim3(kThreads), 0, s, a->latent, a->latent_stride, g, a->gain, a->quantize,   \
+                           a->n_hidden, pk, a->param_stride ? pks : 0, a->mu, a->scale, a->log_scale, a->rate,       \
+                           a->out_stride);                                                                           \
+    } while (0)
+            // quantised latents (integers): the scaled ReLU
+            if (a->dim_arm == 8) {
+                if (a->n_hidden == 2) CCMI_ARM_PAIRS(8, 2);
+                else CCMI_ARM_PAIRS(8, -1);
+            } else {
+                if (a->n_hidden == 2) CCMI_ARM_PAIRS(16, 2);
+                else CCMI_ARM_PAIRS(16, -1);
+            }
+#undef CCMI_ARM_PAIRS
+            CCMI_HIP_CHECK(hipGetLastError());
+            return CCMI_OK;
+        }
+    }
+
 #define CCMI_ARM_LAUNCH(DD)                                                                                     \
     hipLaunchKernelGGL(arm_fwd_kernel<DD>, grid, dim3(kThreads), 0, s, a->latent, a->latent_stride, g, a->gain, \
                        a->quantize, a->n_hidden, a->params, a->param_stride, a->mu, a->scale, a->log_scale,     \

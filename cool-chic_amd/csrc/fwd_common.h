@@ -25,6 +25,35 @@ __device__ __forceinline__ int xcd_order(int i, int n)
     return (rem == 0 ? xcd * per : xcd * per - max(0, xcd - rem)) + (i >> 3);
 }
 
+// ---------------------------------------------------------------- packed ARM weights
+// The pairs form of the path-A ARM (fwd_arm.hip, arm_fwd_pairs_kernel) reads a transposed
+// copy of a frame's ARM parameters, so that the weights of two neighbouring output units for
+// one input are an aligned pair of one scalar row load.  Per frame, in floats:
+//   hidden layer l at l * arm_pack_layer(d): rows i = 0 .. d-1 of arm_pack_row(d) floats,
+//     row i = Wt[i][j] = W_l[j][i] for j < d (the d weights that multiply input i), then one
+//     row b_l[j];
+//   at n_hidden * arm_pack_layer(d): WoT[i][2] = (W_out[0][i], W_out[1][i]), 2 d floats, then
+//     b_out[2].
+// Every row and the output block start on a 64-byte boundary (a row is padded to 16 floats)
+// and the frame stride arm_pack_stride() is a multiple of 16 floats; padding is written as 0.
+constexpr int arm_pack_row(int d) { return (d + 15) & ~15; }
+constexpr int arm_pack_layer(int d) { return (d + 1) * arm_pack_row(d); }
+constexpr int arm_pack_stride(int d, int nh) { return (nh * arm_pack_layer(d) + 2 * d + 2 + 15) & ~15; }
+// Index in the public parameter block (ccmi_arm_args.params order) of the value stored at
+// position t < arm_pack_stride(d, nh) of the packed block; -1 for padding.
+__host__ __device__ constexpr int arm_pack_src(int d, int nh, int t)
+{
+    const int rs = arm_pack_row(d), ls = arm_pack_layer(d), lp = d * d + d;
+    if (t < nh * ls) {
+        const int l = t / ls, r = t - l * ls, i = r / rs, j = r - i * rs;
+        if (j >= d) return -1;
+        return l * lp + (i < d ? j * d + i : d * d + j);
+    }
+    const int u = t - nh * ls;
+    if (u < 2 * d) return nh * lp + (u & 1) * d + (u >> 1);
+    return u < 2 * d + 2 ? nh * lp + u : -1;
+}
+
 // ---------------------------------------------------------------- synthesis plan
 constexpr int kMaxIn = 8;    // fused path: max synthesis input channels
 constexpr int kMaxMid = 4;   // fused path: max channels through the 3x3 layers

@@ -48,7 +48,7 @@ constexpr int kThreads = 256;
 //    the image or outside the stage's valid band are computed but never stored, which keeps
 //    control flow uniform.
 // window height (and threads per workgroup) overridable at build time for the window-size
-// A/B of DESIGN.md 7 (tools/ab_fused_window.sh); the product build uses 32 rows, 512 threads
+// A/B of DESIGN.md 7 (profiles/r4c_fused_window_ab.txt); the product build uses 32 rows, 512 threads
 #ifndef CCMI_FUSED_RH
 #define CCMI_FUSED_RH 32
 #endif

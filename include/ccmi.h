@@ -74,6 +74,36 @@ typedef struct ccmi_arm_args {
 } ccmi_arm_args;
 int ccmi_arm_forward_f32(const ccmi_arm_args *args, void *stream);
 
+/* The same call with the kernel form named.  Both forms give the same bits.
+ *   CCMI_ARM_FORM_DEFAULT: the pairs form where it exists and a buffer is at hand, else the row form;
+ *   CCMI_ARM_FORM_ROWS:    the row form (one output unit of two latents per packed register), reads
+ *                          args->params directly; every dim_arm;
+ *   CCMI_ARM_FORM_PAIRS:   the pairs form (two output units of one latent per packed register;
+ *                          dim_arm 8 and 16), CCMI_ERR_UNSUPPORTED where it cannot run.
+ * ccmi_arm_forward_f32 is the call with CCMI_ARM_FORM_DEFAULT.
+ *
+ * The pairs form reads a transposed copy of the parameters, written by one small launch on `stream`
+ * ahead of the ARM kernel on every call (params may change between calls), into a device buffer the
+ * library owns:
+ *  - one buffer per (device, stream), grown on demand; calls on one stream are ordered by the
+ *    stream, so they share it.  Two graphs captured on one stream share it too: replay them one
+ *    after the other, not concurrently;
+ *  - a buffer that was handed to a launch is neither freed nor moved before the library unloads (a
+ *    captured graph may hold its address);
+ *  - nothing is allocated while `stream` is capturing.  If the stream has no buffer of sufficient
+ *    size by then, CCMI_ARM_FORM_DEFAULT runs the row form (CCMI_ARM_FORM_PAIRS fails): make one
+ *    eager call of the same shape on the stream before capturing, as a capture needs anyway. */
+#define CCMI_ARM_FORM_DEFAULT 0
+#define CCMI_ARM_FORM_ROWS 1
+#define CCMI_ARM_FORM_PAIRS 2
+int ccmi_arm_forward_f32_form(const ccmi_arm_args *args, void *stream, int form);
+/* The transposed copy of one frame's parameters, on the host (the permutation the device copy
+ * applies): writes and returns the number of floats of the packed block, a multiple of 16; -1 on a
+ * bad argument.  Layout: every row Wt[i][0..d) (the weights that multiply input i), then b[d], per
+ * hidden layer, each row padded with zeros to 16 floats; then (W_out[0][i], W_out[1][i]) for
+ * i < d, b_out[2], zeros. */
+int ccmi_arm_pack_host(const float *params, int dim_arm, int n_hidden, float *out);
+
 /* Standalone pieces of the ARM for API parity with the reference modules (the fused
  * ccmi_arm_forward_f32 is what CoolChicEncoder.forward uses):
  *  ccmi_arm_context_f32: _get_neighbor (arm.py:308-352), grids [batch][h][w] -> [batch][h*w][dim_arm]
