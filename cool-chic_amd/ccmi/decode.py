@@ -49,6 +49,10 @@ _PROTOS = {
     "ccmi_decode_batch_dev_col": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _Z, _P],
     "ccmi_latents_render_col_plan": [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
     "ccmi_latents_render_col": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _Z, _P],
+    "ccmi_decode_batch_dev_flt_plan": [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "ccmi_decode_batch_dev_flt": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _Z, _P],
+    "ccmi_latents_render_flt_plan": [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "ccmi_latents_render_flt": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _Z, _P],
     "ccmi_latents_plan": [_P, _P, _I, _I, _P, _P, _P],
     "ccmi_latents_decode": [_P, _P, _I, _I, _P, _Z, _P, _Z, _P, _P],
     "ccmi_latents_free": [_P],
@@ -570,6 +574,95 @@ def colour_jitter(n: int, brightness: float = 0.0, contrast: float = 0.0, satura
     return out
 
 
+FLT_MAX_RADIUS = 15
+
+
+class Filter(C.Structure):
+    """ccmi_filter: the per-frame radii, the flat half taps and the per-frame solarize thresholds."""
+    _fields_ = [("radius", C.c_void_p), ("taps", C.c_void_p), ("solarize", C.c_void_p)]
+
+
+def _filter(blur, solarize, n):
+    """blur= / solarize= of a *_model call -> (ccmi_filter, what it points to), or (None, None) with
+    both None.  blur: one entry for every frame, or one per frame; an entry is None (no blur) or a 1-D
+    float32 array of half taps w_0 (centre) .. w_r.  solarize: None, one threshold for every frame, or
+    one per frame (None or a value above 1: off).  The library checks the values; the shapes are
+    checked here."""
+    import numpy as np
+    if blur is None and solarize is None:
+        return None, None
+    if blur is None:
+        entries = [None] * n
+    elif isinstance(blur, (list, tuple)) and (len(blur) == 0 or blur[0] is None or hasattr(blur[0], "__len__")):
+        entries = list(blur)  # one per frame
+    else:
+        entries = [blur] * n  # one array of taps for all frames
+    if len(entries) != n:
+        raise ValueError(f"model output: blur takes one entry, or one per frame ({n}), got {len(entries)}")
+    taps = []
+    for e in entries:
+        t = np.zeros(0, dtype=np.float32) if e is None else np.asarray(e, dtype=np.float32)
+        if t.ndim != 1 or t.size - 1 > FLT_MAX_RADIUS:
+            raise ValueError(f"model output: a blur entry is None or 1 .. {FLT_MAX_RADIUS + 1} half taps, got shape "
+                             f"{tuple(t.shape)}")
+        taps.append(t if t.size > 1 else t[:0])  # a centre tap alone is radius 0: no blur
+    radius = np.fromiter((max(t.size - 1, 0) for t in taps), dtype=np.int32, count=n)
+    flat = np.ascontiguousarray(np.concatenate(taps + [np.zeros(1, dtype=np.float32)]), dtype=np.float32)
+    th = None
+    if solarize is not None:
+        s = [solarize] * n if not hasattr(solarize, "__len__") else list(solarize)
+        if len(s) != n:
+            raise ValueError(f"model output: solarize takes one threshold, or one per frame ({n}), got {len(s)}")
+        th = np.array([2.0 if v is None else float(v) for v in s], dtype=np.float32)
+    flt = Filter(radius=radius.ctypes.data, taps=flat.ctypes.data, solarize=None if th is None else th.ctypes.data)
+    return flt, (radius, flat, th)
+
+
+def gaussian_taps(sigma: float, kernel_size: int):
+    """The half taps w_0 (centre) .. w_r, r = (kernel_size - 1) / 2, of torchvision's Gaussian kernel
+    (_get_gaussian_kernel1d, restated in torch CPU float32 operations): half = (k - 1) 0.5,
+    x = linspace(-half, half, k), pdf = exp(-0.5 (x / sigma)^2), pdf / pdf.sum().  A float32 numpy
+    array for blur= of the *_model calls; raises if the full kernel is not symmetric bit for bit."""
+    import torch
+    k = int(kernel_size)
+    if k < 1 or k % 2 == 0 or (k - 1) // 2 > FLT_MAX_RADIUS:
+        raise ValueError(f"gaussian_taps: kernel_size {kernel_size} (odd, 1 .. {2 * FLT_MAX_RADIUS + 1})")
+    if not sigma > 0:
+        raise ValueError(f"gaussian_taps: sigma {sigma}")
+    half = (k - 1) * 0.5
+    x = torch.linspace(-half, half, steps=k, dtype=torch.float32)
+    pdf = torch.exp(-0.5 * (x / float(sigma)).pow(2))
+    kern = pdf / pdf.sum()
+    if not torch.equal(kern, kern.flip(0)):
+        raise ValueError(f"gaussian_taps: the kernel of sigma {sigma}, size {k} is not symmetric in float32")
+    return kern[k // 2:].contiguous().numpy()
+
+
+def gaussian_blur(n: int, kernel_size: int, sigma=(0.1, 2.0), p: float = 1.0, generator=None) -> list:
+    """n blur entries (blur= of the *_model calls) drawn as torchvision's GaussianBlur under
+    RandomApply(p) draws them: with probability p a frame gets gaussian_taps(s, kernel_size) with s in
+    U[sigma[0], sigma[1]], else None.  generator: a torch.Generator (CPU); the same seed gives the
+    same list."""
+    import torch
+    lo, hi = (float(sigma), float(sigma)) if not hasattr(sigma, "__len__") else (float(sigma[0]), float(sigma[1]))
+    if not 0 < lo <= hi:
+        raise ValueError(f"gaussian_blur: sigma {sigma}")
+    out = []
+    for _ in range(n):
+        u = torch.rand(2, generator=generator, dtype=torch.float64).tolist()
+        out.append(gaussian_taps(lo + (hi - lo) * u[1], kernel_size) if u[0] < p else None)
+    return out
+
+
+def random_solarize(n: int, threshold: float = 0.5, p: float = 0.2, generator=None) -> list:
+    """n solarize thresholds (solarize= of the *_model calls) drawn as torchvision's RandomSolarize
+    draws them: with probability p a frame gets `threshold`, else None (off).  generator: a
+    torch.Generator (CPU); the same seed gives the same list."""
+    import torch
+    u = torch.rand(n, generator=generator, dtype=torch.float64).tolist()
+    return [float(threshold) if v < p else None for v in u]
+
+
 def last_tail_groups() -> tuple:
     """(batched tail groups, per-frame tails) this thread's last decode or render call launched
     (ccmi_decode_last_tail_groups): frames that share a group share one launch per tail stage."""
@@ -648,15 +741,20 @@ def _model_outs(geom, fmt, dtype, channels_last, out, dev):
 
 
 def _plan_model(plan, head, n, rects, fmt, rs, output_bitdepth, output_chroma_format, warp=None, info=None,
-                window=None, col=None):
+                window=None, col=None, flt=None):
     """(ccmi_frame_geom array, workspace bytes) of a formatted call: plan is the source's *_rs_plan
     entry point (rs None: exactly the *_fmt_plan call), head its first two arguments.  With warp
     (a ccmi_warp) plan is the *_warp_plan entry point, which takes no regions; info / window: its
     optional per-frame outputs.  With col (a ccmi_colour) plan is the *_col_plan entry point, which
-    takes all of them."""
+    takes all of them; with flt (a ccmi_filter) the *_flt_plan entry point, which takes col (or None)
+    and flt."""
     geom, need = (FrameGeom * n)(), C.c_size_t(0)
     probe = TensorFmt.from_buffer_copy(fmt)  # planar strides: the geometry does not depend on them
-    if col is not None:
+    if flt is not None:
+        check(plan(*head, n, None if warp is not None else rects, output_bitdepth, output_chroma_format, C.byref(probe),
+                   None if warp is not None else rs, None if warp is None else C.byref(warp),
+                   None if col is None else C.byref(col), C.byref(flt), geom, info, window, C.byref(need)))
+    elif col is not None:
         check(plan(*head, n, None if warp is not None else rects, output_bitdepth, output_chroma_format, C.byref(probe),
                    None if warp is not None else rs, None if warp is None else C.byref(warp), C.byref(col), geom, info,
                    window, C.byref(need)))
@@ -669,20 +767,25 @@ def _plan_model(plan, head, n, rects, fmt, rs, output_bitdepth, output_chroma_fo
 
 
 def _run_model(plan, run, head, n, rects, dev, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth,
-               output_chroma_format, workspace, stream_handle, size, warp=None, col=None):
+               output_chroma_format, workspace, stream_handle, size, warp=None, col=None, flt=None):
     """The body of decode_batch_model and LatentStore.render_model: plan / run are the source's
     *_rs_plan / *_rs entry points, or with warp (a ccmi_warp, which carries the size) its
-    *_warp_plan / *_warp ones, or with col (a ccmi_colour) its *_col_plan / *_col ones; head their
-    first two arguments; dev None: the current device."""
+    *_warp_plan / *_warp ones, or with col (a ccmi_colour) its *_col_plan / *_col ones, or with flt (a
+    ccmi_filter) its *_flt_plan / *_flt ones; head their first two arguments; dev None: the current
+    device."""
     import torch
     dtype = torch.float32 if dtype is None else dtype
     fmt, keep = _model_fmt(n, colour, mean, std, dtype, mirror)
     rs = None if size is None or warp is not None else C.byref(_resample(size))
-    geom, need = _plan_model(plan, head, n, rects, fmt, rs, output_bitdepth, output_chroma_format, warp, col=col)
+    geom, need = _plan_model(plan, head, n, rects, fmt, rs, output_bitdepth, output_chroma_format, warp, col=col, flt=flt)
     dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else dev
     res, op, cap, frames = _model_outs(geom, fmt, dtype, channels_last, out, dev)
     stream_handle, workspace = _stream_ws(dev, stream_handle, workspace, need)
-    if col is not None:
+    if flt is not None:
+        check(run(*head, n, None if warp is not None else rects, op, cap, C.byref(fmt), None if warp is not None else rs,
+                  None if warp is None else C.byref(warp), None if col is None else C.byref(col), C.byref(flt),
+                  output_bitdepth, output_chroma_format, workspace.data_ptr(), workspace.numel(), stream_handle))
+    elif col is not None:
         check(run(*head, n, None if warp is not None else rects, op, cap, C.byref(fmt), None if warp is not None else rs,
                   None if warp is None else C.byref(warp), C.byref(col), output_bitdepth, output_chroma_format,
                   workspace.data_ptr(), workspace.numel(), stream_handle))
@@ -699,7 +802,7 @@ def _run_model(plan, run, head, n, rects, dev, colour, mean, std, dtype, channel
 def decode_batch_model(streams: Sequence[bytes], roi=None, colour: str = "rgb", mean=None, std=None, dtype=None,
                        channels_last: bool = False, mirror=None, out=None, output_bitdepth: int = 0,
                        output_chroma_format: int = 0, workspace=None, stream_handle: int | None = None, size=None,
-                       affine=None, pad: str = "fill", fill=0.0, colour_ops=None):
+                       affine=None, pad: str = "fill", fill=0.0, colour_ops=None, blur=None, solarize=None):
     """Decode .cool streams into the tensor a model takes (ccmi_decode_batch_dev_fmt): one
     [n, 3, h, w] tensor of `dtype` (torch.float32, the default, torch.float16 or torch.bfloat16),
     every channel at full size (420 chroma nearest-upsampled), RGB (colour="rgb": YUV streams go
@@ -738,12 +841,27 @@ def decode_batch_model(streams: Sequence[bytes], roi=None, colour: str = "rgb", 
     with f >= 0 (at most one contrast op per frame: it blends with the frame's mean grey, which a
     statistics pass of the output stage sums in fixed point), ('matrix', M) with M a [3, 4] matrix
     (hue_matrix(), grey_matrix()).  Every op clamps to [0, 1].  colour_jitter() draws such lists.
-    Frames with different ops, or none, share the tail's launches.  None or []: the call without."""
+    Frames with different ops, or none, share the tail's launches.  None or []: the call without.
+
+    blur= / solarize= (ccmi_decode_batch_dev_flt; with or without everything above): after the colour
+    ops and before the normalisation (the contract's steps 3y-0 .. 3y-2), on the frame as it is stored
+    (after mirror).  blur: one entry for every frame or one per frame, an entry None or a 1-D float32
+    array of half taps w_0 (centre) .. w_r, r <= 15 (gaussian_taps() makes one, gaussian_blur() draws
+    them): a separable blur with reflecting borders, clamped to [0, 1].  solarize: None, one threshold
+    for every frame or one per frame (None or above 1: off): v >= threshold becomes 1 - v.  The frames
+    that take neither go through the kernels of the call without; the others are staged in float32 in
+    the workspace and share one launch of the filter kernel per tail group."""
     n = len(streams)
     keep, sp, ln = _marshal(streams)
     L = _bind()
     warp, keep_w = _warp(affine, n, size, roi, pad, fill)
     col, keep_c = _colour(colour_ops, n)
+    flt, keep_f = _filter(blur, solarize, n)
+    if flt is not None:
+        return _run_model(L.ccmi_decode_batch_dev_flt_plan, L.ccmi_decode_batch_dev_flt, (sp, ln), n,
+                          None if warp is not None else _rects(roi, streams, n), None, colour, mean, std, dtype,
+                          channels_last, mirror, out, output_bitdepth, output_chroma_format, workspace, stream_handle, size,
+                          warp, col, flt)
     if col is not None:
         return _run_model(L.ccmi_decode_batch_dev_col_plan, L.ccmi_decode_batch_dev_col, (sp, ln), n,
                           None if warp is not None else _rects(roi, streams, n), None, colour, mean, std, dtype,
@@ -1145,18 +1263,24 @@ class LatentStore:
     def render_model(self, index=None, roi=None, colour: str = "rgb", mean=None, std=None, dtype=None,
                      channels_last: bool = False, mirror=None, out=None, output_bitdepth: int = 0,
                      output_chroma_format: int = 0, workspace=None, stream_handle: int | None = None, size=None,
-                     affine=None, pad: str = "fill", fill=0.0, colour_ops=None):
+                     affine=None, pad: str = "fill", fill=0.0, colour_ops=None, blur=None, solarize=None):
         """render() into the tensor a model takes (ccmi_latents_render_fmt; with size
         ccmi_latents_render_rs; with affine ccmi_latents_render_warp): frames and regions as for
         render(), the result and every other argument as for decode_batch_model, whose output for
         the same streams and arguments it equals bit for bit.  workspace with a size or an affine:
         at least what render_model_workspace_bytes() reports (the resample's intermediate and a
         warp's windows are not part of render_geometry()'s figure).  With colour_ops
-        ccmi_latents_render_col: render_model_workspace_bytes() takes the same argument."""
+        ccmi_latents_render_col, with blur or solarize ccmi_latents_render_flt:
+        render_model_workspace_bytes() takes the same arguments."""
         m, idx, rects = self._frames(index, None if affine is not None else roi)
         L = _bind()
         warp, keep_w = _warp(affine, m, size, roi, pad, fill)
         col, keep_c = _colour(colour_ops, m)
+        flt, keep_f = _filter(blur, solarize, m)
+        if flt is not None:
+            return _run_model(L.ccmi_latents_render_flt_plan, L.ccmi_latents_render_flt, (self._handle(), idx), m, rects,
+                              self._store.device, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth,
+                              output_chroma_format, workspace, stream_handle, size, warp, col, flt)
         if col is not None:
             return _run_model(L.ccmi_latents_render_col_plan, L.ccmi_latents_render_col, (self._handle(), idx), m, rects,
                               self._store.device, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth,
@@ -1189,17 +1313,24 @@ class LatentStore:
 
     def render_model_workspace_bytes(self, index=None, roi=None, size=None, output_bitdepth: int = 0,
                                      output_chroma_format: int = 0, affine=None, pad: str = "fill", fill=0.0,
-                                     colour_ops=None) -> int:
+                                     colour_ops=None, blur=None, solarize=None) -> int:
         """Header-only: the workspace render_model needs for these frames, regions and size, or
         these frames, matrices and size (ccmi_latents_render_rs_plan / _warp_plan; the element type,
-        colour and strides do not change it), and these colour ops (ccmi_latents_render_col_plan:
-        the op tables and the contrast ops' accumulators)."""
+        colour and strides do not change it), these colour ops (ccmi_latents_render_col_plan:
+        the op tables and the contrast ops' accumulators) and this blur and solarize
+        (ccmi_latents_render_flt_plan: a float32 staging frame and 256 bytes of tables per frame
+        that takes the stage)."""
         m, idx, rects = self._frames(index, None if affine is not None else roi)
         fmt = TensorFmt(elem=ELEM_F32, colour=COLOUR_ASIS)
         for c in range(3):
             fmt.scale[c] = 1.0
         warp, keep_w = _warp(affine, m, size, roi, pad, fill)
         col, keep_c = _colour(colour_ops, m)
+        flt, keep_f = _filter(blur, solarize, m)
+        if flt is not None:
+            rs = None if size is None or warp is not None else C.byref(_resample(size))
+            return _plan_model(_bind().ccmi_latents_render_flt_plan, (self._handle(), idx), m, rects, fmt, rs,
+                               output_bitdepth, output_chroma_format, warp, col=col, flt=flt)[1]
         if col is not None:
             rs = None if size is None or warp is not None else C.byref(_resample(size))
             return _plan_model(_bind().ccmi_latents_render_col_plan, (self._handle(), idx), m, rects, fmt, rs,
@@ -1233,4 +1364,5 @@ class LatentStore:
 __all__ = ["last_timing", "LatentStore", "last_arm_flags", "decode_latents", "decode_file", "decode_batch", "decode_batch_workspace_bytes", "output_size",
            "decode_batch_tensors", "decode_batch_geometry", "roi_plan", "decode_batch_model", "last_tail_groups",
            "affine_matrix", "hue_matrix", "grey_matrix", "colour_jitter",
+           "gaussian_taps", "gaussian_blur", "random_solarize",
            "weights_i32", "ups_forward_i32", "syn_forward_i32", "CcmiError"]

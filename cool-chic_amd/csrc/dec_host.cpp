@@ -357,6 +357,9 @@ struct TailGroup {
     int chunk;
     std::vector<const DecTailFrame *> frames; // table order
     size_t off;                               // of the group's table, from DecodePlan::tail_off
+    // ccmi_filter: the group's last n_flt frames take the stage; their tables, from DecodePlan::flt_tab_off
+    int n_flt = 0;
+    size_t flt_off = 0;
 };
 
 // State of one decode_run.  The host vectors are what the asynchronous uploads read.
@@ -385,6 +388,7 @@ struct Run {
     };
     std::vector<LatLaunch> lat;
     size_t lat_tab() const { return pl.lat_tab_off - pl.tail_off; } // of the job table in `tab`
+    size_t flt_tab() const { return pl.flt_tab_off - pl.tail_off; } // of the filter stage's tables in `tab`
     uint32_t *status() const { return reinterpret_cast<uint32_t *>(dev + pl.status_off); }
 };
 
@@ -521,6 +525,7 @@ int build_tail_groups(Run &r)
         t.rs_tmp = p.rs_elems ? reinterpret_cast<float *>(r.dev + p.rs_off) : nullptr;
         if (t.fmt.col && r.pl.cols[i].contrast >= 0)
             r.pl.cols[i].acc = reinterpret_cast<unsigned long long *>(r.dev + r.pl.col_off) + i;
+        t.flt_tmp = p.flt_elems ? reinterpret_cast<float *>(r.dev + p.flt_off) : nullptr;
         if (!p.batchable) continue;
         const int c = r.chunk_of[i];
         auto it = std::find_if(r.tails.begin(), r.tails.end(), [&](const TailGroup &g) {
@@ -533,11 +538,17 @@ int build_tail_groups(Run &r)
         it->frames.push_back(&t);
     }
     if (r.tab.size() < r.pl.tail_cap + 1) r.tab.resize(r.pl.tail_cap + 1);
-    size_t tpos = 0;
+    size_t tpos = 0, fpos = 0;
     for (TailGroup &g : r.tails) {
         const int m = (int)g.frames.size();
         g.off = tpos;
-        dec_tail_fill(g.frames.data(), m, r.tab.data() + tpos);
+        if (r.pl.n_flt) { // the frames that take the filter stage last, in their order: they run as their own launches
+            auto staged = std::stable_partition(g.frames.begin(), g.frames.end(), [](const DecTailFrame *f) { return !f->flt; });
+            g.n_flt = (int)(g.frames.end() - staged);
+            g.flt_off = fpos;
+            fpos += kFltTableBytes * (size_t)g.n_flt;
+        }
+        dec_tail_fill(g.frames.data(), m, r.tab.data() + tpos, g.n_flt, r.tab.data() + r.flt_tab() + g.flt_off);
         tpos += dec_tail_table_bytes(g.frames[0]->ups.n_layers, m, g.frames[0]->windowed, dec_out_form(g.frames[0]->fmt),
                                      g.frames[0]->fmt.col != 0);
     }
@@ -651,6 +662,7 @@ int launch_frame_tail(const Run &r, const FramePlan &p, hipStream_t cs)
                                           b == 1, cs))
                 return rc;
     }
+    if (t.flt) return launch_dec_out_frame_flt(t, synout, f.h, f.w, cs); // staged, then the filter kernel
     return launch_dec_out_frame(t, synout, f.h, f.w, p.mode == kTailCrop, r.rq.device(), cs);
 }
 
@@ -671,7 +683,8 @@ int launch_chunk(const Run &r, int c, hipStream_t cs, hipEvent_t arm_done)
         return launch_lat(r, r.lat[c], cs);
     for (const TailGroup &g : r.tails)
         if (g.chunk == c)
-            if (int rc = launch_dec_tail_batch(g.frames.data(), (int)g.frames.size(), r.dev + r.pl.tail_off + g.off, cs))
+            if (int rc = launch_dec_tail_batch(g.frames.data(), (int)g.frames.size(), r.dev + r.pl.tail_off + g.off, cs,
+                                               g.n_flt, r.dev + r.pl.flt_tab_off + g.flt_off))
                 return rc;
     for (size_t i = 0; i < r.pl.fr.size(); ++i)
         if (!r.pl.fr[i].batchable && r.chunk_of[i] == c)
@@ -873,11 +886,12 @@ int decode_run(const DecodeRequest &rq, DecodePlan &pl, hipStream_t s)
     if (!render)
         if (int rc = build_arm_groups(r)) return rc;
     // the tables of the call: the tail groups', then the latent store's jobs, in one copy
-    r.tab.assign(r.lat_tab() + pl.lat_tab_cap + 1, 0);
+    r.tab.assign(std::max(r.lat_tab() + pl.lat_tab_cap, r.flt_tab() + kFltTableBytes * (size_t)pl.n_flt) + 1, 0);
     if (!rq.lat_store)
         if (int rc = build_tail_groups(r)) return rc;
     if (rq.lat_store) build_pack_jobs(r);
     if (render) build_unpack_jobs(r);
+    if (pl.n_flt) r.tab_used = r.flt_tab() + kFltTableBytes * (size_t)pl.n_flt; // the filter stage's tables end the image
     if (r.tab_used)
         CCMI_HIP_CHECK(hipMemcpyAsync(r.dev + pl.tail_off, r.tab.data(), r.tab_used, hipMemcpyHostToDevice, s));
     if (rq.lat_store) // the networks' integers: constant part -> store, before the chunks fork
@@ -1005,10 +1019,10 @@ extern "C" int ccmi_decode_batch_ws(const uint8_t *const *streams, const size_t 
 }
 
 // ------------------------------------------------------------------ device sinks
-// Twenty-four entry points over one table: the source is the caller's streams or a latent store, the
+// Twenty-eight entry points over one table: the source is the caller's streams or a latent store, the
 // sink plain samples (sample_type; with or without a region) or formatted ones (fmt, forced to
 // CCMI_SAMPLE_F32, the call whose output kernel the format replaces; with or without a resample,
-// or with a warp, which takes no region),
+// or with a warp, which takes no region; with or without colour ops and a filter),
 // and each comes as a plan and as a run.  `who` is the entry point's name for the error text,
 // `missing` its own null-argument check beyond the source's.
 struct Sink {
@@ -1018,6 +1032,7 @@ struct Sink {
     const ccmi_resample *rs;
     const ccmi_warp *warp;
     const ccmi_colour *colour;
+    const ccmi_filter *filter = nullptr;
 };
 
 static Sink samples(const ccmi_rect *roi, int sample_type) { return Sink{roi, sample_type, nullptr, nullptr, nullptr, nullptr}; }
@@ -1039,6 +1054,13 @@ static Sink coloured(const ccmi_rect *roi, const ccmi_tensor_fmt *fmt, const ccm
     return Sink{roi, CCMI_SAMPLE_F32, fmt, rs, warp, colour};
 }
 
+// ... and a per-frame blur / solarize after the colour ops
+static Sink filtered(const ccmi_rect *roi, const ccmi_tensor_fmt *fmt, const ccmi_resample *rs, const ccmi_warp *warp,
+                     const ccmi_colour *colour, const ccmi_filter *filter)
+{
+    return Sink{roi, CCMI_SAMPLE_F32, fmt, rs, warp, colour, filter};
+}
+
 static void set_sink(DecodeRequest &rq, const Sink &k)
 {
     rq.sample = k.sample;
@@ -1047,6 +1069,7 @@ static void set_sink(DecodeRequest &rq, const Sink &k)
     rq.rs = k.rs;
     rq.warp = k.warp;
     rq.colour = k.colour;
+    rq.filter = k.filter;
 }
 
 // streams as the source: null arguments, then the sample type, then the plan's own errors
@@ -1218,6 +1241,36 @@ extern "C" int ccmi_decode_batch_dev_col(const uint8_t *const *streams, const si
     DecodeRequest rq;
     if (int rc = stream_request("decode_batch_dev_col (frame 0)", streams, lens, n, coloured(roi, fmt, rs, warp, colour),
                                 out_bitdepth, out_chroma, !out_dev || !out_caps || !fmt || (warp && !warp->matrix), rq))
+        return rc;
+    return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
+}
+
+// The filtering sink: the colouring sink with a ccmi_filter (filter NULL: that call itself).
+extern "C" int ccmi_decode_batch_dev_flt_plan(const uint8_t *const *streams, const size_t *lens, int n,
+                                              const ccmi_rect *roi, int out_bitdepth, int out_chroma,
+                                              const ccmi_tensor_fmt *fmt, const ccmi_resample *rs, const ccmi_warp *warp,
+                                              const ccmi_colour *colour, const ccmi_filter *filter, ccmi_frame_geom *geom,
+                                              ccmi_roi_info *info, ccmi_rect *window, size_t *workspace_bytes)
+{
+    DecodeRequest rq;
+    if (int rc = stream_request("decode_batch_dev_flt_plan (frame 0)", streams, lens, n,
+                                filtered(roi, fmt, rs, warp, colour, filter), out_bitdepth, out_chroma,
+                                !fmt || (warp && !warp->matrix) || (window && !warp) || !geom || !workspace_bytes, rq))
+        return rc;
+    rq.window = window;
+    return sink_plan(rq, geom, info, workspace_bytes);
+}
+
+extern "C" int ccmi_decode_batch_dev_flt(const uint8_t *const *streams, const size_t *lens, int n, const ccmi_rect *roi,
+                                         void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
+                                         const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
+                                         const ccmi_filter *filter, int out_bitdepth, int out_chroma, void *workspace,
+                                         size_t workspace_bytes, void *stream)
+{
+    DecodeRequest rq;
+    if (int rc = stream_request("decode_batch_dev_flt (frame 0)", streams, lens, n,
+                                filtered(roi, fmt, rs, warp, colour, filter), out_bitdepth, out_chroma,
+                                !out_dev || !out_caps || !fmt || (warp && !warp->matrix), rq))
         return rc;
     return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
 }
@@ -1440,6 +1493,35 @@ extern "C" int ccmi_latents_render_col(const ccmi_latents *h, const int *index, 
     DecodeRequest rq;
     if (int rc = latents_request("latents_render_col (frame 0)", h, index, m, coloured(roi, fmt, rs, warp, colour),
                                  out_bitdepth, out_chroma, true, !out_dev || !out_caps || !fmt || (warp && !warp->matrix), rq))
+        return rc;
+    return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ccmi_latents_render_flt_plan(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
+                                            int out_bitdepth, int out_chroma, const ccmi_tensor_fmt *fmt,
+                                            const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
+                                            const ccmi_filter *filter, ccmi_frame_geom *geom, ccmi_roi_info *info,
+                                            ccmi_rect *window, size_t *workspace_bytes)
+{
+    DecodeRequest rq;
+    if (int rc = latents_request("latents_render_flt_plan (frame 0)", h, index, m,
+                                 filtered(roi, fmt, rs, warp, colour, filter), out_bitdepth, out_chroma, false,
+                                 !fmt || (warp && !warp->matrix) || (window && !warp) || !geom || !workspace_bytes, rq))
+        return rc;
+    rq.window = window;
+    return sink_plan(rq, geom, info, workspace_bytes);
+}
+
+extern "C" int ccmi_latents_render_flt(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
+                                       void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
+                                       const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
+                                       const ccmi_filter *filter, int out_bitdepth, int out_chroma, void *workspace,
+                                       size_t workspace_bytes, void *stream)
+{
+    DecodeRequest rq;
+    if (int rc = latents_request("latents_render_flt (frame 0)", h, index, m,
+                                 filtered(roi, fmt, rs, warp, colour, filter), out_bitdepth, out_chroma, true,
+                                 !out_dev || !out_caps || !fmt || (warp && !warp->matrix), rq))
         return rc;
     return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
 }

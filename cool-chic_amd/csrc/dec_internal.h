@@ -178,6 +178,19 @@ struct DecCol {
     DecColOp ops[CCMI_COL_MAX_OPS] = {};
 };
 
+// ccmi_filter of one frame that takes the stage (steps 3y-0 .. 3y-2 of the contract in ccmi.h),
+// validated and resolved by the plan.  The frame's geometry and colour kernels write it in the identity
+// format into `tmp`; the filter kernel (dec_filter.hip) reads it there and writes the caller's tensor.
+struct DecFlt {
+    int r = 0;       // radius; 0: solarize only
+    int sol = 0;     // the threshold acts (th <= 1)
+    float th = 0.f;
+    float taps[CCMI_FLT_MAX_RADIUS + 1] = {}; // w_0 .. w_r
+};
+// what the stage adds to the call's tables per staged frame: the frame's entry of the staging launch,
+// its filter entry and the taps in it (the workspace formula of ccmi.h)
+constexpr size_t kFltTableBytes = 256;
+
 // the form of a tail group's output section: the plain entry, or its resample / warp extension
 enum { kOutPlain = 0, kOutRs = 1, kOutWarp = 2 };
 inline int dec_out_form(const DecFmt &f) { return f.rs ? kOutRs : f.warp ? kOutWarp : kOutPlain; }
@@ -198,6 +211,10 @@ struct DecTailFrame {
     DecFmt fmt;      // fmt.on: the formatted tensor at dst instead (sample is then CCMI_SAMPLE_F32, unused)
     float *rs_tmp = nullptr; // fmt.rs: the frame's horizontal-pass intermediate, [3][region h][out_w]
     const DecCol *col = nullptr; // fmt.col: the frame's colour ops (n == 0: none), in DecodePlan::cols
+    // the frame takes the filter stage: its DecFlt (in DecodePlan::flts) and its float32 staging
+    // frame, [3][oh][ow] of the stored frame
+    const DecFlt *flt = nullptr;
+    float *flt_tmp = nullptr;
     // region decode on windows: the latent planes keep their frame pitch and hold roi.arm_rows[l]
     // rows, ups.workspace / ups.out / syn.out hold the windows roi.lev[k] / the region, compact
     // (pitch = the window's width); ups.lh / lw and syn.h / w stay the frame's true sizes
@@ -208,9 +225,12 @@ bool dec_tail_batchable(const DecTailFrame &f);
 bool dec_tail_same_group(const DecTailFrame &a, const DecTailFrame &b);
 // col: the group's frames carry a DecCol each, a fourth section of the table
 size_t dec_tail_table_bytes(int n_layers, int n, bool windowed = false, int out_form = kOutPlain, bool col = false);
-void dec_tail_fill(const DecTailFrame *const *fr, int n, void *host_tab);
+// n_flt: the LAST n_flt frames of the group take the filter stage (DecTailFrame::flt); flt_tab is
+// their part of the call's filter tables, kFltTableBytes per frame (dec_flt_fill)
+void dec_tail_fill(const DecTailFrame *const *fr, int n, void *host_tab, int n_flt = 0, void *host_flt_tab = nullptr);
 // fr: the group's frames, in table order (a window-form group sizes its grids by their windows)
-int launch_dec_tail_batch(const DecTailFrame *const *fr, int n, const void *dev_tab, hipStream_t s);
+int launch_dec_tail_batch(const DecTailFrame *const *fr, int n, const void *dev_tab, hipStream_t s, int n_flt = 0,
+                          const void *dev_flt_tab = nullptr);
 
 // The output stage (dec_out.hip), all the tail knows of it: synthesis output (12-bit, [3][h][w])
 // to file bytes (sample < 0; ccdecapi.cpp:59-240; kind 0 yuv420, 1 yuv444, 2 ppm payload), to the
@@ -232,6 +252,19 @@ int launch_dec_out_group(const DecTailFrame &f0, int h, int w, int n, const void
 // w even).  Planar: crop takes f.roi.rect, else device the whole frame; neither: file bytes.
 int launch_dec_out_frame(const DecTailFrame &f, const int32_t *synout, int h, int w, bool crop, bool device,
                          hipStream_t s);
+
+// The filter stage (dec_filter.hip).  The staged frames of a group, m of them, have their own tables,
+// kFltTableBytes per frame: [m] entries of the group's out_form for the staging launch (the frames'
+// entries with dst = the staging frame), then [m] filter entries.  dec_flt_fill writes frame i's of
+// both (host side; h, w, oy, ox as for dec_out_fill).
+void dec_flt_fill(void *flt_tab, int m, int i, const DecTailFrame &f, int h, int w, int oy, int ox);
+// The output stage of the m staged frames fr[0 .. m) of a group: the group's output kernels in the
+// identity format into the staging frames (h x w and col_sec as for launch_dec_out_group, col_sec
+// being the first staged frame's entry), then dec_filter_batch into the caller's tensors.
+int launch_dec_out_group_flt(const DecTailFrame *const *fr, int m, int h, int w, const void *dev_flt_tab,
+                             const DecCol *col_sec, hipStream_t s);
+// launch_dec_out_frame for a frame that takes the stage (f.flt): staged, then dec_filter.
+int launch_dec_out_frame_flt(const DecTailFrame &f, const int32_t *synout, int h, int w, hipStream_t s);
 
 // Latent store (dec_latents.hip): the ARM output planes (int32, value << kArmPrec) packed to
 // values of the store's element type (CCMI_LATENT_*), and back.  Both kernels are table-driven:

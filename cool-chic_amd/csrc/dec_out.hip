@@ -23,11 +23,12 @@
 
 #include "dec_device.h"
 #include "dec_internal.h"
+#include "dec_out_fmt.h"
 
 namespace ccmi {
 namespace {
 
-constexpr int kThreads = 256;
+constexpr int kThreads = kOutThreads;
 
 // a 12-bit synthesis value as a sample in 0 .. maxv: the rounding and the clamp of ccdecapi.cpp
 __device__ __forceinline__ int32_t smp(int32_t v, int maxv)
@@ -222,43 +223,8 @@ unsigned output_tensor_blocks(int h, int w, int kind)
 // sx == 1 (NCHW) a full group of an aligned channel is one packed store, and with sc == 1,
 // sx == 3 (NHWC) a full group's 12 elements are three; partial groups, channels whose rows are
 // not aligned alike, and every other stride set take one store per element.
-//
-// Every product and sum below is its own float32 operation: the library is built with the
-// compiler's default contraction, under which a * b + c may become one fused operation -- also
-// through __fmul_rn / __fadd_rn, which are plain inline operators in this toolchain's headers --
-// so the two helpers switch contraction off for their own instruction.
-__device__ __forceinline__ float fmt_mul(float a, float b)
-{
-#pragma clang fp contract(off)
-    return a * b;
-}
-__device__ __forceinline__ float fmt_add(float a, float b)
-{
-#pragma clang fp contract(off)
-    return a + b;
-}
-
-struct F16 {
-    _Float16 v;
-};
-struct Bf16 {
-    uint16_t bits;
-};
-template <typename T> struct FmtVec;
-template <> struct FmtVec<float> { using type = float4; };
-template <> struct FmtVec<F16> { using type = uint2; };
-template <> struct FmtVec<Bf16> { using type = uint2; };
-
-template <typename T> __device__ __forceinline__ T fmt_elem(float r);
-template <> __device__ __forceinline__ float fmt_elem<float>(float r) { return r; }
-template <> __device__ __forceinline__ F16 fmt_elem<F16>(float r) { return F16{(_Float16)r}; } // v_cvt_f16_f32, RNE
-template <> __device__ __forceinline__ Bf16 fmt_elem<Bf16>(float r)
-{
-    uint32_t u = __float_as_uint(r);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return Bf16{0x7fc0}; // NaN (a finite scale and bias make none)
-    u += 0x7fffu + ((u >> 16) & 1u); // round to nearest even
-    return Bf16{(uint16_t)(u >> 16)};
-}
+// The uncontracted float32 operations (fmt_mul, fmt_add), the element types and steps 4-6 for a
+// thread's group (fmt_group, fmt_store) are in dec_out_fmt.h, shared with the filter stage.
 
 // the float32 roundings of yuv2rgb's matrix (ccmi/io.py) and of its offsets / 255: R, G, B
 __device__ constexpr float kFmtA[3] = {(float)-0.000007154783816076815, (float)-0.3441331386566162, (float)1.7720025777816772};
@@ -266,14 +232,7 @@ __device__ constexpr float kFmtB[3] = {(float)1.4019975662231445, (float)-0.7141
 __device__ constexpr float kFmtO[3] = {(float)(-179.45477266423404 / 255.0), (float)(135.45870971679688 / 255.0),
                                        (float)(-226.8183044444304 / 255.0)};
 
-struct DecFmtCall { // one value per launch
-    float scale[3], bias[3];
-    int64_t sc, sy, sx;
-};
 enum { kFmtMirror = 1, kFmtMatrix = 2 }; // per-frame flags (DecOut::bps_or_flags of a formatted group)
-
-// groups of 4 destination pixels that cover one row plus the up to 3 lead-in slots
-__host__ __device__ inline int fmt_row_groups(int w) { return (w + 3 + 3) / 4; }
 
 // steps 1-3 of the contract for one pixel: lrow / crow point at the pixel's luma row and at the
 // row its chroma is taken from, x / xc are its luma and chroma columns
@@ -367,70 +326,6 @@ __device__ __forceinline__ DecFmtCall col_stat_call()
 {
     DecFmtCall C{};
     return C;
-}
-
-// step 6 for a thread's 4 destination pixels d0 .. d0 + 3 of the row at `row` elements (w pixels
-// wide): the packed stores where the layout and the alignment allow them
-template <typename T>
-__device__ __forceinline__ void fmt_store(const T (&v)[3][4], T *__restrict__ dst, const DecFmtCall &C, int64_t row,
-                                          int d0, int w, bool nchw, bool nhwc)
-{
-    using Vec = typename FmtVec<T>::type;
-    const bool full = d0 >= 0 && d0 + 4 <= w;
-    if (nchw) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            T *p = dst + c * C.sc + row + d0;
-            if (full && reinterpret_cast<uintptr_t>(p) % sizeof(Vec) == 0) {
-                Vec pk;
-                __builtin_memcpy(&pk, v[c], sizeof pk);
-                *reinterpret_cast<Vec *>(p) = pk;
-            } else {
-#pragma unroll
-                for (int k = 0; k < 4; ++k)
-                    if (d0 + k >= 0 && d0 + k < w) p[k] = v[c][k];
-            }
-        }
-    } else if (nhwc && full) { // aligned by the choice of mis
-        T e[12];
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) e[3 * k + c] = v[c][k];
-        Vec *p = reinterpret_cast<Vec *>(dst + row + 3 * (int64_t)d0);
-#pragma unroll
-        for (int j = 0; j < 3; ++j) {
-            Vec pk;
-            __builtin_memcpy(&pk, e + 4 * j, sizeof pk);
-            p[j] = pk;
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            if (d0 + k < 0 || d0 + k >= w) continue;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) dst[c * C.sc + row + (d0 + k) * C.sx] = v[c][k];
-        }
-    }
-}
-
-// the thread's row y and first destination pixel d0 of a w-wide row (see above); false: no work
-template <typename T>
-__device__ __forceinline__ bool fmt_group(const T *dst, const DecFmtCall &C, int h, int w, int &y, int &d0, int64_t &row,
-                                          bool &nchw, bool &nhwc)
-{
-    const int gpr = fmt_row_groups(w);
-    const int64_t g = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-    y = (int)(g / gpr);
-    if (y >= h) return false;
-    nchw = C.sx == 1, nhwc = !nchw && C.sc == 1 && C.sx == 3;
-    row = (int64_t)y * C.sy;
-    // elements from address 0 to (channel 0, y, x' = 0); group k starts mis slots before it, where
-    // the address of its first pixel is a multiple of 4 elements (NHWC: 3 mis == a0 mod 4)
-    const uint64_t a0 = (uint64_t)(reinterpret_cast<uintptr_t>(dst) / sizeof(T)) + (uint64_t)row;
-    const int mis = nchw ? (int)(a0 & 3) : nhwc ? (int)((3 * a0) & 3) : 0;
-    d0 = 4 * (int)(g - (int64_t)y * gpr) - mis;
-    return d0 < w;
 }
 
 // h x w = the region at (oy, ox) of the synthesis output syn (planes splane apart, pitch spitch;
@@ -530,14 +425,6 @@ __global__ __launch_bounds__(kThreads) void dec_output_fmt_stat_batch(const DecO
 unsigned output_fmt_blocks(int h, int w)
 {
     return (unsigned)(((int64_t)h * fmt_row_groups(w) + kThreads - 1) / kThreads);
-}
-
-DecFmtCall fmt_call(const DecFmt &f)
-{
-    DecFmtCall C;
-    for (int c = 0; c < 3; ++c) C.scale[c] = f.scale[c], C.bias[c] = f.bias[c];
-    C.sc = f.stride_c, C.sy = f.stride_y, C.sx = f.stride_x;
-    return C;
 }
 
 int fmt_flags(const DecFmt &f) { return (f.mirror ? kFmtMirror : 0) | (f.matrix ? kFmtMatrix : 0); }
@@ -911,20 +798,6 @@ static int with_sample_type(int sample, Launch &&launch)
     return CCMI_OK;
 }
 
-// launch(T{}) for the element type T of a formatted-output kernel
-template <typename Launch>
-static int with_elem_type(int elem, Launch &&launch)
-{
-    switch (elem) {
-    case CCMI_ELEM_F32: launch(float{}); break;
-    case CCMI_ELEM_F16: launch(F16{}); break;
-    case CCMI_ELEM_BF16: launch(Bf16{}); break;
-    default: return ccmi_set_error(CCMI_ERR_ARG, "dec: element type %d", elem);
-    }
-    CCMI_HIP_CHECK(hipGetLastError());
-    return CCMI_OK;
-}
-
 // dst as the kernel's element type: as(t, dst) inside a with_*_type launch
 template <typename T> static T *as(T, void *p) { return static_cast<T *>(p); }
 
@@ -1050,6 +923,12 @@ int launch_dec_out_frame(const DecTailFrame &f, const int32_t *syn, int h, int w
 }
 
 // ------------------------------------------------------------------ a tail group's output section
+// a staged frame's share of the filter stage's tables holds its entry here, rounded to 16, and its
+// 96-byte filter entry (dec_filter.hip)
+static_assert(sizeof(DecOut) <= sizeof(DecOutWarp) && sizeof(DecOutRs) <= sizeof(DecOutWarp) &&
+                  sizeof(DecOutWarp) + 16 + 96 <= kFltTableBytes,
+              "kFltTableBytes per staged frame");
+
 size_t dec_out_entry_bytes(int out_form)
 {
     return out_form == kOutRs ? sizeof(DecOutRs) : out_form == kOutWarp ? sizeof(DecOutWarp) : sizeof(DecOut);

@@ -223,6 +223,33 @@ int colour_ops(const ccmi_colour &cl, int i, size_t first, DecCol &d)
     return CCMI_OK;
 }
 
+// ccmi_filter of frame i, whose half taps start at `first` of the flat array: validated and resolved
+// into d; *takes = the frame takes the stage
+int filter_frame(const ccmi_filter &fl, int i, size_t first, DecFlt &d, bool *takes)
+{
+    const int r = fl.radius[i];
+    if (r < 0 || r > CCMI_FLT_MAX_RADIUS)
+        return ccmi_set_error(CCMI_ERR_ARG, "frame %d: blur radius %d (0 .. %d)", i, r, CCMI_FLT_MAX_RADIUS);
+    d = DecFlt{};
+    d.r = r;
+    if (r > 0) {
+        if (!fl.taps) return ccmi_set_error(CCMI_ERR_ARG, "frame %d: blur taps are NULL", i);
+        for (int k = 0; k <= r; ++k) {
+            if (!std::isfinite(fl.taps[first + k]))
+                return ccmi_set_error(CCMI_ERR_ARG, "frame %d: blur tap %d is not finite", i, k);
+            d.taps[k] = fl.taps[first + k];
+        }
+    }
+    if (fl.solarize) {
+        const float th = fl.solarize[i];
+        if (std::isnan(th)) return ccmi_set_error(CCMI_ERR_ARG, "frame %d: solarize threshold is NaN", i);
+        d.sol = th <= 1.0f;
+        d.th = th;
+    }
+    *takes = r > 0 || d.sol;
+    return CCMI_OK;
+}
+
 // the architecture part of a frame's tail arguments (no device pointers): what
 // dec_tail_batchable() looks at, the true plane sizes and the workspace sizes
 void tail_arch(const FrameHost &f, DecTailFrame &t)
@@ -432,6 +459,10 @@ void plan_layout(const DecodeRequest &rq, DecodePlan &pl)
             p.rs_off = tot;
             tot += align_up(p.rs_elems * 4, 256);
         }
+        if (p.flt_elems) {
+            p.flt_off = tot;
+            tot += align_up(p.flt_elems * 4, 256);
+        }
         p.out_off = tot;
         if (!rq.device()) tot += align_up(p.of.payload, 256); // device sinks write to the caller's memory
     }
@@ -452,6 +483,9 @@ void plan_layout(const DecodeRequest &rq, DecodePlan &pl)
         pl.lat_tab_cap += build ? sizeof(DecLatPackJob) * (size_t)(p.f.n_layers + 2)
                                 : render ? sizeof(DecLatUnpackJob) * (size_t)p.f.n_layers : 0;
     tot += align_up(pl.lat_tab_cap, 256);
+    // the filter stage's tables follow the job table in the same host image: the same upload
+    pl.flt_tab_off = tot;
+    tot += kFltTableBytes * (size_t)pl.n_flt;
     pl.col_off = tot;
     if (pl.col) tot += align_up(sizeof(unsigned long long) * pl.fr.size(), 256);
     pl.status_off = tot;
@@ -492,10 +526,33 @@ int decode_plan(const DecodeRequest &rq, DecodePlan &pl)
         }
     }
     if (!pl.col) pl.cols.clear(); // no op in any frame: the call without colour
+    std::vector<char> takes; // ccmi_filter: the frames that take the stage
+    if (rq.filter) { // every frame's filter next: a rejected one is reported before any frame is planned
+        if (!rq.fmt || !rq.filter->radius)
+            return ccmi_set_error(CCMI_ERR_ARG, "frame 0: a filter without %s", rq.fmt ? "its radii" : "a format");
+        size_t first = 0;
+        pl.flts.resize(rq.n);
+        takes.assign(rq.n, 0);
+        for (int i = 0; i < rq.n; ++i) {
+            bool t = false;
+            if (int rc = filter_frame(*rq.filter, i, first, pl.flts[i], &t)) return rc;
+            if (pl.flts[i].r > 0) first += (size_t)pl.flts[i].r + 1;
+            takes[i] = t;
+            pl.n_flt += t;
+        }
+    }
+    if (!pl.n_flt) pl.flts.clear(); // no frame takes the stage: the call without a filter
     for (int i = 0; i < rq.n; ++i) {
-        if (int rc = plan_frame(rq, i, pl.fr[i])) return rc;
-        pl.fr[i].tail.fmt.col = pl.col ? 1 : 0;
-        pl.fr[i].tail.col = pl.col ? &pl.cols[i] : nullptr;
+        FramePlan &p = pl.fr[i];
+        if (int rc = plan_frame(rq, i, p)) return rc;
+        p.tail.fmt.col = pl.col ? 1 : 0;
+        p.tail.col = pl.col ? &pl.cols[i] : nullptr;
+        if (pl.n_flt && takes[i]) { // staged at the size of the stored frame
+            const DecFmt &d = p.tail.fmt;
+            const bool sized = d.rs || d.warp;
+            p.tail.flt = &pl.flts[i];
+            p.flt_elems = 3 * (size_t)(sized ? d.out_h : p.tail.roi.rect.h()) * (size_t)(sized ? d.out_w : p.tail.roi.rect.w());
+        }
     }
     plan_layout(rq, pl);
     return CCMI_OK;

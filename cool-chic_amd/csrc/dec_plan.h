@@ -87,6 +87,9 @@ struct DecodeRequest {
     // with fmt, optional: every frame's own list of colour ops between the geometry and scale / bias
     // (ccmi_colour); with an op in any frame the call runs the colour forms of the output kernels
     const ccmi_colour *colour = nullptr;
+    // with fmt, optional: per-frame blur taps and solarize thresholds after the colour ops (ccmi_filter);
+    // the frames that take the stage are staged in float32 and go through the filter kernel
+    const ccmi_filter *filter = nullptr;
     // either sink
     const size_t *caps = nullptr;    // [n], optional: capacity in bytes of outs[i] / dev[i]
     size_t *sizes = nullptr;         // [n], optional: bytes written per stream (filled by the plan)
@@ -122,6 +125,7 @@ struct FramePlan {
     size_t lat_off, ws_off, dense_off, synout_off, synws_off, out_off;
     size_t lat_elems, ws_elems, dense_elems, synout_elems, synws_elems;
     size_t rs_off = 0, rs_elems = 0; // a resample's horizontal-pass intermediate (float32); none without one
+    size_t flt_off = 0, flt_elems = 0; // the filter stage's staging frame (float32); none unless the frame takes it
 };
 
 struct DecodePlan {
@@ -138,6 +142,12 @@ struct DecodePlan {
     std::vector<DecCol> cols; // col: every frame's ops (DecTailFrame::col points here); empty otherwise
     bool col_stat = false; // a frame has a contrast op: the accumulators are cleared before the tails run
     size_t col_off = 0;    // col: one 64-bit accumulator per frame (S_j of its contrast op)
+    // ccmi_filter: every frame's DecFlt when a frame takes the stage (DecTailFrame::flt points here, NULL
+    // for the frames that do not); n_flt of them do, and their tables, kFltTableBytes each, follow the
+    // job table in the one host image
+    std::vector<DecFlt> flts;
+    int n_flt = 0;
+    size_t flt_tab_off = 0;
 #if defined(CCMI_ARM_STAMPS)
     size_t dbg_off = 0;
 #endif

@@ -795,7 +795,7 @@ size_t dec_tail_table_bytes(int n_layers, int n, bool windowed, int out_form, bo
 }
 
 // the window-form tables
-static void dec_tail_fill_win(const DecTailFrame *const *fr, int n, void *host_tab)
+static void dec_tail_fill_win(const DecTailFrame *const *fr, int n, void *host_tab, int n_flt, void *host_flt_tab)
 {
     const int steps = fr[0]->ups.n_layers - 1;
     const TailTable T(*fr[0], n);
@@ -817,12 +817,13 @@ static void dec_tail_fill_win(const DecTailFrame *const *fr, int n, void *host_t
         // converts it as a frame of the region's size (420: the origin is even, so its even
         // rows and columns are the frame's)
         dec_out_fill(T.at<void>(host_tab, T.out), T.at<void>(host_tab, T.col), i, *fr[i], S.rh, S.rw, S.ry, S.rx);
+        if (i >= n - n_flt) dec_flt_fill(host_flt_tab, n_flt, i - (n - n_flt), *fr[i], S.rh, S.rw, S.ry, S.rx);
     }
 }
 
-void dec_tail_fill(const DecTailFrame *const *fr, int n, void *host_tab)
+void dec_tail_fill(const DecTailFrame *const *fr, int n, void *host_tab, int n_flt, void *host_flt_tab)
 {
-    if (fr[0]->windowed) return dec_tail_fill_win(fr, n, host_tab);
+    if (fr[0]->windowed) return dec_tail_fill_win(fr, n, host_tab, n_flt, host_flt_tab);
     const int steps = fr[0]->ups.n_layers - 1;
     const TailTable T(*fr[0], n);
     DecLevel *lv = T.at<DecLevel>(host_tab, 0);
@@ -833,6 +834,7 @@ void dec_tail_fill(const DecTailFrame *const *fr, int n, void *host_tab)
         for (int st = 0; st < steps; ++st) lv[(size_t)st * n + i] = tmp[st];
         sf[i] = make_syn_fused(fr[i]->syn);
         dec_out_fill(T.at<void>(host_tab, T.out), T.at<void>(host_tab, T.col), i, *fr[i], fr[i]->syn.h, fr[i]->syn.w, 0, 0);
+        if (i >= n - n_flt) dec_flt_fill(host_flt_tab, n_flt, i - (n - n_flt), *fr[i], fr[i]->syn.h, fr[i]->syn.w, 0, 0);
     }
 }
 
@@ -844,9 +846,25 @@ static bool col_group_stat(const DecTailFrame *const *fr, int n)
     return false;
 }
 
+// The output stage of a group whose last n_flt frames take the filter stage: the others through the
+// group's output kernels as ever (their entries lead the output and colour sections), the staged
+// ones as launches of their own (launch_dec_out_group_flt).
+static int launch_out_stage(const DecTailFrame *const *fr, int n, int n_flt, int h, int w, const TailTable &T,
+                            const void *dev_tab, const void *dev_flt_tab, hipStream_t s)
+{
+    const int n0 = n - n_flt;
+    const DecCol *kk = T.at<DecCol>(dev_tab, T.col);
+    if (n0 > 0)
+        if (int rc = launch_dec_out_group(*fr[0], h, w, n0, T.at<void>(dev_tab, T.out), kk, col_group_stat(fr, n0), s))
+            return rc;
+    if (n_flt > 0) return launch_dec_out_group_flt(fr + n0, n_flt, h, w, dev_flt_tab, kk + n0, s);
+    return CCMI_OK;
+}
+
 // region decode: one launch per stage for a window-form group (dec_tail_same_group); the
 // grids cover the group's largest window of each level
-static int launch_dec_tail_batch_win(const DecTailFrame *const *fr, int n, const void *dev_tab, hipStream_t s)
+static int launch_dec_tail_batch_win(const DecTailFrame *const *fr, int n, const void *dev_tab, hipStream_t s, int n_flt,
+                                     const void *dev_flt_tab)
 {
     const DecTailFrame &f0 = *fr[0];
     const int L = f0.ups.n_layers, steps = L - 1;
@@ -877,14 +895,14 @@ static int launch_dec_tail_batch_win(const DecTailFrame *const *fr, int n, const
         hipLaunchKernelGGL((dec_syn_fused_win_batch<decltype(cin)::value, 3>), sg, dim3(kThreads), 0, s, sf, gtx);
     });
     CCMI_HIP_CHECK(hipGetLastError());
-    return launch_dec_out_group(f0, rh, rw, n, T.at<void>(dev_tab, T.out), T.at<DecCol>(dev_tab, T.col), col_group_stat(fr, n),
-                                s);
+    return launch_out_stage(fr, n, n_flt, rh, rw, T, dev_tab, dev_flt_tab, s);
 }
 
-int launch_dec_tail_batch(const DecTailFrame *const *fr, int n, const void *dev_tab, hipStream_t s)
+int launch_dec_tail_batch(const DecTailFrame *const *fr, int n, const void *dev_tab, hipStream_t s, int n_flt,
+                          const void *dev_flt_tab)
 {
-    if (n < 1 || n > 65535) return ccmi_set_error(CCMI_ERR_ARG, "dec: tail batch of %d frames", n);
-    if (fr[0]->windowed) return launch_dec_tail_batch_win(fr, n, dev_tab, s);
+    if (n < 1 || n > 65535 || n_flt < 0 || n_flt > n) return ccmi_set_error(CCMI_ERR_ARG, "dec: tail batch of %d frames", n);
+    if (fr[0]->windowed) return launch_dec_tail_batch_win(fr, n, dev_tab, s, n_flt, dev_flt_tab);
     const DecTailFrame &f0 = *fr[0];
     const int L = f0.ups.n_layers, steps = L - 1;
     const TailTable T(f0, n);
@@ -903,8 +921,7 @@ int launch_dec_tail_batch(const DecTailFrame *const *fr, int n, const void *dev_
         hipLaunchKernelGGL((dec_syn_fused_batch<decltype(cin)::value, 3>), sg, dim3(kThreads), 0, s, sf);
     });
     CCMI_HIP_CHECK(hipGetLastError());
-    return launch_dec_out_group(f0, f0.syn.h, f0.syn.w, n, T.at<void>(dev_tab, T.out), T.at<DecCol>(dev_tab, T.col),
-                                col_group_stat(fr, n), s);
+    return launch_out_stage(fr, n, n_flt, f0.syn.h, f0.syn.w, T, dev_tab, dev_flt_tab, s);
 }
 
 } // namespace ccmi

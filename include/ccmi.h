@@ -835,6 +835,85 @@ int ccmi_latents_render_col(const ccmi_latents *h, const int *index /* [m] or NU
                             const ccmi_warp *warp /* or NULL */, const ccmi_colour *colour /* or NULL */,
                             int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Filtered formatted output: the coloured sink with a per-frame separable blur and a per-frame solarize --
+ * the GaussianBlur / RandomSolarize steps of the self-supervised recipes (SimCLR, BYOL, MoCo v3, DINO) --
+ * applied in the decoder's output stage after step 3z (colour) and before step 4 (scale / bias), on the
+ * frame at the output size oh x ow (the region's for the plain formatted call, out_h x out_w with a
+ * resample or a warp).  Frame j TAKES THE STAGE when radius[j] > 0 or (solarize != NULL and
+ * solarize[j] <= 1.0f); every other frame goes through the kernels it goes through without a filter and
+ * keeps its bits.  For a frame that takes the stage, every product, sum and difference is one float32
+ * operation in the order written (no fused multiply-add):
+ *   3y-0. x_c(i, k) = the value after step 3z at output row i and STORED column k (the column after
+ *         mirror[j], the x' of step 6: the filter runs on the frame as it will be stored, and a mirrored
+ *         row summed in ascending order is a different float32 sum), + 0.0f (a -0 becomes +0);
+ *   3y-1. blur, only when r = radius[j] > 0, with the frame's half taps w_0 (centre) .. w_r:
+ *         refl(a, n) = 0 when n == 1; else p = 2 (n - 1), m = a mod p taken into [0, p), and
+ *         refl = m < n ? m : p - m.  For r < n this is torch's "reflect" padding; for r >= n it folds as
+ *         often as needed (where torch refuses).
+ *         t_c(i, k) = sum_{d = -r .. r} w_|d| x_c(i, refl(k + d, ow)), from 0.0f over d ascending;
+ *         y_c(i, k) = clamp(sum_{d = -r .. r} w_|d| t_c(refl(i + d, oh), k), 0, 1), summed the same way
+ *         (a NaN sum, which only taps that overflow float32 can give, clamps to 0).
+ *         With r = 0 both passes are skipped and y = x;
+ *   3y-2. solarize, only when th = solarize[j] <= 1: y_c = (y_c >= th) ? 1.0f - y_c : y_c
+ *         (torchvision's float solarize).
+ * Steps 4-6 then apply to y, stored at column k (the mirror has been applied already).
+ * The taps are an input and not derived from a sigma here, so the bits never depend on anybody's exp;
+ * half taps make the kernel symmetric by construction; any finite float32 taps are legal.
+ *
+ * One superset pair per source: the _col argument list with `filter` after `colour`.  filter NULL, or no
+ * frame taking the stage: exactly the _col call, plan, workspace, launches and bits.  Otherwise the
+ * workspace grows by exactly
+ *     sum over the frames that take the stage of (12 oh ow rounded up to 256)  +  256 S   bytes,
+ * S the number of those frames: one float32 staging frame [3][oh][ow] each, and 256 bytes each of the
+ * call's tables (the frame's entry of the staging launch, its filter entry and its 16 taps: the tap
+ * table), uploaded with the rest of the tables in one copy.  The frames of one tail group stay one
+ * group (ccmi_decode_last_tail_groups is what the call without a filter reports); the staged frames of
+ * a group run the group's geometry and colour kernels once more on their own -- in the identity format:
+ * float32, planar, scale 1, bias 0, the frame's mirror -- into their staging frames, and then one launch
+ * of the filter kernel (both passes; the horizontal result never leaves the LDS) into the caller's
+ * tensors in the call's format.
+ * Checked by the plan before any GPU work, CCMI_ERR_ARG naming the frame and nothing written: radius
+ * NULL, a radius outside [0, CCMI_FLT_MAX_RADIUS], taps NULL while some radius > 0, a non-finite tap, a
+ * NaN threshold; and everything the _col plan checks.
+ * Measured (profiles/decode_filter_ab.txt): the workload of the colour stage above with a 23-tap Gaussian
+ * blur on half of the frames and solarize on a fifth (589 of 960 frames take the stage): 54.5 ms per call
+ * (tail 47.1 ms) against 52.0-52.1 ms (tail 45.2 ms) for the call without a filter and 58.1-58.2 ms for the
+ * float32 render followed by the same steps as torch operations; peak allocation above store and workspace
+ * 276 MiB against 1654 MiB; the workspace grows by 338 MiB. */
+enum { CCMI_FLT_MAX_RADIUS = 15 };
+typedef struct ccmi_filter {
+    const int   *radius;   /* host, [n]: r_j in [0, CCMI_FLT_MAX_RADIUS]; 0 = no blur for frame j      */
+    const float *taps;     /* host, flat: frame j's r_j + 1 half taps w_0 (centre) .. w_r follow frame  */
+                           /* j - 1's; frames with r_j = 0 contribute none; may be NULL if every r is 0 */
+    const float *solarize; /* host, [n] or NULL: threshold th_j; acts only where th_j <= 1              */
+} ccmi_filter;
+int ccmi_decode_batch_dev_flt_plan(const uint8_t *const *streams, const size_t *lens, int n,
+                                   const ccmi_rect *roi /* [n] or NULL */, int out_bitdepth, int out_chroma,
+                                   const ccmi_tensor_fmt *fmt, const ccmi_resample *rs /* or NULL */,
+                                   const ccmi_warp *warp /* or NULL */, const ccmi_colour *colour /* or NULL */,
+                                   const ccmi_filter *filter /* or NULL */, ccmi_frame_geom *geom /* [n] */,
+                                   ccmi_roi_info *info /* [n] or NULL */, ccmi_rect window[] /* [n] or NULL; warp only */,
+                                   size_t *workspace_bytes);
+int ccmi_decode_batch_dev_flt(const uint8_t *const *streams, const size_t *lens, int n,
+                              const ccmi_rect *roi /* [n] or NULL */, void *const *out_dev, const size_t *out_caps,
+                              const ccmi_tensor_fmt *fmt, const ccmi_resample *rs /* or NULL */,
+                              const ccmi_warp *warp /* or NULL */, const ccmi_colour *colour /* or NULL */,
+                              const ccmi_filter *filter /* or NULL */, int out_bitdepth, int out_chroma,
+                              void *workspace, size_t workspace_bytes, void *stream);
+int ccmi_latents_render_flt_plan(const ccmi_latents *h, const int *index /* [m] or NULL */, int m,
+                                 const ccmi_rect *roi /* [m] or NULL */, int out_bitdepth, int out_chroma,
+                                 const ccmi_tensor_fmt *fmt, const ccmi_resample *rs /* or NULL */,
+                                 const ccmi_warp *warp /* or NULL */, const ccmi_colour *colour /* or NULL */,
+                                 const ccmi_filter *filter /* or NULL */, ccmi_frame_geom *geom /* [m] */,
+                                 ccmi_roi_info *info /* [m] or NULL */, ccmi_rect window[] /* [m] or NULL; warp only */,
+                                 size_t *workspace_bytes);
+int ccmi_latents_render_flt(const ccmi_latents *h, const int *index /* [m] or NULL */, int m,
+                            const ccmi_rect *roi /* [m] or NULL */, void *const *out_dev, const size_t *out_caps,
+                            const ccmi_tensor_fmt *fmt, const ccmi_resample *rs /* or NULL */,
+                            const ccmi_warp *warp /* or NULL */, const ccmi_colour *colour /* or NULL */,
+                            const ccmi_filter *filter /* or NULL */, int out_bitdepth, int out_chroma,
+                            void *workspace, size_t workspace_bytes, void *stream);
+
 /* Network weights of a stream's intra frame as the decoder's fixed-point integers
  * (cc-frame-decoder.cpp:201-353, read_arm / read_ups / read_syn):
  *   arm: per hidden layer W[d][d] (out, in) then b[d]; then W_out[2][d], b_out[2]
