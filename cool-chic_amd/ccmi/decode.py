@@ -53,6 +53,10 @@ _PROTOS = {
     "ccmi_decode_batch_dev_flt": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _Z, _P],
     "ccmi_latents_render_flt_plan": [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "ccmi_latents_render_flt": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _Z, _P],
+    "ccmi_decode_batch_dev_tone_plan": [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "ccmi_decode_batch_dev_tone": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _Z, _P],
+    "ccmi_latents_render_tone_plan": [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "ccmi_latents_render_tone": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _Z, _P],
     "ccmi_latents_plan": [_P, _P, _I, _I, _P, _P, _P],
     "ccmi_latents_decode": [_P, _P, _I, _I, _P, _Z, _P, _Z, _P, _P],
     "ccmi_latents_free": [_P],
@@ -663,6 +667,180 @@ def random_solarize(n: int, threshold: float = 0.5, p: float = 0.2, generator=No
     return [float(threshold) if v < p else None for v in u]
 
 
+TONE_BRIGHTNESS, TONE_SATURATION, TONE_CONTRAST, TONE_MATRIX, TONE_SOLARIZE = 0, 1, 2, 3, 4  # CCMI_TONE_*
+TONE_POSTERIZE, TONE_AUTOCONTRAST, TONE_EQUALIZE, TONE_SHARPNESS = 5, 6, 7, 8
+TONE_MAX_OPS = 8
+_TONE_NAMES = {"brightness": TONE_BRIGHTNESS, "saturation": TONE_SATURATION, "contrast": TONE_CONTRAST,
+               "matrix": TONE_MATRIX, "solarize": TONE_SOLARIZE, "posterize": TONE_POSTERIZE,
+               "autocontrast": TONE_AUTOCONTRAST, "equalize": TONE_EQUALIZE, "sharpness": TONE_SHARPNESS}
+
+
+class ToneOp(C.Structure):
+    """ccmi_tone_op: one tone operation (v[0] the factor, threshold or bits, or the 3 x 4 matrix row-major)."""
+    _fields_ = [("op", C.c_int), ("v", C.c_float * 12)]
+
+
+class Tone(C.Structure):
+    """ccmi_tone: the per-frame op counts and the flat op array of a call with tone ops."""
+    _fields_ = [("count", C.c_void_p), ("ops", C.c_void_p)]
+
+
+def _tone(tone_ops, n):
+    """tone_ops= of a *_model call -> (ccmi_tone, what it points to), or (None, None) without ops.
+    One list of (op, value) tuples for every frame, or one such list per frame; op is a name of
+    _TONE_NAMES (or a TONE_* code), value the factor, threshold or bits, the matrix as 12 numbers or
+    [3][4], and None for 'autocontrast' and 'equalize'.  The library checks the values."""
+    import numpy as np
+    if tone_ops is None:
+        return None, None
+    ops = list(tone_ops)
+    if not ops:
+        return None, None
+    if isinstance(ops[0], tuple) and len(ops[0]) == 2 and isinstance(ops[0][0], (str, int)):
+        ops = [ops] * n  # one list for all frames
+    if len(ops) != n:
+        raise ValueError(f"model output: tone_ops takes one op list, or one per frame ({n}), got {len(ops)}")
+    counts = np.fromiter((len(f) for f in ops), dtype=np.int32, count=n)
+    if not counts.any():
+        return None, None
+    flat = np.zeros(int(counts.sum()), dtype=np.dtype([("op", "<i4"), ("v", "<f4", (12,))]))
+    k = 0
+    for f in ops:
+        for op, value in f:
+            code = _TONE_NAMES.get(op) if isinstance(op, str) else int(op)
+            if code is None:
+                raise ValueError(f"model output: tone op {op!r} ({', '.join(_TONE_NAMES)})")
+            flat["op"][k] = code
+            if code == TONE_MATRIX:
+                try:
+                    flat["v"][k] = np.asarray(value, dtype=np.float32).reshape(12)
+                except ValueError:
+                    raise ValueError("model output: a matrix tone op takes a 3 x 4 matrix (12 values)") from None
+            elif value is not None:
+                flat["v"][k, 0] = np.float32(value)
+            k += 1
+    return Tone(count=counts.ctypes.data, ops=flat.ctypes.data), (counts, flat)
+
+
+# torchvision's op table (RandAugment._augmentation_space): name, signed
+_RA_OPS = (("Identity", False), ("ShearX", True), ("ShearY", True), ("TranslateX", True), ("TranslateY", True),
+           ("Rotate", True), ("Brightness", True), ("Color", True), ("Contrast", True), ("Sharpness", True),
+           ("Posterize", False), ("Solarize", False), ("AutoContrast", False), ("Equalize", False))
+
+
+def _ra_magnitude(name, k, bins, size, wide):
+    """The magnitude of bin k of op `name`: torchvision's RandAugment table, or TrivialAugmentWide's."""
+    import numpy as np
+    lin = lambda hi: float(np.linspace(0.0, hi, bins)[k])  # noqa: E731
+    if name in ("ShearX", "ShearY", "Brightness", "Color", "Contrast", "Sharpness"):
+        return lin(0.99 if wide else (0.3 if name.startswith("Shear") else 0.9))
+    if name == "TranslateX":
+        return lin(32.0 if wide else 150.0 / 331.0 * size[1])
+    if name == "TranslateY":
+        return lin(32.0 if wide else 150.0 / 331.0 * size[0])
+    if name == "Rotate":
+        return lin(135.0 if wide else 30.0)
+    if name == "Posterize":
+        return float(8 - int(round(k / ((bins - 1) / (6 if wide else 4)))))
+    if name == "Solarize":
+        return float(np.linspace(1.0, 0.0, bins)[k])  # the v2 transform's float threshold
+    return 0.0
+
+
+def _ra_apply(name, mag, size, geo, tone):
+    """One drawn op: a geometric one is composed into geo (3 x 3, output pixel -> input pixel of an image of
+    `size`, pixel centres at + 0.5), a photometric one appended to tone."""
+    import math
+    import numpy as np
+    h, w = size
+    m = np.eye(3)
+    if name == "ShearX":
+        m[0, 1] = mag  # F.affine(shear=[atan(mag), 0], center=[0, 0]): x_in = x + mag y
+    elif name == "ShearY":
+        m[1, 0] = mag
+    elif name == "TranslateX":
+        m[0, 2] = -float(int(mag))
+    elif name == "TranslateY":
+        m[1, 2] = -float(int(mag))
+    elif name == "Rotate":  # F.rotate: counter-clockwise about the image's centre
+        c, s = math.cos(math.radians(mag)), math.sin(math.radians(mag))
+        m[:2, :2] = [[c, -s], [s, c]]
+        m[0, 2] = w / 2 - c * w / 2 + s * h / 2
+        m[1, 2] = h / 2 - s * w / 2 - c * h / 2
+    elif name == "Brightness":
+        tone.append(("brightness", 1.0 + mag))
+    elif name == "Color":
+        tone.append(("saturation", 1.0 + mag))
+    elif name == "Contrast":
+        tone.append(("contrast", 1.0 + mag))
+    elif name == "Sharpness":
+        tone.append(("sharpness", 1.0 + mag))
+    elif name == "Posterize":
+        tone.append(("posterize", mag))
+    elif name == "Solarize":
+        tone.append(("solarize", mag))
+    elif name == "AutoContrast":
+        tone.append(("autocontrast", None))
+    elif name == "Equalize":
+        tone.append(("equalize", None))
+    return geo @ m
+
+
+def _ra_draw(n, num_ops, magnitude, bins, generator, size, base, wide):
+    import numpy as np
+    import torch
+    size = (int(size[0]), int(size[1]))
+    if base is not None:
+        base = np.asarray(base, dtype=np.float64).reshape(-1, 2, 3)
+        if base.shape[0] not in (1, n):
+            raise ValueError(f"augment: base takes one [2, 3] matrix, or one per frame ({n}), got {base.shape[0]}")
+    mats, tones = np.zeros((n, 2, 3), dtype=np.float32), []
+    for j in range(n):
+        geo = np.eye(3)
+        if base is not None:
+            geo[:2] = base[j % base.shape[0]]
+        tone = []
+        for _ in range(num_ops):
+            name, signed = _RA_OPS[int(torch.randint(len(_RA_OPS), (1,), generator=generator))]
+            k = int(torch.randint(bins, (1,), generator=generator)) if wide else int(magnitude)
+            mag = _ra_magnitude(name, k, bins, size, wide)
+            if signed and int(torch.randint(2, (1,), generator=generator)):
+                mag = -mag
+            geo = _ra_apply(name, mag, size, geo, tone)
+        mats[j] = geo[:2]
+        tones.append(tone)
+    return mats, tones
+
+
+def rand_augment(n: int, num_ops: int = 2, magnitude: int = 9, num_magnitude_bins: int = 31, generator=None,
+                 size=(224, 224), base=None):
+    """n draws of torchvision's RandAugment(num_ops, magnitude, num_magnitude_bins) from its op table and
+    magnitude ranges: (matrices, tone lists) for affine= and tone_ops= of the *_model calls (with
+    size=size).  matrices: float32 [n, 2, 3]; the geometric draws of a frame (ShearX/Y, TranslateX/Y,
+    Rotate) composed into ONE matrix that maps an output pixel of the size x size image to a pixel of
+    the image before (pixel centres at + 0.5), after `base` (None: the identity; else one [2, 3] matrix
+    or one per frame that maps the output image to the frame, e.g. affine_matrix()'s crop).  tone
+    lists: the photometric draws in their order (Brightness, Color, Contrast, Sharpness as 1 +- m;
+    Posterize bits; Solarize as the v2 transform's threshold in [0, 1]; AutoContrast; Equalize).
+    Geometry always runs first, in one bilinear warp (torchvision resamples once per op, nearest by
+    default): the result follows torchvision's when a frame's photometric ops come after its geometric
+    ones; when one comes before, the statistics of autocontrast / equalize / contrast see the fill
+    pixels the later warp brings in, and torchvision's do not.  magnitude must be below
+    num_magnitude_bins.  generator: a torch.Generator (CPU); the same seed gives the same draws."""
+    if not 0 <= int(magnitude) < int(num_magnitude_bins):
+        raise ValueError(f"rand_augment: magnitude {magnitude} of {num_magnitude_bins} bins")
+    if not 0 <= int(num_ops) <= TONE_MAX_OPS:
+        raise ValueError(f"rand_augment: num_ops {num_ops} (0 .. {TONE_MAX_OPS})")
+    return _ra_draw(n, int(num_ops), magnitude, int(num_magnitude_bins), generator, size, base, False)
+
+
+def trivial_augment_wide(n: int, num_magnitude_bins: int = 31, generator=None, size=(224, 224), base=None):
+    """n draws of torchvision's TrivialAugmentWide: one op per frame, its magnitude bin drawn uniformly, from
+    the wide ranges (shear and the factors to 0.99, translate to 32 pixels, rotate to 135 degrees,
+    posterize down to 2 bits).  Returns what rand_augment() returns, with the same caveats."""
+    return _ra_draw(n, 1, 0, int(num_magnitude_bins), generator, size, base, True)
+
+
 def last_tail_groups() -> tuple:
     """(batched tail groups, per-frame tails) this thread's last decode or render call launched
     (ccmi_decode_last_tail_groups): frames that share a group share one launch per tail stage."""
@@ -741,16 +919,21 @@ def _model_outs(geom, fmt, dtype, channels_last, out, dev):
 
 
 def _plan_model(plan, head, n, rects, fmt, rs, output_bitdepth, output_chroma_format, warp=None, info=None,
-                window=None, col=None, flt=None):
+                window=None, col=None, flt=None, tone=None):
     """(ccmi_frame_geom array, workspace bytes) of a formatted call: plan is the source's *_rs_plan
     entry point (rs None: exactly the *_fmt_plan call), head its first two arguments.  With warp
     (a ccmi_warp) plan is the *_warp_plan entry point, which takes no regions; info / window: its
     optional per-frame outputs.  With col (a ccmi_colour) plan is the *_col_plan entry point, which
     takes all of them; with flt (a ccmi_filter) the *_flt_plan entry point, which takes col (or None)
-    and flt."""
+    and flt; with tone (a ccmi_tone) the *_tone_plan entry point, which takes col, tone and flt (or None)."""
     geom, need = (FrameGeom * n)(), C.c_size_t(0)
     probe = TensorFmt.from_buffer_copy(fmt)  # planar strides: the geometry does not depend on them
-    if flt is not None:
+    if tone is not None:
+        check(plan(*head, n, None if warp is not None else rects, output_bitdepth, output_chroma_format, C.byref(probe),
+                   None if warp is not None else rs, None if warp is None else C.byref(warp),
+                   None if col is None else C.byref(col), C.byref(tone), None if flt is None else C.byref(flt), geom, info,
+                   window, C.byref(need)))
+    elif flt is not None:
         check(plan(*head, n, None if warp is not None else rects, output_bitdepth, output_chroma_format, C.byref(probe),
                    None if warp is not None else rs, None if warp is None else C.byref(warp),
                    None if col is None else C.byref(col), C.byref(flt), geom, info, window, C.byref(need)))
@@ -767,21 +950,27 @@ def _plan_model(plan, head, n, rects, fmt, rs, output_bitdepth, output_chroma_fo
 
 
 def _run_model(plan, run, head, n, rects, dev, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth,
-               output_chroma_format, workspace, stream_handle, size, warp=None, col=None, flt=None):
+               output_chroma_format, workspace, stream_handle, size, warp=None, col=None, flt=None, tone=None):
     """The body of decode_batch_model and LatentStore.render_model: plan / run are the source's
     *_rs_plan / *_rs entry points, or with warp (a ccmi_warp, which carries the size) its
     *_warp_plan / *_warp ones, or with col (a ccmi_colour) its *_col_plan / *_col ones, or with flt (a
-    ccmi_filter) its *_flt_plan / *_flt ones; head their first two arguments; dev None: the current
+    ccmi_filter) its *_flt_plan / *_flt ones, or with tone (a ccmi_tone) its *_tone_plan / *_tone ones; head their first two arguments; dev None: the current
     device."""
     import torch
     dtype = torch.float32 if dtype is None else dtype
     fmt, keep = _model_fmt(n, colour, mean, std, dtype, mirror)
     rs = None if size is None or warp is not None else C.byref(_resample(size))
-    geom, need = _plan_model(plan, head, n, rects, fmt, rs, output_bitdepth, output_chroma_format, warp, col=col, flt=flt)
+    geom, need = _plan_model(plan, head, n, rects, fmt, rs, output_bitdepth, output_chroma_format, warp, col=col, flt=flt,
+                             tone=tone)
     dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else dev
     res, op, cap, frames = _model_outs(geom, fmt, dtype, channels_last, out, dev)
     stream_handle, workspace = _stream_ws(dev, stream_handle, workspace, need)
-    if flt is not None:
+    if tone is not None:
+        check(run(*head, n, None if warp is not None else rects, op, cap, C.byref(fmt), None if warp is not None else rs,
+                  None if warp is None else C.byref(warp), None if col is None else C.byref(col), C.byref(tone),
+                  None if flt is None else C.byref(flt), output_bitdepth, output_chroma_format, workspace.data_ptr(),
+                  workspace.numel(), stream_handle))
+    elif flt is not None:
         check(run(*head, n, None if warp is not None else rects, op, cap, C.byref(fmt), None if warp is not None else rs,
                   None if warp is None else C.byref(warp), None if col is None else C.byref(col), C.byref(flt),
                   output_bitdepth, output_chroma_format, workspace.data_ptr(), workspace.numel(), stream_handle))
@@ -802,7 +991,8 @@ def _run_model(plan, run, head, n, rects, dev, colour, mean, std, dtype, channel
 def decode_batch_model(streams: Sequence[bytes], roi=None, colour: str = "rgb", mean=None, std=None, dtype=None,
                        channels_last: bool = False, mirror=None, out=None, output_bitdepth: int = 0,
                        output_chroma_format: int = 0, workspace=None, stream_handle: int | None = None, size=None,
-                       affine=None, pad: str = "fill", fill=0.0, colour_ops=None, blur=None, solarize=None):
+                       affine=None, pad: str = "fill", fill=0.0, colour_ops=None, blur=None, solarize=None,
+                       tone_ops=None):
     """Decode .cool streams into the tensor a model takes (ccmi_decode_batch_dev_fmt): one
     [n, 3, h, w] tensor of `dtype` (torch.float32, the default, torch.float16 or torch.bfloat16),
     every channel at full size (420 chroma nearest-upsampled), RGB (colour="rgb": YUV streams go
@@ -850,13 +1040,27 @@ def decode_batch_model(streams: Sequence[bytes], roi=None, colour: str = "rgb", 
     them): a separable blur with reflecting borders, clamped to [0, 1].  solarize: None, one threshold
     for every frame or one per frame (None or above 1: off): v >= threshold becomes 1 - v.  The frames
     that take neither go through the kernels of the call without; the others are staged in float32 in
-    the workspace and share one launch of the filter kernel per tail group."""
+    the workspace and share one launch of the filter kernel per tail group.
+
+    tone_ops= (ccmi_decode_batch_dev_tone; with or without everything above): one list of (op, value)
+    tuples for every frame, or one per frame, of at most 8 ops each, applied in the list's order to the
+    staged frame after the colour ops and before blur / solarize (the contract's step 3x), each over the
+    whole frame before the next: ('brightness', f), ('saturation', f), ('contrast', f), ('matrix', M),
+    ('solarize', th), ('posterize', bits 1..8), ('autocontrast', None), ('equalize', None),
+    ('sharpness', f).  rand_augment() and trivial_augment_wide() draw such lists (and the matrices for
+    affine=).  A frame with a list is staged like a blurred one; the others keep their kernels and bits."""
     n = len(streams)
     keep, sp, ln = _marshal(streams)
     L = _bind()
     warp, keep_w = _warp(affine, n, size, roi, pad, fill)
     col, keep_c = _colour(colour_ops, n)
     flt, keep_f = _filter(blur, solarize, n)
+    tone, keep_t = _tone(tone_ops, n)
+    if tone is not None:
+        return _run_model(L.ccmi_decode_batch_dev_tone_plan, L.ccmi_decode_batch_dev_tone, (sp, ln), n,
+                          None if warp is not None else _rects(roi, streams, n), None, colour, mean, std, dtype,
+                          channels_last, mirror, out, output_bitdepth, output_chroma_format, workspace, stream_handle, size,
+                          warp, col, flt, tone)
     if flt is not None:
         return _run_model(L.ccmi_decode_batch_dev_flt_plan, L.ccmi_decode_batch_dev_flt, (sp, ln), n,
                           None if warp is not None else _rects(roi, streams, n), None, colour, mean, std, dtype,
@@ -1263,20 +1467,27 @@ class LatentStore:
     def render_model(self, index=None, roi=None, colour: str = "rgb", mean=None, std=None, dtype=None,
                      channels_last: bool = False, mirror=None, out=None, output_bitdepth: int = 0,
                      output_chroma_format: int = 0, workspace=None, stream_handle: int | None = None, size=None,
-                     affine=None, pad: str = "fill", fill=0.0, colour_ops=None, blur=None, solarize=None):
+                     affine=None, pad: str = "fill", fill=0.0, colour_ops=None, blur=None, solarize=None,
+                     tone_ops=None):
         """render() into the tensor a model takes (ccmi_latents_render_fmt; with size
         ccmi_latents_render_rs; with affine ccmi_latents_render_warp): frames and regions as for
         render(), the result and every other argument as for decode_batch_model, whose output for
         the same streams and arguments it equals bit for bit.  workspace with a size or an affine:
         at least what render_model_workspace_bytes() reports (the resample's intermediate and a
         warp's windows are not part of render_geometry()'s figure).  With colour_ops
-        ccmi_latents_render_col, with blur or solarize ccmi_latents_render_flt:
+        ccmi_latents_render_col, with blur or solarize ccmi_latents_render_flt, with tone_ops
+        ccmi_latents_render_tone:
         render_model_workspace_bytes() takes the same arguments."""
         m, idx, rects = self._frames(index, None if affine is not None else roi)
         L = _bind()
         warp, keep_w = _warp(affine, m, size, roi, pad, fill)
         col, keep_c = _colour(colour_ops, m)
         flt, keep_f = _filter(blur, solarize, m)
+        tone, keep_t = _tone(tone_ops, m)
+        if tone is not None:
+            return _run_model(L.ccmi_latents_render_tone_plan, L.ccmi_latents_render_tone, (self._handle(), idx), m, rects,
+                              self._store.device, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth,
+                              output_chroma_format, workspace, stream_handle, size, warp, col, flt, tone)
         if flt is not None:
             return _run_model(L.ccmi_latents_render_flt_plan, L.ccmi_latents_render_flt, (self._handle(), idx), m, rects,
                               self._store.device, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth,
@@ -1313,13 +1524,13 @@ class LatentStore:
 
     def render_model_workspace_bytes(self, index=None, roi=None, size=None, output_bitdepth: int = 0,
                                      output_chroma_format: int = 0, affine=None, pad: str = "fill", fill=0.0,
-                                     colour_ops=None, blur=None, solarize=None) -> int:
+                                     colour_ops=None, blur=None, solarize=None, tone_ops=None) -> int:
         """Header-only: the workspace render_model needs for these frames, regions and size, or
         these frames, matrices and size (ccmi_latents_render_rs_plan / _warp_plan; the element type,
         colour and strides do not change it), these colour ops (ccmi_latents_render_col_plan:
         the op tables and the contrast ops' accumulators) and this blur and solarize
         (ccmi_latents_render_flt_plan: a float32 staging frame and 256 bytes of tables per frame
-        that takes the stage)."""
+        that takes the stage) and these tone ops (ccmi_latents_render_tone_plan: ccmi.h's formula)."""
         m, idx, rects = self._frames(index, None if affine is not None else roi)
         fmt = TensorFmt(elem=ELEM_F32, colour=COLOUR_ASIS)
         for c in range(3):
@@ -1327,6 +1538,11 @@ class LatentStore:
         warp, keep_w = _warp(affine, m, size, roi, pad, fill)
         col, keep_c = _colour(colour_ops, m)
         flt, keep_f = _filter(blur, solarize, m)
+        tone, keep_t = _tone(tone_ops, m)
+        if tone is not None:
+            rs = None if size is None or warp is not None else C.byref(_resample(size))
+            return _plan_model(_bind().ccmi_latents_render_tone_plan, (self._handle(), idx), m, rects, fmt, rs,
+                               output_bitdepth, output_chroma_format, warp, col=col, flt=flt, tone=tone)[1]
         if flt is not None:
             rs = None if size is None or warp is not None else C.byref(_resample(size))
             return _plan_model(_bind().ccmi_latents_render_flt_plan, (self._handle(), idx), m, rects, fmt, rs,
@@ -1364,5 +1580,5 @@ class LatentStore:
 __all__ = ["last_timing", "LatentStore", "last_arm_flags", "decode_latents", "decode_file", "decode_batch", "decode_batch_workspace_bytes", "output_size",
            "decode_batch_tensors", "decode_batch_geometry", "roi_plan", "decode_batch_model", "last_tail_groups",
            "affine_matrix", "hue_matrix", "grey_matrix", "colour_jitter",
-           "gaussian_taps", "gaussian_blur", "random_solarize",
+           "gaussian_taps", "gaussian_blur", "random_solarize", "rand_augment", "trivial_augment_wide",
            "weights_i32", "ups_forward_i32", "syn_forward_i32", "CcmiError"]

@@ -5,7 +5,9 @@
 // Blur is the one operation of the output stage that needs a pixel's neighbours AFTER the geometry
 // and the colour ops, so the frames that take the stage are staged: the group's own geometry and
 // colour kernels (dec_out.hip, unchanged) run once more over them in the identity format -- float32,
-// planar, scale 1, bias 0, the frame's mirror -- into one float32 frame [3][oh][ow] each, and
+// planar, scale 1, bias 0, the frame's mirror -- into one float32 frame [3][oh][ow] each; the tone ops
+// of a call with a ccmi_tone (dec_tone.hip) then run on the staged frames, in place or into a frame's
+// second buffer; and
 //
 //  dec_filter<T>, dec_filter_batch<T>   read those frames and write the caller's tensors in the
 //                   call's format (steps 4-6: fmt_group_at / fmt_store of dec_out_fmt.h), one launch
@@ -174,7 +176,8 @@ int filter_tiles_y(int oh) { return (oh + kTileH - 1) / kTileH; }
 DecFltEntry filter_entry(const DecTailFrame &f)
 {
     DecFltEntry e{};
-    e.src = f.flt_tmp;
+    // a frame's tone ops leave it in its second buffer after an odd number of sharpness passes
+    e.src = f.tone ? f.tone->buf[dec_tone_sharps(*f.tone) & 1] : f.flt_tmp;
     e.dst = f.dst;
     e.r = f.flt->r, e.sol = f.flt->sol, e.th = f.flt->th;
     memcpy(e.taps, f.flt->taps, sizeof e.taps);
@@ -224,6 +227,7 @@ void dec_flt_fill(void *flt_tab, int m, int i, const DecTailFrame &f, int h, int
     dec_out_fill(flt_tab, nullptr, i, t, h, w, oy, ox);
     DecFltEntry *fe = reinterpret_cast<DecFltEntry *>(static_cast<uint8_t *>(flt_tab) + filter_entries_off(f.fmt, m));
     fe[i] = filter_entry(f);
+    if (f.tone) reinterpret_cast<DecTone *>(static_cast<uint8_t *>(flt_tab) + kFltTableBytes * (size_t)m)[i] = *f.tone;
 }
 
 int launch_dec_out_group_flt(const DecTailFrame *const *fr, int m, int h, int w, const void *dev_flt_tab,
@@ -241,6 +245,16 @@ int launch_dec_out_group_flt(const DecTailFrame *const *fr, int m, int h, int w,
     if (int rc = launch_dec_out_group(staged_frame(f0, oh, ow), h, w, m, dev_flt_tab, col_sec, stat, s)) return rc;
     const DecFltEntry *fe =
         reinterpret_cast<const DecFltEntry *>(static_cast<const uint8_t *>(dev_flt_tab) + filter_entries_off(f0.fmt, m));
+    if (f0.tone) { // the tone ops of the staged frames, segment after segment, on the staging frames
+        std::vector<const DecTone *> es(m);
+        for (int i = 0; i < m; ++i) {
+            if (!fr[i]->tone) return ccmi_set_error(CCMI_ERR_ARG, "dec: a staged frame without its tone entry");
+            es[i] = fr[i]->tone;
+        }
+        const DecTone *dev_es =
+            reinterpret_cast<const DecTone *>(static_cast<const uint8_t *>(dev_flt_tab) + kFltTableBytes * (size_t)m);
+        if (int rc = launch_dec_tone_group(dev_es, es.data(), m, oh, ow, s)) return rc;
+    }
     const int tiles_x = filter_tiles_x(ow);
     const dim3 grid((unsigned)(tiles_x * filter_tiles_y(oh)), (unsigned)m);
     const DecFmtCall C = fmt_call(f0.fmt);
@@ -256,6 +270,8 @@ int launch_dec_out_frame_flt(const DecTailFrame &f, const int32_t *synout, int h
     int oh, ow;
     stored_size(f.fmt, f.roi.rect.h(), f.roi.rect.w(), oh, ow);
     if (int rc = launch_dec_out_frame(staged_frame(f, oh, ow), synout, h, w, false, true, s)) return rc;
+    if (f.tone)
+        if (int rc = launch_dec_tone_frame(*f.tone, oh, ow, s)) return rc;
     const DecFltEntry F = filter_entry(f);
     const int tiles_x = filter_tiles_x(ow);
     const dim3 grid((unsigned)(tiles_x * filter_tiles_y(oh)));

@@ -526,6 +526,12 @@ int build_tail_groups(Run &r)
         if (t.fmt.col && r.pl.cols[i].contrast >= 0)
             r.pl.cols[i].acc = reinterpret_cast<unsigned long long *>(r.dev + r.pl.col_off) + i;
         t.flt_tmp = p.flt_elems ? reinterpret_cast<float *>(r.dev + p.flt_off) : nullptr;
+        if (t.tone) { // the device pointers of the frame's tone entry, before the tables are filled
+            DecTone &e = r.pl.tones[i];
+            e.buf[0] = t.flt_tmp;
+            e.buf[1] = p.tone2_off ? reinterpret_cast<float *>(r.dev + p.tone2_off) : nullptr;
+            e.acc = dec_tone_stats(e) ? r.dev + p.tone_acc_off : nullptr;
+        }
         if (!p.batchable) continue;
         const int c = r.chunk_of[i];
         auto it = std::find_if(r.tails.begin(), r.tails.end(), [&](const TailGroup &g) {
@@ -546,7 +552,7 @@ int build_tail_groups(Run &r)
             auto staged = std::stable_partition(g.frames.begin(), g.frames.end(), [](const DecTailFrame *f) { return !f->flt; });
             g.n_flt = (int)(g.frames.end() - staged);
             g.flt_off = fpos;
-            fpos += kFltTableBytes * (size_t)g.n_flt;
+            fpos += dec_flt_table_bytes(!r.pl.tones.empty()) * (size_t)g.n_flt;
         }
         dec_tail_fill(g.frames.data(), m, r.tab.data() + tpos, g.n_flt, r.tab.data() + r.flt_tab() + g.flt_off);
         tpos += dec_tail_table_bytes(g.frames[0]->ups.n_layers, m, g.frames[0]->windowed, dec_out_form(g.frames[0]->fmt),
@@ -886,18 +892,20 @@ int decode_run(const DecodeRequest &rq, DecodePlan &pl, hipStream_t s)
     if (!render)
         if (int rc = build_arm_groups(r)) return rc;
     // the tables of the call: the tail groups', then the latent store's jobs, in one copy
-    r.tab.assign(std::max(r.lat_tab() + pl.lat_tab_cap, r.flt_tab() + kFltTableBytes * (size_t)pl.n_flt) + 1, 0);
+    r.tab.assign(std::max(r.lat_tab() + pl.lat_tab_cap, r.flt_tab() + pl.flt_table_bytes()) + 1, 0);
     if (!rq.lat_store)
         if (int rc = build_tail_groups(r)) return rc;
     if (rq.lat_store) build_pack_jobs(r);
     if (render) build_unpack_jobs(r);
-    if (pl.n_flt) r.tab_used = r.flt_tab() + kFltTableBytes * (size_t)pl.n_flt; // the filter stage's tables end the image
+    if (pl.n_flt) r.tab_used = r.flt_tab() + pl.flt_table_bytes(); // the filter stage's tables end the image
     if (r.tab_used)
         CCMI_HIP_CHECK(hipMemcpyAsync(r.dev + pl.tail_off, r.tab.data(), r.tab_used, hipMemcpyHostToDevice, s));
     if (rq.lat_store) // the networks' integers: constant part -> store, before the chunks fork
         if (int rc = launch_lat(r, r.lat[r.K], s)) return rc;
     if (pl.col_stat) // the contrast ops' accumulators, cleared in stream before any chunk's statistics pass
         CCMI_HIP_CHECK(hipMemsetAsync(r.dev + pl.col_off, 0, sizeof(unsigned long long) * pl.fr.size(), s));
+    if (pl.tone_acc_bytes) // the tone stage's accumulator blocks likewise (the minima are kept complemented)
+        CCMI_HIP_CHECK(hipMemsetAsync(r.dev + pl.tone_acc_off, 0, pl.tone_acc_bytes, s));
     ev.rec(1, s);
     if (int rc = run_chunks(r, ev, lease)) return rc;
     if (!rq.lat_store) { // what launch_chunk ran: every group, and a tail of its own per other frame
@@ -1019,10 +1027,10 @@ extern "C" int ccmi_decode_batch_ws(const uint8_t *const *streams, const size_t 
 }
 
 // ------------------------------------------------------------------ device sinks
-// Twenty-eight entry points over one table: the source is the caller's streams or a latent store, the
+// Thirty-two entry points over one table: the source is the caller's streams or a latent store, the
 // sink plain samples (sample_type; with or without a region) or formatted ones (fmt, forced to
 // CCMI_SAMPLE_F32, the call whose output kernel the format replaces; with or without a resample,
-// or with a warp, which takes no region; with or without colour ops and a filter),
+// or with a warp, which takes no region; with or without colour ops, tone ops and a filter),
 // and each comes as a plan and as a run.  `who` is the entry point's name for the error text,
 // `missing` its own null-argument check beyond the source's.
 struct Sink {
@@ -1033,6 +1041,7 @@ struct Sink {
     const ccmi_warp *warp;
     const ccmi_colour *colour;
     const ccmi_filter *filter = nullptr;
+    const ccmi_tone *tone = nullptr;
 };
 
 static Sink samples(const ccmi_rect *roi, int sample_type) { return Sink{roi, sample_type, nullptr, nullptr, nullptr, nullptr}; }
@@ -1061,6 +1070,13 @@ static Sink filtered(const ccmi_rect *roi, const ccmi_tensor_fmt *fmt, const ccm
     return Sink{roi, CCMI_SAMPLE_F32, fmt, rs, warp, colour, filter};
 }
 
+// ... and per-frame tone ops between the two
+static Sink toned(const ccmi_rect *roi, const ccmi_tensor_fmt *fmt, const ccmi_resample *rs, const ccmi_warp *warp,
+                  const ccmi_colour *colour, const ccmi_tone *tone, const ccmi_filter *filter)
+{
+    return Sink{roi, CCMI_SAMPLE_F32, fmt, rs, warp, colour, filter, tone};
+}
+
 static void set_sink(DecodeRequest &rq, const Sink &k)
 {
     rq.sample = k.sample;
@@ -1070,6 +1086,7 @@ static void set_sink(DecodeRequest &rq, const Sink &k)
     rq.warp = k.warp;
     rq.colour = k.colour;
     rq.filter = k.filter;
+    rq.tone = k.tone;
 }
 
 // streams as the source: null arguments, then the sample type, then the plan's own errors
@@ -1245,7 +1262,8 @@ extern "C" int ccmi_decode_batch_dev_col(const uint8_t *const *streams, const si
     return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
 }
 
-// The filtering sink: the colouring sink with a ccmi_filter (filter NULL: that call itself).
+// The filtering sink: the colouring sink with a ccmi_filter (filter NULL: that call itself); the _tone
+// calls after each are the same with a ccmi_tone (tone NULL: the _flt call itself).
 extern "C" int ccmi_decode_batch_dev_flt_plan(const uint8_t *const *streams, const size_t *lens, int n,
                                               const ccmi_rect *roi, int out_bitdepth, int out_chroma,
                                               const ccmi_tensor_fmt *fmt, const ccmi_resample *rs, const ccmi_warp *warp,
@@ -1261,6 +1279,22 @@ extern "C" int ccmi_decode_batch_dev_flt_plan(const uint8_t *const *streams, con
     return sink_plan(rq, geom, info, workspace_bytes);
 }
 
+extern "C" int ccmi_decode_batch_dev_tone_plan(const uint8_t *const *streams, const size_t *lens, int n,
+                                               const ccmi_rect *roi, int out_bitdepth, int out_chroma,
+                                               const ccmi_tensor_fmt *fmt, const ccmi_resample *rs, const ccmi_warp *warp,
+                                               const ccmi_colour *colour, const ccmi_tone *tone, const ccmi_filter *filter,
+                                               ccmi_frame_geom *geom, ccmi_roi_info *info, ccmi_rect *window,
+                                               size_t *workspace_bytes)
+{
+    DecodeRequest rq;
+    if (int rc = stream_request("decode_batch_dev_tone_plan (frame 0)", streams, lens, n,
+                                toned(roi, fmt, rs, warp, colour, tone, filter), out_bitdepth, out_chroma,
+                                !fmt || (warp && !warp->matrix) || (window && !warp) || !geom || !workspace_bytes, rq))
+        return rc;
+    rq.window = window;
+    return sink_plan(rq, geom, info, workspace_bytes);
+}
+
 extern "C" int ccmi_decode_batch_dev_flt(const uint8_t *const *streams, const size_t *lens, int n, const ccmi_rect *roi,
                                          void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
                                          const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
@@ -1270,6 +1304,20 @@ extern "C" int ccmi_decode_batch_dev_flt(const uint8_t *const *streams, const si
     DecodeRequest rq;
     if (int rc = stream_request("decode_batch_dev_flt (frame 0)", streams, lens, n,
                                 filtered(roi, fmt, rs, warp, colour, filter), out_bitdepth, out_chroma,
+                                !out_dev || !out_caps || !fmt || (warp && !warp->matrix), rq))
+        return rc;
+    return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ccmi_decode_batch_dev_tone(const uint8_t *const *streams, const size_t *lens, int n, const ccmi_rect *roi,
+                                          void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
+                                          const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
+                                          const ccmi_tone *tone, const ccmi_filter *filter, int out_bitdepth, int out_chroma,
+                                          void *workspace, size_t workspace_bytes, void *stream)
+{
+    DecodeRequest rq;
+    if (int rc = stream_request("decode_batch_dev_tone (frame 0)", streams, lens, n,
+                                toned(roi, fmt, rs, warp, colour, tone, filter), out_bitdepth, out_chroma,
                                 !out_dev || !out_caps || !fmt || (warp && !warp->matrix), rq))
         return rc;
     return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
@@ -1512,6 +1560,21 @@ extern "C" int ccmi_latents_render_flt_plan(const ccmi_latents *h, const int *in
     return sink_plan(rq, geom, info, workspace_bytes);
 }
 
+extern "C" int ccmi_latents_render_tone_plan(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
+                                             int out_bitdepth, int out_chroma, const ccmi_tensor_fmt *fmt,
+                                             const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
+                                             const ccmi_tone *tone, const ccmi_filter *filter, ccmi_frame_geom *geom,
+                                             ccmi_roi_info *info, ccmi_rect *window, size_t *workspace_bytes)
+{
+    DecodeRequest rq;
+    if (int rc = latents_request("latents_render_tone_plan (frame 0)", h, index, m,
+                                 toned(roi, fmt, rs, warp, colour, tone, filter), out_bitdepth, out_chroma, false,
+                                 !fmt || (warp && !warp->matrix) || (window && !warp) || !geom || !workspace_bytes, rq))
+        return rc;
+    rq.window = window;
+    return sink_plan(rq, geom, info, workspace_bytes);
+}
+
 extern "C" int ccmi_latents_render_flt(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
                                        void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
                                        const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
@@ -1521,6 +1584,20 @@ extern "C" int ccmi_latents_render_flt(const ccmi_latents *h, const int *index, 
     DecodeRequest rq;
     if (int rc = latents_request("latents_render_flt (frame 0)", h, index, m,
                                  filtered(roi, fmt, rs, warp, colour, filter), out_bitdepth, out_chroma, true,
+                                 !out_dev || !out_caps || !fmt || (warp && !warp->matrix), rq))
+        return rc;
+    return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ccmi_latents_render_tone(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
+                                        void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
+                                        const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
+                                        const ccmi_tone *tone, const ccmi_filter *filter, int out_bitdepth, int out_chroma,
+                                        void *workspace, size_t workspace_bytes, void *stream)
+{
+    DecodeRequest rq;
+    if (int rc = latents_request("latents_render_tone (frame 0)", h, index, m,
+                                 toned(roi, fmt, rs, warp, colour, tone, filter), out_bitdepth, out_chroma, true,
                                  !out_dev || !out_caps || !fmt || (warp && !warp->matrix), rq))
         return rc;
     return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);

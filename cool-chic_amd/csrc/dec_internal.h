@@ -191,6 +191,51 @@ struct DecFlt {
 // its filter entry and the taps in it (the workspace formula of ccmi.h)
 constexpr size_t kFltTableBytes = 256;
 
+// ccmi_tone of one staged frame (step 3x of the contract in ccmi.h), validated and resolved by the
+// plan; with device pointers filled by decode_run it is also the frame's entry of the tone tables the
+// kernels of dec_tone.hip read.  A call with a tone op has one for EVERY staged frame (n == 0: the
+// frame leaves every pass at once).  The list is cut into segments: a run of pointwise ops ended by
+// a whole-frame op (its terminator) or by the end of the list.
+struct DecToneOp {
+    int op;      // CCMI_TONE_*
+    float v[12]; // v[0] = f / th and, factors, v[1] = 1 - f; POSTERIZE: L, 1 / L, L - 1; MATRIX: M
+};
+struct DecToneSeg {
+    uint8_t first, end; // the segment's pointwise ops [first, end)
+    uint8_t term;       // its terminator's op code (ops[end]), or kToneNoTerm
+    uint8_t src;        // which of buf[] holds the frame when the segment starts
+    uint8_t acc;        // the terminator's accumulator block, counted from the frame's first
+    uint8_t pad_[3];
+};
+constexpr int kToneNoTerm = 255;
+struct DecTone {
+    float *buf[2] = {nullptr, nullptr}; // device: the staging frame and, with a sharpness op, the second frame
+    uint8_t *acc = nullptr;             // device: the frame's accumulator blocks, kToneAccBytes each
+    int n = 0, nseg = 0;
+    DecToneSeg seg[CCMI_TONE_MAX_OPS] = {};
+    DecToneOp ops[CCMI_TONE_MAX_OPS] = {};
+};
+static_assert(sizeof(DecTone) == 512, "kToneTableBytes per staged frame");
+// per staged frame of a call with a tone op, after the group's kFltTableBytes each
+constexpr size_t kToneTableBytes = 512;
+// one accumulator block: 3 x 256 bins, 3 complemented minima, 3 maxima (float bits), one 64-bit sum
+constexpr size_t kToneAccHist = 0, kToneAccMin = 3072, kToneAccMax = 3084, kToneAccSum = 3096, kToneAccBytes = 3328;
+inline int dec_tone_sharps(const DecTone &t)
+{
+    int k = 0;
+    for (int i = 0; i < t.n; ++i) k += t.ops[i].op == CCMI_TONE_SHARPNESS;
+    return k;
+}
+inline int dec_tone_stats(const DecTone &t)
+{
+    int k = 0;
+    for (int i = 0; i < t.n; ++i)
+        k += t.ops[i].op == CCMI_TONE_CONTRAST || t.ops[i].op == CCMI_TONE_AUTOCONTRAST || t.ops[i].op == CCMI_TONE_EQUALIZE;
+    return k;
+}
+// the table bytes of a staged frame: with a tone op in the call, its DecTone follows
+inline size_t dec_flt_table_bytes(bool tone) { return kFltTableBytes + (tone ? kToneTableBytes : 0); }
+
 // the form of a tail group's output section: the plain entry, or its resample / warp extension
 enum { kOutPlain = 0, kOutRs = 1, kOutWarp = 2 };
 inline int dec_out_form(const DecFmt &f) { return f.rs ? kOutRs : f.warp ? kOutWarp : kOutPlain; }
@@ -215,6 +260,9 @@ struct DecTailFrame {
     // frame, [3][oh][ow] of the stored frame
     const DecFlt *flt = nullptr;
     float *flt_tmp = nullptr;
+    // ccmi_tone with an op in the call: every staged frame's DecTone (in DecodePlan::tones; device
+    // pointers set by decode_run), NULL otherwise
+    const DecTone *tone = nullptr;
     // region decode on windows: the latent planes keep their frame pitch and hold roi.arm_rows[l]
     // rows, ups.workspace / ups.out / syn.out hold the windows roi.lev[k] / the region, compact
     // (pitch = the window's width); ups.lh / lw and syn.h / w stay the frame's true sizes
@@ -256,7 +304,8 @@ int launch_dec_out_frame(const DecTailFrame &f, const int32_t *synout, int h, in
 // The filter stage (dec_filter.hip).  The staged frames of a group, m of them, have their own tables,
 // kFltTableBytes per frame: [m] entries of the group's out_form for the staging launch (the frames'
 // entries with dst = the staging frame), then [m] filter entries.  dec_flt_fill writes frame i's of
-// both (host side; h, w, oy, ox as for dec_out_fill).
+// both (host side; h, w, oy, ox as for dec_out_fill).  With a tone op in the call (f.tone) the group's
+// table is dec_flt_table_bytes(true) per frame and [m] DecTone follow at kFltTableBytes * m.
 void dec_flt_fill(void *flt_tab, int m, int i, const DecTailFrame &f, int h, int w, int oy, int ox);
 // The output stage of the m staged frames fr[0 .. m) of a group: the group's output kernels in the
 // identity format into the staging frames (h x w and col_sec as for launch_dec_out_group, col_sec
@@ -265,6 +314,14 @@ int launch_dec_out_group_flt(const DecTailFrame *const *fr, int m, int h, int w,
                              const DecCol *col_sec, hipStream_t s);
 // launch_dec_out_frame for a frame that takes the stage (f.flt): staged, then dec_filter.
 int launch_dec_out_frame_flt(const DecTailFrame &f, const int32_t *synout, int h, int w, hipStream_t s);
+
+// The tone stage (dec_tone.hip), between the staging launches and the filter launch: segment after
+// segment, a statistics pass where a frame's terminator needs one, then the apply pass (in place) or
+// the sharpness pass (into the frame's other buffer).  es: the m entries in device memory, host: the
+// same on the host (the passes to launch are read off them).  The accumulators are cleared by the caller.
+int launch_dec_tone_group(const DecTone *dev_es, const DecTone *const *host, int m, int oh, int ow, hipStream_t s);
+// one frame, its entry as the kernels' own argument (the per-frame tail)
+int launch_dec_tone_frame(const DecTone &e, int oh, int ow, hipStream_t s);
 
 // Latent store (dec_latents.hip): the ARM output planes (int32, value << kArmPrec) packed to
 // values of the store's element type (CCMI_LATENT_*), and back.  Both kernels are table-driven:

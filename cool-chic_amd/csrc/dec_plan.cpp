@@ -250,6 +250,73 @@ int filter_frame(const ccmi_filter &fl, int i, size_t first, DecFlt &d, bool *ta
     return CCMI_OK;
 }
 
+// ccmi_tone of frame i, whose ops start at `first` of the flat array: validated, resolved (1 - f, the
+// posterize levels) and cut into segments in d
+int tone_ops(const ccmi_tone &tn, int i, size_t first, DecTone &d)
+{
+    const int n = tn.count[i];
+    if (n < 0 || n > CCMI_TONE_MAX_OPS)
+        return ccmi_set_error(CCMI_ERR_ARG, "frame %d: %d tone ops (0 .. %d)", i, n, CCMI_TONE_MAX_OPS);
+    d = DecTone{};
+    d.n = n;
+    int seg_first = 0, src = 0, acc = 0;
+    auto close = [&](int end, int term) {
+        DecToneSeg &g = d.seg[d.nseg++];
+        g.first = (uint8_t)seg_first, g.end = (uint8_t)end, g.term = (uint8_t)term, g.src = (uint8_t)src, g.acc = (uint8_t)acc;
+        seg_first = end + 1;
+    };
+    for (int k = 0; k < n; ++k) {
+        const ccmi_tone_op &op = tn.ops[first + k];
+        DecToneOp &o = d.ops[k];
+        o.op = op.op;
+        switch (op.op) {
+        case CCMI_TONE_MATRIX:
+            for (int e = 0; e < 12; ++e) {
+                if (!std::isfinite(op.v[e]))
+                    return ccmi_set_error(CCMI_ERR_ARG, "frame %d: tone op %d: matrix entry %d is not finite", i, k, e);
+                o.v[e] = op.v[e];
+            }
+            break;
+        case CCMI_TONE_BRIGHTNESS:
+        case CCMI_TONE_SATURATION:
+        case CCMI_TONE_CONTRAST:
+        case CCMI_TONE_SHARPNESS:
+            if (!std::isfinite(op.v[0]) || op.v[0] < 0.f)
+                return ccmi_set_error(CCMI_ERR_ARG, "frame %d: tone op %d: factor %g (finite, >= 0)", i, k, (double)op.v[0]);
+            o.v[0] = op.v[0] + 0.f;
+            o.v[1] = 1.f - o.v[0];
+            break;
+        case CCMI_TONE_SOLARIZE:
+            if (std::isnan(op.v[0])) return ccmi_set_error(CCMI_ERR_ARG, "frame %d: tone op %d: solarize threshold is NaN", i, k);
+            o.v[0] = op.v[0];
+            break;
+        case CCMI_TONE_POSTERIZE: {
+            const float b = op.v[0];
+            if (!(b >= 1.f && b <= 8.f) || b != (float)(int)b)
+                return ccmi_set_error(CCMI_ERR_ARG, "frame %d: tone op %d: posterize bits %g (an integer in 1 .. 8)", i, k,
+                                      (double)b);
+            const float L = (float)(1 << (int)b);
+            o.v[0] = L, o.v[1] = 1.0f / L, o.v[2] = L - 1.f;
+            break;
+        }
+        case CCMI_TONE_AUTOCONTRAST:
+        case CCMI_TONE_EQUALIZE:
+            break;
+        default:
+            return ccmi_set_error(CCMI_ERR_ARG, "frame %d: tone op %d: unknown op %d", i, k, op.op);
+        }
+        if (op.op == CCMI_TONE_SHARPNESS) {
+            close(k, op.op);
+            src ^= 1; // the later passes read the other buffer
+        } else if (op.op == CCMI_TONE_CONTRAST || op.op == CCMI_TONE_AUTOCONTRAST || op.op == CCMI_TONE_EQUALIZE) {
+            close(k, op.op);
+            ++acc;
+        }
+    }
+    if (seg_first < n) close(n, kToneNoTerm);
+    return CCMI_OK;
+}
+
 // the architecture part of a frame's tail arguments (no device pointers): what
 // dec_tail_batchable() looks at, the true plane sizes and the workspace sizes
 void tail_arch(const FrameHost &f, DecTailFrame &t)
@@ -462,6 +529,10 @@ void plan_layout(const DecodeRequest &rq, DecodePlan &pl)
         if (p.flt_elems) {
             p.flt_off = tot;
             tot += align_up(p.flt_elems * 4, 256);
+            if (!pl.tones.empty() && dec_tone_sharps(pl.tones[&p - pl.fr.data()])) {
+                p.tone2_off = tot;
+                tot += align_up(p.flt_elems * 4, 256);
+            }
         }
         p.out_off = tot;
         if (!rq.device()) tot += align_up(p.of.payload, 256); // device sinks write to the caller's memory
@@ -485,7 +556,15 @@ void plan_layout(const DecodeRequest &rq, DecodePlan &pl)
     tot += align_up(pl.lat_tab_cap, 256);
     // the filter stage's tables follow the job table in the same host image: the same upload
     pl.flt_tab_off = tot;
-    tot += kFltTableBytes * (size_t)pl.n_flt;
+    tot += pl.flt_table_bytes();
+    if (!pl.tones.empty()) { // ccmi_tone: the accumulator blocks of the call's statistic ops, frame after frame
+        pl.tone_acc_off = tot;
+        for (size_t i = 0; i < pl.fr.size(); ++i) {
+            pl.fr[i].tone_acc_off = tot;
+            tot += kToneAccBytes * (size_t)dec_tone_stats(pl.tones[i]);
+        }
+        pl.tone_acc_bytes = tot - pl.tone_acc_off;
+    }
     pl.col_off = tot;
     if (pl.col) tot += align_up(sizeof(unsigned long long) * pl.fr.size(), 256);
     pl.status_off = tot;
@@ -541,6 +620,27 @@ int decode_plan(const DecodeRequest &rq, DecodePlan &pl)
             pl.n_flt += t;
         }
     }
+    if (rq.tone) { // every frame's tone list: a frame with one takes the stage too
+        if (!rq.fmt || !rq.tone->count)
+            return ccmi_set_error(CCMI_ERR_ARG, "frame 0: tone ops without %s", rq.fmt ? "their counts" : "a format");
+        size_t first = 0;
+        bool any = false;
+        pl.tones.resize(rq.n);
+        for (int i = 0; i < rq.n; ++i) {
+            if (rq.tone->count[i] > 0 && !rq.tone->ops) return ccmi_set_error(CCMI_ERR_ARG, "frame %d: tone ops are NULL", i);
+            if (int rc = tone_ops(*rq.tone, i, first, pl.tones[i])) return rc;
+            first += (size_t)pl.tones[i].n;
+            any = any || pl.tones[i].n > 0;
+        }
+        if (!any) pl.tones.clear(); // no op in any frame: the call without tone
+        if (any) {
+            if (takes.empty()) takes.assign(rq.n, 0);
+            // a frame staged by its tone ops alone is formatted by the filter kernel: radius 0, no solarize
+            pl.flts.resize(rq.n);
+            for (int i = 0; i < rq.n; ++i)
+                if (pl.tones[i].n > 0 && !takes[i]) takes[i] = 1, ++pl.n_flt;
+        }
+    }
     if (!pl.n_flt) pl.flts.clear(); // no frame takes the stage: the call without a filter
     for (int i = 0; i < rq.n; ++i) {
         FramePlan &p = pl.fr[i];
@@ -551,6 +651,7 @@ int decode_plan(const DecodeRequest &rq, DecodePlan &pl)
             const DecFmt &d = p.tail.fmt;
             const bool sized = d.rs || d.warp;
             p.tail.flt = &pl.flts[i];
+            if (!pl.tones.empty()) p.tail.tone = &pl.tones[i];
             p.flt_elems = 3 * (size_t)(sized ? d.out_h : p.tail.roi.rect.h()) * (size_t)(sized ? d.out_w : p.tail.roi.rect.w());
         }
     }

@@ -90,6 +90,9 @@ struct DecodeRequest {
     // with fmt, optional: per-frame blur taps and solarize thresholds after the colour ops (ccmi_filter);
     // the frames that take the stage are staged in float32 and go through the filter kernel
     const ccmi_filter *filter = nullptr;
+    // with fmt, optional: per-frame lists of tone ops on the staged frame, after the colour ops and before
+    // the filter (ccmi_tone); a frame with a list takes the filter's stage
+    const ccmi_tone *tone = nullptr;
     // either sink
     const size_t *caps = nullptr;    // [n], optional: capacity in bytes of outs[i] / dev[i]
     size_t *sizes = nullptr;         // [n], optional: bytes written per stream (filled by the plan)
@@ -126,6 +129,8 @@ struct FramePlan {
     size_t lat_elems, ws_elems, dense_elems, synout_elems, synws_elems;
     size_t rs_off = 0, rs_elems = 0; // a resample's horizontal-pass intermediate (float32); none without one
     size_t flt_off = 0, flt_elems = 0; // the filter stage's staging frame (float32); none unless the frame takes it
+    size_t tone2_off = 0;              // ccmi_tone: a second frame of flt_elems for a list with a sharpness op
+    size_t tone_acc_off = 0;           // ccmi_tone: the frame's accumulator blocks, one per statistic op
 };
 
 struct DecodePlan {
@@ -148,6 +153,12 @@ struct DecodePlan {
     std::vector<DecFlt> flts;
     int n_flt = 0;
     size_t flt_tab_off = 0;
+    // ccmi_tone with an op in the call: every frame's DecTone (DecTailFrame::tone points here for the
+    // staged frames); the staged frames' tables grow to dec_flt_table_bytes(true), and tone_acc_bytes
+    // at tone_acc_off hold the accumulator blocks, cleared in stream before the tails run
+    std::vector<DecTone> tones;
+    size_t tone_acc_off = 0, tone_acc_bytes = 0;
+    size_t flt_table_bytes() const { return dec_flt_table_bytes(!tones.empty()) * (size_t)n_flt; }
 #if defined(CCMI_ARM_STAMPS)
     size_t dbg_off = 0;
 #endif

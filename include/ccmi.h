@@ -914,6 +914,105 @@ int ccmi_latents_render_flt(const ccmi_latents *h, const int *index /* [m] or NU
                             const ccmi_filter *filter /* or NULL */, int out_bitdepth, int out_chroma,
                             void *workspace, size_t workspace_bytes, void *stream);
 
+/* Tone ops: the filtered sink with a per-frame list of tone operations -- the photometric half of the op
+ * tables of RandAugment, TrivialAugmentWide and AutoAugment: brightness, colour (saturation), contrast,
+ * solarize, posterize, autocontrast, equalize and sharpness, in a drawn order -- applied in the decoder's
+ * output stage on the staged frame at the output size oh x ow:
+ *   3x. after step 3z (colour) and before steps 3y-1 / 3y-2 (blur, solarize) and step 4.
+ * Frame j TAKES THE STAGE when count[j] > 0, or when the filter already makes it (the ccmi_filter rule,
+ * unchanged).  The staged value is the x_c(i, k) of step 3y-0: stored column, after the mirror, + 0.0f.
+ * The ops of frame j run in the frame's own order, each over the whole frame before the next starts.
+ * Every product, sum, difference and division is one float32 operation in the order written (no fused
+ * multiply-add; a division is correctly rounded); clamp is to [0, 1] and a NaN clamps to 0; 1 - f is
+ * computed once on the host in float32.
+ *   CCMI_TONE_BRIGHTNESS f, CCMI_TONE_SATURATION f, CCMI_TONE_MATRIX M: the formulas of step 3z;
+ *   CCMI_TONE_CONTRAST f: the formula and the fixed-point mean S_j of step 3z, taken over the frame as it
+ *       stands before this op.  Any number per frame: here each is its own pass;
+ *   CCMI_TONE_SOLARIZE th (v[0]): x_c = (x_c >= th) ? 1.0f - x_c : x_c (step 3y-2's);
+ *   CCMI_TONE_POSTERIZE b (v[0] = b, an integer in 1..8), L = 2^b:
+ *       x_c = min(max(floorf(clamp(x_c) L), 0), L - 1) (1.0f / L)   (torchvision v2's float form; 1 / L is exact);
+ *   CCMI_TONE_AUTOCONTRAST: per channel lo_c, hi_c = the min and max over the frame of clamp(x_c).
+ *       hi_c == lo_c: the channel is unchanged.  Otherwise s = 1.0f / (hi_c - lo_c) and
+ *       x_c = clamp((x_c - lo_c) s).  Min and max do not depend on the order of reduction;
+ *   CCMI_TONE_EQUALIZE, per channel, N = oh ow (N <= 2^28: everything fits 32 bits):
+ *       q = (int) rintf(clamp(x_c) 255.0f), ties to even; H_c[0..255] = the histogram of q over the frame;
+ *       last = the highest non-empty bin; step = (N - H_c[last]) / 255 (integer division);
+ *       step == 0: lut = the identity; otherwise lut[0] = 0 and, t >= 1,
+ *       lut[t] = min(255, ((sum_{u < t} H_c[u]) + step / 2) / step)   (torchvision's _equalize_single_image);
+ *       x_c = (float)lut[q] / 255.0f.  The op always quantises, also when the LUT is the identity;
+ *   CCMI_TONE_SHARPNESS f (f >= 0): oh <= 2 or ow <= 2: the frame is unchanged.  Otherwise, for interior
+ *       pixels (0 < i < oh - 1, 0 < k < ow - 1),
+ *       b_c = sum over di = -1..1, dk = -1..1 (di outer, both ascending, from 0.0f) of w(di, dk) x_c(i + di, k + dk),
+ *       w = (float)(5.0 / 13.0) at the centre and (float)(1.0 / 13.0) elsewhere; on the border b_c = x_c;
+ *       x_c = clamp((f x_c) + ((1 - f) b_c)), all reads of the frame as it stood before this op
+ *       (torchvision's adjust_sharpness).
+ * In a warp, pixels that come from `fill` count in every statistic like any others.
+ * BATCH INVARIANCE: every statistic is an integer sum or a min / max (accumulated with integer atomics in
+ * the workspace, cleared in stream), so a frame gives the same bits alone or in any batch, call after call.
+ *
+ * One superset pair per source: the _flt argument list with `tone` between `colour` and `filter`.  tone
+ * NULL, or every count 0: exactly the _flt call -- plan, workspace, launches and bits;
+ * ccmi_decode_last_tail_groups is what the call without tone reports and the frames of one tail group
+ * stay one group.  Otherwise, with S = the frames that take the stage (by either rule), the workspace is
+ * that of the _flt call in which exactly those S frames take the stage, plus exactly
+ *     512 S  +  sum over the frames with a SHARPNESS op of (12 oh ow rounded up to 256)  +  3328 A   bytes,
+ * A = the number of CONTRAST, AUTOCONTRAST and EQUALIZE ops in the call: a 512-byte entry of the tone
+ * tables per staged frame (its op list and segments; uploaded with the rest of the tables in one copy,
+ * not in the tail's per-frame arguments), a second float32 frame where a sharpness op cannot run in place,
+ * and one accumulator block per statistic op (3 x 256 uint32 bins, 3 minima, 3 maxima, one uint64: 3104
+ * bytes rounded to 256).  A frame staged by its tone ops alone costs what ccmi_filter states for a staged
+ * frame: (12 oh ow rounded up to 256) + 256 bytes.
+ * A frame's list is cut into segments, a run of pointwise ops ended by a whole-frame op; segment p of all
+ * staged frames of a tail group shares its launches (a statistics pass, then an apply or sharpness pass),
+ * and the filter kernel then formats the frame (radius 0 and no solarize for a frame without a filter).
+ * Checked by the plan before any GPU work, CCMI_ERR_ARG naming the frame and nothing written: count or
+ * ops NULL, a count outside [0, CCMI_TONE_MAX_OPS], an unknown op, a negative or non-finite factor, a
+ * non-finite matrix entry, a NaN threshold, posterize bits that are not an integer in 1..8; and
+ * everything the _flt plan checks.
+ * Measured (profiles/decode_tone_ab.txt): 960 class-E streams from an int16 store, RandomResizedCrop windows
+ * x RandAugment(2, 9) draws warped to 224 x 224, bf16 RGB normalised (761 frames take the stage): 41.5 ms
+ * per call (tail 37.5 ms) against 40.4-40.5 ms (tail 36.9-37.0 ms) for the call without tone ops and
+ * 45.9-46.0 ms for the float32 render followed by the same ops as torch operations; peak allocation above
+ * store and workspace 276 MiB against 1654 MiB; the workspace grows by 507 MiB. */
+enum { CCMI_TONE_BRIGHTNESS = 0, CCMI_TONE_SATURATION = 1, CCMI_TONE_CONTRAST = 2, CCMI_TONE_MATRIX = 3,
+       CCMI_TONE_SOLARIZE = 4, CCMI_TONE_POSTERIZE = 5, CCMI_TONE_AUTOCONTRAST = 6,
+       CCMI_TONE_EQUALIZE = 7, CCMI_TONE_SHARPNESS = 8 };
+enum { CCMI_TONE_MAX_OPS = 8 };
+typedef struct ccmi_tone_op {
+    int op;      /* CCMI_TONE_* */
+    float v[12]; /* v[0] = the factor, threshold or bits; CCMI_TONE_MATRIX: M, row-major 3 x 4 */
+} ccmi_tone_op;
+typedef struct ccmi_tone {
+    const int *count;        /* host, [n]: ops of frame j, 0 .. CCMI_TONE_MAX_OPS */
+    const ccmi_tone_op *ops; /* host, flat: frame j's ops follow frame j - 1's */
+} ccmi_tone;
+int ccmi_decode_batch_dev_tone_plan(const uint8_t *const *streams, const size_t *lens, int n,
+                                    const ccmi_rect *roi /* [n] or NULL */, int out_bitdepth, int out_chroma,
+                                    const ccmi_tensor_fmt *fmt, const ccmi_resample *rs /* or NULL */,
+                                    const ccmi_warp *warp /* or NULL */, const ccmi_colour *colour /* or NULL */,
+                                    const ccmi_tone *tone /* or NULL */, const ccmi_filter *filter /* or NULL */,
+                                    ccmi_frame_geom *geom /* [n] */, ccmi_roi_info *info /* [n] or NULL */,
+                                    ccmi_rect window[] /* [n] or NULL; warp only */, size_t *workspace_bytes);
+int ccmi_decode_batch_dev_tone(const uint8_t *const *streams, const size_t *lens, int n,
+                               const ccmi_rect *roi /* [n] or NULL */, void *const *out_dev, const size_t *out_caps,
+                               const ccmi_tensor_fmt *fmt, const ccmi_resample *rs /* or NULL */,
+                               const ccmi_warp *warp /* or NULL */, const ccmi_colour *colour /* or NULL */,
+                               const ccmi_tone *tone /* or NULL */, const ccmi_filter *filter /* or NULL */,
+                               int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes, void *stream);
+int ccmi_latents_render_tone_plan(const ccmi_latents *h, const int *index /* [m] or NULL */, int m,
+                                  const ccmi_rect *roi /* [m] or NULL */, int out_bitdepth, int out_chroma,
+                                  const ccmi_tensor_fmt *fmt, const ccmi_resample *rs /* or NULL */,
+                                  const ccmi_warp *warp /* or NULL */, const ccmi_colour *colour /* or NULL */,
+                                  const ccmi_tone *tone /* or NULL */, const ccmi_filter *filter /* or NULL */,
+                                  ccmi_frame_geom *geom /* [m] */, ccmi_roi_info *info /* [m] or NULL */,
+                                  ccmi_rect window[] /* [m] or NULL; warp only */, size_t *workspace_bytes);
+int ccmi_latents_render_tone(const ccmi_latents *h, const int *index /* [m] or NULL */, int m,
+                             const ccmi_rect *roi /* [m] or NULL */, void *const *out_dev, const size_t *out_caps,
+                             const ccmi_tensor_fmt *fmt, const ccmi_resample *rs /* or NULL */,
+                             const ccmi_warp *warp /* or NULL */, const ccmi_colour *colour /* or NULL */,
+                             const ccmi_tone *tone /* or NULL */, const ccmi_filter *filter /* or NULL */,
+                             int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Network weights of a stream's intra frame as the decoder's fixed-point integers
  * (cc-frame-decoder.cpp:201-353, read_arm / read_ups / read_syn):
  *   arm: per hidden layer W[d][d] (out, in) then b[d]; then W_out[2][d], b_out[2]
