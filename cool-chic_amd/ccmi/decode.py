@@ -388,7 +388,7 @@ class TensorFmt(C.Structure):
                 ("stride_c", C.c_int64), ("stride_y", C.c_int64), ("stride_x", C.c_int64), ("mirror", C.c_void_p)]
 
 
-FILTER_TRIANGLE = 0  # CCMI_FILTER_*
+FILTER_TRIANGLE, FILTER_CUBIC, FILTER_CLAMP = 0, 2, 0x100  # CCMI_FILTER_*
 
 
 class Resample(C.Structure):
@@ -396,14 +396,27 @@ class Resample(C.Structure):
     _fields_ = [("out_w", C.c_int), ("out_h", C.c_int), ("filter", C.c_int)]
 
 
-def _resample(size):
-    """size=(out_h, out_w) of a *_model call -> ccmi_resample (the library checks the range)."""
+def _resample(size, interp=(FILTER_TRIANGLE, 0)):
+    """size=(out_h, out_w) of a *_model call -> ccmi_resample (the library checks the range);
+    interp: _interp()'s pair."""
     if len(size) != 2:
         raise ValueError(f"model output: size takes (out_h, out_w), got {size!r}")
-    return Resample(out_w=int(size[1]), out_h=int(size[0]), filter=FILTER_TRIANGLE)
+    return Resample(out_w=int(size[1]), out_h=int(size[0]), filter=interp[0])
 
 
 PAD_FILL, PAD_EDGE = 0, 1  # CCMI_PAD_*
+WARP_CUBIC, WARP_CLAMP = 0x100, 0x200  # or'ed into ccmi_warp.pad
+
+
+def _interp(interpolation, clamp):
+    """interpolation= / clamp= of a *_model call -> (ccmi_resample.filter, the flags of ccmi_warp.pad)."""
+    if interpolation not in ("bilinear", "bicubic"):
+        raise ValueError(f"model output: interpolation {interpolation!r} ('bilinear' or 'bicubic')")
+    if interpolation == "bilinear":
+        if clamp:
+            raise ValueError("model output: clamp=True needs interpolation='bicubic'")
+        return FILTER_TRIANGLE, 0
+    return (FILTER_CUBIC | FILTER_CLAMP, WARP_CUBIC | WARP_CLAMP) if clamp else (FILTER_CUBIC, WARP_CUBIC)
 
 
 class Warp(C.Structure):
@@ -412,9 +425,9 @@ class Warp(C.Structure):
                 ("matrix", C.c_void_p)]
 
 
-def _warp(affine, n, size, roi, pad, fill):
+def _warp(affine, n, size, roi, pad, fill, interp=(FILTER_TRIANGLE, 0)):
     """affine= / pad= / fill= of a *_model call -> (ccmi_warp, what it points to), or (None, None)
-    without affine.  The library checks the values; the shapes are checked here."""
+    without affine.  The library checks the values; the shapes are checked here.  interp: _interp()'s pair."""
     import numpy as np
     if affine is None:
         return None, None
@@ -436,7 +449,7 @@ def _warp(affine, n, size, roi, pad, fill):
     f = [float(v) for v in fill] if hasattr(fill, "__len__") else [float(fill)] * 3
     if len(f) != 3:
         raise ValueError("model output: fill takes one value, or one per channel")
-    w = Warp(out_w=int(size[1]), out_h=int(size[0]), pad=pads[pad], matrix=a.ctypes.data)
+    w = Warp(out_w=int(size[1]), out_h=int(size[0]), pad=pads[pad] | interp[1], matrix=a.ctypes.data)
     for c in range(3):
         w.fill[c] = f[c]
     return w, a
@@ -950,16 +963,17 @@ def _plan_model(plan, head, n, rects, fmt, rs, output_bitdepth, output_chroma_fo
 
 
 def _run_model(plan, run, head, n, rects, dev, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth,
-               output_chroma_format, workspace, stream_handle, size, warp=None, col=None, flt=None, tone=None):
+               output_chroma_format, workspace, stream_handle, size, warp=None, col=None, flt=None, tone=None,
+               interp=(FILTER_TRIANGLE, 0)):
     """The body of decode_batch_model and LatentStore.render_model: plan / run are the source's
     *_rs_plan / *_rs entry points, or with warp (a ccmi_warp, which carries the size) its
     *_warp_plan / *_warp ones, or with col (a ccmi_colour) its *_col_plan / *_col ones, or with flt (a
     ccmi_filter) its *_flt_plan / *_flt ones, or with tone (a ccmi_tone) its *_tone_plan / *_tone ones; head their first two arguments; dev None: the current
-    device."""
+    device.  interp: _interp()'s pair, for the resample (a warp carries its own)."""
     import torch
     dtype = torch.float32 if dtype is None else dtype
     fmt, keep = _model_fmt(n, colour, mean, std, dtype, mirror)
-    rs = None if size is None or warp is not None else C.byref(_resample(size))
+    rs = None if size is None or warp is not None else C.byref(_resample(size, interp))
     geom, need = _plan_model(plan, head, n, rects, fmt, rs, output_bitdepth, output_chroma_format, warp, col=col, flt=flt,
                              tone=tone)
     dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else dev
@@ -992,7 +1006,7 @@ def decode_batch_model(streams: Sequence[bytes], roi=None, colour: str = "rgb", 
                        channels_last: bool = False, mirror=None, out=None, output_bitdepth: int = 0,
                        output_chroma_format: int = 0, workspace=None, stream_handle: int | None = None, size=None,
                        affine=None, pad: str = "fill", fill=0.0, colour_ops=None, blur=None, solarize=None,
-                       tone_ops=None):
+                       tone_ops=None, interpolation: str = "bilinear", clamp: bool = False):
     """Decode .cool streams into the tensor a model takes (ccmi_decode_batch_dev_fmt): one
     [n, 3, h, w] tensor of `dtype` (torch.float32, the default, torch.float16 or torch.bfloat16),
     every channel at full size (420 chroma nearest-upsampled), RGB (colour="rgb": YUV streams go
@@ -1048,11 +1062,19 @@ def decode_batch_model(streams: Sequence[bytes], roi=None, colour: str = "rgb", 
     whole frame before the next: ('brightness', f), ('saturation', f), ('contrast', f), ('matrix', M),
     ('solarize', th), ('posterize', bits 1..8), ('autocontrast', None), ('equalize', None),
     ('sharpness', f).  rand_augment() and trivial_augment_wide() draw such lists (and the matrices for
-    affine=).  A frame with a list is staged like a blurred one; the others keep their kernels and bits."""
+    affine=).  A frame with a list is staged like a blurred one; the others keep their kernels and bits.
+
+    interpolation="bicubic" (CCMI_FILTER_CUBIC / CCMI_WARP_CUBIC; one value per call, "bilinear" is the
+    default and the call as it always was): size= resamples with the antialiased Keys cubic of
+    interpolate(mode="bicubic", antialias=True) and of PIL's BICUBIC, affine= samples 16 taps as
+    grid_sample(mode="bicubic") does.  A bicubic result may leave [0, 1], as torch's; clamp=True
+    (bicubic only) clamps it to [0, 1] before the colour ops and the normalisation, which is what a
+    uint8 pipeline gives.  Any other string, and clamp=True with "bilinear", is a ValueError."""
     n = len(streams)
     keep, sp, ln = _marshal(streams)
     L = _bind()
-    warp, keep_w = _warp(affine, n, size, roi, pad, fill)
+    interp = _interp(interpolation, clamp)
+    warp, keep_w = _warp(affine, n, size, roi, pad, fill, interp)
     col, keep_c = _colour(colour_ops, n)
     flt, keep_f = _filter(blur, solarize, n)
     tone, keep_t = _tone(tone_ops, n)
@@ -1060,24 +1082,24 @@ def decode_batch_model(streams: Sequence[bytes], roi=None, colour: str = "rgb", 
         return _run_model(L.ccmi_decode_batch_dev_tone_plan, L.ccmi_decode_batch_dev_tone, (sp, ln), n,
                           None if warp is not None else _rects(roi, streams, n), None, colour, mean, std, dtype,
                           channels_last, mirror, out, output_bitdepth, output_chroma_format, workspace, stream_handle, size,
-                          warp, col, flt, tone)
+                          warp, col, flt, tone, interp=interp)
     if flt is not None:
         return _run_model(L.ccmi_decode_batch_dev_flt_plan, L.ccmi_decode_batch_dev_flt, (sp, ln), n,
                           None if warp is not None else _rects(roi, streams, n), None, colour, mean, std, dtype,
                           channels_last, mirror, out, output_bitdepth, output_chroma_format, workspace, stream_handle, size,
-                          warp, col, flt)
+                          warp, col, flt, interp=interp)
     if col is not None:
         return _run_model(L.ccmi_decode_batch_dev_col_plan, L.ccmi_decode_batch_dev_col, (sp, ln), n,
                           None if warp is not None else _rects(roi, streams, n), None, colour, mean, std, dtype,
                           channels_last, mirror, out, output_bitdepth, output_chroma_format, workspace, stream_handle, size,
-                          warp, col)
+                          warp, col, interp=interp)
     if warp is not None:
         return _run_model(L.ccmi_decode_batch_dev_warp_plan, L.ccmi_decode_batch_dev_warp, (sp, ln), n, None, None,
                           colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth, output_chroma_format,
-                          workspace, stream_handle, size, warp)
+                          workspace, stream_handle, size, warp, interp=interp)
     return _run_model(L.ccmi_decode_batch_dev_rs_plan, L.ccmi_decode_batch_dev_rs, (sp, ln), n, _rects(roi, streams, n),
                       None, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth, output_chroma_format,
-                      workspace, stream_handle, size)
+                      workspace, stream_handle, size, interp=interp)
 
 
 def weights_i32(stream: bytes):
@@ -1468,7 +1490,7 @@ class LatentStore:
                      channels_last: bool = False, mirror=None, out=None, output_bitdepth: int = 0,
                      output_chroma_format: int = 0, workspace=None, stream_handle: int | None = None, size=None,
                      affine=None, pad: str = "fill", fill=0.0, colour_ops=None, blur=None, solarize=None,
-                     tone_ops=None):
+                     tone_ops=None, interpolation: str = "bilinear", clamp: bool = False):
         """render() into the tensor a model takes (ccmi_latents_render_fmt; with size
         ccmi_latents_render_rs; with affine ccmi_latents_render_warp): frames and regions as for
         render(), the result and every other argument as for decode_batch_model, whose output for
@@ -1477,40 +1499,44 @@ class LatentStore:
         warp's windows are not part of render_geometry()'s figure).  With colour_ops
         ccmi_latents_render_col, with blur or solarize ccmi_latents_render_flt, with tone_ops
         ccmi_latents_render_tone:
-        render_model_workspace_bytes() takes the same arguments."""
+        render_model_workspace_bytes() takes the same arguments.  interpolation= / clamp= as for
+        decode_batch_model (a bicubic warp's windows, and so its workspace, are a tap wider)."""
         m, idx, rects = self._frames(index, None if affine is not None else roi)
         L = _bind()
-        warp, keep_w = _warp(affine, m, size, roi, pad, fill)
+        interp = _interp(interpolation, clamp)
+        warp, keep_w = _warp(affine, m, size, roi, pad, fill, interp)
         col, keep_c = _colour(colour_ops, m)
         flt, keep_f = _filter(blur, solarize, m)
         tone, keep_t = _tone(tone_ops, m)
         if tone is not None:
             return _run_model(L.ccmi_latents_render_tone_plan, L.ccmi_latents_render_tone, (self._handle(), idx), m, rects,
                               self._store.device, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth,
-                              output_chroma_format, workspace, stream_handle, size, warp, col, flt, tone)
+                              output_chroma_format, workspace, stream_handle, size, warp, col, flt, tone,
+                              interp=interp)
         if flt is not None:
             return _run_model(L.ccmi_latents_render_flt_plan, L.ccmi_latents_render_flt, (self._handle(), idx), m, rects,
                               self._store.device, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth,
-                              output_chroma_format, workspace, stream_handle, size, warp, col, flt)
+                              output_chroma_format, workspace, stream_handle, size, warp, col, flt, interp=interp)
         if col is not None:
             return _run_model(L.ccmi_latents_render_col_plan, L.ccmi_latents_render_col, (self._handle(), idx), m, rects,
                               self._store.device, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth,
-                              output_chroma_format, workspace, stream_handle, size, warp, col)
+                              output_chroma_format, workspace, stream_handle, size, warp, col, interp=interp)
         if warp is not None:
             return _run_model(L.ccmi_latents_render_warp_plan, L.ccmi_latents_render_warp, (self._handle(), idx), m,
                               None, self._store.device, colour, mean, std, dtype, channels_last, mirror, out,
-                              output_bitdepth, output_chroma_format, workspace, stream_handle, size, warp)
+                              output_bitdepth, output_chroma_format, workspace, stream_handle, size, warp, interp=interp)
         return _run_model(L.ccmi_latents_render_rs_plan, L.ccmi_latents_render_rs, (self._handle(), idx), m, rects,
                           self._store.device, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth,
-                          output_chroma_format, workspace, stream_handle, size)
+                          output_chroma_format, workspace, stream_handle, size, interp=interp)
 
     def warp_plan(self, index, affine, size, pad: str = "fill", fill=0.0, output_bitdepth: int = 0,
-                  output_chroma_format: int = 0) -> list:
+                  output_chroma_format: int = 0, interpolation: str = "bilinear", clamp: bool = False) -> list:
         """What render_model(affine=...) will do, per output frame (ccmi_latents_render_warp_plan,
         header-only), like roi_plan: {'window': (x, y, w, h), the rectangle of the frame the tail
-        renders for that frame's matrix, 'windowed', 'arm_rows'}."""
+        renders for that frame's matrix, 'windowed', 'arm_rows'}.  interpolation="bicubic": the window
+        of the 16 taps, one pixel wider on every side the frame allows."""
         m, idx, _ = self._frames(index, None)
-        warp, keep_w = _warp(affine, m, size, None, pad, fill)
+        warp, keep_w = _warp(affine, m, size, None, pad, fill, _interp(interpolation, clamp))
         if warp is None:
             raise ValueError("LatentStore.warp_plan: affine is None")
         fmt = TensorFmt(elem=ELEM_F32, colour=COLOUR_ASIS)
@@ -1524,7 +1550,8 @@ class LatentStore:
 
     def render_model_workspace_bytes(self, index=None, roi=None, size=None, output_bitdepth: int = 0,
                                      output_chroma_format: int = 0, affine=None, pad: str = "fill", fill=0.0,
-                                     colour_ops=None, blur=None, solarize=None, tone_ops=None) -> int:
+                                     colour_ops=None, blur=None, solarize=None, tone_ops=None,
+                                     interpolation: str = "bilinear", clamp: bool = False) -> int:
         """Header-only: the workspace render_model needs for these frames, regions and size, or
         these frames, matrices and size (ccmi_latents_render_rs_plan / _warp_plan; the element type,
         colour and strides do not change it), these colour ops (ccmi_latents_render_col_plan:
@@ -1535,26 +1562,27 @@ class LatentStore:
         fmt = TensorFmt(elem=ELEM_F32, colour=COLOUR_ASIS)
         for c in range(3):
             fmt.scale[c] = 1.0
-        warp, keep_w = _warp(affine, m, size, roi, pad, fill)
+        interp = _interp(interpolation, clamp)
+        warp, keep_w = _warp(affine, m, size, roi, pad, fill, interp)
         col, keep_c = _colour(colour_ops, m)
         flt, keep_f = _filter(blur, solarize, m)
         tone, keep_t = _tone(tone_ops, m)
         if tone is not None:
-            rs = None if size is None or warp is not None else C.byref(_resample(size))
+            rs = None if size is None or warp is not None else C.byref(_resample(size, interp))
             return _plan_model(_bind().ccmi_latents_render_tone_plan, (self._handle(), idx), m, rects, fmt, rs,
                                output_bitdepth, output_chroma_format, warp, col=col, flt=flt, tone=tone)[1]
         if flt is not None:
-            rs = None if size is None or warp is not None else C.byref(_resample(size))
+            rs = None if size is None or warp is not None else C.byref(_resample(size, interp))
             return _plan_model(_bind().ccmi_latents_render_flt_plan, (self._handle(), idx), m, rects, fmt, rs,
                                output_bitdepth, output_chroma_format, warp, col=col, flt=flt)[1]
         if col is not None:
-            rs = None if size is None or warp is not None else C.byref(_resample(size))
+            rs = None if size is None or warp is not None else C.byref(_resample(size, interp))
             return _plan_model(_bind().ccmi_latents_render_col_plan, (self._handle(), idx), m, rects, fmt, rs,
                                output_bitdepth, output_chroma_format, warp, col=col)[1]
         if warp is not None:
             return _plan_model(_bind().ccmi_latents_render_warp_plan, (self._handle(), idx), m, None, fmt, None,
                                output_bitdepth, output_chroma_format, warp)[1]
-        rs = None if size is None else C.byref(_resample(size))
+        rs = None if size is None else C.byref(_resample(size, interp))
         return _plan_model(_bind().ccmi_latents_render_rs_plan, (self._handle(), idx), m, rects, fmt, rs, output_bitdepth,
                            output_chroma_format)[1]
 

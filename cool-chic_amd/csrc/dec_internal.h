@@ -159,6 +159,10 @@ struct DecFmt {
     int pad = 0;
     float fill[3] = {0.f, 0.f, 0.f};
     float m[6] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f};
+    // CCMI_FILTER_CUBIC / CCMI_WARP_CUBIC (one per call): the cubic forms of the rs / warp kernels
+    // (dec_cubic_h, dec_cubic_v<T>, dec_wcubic<T>); clamp: their r' is clamped to [0, 1].  pad is
+    // CCMI_PAD_FILL or CCMI_PAD_EDGE, without the flags
+    int cubic = 0, clamp = 0;
     // ccmi_colour with at least one op in the call (one value per call): the colour forms of the
     // output kernels run, each frame with its own DecCol (DecTailFrame::col), after any of the above
     int col = 0;

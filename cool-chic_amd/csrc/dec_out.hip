@@ -11,6 +11,9 @@
 //                   antialiased triangle filter to the output size, horizontal then vertical pass.
 //  dec_warp         the formatted tensor with a ccmi_warp: every output pixel a bilinear sample of
 //                   the frame at the position the frame's 2 x 3 matrix gives, fill or edge padding.
+//  dec_cubic_h, dec_cubic_v, dec_wcubic  the bicubic forms of the three kernels above
+//                   (CCMI_FILTER_CUBIC: the Keys cubic, a = -0.5, antialiased; CCMI_WARP_CUBIC:
+//                   cubic convolution, A = -0.75, 16 taps), with the optional clamp of r' to [0, 1].
 //  *_col, *_stat    the colour forms of the three formatted kernels (ccmi_colour) and their
 //                   statistics pass.
 //
@@ -232,7 +235,9 @@ __device__ constexpr float kFmtB[3] = {(float)1.4019975662231445, (float)-0.7141
 __device__ constexpr float kFmtO[3] = {(float)(-179.45477266423404 / 255.0), (float)(135.45870971679688 / 255.0),
                                        (float)(-226.8183044444304 / 255.0)};
 
-enum { kFmtMirror = 1, kFmtMatrix = 2 }; // per-frame flags (DecOut::bps_or_flags of a formatted group)
+// per-frame flags (DecOut::bps_or_flags of a formatted group); kFmtClamp is a cubic call's (one per
+// call): its kernels clamp r' to [0, 1], the others never see it
+enum { kFmtMirror = 1, kFmtMatrix = 2, kFmtClamp = 4 };
 
 // steps 1-3 of the contract for one pixel: lrow / crow point at the pixel's luma row and at the
 // row its chroma is taken from, x / xc are its luma and chroma columns
@@ -427,7 +432,10 @@ unsigned output_fmt_blocks(int h, int w)
     return (unsigned)(((int64_t)h * fmt_row_groups(w) + kThreads - 1) / kThreads);
 }
 
-int fmt_flags(const DecFmt &f) { return (f.mirror ? kFmtMirror : 0) | (f.matrix ? kFmtMatrix : 0); }
+int fmt_flags(const DecFmt &f)
+{
+    return (f.mirror ? kFmtMirror : 0) | (f.matrix ? kFmtMatrix : 0) | (f.cubic && f.clamp ? kFmtClamp : 0);
+}
 
 // ------------------------------------------------------------------ resampled formatted output
 // The formatted sink with a ccmi_resample (steps 3a-3c of the contract in ccmi.h): the region,
@@ -466,6 +474,48 @@ __device__ __forceinline__ RsTaps rs_taps(int i, int I, int O)
     return t;
 }
 
+// CCMI_FILTER_CUBIC (step 3a of its contract in ccmi.h): the Keys cubic, a = -0.5, in the same
+// integers.  n = |(2j + 1) O - c| < 2 D2 <= 2^16 over the run, so u takes int64: Horner, every
+// intermediate below 2^51; U below 2^61.  A tap at the end of the run may have u = 0.
+struct CubTaps {
+    int j0, j1, c, O, D2;
+    float fU;
+    __device__ __forceinline__ int64_t u(int j) const
+    {
+        const int64_t n = abs((2 * j + 1) * O - c), d = D2;
+        return n < d ? ((3 * n - 5 * d) * n) * n + 2 * d * d * d : (((5 * d - n) * n - 8 * d * d) * n) + 4 * d * d * d;
+    }
+    __device__ __forceinline__ float w(int j) const { return __fdiv_rn((float)u(j), fU); }
+};
+
+__device__ __forceinline__ CubTaps cub_taps(int i, int I, int O)
+{
+    CubTaps t;
+    t.O = O;
+    t.D2 = 2 * max(I, O);
+    t.c = (2 * i + 1) * I;
+    // n < 2 D2: (c - 2 D2 - O) / 2O < j < (c + 2 D2 - O) / 2O, clipped to the region
+    const int a = t.c - 2 * t.D2 - O, b = t.c + 2 * t.D2 - O; // b >= 1
+    t.j0 = a >= 0 ? a / (2 * O) + 1 : 0;
+    t.j1 = min((b - 1) / (2 * O), I - 1);
+    int64_t U = 0;
+    for (int j = t.j0; j <= t.j1; ++j) U += t.u(j);
+    t.fU = (float)U;
+    return t;
+}
+
+// The int64 weights take the cubic resize kernels a few registers past 64; asked for 8 waves per SIMD
+// the compiler keeps them at 60 or below without a spill (tests/test_decode_cubic_resources.py).  The
+// typed cubic warp kernels spill at 64 and are left to the allocator (72 - 91, 5 - 7 waves).
+#define CUBIC_WAVES8 __attribute__((amdgpu_waves_per_eu(8)))
+
+// the taps of output index i of an axis resampled from I to O: the triangle's, or the cubic's
+template <bool CUBIC> __device__ __forceinline__ auto axis_taps(int i, int I, int O)
+{
+    if constexpr (CUBIC) return cub_taps(i, I, O);
+    else return rs_taps(i, I, O);
+}
+
 // one frame of a resampling group: DecOut as for dec_output_fmt_batch (H x W = the region, compact)
 struct DecOutRs {
     DecOut o;
@@ -473,6 +523,7 @@ struct DecOutRs {
 };
 
 // h x w = the region at (oy, ox) of the synthesis output, as for output_fmt_body
+template <bool CUBIC = false>
 __device__ __forceinline__ void resample_h_body(const int32_t *__restrict__ syn, int64_t splane, int spitch, int oy, int ox,
                                                 int h, int w, int ow, int maxv, int kind, int flags,
                                                 float *__restrict__ tmp)
@@ -481,7 +532,7 @@ __device__ __forceinline__ void resample_h_body(const int32_t *__restrict__ syn,
     const int y = (int)(g / ow);
     if (y >= h) return;
     const int i = (int)(g - (int64_t)y * ow);
-    const RsTaps T = rs_taps(i, w, ow);
+    const auto T = axis_taps<CUBIC>(i, w, ow);
     const float fmax = (float)maxv;
     const bool matrix = flags & kFmtMatrix;
     const int32_t *__restrict__ lrow = syn + (int64_t)(oy + y) * spitch + ox;
@@ -500,7 +551,7 @@ __device__ __forceinline__ void resample_h_body(const int32_t *__restrict__ syn,
 }
 
 // tmp = [3][h][ow] of resample_h_body; the frame at dst is oh x ow
-template <typename T, int COL = kColNone>
+template <typename T, int COL = kColNone, bool CUBIC = false>
 __device__ __forceinline__ uint32_t resample_v_body(const float *__restrict__ tmp, int h, int oh, int ow, int flags,
                                                     T *__restrict__ dst, const DecFmtCall &C, const DecCol *K = nullptr)
 {
@@ -508,7 +559,7 @@ __device__ __forceinline__ uint32_t resample_v_body(const float *__restrict__ tm
     int64_t row;
     bool nchw, nhwc;
     if (!fmt_group<T>(dst, C, oh, ow, y, d0, row, nchw, nhwc)) return 0;
-    const RsTaps R = rs_taps(y, h, oh);
+    const auto R = axis_taps<CUBIC>(y, h, oh);
     const bool mirror = flags & kFmtMirror;
     // element indices of tmp fit 32 bits (3 h ow <= 3 * 2^28): one base and 32-bit offsets
     const unsigned tplane = (unsigned)h * (unsigned)ow;
@@ -528,6 +579,14 @@ __device__ __forceinline__ uint32_t resample_v_body(const float *__restrict__ tm
         for (int c = 0; c < 3; ++c)
 #pragma unroll
             for (int k = 0; k < 4; ++k) acc[c][k] = fmt_add(acc[c][k], fmt_mul(wj, tmp[c * tplane + r0 + x[k]]));
+    }
+    if constexpr (CUBIC) {
+        if (flags & kFmtClamp) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) acc[c][k] = col_clamp(acc[c][k]);
+        }
     }
     if constexpr (COL != kColNone) {
         const float mean = COL == kColWrite ? col_mean(*K, oh * ow) : 0.f;
@@ -612,6 +671,67 @@ __global__ __launch_bounds__(kThreads) void dec_resample_v_stat_batch(const DecO
     if (K.contrast < 0) return;
     const DecOutRs R = Os[blockIdx.y];
     col_accumulate(K, resample_v_body<float, kColStat>(R.tmp, R.o.H, oh, ow, R.o.bps_or_flags, nullptr, col_stat_call(), &K));
+}
+
+// the cubic forms (CCMI_FILTER_CUBIC): the same bodies on CubTaps, argument for argument
+__global__ __launch_bounds__(kThreads) CUBIC_WAVES8 void dec_cubic_h(const int32_t *__restrict__ syn, int H, int W, int oy, int ox, int h,
+                                                        int w, int ow, int maxv, int kind, int flags,
+                                                        float *__restrict__ tmp)
+{
+    resample_h_body<true>(syn, (int64_t)H * W, W, oy, ox, h, w, ow, maxv, kind, flags, tmp);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) CUBIC_WAVES8 void dec_cubic_v(const float *__restrict__ tmp, int h, int oh, int ow, int flags,
+                                                        T *__restrict__ dst, DecFmtCall C)
+{
+    resample_v_body<T, kColNone, true>(tmp, h, oh, ow, flags, dst, C);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) CUBIC_WAVES8 void dec_cubic_v_col(const float *__restrict__ tmp, int h, int oh, int ow, int flags,
+                                                            T *__restrict__ dst, DecFmtCall C, DecCol K)
+{
+    resample_v_body<T, kColWrite, true>(tmp, h, oh, ow, flags, dst, C, &K);
+}
+
+__global__ __launch_bounds__(kThreads) CUBIC_WAVES8 void dec_cubic_v_stat(const float *__restrict__ tmp, int h, int oh, int ow, int flags,
+                                                             DecCol K)
+{
+    col_accumulate(K, resample_v_body<float, kColStat, true>(tmp, h, oh, ow, flags, nullptr, col_stat_call(), &K));
+}
+
+__global__ __launch_bounds__(kThreads) CUBIC_WAVES8 void dec_cubic_h_batch(const DecOutRs *__restrict__ Os, int ow)
+{
+    const DecOutRs R = Os[blockIdx.y];
+    const DecOut &O = R.o;
+    resample_h_body<true>(O.syn, (int64_t)O.H * O.W, O.W, 0, 0, O.H, O.W, ow, O.maxv, O.kind, O.bps_or_flags, R.tmp);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) CUBIC_WAVES8 void dec_cubic_v_batch(const DecOutRs *__restrict__ Os, int oh, int ow, DecFmtCall C)
+{
+    const DecOutRs R = Os[blockIdx.y];
+    resample_v_body<T, kColNone, true>(R.tmp, R.o.H, oh, ow, R.o.bps_or_flags, reinterpret_cast<T *>(R.o.dst), C);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) CUBIC_WAVES8 void dec_cubic_v_col_batch(const DecOutRs *__restrict__ Os, int oh, int ow,
+                                                                  DecFmtCall C, const DecCol *__restrict__ Ks)
+{
+    const DecOutRs R = Os[blockIdx.y];
+    resample_v_body<T, kColWrite, true>(R.tmp, R.o.H, oh, ow, R.o.bps_or_flags, reinterpret_cast<T *>(R.o.dst), C,
+                                        Ks + blockIdx.y);
+}
+
+__global__ __launch_bounds__(kThreads) CUBIC_WAVES8 void dec_cubic_v_stat_batch(const DecOutRs *__restrict__ Os, int oh, int ow,
+                                                                   const DecCol *__restrict__ Ks)
+{
+    const DecCol &K = Ks[blockIdx.y];
+    if (K.contrast < 0) return;
+    const DecOutRs R = Os[blockIdx.y];
+    col_accumulate(K, resample_v_body<float, kColStat, true>(R.tmp, R.o.H, oh, ow, R.o.bps_or_flags, nullptr, col_stat_call(),
+                                                             &K));
 }
 
 unsigned resample_h_blocks(int h, int ow) { return (unsigned)(((int64_t)h * ow + kThreads - 1) / kThreads); }
@@ -767,6 +887,149 @@ __global__ __launch_bounds__(kThreads) void dec_warp_stat_batch(const DecOutWarp
                                                  A.o.bps_or_flags, nullptr, col_stat_call(), Wc, &K));
 }
 
+// ---- the cubic warp (CCMI_WARP_CUBIC: steps 3c-3d of its contract in ccmi.h)
+// The same thread layout, positions and tap rule as warp_body, 16 taps per pixel: cubic convolution
+// with A = -0.75 in the contract's operation order.  The four tap rows go one at a time (the loop
+// over a is kept rolled, its coefficient picked by selects): 8 coefficients, 3 row sums and 3
+// accumulators are live next to one tap, and the code holds 4 x 4 copies of fmt_pixel, as warp_body's.
+__device__ __forceinline__ float fmt_sub(float a, float b)
+{
+#pragma clang fp contract(off)
+    return a - b;
+}
+__device__ __forceinline__ float cub_in(float t) // |t| <= 1
+{
+    return fmt_add(fmt_mul(fmt_mul(fmt_sub(fmt_mul(1.25f, t), 2.25f), t), t), 1.f);
+}
+__device__ __forceinline__ float cub_out(float s) // 1 <= |s| <= 2
+{
+    return fmt_sub(fmt_mul(fmt_add(fmt_mul(fmt_sub(fmt_mul(-0.75f, s), -3.75f), s), -6.f), s), -3.f);
+}
+
+template <typename T, int COL = kColNone>
+__device__ __forceinline__ uint32_t wcubic_body(const int32_t *__restrict__ syn, int h, int w, int oy, int ox, int fh, int fw,
+                                                const float (&m)[6], int maxv, int kind, int flags, T *__restrict__ dst,
+                                                const DecFmtCall &C, const DecWarpCall &Wc, const DecCol *K = nullptr)
+{
+    int y, d0;
+    int64_t row;
+    bool nchw, nhwc;
+    if (!fmt_group<T>(dst, C, Wc.oh, Wc.ow, y, d0, row, nchw, nhwc)) return 0;
+    float mean = 0.f;
+    uint32_t sum = 0;
+    if constexpr (COL == kColWrite) mean = col_mean(*K, Wc.oh * Wc.ow);
+    const float fmax = (float)maxv;
+    const bool mirror = flags & kFmtMirror, matrix = flags & kFmtMatrix, clamp = flags & kFmtClamp;
+    const int64_t splane = (int64_t)h * w;
+    const float cy = (float)y + 0.5f;
+    const float xr = fmt_mul(m[1], cy), yr = fmt_mul(m[4], cy); // the row's share of the position
+    T v[3][4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int d = d0 + k;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[c][k] = fmt_elem<T>(0.f);
+        if (d < 0 || d >= Wc.ow) continue;
+        const float cx = (float)(mirror ? Wc.ow - 1 - d : d) + 0.5f;
+        const float xs = fmt_add(fmt_add(fmt_mul(m[0], cx), xr), m[2]);
+        const float ys = fmt_add(fmt_add(fmt_mul(m[3], cx), yr), m[5]);
+        const float u = xs - 0.5f, vv = ys - 0.5f;
+        const float uf = floorf(u), vf = floorf(vv); // |u|, |v| <= 2^22 + 1: exact in an int
+        const float fx = u - uf, fy = vv - vf;
+        const int x0 = (int)uf, y0 = (int)vf;
+        const float gx = 1.f - fx, gy = 1.f - fy;
+        const float wx[4] = {cub_out(fmt_add(fx, 1.f)), cub_in(fx), cub_in(gx), cub_out(fmt_add(gx, 1.f))};
+        const float wy0 = cub_out(fmt_add(fy, 1.f)), wy1 = cub_in(fy), wy2 = cub_in(gy), wy3 = cub_out(fmt_add(gy, 1.f));
+        float r[3] = {0.f, 0.f, 0.f};
+#pragma unroll 1
+        for (int a = 0; a < 4; ++a) {
+            const int yy = y0 - 1 + a;
+            const bool yin = yy >= 0 && yy < fh;
+            const int ry = min(max(min(max(yy, 0), fh - 1) - oy, 0), h - 1);
+            const int32_t *__restrict__ lrow = syn + (int64_t)ry * w;
+            const int32_t *__restrict__ crow = syn + (int64_t)(kind == 1 ? ry : ry & ~1) * w;
+            float line[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const int xx = x0 - 1 + b;
+                const bool in = yin && xx >= 0 && xx < fw;
+                const int rx = min(max(min(max(xx, 0), fw - 1) - ox, 0), w - 1);
+                float t[3];
+                fmt_pixel(lrow, crow, splane, rx, kind == 1 ? rx : rx & ~1, maxv, fmax, matrix, t);
+                if (!in && Wc.pad == CCMI_PAD_FILL) {
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) t[c] = Wc.fill[c];
+                }
+#pragma unroll
+                for (int c = 0; c < 3; ++c) line[c] = fmt_add(line[c], fmt_mul(t[c], wx[b]));
+            }
+            const float wya = a == 0 ? wy0 : a == 1 ? wy1 : a == 2 ? wy2 : wy3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) r[c] = fmt_add(r[c], fmt_mul(line[c], wya));
+        }
+        if (clamp) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) r[c] = col_clamp(r[c]);
+        }
+        if constexpr (COL == kColStat) {
+            sum += col_term(*K, r);
+        } else {
+            if constexpr (COL == kColWrite) col_ops(*K, 0, K->n, mean, r);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) v[c][k] = fmt_elem<T>(fmt_add(fmt_mul(r[c], C.scale[c]), C.bias[c]));
+        }
+    }
+    if constexpr (COL != kColStat) fmt_store<T>(v, dst, C, row, d0, Wc.ow, nchw, nhwc);
+    return sum;
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_wcubic(DecOutWarp A, DecFmtCall C, DecWarpCall Wc)
+{
+    wcubic_body<T>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind, A.o.bps_or_flags,
+                   reinterpret_cast<T *>(A.o.dst), C, Wc);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_wcubic_batch(const DecOutWarp *__restrict__ Os, DecFmtCall C, DecWarpCall Wc)
+{
+    const DecOutWarp A = Os[blockIdx.y];
+    wcubic_body<T>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind, A.o.bps_or_flags,
+                   reinterpret_cast<T *>(A.o.dst), C, Wc);
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_wcubic_col(DecOutWarp A, DecFmtCall C, DecWarpCall Wc, DecCol K)
+{
+    wcubic_body<T, kColWrite>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind, A.o.bps_or_flags,
+                              reinterpret_cast<T *>(A.o.dst), C, Wc, &K);
+}
+
+__global__ __launch_bounds__(kThreads) CUBIC_WAVES8 void dec_wcubic_stat(DecOutWarp A, DecWarpCall Wc, DecCol K)
+{
+    col_accumulate(K, wcubic_body<float, kColStat>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind,
+                                                   A.o.bps_or_flags, nullptr, col_stat_call(), Wc, &K));
+}
+
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dec_wcubic_col_batch(const DecOutWarp *__restrict__ Os, DecFmtCall C,
+                                                                 DecWarpCall Wc, const DecCol *__restrict__ Ks)
+{
+    const DecOutWarp A = Os[blockIdx.y];
+    wcubic_body<T, kColWrite>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind, A.o.bps_or_flags,
+                              reinterpret_cast<T *>(A.o.dst), C, Wc, Ks + blockIdx.y);
+}
+
+__global__ __launch_bounds__(kThreads) CUBIC_WAVES8 void dec_wcubic_stat_batch(const DecOutWarp *__restrict__ Os, DecWarpCall Wc,
+                                                                  const DecCol *__restrict__ Ks)
+{
+    const DecCol &K = Ks[blockIdx.y];
+    if (K.contrast < 0) return;
+    const DecOutWarp A = Os[blockIdx.y];
+    col_accumulate(K, wcubic_body<float, kColStat>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind,
+                                                   A.o.bps_or_flags, nullptr, col_stat_call(), Wc, &K));
+}
+
 DecWarpCall warp_call(const DecFmt &f)
 {
     DecWarpCall Wc;
@@ -898,6 +1161,11 @@ int launch_dec_out_frame(const DecTailFrame &f, const int32_t *syn, int h, int w
     if (fmt.warp) {
         const DecOutWarp A = make_out_warp(DecOut{syn, h, w, maxv, kind, flags, f.dst}, fmt, 0, 0, h, w);
         const DecWarpCall Wc = warp_call(fmt);
+        if (fmt.cubic)
+            return launch_fmt_forms(
+                fmt, stat, [&] { launch(dec_wcubic_stat, grid, s, A, Wc, *K); },
+                [&](auto t) { launch(dec_wcubic_col<decltype(t)>, grid, s, A, C, Wc, *K); },
+                [&](auto t) { launch(dec_wcubic<decltype(t)>, grid, s, A, C, Wc); });
         return launch_fmt_forms(
             fmt, stat, [&] { launch(dec_warp_stat, grid, s, A, Wc, *K); },
             [&](auto t) { launch(dec_warp_col<decltype(t)>, grid, s, A, C, Wc, *K); },
@@ -905,8 +1173,14 @@ int launch_dec_out_frame(const DecTailFrame &f, const int32_t *syn, int h, int w
     }
     if (fmt.rs) { // rs_tmp holds the horizontal pass
         float *tmp = f.rs_tmp;
-        launch(dec_resample_h, dim3(resample_h_blocks(rh, ow)), s, syn, h, w, rect.y0, rect.x0, rh, rw, ow, maxv, kind, flags, tmp);
+        launch(fmt.cubic ? dec_cubic_h : dec_resample_h, dim3(resample_h_blocks(rh, ow)), s, syn, h, w, rect.y0, rect.x0, rh, rw,
+               ow, maxv, kind, flags, tmp);
         CCMI_HIP_CHECK(hipGetLastError());
+        if (fmt.cubic)
+            return launch_fmt_forms(
+                fmt, stat, [&] { launch(dec_cubic_v_stat, grid, s, tmp, rh, oh, ow, flags, *K); },
+                [&](auto t) { launch(dec_cubic_v_col<decltype(t)>, grid, s, tmp, rh, oh, ow, flags, as(t, dst), C, *K); },
+                [&](auto t) { launch(dec_cubic_v<decltype(t)>, grid, s, tmp, rh, oh, ow, flags, as(t, dst), C); });
         return launch_fmt_forms(
             fmt, stat, [&] { launch(dec_resample_v_stat, grid, s, tmp, rh, oh, ow, flags, *K); },
             [&](auto t) { launch(dec_resample_v_col<decltype(t)>, grid, s, tmp, rh, oh, ow, flags, as(t, dst), C, *K); },
@@ -964,6 +1238,11 @@ int launch_dec_out_group(const DecTailFrame &f0, int h, int w, int n, const void
     if (fmt.warp) { // the section holds DecOutWarp
         const DecOutWarp *ww = static_cast<const DecOutWarp *>(out_sec);
         const DecWarpCall Wc = warp_call(fmt);
+        if (fmt.cubic)
+            return launch_fmt_forms(
+                fmt, stat, [&] { launch(dec_wcubic_stat_batch, grid, s, ww, Wc, kk); },
+                [&](auto t) { launch(dec_wcubic_col_batch<decltype(t)>, grid, s, ww, C, Wc, kk); },
+                [&](auto t) { launch(dec_wcubic_batch<decltype(t)>, grid, s, ww, C, Wc); });
         return launch_fmt_forms(
             fmt, stat, [&] { launch(dec_warp_stat_batch, grid, s, ww, Wc, kk); },
             [&](auto t) { launch(dec_warp_col_batch<decltype(t)>, grid, s, ww, C, Wc, kk); },
@@ -972,8 +1251,13 @@ int launch_dec_out_group(const DecTailFrame &f0, int h, int w, int n, const void
     if (fmt.rs) { // the section holds DecOutRs; h = the group's tallest region
         const DecOutRs *rr = static_cast<const DecOutRs *>(out_sec);
         const int oh = fmt.out_h, ow = fmt.out_w;
-        launch(dec_resample_h_batch, dim3(resample_h_blocks(h, ow), n), s, rr, ow);
+        launch(fmt.cubic ? dec_cubic_h_batch : dec_resample_h_batch, dim3(resample_h_blocks(h, ow), n), s, rr, ow);
         CCMI_HIP_CHECK(hipGetLastError());
+        if (fmt.cubic)
+            return launch_fmt_forms(
+                fmt, stat, [&] { launch(dec_cubic_v_stat_batch, grid, s, rr, oh, ow, kk); },
+                [&](auto t) { launch(dec_cubic_v_col_batch<decltype(t)>, grid, s, rr, oh, ow, C, kk); },
+                [&](auto t) { launch(dec_cubic_v_batch<decltype(t)>, grid, s, rr, oh, ow, C); });
         return launch_fmt_forms(
             fmt, stat, [&] { launch(dec_resample_v_stat_batch, grid, s, rr, oh, ow, kk); },
             [&](auto t) { launch(dec_resample_v_col_batch<decltype(t)>, grid, s, rr, oh, ow, C, kk); },

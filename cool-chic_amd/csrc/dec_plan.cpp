@@ -60,7 +60,9 @@ int tensor_format(const FrameHost &f, int out_bitdepth, int out_chroma, int samp
 
 size_t elem_bytes(int elem) { return elem == CCMI_ELEM_F32 ? 4 : 2; }
 
-constexpr int kMaxResample = 16384; // region and output extents of a resample: its integer weights fit int32
+// region and output extents of a resample: the triangle's integer weights and their sums fit int32,
+// the cubic's terms stay below 2^51 and their sums below 2^61 (int64)
+constexpr int kMaxResample = 16384;
 
 constexpr double kMaxWarpReach = 4194304.0; // 2^22: the bound on a warp's float32 positions
 
@@ -71,7 +73,8 @@ int warp_check(const ccmi_warp &wp, int i)
     if (wp.out_w < 1 || wp.out_w > kMaxResample || wp.out_h < 1 || wp.out_h > kMaxResample)
         return ccmi_set_error(CCMI_ERR_ARG, "frame %d: output size w %d h %d (1 .. %d)", i, wp.out_w, wp.out_h,
                               kMaxResample);
-    if (wp.pad != CCMI_PAD_FILL && wp.pad != CCMI_PAD_EDGE)
+    const int flags = wp.pad & ~1; // none, CCMI_WARP_CUBIC, or CCMI_WARP_CUBIC | CCMI_WARP_CLAMP
+    if (wp.pad < 0 || (flags != 0 && flags != CCMI_WARP_CUBIC && flags != (CCMI_WARP_CUBIC | CCMI_WARP_CLAMP)))
         return ccmi_set_error(CCMI_ERR_ARG, "frame %d: unknown pad %d", i, wp.pad);
     const float *m = wp.matrix + 6 * (size_t)i;
     for (int k = 0; k < 6; ++k)
@@ -91,9 +94,9 @@ int warp_check(const ccmi_warp &wp, int i)
 }
 
 // The window of an h x w frame a checked warp samples (the rule is in ccmi.h): the bounding box of
-// the taps in double, grown by one pixel, each end clamped into the frame; even = grown to even
-// x, y, w, h (h and w even).
-DecWindow warp_window(const ccmi_warp &wp, int i, int h, int w, bool even)
+// the taps in double (reach = 1: the bilinear taps x0, x0 + 1; 2: the cubic's x0 - 1 .. x0 + 2), grown
+// by one pixel, each end clamped into the frame; even = grown to even x, y, w, h (h and w even).
+DecWindow warp_window(const ccmi_warp &wp, int i, int h, int w, bool even, int reach)
 {
     const float *m = wp.matrix + 6 * (size_t)i;
     const double cx[2] = {0.5, wp.out_w - 0.5}, cy[2] = {0.5, wp.out_h - 0.5};
@@ -107,8 +110,8 @@ DecWindow warp_window(const ccmi_warp &wp, int i, int h, int w, bool even)
                 if ((a | b) == 0 || v > hi) hi = v;
             }
         const double last = (r == 0 ? w : h) - 1;
-        end[r][0] = (int)std::min(std::max(std::floor(lo - 0.5) - 1, 0.0), last);
-        end[r][1] = (int)std::min(std::max(std::floor(hi - 0.5) + 2, 0.0), last);
+        end[r][0] = (int)std::min(std::max(std::floor(lo - 0.5) - reach, 0.0), last);
+        end[r][1] = (int)std::min(std::max(std::floor(hi - 0.5) + reach + 1, 0.0), last);
     }
     DecWindow win{end[1][0], end[1][1] + 1, end[0][0], end[0][1] + 1};
     if (even) win = DecWindow{win.y0 & ~1, (win.y1 + 1) & ~1, win.x0 & ~1, (win.x1 + 1) & ~1};
@@ -135,7 +138,9 @@ int tensor_fmt(const ccmi_tensor_fmt &m, const ccmi_resample *rs, const ccmi_war
                               "frame %d: a formatted 420 region needs an even size (w %d h %d); out_chroma = 444 takes any",
                               i, rect.w(), rect.h());
     if (rs) {
-        if (rs->filter != CCMI_FILTER_TRIANGLE) return ccmi_set_error(CCMI_ERR_ARG, "frame %d: unknown filter %d", i, rs->filter);
+        if (rs->filter != CCMI_FILTER_TRIANGLE && rs->filter != CCMI_FILTER_CUBIC &&
+            rs->filter != (CCMI_FILTER_CUBIC | CCMI_FILTER_CLAMP))
+            return ccmi_set_error(CCMI_ERR_ARG, "frame %d: unknown filter %d", i, rs->filter);
         if (rs->out_w < 1 || rs->out_w > kMaxResample || rs->out_h < 1 || rs->out_h > kMaxResample)
             return ccmi_set_error(CCMI_ERR_ARG, "frame %d: output size w %d h %d (1 .. %d)", i, rs->out_w, rs->out_h,
                                   kMaxResample);
@@ -170,9 +175,13 @@ int tensor_fmt(const ccmi_tensor_fmt &m, const ccmi_resample *rs, const ccmi_war
     d.mirror = m.mirror && m.mirror[i];
     for (int c = 0; c < 3; ++c) d.scale[c] = m.scale[c], d.bias[c] = m.bias[c];
     d.stride_c = sc, d.stride_y = sy, d.stride_x = sx;
-    if (rs) d.rs = 1, d.out_h = h, d.out_w = w;
+    if (rs) {
+        d.rs = 1, d.out_h = h, d.out_w = w;
+        d.cubic = (rs->filter & 0xff) == CCMI_FILTER_CUBIC, d.clamp = (rs->filter & CCMI_FILTER_CLAMP) != 0;
+    }
     if (wp) {
-        d.warp = 1, d.out_h = h, d.out_w = w, d.pad = wp->pad;
+        d.warp = 1, d.out_h = h, d.out_w = w, d.pad = wp->pad & 1;
+        d.cubic = (wp->pad & CCMI_WARP_CUBIC) != 0, d.clamp = (wp->pad & CCMI_WARP_CLAMP) != 0;
         for (int c = 0; c < 3; ++c) d.fill[c] = wp->fill[c];
         for (int k = 0; k < 6; ++k) d.m[k] = wp->matrix[6 * (size_t)i + k];
     }
@@ -358,7 +367,7 @@ int plan_tensor_sink(const DecodeRequest &rq, int i, FramePlan &p)
     }
     if (rq.warp) { // the region is the window the matrix reaches
         if (int rc = warp_check(*rq.warp, i)) return rc;
-        rect = warp_window(*rq.warp, i, f.h, f.w, false);
+        rect = warp_window(*rq.warp, i, f.h, f.w, false, rq.warp->pad & CCMI_WARP_CUBIC ? 2 : 1);
     }
     if (int rc = tensor_format(f, rq.out_bitdepth, rq.out_chroma, rq.sample, p.of, &elems, rect)) {
         if (!rq.src) return rc;
@@ -370,7 +379,7 @@ int plan_tensor_sink(const DecodeRequest &rq, int i, FramePlan &p)
             return ccmi_set_error(
                 CCMI_ERR_ARG, "frame %d: a warp of 420 samples needs an even frame size (w %d h %d); out_chroma = 444 takes any",
                 i, f.w, f.h);
-        rect = warp_window(*rq.warp, i, f.h, f.w, true);
+        rect = warp_window(*rq.warp, i, f.h, f.w, true, rq.warp->pad & CCMI_WARP_CUBIC ? 2 : 1);
     }
     if (rq.window) rq.window[i] = ccmi_rect{rect.x0, rect.y0, rect.w(), rect.h()};
     if (p.of.kind == kYuv420 && ((rect.x0 | rect.y0) & 1))

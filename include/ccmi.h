@@ -669,8 +669,29 @@ int ccmi_latents_render_fmt(const ccmi_latents *h, const int *index /* [m] or NU
  * their region sizes (whole-frame requests: one per frame size, as ever); the others run their
  * per-frame tail.  ccmi_decode_last_tail_groups(): how many batched tail groups and how many
  * per-frame tails this thread's last decode or render call launched (0, 0 after a call that
- * failed or only planned, and after ccmi_latents_decode, which runs no tail). */
-enum { CCMI_FILTER_TRIANGLE = 0 };
+ * failed or only planned, and after ccmi_latents_decode, which runs no tail).
+ *
+ * CCMI_FILTER_CUBIC: the same call with the Keys cubic, a = -0.5, in place of the triangle -- the
+ * filter of interpolate(mode="bicubic", antialias=True, align_corners=False) and of PIL's BICUBIC,
+ * its support scaled by max(I / O, 1).  filter is one value per call: 0 (triangle), 2 (cubic) or
+ * 0x102 (cubic | CCMI_FILTER_CLAMP); 1 is reserved, and every other value is an unknown filter.
+ * Steps 3b and 3c are the triangle's (the same two passes, taps ascending, sums from 0, the region
+ * as the image); only the weights of 3a differ, and they stay integers:
+ *   3a. per axis: D2 = 2 max(I, O), n(i, j) = |(2 j + 1) O - (2 i + 1) I|, in 64-bit arithmetic
+ *         n < D2:         u = 3 n^3 - 5 n^2 D2 + 2 D2^3
+ *         D2 <= n < 2 D2: u = -n^3 + 5 n^2 D2 - 8 n D2^2 + 4 D2^3   (negative: the side lobes)
+ *       The taps of i are the j with n < 2 D2, a contiguous run, clipped to the region (a tap may
+ *       have u = 0).  U(i) = sum_j u(i, j) > 0; w(i, j) = (float)u / (float)U: two int64 -> float32
+ *       conversions to nearest even, one correctly rounded float32 division.  With I, O <= 16384
+ *       every term stays below 2^51 and |U| below 2^61.  With I == O the neighbours' u is exactly 0
+ *       and w(i, i) = 1: that pass is the identity, bit for bit.
+ * The weights of a tap row sum to 1 but are not all positive, so r' may leave [0, 1] (torch's float
+ * path does not clamp either).  With CCMI_FILTER_CLAMP, r' = min(max(r', 0), 1) after step 3c and
+ * before the colour ops (step 3z) -- what a uint8 / PIL pipeline gives.  The flag is valid with
+ * CCMI_FILTER_CUBIC only.  The workspace formula is unchanged.
+ * Kernels (dec_out.hip): dec_cubic_h, dec_cubic_v<T> and their _col / _stat / _batch forms, the
+ * weights recomputed per thread by Horner in int64. */
+enum { CCMI_FILTER_TRIANGLE = 0, CCMI_FILTER_CUBIC = 2, CCMI_FILTER_CLAMP = 0x100 };
 typedef struct ccmi_resample { int out_w, out_h, filter; } ccmi_resample;
 int ccmi_decode_batch_dev_rs_plan(const uint8_t *const *streams, const size_t *lens, int n,
                                   const ccmi_rect *roi /* [n] or NULL */, int out_bitdepth, int out_chroma,
@@ -734,8 +755,27 @@ int ccmi_decode_last_tail_groups(int *batched, int *per_frame);
  * Measured (profiles/decode_warp_ab.txt): 960 class-E streams from an int16 store, rotation +-30
  * degrees, scale 0.5-1.5, random centres, 224 x 224 bf16 RGB normalised: 14.8-14.9 ms per call (tail
  * 11.3 ms) in one tail group, against 194-209 ms for the CCMI_ELEM_F32 render of the same windows per
- * window size (737 groups) followed by torch's grid_sample; workspace 6.6 GiB. */
-enum { CCMI_PAD_FILL = 0, CCMI_PAD_EDGE = 1 };
+ * window size (737 groups) followed by torch's grid_sample; workspace 6.6 GiB.
+ *
+ * CCMI_WARP_CUBIC, or'ed into pad: every output pixel is a bicubic sample instead -- cubic
+ * convolution with A = -0.75, grid_sample(mode="bicubic", align_corners=False).  pad is one value
+ * per call: 0, 1, 0x100, 0x101 and, with CCMI_WARP_CLAMP (valid with CCMI_WARP_CUBIC only), 0x300
+ * and 0x301; every other value is an unknown pad.  The struct is unchanged.  Steps 3a-3b are as
+ * above; then, every product, sum and difference one float32 operation in the order written:
+ *   3c. 16 taps T_c(a, b) = q_c(y0 - 1 + a, x0 - 1 + b), a, b in 0 .. 3, each with the fill / edge
+ *       rule of the bilinear tap;
+ *   3d. c_in(t) = ((((A + 2) t) - (A + 3)) t) t + 1, c_out(s) = ((((A s) - 5 A) s + 8 A) s) - 4 A
+ *       with the constants A + 2 = 1.25, A + 3 = 2.25, 5 A = -3.75, 8 A = -6, 4 A = -3;
+ *       gx = 1 - fx; wx = { c_out(fx + 1), c_in(fx), c_in(gx), c_out(gx + 1) }, wy alike from fy;
+ *       row_a = sum_b T(a, b) wx[b], from 0 over b ascending; r' = sum_a row_a wy[a], from 0 over
+ *       a ascending.
+ * At fx = 0 the coefficients are exactly 0, 1, 0, 0, so an integer translation is still the crop
+ * and m00 = -1 the flip, bit for bit.  r' may leave [0, 1]; with CCMI_WARP_CLAMP r' = min(max(r',
+ * 0), 1) before the colour ops -- on r' whatever its taps were, fill included.
+ * window[j] grows by one tap on each side: columns floor(min xs - 0.5) - 2 .. floor(max xs - 0.5)
+ * + 3 and rows alike, then the same clamp into the frame and the same even-ing.
+ * Kernels (dec_out.hip): dec_wcubic<T> and its _col / _stat / _batch forms. */
+enum { CCMI_PAD_FILL = 0, CCMI_PAD_EDGE = 1, CCMI_WARP_CUBIC = 0x100, CCMI_WARP_CLAMP = 0x200 };
 typedef struct ccmi_warp {
     int out_w, out_h, pad;
     float fill[3];        /* CCMI_PAD_FILL: value of a tap outside the frame, in q units (after step 3) */
