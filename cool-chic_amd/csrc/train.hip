@@ -192,8 +192,9 @@ __global__ void t_quant(const float *__restrict__ lat, int64_t ls, int N, float 
         const uint64_t r = mix64(seed ^ mix64(((uint64_t)step << 40) ^ ((uint64_t)b << 32) ^ (uint64_t)i));
         const float u1 = unif(r);
         if (nz == CCMI_NOISE_KUMARASWAMY) { // generate_kumaraswamy_noise: (1 - (1 - u)^(1/b))^(1/a) - 1/2
-            // powers through v_log_f32 / v_exp_f32 (u1 in (0, 1): both bases in (0, 1]); the
-            // draw only has to follow the distribution, parity tests pass their noise in
+            // powers through v_log_f32 / v_exp_f32 (u1 in (0, 1]: both bases in [0, 1], the ends
+            // giving -inf -> 0); every draw is held to the generator of ccmi.h by
+            // tests/test_train_noise_gpu.py: |CDF(n) - u1| <= K(a) 2^-24 (tests/noise_ref.py)
             const float p = exp2f(__log2f(1.f - u1) * Q.kb_inv);
             n = exp2f(__log2f(1.f - p) * Q.ka_inv) - 0.5f;
         } else { // gaussian: Box-Muller

@@ -1198,7 +1198,25 @@ enum { CCMI_NOISE_NONE = 0, CCMI_NOISE_KUMARASWAMY, CCMI_NOISE_GAUSSIAN };
  * Supported synthesis: a 1x1 head of 2 non-residual layers (C -> hid <= 64 -> 3), then
  * 0..3 3x3 layers 3 -> 3 (replicate padding).  Adam moments: [batch][latent_stride +
  * param_stride], each row N latents then P parameters.  grad_out rows: [N + P], same
- * order.  target: 444 [3][H][W] or 420 Y[H][W], U, V[H/2][W/2]. */
+ * order.  target: 444 [3][H][W] or 420 Y[H][W], U, V[H/2][W/2].
+ *
+ * The noise generator (noise != CCMI_NOISE_NONE, noise_in null) is part of the contract; tests/
+ * noise_ref.py restates this text and tests/test_train_noise_gpu.py holds every draw to it:
+ *   mix64(z):  z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9;
+ *              z = (z ^ z >> 27) * 0x94D049BB133111EB; return z ^ z >> 31      (mod 2^64)
+ *   key      = (uint64) step << 40 ^ (uint64) frame << 32 ^ (uint64) index
+ *   r        = mix64(seed ^ mix64(key)),  r2 = mix64(r + 0x632BE59BD9B4E019)
+ *   unif(r)  = ((float) (r >> 40) + 0.5f) * 2^-24, the add rounded in float32: a 24-bit uniform
+ *              in (0, 1]; r >> 40 = 0 gives 2^-25, r >> 40 >= 2^23 rounds the half to the even
+ *              neighbour and r >> 40 = 2^24 - 1 gives 1.0
+ *   u1 = unif(r), u2 = unif(r2)
+ *   CCMI_NOISE_KUMARASWAMY  a = noise_param > 0, b = (2^a (a - 1) + 1) / a:
+ *                           n = (1 - (1 - u1)^(1/b))^(1/a) - 1/2, in [-1/2, 1/2] (quantizer.py:60-102)
+ *   CCMI_NOISE_GAUSSIAN     sigma = noise_param: n = sigma sqrt(-2 ln u1) cos(2 pi u2), |n| <= 5.9 sigma
+ * `frame` is the row of the batch and `index` the latent's position among the frame's N latents
+ * (grid 0 first), not its address: latent_stride does not enter.  Equal (seed, step, frame, index)
+ * give equal draws in every call.  step keeps its low 24 bits in the key and frame its low 8 bits
+ * clear of them: steps 2^24 apart, or frames 256 apart at steps that differ accordingly, share keys. */
 typedef struct ccmi_train_args {
     int batch;
     int n_grids;
