@@ -405,7 +405,7 @@ def _resample(size, interp=(FILTER_TRIANGLE, 0)):
 
 
 PAD_FILL, PAD_EDGE = 0, 1  # CCMI_PAD_*
-WARP_CUBIC, WARP_CLAMP = 0x100, 0x200  # or'ed into ccmi_warp.pad
+WARP_CUBIC, WARP_CLAMP, WARP_PROJECTIVE = 0x100, 0x200, 0x800  # or'ed into ccmi_warp.pad
 
 
 def _interp(interpolation, clamp):
@@ -425,16 +425,23 @@ class Warp(C.Structure):
                 ("matrix", C.c_void_p)]
 
 
-def _warp(affine, n, size, roi, pad, fill, interp=(FILTER_TRIANGLE, 0)):
-    """affine= / pad= / fill= of a *_model call -> (ccmi_warp, what it points to), or (None, None)
-    without affine.  The library checks the values; the shapes are checked here.  interp: _interp()'s pair."""
+def _warp(affine, n, size, roi, pad, fill, interp=(FILTER_TRIANGLE, 0), perspective=None):
+    """affine= or perspective= / pad= / fill= of a *_model call -> (ccmi_warp, what it points to), or
+    (None, None) without either.  The library checks the values; the shapes are checked here.  interp:
+    _interp()'s pair.  perspective= sets CCMI_WARP_PROJECTIVE: the matrices are [n, 3, 3]."""
     import numpy as np
-    if affine is None:
+    if affine is None and perspective is None:
         return None, None
+    if affine is not None and perspective is not None:
+        raise ValueError("model output: perspective excludes affine (a call is wholly affine or wholly projective; "
+                         "an affine frame of a perspective call has the last row 0 0 1)")
+    word, rows = ("affine", 2) if perspective is None else ("perspective", 3)
+    if perspective is not None:
+        affine, interp = perspective, (interp[0], interp[1] | WARP_PROJECTIVE)
     if size is None:
-        raise ValueError("model output: affine needs size=(out_h, out_w)")
+        raise ValueError(f"model output: {word} needs size=(out_h, out_w)")
     if roi is not None:
-        raise ValueError("model output: affine excludes roi (the matrix says where the output lies in the frame)")
+        raise ValueError(f"model output: {word} excludes roi (the matrix says where the output lies in the frame)")
     if len(size) != 2:
         raise ValueError(f"model output: size takes (out_h, out_w), got {size!r}")
     pads = {"fill": PAD_FILL, "edge": PAD_EDGE}
@@ -442,10 +449,10 @@ def _warp(affine, n, size, roi, pad, fill, interp=(FILTER_TRIANGLE, 0)):
         raise ValueError(f"model output: pad {pad!r} ('fill' or 'edge')")
     a = affine.detach().cpu().numpy() if hasattr(affine, "detach") else np.asarray(affine)
     a = np.ascontiguousarray(a, dtype=np.float32)
-    if a.shape == (2, 3):
-        a = np.ascontiguousarray(np.broadcast_to(a, (n, 2, 3)))
-    if a.shape != (n, 2, 3):
-        raise ValueError(f"model output: affine takes [{n}, 2, 3] or one [2, 3], got {list(a.shape)}")
+    if a.shape == (rows, 3):
+        a = np.ascontiguousarray(np.broadcast_to(a, (n, rows, 3)))
+    if a.shape != (n, rows, 3):
+        raise ValueError(f"model output: {word} takes [{n}, {rows}, 3] or one [{rows}, 3], got {list(a.shape)}")
     f = [float(v) for v in fill] if hasattr(fill, "__len__") else [float(fill)] * 3
     if len(f) != 3:
         raise ValueError("model output: fill takes one value, or one per channel")
@@ -470,6 +477,78 @@ def affine_matrix(size, centre, angle: float = 0.0, scale: float = 1.0, flip: bo
     c, s, f = math.cos(angle), math.sin(angle), -1.0 if flip else 1.0
     return np.array([[f * c / scale, -s / scale, cx + (-f * c * ow / 2 + s * oh / 2) / scale],
                      [f * s / scale, c / scale, cy + (-f * s * ow / 2 - c * oh / 2) / scale]], dtype=np.float32)
+
+
+def _perspective_f64(startpoints, endpoints):
+    """perspective_matrix() before its rounding to float32."""
+    import numpy as np
+    s, e = np.asarray(startpoints, dtype=np.float64), np.asarray(endpoints, dtype=np.float64)
+    if s.shape != (4, 2) or e.shape != (4, 2):
+        raise ValueError("perspective_matrix: startpoints and endpoints take four (x, y) points each")
+    A, b = np.zeros((8, 8)), np.zeros(8)
+    for i in range(4):
+        (ex, ey), (sx, sy) = e[i], s[i]
+        A[2 * i] = [ex, ey, 1, 0, 0, 0, -sx * ex, -sx * ey]
+        A[2 * i + 1] = [0, 0, 0, ex, ey, 1, -sy * ex, -sy * ey]
+        b[2 * i], b[2 * i + 1] = sx, sy
+    try:
+        h = np.linalg.solve(A, b)
+    except np.linalg.LinAlgError as err:
+        raise ValueError("perspective_matrix: the points do not determine a homography") from err
+    return np.append(h, 1.0).reshape(3, 3)
+
+
+def perspective_matrix(startpoints, endpoints):
+    """The [3, 3] float32 matrix (perspective= of the *_model calls), m22 = 1, of the homography that
+    sends each of the four endpoints (x, y) of the OUTPUT to its startpoint (x, y) of the FRAME, in
+    pixels (pixel (y, x) covers [x, x + 1) x [y, y + 1)): torchvision's _get_perspective_coeffs
+    system -- per pair the two rows
+        [ex, ey, 1, 0, 0, 0, -sx ex, -sx ey] . h = sx,    [0, 0, 0, ex, ey, 1, -sy ex, -sy ey] . h = sy
+    -- solved in float64 (an exact solve; torchvision takes a float32 least squares).  A degenerate
+    quadrilateral is a ValueError."""
+    import numpy as np
+    return _perspective_f64(startpoints, endpoints).astype(np.float32)
+
+
+def random_perspective(n: int, size, distortion_scale: float = 0.5, p: float = 0.5, base=None, generator=None):
+    """n [3, 3] float32 matrices for perspective= of the *_model calls, drawn as torchvision's
+    RandomPerspective does for an image of size = (height, width) = (h, w): with hh = floor(d h / 2),
+    hw = floor(d w / 2), d = distortion_scale, the four endpoints are integers drawn uniformly from
+        top left      x in [0, hw],          y in [0, hh]
+        top right     x in [w - hw - 1, w - 1],  y in [0, hh]
+        bottom right  x in [w - hw - 1, w - 1],  y in [h - hh - 1, h - 1]
+        bottom left   x in [0, hw],          y in [h - hh - 1, h - 1]
+    (both ends included), and the frame's matrix is P = perspective_matrix(startpoints = (0, 0),
+    (w - 1, 0), (w - 1, h - 1), (0, h - 1), endpoints = the drawn points): as F.perspective does, the
+    output shows the image's own corners at the drawn points.  A frame is drawn with probability p and
+    is the identity otherwise.  base: None, or [n, 2, 3] (or one [2, 3]) matrices that map the image of
+    that size to the frame -- the crop / RandomResizedCrop matrices, as for rand_augment(base=...); the
+    result is [base; 0 0 1] @ P, composed in float64 and rounded to float32 once.  generator: a numpy
+    Generator, a seed, or None.  torchvision is not a dependency: the ranges above are the contract."""
+    import numpy as np
+    rng = generator if isinstance(generator, np.random.Generator) else np.random.default_rng(generator)
+    h, w = int(size[0]), int(size[1])
+    if not 0.0 <= distortion_scale <= 1.0 or not 0.0 <= p <= 1.0:
+        raise ValueError("random_perspective: distortion_scale and p lie in [0, 1]")
+    hh, hw = int(distortion_scale * h / 2), int(distortion_scale * w / 2)
+    if base is not None:
+        base = np.asarray(base.detach().cpu().numpy() if hasattr(base, "detach") else base, dtype=np.float64)
+        if base.shape == (2, 3):
+            base = np.broadcast_to(base, (n, 2, 3))
+        if base.shape != (n, 2, 3):
+            raise ValueError(f"random_perspective: base takes [{n}, 2, 3] or one [2, 3], got {list(base.shape)}")
+    starts = [(0, 0), (w - 1, 0), (w - 1, h - 1), (0, h - 1)]
+    out = np.empty((n, 3, 3), dtype=np.float32)
+    for j in range(n):
+        P = np.eye(3)
+        if rng.random() < p:
+            xl, xr = rng.integers(0, hw + 1, 2), rng.integers(w - hw - 1, w, 2)
+            yt, yb = rng.integers(0, hh + 1, 2), rng.integers(h - hh - 1, h, 2)
+            P = _perspective_f64(starts, [(xl[0], yt[0]), (xr[0], yt[1]), (xr[1], yb[0]), (xl[1], yb[1])])
+        if base is not None:
+            P = np.vstack([base[j], [0.0, 0.0, 1.0]]) @ P
+        out[j] = P
+    return out
 
 
 COL_BRIGHTNESS, COL_SATURATION, COL_CONTRAST, COL_MATRIX = 0, 1, 2, 3  # CCMI_COL_*
@@ -1006,7 +1085,7 @@ def decode_batch_model(streams: Sequence[bytes], roi=None, colour: str = "rgb", 
                        channels_last: bool = False, mirror=None, out=None, output_bitdepth: int = 0,
                        output_chroma_format: int = 0, workspace=None, stream_handle: int | None = None, size=None,
                        affine=None, pad: str = "fill", fill=0.0, colour_ops=None, blur=None, solarize=None,
-                       tone_ops=None, interpolation: str = "bilinear", clamp: bool = False):
+                       tone_ops=None, interpolation: str = "bilinear", clamp: bool = False, perspective=None):
     """Decode .cool streams into the tensor a model takes (ccmi_decode_batch_dev_fmt): one
     [n, 3, h, w] tensor of `dtype` (torch.float32, the default, torch.float16 or torch.bfloat16),
     every channel at full size (420 chroma nearest-upsampled), RGB (colour="rgb": YUV streams go
@@ -1069,12 +1148,19 @@ def decode_batch_model(streams: Sequence[bytes], roi=None, colour: str = "rgb", 
     interpolate(mode="bicubic", antialias=True) and of PIL's BICUBIC, affine= samples 16 taps as
     grid_sample(mode="bicubic") does.  A bicubic result may leave [0, 1], as torch's; clamp=True
     (bicubic only) clamps it to [0, 1] before the colour ops and the normalisation, which is what a
-    uint8 pipeline gives.  Any other string, and clamp=True with "bilinear", is a ValueError."""
+    uint8 pipeline gives.  Any other string, and clamp=True with "bilinear", is a ValueError.
+    perspective= (CCMI_WARP_PROJECTIVE; needs size, excludes affine and roi): [n, 3, 3], or one [3, 3]
+    for every frame: the homography that maps an output position to the frame position, xs = xn / wn,
+    ys = yn / wn (torchvision's F.perspective convention; perspective_matrix() makes one,
+    random_perspective() draws them).  It composes with pad, fill, interpolation, clamp, mirror,
+    colour_ops, tone_ops, blur and solarize exactly as affine= does; rows 0 0 1 give affine='s bits.
+    The library refuses a denominator that is not positive over the output and a perspective too
+    strong for float32 positions (ccmi.h)."""
     n = len(streams)
     keep, sp, ln = _marshal(streams)
     L = _bind()
     interp = _interp(interpolation, clamp)
-    warp, keep_w = _warp(affine, n, size, roi, pad, fill, interp)
+    warp, keep_w = _warp(affine, n, size, roi, pad, fill, interp, perspective)
     col, keep_c = _colour(colour_ops, n)
     flt, keep_f = _filter(blur, solarize, n)
     tone, keep_t = _tone(tone_ops, n)
@@ -1490,7 +1576,7 @@ class LatentStore:
                      channels_last: bool = False, mirror=None, out=None, output_bitdepth: int = 0,
                      output_chroma_format: int = 0, workspace=None, stream_handle: int | None = None, size=None,
                      affine=None, pad: str = "fill", fill=0.0, colour_ops=None, blur=None, solarize=None,
-                     tone_ops=None, interpolation: str = "bilinear", clamp: bool = False):
+                     tone_ops=None, interpolation: str = "bilinear", clamp: bool = False, perspective=None):
         """render() into the tensor a model takes (ccmi_latents_render_fmt; with size
         ccmi_latents_render_rs; with affine ccmi_latents_render_warp): frames and regions as for
         render(), the result and every other argument as for decode_batch_model, whose output for
@@ -1500,11 +1586,12 @@ class LatentStore:
         ccmi_latents_render_col, with blur or solarize ccmi_latents_render_flt, with tone_ops
         ccmi_latents_render_tone:
         render_model_workspace_bytes() takes the same arguments.  interpolation= / clamp= as for
-        decode_batch_model (a bicubic warp's windows, and so its workspace, are a tap wider)."""
-        m, idx, rects = self._frames(index, None if affine is not None else roi)
+        decode_batch_model (a bicubic warp's windows, and so its workspace, are a tap wider);
+        perspective= as for decode_batch_model, in place of affine=."""
+        m, idx, rects = self._frames(index, None if affine is not None or perspective is not None else roi)
         L = _bind()
         interp = _interp(interpolation, clamp)
-        warp, keep_w = _warp(affine, m, size, roi, pad, fill, interp)
+        warp, keep_w = _warp(affine, m, size, roi, pad, fill, interp, perspective)
         col, keep_c = _colour(colour_ops, m)
         flt, keep_f = _filter(blur, solarize, m)
         tone, keep_t = _tone(tone_ops, m)
@@ -1530,13 +1617,15 @@ class LatentStore:
                           output_chroma_format, workspace, stream_handle, size, interp=interp)
 
     def warp_plan(self, index, affine, size, pad: str = "fill", fill=0.0, output_bitdepth: int = 0,
-                  output_chroma_format: int = 0, interpolation: str = "bilinear", clamp: bool = False) -> list:
+                  output_chroma_format: int = 0, interpolation: str = "bilinear", clamp: bool = False,
+                  perspective=None) -> list:
         """What render_model(affine=...) will do, per output frame (ccmi_latents_render_warp_plan,
         header-only), like roi_plan: {'window': (x, y, w, h), the rectangle of the frame the tail
         renders for that frame's matrix, 'windowed', 'arm_rows'}.  interpolation="bicubic": the window
-        of the 16 taps, one pixel wider on every side the frame allows."""
+        of the 16 taps, one pixel wider on every side the frame allows.  perspective= (with affine=None):
+        the plan of render_model(perspective=...)."""
         m, idx, _ = self._frames(index, None)
-        warp, keep_w = _warp(affine, m, size, None, pad, fill, _interp(interpolation, clamp))
+        warp, keep_w = _warp(affine, m, size, None, pad, fill, _interp(interpolation, clamp), perspective)
         if warp is None:
             raise ValueError("LatentStore.warp_plan: affine is None")
         fmt = TensorFmt(elem=ELEM_F32, colour=COLOUR_ASIS)
@@ -1551,19 +1640,20 @@ class LatentStore:
     def render_model_workspace_bytes(self, index=None, roi=None, size=None, output_bitdepth: int = 0,
                                      output_chroma_format: int = 0, affine=None, pad: str = "fill", fill=0.0,
                                      colour_ops=None, blur=None, solarize=None, tone_ops=None,
-                                     interpolation: str = "bilinear", clamp: bool = False) -> int:
+                                     interpolation: str = "bilinear", clamp: bool = False, perspective=None) -> int:
         """Header-only: the workspace render_model needs for these frames, regions and size, or
         these frames, matrices and size (ccmi_latents_render_rs_plan / _warp_plan; the element type,
         colour and strides do not change it), these colour ops (ccmi_latents_render_col_plan:
         the op tables and the contrast ops' accumulators) and this blur and solarize
         (ccmi_latents_render_flt_plan: a float32 staging frame and 256 bytes of tables per frame
-        that takes the stage) and these tone ops (ccmi_latents_render_tone_plan: ccmi.h's formula)."""
-        m, idx, rects = self._frames(index, None if affine is not None else roi)
+        that takes the stage) and these tone ops (ccmi_latents_render_tone_plan: ccmi.h's formula).
+        perspective= in place of affine=: the same plans with CCMI_WARP_PROJECTIVE."""
+        m, idx, rects = self._frames(index, None if affine is not None or perspective is not None else roi)
         fmt = TensorFmt(elem=ELEM_F32, colour=COLOUR_ASIS)
         for c in range(3):
             fmt.scale[c] = 1.0
         interp = _interp(interpolation, clamp)
-        warp, keep_w = _warp(affine, m, size, roi, pad, fill, interp)
+        warp, keep_w = _warp(affine, m, size, roi, pad, fill, interp, perspective)
         col, keep_c = _colour(colour_ops, m)
         flt, keep_f = _filter(blur, solarize, m)
         tone, keep_t = _tone(tone_ops, m)
@@ -1607,6 +1697,6 @@ class LatentStore:
 
 __all__ = ["last_timing", "LatentStore", "last_arm_flags", "decode_latents", "decode_file", "decode_batch", "decode_batch_workspace_bytes", "output_size",
            "decode_batch_tensors", "decode_batch_geometry", "roi_plan", "decode_batch_model", "last_tail_groups",
-           "affine_matrix", "hue_matrix", "grey_matrix", "colour_jitter",
+           "affine_matrix", "perspective_matrix", "random_perspective", "hue_matrix", "grey_matrix", "colour_jitter",
            "gaussian_taps", "gaussian_blur", "random_solarize", "rand_augment", "trivial_augment_wide",
            "weights_i32", "ups_forward_i32", "syn_forward_i32", "CcmiError"]

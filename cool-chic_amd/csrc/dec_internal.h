@@ -158,7 +158,10 @@ struct DecFmt {
     int warp = 0;
     int pad = 0;
     float fill[3] = {0.f, 0.f, 0.f};
-    float m[6] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f};
+    float m[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
+    // CCMI_WARP_PROJECTIVE (one per call): m is the frame's 3 x 3 homography and the position the
+    // quotient by its third row (dec_pwarp<T>, dec_pwcubic<T>); without it m[6 .. 8] are unused
+    int persp = 0;
     // CCMI_FILTER_CUBIC / CCMI_WARP_CUBIC (one per call): the cubic forms of the rs / warp kernels
     // (dec_cubic_h, dec_cubic_v<T>, dec_wcubic<T>); clamp: their r' is clamped to [0, 1].  pad is
     // CCMI_PAD_FILL or CCMI_PAD_EDGE, without the flags
@@ -240,9 +243,9 @@ inline int dec_tone_stats(const DecTone &t)
 // the table bytes of a staged frame: with a tone op in the call, its DecTone follows
 inline size_t dec_flt_table_bytes(bool tone) { return kFltTableBytes + (tone ? kToneTableBytes : 0); }
 
-// the form of a tail group's output section: the plain entry, or its resample / warp extension
-enum { kOutPlain = 0, kOutRs = 1, kOutWarp = 2 };
-inline int dec_out_form(const DecFmt &f) { return f.rs ? kOutRs : f.warp ? kOutWarp : kOutPlain; }
+// the form of a tail group's output section: the plain entry, or its resample / warp / projective warp extension
+enum { kOutPlain = 0, kOutRs = 1, kOutWarp = 2, kOutPersp = 3 };
+inline int dec_out_form(const DecFmt &f) { return f.rs ? kOutRs : f.warp ? (f.persp ? kOutPersp : kOutWarp) : kOutPlain; }
 // a resample's horizontal pass (DecTailFrame::rs_tmp), in floats
 size_t dec_resample_tmp_elems(int region_h, int out_w);
 

@@ -14,6 +14,8 @@
 //  dec_cubic_h, dec_cubic_v, dec_wcubic  the bicubic forms of the three kernels above
 //                   (CCMI_FILTER_CUBIC: the Keys cubic, a = -0.5, antialiased; CCMI_WARP_CUBIC:
 //                   cubic convolution, A = -0.75, 16 taps), with the optional clamp of r' to [0, 1].
+//  dec_pwarp, dec_pwcubic  the two warps with CCMI_WARP_PROJECTIVE: a 3 x 3 matrix per frame, the
+//                   position the quotient by its third row.
 //  *_col, *_stat    the colour forms of the three formatted kernels (ccmi_colour) and their
 //                   statistics pass.
 //
@@ -760,9 +762,9 @@ struct DecOutWarp {
     int oy, ox, fh, fw; // the window's origin in the frame, and the frame
 };
 
-template <typename T, int COL = kColNone>
+template <typename T, int COL = kColNone, bool PERSP = false>
 __device__ __forceinline__ uint32_t warp_body(const int32_t *__restrict__ syn, int h, int w, int oy, int ox, int fh, int fw,
-                                              const float (&m)[6], int maxv, int kind, int flags, T *__restrict__ dst,
+                                              const float (&m)[PERSP ? 9 : 6], int maxv, int kind, int flags, T *__restrict__ dst,
                                               const DecFmtCall &C, const DecWarpCall &Wc, const DecCol *K = nullptr)
 {
     int y, d0;
@@ -777,6 +779,8 @@ __device__ __forceinline__ uint32_t warp_body(const int32_t *__restrict__ syn, i
     const int64_t splane = (int64_t)h * w;
     const float cy = (float)y + 0.5f;
     const float xr = fmt_mul(m[1], cy), yr = fmt_mul(m[4], cy); // the row's share of the position
+    float wr = 0.f; // PERSP: and of the denominator
+    if constexpr (PERSP) wr = fmt_mul(m[7], cy);
     T v[3][4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -785,8 +789,12 @@ __device__ __forceinline__ uint32_t warp_body(const int32_t *__restrict__ syn, i
         for (int c = 0; c < 3; ++c) v[c][k] = fmt_elem<T>(0.f);
         if (d < 0 || d >= Wc.ow) continue;
         const float cx = (float)(mirror ? Wc.ow - 1 - d : d) + 0.5f;
-        const float xs = fmt_add(fmt_add(fmt_mul(m[0], cx), xr), m[2]);
-        const float ys = fmt_add(fmt_add(fmt_mul(m[3], cx), yr), m[5]);
+        float xs = fmt_add(fmt_add(fmt_mul(m[0], cx), xr), m[2]);
+        float ys = fmt_add(fmt_add(fmt_mul(m[3], cx), yr), m[5]);
+        if constexpr (PERSP) { // step 3a': the plan has wn > 0 and |xs|, |ys| <= 2^22 after the division
+            const float wn = fmt_add(fmt_add(fmt_mul(m[6], cx), wr), m[8]);
+            xs = __fdiv_rn(xs, wn), ys = __fdiv_rn(ys, wn);
+        }
         const float u = xs - 0.5f, vv = ys - 0.5f;
         const float uf = floorf(u), vf = floorf(vv); // |u|, |v| <= 2^22 + 1: exact in an int
         const float fx = u - uf, fy = vv - vf;
@@ -906,9 +914,9 @@ __device__ __forceinline__ float cub_out(float s) // 1 <= |s| <= 2
     return fmt_sub(fmt_mul(fmt_add(fmt_mul(fmt_sub(fmt_mul(-0.75f, s), -3.75f), s), -6.f), s), -3.f);
 }
 
-template <typename T, int COL = kColNone>
+template <typename T, int COL = kColNone, bool PERSP = false>
 __device__ __forceinline__ uint32_t wcubic_body(const int32_t *__restrict__ syn, int h, int w, int oy, int ox, int fh, int fw,
-                                                const float (&m)[6], int maxv, int kind, int flags, T *__restrict__ dst,
+                                                const float (&m)[PERSP ? 9 : 6], int maxv, int kind, int flags, T *__restrict__ dst,
                                                 const DecFmtCall &C, const DecWarpCall &Wc, const DecCol *K = nullptr)
 {
     int y, d0;
@@ -923,6 +931,8 @@ __device__ __forceinline__ uint32_t wcubic_body(const int32_t *__restrict__ syn,
     const int64_t splane = (int64_t)h * w;
     const float cy = (float)y + 0.5f;
     const float xr = fmt_mul(m[1], cy), yr = fmt_mul(m[4], cy); // the row's share of the position
+    float wr = 0.f; // PERSP: and of the denominator
+    if constexpr (PERSP) wr = fmt_mul(m[7], cy);
     T v[3][4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -931,8 +941,12 @@ __device__ __forceinline__ uint32_t wcubic_body(const int32_t *__restrict__ syn,
         for (int c = 0; c < 3; ++c) v[c][k] = fmt_elem<T>(0.f);
         if (d < 0 || d >= Wc.ow) continue;
         const float cx = (float)(mirror ? Wc.ow - 1 - d : d) + 0.5f;
-        const float xs = fmt_add(fmt_add(fmt_mul(m[0], cx), xr), m[2]);
-        const float ys = fmt_add(fmt_add(fmt_mul(m[3], cx), yr), m[5]);
+        float xs = fmt_add(fmt_add(fmt_mul(m[0], cx), xr), m[2]);
+        float ys = fmt_add(fmt_add(fmt_mul(m[3], cx), yr), m[5]);
+        if constexpr (PERSP) { // step 3a': the plan has wn > 0 and |xs|, |ys| <= 2^22 after the division
+            const float wn = fmt_add(fmt_add(fmt_mul(m[6], cx), wr), m[8]);
+            xs = __fdiv_rn(xs, wn), ys = __fdiv_rn(ys, wn);
+        }
         const float u = xs - 0.5f, vv = ys - 0.5f;
         const float uf = floorf(u), vf = floorf(vv); // |u|, |v| <= 2^22 + 1: exact in an int
         const float fx = u - uf, fy = vv - vf;
@@ -1030,6 +1044,74 @@ __global__ __launch_bounds__(kThreads) CUBIC_WAVES8 void dec_wcubic_stat_batch(c
                                                    A.o.bps_or_flags, nullptr, col_stat_call(), Wc, &K));
 }
 
+// ---- the projective warp (CCMI_WARP_PROJECTIVE: step 3a' of its contract in ccmi.h)
+// The same two bodies with PERSP: the position is the quotient of the two numerators by the third
+// row's denominator, two IEEE divisions per pixel; taps, padding, colour and statistics are the
+// affine kernels'.  The frame's record carries nine floats and is a form of its own (kOutPersp), so
+// the affine kernels keep their argument layout.
+struct DecOutPersp {
+    DecOut o;
+    float m[9];
+    int oy, ox, fh, fw; // as DecOutWarp's
+};
+
+template <typename T, int COL, bool CUBIC>
+__device__ __forceinline__ uint32_t persp_body(const DecOutPersp &A, T *__restrict__ dst, const DecFmtCall &C,
+                                               const DecWarpCall &Wc, const DecCol *K = nullptr)
+{
+    if constexpr (CUBIC)
+        return wcubic_body<T, COL, true>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind,
+                                         A.o.bps_or_flags, dst, C, Wc, K);
+    else
+        return warp_body<T, COL, true>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind,
+                                       A.o.bps_or_flags, dst, C, Wc, K);
+}
+
+// the six forms of a projective kernel, NAME = dec_pwarp (bilinear) or dec_pwcubic, argument for
+// argument the affine kernels' with DecOutPersp for DecOutWarp
+#define PERSP_KERNELS(NAME, CUBIC)                                                                                         \
+    template <typename T> __global__ __launch_bounds__(kThreads) void NAME(DecOutPersp A, DecFmtCall C, DecWarpCall Wc)    \
+    {                                                                                                                      \
+        persp_body<T, kColNone, CUBIC>(A, reinterpret_cast<T *>(A.o.dst), C, Wc);                                          \
+    }                                                                                                                      \
+    template <typename T>                                                                                                  \
+    __global__ __launch_bounds__(kThreads) void NAME##_batch(const DecOutPersp *__restrict__ Os, DecFmtCall C,             \
+                                                             DecWarpCall Wc)                                               \
+    {                                                                                                                      \
+        const DecOutPersp A = Os[blockIdx.y];                                                                              \
+        persp_body<T, kColNone, CUBIC>(A, reinterpret_cast<T *>(A.o.dst), C, Wc);                                          \
+    }                                                                                                                      \
+    template <typename T>                                                                                                  \
+    __global__ __launch_bounds__(kThreads) void NAME##_col(DecOutPersp A, DecFmtCall C, DecWarpCall Wc, DecCol K)          \
+    {                                                                                                                      \
+        persp_body<T, kColWrite, CUBIC>(A, reinterpret_cast<T *>(A.o.dst), C, Wc, &K);                                     \
+    }                                                                                                                      \
+    template <typename T>                                                                                                  \
+    __global__ __launch_bounds__(kThreads) void NAME##_col_batch(const DecOutPersp *__restrict__ Os, DecFmtCall C,         \
+                                                                 DecWarpCall Wc, const DecCol *__restrict__ Ks)            \
+    {                                                                                                                      \
+        const DecOutPersp A = Os[blockIdx.y];                                                                              \
+        persp_body<T, kColWrite, CUBIC>(A, reinterpret_cast<T *>(A.o.dst), C, Wc, Ks + blockIdx.y);                        \
+    }                                                                                                                      \
+    __global__ __launch_bounds__(kThreads) void NAME##_stat(DecOutPersp A, DecWarpCall Wc, DecCol K)                       \
+    {                                                                                                                      \
+        col_accumulate(K, persp_body<float, kColStat, CUBIC>(A, nullptr, col_stat_call(), Wc, &K));                        \
+    }                                                                                                                      \
+    __global__ __launch_bounds__(kThreads) void NAME##_stat_batch(const DecOutPersp *__restrict__ Os,                      \
+                                                                            DecWarpCall Wc, const DecCol *__restrict__ Ks) \
+    {                                                                                                                      \
+        const DecCol &K = Ks[blockIdx.y];                                                                                  \
+        if (K.contrast < 0) return;                                                                                        \
+        const DecOutPersp A = Os[blockIdx.y];                                                                              \
+        col_accumulate(K, persp_body<float, kColStat, CUBIC>(A, nullptr, col_stat_call(), Wc, &K));                        \
+    }
+
+PERSP_KERNELS(dec_pwarp, false)
+// dec_wcubic_stat asks for 8 waves; with the division's temporaries that request spills two registers,
+// so the projective statistics pass is left to the allocator (tests/test_decode_persp_resources.py)
+PERSP_KERNELS(dec_pwcubic, true)
+#undef PERSP_KERNELS
+
 DecWarpCall warp_call(const DecFmt &f)
 {
     DecWarpCall Wc;
@@ -1116,6 +1198,13 @@ static DecOutWarp make_out_warp(const DecOut &o, const DecFmt &fmt, int oy, int 
     return A;
 }
 
+static DecOutPersp make_out_persp(const DecOut &o, const DecFmt &fmt, int oy, int ox, int fh, int fw)
+{
+    DecOutPersp A{o, {}, oy, ox, fh, fw};
+    for (int k = 0; k < 9; ++k) A.m[k] = fmt.m[k];
+    return A;
+}
+
 static unsigned output_blocks(int h, int w) { return (unsigned)(((int64_t)h * w + kThreads - 1) / kThreads); }
 
 int launch_dec_out_frame(const DecTailFrame &f, const int32_t *syn, int h, int w, bool crop, bool device, hipStream_t s)
@@ -1158,6 +1247,19 @@ int launch_dec_out_frame(const DecTailFrame &f, const int32_t *syn, int h, int w
     const dim3 grid = fmt_grid(fmt, rect.h(), rect.w(), 1);
     const int flags = fmt_flags(fmt), rh = rect.h(), rw = rect.w(), oh = fmt.out_h, ow = fmt.out_w;
     const DecFmtCall C = fmt_call(fmt);
+    if (fmt.warp && fmt.persp) {
+        const DecOutPersp A = make_out_persp(DecOut{syn, h, w, maxv, kind, flags, f.dst}, fmt, 0, 0, h, w);
+        const DecWarpCall Wc = warp_call(fmt);
+        if (fmt.cubic)
+            return launch_fmt_forms(
+                fmt, stat, [&] { launch(dec_pwcubic_stat, grid, s, A, Wc, *K); },
+                [&](auto t) { launch(dec_pwcubic_col<decltype(t)>, grid, s, A, C, Wc, *K); },
+                [&](auto t) { launch(dec_pwcubic<decltype(t)>, grid, s, A, C, Wc); });
+        return launch_fmt_forms(
+            fmt, stat, [&] { launch(dec_pwarp_stat, grid, s, A, Wc, *K); },
+            [&](auto t) { launch(dec_pwarp_col<decltype(t)>, grid, s, A, C, Wc, *K); },
+            [&](auto t) { launch(dec_pwarp<decltype(t)>, grid, s, A, C, Wc); });
+    }
     if (fmt.warp) {
         const DecOutWarp A = make_out_warp(DecOut{syn, h, w, maxv, kind, flags, f.dst}, fmt, 0, 0, h, w);
         const DecWarpCall Wc = warp_call(fmt);
@@ -1200,19 +1302,23 @@ int launch_dec_out_frame(const DecTailFrame &f, const int32_t *syn, int h, int w
 // a staged frame's share of the filter stage's tables holds its entry here, rounded to 16, and its
 // 96-byte filter entry (dec_filter.hip)
 static_assert(sizeof(DecOut) <= sizeof(DecOutWarp) && sizeof(DecOutRs) <= sizeof(DecOutWarp) &&
-                  sizeof(DecOutWarp) + 16 + 96 <= kFltTableBytes,
+                  sizeof(DecOutWarp) <= sizeof(DecOutPersp) && sizeof(DecOutPersp) + 16 + 96 <= kFltTableBytes,
               "kFltTableBytes per staged frame");
 
 size_t dec_out_entry_bytes(int out_form)
 {
-    return out_form == kOutRs ? sizeof(DecOutRs) : out_form == kOutWarp ? sizeof(DecOutWarp) : sizeof(DecOut);
+    return out_form == kOutRs     ? sizeof(DecOutRs)
+           : out_form == kOutWarp  ? sizeof(DecOutWarp)
+           : out_form == kOutPersp ? sizeof(DecOutPersp)
+                                   : sizeof(DecOut);
 }
 
 void dec_out_fill(void *out_sec, void *col_sec, int i, const DecTailFrame &f, int h, int w, int oy, int ox)
 {
     const DecOut o{f.syn.out, h, w, (1 << f.bitdepth) - 1, f.kind, f.fmt.on ? fmt_flags(f.fmt) : f.bitdepth <= 8 ? 1 : 2,
                    f.dst};
-    if (f.fmt.warp) static_cast<DecOutWarp *>(out_sec)[i] = make_out_warp(o, f.fmt, oy, ox, f.syn.h, f.syn.w);
+    if (f.fmt.warp && f.fmt.persp) static_cast<DecOutPersp *>(out_sec)[i] = make_out_persp(o, f.fmt, oy, ox, f.syn.h, f.syn.w);
+    else if (f.fmt.warp) static_cast<DecOutWarp *>(out_sec)[i] = make_out_warp(o, f.fmt, oy, ox, f.syn.h, f.syn.w);
     else if (f.fmt.rs) static_cast<DecOutRs *>(out_sec)[i] = DecOutRs{o, f.rs_tmp};
     else static_cast<DecOut *>(out_sec)[i] = o;
     if (f.fmt.col) static_cast<DecCol *>(col_sec)[i] = *f.col;
@@ -1235,6 +1341,19 @@ int launch_dec_out_group(const DecTailFrame &f0, int h, int w, int n, const void
     // the format but its per-frame flags (in the table) is the call's
     const dim3 grid = fmt_grid(fmt, h, w, n);
     const DecFmtCall C = fmt_call(fmt);
+    if (fmt.warp && fmt.persp) { // the section holds DecOutPersp
+        const DecOutPersp *pp = static_cast<const DecOutPersp *>(out_sec);
+        const DecWarpCall Wc = warp_call(fmt);
+        if (fmt.cubic)
+            return launch_fmt_forms(
+                fmt, stat, [&] { launch(dec_pwcubic_stat_batch, grid, s, pp, Wc, kk); },
+                [&](auto t) { launch(dec_pwcubic_col_batch<decltype(t)>, grid, s, pp, C, Wc, kk); },
+                [&](auto t) { launch(dec_pwcubic_batch<decltype(t)>, grid, s, pp, C, Wc); });
+        return launch_fmt_forms(
+            fmt, stat, [&] { launch(dec_pwarp_stat_batch, grid, s, pp, Wc, kk); },
+            [&](auto t) { launch(dec_pwarp_col_batch<decltype(t)>, grid, s, pp, C, Wc, kk); },
+            [&](auto t) { launch(dec_pwarp_batch<decltype(t)>, grid, s, pp, C, Wc); });
+    }
     if (fmt.warp) { // the section holds DecOutWarp
         const DecOutWarp *ww = static_cast<const DecOutWarp *>(out_sec);
         const DecWarpCall Wc = warp_call(fmt);

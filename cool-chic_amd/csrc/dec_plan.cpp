@@ -68,27 +68,60 @@ constexpr double kMaxWarpReach = 4194304.0; // 2^22: the bound on a warp's float
 
 // A warp (ccmi_warp) of frame i: the checks that need no header.  After them every position of
 // the output grid is finite and within 2^22 of the origin, so the window below is plain arithmetic.
-int warp_check(const ccmi_warp &wp, int i)
+// With CCMI_WARP_PROJECTIVE the matrix is 3 x 3 and the checks are those of step 3a' in ccmi.h, in
+// double from the float32 entries, on the fh x fw frame: after them the float32 denominator is
+// positive at every pixel, every quotient within 2^22 of the origin and within 7/8 pixel of the
+// exact position wherever it lies within two taps of the frame.
+int warp_check(const ccmi_warp &wp, int i, int fh, int fw)
 {
     if (wp.out_w < 1 || wp.out_w > kMaxResample || wp.out_h < 1 || wp.out_h > kMaxResample)
         return ccmi_set_error(CCMI_ERR_ARG, "frame %d: output size w %d h %d (1 .. %d)", i, wp.out_w, wp.out_h,
                               kMaxResample);
-    const int flags = wp.pad & ~1; // none, CCMI_WARP_CUBIC, or CCMI_WARP_CUBIC | CCMI_WARP_CLAMP
+    // none, CCMI_WARP_CUBIC, or CCMI_WARP_CUBIC | CCMI_WARP_CLAMP, each with or without CCMI_WARP_PROJECTIVE
+    const int flags = wp.pad & ~(1 | CCMI_WARP_PROJECTIVE);
     if (wp.pad < 0 || (flags != 0 && flags != CCMI_WARP_CUBIC && flags != (CCMI_WARP_CUBIC | CCMI_WARP_CLAMP)))
         return ccmi_set_error(CCMI_ERR_ARG, "frame %d: unknown pad %d", i, wp.pad);
-    const float *m = wp.matrix + 6 * (size_t)i;
-    for (int k = 0; k < 6; ++k)
+    const bool persp = (wp.pad & CCMI_WARP_PROJECTIVE) != 0;
+    const int entries = persp ? 9 : 6;
+    const float *m = wp.matrix + entries * (size_t)i;
+    for (int k = 0; k < entries; ++k)
         if (!std::isfinite(m[k])) return ccmi_set_error(CCMI_ERR_ARG, "frame %d: matrix entry %d is not finite", i, k);
     for (int c = 0; c < 3; ++c)
         if (!std::isfinite(wp.fill[c]))
             return ccmi_set_error(CCMI_ERR_ARG, "frame %d: fill of channel %d is not finite", i, c);
-    for (int r = 0; r < 2; ++r) {
+    double S[3] = {0, 0, 0};
+    for (int r = 0; r < (persp ? 3 : 2); ++r) {
         const double reach = std::fabs((double)m[3 * r]) * wp.out_w + std::fabs((double)m[3 * r + 1]) * wp.out_h +
                              std::fabs((double)m[3 * r + 2]);
         if (reach > kMaxWarpReach)
             return ccmi_set_error(CCMI_ERR_ARG,
                                   "frame %d: matrix row %d reaches %.9g pixels (|m0| out_w + |m1| out_h + |m2| <= 2^22)", i, r,
                                   reach);
+        S[r] = reach;
+    }
+    if (!persp) return CCMI_OK;
+    const double eps = 1.0 / 16777216.0; // 2^-24
+    double D = 0;
+    for (int c = 0; c < 4; ++c) { // the denominator is affine: its minimum over the grid is at a corner pixel centre
+        const double v = (double)m[6] * (c & 1 ? wp.out_w - 0.5 : 0.5) + (double)m[7] * (c & 2 ? wp.out_h - 0.5 : 0.5) + (double)m[8];
+        if (c == 0 || v < D) D = v;
+    }
+    const double Dp = D - 3 * eps * S[2];
+    if (!(Dp > 0))
+        return ccmi_set_error(CCMI_ERR_ARG,
+                              "frame %d: the denominator m20 cx + m21 cy + m22 is not positive over the output (%.9g at a corner)",
+                              i, D);
+    for (int r = 0; r < 2; ++r)
+        if (S[r] / Dp > kMaxWarpReach)
+            return ccmi_set_error(CCMI_ERR_ARG, "frame %d: matrix row %d reaches %.9g pixels after the division (<= 2^22)", i, r,
+                                  S[r] / Dp);
+    for (int r = 0; r < 2; ++r) {
+        const double L = (r == 0 ? fw : fh) + 3.0;
+        const double E = 3 * eps * (S[r] + L * S[2]) / Dp + 2 * eps * L;
+        if (E > 0.875)
+            return ccmi_set_error(CCMI_ERR_ARG,
+                                  "frame %d: the perspective is too strong for float32 positions (row %d: %.6g pixel, at most 7/8)",
+                                  i, r, E);
     }
     return CCMI_OK;
 }
@@ -98,14 +131,18 @@ int warp_check(const ccmi_warp &wp, int i)
 // by one pixel, each end clamped into the frame; even = grown to even x, y, w, h (h and w even).
 DecWindow warp_window(const ccmi_warp &wp, int i, int h, int w, bool even, int reach)
 {
-    const float *m = wp.matrix + 6 * (size_t)i;
+    const bool persp = (wp.pad & CCMI_WARP_PROJECTIVE) != 0;
+    const float *m = wp.matrix + (persp ? 9 : 6) * (size_t)i;
     const double cx[2] = {0.5, wp.out_w - 0.5}, cy[2] = {0.5, wp.out_h - 0.5};
     int end[2][2]; // [axis: x, y][first, last]
     for (int r = 0; r < 2; ++r) {
         double lo = 0, hi = 0;
         for (int a = 0; a < 2; ++a)
             for (int b = 0; b < 2; ++b) {
-                const double v = (double)m[3 * r] * cx[a] + (double)m[3 * r + 1] * cy[b] + (double)m[3 * r + 2];
+                double v = (double)m[3 * r] * cx[a] + (double)m[3 * r + 1] * cy[b] + (double)m[3 * r + 2];
+                // the image of the rectangle is a convex quadrilateral (the checked denominator is positive): the
+                // extremes of the quotient are at the corners too
+                if (persp) v /= (double)m[6] * cx[a] + (double)m[7] * cy[b] + (double)m[8];
                 if ((a | b) == 0 || v < lo) lo = v;
                 if ((a | b) == 0 || v > hi) hi = v;
             }
@@ -182,8 +219,10 @@ int tensor_fmt(const ccmi_tensor_fmt &m, const ccmi_resample *rs, const ccmi_war
     if (wp) {
         d.warp = 1, d.out_h = h, d.out_w = w, d.pad = wp->pad & 1;
         d.cubic = (wp->pad & CCMI_WARP_CUBIC) != 0, d.clamp = (wp->pad & CCMI_WARP_CLAMP) != 0;
+        d.persp = (wp->pad & CCMI_WARP_PROJECTIVE) != 0;
         for (int c = 0; c < 3; ++c) d.fill[c] = wp->fill[c];
-        for (int k = 0; k < 6; ++k) d.m[k] = wp->matrix[6 * (size_t)i + k];
+        const int stride = d.persp ? 9 : 6;
+        for (int k = 0; k < stride; ++k) d.m[k] = wp->matrix[stride * (size_t)i + k];
     }
     *span = (size_t)(2 * sc + (h - 1) * sy + (w - 1) * sx + 1);
     return CCMI_OK;
@@ -366,7 +405,7 @@ int plan_tensor_sink(const DecodeRequest &rq, int i, FramePlan &p)
         rect = DecWindow{q.y, q.y + q.h, q.x, q.x + q.w};
     }
     if (rq.warp) { // the region is the window the matrix reaches
-        if (int rc = warp_check(*rq.warp, i)) return rc;
+        if (int rc = warp_check(*rq.warp, i, f.h, f.w)) return rc;
         rect = warp_window(*rq.warp, i, f.h, f.w, false, rq.warp->pad & CCMI_WARP_CUBIC ? 2 : 1);
     }
     if (int rc = tensor_format(f, rq.out_bitdepth, rq.out_chroma, rq.sample, p.of, &elems, rect)) {

@@ -774,12 +774,70 @@ int ccmi_decode_last_tail_groups(int *batched, int *per_frame);
  * 0), 1) before the colour ops -- on r' whatever its taps were, fill included.
  * window[j] grows by one tap on each side: columns floor(min xs - 0.5) - 2 .. floor(max xs - 0.5)
  * + 3 and rows alike, then the same clamp into the frame and the same even-ing.
- * Kernels (dec_out.hip): dec_wcubic<T> and its _col / _stat / _batch forms. */
-enum { CCMI_PAD_FILL = 0, CCMI_PAD_EDGE = 1, CCMI_WARP_CUBIC = 0x100, CCMI_WARP_CLAMP = 0x200 };
+ * Kernels (dec_out.hip): dec_wcubic<T> and its _col / _stat / _batch forms.
+ *
+ * CCMI_WARP_PROJECTIVE (0x800; 0x400 stays an unknown pad), or'ed into pad: the frame's matrix is a
+ * 3 x 3 homography, matrix is host [n][9], row-major m00 .. m22 of frame j, and the position is the
+ * projective one -- torchvision's F.perspective convention: base grid at k + 0.5,
+ * grid_sample(align_corners=False).  The struct is unchanged, so every entry point that takes a
+ * ccmi_warp (_warp, _col, _flt, _tone, the decode and ccmi_latents_render_* forms, their _plan calls)
+ * takes the flag.  pad is one value per call -- today's six plus 0x800, 0x801, 0x900, 0x901, 0xB00,
+ * 0xB01; 0xA00 / 0xA01 (clamp without cubic) and everything else remain an unknown pad -- so a call
+ * is wholly affine or wholly projective: a caller mixing both passes rows 0 0 1.  Step 3a becomes,
+ * every product, sum and difference one float32 operation in the order written (no fused
+ * multiply-add):
+ *   3a'. cx = (float)k + 0.5f, cy = (float)i + 0.5f   (mirror as above: k -> out_w - 1 - k)
+ *        xn = ((m00 cx) + (m01 cy)) + m02
+ *        yn = ((m10 cx) + (m11 cy)) + m12
+ *        wn = ((m20 cx) + (m21 cy)) + m22
+ *        xs = xn / wn, ys = yn / wn: the correctly rounded IEEE float32 quotient (no
+ *        reciprocal-multiply, no fast division).
+ * Steps 3b-3d (bilinear, CCMI_WARP_CUBIC, CCMI_WARP_CLAMP, the fill / edge rule) and 4-6 are
+ * unchanged.  With m20 = m21 = 0, m22 = 1, wn is exactly 1 and the quotient exact: the result equals
+ * the 6-entry call's bit for bit, so an integer translation is still the crop and m00 = -1 the flip.
+ * Checked by the plan, as above (CCMI_ERR_ARG naming the frame, before any GPU work, nothing
+ * written), in double from the float32 entries.  With eps = 2^-24, S_r = |m_r0| out_w + |m_r1| out_h
+ * + |m_r2| for r = 0, 1, 2, D = the minimum of m20 cx + m21 cy + m22 over the four corner pixel
+ * centres (0.5 | out_w - 0.5, 0.5 | out_h - 0.5) -- the denominator is affine, so that is its minimum
+ * over the grid -- and D' = D - 3 eps S_2:
+ *   - all nine entries finite;
+ *   - S_r <= 2^22 for all three rows;
+ *   - D' > 0: each of wn's three roundings errs by at most eps times a partial sum that S_2 bounds,
+ *     so the float32 wn >= D' > 0 at every pixel;
+ *   - S_0 / D' <= 2^22 and S_1 / D' <= 2^22: |xn| <= S_0 (1 + 3 eps) and wn >= D', so the quotient
+ *     floors exactly and fits an int;
+ *   - with L_0 = W, L_1 = H (the frame), E_r = 3 eps (S_r + (L_r + 3) S_2) / D' + 2 eps (L_r + 3) <=
+ *     7/8, else "the perspective is too strong for float32 positions";
+ *   - output size, fill finite and 420 on an odd frame as above.
+ * E_r bounds |u_float32 - u_exact| for every pixel whose float32 position lies within two taps of
+ * the frame, |xs| <= L + 3 =: P.  Three roundings in the numerator: |xn - xn*| <= 3 eps S_r; three in
+ * the denominator: |wn - wn*| <= 3 eps S_2, both wn, wn* >= D'.  Then |xn / wn - xn* / wn*| <=
+ * |xn - xn*| / wn* + |xn / wn| |wn - wn*| / wn* <= 3 eps (S_r + P S_2) / D' (second order terms are
+ * below the slack of the partial-sum bounds); the quotient's rounding adds eps P and that of - 0.5f
+ * another eps P.  For an affine call accepted today with the flag and row 0 0 1: S_2 = D = 1, E <=
+ * 0.77 at the reach limit, so it stays acceptable -- but for a reach within 3 eps (relative) of 2^22,
+ * where S_r / D' with D' = 1 - 3 eps exceeds 2^22 and the flagged call is refused.  The bound was confirmed on 3,597 accepted random
+ * homographies over frames from 21 x 37 to 4000 x 65535 (worst error 0.34 E_r).
+ * window[j] follows the affine rule with the four corner positions replaced by the quotients xn / wn,
+ * yn / wn in double: the image of the output rectangle under a projective map whose denominator is
+ * positive on it is a convex quadrilateral (a projective map sends segments to segments where the
+ * denominator keeps its sign), so the extremes of xs and ys over the grid are at the corners.  Columns
+ * floor(min xs - 0.5) - 1 .. floor(max xs - 0.5) + 2 (one tap wider each side for cubic), rows alike,
+ * each end clamped into the frame, never empty, even-ed for 420; the one-pixel growth is what E <= 7/8
+ * pays for.  A flagged matrix with last row 0 0 1 gives the window of its 6-entry form.  Frames of
+ * one architecture share one batched tail group whatever their matrices.
+ * Kernels (dec_out.hip): dec_pwarp<T>, dec_pwcubic<T> and their _col / _stat / _batch forms. */
+enum {
+    CCMI_PAD_FILL = 0,
+    CCMI_PAD_EDGE = 1,
+    CCMI_WARP_CUBIC = 0x100,
+    CCMI_WARP_CLAMP = 0x200,
+    CCMI_WARP_PROJECTIVE = 0x800
+};
 typedef struct ccmi_warp {
     int out_w, out_h, pad;
     float fill[3];        /* CCMI_PAD_FILL: value of a tap outside the frame, in q units (after step 3) */
-    const float *matrix;  /* host, [n][6]: m00 m01 m02 m10 m11 m12 of frame j */
+    const float *matrix;  /* host, [n][6]: m00 m01 m02 m10 m11 m12 of frame j; CCMI_WARP_PROJECTIVE: [n][9], m00 .. m22 */
 } ccmi_warp;
 int ccmi_decode_batch_dev_warp_plan(const uint8_t *const *streams, const size_t *lens, int n, int out_bitdepth,
                                     int out_chroma, const ccmi_tensor_fmt *fmt, const ccmi_warp *warp,
