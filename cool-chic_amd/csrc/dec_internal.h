@@ -139,7 +139,7 @@ size_t dec_ups_workspace_elems_win(const DecRoi &r, int L); // the stacks of lev
 
 // Formatted tensor output (ccmi_tensor_fmt, validated and resolved by the plan): three full-size
 // channels per pixel, colour, affine, element type, strides and mirror applied by the output
-// kernel (dec_output_fmt<T>, dec_out.hip).  Everything but `matrix` and `mirror` is one value per call.
+// kernel (dec_fmt<Plain, T, TABLE>, dec_out.hip).  Everything but `matrix` and `mirror` is one value per call.
 struct DecFmt {
     int on = 0;     // 0: the planar u8 / u16 / f32 tensor output
     int elem = 0;   // CCMI_ELEM_*
@@ -148,22 +148,22 @@ struct DecFmt {
     float scale[3] = {1.f, 1.f, 1.f}, bias[3] = {0.f, 0.f, 0.f};
     int64_t stride_c = 0, stride_y = 0, stride_x = 0; // elements, resolved (never all 0)
     // ccmi_resample (one per call): the region, of any size, is resampled to out_h x out_w between
-    // the colour step and scale / bias (dec_resample_h, dec_resample_v<T>); strides and mirror
+    // the colour step and scale / bias (dec_resize_h<CUBIC>, dec_fmt<Resize<CUBIC>, T, TABLE>); strides and mirror
     // then refer to the output size
     int rs = 0;
     int out_h = 0, out_w = 0;
     // ccmi_warp: every out_h x out_w output pixel is a bilinear sample of the whole frame at the
-    // position this frame's matrix m gives (dec_warp<T>), between the same two steps; pad and
+    // position this frame's matrix m gives (dec_fmt<Warp<CUBIC, PERSP>, T, TABLE>), between the same two steps; pad and
     // fill are one per call.  Never together with rs
     int warp = 0;
     int pad = 0;
     float fill[3] = {0.f, 0.f, 0.f};
     float m[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f};
     // CCMI_WARP_PROJECTIVE (one per call): m is the frame's 3 x 3 homography and the position the
-    // quotient by its third row (dec_pwarp<T>, dec_pwcubic<T>); without it m[6 .. 8] are unused
+    // quotient by its third row (Warp<CUBIC, true>); without it m[6 .. 8] are unused
     int persp = 0;
     // CCMI_FILTER_CUBIC / CCMI_WARP_CUBIC (one per call): the cubic forms of the rs / warp kernels
-    // (dec_cubic_h, dec_cubic_v<T>, dec_wcubic<T>); clamp: their r' is clamped to [0, 1].  pad is
+    // (Resize<true>, Warp<true, PERSP>); clamp: their r' is clamped to [0, 1].  pad is
     // CCMI_PAD_FILL or CCMI_PAD_EDGE, without the flags
     int cubic = 0, clamp = 0;
     // ccmi_colour with at least one op in the call (one value per call): the colour forms of the

@@ -1,30 +1,35 @@
 // dec_out.hip -- path B: the output stage of the bit-exact fixed-point .cool decoder: the 12-bit
 // synthesis output of dec_tail.hip to file bytes, planar tensors or the formatted tensor, every
-// sink as a single-frame kernel (the per-frame tail) and a _batch kernel (a tail group).
+// sink for one frame (the per-frame tail: the frame is the kernel's argument) and for a tail group
+// (frame blockIdx.y of the group's tables).
 //
 //  dec_output       444 -> 420/444 8/10-bit or PPM payload (ccdecapi.cpp:59-240).
 //  dec_output_tensor  the same samples as planar u8 / u16 / f32 device tensors (no file
 //                   layout): one packed store per 4 destination samples, any sample alignment.
-//  dec_output_fmt   the same samples as the formatted tensor of a ccmi_tensor_fmt: three
-//                   full-size channels, YUV -> RGB, scale / bias, f32 / f16 / bf16, strides, mirror.
-//  dec_resample_h, dec_resample_v  the formatted tensor with a ccmi_resample: the region through an
-//                   antialiased triangle filter to the output size, horizontal then vertical pass.
-//  dec_warp         the formatted tensor with a ccmi_warp: every output pixel a bilinear sample of
-//                   the frame at the position the frame's 2 x 3 matrix gives, fill or edge padding.
-//  dec_cubic_h, dec_cubic_v, dec_wcubic  the bicubic forms of the three kernels above
-//                   (CCMI_FILTER_CUBIC: the Keys cubic, a = -0.5, antialiased; CCMI_WARP_CUBIC:
-//                   cubic convolution, A = -0.75, 16 taps), with the optional clamp of r' to [0, 1].
-//  dec_pwarp, dec_pwcubic  the two warps with CCMI_WARP_PROJECTIVE: a 3 x 3 matrix per frame, the
-//                   position the quotient by its third row.
-//  *_col, *_stat    the colour forms of the three formatted kernels (ccmi_colour) and their
-//                   statistics pass.
+//  The formatted tensor of a ccmi_tensor_fmt has seven geometries, each a description (a struct)
+//  that three kernel templates are instantiated over -- dec_fmt<G, T, TABLE>, its colour form
+//  dec_fmt_col<G, T, TABLE> (ccmi_colour) and the statistics pass dec_fmt_stat<G, TABLE>:
+//  Plain            the same samples as three full-size channels, YUV -> RGB, scale / bias, f32 /
+//                   f16 / bf16, strides, mirror.
+//  Resize<CUBIC>    with a ccmi_resample: the region through an antialiased triangle filter to the
+//                   output size, horizontal (dec_resize_h<CUBIC>, dec_resize_h_batch<CUBIC>) then
+//                   vertical pass; CUBIC (CCMI_FILTER_CUBIC): the Keys cubic, a = -0.5.
+//  Warp<CUBIC, PERSP>  with a ccmi_warp: every output pixel a bilinear sample of the frame at the
+//                   position the frame's 2 x 3 matrix gives, fill or edge padding; CUBIC
+//                   (CCMI_WARP_CUBIC): cubic convolution, A = -0.75, 16 taps; PERSP
+//                   (CCMI_WARP_PROJECTIVE): a 3 x 3 matrix per frame, the position the quotient by
+//                   its third row.  The cubic forms have the optional clamp of r' to [0, 1].
 //
 // The tail sees four functions (dec_internal.h): the size and the filling of an entry of a group's
 // output section, launch_dec_out_group and launch_dec_out_frame.  Both launchers choose the
-// geometry, hand its grid, its three kernel forms and their arguments to launch_fmt_forms, which
-// is the only place that knows the colour protocol and the element types.  A new formatted sink is
-// one more branch in each launcher; a new element type one more case of with_elem_type.
+// geometry once (with_geometry) and hand its grid and its frame or tables to launch_fmt_forms,
+// which is the only place that knows the colour protocol and the element types.  A new formatted
+// sink is one more geometry struct and one more row of with_geometry; a new element type one more
+// case of with_elem_type.
 #include <stdlib.h>
+
+#include <tuple>
+#include <type_traits>
 
 #include "dec_device.h"
 #include "dec_internal.h"
@@ -375,60 +380,6 @@ __device__ __forceinline__ uint32_t output_fmt_body(const int32_t *__restrict__ 
     return sum;
 }
 
-template <typename T>
-__global__ __launch_bounds__(kThreads) void dec_output_fmt(const int32_t *__restrict__ syn, int H, int W, int oy, int ox,
-                                                           int h, int w, int maxv, int kind, int flags,
-                                                           T *__restrict__ dst, DecFmtCall C)
-{
-    output_fmt_body<T>(syn, (int64_t)H * W, W, oy, ox, h, w, maxv, kind, flags, dst, C);
-}
-
-// the colour forms (ccmi_colour): K = the frame's ops; the statistics pass of a frame with a contrast op
-template <typename T>
-__global__ __launch_bounds__(kThreads) void dec_output_fmt_col(const int32_t *__restrict__ syn, int H, int W, int oy, int ox,
-                                                               int h, int w, int maxv, int kind, int flags,
-                                                               T *__restrict__ dst, DecFmtCall C, DecCol K)
-{
-    output_fmt_body<T, kColWrite>(syn, (int64_t)H * W, W, oy, ox, h, w, maxv, kind, flags, dst, C, &K);
-}
-
-__global__ __launch_bounds__(kThreads) void dec_output_fmt_stat(const int32_t *__restrict__ syn, int H, int W, int oy, int ox,
-                                                                int h, int w, int maxv, int kind, int flags, DecCol K)
-{
-    col_accumulate(K, output_fmt_body<float, kColStat>(syn, (int64_t)H * W, W, oy, ox, h, w, maxv, kind, flags, nullptr,
-                                                       col_stat_call(), &K));
-}
-
-// a tail group: frame blockIdx.y's compact H x W synthesis output (DecOut::bps_or_flags = its kFmt* flags)
-template <typename T>
-__global__ __launch_bounds__(kThreads) void dec_output_fmt_batch(const DecOut *__restrict__ Os, DecFmtCall C)
-{
-    const DecOut O = Os[blockIdx.y];
-    output_fmt_body<T>(O.syn, (int64_t)O.H * O.W, O.W, 0, 0, O.H, O.W, O.maxv, O.kind, O.bps_or_flags, reinterpret_cast<T *>(O.dst),
-                       C);
-}
-
-// the colour forms of a tail group: Ks = the group's op tables, one per frame
-template <typename T>
-__global__ __launch_bounds__(kThreads) void dec_output_fmt_col_batch(const DecOut *__restrict__ Os, DecFmtCall C,
-                                                                     const DecCol *__restrict__ Ks)
-{
-    const DecOut O = Os[blockIdx.y];
-    output_fmt_body<T, kColWrite>(O.syn, (int64_t)O.H * O.W, O.W, 0, 0, O.H, O.W, O.maxv, O.kind, O.bps_or_flags,
-                                  reinterpret_cast<T *>(O.dst), C, Ks + blockIdx.y);
-}
-
-// only the frames with a contrast op take part
-__global__ __launch_bounds__(kThreads) void dec_output_fmt_stat_batch(const DecOut *__restrict__ Os,
-                                                                      const DecCol *__restrict__ Ks)
-{
-    const DecCol &K = Ks[blockIdx.y];
-    if (K.contrast < 0) return;
-    const DecOut O = Os[blockIdx.y];
-    col_accumulate(K, output_fmt_body<float, kColStat>(O.syn, (int64_t)O.H * O.W, O.W, 0, 0, O.H, O.W, O.maxv, O.kind, O.bps_or_flags,
-                                                       nullptr, col_stat_call(), &K));
-}
-
 unsigned output_fmt_blocks(int h, int w)
 {
     return (unsigned)(((int64_t)h * fmt_row_groups(w) + kThreads - 1) / kThreads);
@@ -443,9 +394,9 @@ int fmt_flags(const DecFmt &f)
 // The formatted sink with a ccmi_resample (steps 3a-3c of the contract in ccmi.h): the region,
 // h x w, goes through an antialiased triangle filter to oh x ow between the colour step and
 // scale / bias.  Two launches:
-//   dec_resample_h     thread = (region row y, output column i), three channels: q per tap from
+//   dec_resize_h       thread = (region row y, output column i), three channels: q per tap from
 //                      the synthesis output, t[c][y][i] (float32, [3][h][ow]) to the workspace;
-//   dec_resample_v<T>  thread = (output row, 4 destination pixels), as the formatted output stage:
+//   dec_fmt<Resize, T> thread = (output row, 4 destination pixels), as the formatted output stage:
 //                      the vertical pass over t (loads coalesced along the row), then scale / bias,
 //                      element conversion and the stores of fmt_store.  mirror reads column
 //                      ow - 1 - x'.
@@ -506,11 +457,6 @@ __device__ __forceinline__ CubTaps cub_taps(int i, int I, int O)
     return t;
 }
 
-// The int64 weights take the cubic resize kernels a few registers past 64; asked for 8 waves per SIMD
-// the compiler keeps them at 60 or below without a spill (tests/test_decode_cubic_resources.py).  The
-// typed cubic warp kernels spill at 64 and are left to the allocator (72 - 91, 5 - 7 waves).
-#define CUBIC_WAVES8 __attribute__((amdgpu_waves_per_eu(8)))
-
 // the taps of output index i of an axis resampled from I to O: the triangle's, or the cubic's
 template <bool CUBIC> __device__ __forceinline__ auto axis_taps(int i, int I, int O)
 {
@@ -518,7 +464,7 @@ template <bool CUBIC> __device__ __forceinline__ auto axis_taps(int i, int I, in
     else return rs_taps(i, I, O);
 }
 
-// one frame of a resampling group: DecOut as for dec_output_fmt_batch (H x W = the region, compact)
+// one frame of a resampling group: DecOut as Plain's entry (H x W = the region, compact)
 struct DecOutRs {
     DecOut o;
     float *tmp;
@@ -615,127 +561,6 @@ __device__ __forceinline__ uint32_t resample_v_body(const float *__restrict__ tm
     return 0;
 }
 
-__global__ __launch_bounds__(kThreads) void dec_resample_h(const int32_t *__restrict__ syn, int H, int W, int oy, int ox,
-                                                           int h, int w, int ow, int maxv, int kind, int flags,
-                                                           float *__restrict__ tmp)
-{
-    resample_h_body(syn, (int64_t)H * W, W, oy, ox, h, w, ow, maxv, kind, flags, tmp);
-}
-
-template <typename T>
-__global__ __launch_bounds__(kThreads) void dec_resample_v(const float *__restrict__ tmp, int h, int oh, int ow, int flags,
-                                                           T *__restrict__ dst, DecFmtCall C)
-{
-    resample_v_body<T>(tmp, h, oh, ow, flags, dst, C);
-}
-
-template <typename T>
-__global__ __launch_bounds__(kThreads) void dec_resample_v_col(const float *__restrict__ tmp, int h, int oh, int ow,
-                                                               int flags, T *__restrict__ dst, DecFmtCall C, DecCol K)
-{
-    resample_v_body<T, kColWrite>(tmp, h, oh, ow, flags, dst, C, &K);
-}
-
-__global__ __launch_bounds__(kThreads) void dec_resample_v_stat(const float *__restrict__ tmp, int h, int oh, int ow,
-                                                                int flags, DecCol K)
-{
-    col_accumulate(K, resample_v_body<float, kColStat>(tmp, h, oh, ow, flags, nullptr, col_stat_call(), &K));
-}
-
-// a tail group: frame blockIdx.y's compact region; the grid covers the group's largest region
-__global__ __launch_bounds__(kThreads) void dec_resample_h_batch(const DecOutRs *__restrict__ Os, int ow)
-{
-    const DecOutRs R = Os[blockIdx.y];
-    const DecOut &O = R.o;
-    resample_h_body(O.syn, (int64_t)O.H * O.W, O.W, 0, 0, O.H, O.W, ow, O.maxv, O.kind, O.bps_or_flags, R.tmp);
-}
-
-template <typename T>
-__global__ __launch_bounds__(kThreads) void dec_resample_v_batch(const DecOutRs *__restrict__ Os, int oh, int ow,
-                                                                 DecFmtCall C)
-{
-    const DecOutRs R = Os[blockIdx.y];
-    resample_v_body<T>(R.tmp, R.o.H, oh, ow, R.o.bps_or_flags, reinterpret_cast<T *>(R.o.dst), C);
-}
-
-template <typename T>
-__global__ __launch_bounds__(kThreads) void dec_resample_v_col_batch(const DecOutRs *__restrict__ Os, int oh, int ow,
-                                                                     DecFmtCall C, const DecCol *__restrict__ Ks)
-{
-    const DecOutRs R = Os[blockIdx.y];
-    resample_v_body<T, kColWrite>(R.tmp, R.o.H, oh, ow, R.o.bps_or_flags, reinterpret_cast<T *>(R.o.dst), C, Ks + blockIdx.y);
-}
-
-__global__ __launch_bounds__(kThreads) void dec_resample_v_stat_batch(const DecOutRs *__restrict__ Os, int oh, int ow,
-                                                                      const DecCol *__restrict__ Ks)
-{
-    const DecCol &K = Ks[blockIdx.y];
-    if (K.contrast < 0) return;
-    const DecOutRs R = Os[blockIdx.y];
-    col_accumulate(K, resample_v_body<float, kColStat>(R.tmp, R.o.H, oh, ow, R.o.bps_or_flags, nullptr, col_stat_call(), &K));
-}
-
-// the cubic forms (CCMI_FILTER_CUBIC): the same bodies on CubTaps, argument for argument
-__global__ __launch_bounds__(kThreads) CUBIC_WAVES8 void dec_cubic_h(const int32_t *__restrict__ syn, int H, int W, int oy, int ox, int h,
-                                                        int w, int ow, int maxv, int kind, int flags,
-                                                        float *__restrict__ tmp)
-{
-    resample_h_body<true>(syn, (int64_t)H * W, W, oy, ox, h, w, ow, maxv, kind, flags, tmp);
-}
-
-template <typename T>
-__global__ __launch_bounds__(kThreads) CUBIC_WAVES8 void dec_cubic_v(const float *__restrict__ tmp, int h, int oh, int ow, int flags,
-                                                        T *__restrict__ dst, DecFmtCall C)
-{
-    resample_v_body<T, kColNone, true>(tmp, h, oh, ow, flags, dst, C);
-}
-
-template <typename T>
-__global__ __launch_bounds__(kThreads) CUBIC_WAVES8 void dec_cubic_v_col(const float *__restrict__ tmp, int h, int oh, int ow, int flags,
-                                                            T *__restrict__ dst, DecFmtCall C, DecCol K)
-{
-    resample_v_body<T, kColWrite, true>(tmp, h, oh, ow, flags, dst, C, &K);
-}
-
-__global__ __launch_bounds__(kThreads) CUBIC_WAVES8 void dec_cubic_v_stat(const float *__restrict__ tmp, int h, int oh, int ow, int flags,
-                                                             DecCol K)
-{
-    col_accumulate(K, resample_v_body<float, kColStat, true>(tmp, h, oh, ow, flags, nullptr, col_stat_call(), &K));
-}
-
-__global__ __launch_bounds__(kThreads) CUBIC_WAVES8 void dec_cubic_h_batch(const DecOutRs *__restrict__ Os, int ow)
-{
-    const DecOutRs R = Os[blockIdx.y];
-    const DecOut &O = R.o;
-    resample_h_body<true>(O.syn, (int64_t)O.H * O.W, O.W, 0, 0, O.H, O.W, ow, O.maxv, O.kind, O.bps_or_flags, R.tmp);
-}
-
-template <typename T>
-__global__ __launch_bounds__(kThreads) CUBIC_WAVES8 void dec_cubic_v_batch(const DecOutRs *__restrict__ Os, int oh, int ow, DecFmtCall C)
-{
-    const DecOutRs R = Os[blockIdx.y];
-    resample_v_body<T, kColNone, true>(R.tmp, R.o.H, oh, ow, R.o.bps_or_flags, reinterpret_cast<T *>(R.o.dst), C);
-}
-
-template <typename T>
-__global__ __launch_bounds__(kThreads) CUBIC_WAVES8 void dec_cubic_v_col_batch(const DecOutRs *__restrict__ Os, int oh, int ow,
-                                                                  DecFmtCall C, const DecCol *__restrict__ Ks)
-{
-    const DecOutRs R = Os[blockIdx.y];
-    resample_v_body<T, kColWrite, true>(R.tmp, R.o.H, oh, ow, R.o.bps_or_flags, reinterpret_cast<T *>(R.o.dst), C,
-                                        Ks + blockIdx.y);
-}
-
-__global__ __launch_bounds__(kThreads) CUBIC_WAVES8 void dec_cubic_v_stat_batch(const DecOutRs *__restrict__ Os, int oh, int ow,
-                                                                   const DecCol *__restrict__ Ks)
-{
-    const DecCol &K = Ks[blockIdx.y];
-    if (K.contrast < 0) return;
-    const DecOutRs R = Os[blockIdx.y];
-    col_accumulate(K, resample_v_body<float, kColStat, true>(R.tmp, R.o.H, oh, ow, R.o.bps_or_flags, nullptr, col_stat_call(),
-                                                             &K));
-}
-
 unsigned resample_h_blocks(int h, int ow) { return (unsigned)(((int64_t)h * ow + kThreads - 1) / kThreads); }
 
 // ------------------------------------------------------------------ warped formatted output
@@ -755,7 +580,7 @@ struct DecWarpCall { // one value per launch
     float fill[3];
 };
 
-// one frame of a warping group: DecOut as for dec_output_fmt_batch (H x W = the window, compact)
+// one frame of a warping group: DecOut as Plain's entry (H x W = the window, compact)
 struct DecOutWarp {
     DecOut o;
     float m[6];
@@ -844,55 +669,6 @@ __device__ __forceinline__ uint32_t warp_body(const int32_t *__restrict__ syn, i
     }
     if constexpr (COL != kColStat) fmt_store<T>(v, dst, C, row, d0, Wc.ow, nchw, nhwc);
     return sum;
-}
-
-// one frame (DecOut::bps_or_flags = its kFmt* flags): the per-frame tail's, A.o = the whole synthesis output
-template <typename T>
-__global__ __launch_bounds__(kThreads) void dec_warp(DecOutWarp A, DecFmtCall C, DecWarpCall Wc)
-{
-    warp_body<T>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind, A.o.bps_or_flags,
-                 reinterpret_cast<T *>(A.o.dst), C, Wc);
-}
-
-// a tail group: frame blockIdx.y's compact window
-template <typename T>
-__global__ __launch_bounds__(kThreads) void dec_warp_batch(const DecOutWarp *__restrict__ Os, DecFmtCall C, DecWarpCall Wc)
-{
-    const DecOutWarp A = Os[blockIdx.y];
-    warp_body<T>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind, A.o.bps_or_flags,
-                 reinterpret_cast<T *>(A.o.dst), C, Wc);
-}
-
-template <typename T>
-__global__ __launch_bounds__(kThreads) void dec_warp_col(DecOutWarp A, DecFmtCall C, DecWarpCall Wc, DecCol K)
-{
-    warp_body<T, kColWrite>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind, A.o.bps_or_flags,
-                            reinterpret_cast<T *>(A.o.dst), C, Wc, &K);
-}
-
-__global__ __launch_bounds__(kThreads) void dec_warp_stat(DecOutWarp A, DecWarpCall Wc, DecCol K)
-{
-    col_accumulate(K, warp_body<float, kColStat>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind,
-                                                 A.o.bps_or_flags, nullptr, col_stat_call(), Wc, &K));
-}
-
-template <typename T>
-__global__ __launch_bounds__(kThreads) void dec_warp_col_batch(const DecOutWarp *__restrict__ Os, DecFmtCall C, DecWarpCall Wc,
-                                                               const DecCol *__restrict__ Ks)
-{
-    const DecOutWarp A = Os[blockIdx.y];
-    warp_body<T, kColWrite>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind, A.o.bps_or_flags,
-                            reinterpret_cast<T *>(A.o.dst), C, Wc, Ks + blockIdx.y);
-}
-
-__global__ __launch_bounds__(kThreads) void dec_warp_stat_batch(const DecOutWarp *__restrict__ Os, DecWarpCall Wc,
-                                                                const DecCol *__restrict__ Ks)
-{
-    const DecCol &K = Ks[blockIdx.y];
-    if (K.contrast < 0) return;
-    const DecOutWarp A = Os[blockIdx.y];
-    col_accumulate(K, warp_body<float, kColStat>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind,
-                                                 A.o.bps_or_flags, nullptr, col_stat_call(), Wc, &K));
 }
 
 // ---- the cubic warp (CCMI_WARP_CUBIC: steps 3c-3d of its contract in ccmi.h)
@@ -997,53 +773,6 @@ __device__ __forceinline__ uint32_t wcubic_body(const int32_t *__restrict__ syn,
     return sum;
 }
 
-template <typename T>
-__global__ __launch_bounds__(kThreads) void dec_wcubic(DecOutWarp A, DecFmtCall C, DecWarpCall Wc)
-{
-    wcubic_body<T>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind, A.o.bps_or_flags,
-                   reinterpret_cast<T *>(A.o.dst), C, Wc);
-}
-
-template <typename T>
-__global__ __launch_bounds__(kThreads) void dec_wcubic_batch(const DecOutWarp *__restrict__ Os, DecFmtCall C, DecWarpCall Wc)
-{
-    const DecOutWarp A = Os[blockIdx.y];
-    wcubic_body<T>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind, A.o.bps_or_flags,
-                   reinterpret_cast<T *>(A.o.dst), C, Wc);
-}
-
-template <typename T>
-__global__ __launch_bounds__(kThreads) void dec_wcubic_col(DecOutWarp A, DecFmtCall C, DecWarpCall Wc, DecCol K)
-{
-    wcubic_body<T, kColWrite>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind, A.o.bps_or_flags,
-                              reinterpret_cast<T *>(A.o.dst), C, Wc, &K);
-}
-
-__global__ __launch_bounds__(kThreads) CUBIC_WAVES8 void dec_wcubic_stat(DecOutWarp A, DecWarpCall Wc, DecCol K)
-{
-    col_accumulate(K, wcubic_body<float, kColStat>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind,
-                                                   A.o.bps_or_flags, nullptr, col_stat_call(), Wc, &K));
-}
-
-template <typename T>
-__global__ __launch_bounds__(kThreads) void dec_wcubic_col_batch(const DecOutWarp *__restrict__ Os, DecFmtCall C,
-                                                                 DecWarpCall Wc, const DecCol *__restrict__ Ks)
-{
-    const DecOutWarp A = Os[blockIdx.y];
-    wcubic_body<T, kColWrite>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind, A.o.bps_or_flags,
-                              reinterpret_cast<T *>(A.o.dst), C, Wc, Ks + blockIdx.y);
-}
-
-__global__ __launch_bounds__(kThreads) CUBIC_WAVES8 void dec_wcubic_stat_batch(const DecOutWarp *__restrict__ Os, DecWarpCall Wc,
-                                                                  const DecCol *__restrict__ Ks)
-{
-    const DecCol &K = Ks[blockIdx.y];
-    if (K.contrast < 0) return;
-    const DecOutWarp A = Os[blockIdx.y];
-    col_accumulate(K, wcubic_body<float, kColStat>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind,
-                                                   A.o.bps_or_flags, nullptr, col_stat_call(), Wc, &K));
-}
-
 // ---- the projective warp (CCMI_WARP_PROJECTIVE: step 3a' of its contract in ccmi.h)
 // The same two bodies with PERSP: the position is the quotient of the two numerators by the third
 // row's denominator, two IEEE divisions per pixel; taps, padding, colour and statistics are the
@@ -1055,63 +784,6 @@ struct DecOutPersp {
     int oy, ox, fh, fw; // as DecOutWarp's
 };
 
-template <typename T, int COL, bool CUBIC>
-__device__ __forceinline__ uint32_t persp_body(const DecOutPersp &A, T *__restrict__ dst, const DecFmtCall &C,
-                                               const DecWarpCall &Wc, const DecCol *K = nullptr)
-{
-    if constexpr (CUBIC)
-        return wcubic_body<T, COL, true>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind,
-                                         A.o.bps_or_flags, dst, C, Wc, K);
-    else
-        return warp_body<T, COL, true>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind,
-                                       A.o.bps_or_flags, dst, C, Wc, K);
-}
-
-// the six forms of a projective kernel, NAME = dec_pwarp (bilinear) or dec_pwcubic, argument for
-// argument the affine kernels' with DecOutPersp for DecOutWarp
-#define PERSP_KERNELS(NAME, CUBIC)                                                                                         \
-    template <typename T> __global__ __launch_bounds__(kThreads) void NAME(DecOutPersp A, DecFmtCall C, DecWarpCall Wc)    \
-    {                                                                                                                      \
-        persp_body<T, kColNone, CUBIC>(A, reinterpret_cast<T *>(A.o.dst), C, Wc);                                          \
-    }                                                                                                                      \
-    template <typename T>                                                                                                  \
-    __global__ __launch_bounds__(kThreads) void NAME##_batch(const DecOutPersp *__restrict__ Os, DecFmtCall C,             \
-                                                             DecWarpCall Wc)                                               \
-    {                                                                                                                      \
-        const DecOutPersp A = Os[blockIdx.y];                                                                              \
-        persp_body<T, kColNone, CUBIC>(A, reinterpret_cast<T *>(A.o.dst), C, Wc);                                          \
-    }                                                                                                                      \
-    template <typename T>                                                                                                  \
-    __global__ __launch_bounds__(kThreads) void NAME##_col(DecOutPersp A, DecFmtCall C, DecWarpCall Wc, DecCol K)          \
-    {                                                                                                                      \
-        persp_body<T, kColWrite, CUBIC>(A, reinterpret_cast<T *>(A.o.dst), C, Wc, &K);                                     \
-    }                                                                                                                      \
-    template <typename T>                                                                                                  \
-    __global__ __launch_bounds__(kThreads) void NAME##_col_batch(const DecOutPersp *__restrict__ Os, DecFmtCall C,         \
-                                                                 DecWarpCall Wc, const DecCol *__restrict__ Ks)            \
-    {                                                                                                                      \
-        const DecOutPersp A = Os[blockIdx.y];                                                                              \
-        persp_body<T, kColWrite, CUBIC>(A, reinterpret_cast<T *>(A.o.dst), C, Wc, Ks + blockIdx.y);                        \
-    }                                                                                                                      \
-    __global__ __launch_bounds__(kThreads) void NAME##_stat(DecOutPersp A, DecWarpCall Wc, DecCol K)                       \
-    {                                                                                                                      \
-        col_accumulate(K, persp_body<float, kColStat, CUBIC>(A, nullptr, col_stat_call(), Wc, &K));                        \
-    }                                                                                                                      \
-    __global__ __launch_bounds__(kThreads) void NAME##_stat_batch(const DecOutPersp *__restrict__ Os,                      \
-                                                                            DecWarpCall Wc, const DecCol *__restrict__ Ks) \
-    {                                                                                                                      \
-        const DecCol &K = Ks[blockIdx.y];                                                                                  \
-        if (K.contrast < 0) return;                                                                                        \
-        const DecOutPersp A = Os[blockIdx.y];                                                                              \
-        col_accumulate(K, persp_body<float, kColStat, CUBIC>(A, nullptr, col_stat_call(), Wc, &K));                        \
-    }
-
-PERSP_KERNELS(dec_pwarp, false)
-// dec_wcubic_stat asks for 8 waves; with the division's temporaries that request spills two registers,
-// so the projective statistics pass is left to the allocator (tests/test_decode_persp_resources.py)
-PERSP_KERNELS(dec_pwcubic, true)
-#undef PERSP_KERNELS
-
 DecWarpCall warp_call(const DecFmt &f)
 {
     DecWarpCall Wc;
@@ -1119,6 +791,200 @@ DecWarpCall warp_call(const DecFmt &f)
     for (int c = 0; c < 3; ++c) Wc.fill[c] = f.fill[c];
     return Wc;
 }
+
+// ------------------------------------------------------------------ the geometries and their kernels
+// The formatted sink has seven geometries: Plain, Resize<CUBIC> and Warp<CUBIC, PERSP>.  Each is a
+// description that the kernel templates and launch_geometry below are written over:
+//   Frame, Out  what the per-frame tail passes by value: the statistics pass takes the Frame, the
+//               typed forms the Out, which is the Frame with the destination; value() makes it
+//   Entry       the frame's record in a tail group's output section; entry() makes it
+//   Table       what a group's launch passes, the section and, for a resize, the output size;
+//               table() makes it, at() is its entry blockIdx.y as an Out
+//   call()      the values per launch that follow the format in the argument list: none, or DecWarpCall
+//   body()      the geometry's body of above, from a Frame
+//   kWaves, kStatWaves  the waves per SIMD the typed forms and the statistics pass ask of the compiler, or
+//               0.  The int64 weights take the cubic resize kernels a few registers past 64; asked for 8
+//               waves the compiler keeps them at 60 or below without a spill, and so it does the cubic
+//               warp's statistics pass.  The typed cubic warp kernels spill at 64 and are left to the
+//               allocator (72 - 91, 5 - 7 waves), as is the projective cubic statistics pass, whose
+//               division's temporaries spill two registers under that request
+//               (tests/test_decode_cubic_resources.py, tests/test_decode_persp_resources.py).
+// The argument lists are laid out as the hand-written kernels' were that these replace.
+template <typename F> struct WithDst : F {
+    void *dst;
+};
+
+struct Plain {
+    struct Frame { // h x w = the region at (oy, ox) of the H x W synthesis output
+        const int32_t *syn;
+        int H, W, oy, ox, h, w, maxv, kind, flags;
+    };
+    using Out = WithDst<Frame>;
+    using Entry = DecOut; // the frame's compact H x W synthesis output (bps_or_flags = its kFmt* flags)
+    using Table = const DecOut *__restrict__;
+    static constexpr int kWaves = 0, kStatWaves = 0;
+    static constexpr bool kHPass = false;
+
+    static std::tuple<> call(const DecFmt &) { return {}; }
+    static Out value(const DecOut &o, const DecTailFrame &f)
+    {
+        const DecWindow &r = f.roi.rect;
+        return {{o.syn, o.H, o.W, r.y0, r.x0, r.h(), r.w(), o.maxv, o.kind, o.bps_or_flags}, o.dst};
+    }
+    static Entry entry(const DecOut &o, const DecTailFrame &, int, int) { return o; }
+    static Table table(const void *sec, const DecFmt &) { return static_cast<const DecOut *>(sec); }
+    static __device__ __forceinline__ Out at(Table Os)
+    {
+        const DecOut O = Os[blockIdx.y];
+        return {{O.syn, O.H, O.W, 0, 0, O.H, O.W, O.maxv, O.kind, O.bps_or_flags}, O.dst};
+    }
+    template <typename T, int COL>
+    static __device__ __forceinline__ uint32_t body(const Frame &F, T *dst, const DecFmtCall &C, const DecCol *K)
+    {
+        return output_fmt_body<T, COL>(F.syn, (int64_t)F.H * F.W, F.W, F.oy, F.ox, F.h, F.w, F.maxv, F.kind, F.flags, dst, C, K);
+    }
+};
+
+// the horizontal pass of a resize runs first, into the frame's tmp: a kernel of its own (dec_resize_h)
+struct RsHFrame { // as Plain::Frame, with the output width and tmp
+    const int32_t *syn;
+    int H, W, oy, ox, h, w, ow, maxv, kind, flags;
+    float *tmp;
+};
+
+template <bool CUBIC> struct Resize {
+    struct Frame { // tmp = [3][h][ow] of the horizontal pass
+        const float *tmp;
+        int h, oh, ow, flags;
+    };
+    using Out = WithDst<Frame>;
+    using Entry = DecOutRs;
+    struct Table {
+        const DecOutRs *__restrict__ Os;
+        int oh, ow;
+    };
+    static constexpr int kWaves = CUBIC ? 8 : 0, kStatWaves = kWaves;
+    static constexpr bool kHPass = true, kCubic = CUBIC;
+
+    static std::tuple<> call(const DecFmt &) { return {}; }
+    static Out value(const DecOut &o, const DecTailFrame &f)
+    {
+        return {{f.rs_tmp, f.roi.rect.h(), f.fmt.out_h, f.fmt.out_w, o.bps_or_flags}, o.dst};
+    }
+    static Entry entry(const DecOut &o, const DecTailFrame &f, int, int) { return {o, f.rs_tmp}; }
+    static Table table(const void *sec, const DecFmt &fmt) { return {static_cast<const DecOutRs *>(sec), fmt.out_h, fmt.out_w}; }
+    static __device__ __forceinline__ Out at(const Table &S)
+    {
+        const DecOutRs R = S.Os[blockIdx.y];
+        return {{R.tmp, R.o.H, S.oh, S.ow, R.o.bps_or_flags}, R.o.dst};
+    }
+    template <typename T, int COL>
+    static __device__ __forceinline__ uint32_t body(const Frame &F, T *dst, const DecFmtCall &C, const DecCol *K)
+    {
+        return resample_v_body<T, COL, CUBIC>(F.tmp, F.h, F.oh, F.ow, F.flags, dst, C, K);
+    }
+};
+
+template <bool CUBIC, bool PERSP> struct Warp {
+    using Frame = std::conditional_t<PERSP, DecOutPersp, DecOutWarp>; // o.dst is the destination
+    using Out = Frame;
+    using Entry = Frame;
+    using Table = const Frame *__restrict__;
+    static constexpr int kWaves = 0, kStatWaves = CUBIC && !PERSP ? 8 : 0;
+    static constexpr bool kHPass = false;
+
+    static std::tuple<DecWarpCall> call(const DecFmt &fmt) { return {warp_call(fmt)}; }
+    // the window h x w at (oy, ox) of the fh x fw frame
+    static Frame make(const DecOut &o, const DecFmt &fmt, int oy, int ox, int fh, int fw)
+    {
+        Frame A{o, {}, oy, ox, fh, fw};
+        for (int k = 0; k < (PERSP ? 9 : 6); ++k) A.m[k] = fmt.m[k];
+        return A;
+    }
+    static Out value(const DecOut &o, const DecTailFrame &f) { return make(o, f.fmt, 0, 0, o.H, o.W); } // the whole frame
+    static Entry entry(const DecOut &o, const DecTailFrame &f, int oy, int ox) { return make(o, f.fmt, oy, ox, f.syn.h, f.syn.w); }
+    static Table table(const void *sec, const DecFmt &) { return static_cast<const Frame *>(sec); }
+    static __device__ __forceinline__ Out at(Table Os) { return Os[blockIdx.y]; }
+    template <typename T, int COL>
+    static __device__ __forceinline__ uint32_t body(const Frame &A, T *dst, const DecFmtCall &C, const DecWarpCall &Wc,
+                                                    const DecCol *K)
+    {
+        if constexpr (CUBIC)
+            return wcubic_body<T, COL, PERSP>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind,
+                                              A.o.bps_or_flags, dst, C, Wc, K);
+        else
+            return warp_body<T, COL, PERSP>(A.o.syn, A.o.H, A.o.W, A.oy, A.ox, A.fh, A.fw, A.m, A.o.maxv, A.o.kind,
+                                            A.o.bps_or_flags, dst, C, Wc, K);
+    }
+};
+
+__device__ __forceinline__ void *out_dst(const DecOutWarp &A) { return A.o.dst; }
+__device__ __forceinline__ void *out_dst(const DecOutPersp &A) { return A.o.dst; }
+template <typename F> __device__ __forceinline__ void *out_dst(const WithDst<F> &A) { return A.dst; }
+
+// Where a kernel's frame and its op table come from is the template argument TABLE: its own arguments
+// (the per-frame tail) or, TABLE, entry blockIdx.y of the group's tables.
+template <typename G, bool TABLE> using OutArg = std::conditional_t<TABLE, typename G::Table, typename G::Out>;
+template <typename G, bool TABLE> using StatArg = std::conditional_t<TABLE, typename G::Table, typename G::Frame>;
+template <bool TABLE> using ColArg = std::conditional_t<TABLE, const DecCol *__restrict__, DecCol>;
+
+template <typename G, bool TABLE, typename S> __device__ __forceinline__ decltype(auto) frame_of(const S &s)
+{
+    if constexpr (TABLE) return G::at(s);
+    else return (s); // the argument itself
+}
+template <bool TABLE> __device__ __forceinline__ const DecCol *col_of(const ColArg<TABLE> &K)
+{
+    if constexpr (TABLE) return K + blockIdx.y;
+    else return &K;
+}
+
+#define WAVES_PER_EU(N) __attribute__((amdgpu_waves_per_eu(N))) // 0: no request
+
+// the typed forms: without colour ops, and with the frame's ops K.  Call = the types G::call() holds
+template <typename G, typename T, bool TABLE, typename... Call>
+__global__ __launch_bounds__(kThreads) WAVES_PER_EU(G::kWaves) void dec_fmt(OutArg<G, TABLE> S, DecFmtCall C, Call... L)
+{
+    const auto &F = frame_of<G, TABLE>(S);
+    G::template body<T, kColNone>(F, static_cast<T *>(out_dst(F)), C, L..., nullptr);
+}
+
+template <typename G, typename T, bool TABLE, typename... Call>
+__global__ __launch_bounds__(kThreads) WAVES_PER_EU(G::kWaves) void dec_fmt_col(OutArg<G, TABLE> S, DecFmtCall C, Call... L,
+                                                                                ColArg<TABLE> K)
+{
+    const auto &F = frame_of<G, TABLE>(S);
+    G::template body<T, kColWrite>(F, static_cast<T *>(out_dst(F)), C, L..., col_of<TABLE>(K));
+}
+
+// the statistics pass of a frame with a contrast op; of a group only those frames take part
+template <typename G, bool TABLE, typename... Call>
+__global__ __launch_bounds__(kThreads) WAVES_PER_EU(G::kStatWaves) void dec_fmt_stat(StatArg<G, TABLE> S, Call... L,
+                                                                                     ColArg<TABLE> K)
+{
+    const DecCol &Kf = *col_of<TABLE>(K);
+    if constexpr (TABLE)
+        if (Kf.contrast < 0) return;
+    const auto &F = frame_of<G, TABLE>(S);
+    col_accumulate(Kf, G::template body<float, kColStat>(F, (float *)nullptr, col_stat_call(), L..., &Kf));
+}
+
+// the horizontal pass of a resize, per frame and of a tail group, whose grid covers the group's largest region
+template <bool CUBIC>
+__global__ __launch_bounds__(kThreads) WAVES_PER_EU(Resize<CUBIC>::kWaves) void dec_resize_h(RsHFrame S)
+{
+    resample_h_body<CUBIC>(S.syn, (int64_t)S.H * S.W, S.W, S.oy, S.ox, S.h, S.w, S.ow, S.maxv, S.kind, S.flags, S.tmp);
+}
+
+template <bool CUBIC>
+__global__ __launch_bounds__(kThreads) WAVES_PER_EU(Resize<CUBIC>::kWaves) void dec_resize_h_batch(
+    const DecOutRs *__restrict__ Os, int ow)
+{
+    const DecOutRs R = Os[blockIdx.y];
+    const DecOut &O = R.o;
+    resample_h_body<CUBIC>(O.syn, (int64_t)O.H * O.W, O.W, 0, 0, O.H, O.W, ow, O.maxv, O.kind, O.bps_or_flags, R.tmp);
+}
+#undef WAVES_PER_EU
 
 } // namespace
 
@@ -1146,19 +1012,42 @@ static int with_sample_type(int sample, Launch &&launch)
 // dst as the kernel's element type: as(t, dst) inside a with_*_type launch
 template <typename T> static T *as(T, void *p) { return static_cast<T *>(p); }
 
-// The colour protocol of the formatted sinks, for all three geometries and both launchers.  A
-// geometry hands in its three kernel forms, each a launch on its output grid: a call without
-// colour ops runs the plain form; a call with them the statistics pass, if a frame has a contrast
-// op (stat), and then the colour form.  The plain and the colour form take the element type as T{}.
-template <typename Stat, typename Col, typename Plain>
-static int launch_fmt_forms(const DecFmt &fmt, bool stat, Stat &&stat_form, Col &&col_form, Plain &&plain_form)
+// f(G{}) for the geometry G of a formatted call
+template <typename F> static int with_geometry(const DecFmt &fmt, F &&f)
 {
-    if (!fmt.col) return with_elem_type(fmt.elem, plain_form);
-    if (stat) {
-        stat_form();
-        CCMI_HIP_CHECK(hipGetLastError());
-    }
-    return with_elem_type(fmt.elem, col_form);
+    if (fmt.warp && fmt.persp) return fmt.cubic ? f(Warp<true, true>{}) : f(Warp<false, true>{});
+    if (fmt.warp) return fmt.cubic ? f(Warp<true, false>{}) : f(Warp<false, false>{});
+    if (fmt.rs) return fmt.cubic ? f(Resize<true>{}) : f(Resize<false>{});
+    return f(Plain{});
+}
+
+// The colour protocol of the formatted sinks, for every geometry G and both launchers: src is the
+// frame by value and K its op table (the per-frame tail) or, TABLE, the group's two tables.  A call
+// without colour ops runs the plain form on the output grid; a call with them the statistics pass, if
+// a frame has a contrast op (stat), and then the colour form.  K is read only where fmt.col is set.
+template <typename G, bool TABLE>
+static int launch_fmt_forms(const DecFmt &fmt, bool stat, dim3 grid, hipStream_t s, const OutArg<G, TABLE> &src, const DecCol *K)
+{
+    const DecFmtCall C = fmt_call(fmt);
+    return std::apply(
+        [&](auto... call) {
+            auto col = [K]() -> ColArg<TABLE> {
+                if constexpr (TABLE) return K;
+                else return *K;
+            };
+            if (!fmt.col)
+                return with_elem_type(fmt.elem, [&](auto t) {
+                    launch(dec_fmt<G, decltype(t), TABLE, decltype(call)...>, grid, s, src, C, call...);
+                });
+            if (stat) {
+                launch(dec_fmt_stat<G, TABLE, decltype(call)...>, grid, s, StatArg<G, TABLE>(src), call..., col());
+                CCMI_HIP_CHECK(hipGetLastError());
+            }
+            return with_elem_type(fmt.elem, [&](auto t) {
+                launch(dec_fmt_col<G, decltype(t), TABLE, decltype(call)...>, grid, s, src, C, call..., col());
+            });
+        },
+        G::call(fmt));
 }
 
 // the output grid of a formatted sink, n frames: a resample's and a warp's cover the output size,
@@ -1190,20 +1079,6 @@ static int col_frame(const DecFmt &fmt, const DecCol *col)
 }
 
 size_t dec_resample_tmp_elems(int region_h, int out_w) { return 3 * (size_t)region_h * out_w; }
-
-static DecOutWarp make_out_warp(const DecOut &o, const DecFmt &fmt, int oy, int ox, int fh, int fw)
-{
-    DecOutWarp A{o, {}, oy, ox, fh, fw};
-    for (int k = 0; k < 6; ++k) A.m[k] = fmt.m[k];
-    return A;
-}
-
-static DecOutPersp make_out_persp(const DecOut &o, const DecFmt &fmt, int oy, int ox, int fh, int fw)
-{
-    DecOutPersp A{o, {}, oy, ox, fh, fw};
-    for (int k = 0; k < 9; ++k) A.m[k] = fmt.m[k];
-    return A;
-}
 
 static unsigned output_blocks(int h, int w) { return (unsigned)(((int64_t)h * w + kThreads - 1) / kThreads); }
 
@@ -1242,60 +1117,17 @@ int launch_dec_out_frame(const DecTailFrame &f, const int32_t *syn, int h, int w
         return ccmi_set_error(CCMI_ERR_ARG, "dec: resample without a size");
     }
     if (int rc = col_frame(fmt, f.col)) return rc;
-    const DecCol *K = f.col; // the colour forms take the frame's op table by value
-    const bool stat = fmt.col && K->contrast >= 0;
-    const dim3 grid = fmt_grid(fmt, rect.h(), rect.w(), 1);
-    const int flags = fmt_flags(fmt), rh = rect.h(), rw = rect.w(), oh = fmt.out_h, ow = fmt.out_w;
-    const DecFmtCall C = fmt_call(fmt);
-    if (fmt.warp && fmt.persp) {
-        const DecOutPersp A = make_out_persp(DecOut{syn, h, w, maxv, kind, flags, f.dst}, fmt, 0, 0, h, w);
-        const DecWarpCall Wc = warp_call(fmt);
-        if (fmt.cubic)
-            return launch_fmt_forms(
-                fmt, stat, [&] { launch(dec_pwcubic_stat, grid, s, A, Wc, *K); },
-                [&](auto t) { launch(dec_pwcubic_col<decltype(t)>, grid, s, A, C, Wc, *K); },
-                [&](auto t) { launch(dec_pwcubic<decltype(t)>, grid, s, A, C, Wc); });
-        return launch_fmt_forms(
-            fmt, stat, [&] { launch(dec_pwarp_stat, grid, s, A, Wc, *K); },
-            [&](auto t) { launch(dec_pwarp_col<decltype(t)>, grid, s, A, C, Wc, *K); },
-            [&](auto t) { launch(dec_pwarp<decltype(t)>, grid, s, A, C, Wc); });
-    }
-    if (fmt.warp) {
-        const DecOutWarp A = make_out_warp(DecOut{syn, h, w, maxv, kind, flags, f.dst}, fmt, 0, 0, h, w);
-        const DecWarpCall Wc = warp_call(fmt);
-        if (fmt.cubic)
-            return launch_fmt_forms(
-                fmt, stat, [&] { launch(dec_wcubic_stat, grid, s, A, Wc, *K); },
-                [&](auto t) { launch(dec_wcubic_col<decltype(t)>, grid, s, A, C, Wc, *K); },
-                [&](auto t) { launch(dec_wcubic<decltype(t)>, grid, s, A, C, Wc); });
-        return launch_fmt_forms(
-            fmt, stat, [&] { launch(dec_warp_stat, grid, s, A, Wc, *K); },
-            [&](auto t) { launch(dec_warp_col<decltype(t)>, grid, s, A, C, Wc, *K); },
-            [&](auto t) { launch(dec_warp<decltype(t)>, grid, s, A, C, Wc); });
-    }
-    if (fmt.rs) { // rs_tmp holds the horizontal pass
-        float *tmp = f.rs_tmp;
-        launch(fmt.cubic ? dec_cubic_h : dec_resample_h, dim3(resample_h_blocks(rh, ow)), s, syn, h, w, rect.y0, rect.x0, rh, rw,
-               ow, maxv, kind, flags, tmp);
-        CCMI_HIP_CHECK(hipGetLastError());
-        if (fmt.cubic)
-            return launch_fmt_forms(
-                fmt, stat, [&] { launch(dec_cubic_v_stat, grid, s, tmp, rh, oh, ow, flags, *K); },
-                [&](auto t) { launch(dec_cubic_v_col<decltype(t)>, grid, s, tmp, rh, oh, ow, flags, as(t, dst), C, *K); },
-                [&](auto t) { launch(dec_cubic_v<decltype(t)>, grid, s, tmp, rh, oh, ow, flags, as(t, dst), C); });
-        return launch_fmt_forms(
-            fmt, stat, [&] { launch(dec_resample_v_stat, grid, s, tmp, rh, oh, ow, flags, *K); },
-            [&](auto t) { launch(dec_resample_v_col<decltype(t)>, grid, s, tmp, rh, oh, ow, flags, as(t, dst), C, *K); },
-            [&](auto t) { launch(dec_resample_v<decltype(t)>, grid, s, tmp, rh, oh, ow, flags, as(t, dst), C); });
-    }
-    return launch_fmt_forms(
-        fmt, stat, [&] { launch(dec_output_fmt_stat, grid, s, syn, h, w, rect.y0, rect.x0, rh, rw, maxv, kind, flags, *K); },
-        [&](auto t) {
-            launch(dec_output_fmt_col<decltype(t)>, grid, s, syn, h, w, rect.y0, rect.x0, rh, rw, maxv, kind, flags, as(t, dst), C, *K);
-        },
-        [&](auto t) {
-            launch(dec_output_fmt<decltype(t)>, grid, s, syn, h, w, rect.y0, rect.x0, rh, rw, maxv, kind, flags, as(t, dst), C);
-        });
+    const bool stat = fmt.col && f.col->contrast >= 0; // the colour forms take the frame's op table by value
+    const DecOut o{syn, h, w, maxv, kind, fmt_flags(fmt), f.dst};
+    return with_geometry(fmt, [&](auto g) {
+        using G = decltype(g);
+        if constexpr (G::kHPass) { // into rs_tmp
+            launch(dec_resize_h<G::kCubic>, dim3(resample_h_blocks(rect.h(), fmt.out_w)), s,
+                   RsHFrame{syn, h, w, rect.y0, rect.x0, rect.h(), rect.w(), fmt.out_w, maxv, kind, o.bps_or_flags, f.rs_tmp});
+            CCMI_HIP_CHECK(hipGetLastError());
+        }
+        return launch_fmt_forms<G, false>(fmt, stat, fmt_grid(fmt, rect.h(), rect.w(), 1), s, G::value(o, f), f.col);
+    });
 }
 
 // ------------------------------------------------------------------ a tail group's output section
@@ -1317,10 +1149,11 @@ void dec_out_fill(void *out_sec, void *col_sec, int i, const DecTailFrame &f, in
 {
     const DecOut o{f.syn.out, h, w, (1 << f.bitdepth) - 1, f.kind, f.fmt.on ? fmt_flags(f.fmt) : f.bitdepth <= 8 ? 1 : 2,
                    f.dst};
-    if (f.fmt.warp && f.fmt.persp) static_cast<DecOutPersp *>(out_sec)[i] = make_out_persp(o, f.fmt, oy, ox, f.syn.h, f.syn.w);
-    else if (f.fmt.warp) static_cast<DecOutWarp *>(out_sec)[i] = make_out_warp(o, f.fmt, oy, ox, f.syn.h, f.syn.w);
-    else if (f.fmt.rs) static_cast<DecOutRs *>(out_sec)[i] = DecOutRs{o, f.rs_tmp};
-    else static_cast<DecOut *>(out_sec)[i] = o;
+    with_geometry(f.fmt, [&](auto g) {
+        using G = decltype(g);
+        static_cast<typename G::Entry *>(out_sec)[i] = G::entry(o, f, oy, ox);
+        return 0;
+    });
     if (f.fmt.col) static_cast<DecCol *>(col_sec)[i] = *f.col;
 }
 
@@ -1338,55 +1171,16 @@ int launch_dec_out_group(const DecTailFrame &f0, int h, int w, int n, const void
         const dim3 grid(output_tensor_blocks(h, w, f0.kind), n); // one kind per group
         return with_sample_type(f0.sample, [&](auto t) { launch(dec_output_tensor_batch<decltype(t)>, grid, s, oo); });
     }
-    // the format but its per-frame flags (in the table) is the call's
-    const dim3 grid = fmt_grid(fmt, h, w, n);
-    const DecFmtCall C = fmt_call(fmt);
-    if (fmt.warp && fmt.persp) { // the section holds DecOutPersp
-        const DecOutPersp *pp = static_cast<const DecOutPersp *>(out_sec);
-        const DecWarpCall Wc = warp_call(fmt);
-        if (fmt.cubic)
-            return launch_fmt_forms(
-                fmt, stat, [&] { launch(dec_pwcubic_stat_batch, grid, s, pp, Wc, kk); },
-                [&](auto t) { launch(dec_pwcubic_col_batch<decltype(t)>, grid, s, pp, C, Wc, kk); },
-                [&](auto t) { launch(dec_pwcubic_batch<decltype(t)>, grid, s, pp, C, Wc); });
-        return launch_fmt_forms(
-            fmt, stat, [&] { launch(dec_pwarp_stat_batch, grid, s, pp, Wc, kk); },
-            [&](auto t) { launch(dec_pwarp_col_batch<decltype(t)>, grid, s, pp, C, Wc, kk); },
-            [&](auto t) { launch(dec_pwarp_batch<decltype(t)>, grid, s, pp, C, Wc); });
-    }
-    if (fmt.warp) { // the section holds DecOutWarp
-        const DecOutWarp *ww = static_cast<const DecOutWarp *>(out_sec);
-        const DecWarpCall Wc = warp_call(fmt);
-        if (fmt.cubic)
-            return launch_fmt_forms(
-                fmt, stat, [&] { launch(dec_wcubic_stat_batch, grid, s, ww, Wc, kk); },
-                [&](auto t) { launch(dec_wcubic_col_batch<decltype(t)>, grid, s, ww, C, Wc, kk); },
-                [&](auto t) { launch(dec_wcubic_batch<decltype(t)>, grid, s, ww, C, Wc); });
-        return launch_fmt_forms(
-            fmt, stat, [&] { launch(dec_warp_stat_batch, grid, s, ww, Wc, kk); },
-            [&](auto t) { launch(dec_warp_col_batch<decltype(t)>, grid, s, ww, C, Wc, kk); },
-            [&](auto t) { launch(dec_warp_batch<decltype(t)>, grid, s, ww, C, Wc); });
-    }
-    if (fmt.rs) { // the section holds DecOutRs; h = the group's tallest region
-        const DecOutRs *rr = static_cast<const DecOutRs *>(out_sec);
-        const int oh = fmt.out_h, ow = fmt.out_w;
-        launch(fmt.cubic ? dec_cubic_h_batch : dec_resample_h_batch, dim3(resample_h_blocks(h, ow), n), s, rr, ow);
-        CCMI_HIP_CHECK(hipGetLastError());
-        if (fmt.cubic)
-            return launch_fmt_forms(
-                fmt, stat, [&] { launch(dec_cubic_v_stat_batch, grid, s, rr, oh, ow, kk); },
-                [&](auto t) { launch(dec_cubic_v_col_batch<decltype(t)>, grid, s, rr, oh, ow, C, kk); },
-                [&](auto t) { launch(dec_cubic_v_batch<decltype(t)>, grid, s, rr, oh, ow, C); });
-        return launch_fmt_forms(
-            fmt, stat, [&] { launch(dec_resample_v_stat_batch, grid, s, rr, oh, ow, kk); },
-            [&](auto t) { launch(dec_resample_v_col_batch<decltype(t)>, grid, s, rr, oh, ow, C, kk); },
-            [&](auto t) { launch(dec_resample_v_batch<decltype(t)>, grid, s, rr, oh, ow, C); });
-    }
-    const DecOut *oo = static_cast<const DecOut *>(out_sec);
-    return launch_fmt_forms(
-        fmt, stat, [&] { launch(dec_output_fmt_stat_batch, grid, s, oo, kk); },
-        [&](auto t) { launch(dec_output_fmt_col_batch<decltype(t)>, grid, s, oo, C, kk); },
-        [&](auto t) { launch(dec_output_fmt_batch<decltype(t)>, grid, s, oo, C); });
+    // the format but its per-frame flags (in the table) is the call's; the section holds G::Entry
+    return with_geometry(fmt, [&](auto g) {
+        using G = decltype(g);
+        if constexpr (G::kHPass) { // h = the group's tallest region
+            launch(dec_resize_h_batch<G::kCubic>, dim3(resample_h_blocks(h, fmt.out_w), n), s,
+                   static_cast<const DecOutRs *>(out_sec), fmt.out_w);
+            CCMI_HIP_CHECK(hipGetLastError());
+        }
+        return launch_fmt_forms<G, true>(fmt, stat, fmt_grid(fmt, h, w, n), s, G::table(out_sec, fmt), kk);
+    });
 }
 
 } // namespace ccmi

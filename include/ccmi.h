@@ -689,8 +689,8 @@ int ccmi_latents_render_fmt(const ccmi_latents *h, const int *index /* [m] or NU
  * path does not clamp either).  With CCMI_FILTER_CLAMP, r' = min(max(r', 0), 1) after step 3c and
  * before the colour ops (step 3z) -- what a uint8 / PIL pipeline gives.  The flag is valid with
  * CCMI_FILTER_CUBIC only.  The workspace formula is unchanged.
- * Kernels (dec_out.hip): dec_cubic_h, dec_cubic_v<T> and their _col / _stat / _batch forms, the
- * weights recomputed per thread by Horner in int64. */
+ * Kernels (dec_out.hip): dec_resize_h<true>, dec_resize_h_batch<true> and the geometry Resize<true> of
+ * dec_fmt, dec_fmt_col and dec_fmt_stat, the weights recomputed per thread by Horner in int64. */
 enum { CCMI_FILTER_TRIANGLE = 0, CCMI_FILTER_CUBIC = 2, CCMI_FILTER_CLAMP = 0x100 };
 typedef struct ccmi_resample { int out_w, out_h, filter; } ccmi_resample;
 int ccmi_decode_batch_dev_rs_plan(const uint8_t *const *streams, const size_t *lens, int n,
@@ -774,7 +774,7 @@ int ccmi_decode_last_tail_groups(int *batched, int *per_frame);
  * 0), 1) before the colour ops -- on r' whatever its taps were, fill included.
  * window[j] grows by one tap on each side: columns floor(min xs - 0.5) - 2 .. floor(max xs - 0.5)
  * + 3 and rows alike, then the same clamp into the frame and the same even-ing.
- * Kernels (dec_out.hip): dec_wcubic<T> and its _col / _stat / _batch forms.
+ * Kernels (dec_out.hip): the geometry Warp<true, false> of dec_fmt, dec_fmt_col and dec_fmt_stat.
  *
  * CCMI_WARP_PROJECTIVE (0x800; 0x400 stays an unknown pad), or'ed into pad: the frame's matrix is a
  * 3 x 3 homography, matrix is host [n][9], row-major m00 .. m22 of frame j, and the position is the
@@ -826,7 +826,8 @@ int ccmi_decode_last_tail_groups(int *batched, int *per_frame);
  * each end clamped into the frame, never empty, even-ed for 420; the one-pixel growth is what E <= 7/8
  * pays for.  A flagged matrix with last row 0 0 1 gives the window of its 6-entry form.  Frames of
  * one architecture share one batched tail group whatever their matrices.
- * Kernels (dec_out.hip): dec_pwarp<T>, dec_pwcubic<T> and their _col / _stat / _batch forms. */
+ * Kernels (dec_out.hip): the geometries Warp<false, true> and Warp<true, true> of dec_fmt, dec_fmt_col
+ * and dec_fmt_stat. */
 enum {
     CCMI_PAD_FILL = 0,
     CCMI_PAD_EDGE = 1,
