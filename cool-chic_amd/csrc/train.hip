@@ -2872,10 +2872,12 @@ __global__ void t_adam(const float *__restrict__ G, float *__restrict__ lat, flo
     *p -= lr_bc1 * mm / denom;
 }
 
+// one thread per frame, ceil(B / 64) blocks of 64 (one block of B threads is no valid launch
+// past B = 1024)
 __global__ void t_finish(const float *__restrict__ acc4, const float *__restrict__ rslots, const float *__restrict__ mslots,
                          float inv_total, float lam_px, float *__restrict__ out, int B)
 {
-    const int b = threadIdx.x;
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b < B) finish_row(acc4, rslots, mslots, inv_total, lam_px, out, b);
 }
 
@@ -3406,7 +3408,7 @@ extern "C" int ccmi_train_step(const ccmi_train_args *a, void *stream)
                 hipLaunchKernelGGL(t_loss, dim3(sum_blocks(npx, kLossPx), B), dim3(kT), 0, s, F(pl.z[g.n_sp]), g,
                                    a->target, a->target_stride, a->yuv420, graw, acc4);
             const float total = a->yuv420 ? (float)(npx + 2 * (int64_t)(g.H / 2) * (g.W / 2)) : (float)(3 * npx);
-            hipLaunchKernelGGL(t_finish, dim3(1), dim3(std::max(64, B)), 0, s, acc4, F(pl.rslots), F(pl.mslots), 1.f / total, lam_px, a->loss_out, B);
+            hipLaunchKernelGGL(t_finish, dim3((unsigned)ccmi_div_up(B, 64)), dim3(64), 0, s, acc4, F(pl.rslots), F(pl.mslots), 1.f / total, lam_px, a->loss_out, B);
         }
         CCMI_HIP_CHECK(hipGetLastError());
         return CCMI_OK;
@@ -3538,7 +3540,7 @@ extern "C" int ccmi_train_step(const ccmi_train_args *a, void *stream)
                        GS, acc4);
     const float total = a->yuv420 ? (float)(npx + 2 * (int64_t)(g.H / 2) * (g.W / 2)) : (float)(3 * npx);
     if (a->loss_out && !a->update)
-        hipLaunchKernelGGL(t_finish, dim3(1), dim3(std::max(64, B)), 0, s, acc4, F(pl.rslots), F(pl.mslots), 1.f / total, lam_px, a->loss_out, B);
+        hipLaunchKernelGGL(t_finish, dim3((unsigned)ccmi_div_up(B, 64)), dim3(64), 0, s, acc4, F(pl.rslots), F(pl.mslots), 1.f / total, lam_px, a->loss_out, B);
     if (a->update) {
         const double bc1 = 1.0 - std::pow((double)a->beta1, a->step), bc2 = 1.0 - std::pow((double)a->beta2, a->step);
         AdamArgs A{(float)(a->lr / bc1), (float)(1.0 / std::sqrt(bc2)), a->beta1, a->beta2, a->eps, a->clip, g.N,

@@ -55,15 +55,18 @@ def quantize(x, qtype: str, t: float, noise=None):
 
 
 class TrainState:
-    """Trainable tensors of one frame, in the reference's parameter order."""
+    """Trainable tensors of one frame, in the reference's parameter order.  dtype (tests only):
+    every tensor cast to it, so the dtype-generic code below runs as a float64 reference of
+    itself; None keeps the latents float32 and the parameters as they come."""
 
-    def __init__(self, mp: fo.ModelParams, latents):
+    def __init__(self, mp: fo.ModelParams, latents, dtype=None):
         self.mp = mp
-        self.lat = [x.clone().float().requires_grad_(True) for x in latents]
-        self.arm = [(W.clone().requires_grad_(True), b.clone().requires_grad_(True)) for W, b in mp.arm]
-        self.ups = [h.clone().requires_grad_(True) for h in mp.ups_half]
-        self.pre = [h.clone().requires_grad_(True) for h in mp.pre_half]
-        self.syn = [(W.clone().requires_grad_(True), b.clone().requires_grad_(True)) for W, b in mp.syn]
+        c = (lambda x: x.clone()) if dtype is None else (lambda x: x.clone().to(dtype))
+        self.lat = [(x.clone().float() if dtype is None else c(x)).requires_grad_(True) for x in latents]
+        self.arm = [(c(W).requires_grad_(True), c(b).requires_grad_(True)) for W, b in mp.arm]
+        self.ups = [c(h).requires_grad_(True) for h in mp.ups_half]
+        self.pre = [c(h).requires_grad_(True) for h in mp.pre_half]
+        self.syn = [(c(W).requires_grad_(True), c(b).requires_grad_(True)) for W, b in mp.syn]
 
     def params(self):
         out = list(self.lat)
@@ -79,7 +82,7 @@ def loss(st: TrainState, target, qtype, t, lmbda, yuv420, noise=None, keep=None)
     """Training forward + loss.  target: [3,H,W] (444) or dict(y, u, v).  Returns
     (loss, mse, rate_bit_sum).  keep (a dict, tests only): receives the ARM outputs mu and
     log_scale with their gradients retained, so a test can see the per-latent terms a
-    bias gradient sums."""
+    bias gradient sums, and the quantised latents q and the scale (detached)."""
     mp = st.mp
     flat = torch.cat([x.reshape(-1) for x in st.lat]) * mp.gain
     q = quantize(flat, qtype, t, noise)
@@ -92,7 +95,7 @@ def loss(st: TrainState, target, qtype, t, lmbda, yuv420, noise=None, keep=None)
     if keep is not None:
         mu.retain_grad()
         log_scale.retain_grad()
-        keep.update(mu=mu, log_scale=log_scale)
+        keep.update(mu=mu, log_scale=log_scale, scale=scale.detach(), q=q.detach())
     r = fo.rate(q, mu, scale)
     ups = fo.upsampling(grids, [fo.sym_kernel(h, mp.ups_k) for h in st.ups],
                         [fo.sym_kernel(h, mp.pre_k) for h in st.pre])
