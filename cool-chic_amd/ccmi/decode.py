@@ -57,6 +57,10 @@ _PROTOS = {
     "ccmi_decode_batch_dev_tone": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _Z, _P],
     "ccmi_latents_render_tone_plan": [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "ccmi_latents_render_tone": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _Z, _P],
+    "ccmi_decode_batch_dev_mix_plan": [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "ccmi_decode_batch_dev_mix": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _Z, _P],
+    "ccmi_latents_render_mix_plan": [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "ccmi_latents_render_mix": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _Z, _P],
     "ccmi_latents_plan": [_P, _P, _I, _I, _P, _P, _P],
     "ccmi_latents_decode": [_P, _P, _I, _I, _P, _Z, _P, _Z, _P, _P],
     "ccmi_latents_free": [_P],
@@ -933,6 +937,190 @@ def trivial_augment_wide(n: int, num_magnitude_bins: int = 31, generator=None, s
     return _ra_draw(n, 1, 0, int(num_magnitude_bins), generator, size, base, True)
 
 
+MIX_MAX_RECTS = 4  # CCMI_MIX_MAX_RECTS
+
+
+class EraseRect(C.Structure):
+    """ccmi_erase_rect: one erase rectangle in stored coordinates, its value per channel and its sigma."""
+    _fields_ = [("x", C.c_int), ("y", C.c_int), ("w", C.c_int), ("h", C.c_int), ("v", C.c_float * 3), ("sigma", C.c_float)]
+
+
+class Mix(C.Structure):
+    """ccmi_mix: per-frame rectangle counts, the flat rectangles, seeds, partners, blend weights and boxes."""
+    _fields_ = [("count", C.c_void_p), ("rects", C.c_void_p), ("seed", C.c_void_p), ("partner", C.c_void_p),
+                ("lam", C.c_void_p), ("box", C.c_void_p)]
+
+
+def _mix(erase, erase_seed, mix, n):
+    """erase= / erase_seed= / mix= of a *_model call -> (ccmi_mix, what it points to), or (None, None) with
+    all three None.  erase: one entry per frame, None or a list of at most 4 (x, y, w, h, value[, sigma]) in
+    stored coordinates (after mirror), value one float or three, in the normalised units; erase_seed: one
+    int for every frame or one per frame (the noise of rectangles with sigma > 0); mix: one entry per
+    frame, None, (partner, lam) or (partner, (x, y, w, h)).  The library checks the values; the shapes
+    are checked here."""
+    import numpy as np
+    if erase is None and mix is None:
+        return None, None
+    counts = np.zeros(n, dtype=np.int32)
+    rects = []
+    if erase is not None:
+        entries = list(erase)
+        if len(entries) != n:
+            raise ValueError(f"model output: erase takes one entry per frame ({n}), got {len(entries)}")
+        for j, e in enumerate(entries):
+            e = [] if e is None else list(e)
+            if len(e) > MIX_MAX_RECTS:
+                raise ValueError(f"model output: frame {j}: {len(e)} erase rectangles (at most {MIX_MAX_RECTS})")
+            counts[j] = len(e)
+            for r in e:
+                if len(r) not in (5, 6):
+                    raise ValueError("model output: an erase rectangle is (x, y, w, h, value[, sigma])")
+                v = [float(t) for t in r[4]] if hasattr(r[4], "__len__") else [float(r[4])] * 3
+                if len(v) != 3:
+                    raise ValueError("model output: an erase value is one float or one per channel")
+                rects.append((int(r[0]), int(r[1]), int(r[2]), int(r[3]), v, float(r[5]) if len(r) == 6 else 0.0))
+    flat = (EraseRect * max(len(rects), 1))()
+    for k, (x, y, w, h, v, sigma) in enumerate(rects):
+        flat[k] = EraseRect(x, y, w, h, (C.c_float * 3)(*v), sigma)
+    if erase_seed is None:
+        seeds = np.zeros(n, dtype=np.uint64)
+    elif hasattr(erase_seed, "__len__"):
+        if len(erase_seed) != n:
+            raise ValueError(f"model output: erase_seed takes one int, or one per frame ({n}), got {len(erase_seed)}")
+        seeds = np.array([int(v) & 0xFFFFFFFFFFFFFFFF for v in erase_seed], dtype=np.uint64)
+    else:
+        seeds = np.full(n, int(erase_seed) & 0xFFFFFFFFFFFFFFFF, dtype=np.uint64)
+    partner = np.full(n, -1, dtype=np.int32)
+    lam = np.ones(n, dtype=np.float32)
+    box = (Rect * n)()
+    if mix is not None:
+        entries = list(mix)
+        if len(entries) != n:
+            raise ValueError(f"model output: mix takes one entry per frame ({n}), got {len(entries)}")
+        for j, e in enumerate(entries):
+            if e is None:
+                continue
+            if len(e) != 2:
+                raise ValueError("model output: a mix entry is None, (partner, lam) or (partner, (x, y, w, h))")
+            partner[j] = int(e[0])
+            if hasattr(e[1], "__len__"):
+                if len(e[1]) != 4:
+                    raise ValueError("model output: a mix box is (x, y, w, h)")
+                box[j] = Rect(*[int(t) for t in e[1]])
+            else:
+                lam[j] = np.float32(e[1])
+    mx = Mix(count=counts.ctypes.data, rects=C.addressof(flat), seed=seeds.ctypes.data, partner=partner.ctypes.data,
+             lam=lam.ctypes.data, box=C.addressof(box))
+    return mx, (counts, flat, seeds, partner, lam, box)
+
+
+def random_erasing(n: int, size, p: float = 0.5, scale=(0.02, 0.33), ratio=(0.3, 3.3), value=0.0, count: int = 1,
+                   generator=None):
+    """n draws of torchvision's RandomErasing(p, scale, ratio, value) for frames stored at size = (H, W):
+    (erase, seeds) for erase= and erase_seed= of the *_model calls.  Per frame, with probability p, `count`
+    rectangles (timm's max_count; torchvision has 1), each by RandomErasing.get_params: up to 10 attempts of
+    area = H W U[scale], aspect = exp(U[log ratio[0], log ratio[1]]), h = round(sqrt(area aspect)),
+    w = round(sqrt(area / aspect)), accepted when h < H and w < W (and neither is 0), then the origin
+    uniform over the integers y in [0, H - h], x in [0, W - w]; ten rejections give no rectangle.
+    value: one float or three, in the normalised units (sigma 0), or "pixel": value 0, sigma 1 (a unit
+    Gaussian per element, as torchvision's value="random" and timm's mode="pixel") with one 63-bit seed
+    per frame drawn from the generator; seeds is None otherwise.  A frame consumes a fixed number of
+    draws (float64), so frame j's rectangles do not depend on what the frames before it were given.
+    generator: a torch.Generator (CPU); the same seed gives the same lists."""
+    import math
+    import torch
+    H, W = int(size[0]), int(size[1])
+    if not (0.0 <= p <= 1.0) or not 0 < scale[0] <= scale[1] or not 0 < ratio[0] <= ratio[1]:
+        raise ValueError(f"random_erasing: p {p}, scale {scale}, ratio {ratio}")
+    if not 1 <= int(count) <= MIX_MAX_RECTS:
+        raise ValueError(f"random_erasing: count {count} (1 .. {MIX_MAX_RECTS})")
+    pixel = isinstance(value, str)
+    if pixel and value != "pixel":
+        raise ValueError(f"random_erasing: value {value!r} (a float, three floats or 'pixel')")
+    v, sigma = (0.0, 1.0) if pixel else (value, 0.0)
+    lr0, lr1 = math.log(ratio[0]), math.log(ratio[1])
+    erase = []
+    for _ in range(n):
+        u = torch.rand(1 + 40 * int(count), generator=generator, dtype=torch.float64).tolist()
+        rects = []
+        for t in range(int(count)):
+            for a in range(10):
+                ua, ur, uy, ux = u[1 + 40 * t + 4 * a: 5 + 40 * t + 4 * a]
+                area = H * W * (scale[0] + (scale[1] - scale[0]) * ua)
+                aspect = math.exp(lr0 + (lr1 - lr0) * ur)
+                h, w = int(round(math.sqrt(area * aspect))), int(round(math.sqrt(area / aspect)))
+                if not (0 < h < H and 0 < w < W):
+                    continue
+                y, x = min(int(uy * (H - h + 1)), H - h), min(int(ux * (W - w + 1)), W - w)
+                rects.append((x, y, w, h, v, sigma))
+                break
+        erase.append(rects if u[0] < p and rects else None)
+    seeds = None
+    if pixel:
+        seeds = torch.randint(0, 2 ** 63 - 1, (n,), generator=generator, dtype=torch.int64).tolist()
+    return erase, seeds
+
+
+def mixup_cutmix(n: int, size, mixup_alpha: float = 0.8, cutmix_alpha: float = 1.0, prob: float = 1.0,
+                 switch_prob: float = 0.5, pairing: str = "roll", per_frame: bool = False, generator=None):
+    """n draws of MixUp / CutMix as timm's Mixup(mixup_alpha, cutmix_alpha, prob, switch_prob) makes them for
+    frames stored at size = (H, W): (mix, label_lam) for mix= of the *_model calls.  One decision for the
+    whole call, or per_frame=True one per frame (timm's mode="elem"): with probability prob the frame mixes;
+    CutMix with probability switch_prob when both alphas are positive (else whichever alpha is positive);
+    lam ~ Beta(a, a) as G1 / (G1 + G2) from torch._standard_gamma (float64).  pairing="roll": frame j's
+    partner is frame j - 1 mod n (batch.roll(1, 0), torchvision v2's); "flip": frame n - 1 - j (timm's).
+    MixUp: the entry is (partner, lam) and label_lam[j] = lam as float32.  CutMix, torchvision v2's box:
+    centre (cx, cy) uniform over the integers [0, W) x [0, H), half sides int(0.5 sqrt(1 - lam) W) and
+    int(0.5 sqrt(1 - lam) H), clamped to the frame; the entry is (partner, (x, y, w, h)) and
+    label_lam[j] = 1 - w h / (H W); an empty box gives None (no mix) and label_lam 1, as does a frame that
+    does not mix.  The caller's target is label_lam[j] y_j + (1 - label_lam[j]) y_partner.  Every decision
+    consumes a fixed number of draws.  generator: a torch.Generator (CPU); the same seed gives the same
+    lists."""
+    import math
+    import numpy as np
+    import torch
+    H, W = int(size[0]), int(size[1])
+    if pairing not in ("roll", "flip"):
+        raise ValueError(f"mixup_cutmix: pairing {pairing!r} ('roll' or 'flip')")
+    if mixup_alpha < 0 or cutmix_alpha < 0 or not (0.0 <= prob <= 1.0) or not (0.0 <= switch_prob <= 1.0):
+        raise ValueError(f"mixup_cutmix: alphas {mixup_alpha}, {cutmix_alpha}, prob {prob}, switch_prob {switch_prob}")
+    draws = n if per_frame else 1
+    u = torch.rand(draws, 4, generator=generator, dtype=torch.float64).tolist()
+    alphas = torch.tensor([max(mixup_alpha, 1e-30), max(mixup_alpha, 1e-30), max(cutmix_alpha, 1e-30),
+                           max(cutmix_alpha, 1e-30)], dtype=torch.float64).repeat(draws, 1)
+    g = torch._standard_gamma(alphas, generator=generator).tolist()
+    decisions = []
+    for k in range(draws):
+        if not (u[k][0] < prob) or (mixup_alpha <= 0 and cutmix_alpha <= 0):
+            decisions.append(None)
+            continue
+        cut = cutmix_alpha > 0 and (mixup_alpha <= 0 or u[k][1] < switch_prob)
+        g1, g2 = (g[k][2], g[k][3]) if cut else (g[k][0], g[k][1])
+        lam = g1 / (g1 + g2) if g1 + g2 > 0 else 0.5
+        if not cut:
+            lam = float(np.float32(lam))
+            decisions.append((lam, lam))
+            continue
+        cx, cy = min(int(u[k][2] * W), W - 1), min(int(u[k][3] * H), H - 1)
+        r = 0.5 * math.sqrt(1.0 - lam)
+        hw, hh = int(r * W), int(r * H)
+        x1, y1, x2, y2 = max(cx - hw, 0), max(cy - hh, 0), min(cx + hw, W), min(cy + hh, H)
+        if x2 <= x1 or y2 <= y1:
+            decisions.append(None)
+            continue
+        decisions.append(((x1, y1, x2 - x1, y2 - y1), 1.0 - (x2 - x1) * (y2 - y1) / float(H * W)))
+    mix, label_lam = [], []
+    for j in range(n):
+        d = decisions[j if per_frame else 0]
+        if d is None:
+            mix.append(None)
+            label_lam.append(1.0)
+            continue
+        mix.append(((j - 1) % n if pairing == "roll" else n - 1 - j, d[0]))
+        label_lam.append(d[1])
+    return mix, label_lam
+
+
 def last_tail_groups() -> tuple:
     """(batched tail groups, per-frame tails) this thread's last decode or render call launched
     (ccmi_decode_last_tail_groups): frames that share a group share one launch per tail stage."""
@@ -1011,16 +1199,22 @@ def _model_outs(geom, fmt, dtype, channels_last, out, dev):
 
 
 def _plan_model(plan, head, n, rects, fmt, rs, output_bitdepth, output_chroma_format, warp=None, info=None,
-                window=None, col=None, flt=None, tone=None):
+                window=None, col=None, flt=None, tone=None, mx=None):
     """(ccmi_frame_geom array, workspace bytes) of a formatted call: plan is the source's *_rs_plan
     entry point (rs None: exactly the *_fmt_plan call), head its first two arguments.  With warp
     (a ccmi_warp) plan is the *_warp_plan entry point, which takes no regions; info / window: its
     optional per-frame outputs.  With col (a ccmi_colour) plan is the *_col_plan entry point, which
     takes all of them; with flt (a ccmi_filter) the *_flt_plan entry point, which takes col (or None)
-    and flt; with tone (a ccmi_tone) the *_tone_plan entry point, which takes col, tone and flt (or None)."""
+    and flt; with tone (a ccmi_tone) the *_tone_plan entry point, which takes col, tone and flt (or None);
+    with mx (a ccmi_mix) the *_mix_plan entry point, which takes col, tone, flt (or None) and mx."""
     geom, need = (FrameGeom * n)(), C.c_size_t(0)
     probe = TensorFmt.from_buffer_copy(fmt)  # planar strides: the geometry does not depend on them
-    if tone is not None:
+    if mx is not None:
+        check(plan(*head, n, None if warp is not None else rects, output_bitdepth, output_chroma_format, C.byref(probe),
+                   None if warp is not None else rs, None if warp is None else C.byref(warp),
+                   None if col is None else C.byref(col), None if tone is None else C.byref(tone),
+                   None if flt is None else C.byref(flt), C.byref(mx), geom, info, window, C.byref(need)))
+    elif tone is not None:
         check(plan(*head, n, None if warp is not None else rects, output_bitdepth, output_chroma_format, C.byref(probe),
                    None if warp is not None else rs, None if warp is None else C.byref(warp),
                    None if col is None else C.byref(col), C.byref(tone), None if flt is None else C.byref(flt), geom, info,
@@ -1043,22 +1237,28 @@ def _plan_model(plan, head, n, rects, fmt, rs, output_bitdepth, output_chroma_fo
 
 def _run_model(plan, run, head, n, rects, dev, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth,
                output_chroma_format, workspace, stream_handle, size, warp=None, col=None, flt=None, tone=None,
-               interp=(FILTER_TRIANGLE, 0)):
+               interp=(FILTER_TRIANGLE, 0), mx=None):
     """The body of decode_batch_model and LatentStore.render_model: plan / run are the source's
     *_rs_plan / *_rs entry points, or with warp (a ccmi_warp, which carries the size) its
     *_warp_plan / *_warp ones, or with col (a ccmi_colour) its *_col_plan / *_col ones, or with flt (a
-    ccmi_filter) its *_flt_plan / *_flt ones, or with tone (a ccmi_tone) its *_tone_plan / *_tone ones; head their first two arguments; dev None: the current
+    ccmi_filter) its *_flt_plan / *_flt ones, or with tone (a ccmi_tone) its *_tone_plan / *_tone ones, or
+    with mx (a ccmi_mix) its *_mix_plan / *_mix ones; head their first two arguments; dev None: the current
     device.  interp: _interp()'s pair, for the resample (a warp carries its own)."""
     import torch
     dtype = torch.float32 if dtype is None else dtype
     fmt, keep = _model_fmt(n, colour, mean, std, dtype, mirror)
     rs = None if size is None or warp is not None else C.byref(_resample(size, interp))
     geom, need = _plan_model(plan, head, n, rects, fmt, rs, output_bitdepth, output_chroma_format, warp, col=col, flt=flt,
-                             tone=tone)
+                             tone=tone, mx=mx)
     dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else dev
     res, op, cap, frames = _model_outs(geom, fmt, dtype, channels_last, out, dev)
     stream_handle, workspace = _stream_ws(dev, stream_handle, workspace, need)
-    if tone is not None:
+    if mx is not None:
+        check(run(*head, n, None if warp is not None else rects, op, cap, C.byref(fmt), None if warp is not None else rs,
+                  None if warp is None else C.byref(warp), None if col is None else C.byref(col),
+                  None if tone is None else C.byref(tone), None if flt is None else C.byref(flt), C.byref(mx),
+                  output_bitdepth, output_chroma_format, workspace.data_ptr(), workspace.numel(), stream_handle))
+    elif tone is not None:
         check(run(*head, n, None if warp is not None else rects, op, cap, C.byref(fmt), None if warp is not None else rs,
                   None if warp is None else C.byref(warp), None if col is None else C.byref(col), C.byref(tone),
                   None if flt is None else C.byref(flt), output_bitdepth, output_chroma_format, workspace.data_ptr(),
@@ -1085,7 +1285,8 @@ def decode_batch_model(streams: Sequence[bytes], roi=None, colour: str = "rgb", 
                        channels_last: bool = False, mirror=None, out=None, output_bitdepth: int = 0,
                        output_chroma_format: int = 0, workspace=None, stream_handle: int | None = None, size=None,
                        affine=None, pad: str = "fill", fill=0.0, colour_ops=None, blur=None, solarize=None,
-                       tone_ops=None, interpolation: str = "bilinear", clamp: bool = False, perspective=None):
+                       tone_ops=None, erase=None, erase_seed=None, mix=None, interpolation: str = "bilinear",
+                       clamp: bool = False, perspective=None):
     """Decode .cool streams into the tensor a model takes (ccmi_decode_batch_dev_fmt): one
     [n, 3, h, w] tensor of `dtype` (torch.float32, the default, torch.float16 or torch.bfloat16),
     every channel at full size (420 chroma nearest-upsampled), RGB (colour="rgb": YUV streams go
@@ -1155,7 +1356,20 @@ def decode_batch_model(streams: Sequence[bytes], roi=None, colour: str = "rgb", 
     random_perspective() draws them).  It composes with pad, fill, interpolation, clamp, mirror,
     colour_ops, tone_ops, blur and solarize exactly as affine= does; rows 0 0 1 give affine='s bits.
     The library refuses a denominator that is not positive over the output and a perspective too
-    strong for float32 positions (ccmi.h)."""
+    strong for float32 positions (ccmi.h).
+
+    erase= / erase_seed= / mix= (ccmi_decode_batch_dev_mix; with or without everything above): RandomErasing,
+    MixUp and CutMix AFTER the normalisation and before the one rounding to `dtype` (the contract's steps
+    4e and 4m), in stored coordinates (after mirror).  erase: one entry per frame, None or a list of at
+    most 4 rectangles (x, y, w, h, value[, sigma]), value one float or three in the normalised units, a
+    later rectangle winning; sigma > 0 adds a Gaussian of that sigma per element from the counter-based
+    generator of ccmi.h, keyed by erase_seed (one int, or one per frame) and the element's stored position
+    alone: a frame gives the same bits alone or anywhere in any batch.  mix: one entry per frame, None,
+    (partner, lam): lam * frame + (1 - lam) * partner, or (partner, (x, y, w, h)): the partner's pixels
+    inside the box; the partner enters erased but unmixed (batch.roll() / flip() of the erased batch) and
+    must be stored at the frame's size.  random_erasing() and mixup_cutmix() draw such lists.  The frames
+    concerned are staged in float32 like blurred ones and formatted by one launch per call; the others
+    keep their kernels and bits."""
     n = len(streams)
     keep, sp, ln = _marshal(streams)
     L = _bind()
@@ -1164,6 +1378,12 @@ def decode_batch_model(streams: Sequence[bytes], roi=None, colour: str = "rgb", 
     col, keep_c = _colour(colour_ops, n)
     flt, keep_f = _filter(blur, solarize, n)
     tone, keep_t = _tone(tone_ops, n)
+    mx, keep_m = _mix(erase, erase_seed, mix, n)
+    if mx is not None:
+        return _run_model(L.ccmi_decode_batch_dev_mix_plan, L.ccmi_decode_batch_dev_mix, (sp, ln), n,
+                          None if warp is not None else _rects(roi, streams, n), None, colour, mean, std, dtype,
+                          channels_last, mirror, out, output_bitdepth, output_chroma_format, workspace, stream_handle, size,
+                          warp, col, flt, tone, interp=interp, mx=mx)
     if tone is not None:
         return _run_model(L.ccmi_decode_batch_dev_tone_plan, L.ccmi_decode_batch_dev_tone, (sp, ln), n,
                           None if warp is not None else _rects(roi, streams, n), None, colour, mean, std, dtype,
@@ -1576,7 +1796,8 @@ class LatentStore:
                      channels_last: bool = False, mirror=None, out=None, output_bitdepth: int = 0,
                      output_chroma_format: int = 0, workspace=None, stream_handle: int | None = None, size=None,
                      affine=None, pad: str = "fill", fill=0.0, colour_ops=None, blur=None, solarize=None,
-                     tone_ops=None, interpolation: str = "bilinear", clamp: bool = False, perspective=None):
+                     tone_ops=None, erase=None, erase_seed=None, mix=None, interpolation: str = "bilinear",
+                     clamp: bool = False, perspective=None):
         """render() into the tensor a model takes (ccmi_latents_render_fmt; with size
         ccmi_latents_render_rs; with affine ccmi_latents_render_warp): frames and regions as for
         render(), the result and every other argument as for decode_batch_model, whose output for
@@ -1587,7 +1808,8 @@ class LatentStore:
         ccmi_latents_render_tone:
         render_model_workspace_bytes() takes the same arguments.  interpolation= / clamp= as for
         decode_batch_model (a bicubic warp's windows, and so its workspace, are a tap wider);
-        perspective= as for decode_batch_model, in place of affine=."""
+        perspective= as for decode_batch_model, in place of affine=; erase= / erase_seed= / mix= as for
+        decode_batch_model (ccmi_latents_render_mix), partners being frames of this call."""
         m, idx, rects = self._frames(index, None if affine is not None or perspective is not None else roi)
         L = _bind()
         interp = _interp(interpolation, clamp)
@@ -1595,6 +1817,12 @@ class LatentStore:
         col, keep_c = _colour(colour_ops, m)
         flt, keep_f = _filter(blur, solarize, m)
         tone, keep_t = _tone(tone_ops, m)
+        mx, keep_m = _mix(erase, erase_seed, mix, m)
+        if mx is not None:
+            return _run_model(L.ccmi_latents_render_mix_plan, L.ccmi_latents_render_mix, (self._handle(), idx), m, rects,
+                              self._store.device, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth,
+                              output_chroma_format, workspace, stream_handle, size, warp, col, flt, tone,
+                              interp=interp, mx=mx)
         if tone is not None:
             return _run_model(L.ccmi_latents_render_tone_plan, L.ccmi_latents_render_tone, (self._handle(), idx), m, rects,
                               self._store.device, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth,
@@ -1639,15 +1867,18 @@ class LatentStore:
 
     def render_model_workspace_bytes(self, index=None, roi=None, size=None, output_bitdepth: int = 0,
                                      output_chroma_format: int = 0, affine=None, pad: str = "fill", fill=0.0,
-                                     colour_ops=None, blur=None, solarize=None, tone_ops=None,
-                                     interpolation: str = "bilinear", clamp: bool = False, perspective=None) -> int:
+                                     colour_ops=None, blur=None, solarize=None, tone_ops=None, erase=None,
+                                     erase_seed=None, mix=None, interpolation: str = "bilinear", clamp: bool = False,
+                                     perspective=None) -> int:
         """Header-only: the workspace render_model needs for these frames, regions and size, or
         these frames, matrices and size (ccmi_latents_render_rs_plan / _warp_plan; the element type,
         colour and strides do not change it), these colour ops (ccmi_latents_render_col_plan:
         the op tables and the contrast ops' accumulators) and this blur and solarize
         (ccmi_latents_render_flt_plan: a float32 staging frame and 256 bytes of tables per frame
         that takes the stage) and these tone ops (ccmi_latents_render_tone_plan: ccmi.h's formula).
-        perspective= in place of affine=: the same plans with CCMI_WARP_PROJECTIVE."""
+        perspective= in place of affine=: the same plans with CCMI_WARP_PROJECTIVE.  erase= / mix=
+        (ccmi_latents_render_mix_plan): 256 bytes per mix-staged frame and a second float32 frame for
+        those with a blur or a solarize, on top of their staging (ccmi.h's formula)."""
         m, idx, rects = self._frames(index, None if affine is not None or perspective is not None else roi)
         fmt = TensorFmt(elem=ELEM_F32, colour=COLOUR_ASIS)
         for c in range(3):
@@ -1657,6 +1888,11 @@ class LatentStore:
         col, keep_c = _colour(colour_ops, m)
         flt, keep_f = _filter(blur, solarize, m)
         tone, keep_t = _tone(tone_ops, m)
+        mx, keep_m = _mix(erase, erase_seed, mix, m)
+        if mx is not None:
+            rs = None if size is None or warp is not None else C.byref(_resample(size, interp))
+            return _plan_model(_bind().ccmi_latents_render_mix_plan, (self._handle(), idx), m, rects, fmt, rs,
+                               output_bitdepth, output_chroma_format, warp, col=col, flt=flt, tone=tone, mx=mx)[1]
         if tone is not None:
             rs = None if size is None or warp is not None else C.byref(_resample(size, interp))
             return _plan_model(_bind().ccmi_latents_render_tone_plan, (self._handle(), idx), m, rects, fmt, rs,

@@ -178,7 +178,7 @@ DecFltEntry filter_entry(const DecTailFrame &f)
     DecFltEntry e{};
     // a frame's tone ops leave it in its second buffer after an odd number of sharpness passes
     e.src = f.tone ? f.tone->buf[dec_tone_sharps(*f.tone) & 1] : f.flt_tmp;
-    e.dst = f.dst;
+    e.dst = f.mix ? static_cast<void *>(f.mix_buf) : f.dst; // a mix-staged frame stays in float32 (identity_call)
     e.r = f.flt->r, e.sol = f.flt->sol, e.th = f.flt->th;
     memcpy(e.taps, f.flt->taps, sizeof e.taps);
     return e;
@@ -204,6 +204,16 @@ DecTailFrame staged_frame(const DecTailFrame &f, int oh, int ow)
     return t;
 }
 
+// the identity format as the filter kernel's own launch argument: what it writes for a mix-staged frame,
+// [3][oh][ow] float32 at DecTailFrame::mix_buf (y 1 + 0: y with a -0 turned into +0)
+DecFmtCall identity_call(int oh, int ow)
+{
+    DecFmtCall C;
+    for (int c = 0; c < 3; ++c) C.scale[c] = 1.f, C.bias[c] = 0.f;
+    C.sc = (int64_t)oh * ow, C.sy = ow, C.sx = 1;
+    return C;
+}
+
 size_t al16(size_t x) { return (x + 15) & ~(size_t)15; }
 
 // the filter entries of a group of m staged frames follow their staging entries
@@ -213,10 +223,13 @@ int check_staged(const DecTailFrame &f)
 {
     if (!f.fmt.on || !f.flt || !f.flt_tmp || !f.dst) return ccmi_set_error(CCMI_ERR_ARG, "dec: a filter without its staging frame");
     if (f.flt->r < 0 || f.flt->r > kR) return ccmi_set_error(CCMI_ERR_ARG, "dec: filter radius %d", f.flt->r);
+    if (dec_flt_class(f) == 1 && !f.mix_buf) return ccmi_set_error(CCMI_ERR_ARG, "dec: a mix-staged frame without its second frame");
     return CCMI_OK;
 }
 
 } // namespace
+
+const float *dec_mix_source(const DecTailFrame &f) { return dec_flt_class(f) == 1 ? f.mix_buf : filter_entry(f).src; }
 
 void dec_flt_fill(void *flt_tab, int m, int i, const DecTailFrame &f, int h, int w, int oy, int ox)
 {
@@ -255,12 +268,29 @@ int launch_dec_out_group_flt(const DecTailFrame *const *fr, int m, int h, int w,
             reinterpret_cast<const DecTone *>(static_cast<const uint8_t *>(dev_flt_tab) + kFltTableBytes * (size_t)m);
         if (int rc = launch_dec_tone_group(dev_es, es.data(), m, oh, ow, s)) return rc;
     }
+    // the frames the filter kernel formats, then the mix-staged ones it filters in float32, then the
+    // mix-staged ones it has nothing to do for (dec_flt_class: 0, 1, 2, in this order)
+    int m0 = 0, m1 = 0;
+    for (int i = 0; i < m; ++i) {
+        const int k = dec_flt_class(*fr[i]);
+        if (k < (i ? dec_flt_class(*fr[i - 1]) : 0)) return ccmi_set_error(CCMI_ERR_ARG, "dec: staged frames out of order");
+        m0 += k == 0, m1 += k == 1;
+    }
     const int tiles_x = filter_tiles_x(ow);
-    const dim3 grid((unsigned)(tiles_x * filter_tiles_y(oh)), (unsigned)m);
-    const DecFmtCall C = fmt_call(f0.fmt);
-    return with_elem_type(f0.fmt.elem, [&](auto t) {
-        hipLaunchKernelGGL(dec_filter_batch<decltype(t)>, grid, dim3(kThreads), 0, s, fe, oh, ow, C, tiles_x);
-    });
+    if (m0 > 0) {
+        const dim3 grid((unsigned)(tiles_x * filter_tiles_y(oh)), (unsigned)m0);
+        const DecFmtCall C = fmt_call(f0.fmt);
+        if (int rc = with_elem_type(f0.fmt.elem, [&](auto t) {
+                hipLaunchKernelGGL(dec_filter_batch<decltype(t)>, grid, dim3(kThreads), 0, s, fe, oh, ow, C, tiles_x);
+            }))
+            return rc;
+    }
+    if (m1 > 0) {
+        const dim3 grid((unsigned)(tiles_x * filter_tiles_y(oh)), (unsigned)m1);
+        hipLaunchKernelGGL(dec_filter_batch<float>, grid, dim3(kThreads), 0, s, fe + m0, oh, ow, identity_call(oh, ow), tiles_x);
+        CCMI_HIP_CHECK(hipGetLastError());
+    }
+    return CCMI_OK;
 }
 
 int launch_dec_out_frame_flt(const DecTailFrame &f, const int32_t *synout, int h, int w, hipStream_t s)
@@ -272,9 +302,15 @@ int launch_dec_out_frame_flt(const DecTailFrame &f, const int32_t *synout, int h
     if (int rc = launch_dec_out_frame(staged_frame(f, oh, ow), synout, h, w, false, true, s)) return rc;
     if (f.tone)
         if (int rc = launch_dec_tone_frame(*f.tone, oh, ow, s)) return rc;
+    if (dec_flt_class(f) == 2) return CCMI_OK; // mix-staged, nothing to filter: dec_mix_batch reads the staged frame
     const DecFltEntry F = filter_entry(f);
     const int tiles_x = filter_tiles_x(ow);
     const dim3 grid((unsigned)(tiles_x * filter_tiles_y(oh)));
+    if (f.mix) { // mix-staged: filtered in float32 into its second frame
+        hipLaunchKernelGGL(dec_filter<float>, grid, dim3(kThreads), 0, s, F, oh, ow, identity_call(oh, ow), tiles_x);
+        CCMI_HIP_CHECK(hipGetLastError());
+        return CCMI_OK;
+    }
     const DecFmtCall C = fmt_call(f.fmt);
     return with_elem_type(f.fmt.elem, [&](auto t) {
         hipLaunchKernelGGL(dec_filter<decltype(t)>, grid, dim3(kThreads), 0, s, F, oh, ow, C, tiles_x);

@@ -389,6 +389,7 @@ struct Run {
     std::vector<LatLaunch> lat;
     size_t lat_tab() const { return pl.lat_tab_off - pl.tail_off; } // of the job table in `tab`
     size_t flt_tab() const { return pl.flt_tab_off - pl.tail_off; } // of the filter stage's tables in `tab`
+    size_t mix_tab() const { return pl.mix_tab_off - pl.tail_off; } // of the mix table in `tab`
     uint32_t *status() const { return reinterpret_cast<uint32_t *>(dev + pl.status_off); }
 };
 
@@ -532,6 +533,7 @@ int build_tail_groups(Run &r)
             e.buf[1] = p.tone2_off ? reinterpret_cast<float *>(r.dev + p.tone2_off) : nullptr;
             e.acc = dec_tone_stats(e) ? r.dev + p.tone_acc_off : nullptr;
         }
+        t.mix_buf = p.mix2_off ? reinterpret_cast<float *>(r.dev + p.mix2_off) : nullptr;
         if (!p.batchable) continue;
         const int c = r.chunk_of[i];
         auto it = std::find_if(r.tails.begin(), r.tails.end(), [&](const TailGroup &g) {
@@ -551,6 +553,9 @@ int build_tail_groups(Run &r)
         if (r.pl.n_flt) { // the frames that take the filter stage last, in their order: they run as their own launches
             auto staged = std::stable_partition(g.frames.begin(), g.frames.end(), [](const DecTailFrame *f) { return !f->flt; });
             g.n_flt = (int)(g.frames.end() - staged);
+            if (r.pl.n_mix) // ... and among them the mix-staged ones last (dec_flt_class)
+                std::stable_sort(staged, g.frames.end(),
+                                 [](const DecTailFrame *a, const DecTailFrame *b) { return dec_flt_class(*a) < dec_flt_class(*b); });
             g.flt_off = fpos;
             fpos += dec_flt_table_bytes(!r.pl.tones.empty()) * (size_t)g.n_flt;
         }
@@ -560,6 +565,20 @@ int build_tail_groups(Run &r)
     }
     r.tab_used = tpos;
     return CCMI_OK;
+}
+
+// ccmi_mix: the entries of the mix-staged frames, once every frame has its device pointers
+void build_mix_table(Run &r, int &max_oh, int &max_ow)
+{
+    max_oh = max_ow = 0;
+    for (const FramePlan &p : r.pl.fr) {
+        const DecTailFrame &t = p.tail;
+        if (!t.mix) continue;
+        const bool sized = t.fmt.rs || t.fmt.warp;
+        const int oh = sized ? t.fmt.out_h : t.roi.rect.h(), ow = sized ? t.fmt.out_w : t.roi.rect.w();
+        dec_mix_fill(r.tab.data() + r.mix_tab(), t, oh, ow, t.mix->partner >= 0 ? r.pl.mixes[t.mix->partner].entry : -1);
+        max_oh = std::max(max_oh, oh), max_ow = std::max(max_ow, ow);
+    }
 }
 
 // Latent-store sink: a pack job per non-empty grid, chunk by chunk, then two copy jobs per
@@ -850,6 +869,9 @@ void store_timing(const Run &r, const EventSet &ev, const StreamSet *fk)
             if (hipEventElapsedTime(&t, e.start, e.arm_done) == hipSuccess) arm = std::max(arm, t);
             if (hipEventElapsedTime(&t, ev.e[1], e.tail_done) == hipSuccess) span = std::max(span, t);
         }
+        // ccmi_mix: the call's one mix launch runs on the caller's stream after the join and ends the tail
+        float t = 0.f;
+        if (r.pl.n_mix && hipEventElapsedTime(&t, ev.e[1], ev.e[3]) == hipSuccess) span = std::max(span, t);
         g_last_ms[1] = arm;
         g_last_ms[2] = span - arm;
         g_last_ms[3] = all - span;
@@ -892,12 +914,17 @@ int decode_run(const DecodeRequest &rq, DecodePlan &pl, hipStream_t s)
     if (!render)
         if (int rc = build_arm_groups(r)) return rc;
     // the tables of the call: the tail groups', then the latent store's jobs, in one copy
-    r.tab.assign(std::max(r.lat_tab() + pl.lat_tab_cap, r.flt_tab() + pl.flt_table_bytes()) + 1, 0);
+    r.tab.assign(std::max(r.lat_tab() + pl.lat_tab_cap, r.mix_tab() + pl.mix_table_bytes()) + 1, 0);
     if (!rq.lat_store)
         if (int rc = build_tail_groups(r)) return rc;
     if (rq.lat_store) build_pack_jobs(r);
     if (render) build_unpack_jobs(r);
-    if (pl.n_flt) r.tab_used = r.flt_tab() + pl.flt_table_bytes(); // the filter stage's tables end the image
+    if (pl.n_flt) r.tab_used = r.flt_tab() + pl.flt_table_bytes(); // the filter stage's tables end the image ...
+    int mix_oh = 0, mix_ow = 0;
+    if (pl.n_mix) { // ... or the mix table after them
+        build_mix_table(r, mix_oh, mix_ow);
+        r.tab_used = r.mix_tab() + pl.mix_table_bytes();
+    }
     if (r.tab_used)
         CCMI_HIP_CHECK(hipMemcpyAsync(r.dev + pl.tail_off, r.tab.data(), r.tab_used, hipMemcpyHostToDevice, s));
     if (rq.lat_store) // the networks' integers: constant part -> store, before the chunks fork
@@ -908,6 +935,13 @@ int decode_run(const DecodeRequest &rq, DecodePlan &pl, hipStream_t s)
         CCMI_HIP_CHECK(hipMemsetAsync(r.dev + pl.tone_acc_off, 0, pl.tone_acc_bytes, s));
     ev.rec(1, s);
     if (int rc = run_chunks(r, ev, lease)) return rc;
+    if (pl.n_mix) { // every chunk is joined: a partner may sit in any chunk, tail group or per-frame tail
+        const FramePlan *m0 = nullptr;
+        for (const FramePlan &p : pl.fr)
+            if (p.tail.mix && !m0) m0 = &p;
+        if (int rc = launch_dec_mix(r.dev + pl.mix_tab_off, pl.n_mix, mix_oh, mix_ow, m0->tail.fmt, s)) return rc;
+        ev.rec(3, s); // the mix launch ends the tail (store_timing; forked chunks record their own tail ends)
+    }
     if (!rq.lat_store) { // what launch_chunk ran: every group, and a tail of its own per other frame
         g_last_tails[0] = (int)r.tails.size();
         for (const FramePlan &p : pl.fr) g_last_tails[1] += p.batchable ? 0 : 1;
@@ -1027,10 +1061,10 @@ extern "C" int ccmi_decode_batch_ws(const uint8_t *const *streams, const size_t 
 }
 
 // ------------------------------------------------------------------ device sinks
-// Thirty-two entry points over one table: the source is the caller's streams or a latent store, the
+// Thirty-six entry points over one table: the source is the caller's streams or a latent store, the
 // sink plain samples (sample_type; with or without a region) or formatted ones (fmt, forced to
 // CCMI_SAMPLE_F32, the call whose output kernel the format replaces; with or without a resample,
-// or with a warp, which takes no region; with or without colour ops, tone ops and a filter),
+// or with a warp, which takes no region; with or without colour ops, tone ops, a filter and a mix),
 // and each comes as a plan and as a run.  `who` is the entry point's name for the error text,
 // `missing` its own null-argument check beyond the source's.
 struct Sink {
@@ -1042,6 +1076,7 @@ struct Sink {
     const ccmi_colour *colour;
     const ccmi_filter *filter = nullptr;
     const ccmi_tone *tone = nullptr;
+    const ccmi_mix *mix = nullptr;
 };
 
 static Sink samples(const ccmi_rect *roi, int sample_type) { return Sink{roi, sample_type, nullptr, nullptr, nullptr, nullptr}; }
@@ -1077,6 +1112,13 @@ static Sink toned(const ccmi_rect *roi, const ccmi_tensor_fmt *fmt, const ccmi_r
     return Sink{roi, CCMI_SAMPLE_F32, fmt, rs, warp, colour, filter, tone};
 }
 
+// ... and the erase / mix pass on the normalised frames
+static Sink mixed(const ccmi_rect *roi, const ccmi_tensor_fmt *fmt, const ccmi_resample *rs, const ccmi_warp *warp,
+                  const ccmi_colour *colour, const ccmi_tone *tone, const ccmi_filter *filter, const ccmi_mix *mix)
+{
+    return Sink{roi, CCMI_SAMPLE_F32, fmt, rs, warp, colour, filter, tone, mix};
+}
+
 static void set_sink(DecodeRequest &rq, const Sink &k)
 {
     rq.sample = k.sample;
@@ -1087,6 +1129,7 @@ static void set_sink(DecodeRequest &rq, const Sink &k)
     rq.colour = k.colour;
     rq.filter = k.filter;
     rq.tone = k.tone;
+    rq.mix = k.mix;
 }
 
 // streams as the source: null arguments, then the sample type, then the plan's own errors
@@ -1279,6 +1322,31 @@ extern "C" int ccmi_decode_batch_dev_flt_plan(const uint8_t *const *streams, con
     return sink_plan(rq, geom, info, workspace_bytes);
 }
 
+// The mixing sink: the _tone sink with a ccmi_mix (mix NULL: that call itself, which is how the _tone
+// entry points run).
+static int dev_mix_plan(const char *who, const uint8_t *const *streams, const size_t *lens, int n, const Sink &k,
+                        int out_bitdepth, int out_chroma, ccmi_frame_geom *geom, ccmi_roi_info *info, ccmi_rect *window,
+                        size_t *workspace_bytes)
+{
+    DecodeRequest rq;
+    if (int rc = stream_request(who, streams, lens, n, k, out_bitdepth, out_chroma,
+                                !k.fmt || (k.warp && !k.warp->matrix) || (window && !k.warp) || !geom || !workspace_bytes, rq))
+        return rc;
+    rq.window = window;
+    return sink_plan(rq, geom, info, workspace_bytes);
+}
+
+static int dev_mix_run(const char *who, const uint8_t *const *streams, const size_t *lens, int n, const Sink &k,
+                       void *const *out_dev, const size_t *out_caps, int out_bitdepth, int out_chroma, void *workspace,
+                       size_t workspace_bytes, void *stream)
+{
+    DecodeRequest rq;
+    if (int rc = stream_request(who, streams, lens, n, k, out_bitdepth, out_chroma,
+                                !out_dev || !out_caps || !k.fmt || (k.warp && !k.warp->matrix), rq))
+        return rc;
+    return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
+}
+
 extern "C" int ccmi_decode_batch_dev_tone_plan(const uint8_t *const *streams, const size_t *lens, int n,
                                                const ccmi_rect *roi, int out_bitdepth, int out_chroma,
                                                const ccmi_tensor_fmt *fmt, const ccmi_resample *rs, const ccmi_warp *warp,
@@ -1286,13 +1354,20 @@ extern "C" int ccmi_decode_batch_dev_tone_plan(const uint8_t *const *streams, co
                                                ccmi_frame_geom *geom, ccmi_roi_info *info, ccmi_rect *window,
                                                size_t *workspace_bytes)
 {
-    DecodeRequest rq;
-    if (int rc = stream_request("decode_batch_dev_tone_plan (frame 0)", streams, lens, n,
-                                toned(roi, fmt, rs, warp, colour, tone, filter), out_bitdepth, out_chroma,
-                                !fmt || (warp && !warp->matrix) || (window && !warp) || !geom || !workspace_bytes, rq))
-        return rc;
-    rq.window = window;
-    return sink_plan(rq, geom, info, workspace_bytes);
+    return dev_mix_plan("decode_batch_dev_tone_plan (frame 0)", streams, lens, n, toned(roi, fmt, rs, warp, colour, tone, filter),
+                        out_bitdepth, out_chroma, geom, info, window, workspace_bytes);
+}
+
+extern "C" int ccmi_decode_batch_dev_mix_plan(const uint8_t *const *streams, const size_t *lens, int n,
+                                              const ccmi_rect *roi, int out_bitdepth, int out_chroma,
+                                              const ccmi_tensor_fmt *fmt, const ccmi_resample *rs, const ccmi_warp *warp,
+                                              const ccmi_colour *colour, const ccmi_tone *tone, const ccmi_filter *filter,
+                                              const ccmi_mix *mix, ccmi_frame_geom *geom, ccmi_roi_info *info,
+                                              ccmi_rect *window, size_t *workspace_bytes)
+{
+    return dev_mix_plan("decode_batch_dev_mix_plan (frame 0)", streams, lens, n,
+                        mixed(roi, fmt, rs, warp, colour, tone, filter, mix), out_bitdepth, out_chroma, geom, info, window,
+                        workspace_bytes);
 }
 
 extern "C" int ccmi_decode_batch_dev_flt(const uint8_t *const *streams, const size_t *lens, int n, const ccmi_rect *roi,
@@ -1315,12 +1390,19 @@ extern "C" int ccmi_decode_batch_dev_tone(const uint8_t *const *streams, const s
                                           const ccmi_tone *tone, const ccmi_filter *filter, int out_bitdepth, int out_chroma,
                                           void *workspace, size_t workspace_bytes, void *stream)
 {
-    DecodeRequest rq;
-    if (int rc = stream_request("decode_batch_dev_tone (frame 0)", streams, lens, n,
-                                toned(roi, fmt, rs, warp, colour, tone, filter), out_bitdepth, out_chroma,
-                                !out_dev || !out_caps || !fmt || (warp && !warp->matrix), rq))
-        return rc;
-    return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
+    return dev_mix_run("decode_batch_dev_tone (frame 0)", streams, lens, n, toned(roi, fmt, rs, warp, colour, tone, filter),
+                       out_dev, out_caps, out_bitdepth, out_chroma, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ccmi_decode_batch_dev_mix(const uint8_t *const *streams, const size_t *lens, int n, const ccmi_rect *roi,
+                                         void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
+                                         const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
+                                         const ccmi_tone *tone, const ccmi_filter *filter, const ccmi_mix *mix,
+                                         int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes,
+                                         void *stream)
+{
+    return dev_mix_run("decode_batch_dev_mix (frame 0)", streams, lens, n, mixed(roi, fmt, rs, warp, colour, tone, filter, mix),
+                       out_dev, out_caps, out_bitdepth, out_chroma, workspace, workspace_bytes, stream);
 }
 
 extern "C" int ccmi_decode_batch_dev_fmt_plan(const uint8_t *const *streams, const size_t *lens, int n,
@@ -1545,6 +1627,28 @@ extern "C" int ccmi_latents_render_col(const ccmi_latents *h, const int *index, 
     return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
 }
 
+static int lat_mix_plan(const char *who, const ccmi_latents *h, const int *index, int m, const Sink &k, int out_bitdepth,
+                        int out_chroma, ccmi_frame_geom *geom, ccmi_roi_info *info, ccmi_rect *window, size_t *workspace_bytes)
+{
+    DecodeRequest rq;
+    if (int rc = latents_request(who, h, index, m, k, out_bitdepth, out_chroma, false,
+                                 !k.fmt || (k.warp && !k.warp->matrix) || (window && !k.warp) || !geom || !workspace_bytes, rq))
+        return rc;
+    rq.window = window;
+    return sink_plan(rq, geom, info, workspace_bytes);
+}
+
+static int lat_mix_run(const char *who, const ccmi_latents *h, const int *index, int m, const Sink &k, void *const *out_dev,
+                       const size_t *out_caps, int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes,
+                       void *stream)
+{
+    DecodeRequest rq;
+    if (int rc = latents_request(who, h, index, m, k, out_bitdepth, out_chroma, true,
+                                 !out_dev || !out_caps || !k.fmt || (k.warp && !k.warp->matrix), rq))
+        return rc;
+    return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
+}
+
 extern "C" int ccmi_latents_render_flt_plan(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
                                             int out_bitdepth, int out_chroma, const ccmi_tensor_fmt *fmt,
                                             const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
@@ -1566,13 +1670,19 @@ extern "C" int ccmi_latents_render_tone_plan(const ccmi_latents *h, const int *i
                                              const ccmi_tone *tone, const ccmi_filter *filter, ccmi_frame_geom *geom,
                                              ccmi_roi_info *info, ccmi_rect *window, size_t *workspace_bytes)
 {
-    DecodeRequest rq;
-    if (int rc = latents_request("latents_render_tone_plan (frame 0)", h, index, m,
-                                 toned(roi, fmt, rs, warp, colour, tone, filter), out_bitdepth, out_chroma, false,
-                                 !fmt || (warp && !warp->matrix) || (window && !warp) || !geom || !workspace_bytes, rq))
-        return rc;
-    rq.window = window;
-    return sink_plan(rq, geom, info, workspace_bytes);
+    return lat_mix_plan("latents_render_tone_plan (frame 0)", h, index, m, toned(roi, fmt, rs, warp, colour, tone, filter),
+                        out_bitdepth, out_chroma, geom, info, window, workspace_bytes);
+}
+
+extern "C" int ccmi_latents_render_mix_plan(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
+                                            int out_bitdepth, int out_chroma, const ccmi_tensor_fmt *fmt,
+                                            const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
+                                            const ccmi_tone *tone, const ccmi_filter *filter, const ccmi_mix *mix,
+                                            ccmi_frame_geom *geom, ccmi_roi_info *info, ccmi_rect *window,
+                                            size_t *workspace_bytes)
+{
+    return lat_mix_plan("latents_render_mix_plan (frame 0)", h, index, m, mixed(roi, fmt, rs, warp, colour, tone, filter, mix),
+                        out_bitdepth, out_chroma, geom, info, window, workspace_bytes);
 }
 
 extern "C" int ccmi_latents_render_flt(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
@@ -1595,12 +1705,18 @@ extern "C" int ccmi_latents_render_tone(const ccmi_latents *h, const int *index,
                                         const ccmi_tone *tone, const ccmi_filter *filter, int out_bitdepth, int out_chroma,
                                         void *workspace, size_t workspace_bytes, void *stream)
 {
-    DecodeRequest rq;
-    if (int rc = latents_request("latents_render_tone (frame 0)", h, index, m,
-                                 toned(roi, fmt, rs, warp, colour, tone, filter), out_bitdepth, out_chroma, true,
-                                 !out_dev || !out_caps || !fmt || (warp && !warp->matrix), rq))
-        return rc;
-    return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
+    return lat_mix_run("latents_render_tone (frame 0)", h, index, m, toned(roi, fmt, rs, warp, colour, tone, filter), out_dev,
+                       out_caps, out_bitdepth, out_chroma, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ccmi_latents_render_mix(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
+                                       void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
+                                       const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
+                                       const ccmi_tone *tone, const ccmi_filter *filter, const ccmi_mix *mix,
+                                       int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return lat_mix_run("latents_render_mix (frame 0)", h, index, m, mixed(roi, fmt, rs, warp, colour, tone, filter, mix),
+                       out_dev, out_caps, out_bitdepth, out_chroma, workspace, workspace_bytes, stream);
 }
 
 extern "C" int ccmi_latents_render_fmt_plan(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,

@@ -243,6 +243,27 @@ inline int dec_tone_stats(const DecTone &t)
 // the table bytes of a staged frame: with a tone op in the call, its DecTone follows
 inline size_t dec_flt_table_bytes(bool tone) { return kFltTableBytes + (tone ? kToneTableBytes : 0); }
 
+// ccmi_mix of one frame (steps 4e and 4m of the contract in ccmi.h), validated and resolved by the plan.
+// A mix-staged frame takes the filter stage, which leaves it in float32 in the workspace (the staging
+// frame, or DecTailFrame::mix_buf where the filter kernel has something to compute); dec_mix_batch
+// (dec_mix.hip) then formats all of them in one launch from the call's mix table.
+struct DecMixRect {
+    int x, y, w, h;
+    float v[3], sigma;
+};
+struct DecMix {
+    int staged = 0;    // the frame is mix-staged: it takes the stage or is the partner of a frame that does
+    int entry = -1;    // staged: its entry of the mix table
+    int count = 0;     // rectangles
+    int partner = -1;  // a frame of the call, or -1
+    float lam = 1.f, oml = 0.f; // lam and 1.0f - lam (float32, computed once here)
+    int box[4] = {0, 0, 0, 0};  // x, y, w, h; w == 0: no box (a blend)
+    uint64_t seed = 0;
+    DecMixRect r[CCMI_MIX_MAX_RECTS] = {};
+};
+// what the stage adds to the call's tables per mix-staged frame (the workspace formula of ccmi.h)
+constexpr size_t kMixTableBytes = 256;
+
 // the form of a tail group's output section: the plain entry, or its resample / warp / projective warp extension
 enum { kOutPlain = 0, kOutRs = 1, kOutWarp = 2, kOutPersp = 3 };
 inline int dec_out_form(const DecFmt &f) { return f.rs ? kOutRs : f.warp ? (f.persp ? kOutPersp : kOutWarp) : kOutPlain; }
@@ -270,6 +291,11 @@ struct DecTailFrame {
     // ccmi_tone with an op in the call: every staged frame's DecTone (in DecodePlan::tones; device
     // pointers set by decode_run), NULL otherwise
     const DecTone *tone = nullptr;
+    // ccmi_mix: the frame is mix-staged (its DecMix, in DecodePlan::mixes; NULL otherwise): the filter
+    // kernel does not write `dst` -- with a radius or a solarize it writes mix_buf, [3][oh][ow] float32 in
+    // the identity format, and otherwise it is not launched for the frame -- and dec_mix_batch does
+    const DecMix *mix = nullptr;
+    float *mix_buf = nullptr;
     // region decode on windows: the latent planes keep their frame pitch and hold roi.arm_rows[l]
     // rows, ups.workspace / ups.out / syn.out hold the windows roi.lev[k] / the region, compact
     // (pitch = the window's width); ups.lh / lw and syn.h / w stay the frame's true sizes
@@ -321,6 +347,21 @@ int launch_dec_out_group_flt(const DecTailFrame *const *fr, int m, int h, int w,
                              const DecCol *col_sec, hipStream_t s);
 // launch_dec_out_frame for a frame that takes the stage (f.flt): staged, then dec_filter.
 int launch_dec_out_frame_flt(const DecTailFrame &f, const int32_t *synout, int h, int w, hipStream_t s);
+
+// The frames of a group that take the filter stage run in this order (build_tail_groups sorts them so):
+// 0, formatted to the caller's tensor by the filter kernel; 1, mix-staged with a radius or a solarize
+// (the filter kernel writes mix_buf); 2, mix-staged without (no filter launch).
+inline int dec_flt_class(const DecTailFrame &f) { return !f.mix ? 0 : (f.flt && (f.flt->r > 0 || f.flt->sol)) ? 1 : 2; }
+// where a mix-staged frame stands in float32 once its tail has run: what dec_mix_batch reads
+const float *dec_mix_source(const DecTailFrame &f);
+
+// The mix stage (dec_mix.hip): the call's mix table, kMixTableBytes per mix-staged frame.  dec_mix_fill
+// writes entry f.mix->entry (host side; the device pointers are the frame's and its partner's,
+// partner_entry the partner's entry or -1), launch_dec_mix formats the n_entries frames in one launch
+// per 65535 of them; fmt: any of the frames' (element type, scale and bias are one per call; the resolved
+// strides are each frame's own and travel in its entry), max_oh x max_ow: the largest stored frame among them.
+void dec_mix_fill(void *host_tab, const DecTailFrame &f, int oh, int ow, int partner_entry);
+int launch_dec_mix(const void *dev_tab, int n_entries, int max_oh, int max_ow, const DecFmt &fmt, hipStream_t s);
 
 // The tone stage (dec_tone.hip), between the staging launches and the filter launch: segment after
 // segment, a statistics pass where a frame's terminator needs one, then the apply pass (in place) or

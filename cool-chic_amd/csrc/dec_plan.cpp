@@ -298,6 +298,68 @@ int filter_frame(const ccmi_filter &fl, int i, size_t first, DecFlt &d, bool *ta
     return CCMI_OK;
 }
 
+// ccmi_mix of frame i of n, whose rectangles start at `first` of the flat array: everything that needs no
+// stored size, validated and resolved (1 - lam) into d
+int mix_frame(const ccmi_mix &mx, int i, int n, size_t first, DecMix &d)
+{
+    d = DecMix{};
+    const int cnt = mx.count ? mx.count[i] : 0;
+    if (cnt < 0 || cnt > CCMI_MIX_MAX_RECTS)
+        return ccmi_set_error(CCMI_ERR_ARG, "frame %d: %d erase rectangles (0 .. %d)", i, cnt, CCMI_MIX_MAX_RECTS);
+    if (cnt > 0 && !mx.rects) return ccmi_set_error(CCMI_ERR_ARG, "frame %d: erase rectangles are NULL", i);
+    d.count = cnt;
+    d.seed = mx.seed ? mx.seed[i] : 0;
+    for (int k = 0; k < cnt; ++k) {
+        const ccmi_erase_rect &q = mx.rects[first + k];
+        for (int c = 0; c < 3; ++c)
+            if (!std::isfinite(q.v[c]))
+                return ccmi_set_error(CCMI_ERR_ARG, "frame %d: erase rectangle %d: value %d is not finite", i, k, c);
+        if (!std::isfinite(q.sigma) || q.sigma < 0.f)
+            return ccmi_set_error(CCMI_ERR_ARG, "frame %d: erase rectangle %d: sigma %g (finite, >= 0)", i, k, (double)q.sigma);
+        if (q.w < 0 || q.h < 0)
+            return ccmi_set_error(CCMI_ERR_ARG, "frame %d: erase rectangle %d: negative size (w %d h %d)", i, k, q.w, q.h);
+        d.r[k] = DecMixRect{q.x, q.y, q.w, q.h, {q.v[0], q.v[1], q.v[2]}, q.sigma};
+    }
+    const int p = mx.partner ? mx.partner[i] : -1;
+    if (p < -1 || p >= n) return ccmi_set_error(CCMI_ERR_ARG, "frame %d: partner %d (-1, or a frame 0 .. %d)", i, p, n - 1);
+    d.partner = p;
+    const ccmi_rect b = mx.box ? mx.box[i] : ccmi_rect{0, 0, 0, 0};
+    if (b.w < 0 || b.h < 0) return ccmi_set_error(CCMI_ERR_ARG, "frame %d: mix box of negative size (w %d h %d)", i, b.w, b.h);
+    if (p < 0) return CCMI_OK;
+    if (b.w > 0 && b.h > 0) { // CutMix: lam is not read
+        d.box[0] = b.x, d.box[1] = b.y, d.box[2] = b.w, d.box[3] = b.h;
+        return CCMI_OK;
+    }
+    if (!mx.lam) return ccmi_set_error(CCMI_ERR_ARG, "frame %d: lam is NULL", i);
+    const float lam = mx.lam[i];
+    if (!(lam >= 0.f && lam <= 1.f)) return ccmi_set_error(CCMI_ERR_ARG, "frame %d: lam %g (in [0, 1])", i, (double)lam);
+    d.lam = lam, d.oml = 1.0f - lam;
+    return CCMI_OK;
+}
+
+// the rest of frame i's ccmi_mix, once every frame's stored size oh[] x ow[] is known: non-empty
+// rectangles and boxes inside the frame, and a partner of the frame's size
+int mix_frame_sized(const DecMix &d, int i, const std::vector<int> &oh, const std::vector<int> &ow)
+{
+    const auto inside = [&](int x, int y, int w, int h) {
+        return x >= 0 && y >= 0 && w <= ow[i] && h <= oh[i] && x <= ow[i] - w && y <= oh[i] - h;
+    };
+    for (int k = 0; k < d.count; ++k) {
+        const DecMixRect &q = d.r[k];
+        if (q.w > 0 && q.h > 0 && !inside(q.x, q.y, q.w, q.h))
+            return ccmi_set_error(CCMI_ERR_ARG, "frame %d: erase rectangle %d (x %d y %d w %d h %d) outside the %d x %d frame", i,
+                                  k, q.x, q.y, q.w, q.h, ow[i], oh[i]);
+    }
+    if (d.partner < 0) return CCMI_OK;
+    if (d.box[2] > 0 && !inside(d.box[0], d.box[1], d.box[2], d.box[3]))
+        return ccmi_set_error(CCMI_ERR_ARG, "frame %d: mix box (x %d y %d w %d h %d) outside the %d x %d frame", i, d.box[0],
+                              d.box[1], d.box[2], d.box[3], ow[i], oh[i]);
+    if (oh[d.partner] != oh[i] || ow[d.partner] != ow[i])
+        return ccmi_set_error(CCMI_ERR_ARG, "frame %d: partner %d is stored at %d x %d, the frame at %d x %d", i, d.partner,
+                              ow[d.partner], oh[d.partner], ow[i], oh[i]);
+    return CCMI_OK;
+}
+
 // ccmi_tone of frame i, whose ops start at `first` of the flat array: validated, resolved (1 - f, the
 // posterize levels) and cut into segments in d
 int tone_ops(const ccmi_tone &tn, int i, size_t first, DecTone &d)
@@ -581,6 +643,10 @@ void plan_layout(const DecodeRequest &rq, DecodePlan &pl)
                 p.tone2_off = tot;
                 tot += align_up(p.flt_elems * 4, 256);
             }
+            if (p.tail.mix && dec_flt_class(p.tail) == 1) { // ccmi_mix: the filter kernel's float32 output
+                p.mix2_off = tot;
+                tot += align_up(p.flt_elems * 4, 256);
+            }
         }
         p.out_off = tot;
         if (!rq.device()) tot += align_up(p.of.payload, 256); // device sinks write to the caller's memory
@@ -605,6 +671,8 @@ void plan_layout(const DecodeRequest &rq, DecodePlan &pl)
     // the filter stage's tables follow the job table in the same host image: the same upload
     pl.flt_tab_off = tot;
     tot += pl.flt_table_bytes();
+    pl.mix_tab_off = tot; // ccmi_mix: the mix table ends the image
+    tot += pl.mix_table_bytes();
     if (!pl.tones.empty()) { // ccmi_tone: the accumulator blocks of the call's statistic ops, frame after frame
         pl.tone_acc_off = tot;
         for (size_t i = 0; i < pl.fr.size(); ++i) {
@@ -689,20 +757,52 @@ int decode_plan(const DecodeRequest &rq, DecodePlan &pl)
                 if (pl.tones[i].n > 0 && !takes[i]) takes[i] = 1, ++pl.n_flt;
         }
     }
+    if (rq.mix) { // every frame's rectangles, partner and weights: the mix-staged frames take the stage too
+        if (!rq.fmt) return ccmi_set_error(CCMI_ERR_ARG, "frame 0: mix without a format");
+        size_t first = 0;
+        bool any = false;
+        pl.mixes.resize(rq.n);
+        for (int i = 0; i < rq.n; ++i) {
+            if (int rc = mix_frame(*rq.mix, i, rq.n, first, pl.mixes[i])) return rc;
+            first += (size_t)pl.mixes[i].count;
+            any = any || pl.mixes[i].count > 0 || pl.mixes[i].partner >= 0;
+        }
+        if (!any) pl.mixes.clear(); // no frame takes the stage: the call without mix
+        if (any) {
+            for (int i = 0; i < rq.n; ++i)
+                if (pl.mixes[i].count > 0 || pl.mixes[i].partner >= 0) {
+                    pl.mixes[i].staged = 1;
+                    if (pl.mixes[i].partner >= 0) pl.mixes[pl.mixes[i].partner].staged = 1;
+                }
+            if (takes.empty()) takes.assign(rq.n, 0);
+            // a frame staged for the mix alone passes the filter stage with radius 0 and no solarize
+            pl.flts.resize(rq.n);
+            for (int i = 0; i < rq.n; ++i) {
+                if (!pl.mixes[i].staged) continue;
+                pl.mixes[i].entry = pl.n_mix++;
+                if (!takes[i]) takes[i] = 1, ++pl.n_flt;
+            }
+        }
+    }
     if (!pl.n_flt) pl.flts.clear(); // no frame takes the stage: the call without a filter
+    std::vector<int> oh(rq.n, 0), ow(rq.n, 0); // the stored sizes
     for (int i = 0; i < rq.n; ++i) {
         FramePlan &p = pl.fr[i];
         if (int rc = plan_frame(rq, i, p)) return rc;
         p.tail.fmt.col = pl.col ? 1 : 0;
         p.tail.col = pl.col ? &pl.cols[i] : nullptr;
+        const DecFmt &d = p.tail.fmt;
+        const bool sized = d.rs || d.warp;
+        oh[i] = sized ? d.out_h : p.tail.roi.rect.h(), ow[i] = sized ? d.out_w : p.tail.roi.rect.w();
         if (pl.n_flt && takes[i]) { // staged at the size of the stored frame
-            const DecFmt &d = p.tail.fmt;
-            const bool sized = d.rs || d.warp;
             p.tail.flt = &pl.flts[i];
             if (!pl.tones.empty()) p.tail.tone = &pl.tones[i];
-            p.flt_elems = 3 * (size_t)(sized ? d.out_h : p.tail.roi.rect.h()) * (size_t)(sized ? d.out_w : p.tail.roi.rect.w());
+            if (pl.n_mix && pl.mixes[i].staged) p.tail.mix = &pl.mixes[i];
+            p.flt_elems = 3 * (size_t)oh[i] * (size_t)ow[i];
         }
     }
+    for (int i = 0; i < rq.n && pl.n_mix; ++i)
+        if (int rc = mix_frame_sized(pl.mixes[i], i, oh, ow)) return rc;
     plan_layout(rq, pl);
     return CCMI_OK;
 }

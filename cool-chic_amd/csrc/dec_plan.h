@@ -93,6 +93,9 @@ struct DecodeRequest {
     // with fmt, optional: per-frame lists of tone ops on the staged frame, after the colour ops and before
     // the filter (ccmi_tone); a frame with a list takes the filter's stage
     const ccmi_tone *tone = nullptr;
+    // with fmt, optional: per-frame erase rectangles, partners, blend weights and boxes (ccmi_mix); the
+    // mix-staged frames take the filter's stage and are formatted by the call's one mix launch
+    const ccmi_mix *mix = nullptr;
     // either sink
     const size_t *caps = nullptr;    // [n], optional: capacity in bytes of outs[i] / dev[i]
     size_t *sizes = nullptr;         // [n], optional: bytes written per stream (filled by the plan)
@@ -131,6 +134,7 @@ struct FramePlan {
     size_t flt_off = 0, flt_elems = 0; // the filter stage's staging frame (float32); none unless the frame takes it
     size_t tone2_off = 0;              // ccmi_tone: a second frame of flt_elems for a list with a sharpness op
     size_t tone_acc_off = 0;           // ccmi_tone: the frame's accumulator blocks, one per statistic op
+    size_t mix2_off = 0;               // ccmi_mix: a mix-staged frame's filter output (flt_elems), with a radius or a solarize
 };
 
 struct DecodePlan {
@@ -159,6 +163,13 @@ struct DecodePlan {
     std::vector<DecTone> tones;
     size_t tone_acc_off = 0, tone_acc_bytes = 0;
     size_t flt_table_bytes() const { return dec_flt_table_bytes(!tones.empty()) * (size_t)n_flt; }
+    // ccmi_mix with a frame that takes the stage: every frame's DecMix (DecTailFrame::mix points here for
+    // the n_mix mix-staged frames, which all take the filter stage); their table, kMixTableBytes each,
+    // follows the filter stage's in the one host image
+    std::vector<DecMix> mixes;
+    int n_mix = 0;
+    size_t mix_tab_off = 0;
+    size_t mix_table_bytes() const { return kMixTableBytes * (size_t)n_mix; }
 #if defined(CCMI_ARM_STAMPS)
     size_t dbg_off = 0;
 #endif

@@ -34,6 +34,7 @@
 #include <tuple>
 #include <type_traits>
 
+#include "ccmi_noise.h"
 #include "fwd_common.h"
 
 using ccmi_fwd::cfloat_ptr;
@@ -129,14 +130,8 @@ __global__ void t_prologue(float *__restrict__ z, int64_t nz, const float *__res
 }
 
 // ------------------------------------------------------------------ quantizer
-__device__ __forceinline__ uint64_t mix64(uint64_t z)
-{
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-__device__ __forceinline__ float unif(uint64_t r) { return ((float)(r >> 40) + 0.5f) * 5.9604644775390625e-08f; }
+using ccmi::mix64; // the generator of ccmi.h (ccmi_noise.h)
+using ccmi::unif;
 
 struct SoftRound {
     float t, inv; // inv = 1 / tanh(1 / (2t))

@@ -1112,6 +1112,103 @@ int ccmi_latents_render_tone(const ccmi_latents *h, const int *index /* [m] or N
                              const ccmi_tone *tone /* or NULL */, const ccmi_filter *filter /* or NULL */,
                              int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes, void *stream);
 
+/* Mix stage: the tone sink with RandomErasing, MixUp and CutMix -- the three steps the supervised ViT
+ * recipes (DeiT, timm, torchvision's reference scripts) add after the normalisation -- applied in the
+ * decoder's output stage by one pass per call that sees two staged float32 frames at once and writes the
+ * caller's tensor, steps 5 and 6 applied once, after the mix.
+ * Frame j of a call of n frames TAKES THE MIX STAGE when count[j] > 0 or partner[j] >= 0.  A frame is
+ * MIX-STAGED when it takes the stage or is the partner of a frame that does.  Every other frame goes
+ * through the kernels it goes through without `mix` and keeps its bits.
+ * For a mix-staged frame y_c(i, k) is the value after step 3y-2 (without a filter: the x_c(i, k) of step
+ * 3y-0): the stored column after the mirror, + 0.0f, at the stored size oh x ow.  Every product and sum is
+ * one float32 operation in the order written (no fused multiply-add); rectangles and boxes are in stored
+ * coordinates, after mirror[j], like the filter's.
+ *   4.  a_c = y_c scale[c] + bias[c], as ever;
+ *   4e. erase, in the normalised units (torchvision and timm apply RandomErasing after Normalize): the
+ *       frame's rectangles t = 0 .. count[j] - 1 in order, a later one winning: where x_t <= k < x_t + w_t
+ *       and y_t <= i < y_t + h_t:  a_c = (sigma_t == 0) ? v_t[c] : v_t[c] + g,
+ *       g = (sqrtf(-2.f * logf(u1)) * cospif(2.f * u2)) * sigma_t, u1 = unif(r),
+ *       u2 = unif(mix64(r + 0x632BE59BD9B4E019)), r = mix64(seed[j] ^ mix64(index)),
+ *       index = (c oh + i) ow + k (< 3 * 2^28): the generator of ccmi_train_args at step 0, frame 0.  The
+ *       draw depends on (seed[j], c, i, k, oh, ow) and on nothing else -- not on the frame's place in the
+ *       call, the layout or the element type (batch invariance) -- and overlapping noise rectangles see
+ *       the same draw;
+ *   4m. mix, p = partner[j] >= 0: b_c = steps 4 and 4e of frame p at the same (i, k), with p's own
+ *       rectangles and seed; p's own partner does not enter (batch.roll() / batch.flip() of the erased,
+ *       unmixed batch).  box[j] non-empty (w > 0 and h > 0): m_c = b_c inside the box, a_c outside
+ *       (CutMix; lam is not read).  box[j] empty: m_c = (lam[j] a_c) + (oml_j b_c), oml_j = 1.0f - lam[j]
+ *       computed once on the host in float32 (MixUp; torch's rolled.mul(1 - lam).add_(x.mul(lam)) gives
+ *       the same bits).  p == j is legal and follows the formula.  partner[j] < 0: m_c = a_c;
+ *   5, 6. m_c to `elem`, round to nearest even, stored as ever.
+ * A mix-staged frame with neither rectangles nor a partner is formatted by the same kernel with m = a: the
+ * bits of a frame staged by the filter stage with radius 0 and no solarize, which are those of the call
+ * without the stage wherever no staged value is -0.
+ *
+ * One superset pair per source: the _tone argument list with `mix` after `filter`.  mix NULL, or no frame
+ * taking the stage: exactly the _tone call -- plan, workspace, launches, ccmi_decode_last_tail_groups and
+ * bits.  Otherwise, with M = the mix-staged frames, the workspace is that of the _tone call in which the
+ * M frames take the filter stage as well (a staging frame and 256 bytes each by ccmi_filter's formula, and
+ * the tone entry a call with tone ops gives every staged frame), plus exactly
+ *     256 |M|  +  sum over the M frames with radius > 0 or a solarize of (12 oh ow rounded up to 256)  bytes:
+ * the frame's 256-byte entry of the mix table (source, destination, size, its own resolved strides, seed,
+ * rectangles, partner's entry, lam, 1 - lam, box), uploaded with the rest of the tables in the call's one copy, and a second
+ * float32 frame where the filter kernel has something to compute: it then writes there in the identity
+ * format instead of the caller's tensor; with radius 0 and no solarize it is not launched for the frame and
+ * the mix kernel reads the staging frame.  The mix kernel is one launch per call over the M frames, on the
+ * call's stream after every chunk and tail group has been joined: a partner may sit in any of them.
+ * Checked by the plan before any GPU work, CCMI_ERR_ARG naming the frame and nothing written: mix without a
+ * format; a count outside [0, CCMI_MIX_MAX_RECTS]; rects NULL while a count is positive; a non-finite v or
+ * sigma, or sigma < 0; a rectangle or box with a negative size, or a non-empty one not inside
+ * [0, ow) x [0, oh) (an empty one is legal and does nothing); a partner outside [-1, n); a partner whose
+ * stored size differs from the frame's; lam NULL where it is read; a lam that is NaN or outside [0, 1];
+ * and everything the _tone plan checks.
+ * Measured (profiles/decode_mix_ab.txt): the workload of the tone stage above plus RandomErasing(p = 0.25,
+ * per-element Gaussian) on 248 frames and a per-frame MixUp(0.8) / CutMix(1.0) with the frame before (475
+ * blends, 485 boxes; all 960 frames mix-staged): 43.6-44.3 ms per call (tail 37.6-37.7 ms) against
+ * 43.0 ms (tail 37.5-37.6 ms) for the call without the stage and 48.4-48.8 ms for that call followed by the
+ * same steps as torch operations on the bf16 tensor; peak allocation above store and workspace 276 MiB
+ * against 827 MiB; the workspace grows by 114.6 MiB. */
+enum { CCMI_MIX_MAX_RECTS = 4 };
+typedef struct ccmi_erase_rect { int x, y, w, h; float v[3]; float sigma; } ccmi_erase_rect; /* 32 bytes */
+typedef struct ccmi_mix {
+    const int *count;             /* host, [n] or NULL (no frame erases): rectangles of frame j, 0 .. 4 */
+    const ccmi_erase_rect *rects; /* host, flat: frame j's follow frame j - 1's                         */
+    const uint64_t *seed;         /* host, [n] or NULL (0 for every frame); read where a sigma > 0      */
+    const int *partner;           /* host, [n] or NULL (no frame mixes): -1 or a frame of this call     */
+    const float *lam;             /* host, [n]; read where partner[j] >= 0 and box[j] is empty          */
+    const ccmi_rect *box;         /* host, [n] or NULL (every box empty)                                */
+} ccmi_mix;
+int ccmi_decode_batch_dev_mix_plan(const uint8_t *const *streams, const size_t *lens, int n,
+                                   const ccmi_rect *roi /* [n] or NULL */, int out_bitdepth, int out_chroma,
+                                   const ccmi_tensor_fmt *fmt, const ccmi_resample *rs /* or NULL */,
+                                   const ccmi_warp *warp /* or NULL */, const ccmi_colour *colour /* or NULL */,
+                                   const ccmi_tone *tone /* or NULL */, const ccmi_filter *filter /* or NULL */,
+                                   const ccmi_mix *mix /* or NULL */, ccmi_frame_geom *geom /* [n] */,
+                                   ccmi_roi_info *info /* [n] or NULL */, ccmi_rect window[] /* [n] or NULL; warp only */,
+                                   size_t *workspace_bytes);
+int ccmi_decode_batch_dev_mix(const uint8_t *const *streams, const size_t *lens, int n,
+                              const ccmi_rect *roi /* [n] or NULL */, void *const *out_dev, const size_t *out_caps,
+                              const ccmi_tensor_fmt *fmt, const ccmi_resample *rs /* or NULL */,
+                              const ccmi_warp *warp /* or NULL */, const ccmi_colour *colour /* or NULL */,
+                              const ccmi_tone *tone /* or NULL */, const ccmi_filter *filter /* or NULL */,
+                              const ccmi_mix *mix /* or NULL */, int out_bitdepth, int out_chroma, void *workspace,
+                              size_t workspace_bytes, void *stream);
+int ccmi_latents_render_mix_plan(const ccmi_latents *h, const int *index /* [m] or NULL */, int m,
+                                 const ccmi_rect *roi /* [m] or NULL */, int out_bitdepth, int out_chroma,
+                                 const ccmi_tensor_fmt *fmt, const ccmi_resample *rs /* or NULL */,
+                                 const ccmi_warp *warp /* or NULL */, const ccmi_colour *colour /* or NULL */,
+                                 const ccmi_tone *tone /* or NULL */, const ccmi_filter *filter /* or NULL */,
+                                 const ccmi_mix *mix /* or NULL */, ccmi_frame_geom *geom /* [m] */,
+                                 ccmi_roi_info *info /* [m] or NULL */, ccmi_rect window[] /* [m] or NULL; warp only */,
+                                 size_t *workspace_bytes);
+int ccmi_latents_render_mix(const ccmi_latents *h, const int *index /* [m] or NULL */, int m,
+                            const ccmi_rect *roi /* [m] or NULL */, void *const *out_dev, const size_t *out_caps,
+                            const ccmi_tensor_fmt *fmt, const ccmi_resample *rs /* or NULL */,
+                            const ccmi_warp *warp /* or NULL */, const ccmi_colour *colour /* or NULL */,
+                            const ccmi_tone *tone /* or NULL */, const ccmi_filter *filter /* or NULL */,
+                            const ccmi_mix *mix /* or NULL */, int out_bitdepth, int out_chroma, void *workspace,
+                            size_t workspace_bytes, void *stream);
+
 /* Network weights of a stream's intra frame as the decoder's fixed-point integers
  * (cc-frame-decoder.cpp:201-353, read_arm / read_ups / read_syn):
  *   arm: per hidden layer W[d][d] (out, in) then b[d]; then W_out[2][d], b_out[2]
