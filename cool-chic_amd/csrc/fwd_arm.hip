@@ -317,7 +317,7 @@ __device__ __forceinline__ void arm_fence(f2 (&o)[kNL][N])
 // and the latent's own value are multiplied back by 2^32 at the end.  Nothing is rescaled on
 // the scalar unit: the weights are used as they are.  A power-of-two scaling commutes with
 // every rounding of the chain, so the bits are the unscaled form's, under the conditions
-// written at the fused head's unit() (fwd_syn.hip, "Scaled ReLU"): every bias, activation and
+// written at the fused head (fwd_syn.hip, "Scaled ReLU"): every bias, activation and
 // partial sum is 0 or at least 2^-94 in magnitude, and no pre-activation exceeds 2^32.
 template <int D, int NH = -1, bool SC = false>
 __global__ __launch_bounds__(kThreads) void arm_fwd_pairs_kernel(

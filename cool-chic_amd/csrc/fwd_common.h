@@ -2,6 +2,8 @@
 // fwd_syn.hip) and the fused decode kernel (fwd_fused.hip).  Internal.
 #pragma once
 
+#include <type_traits>
+
 #include "ccmi_internal.h"
 
 namespace ccmi_fwd {
@@ -52,6 +54,122 @@ __host__ __device__ constexpr int arm_pack_src(int d, int nh, int t)
     const int u = t - nh * ls;
     if (u < 2 * d) return nh * lp + (u & 1) * d + (u >> 1);
     return u < 2 * d + 2 ? nh * lp + u : -1;
+}
+
+// ---------------------------------------------------------------- head weight records
+// The packed FMAs of a 1x1 head that reads its weights from LDS records (the fused kernel's VALU
+// head in fwd_syn.hip, the training forward's t_head_fwd in train.hip).  A hidden unit's record
+// is 16 floats, its fields dense from slot 0: w0[0..CIN), b0, w1[0..CMID), read back as whole
+// 128-bit vectors.  Both halves of an FMA are d = fma(w, x, c) with the weight w one half of an
+// aligned register pair, selected by op_sel / op_sel_hi, so a weight is used where its
+// ds_read_b128 left it (a plain f2(w) splat of the dword in slot 3 or 7 of a dense record is
+// copied into a fresh pair first: one v_mov_b32 in ten of the head's vector instructions).
+// They are written as few, long statements: the compiler cannot see into a statement, and
+// wherever one reads a register that an earlier one wrote with no instruction of its own in
+// between, it pads a wait state (s_nop) that the hardware does not need.  Inside a statement
+// nothing is padded, and between the statements of a unit stand the next record's reads.
+typedef float f4v __attribute__((ext_vector_type(4)));
+// the aligned register pair that holds slot S of a record read as N vectors; the slot is its
+// half S & 1 (S past the record: pair 0, for operands that are never named)
+template <int S, int N>
+__device__ __forceinline__ f2 rec_pair(const f4v (&v)[N])
+{
+    constexpr int s = S < 4 * N ? S : 0;
+    return __builtin_shufflevector(v[s / 4], v[s / 4], s & 2, (s & 2) + 1);
+}
+// the four pairs that hold w0[0..8) of a record, as head_hidden2 takes them
+template <int CIN, int N>
+__device__ __forceinline__ void rec_w0_pairs(const f4v (&v)[N], f2 (&w)[4])
+{
+    w[0] = rec_pair<0>(v);
+    w[1] = rec_pair<(CIN >= 3 ? 2 : 0)>(v);
+    w[2] = rec_pair<(CIN >= 5 ? 4 : 0)>(v);
+    w[3] = rec_pair<(CIN >= 7 ? 6 : 0)>(v);
+}
+// head_hidden2: the hidden chain of one unit on two pixel pairs, per pair as it always was:
+// the bias (half CIN & 1 of the pair b), then the CIN products in order, w0[k] being half
+// k & 1 of the pair w[k / 2], the last one clamped to [0, 1] with RELU (the scaled ReLU).
+// The two pairs' chains alternate.
+#define CCMI_HS0(CL)                                                                                      \
+    "v_pk_fma_f32 %[a0], %[w0], %[x00], %[b] op_sel:[0,0,%[bh]] op_sel_hi:[0,1,%[bh]]" CL "\n\t"          \
+    "v_pk_fma_f32 %[a1], %[w0], %[x10], %[b] op_sel:[0,0,%[bh]] op_sel_hi:[0,1,%[bh]]" CL "\n\t"
+#define CCMI_HS(K, P, H, CL)                                                                              \
+    "v_pk_fma_f32 %[a0], %[w" #P "], %[x0" #K "], %[a0] op_sel:[" #H ",0,0] op_sel_hi:[" #H ",1,1]" CL "\n\t" \
+    "v_pk_fma_f32 %[a1], %[w" #P "], %[x1" #K "], %[a1] op_sel:[" #H ",0,0] op_sel_hi:[" #H ",1,1]" CL "\n\t"
+#define CCMI_HPRE1 CCMI_HS0("")
+#define CCMI_HPRE2 CCMI_HPRE1 CCMI_HS(1, 0, 1, "")
+#define CCMI_HPRE3 CCMI_HPRE2 CCMI_HS(2, 1, 0, "")
+#define CCMI_HPRE4 CCMI_HPRE3 CCMI_HS(3, 1, 1, "")
+#define CCMI_HPRE5 CCMI_HPRE4 CCMI_HS(4, 2, 0, "")
+#define CCMI_HPRE6 CCMI_HPRE5 CCMI_HS(5, 2, 1, "")
+#define CCMI_HPRE7 CCMI_HPRE6 CCMI_HS(6, 3, 0, "")
+#define CCMI_HCHAIN1(CL) CCMI_HS0(CL)
+#define CCMI_HCHAIN2(CL) CCMI_HPRE1 CCMI_HS(1, 0, 1, CL)
+#define CCMI_HCHAIN3(CL) CCMI_HPRE2 CCMI_HS(2, 1, 0, CL)
+#define CCMI_HCHAIN4(CL) CCMI_HPRE3 CCMI_HS(3, 1, 1, CL)
+#define CCMI_HCHAIN5(CL) CCMI_HPRE4 CCMI_HS(4, 2, 0, CL)
+#define CCMI_HCHAIN6(CL) CCMI_HPRE5 CCMI_HS(5, 2, 1, CL)
+#define CCMI_HCHAIN7(CL) CCMI_HPRE6 CCMI_HS(6, 3, 0, CL)
+#define CCMI_HCHAIN8(CL) CCMI_HPRE7 CCMI_HS(7, 3, 1, CL)
+template <int CIN, bool RELU>
+__device__ __forceinline__ void head_hidden2(const f2 (&w)[4], f2 b, const f2 (&x0)[CIN], const f2 (&x1)[CIN], f2 &a0, f2 &a1)
+{
+    static_assert(CIN >= 1 && CIN <= 8, "hidden chain length");
+    constexpr int L = CIN - 1;
+    auto X = [](int k) constexpr { return k < L ? k : L; }; // (operands past the chain's end are not named in its string)
+    // the results are early-clobber: the chain writes them while it still has operands to read
+#define CCMI_HOPS                                                                                         \
+    : [a0] "=&v"(a0), [a1] "=&v"(a1)                                                                      \
+    : [w0] "v"(w[0]), [w1] "v"(w[1]), [w2] "v"(w[2]), [w3] "v"(w[3]), [b] "v"(b), [bh] "n"(CIN & 1),      \
+      [x00] "v"(x0[0]), [x01] "v"(x0[X(1)]), [x02] "v"(x0[X(2)]), [x03] "v"(x0[X(3)]), [x04] "v"(x0[X(4)]), \
+      [x05] "v"(x0[X(5)]), [x06] "v"(x0[X(6)]), [x07] "v"(x0[X(7)]),                                      \
+      [x10] "v"(x1[0]), [x11] "v"(x1[X(1)]), [x12] "v"(x1[X(2)]), [x13] "v"(x1[X(3)]), [x14] "v"(x1[X(4)]), \
+      [x15] "v"(x1[X(5)]), [x16] "v"(x1[X(6)]), [x17] "v"(x1[X(7)])
+#define CCMI_HCASE(N)                                                                                     \
+    if constexpr (CIN == N) {                                                                             \
+        if constexpr (RELU) asm volatile(CCMI_HCHAIN##N(" clamp") CCMI_HOPS);                             \
+        else asm volatile(CCMI_HCHAIN##N("") CCMI_HOPS);                                                  \
+    }
+    CCMI_HCASE(1) CCMI_HCASE(2) CCMI_HCASE(3) CCMI_HCASE(4) CCMI_HCASE(5) CCMI_HCASE(6) CCMI_HCASE(7) CCMI_HCASE(8)
+#undef CCMI_HCASE
+#undef CCMI_HOPS
+}
+#undef CCMI_HCHAIN1
+#undef CCMI_HCHAIN2
+#undef CCMI_HCHAIN3
+#undef CCMI_HCHAIN4
+#undef CCMI_HCHAIN5
+#undef CCMI_HCHAIN6
+#undef CCMI_HCHAIN7
+#undef CCMI_HCHAIN8
+#undef CCMI_HPRE1
+#undef CCMI_HPRE2
+#undef CCMI_HPRE3
+#undef CCMI_HPRE4
+#undef CCMI_HPRE5
+#undef CCMI_HPRE6
+#undef CCMI_HPRE7
+#undef CCMI_HS
+#undef CCMI_HS0
+// head_out2: one output channel's FMAs of a unit on two pixel pairs, o += w1 h with w1 = half H
+// of the pair w
+template <int H>
+__device__ __forceinline__ void head_out2(f2 w, f2 h0, f2 h1, f2 &o0, f2 &o1)
+{
+    asm volatile("v_pk_fma_f32 %[o0], %[w], %[h0], %[o0] op_sel:[%[h],0,0] op_sel_hi:[%[h],1,1]\n\t"
+                 "v_pk_fma_f32 %[o1], %[w], %[h1], %[o1] op_sel:[%[h],0,0] op_sel_hi:[%[h],1,1]"
+                 : [o0] "+v"(o0), [o1] "+v"(o1)
+                 : [w] "v"(w), [h0] "v"(h0), [h1] "v"(h1), [h] "n"(H));
+}
+
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>), in order
+template <int N, class F>
+__device__ __forceinline__ void static_for(F &&f)
+{
+    if constexpr (N > 0) {
+        static_for<N - 1>(f);
+        f(std::integral_constant<int, N - 1>{});
+    }
 }
 
 // ---------------------------------------------------------------- synthesis plan

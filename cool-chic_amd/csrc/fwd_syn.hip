@@ -224,17 +224,24 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
 #if defined(CCMI_ARM_STAMPS)
     unsigned long long t_prev = __builtin_amdgcn_s_memtime();
 #endif
-    // head hidden unit j as 16 floats: w0[j][0..CIN), b0[j], w1[0..CMID)[j]; read back as
-    // four broadcast ds_read_b128 (all lanes, one address) -- the loads are issued well
-    // ahead of use, unlike the SGPR path whose scalar loads the compiler waits on at once
+    // head hidden unit j as a record of 16 floats, its fields dense from slot 0: w0[j][0..CIN),
+    // b0[j], w1[0..CMID)[j].  The VALU head reads a record back as kRecVecs broadcast
+    // ds_read_b128 (all lanes, one address; three for up to 12 fields: hop has 11), issued a
+    // unit ahead of use, unlike the SGPR path whose scalar loads the compiler waits on at once.
+    // The slots behind the fields are read with the last vector but are never operands.
+    // An LDS read is serviced in lane groups whatever its addresses (identical addresses
+    // only remove bank conflicts inside a group): a ds_read_b128 takes 4 LDS-array cycles per
+    // wave, a ds_read_b96 or a ds_read2_b64 takes 8, and the four SIMDs of a CU share the
+    // array.  So the reads must stay whole 128-bit ones: from a record that skipped every
+    // fourth slot (to spare the compiler's copy of a broadcast operand out of an odd dword)
+    // the compiler read three ds_read_b96 and half a ds_read2_b64 per unit, 28 array cycles
+    // against 12 here, more than the unit's 80 VALU cycles on each of four SIMDs leave room
+    // for.  The operands are taken in place by op_sel instead (head_hidden2 / head_out2,
+    // fwd_common.h).
     float(*s_head)[16] = reinterpret_cast<float(*)[16]>(s_pool + kBuf0);
     float *s_w1p = s_pool + kBuf0 + kMaxHid * 16; // MH: the second layer's weights by lane row
     static_assert(CIN + 1 + CMID <= 16, "hidden-unit record");
-    // field f of a record sits at slot hr(f): slots 3, 7, 11, 15 (the last dword of each
-    // ds_read_b128) stay empty when the fields fit without them, because the compiler
-    // copies a broadcast operand out of that position into a fresh register pair first
-    constexpr bool kPadRec = CIN + 1 + CMID <= 12;
-    auto hr = [](int f) constexpr { return kPadRec ? f + f / 3 : f; };
+    constexpr int kRecVecs = (CIN + 1 + CMID + 3) / 4;
 
     // XCD-aware order of the runs (raster order, frame after frame, a contiguous stretch per
     // XCD): neighbouring strips re-read each other's halo columns from one L2
@@ -311,7 +318,7 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
             const int i = tid + k * kFThreads, j = i >> 4, f = i & 15;
             float v = 0.f;
             if (i < kMaxHid * 16 && A.n_head == 2 && j < A.hid) {
-                // the unrolled VALU head's records carry the scaled-ReLU exponents (see unit()):
+                // the unrolled VALU head's records carry the scaled-ReLU exponents ("Scaled ReLU" below):
                 // hidden weights / bias x 2^-32, output weights x 2^32 -- exact power-of-two scalings
                 if (f < CIN) v = prm[A.w0_off + j * CIN + f] * kW0Scale;
                 else if (f == CIN) v = prm[A.b0_off + j] * kW0Scale;
@@ -325,7 +332,7 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
 #pragma unroll
         for (int k = 0; k < kHeadRegs; ++k) {
             const int i = tid + k * kFThreads, j = i >> 4, f = i & 15;
-            if (i < kMaxHid * 16 && f <= CIN + CMID) s_head[j][hr(f)] = hv[k]; // other slots are never operands
+            if (i < kMaxHid * 16 && f <= CIN + CMID) s_head[j][f] = hv[k]; // other slots are never operands
         }
         if constexpr (MH) {
             // [tile][lane row][m][4 units]: the second layer's weights of the 4 hidden units a
@@ -768,7 +775,7 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
 #pragma unroll
                 for (int k = 0; k < 2; ++k) {
                     const int ch = 4 * k + lg;
-                    a1[mt][k] = ch <= CIN ? s_head[16 * mt + lr][hr(ch < CIN ? ch : CIN)] : 0.f;
+                    a1[mt][k] = ch <= CIN ? s_head[16 * mt + lr][ch] : 0.f; // slot CIN: the bias
                 }
             const f2 lo0 = f2(A.relu0 ? 0.f : -INFINITY);
             const float lo1 = A.relu1 ? 0.f : -INFINITY;
@@ -844,9 +851,8 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
                 for (int m = 0; m < CMID; ++m) op[q][m] = f2(0.f);
             }
             __syncthreads(); // s_head staged
-            // software pipelined: the record of unit j+2 is loaded while unit j+1 computes
-            typedef float f4v __attribute__((ext_vector_type(4)));
-            struct Rec { f4v v[4]; };
+            // software pipelined: the record of unit j+1 is loaded while unit j computes
+            struct Rec { f4v v[kRecVecs]; };
             // records through an LDS pointer the compiler cannot fold to a constant, so the
             // unrolled reads are base + immediate offset (not one v_mov of an address each)
             typedef const __attribute__((address_space(3))) f4v *lds_f4;
@@ -854,7 +860,10 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
             asm volatile("" : "+v"(hb));
             auto load = [&](int j) {
                 const lds_f4 p = hb + 4 * (j < hid ? j : hid - 1);
-                return Rec{{p[0], p[1], p[2], p[3]}};
+                Rec r;
+#pragma unroll
+                for (int i = 0; i < kRecVecs; ++i) r.v[i] = p[i];
+                return r;
             };
             // Scaled ReLU: the records hold w0, b0 x 2^-32 and w1 x 2^32 (stage_head), so the
             // hidden pre-activation arrives as h 2^-32 and max(h, 0) is the last fma's
@@ -868,36 +877,58 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
             // loses bits as a subnormal (its term is below 2^-94 |w1|), a larger positive h is
             // clamped to 2^32.  Decoder weights and activations are far inside both limits.
             const f2 lo0 = f2(A.relu0 ? 0.f : -INFINITY); // the generic head's ReLU (max)
-            auto unit = [&](const Rec &r) {
-                constexpr bool RELU = kScaledRelu;
-                const float *u = reinterpret_cast<const float *>(r.v);
-                const f2 bj = f2(u[hr(CIN)]);
-                constexpr int kl = hr(CIN - 1), kp = kl & ~1; // the last hidden weight and its aligned pair
-                const f2 wl = f2{u[kp], u[kp + 1]};
+            // One unit on the thread's pixel pairs, two pairs at a time.  Per pair the chain is
+            // what it always was: the bias, the CIN products in order, the clamp on the last
+            // (hidden), then the CMID output FMAs (outs).
+            constexpr bool RELU = kScaledRelu;
+            constexpr int NQ = NR / 2;
+            static_assert(NQ % 2 == 0, "the head's statements take two pixel pairs");
+            auto hidden = [&](const Rec &r, f2(&h)[NQ]) __attribute__((always_inline)) {
+                f2 w[4];
+                rec_w0_pairs<CIN>(r.v, w);
 #pragma unroll
-                for (int q = 0; q < NR / 2; ++q) {
-                    f2 acc = bj;
-#pragma unroll
-                    for (int k = 0; k < CIN - 1; ++k) acc = __builtin_elementwise_fma(f2(u[hr(k)]), xp[q][k], acc);
-                    if constexpr (RELU) {
-                        f2 h;
-                        if constexpr ((kl & 1) == 0)
-                            asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[0,1,1] clamp" : "=v"(h) : "v"(wl), "v"(xp[q][CIN - 1]), "v"(acc));
-                        else
-                            asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,1,1] clamp" : "=v"(h) : "v"(wl), "v"(xp[q][CIN - 1]), "v"(acc));
-                        acc = h;
-                    } else {
-                        acc = __builtin_elementwise_fma(f2(u[kl]), xp[q][CIN - 1], acc);
-                        acc = __builtin_elementwise_max(acc, lo0);
+                for (int q = 0; q < NQ; q += 2) {
+                    head_hidden2<CIN, RELU>(w, rec_pair<CIN>(r.v), xp[q], xp[q + 1], h[q], h[q + 1]);
+                    if constexpr (!RELU) {
+                        h[q] = __builtin_elementwise_max(h[q], lo0);
+                        h[q + 1] = __builtin_elementwise_max(h[q + 1], lo0);
                     }
-#pragma unroll
-                    for (int m = 0; m < CMID; ++m) op[q][m] = __builtin_elementwise_fma(f2(u[hr(CIN + 1 + m)]), acc, op[q][m]);
                 }
             };
-            if constexpr (HID > 0) {
+            auto outs = [&](const Rec &r, const f2(&h)[NQ]) __attribute__((always_inline)) {
+                static_for<CMID>([&](auto mc) __attribute__((always_inline)) {
+                    constexpr int m = decltype(mc)::value, S = CIN + 1 + m;
 #pragma unroll
-                for (int j = 0; j < HID; ++j) unit(load(j));
+                    for (int q = 0; q < NQ; q += 2) head_out2<S & 1>(rec_pair<S>(r.v), h[q], h[q + 1], op[q][m], op[q + 1][m]);
+                });
+            };
+            if constexpr (HID > 0) {
+                // Unrolled.  The reads are placed by hand (an LDS read does not move across a
+                // volatile statement): the vectors of the next record that hold w0 and the bias
+                // before the unit's hidden chain, its others between the chain and the outputs.
+                constexpr int kHidVecs = CIN / 4 + 1;
+                auto read = [&](Rec &r, int j, int v0, int v1) __attribute__((always_inline)) {
+#pragma unroll
+                    for (int i = v0; i < v1; ++i) r.v[i] = hb[4 * j + i];
+                };
+                Rec cur, nxt;
+                read(cur, 0, 0, kRecVecs);
+                nxt = cur;
+#pragma unroll
+                for (int j = 0; j < HID; ++j) {
+                    f2 h[NQ];
+                    if (j + 1 < HID) read(nxt, j + 1, 0, kHidVecs);
+                    hidden(cur, h);
+                    if (j + 1 < HID) read(nxt, j + 1, kHidVecs, kRecVecs);
+                    outs(cur, h);
+                    cur = nxt;
+                }
             } else {
+                auto unit = [&](const Rec &r) __attribute__((always_inline)) {
+                    f2 h[NQ];
+                    hidden(r, h);
+                    outs(r, h);
+                };
                 Rec ra = load(0), rb2 = load(1);
                 for (int j = 0; j < hid; j += 2) {
                     unit(ra);

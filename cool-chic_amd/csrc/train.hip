@@ -1016,17 +1016,22 @@ __global__ void t_colsum(const float *__restrict__ part, int nrows, int ncols, f
 // Four pixels per thread (p + u kT of the workgroup's 4 kT, u = 0..3, as two packed pairs):
 // each broadcast weight record serves four pixels, a quarter of the one-pixel form's LDS record
 // traffic per pixel (that form sat 56 % of its wave cycles in SQ_WAIT_INST_LDS, the two-pixel
-// form still 55 %, profiles/r5d_train_pmc.txt).  Record slots 3, 7, 11 stay empty when the
-// fields fit without them (the compiler copies a broadcast operand out of the last dword of a
-// ds_read_b128 first), as in the path-A fused kernel.
+// form still 55 %, profiles/r5d_train_pmc.txt).  The records and the packed FMAs that take
+// their weights in place are the path-A fused kernel's (fwd_common.h, "head weight records"):
+// fields dense from slot 0, read as whole ds_read_b128, a unit of two pixel pairs as one
+// hidden-chain statement and one statement per output channel.
 constexpr int kHeadFwdPx = 4 * kT; // pixels per workgroup
 template <int CIN>
 __global__ __launch_bounds__(kT) void t_head_fwd(const float *__restrict__ dense, Geo g, const float *__restrict__ th,
                                                  int64_t ps, float *__restrict__ z0)
 {
     using ccmi_fwd::f2;
-    constexpr bool kPad = CIN + 4 <= 12;
-    auto hr = [](int f) constexpr { return kPad ? f + f / 3 : f; };
+    using ccmi_fwd::f4v;
+    using ccmi_fwd::head_hidden2;
+    using ccmi_fwd::head_out2;
+    using ccmi_fwd::rec_pair;
+    using ccmi_fwd::rec_w0_pairs;
+    constexpr int kRecVecs = (CIN + 4 + 3) / 4;
     __shared__ __attribute__((aligned(16))) float s_rec[64][16];
     static_assert(CIN + 4 <= 16, "hidden-unit record");
     const int b = blockIdx.y, hid = g.hid;
@@ -1039,7 +1044,7 @@ __global__ __launch_bounds__(kT) void t_head_fwd(const float *__restrict__ dense
             else if (f == CIN) v = P[g.b0 + j];
             else if (f <= CIN + 3) v = P[g.w1 + (f - CIN - 1) * hid + j];
         }
-        if (f <= CIN + 3) s_rec[j][hr(f)] = v;
+        if (f <= CIN + 3) s_rec[j][f] = v; // other slots are never operands
     }
     const int64_t npx = (int64_t)g.H * g.W, p0 = (int64_t)blockIdx.x * kHeadFwdPx + threadIdx.x;
     const float *x = dense + (int64_t)b * CIN * npx;
@@ -1058,18 +1063,36 @@ __global__ __launch_bounds__(kT) void t_head_fwd(const float *__restrict__ dense
     for (int q = 0; q < 2; ++q)
 #pragma unroll
         for (int m = 0; m < 3; ++m) o[q][m] = f2(P[g.b1 + m]);
-#pragma unroll 4
-    for (int j = 0; j < hid; ++j) {
-        const float *r = s_rec[j];
+    struct Rec { f4v v[kRecVecs]; };
+    // (through an LDS pointer the compiler cannot fold to a constant: base + immediate offsets)
+    typedef const __attribute__((address_space(3))) f4v *lds_f4;
+    lds_f4 hb = (lds_f4)(&s_rec[0][0]);
+    asm volatile("" : "+v"(hb));
+    auto load = [&](int j) {
+        const lds_f4 p = hb + 4 * (j < 63 ? j : 63);
+        Rec r;
 #pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            f2 h = f2(r[hr(CIN)]);
-#pragma unroll
-            for (int i = 0; i < CIN; ++i) h = __builtin_elementwise_fma(f2(r[hr(i)]), xv[q][i], h);
-            h = __builtin_elementwise_max(h, lo0);
-#pragma unroll
-            for (int m = 0; m < 3; ++m) o[q][m] = __builtin_elementwise_fma(f2(r[hr(CIN + 1 + m)]), h, o[q][m]);
-        }
+        for (int i = 0; i < kRecVecs; ++i) r.v[i] = p[i];
+        return r;
+    };
+    auto unit = [&](const Rec &r) __attribute__((always_inline)) {
+        f2 w[4], h[2];
+        rec_w0_pairs<CIN>(r.v, w);
+        head_hidden2<CIN, false>(w, rec_pair<CIN>(r.v), xv[0], xv[1], h[0], h[1]);
+        h[0] = __builtin_elementwise_max(h[0], lo0);
+        h[1] = __builtin_elementwise_max(h[1], lo0);
+        head_out2<(CIN + 1) & 1>(rec_pair<CIN + 1>(r.v), h[0], h[1], o[0][0], o[1][0]);
+        head_out2<(CIN + 2) & 1>(rec_pair<CIN + 2>(r.v), h[0], h[1], o[0][1], o[1][1]);
+        head_out2<(CIN + 3) & 1>(rec_pair<CIN + 3>(r.v), h[0], h[1], o[0][2], o[1][2]);
+    };
+    // software pipelined: the records of units j + 2 and j + 3 are read while units j and j + 1
+    // compute (an LDS read does not move across the units' statements)
+    Rec ra = load(0), rb = load(1);
+    for (int j = 0; j < hid; j += 2) {
+        unit(ra);
+        ra = load(j + 2);
+        if (j + 1 < hid) unit(rb);
+        rb = load(j + 3);
     }
     float *z = z0 + (int64_t)b * 3 * npx;
 #pragma unroll
