@@ -10,7 +10,8 @@
 //
 // Layout: one workgroup (256 threads, 4 waves) owns a (4 NL) x 64 tile of one grid of one
 // frame.  The quantised tile plus its causal halo (4 rows above, 4 columns either
-// side) is staged once in LDS; each thread evaluates the MLP for NL = 2 latents of the
+// side) is staged once in LDS, a wave taking whole rows of it through buffer descriptors made on
+// the scalar unit (arm_stage_tile); each thread evaluates the MLP for NL = 2 latents of the
 // same column as one packed pair, so every weight (wave-uniform, held in SGPRs via
 // scalar loads) feeds one v_pk_fma_f32 (two FMAs).  NL = 4 (two pairs per weight) was
 // measured 13 % slower: 132 VGPRs, 3 waves per SIMD instead of 7.  LDS reads are lane-consecutive (conflict-free).  Grids of all resolutions
@@ -48,12 +49,63 @@ constexpr int kLH = kTY + kHalo;              // 12
 // scaled ReLU of the pairs form: activations travel times 2^-32
 constexpr float kArmDown = 0x1p-32f, kArmUp = 0x1p+32f;
 
+// floor(n / d) for 0 <= n < 2^31 and 1 <= d < 2^31 as a multiply-high and a shift, so that a
+// wave-uniform division stays on the scalar unit (s_mul_hi_u32; the compiler expands n / d into a
+// float reciprocal on the VALU).  Granlund and Montgomery's constants for 31-bit n: with
+// L = ceil(log2 d) and m = ceil(2^(31 + L) / d), which is in [2^31, 2^32), m d = 2^(31 + L) + e with
+// 0 <= e < d <= 2^L, so n m / 2^(31 + L) = n / d + n e / (d 2^(31 + L)) and the second term is below
+// 1 / d: the floors agree.  (2 n) m >> 32 >> L is that floor, and 2 n < 2^32.  Exact over the whole
+// range; ccmi_launch_arm_f32 refuses a launch with 2^31 tiles or more.
+struct ArmDiv {
+    unsigned m, s;
+};
+inline ArmDiv arm_div_of(unsigned d)
+{
+    unsigned L = 0;
+    while ((1u << L) < d) ++L;
+    return ArmDiv{(unsigned)(((1ull << (31 + L)) + d - 1) / d), L};
+}
+__host__ __device__ __forceinline__ unsigned arm_div(unsigned n, ArmDiv d)
+{
+    return (unsigned)(((uint64_t)(n << 1) * d.m) >> 32) >> d.s;
+}
+
 struct ArmGeom {
     int n;
     int h[CCMI_MAX_GRIDS], w[CCMI_MAX_GRIDS], off[CCMI_MAX_GRIDS];
     int tiles_x[CCMI_MAX_GRIDS];
-    int tile_start[CCMI_MAX_GRIDS + 1];
+    int tile_start[CCMI_MAX_GRIDS];  // first tile of a grid in its frame; INT32_MAX past the last grid
+    int ntl;                         // tiles of a frame
+    ArmDiv by_ntl, by_tiles_x[CCMI_MAX_GRIDS];
 };
+
+// The tile a workgroup owns: grid l of frame b, rows y0.., columns x0.. of its H x W latents;
+// wave and lane of the thread (the wave as a scalar) and what staging leaves for the stores.
+struct ArmTile {
+    int b, l, H, W, y0, x0;
+    int wave, lane, xm;  // xm: the lane's first staged column, x0 - kHalo + lane
+};
+
+// Tile wt of a launch (the frames' tiles one after the other, a frame's by grid, a grid's row by
+// row).  Everything is wave-uniform 32-bit arithmetic, so on the device it runs on the scalar unit.
+__host__ __device__ __forceinline__ ArmTile arm_tile_of(const ArmGeom &g, unsigned wt)
+{
+    ArmTile T{};
+    T.b = (int)arm_div(wt, g.by_ntl);
+    const int t = (int)(wt - (unsigned)T.b * (unsigned)g.ntl);
+    // the starts rise strictly (a grid has a tile) and those past the last grid are INT32_MAX
+    int l = 0;
+#pragma unroll
+    for (int k = 1; k < CCMI_MAX_GRIDS; ++k) l += (int)((unsigned)(g.tile_start[k] - 1 - t) >> 31); // t >= start
+    const unsigned lt = (unsigned)(t - g.tile_start[l]);
+    const unsigned ty = arm_div(lt, g.by_tiles_x[l]);
+    T.l = l;
+    T.H = g.h[l];
+    T.W = g.w[l];
+    T.y0 = (int)ty * kTY;
+    T.x0 = (int)(lt - ty * (unsigned)g.tiles_x[l]) * kTX;
+    return T;
+}
 
 // Context pixel offsets (dy, dx) in the reference's gather order: flattened 9x9
 // mask index k -> (k / 9 - 4, k % 9 - 4) for the indices of arm.py:373-506.
@@ -86,82 +138,131 @@ __device__ __forceinline__ float laplace_cdf(float x, float mu, float inv_scale)
     return 0.5f - 0.5f * sg * (__expf(-fabsf(s) * inv_scale) - 1.f);
 }
 
-// The tile a workgroup owns: grid l of frame b, rows y0.., columns x0.. of its H x W latents.
-struct ArmTile {
-    int b, l, H, W, y0, x0;
-};
+// A frame's latents at most: the stores address an output of grid l as a wave-uniform base plus
+// a 32-bit byte offset
+constexpr int64_t kArmMaxLatents = (int64_t)1 << 30;
 
 // Finds the workgroup's tile and stages it, quantised, with its causal halo in LDS.  SC: the
 // quantised values are stored times 2^-32 (arm_fwd_pairs_kernel's scaled ReLU).
+//
+// A wave owns the rows wave, wave + 4, ... of the kLH x kLW tile: lane = column for the first 64
+// columns, and lanes 0 .. kLW - 65 take the remaining columns in a second load per row.  A load
+// goes through a buffer descriptor made on the scalar unit: the W floats of the row for the first
+// load, the (at most) kLW - 64 floats from column x0 + 60 on that the image still has for the
+// second, and no records at all for a row outside the image.  The hardware's range check then
+// gives 0 for every column outside the image and touches no memory for it, and no load has a
+// predicate, a branch or 64-bit address arithmetic of its own.
 template <bool SC = false>
 __device__ __forceinline__ ArmTile arm_stage_tile(float (&tile)[kLH][kLW], const float *__restrict__ lat,
                                                   int64_t lat_stride, const ArmGeom &g, float gain, int quantize)
 {
+    constexpr int kWaves = kThreads / 64, NR = kLH / kWaves, XC = kLW - 64;
+    static_assert(kLH % kWaves == 0 && XC >= 0 && XC <= 64, "whole rows per wave, at most two loads per row");
     // XCD-aware tile order (ccmi_fwd::xcd_order): vertically adjacent tiles, which share the
     // 4 causal halo rows, meet in one L2
-    const int wt = ccmi_fwd::xcd_order(blockIdx.x, gridDim.x);
-    const int ntl = g.tile_start[g.n];
-    ArmTile T;
-    T.b = wt / ntl;
-    const int t = wt - T.b * ntl;
-    int l = 0;
-#pragma unroll
-    for (int k = 1; k < CCMI_MAX_GRIDS; ++k)
-        if (k < g.n && t >= g.tile_start[k]) l = k;
-    const int lt = t - g.tile_start[l];
-    T.l = l;
-    T.H = g.h[l];
-    T.W = g.w[l];
-    T.y0 = (lt / g.tiles_x[l]) * kTY;
-    T.x0 = (lt % g.tiles_x[l]) * kTX;
-    const int H = T.H, W = T.W, y0 = T.y0, x0 = T.x0;
-    const float *src = lat + (int64_t)T.b * lat_stride + g.off[l];
+    ArmTile T = arm_tile_of(g, (unsigned)ccmi_fwd::xcd_order(blockIdx.x, gridDim.x));
+    T.wave = __builtin_amdgcn_readfirstlane(threadIdx.x / 64);
+    T.lane = threadIdx.x % 64;
+    const float *src = lat + (int64_t)T.b * lat_stride + g.off[T.l];
 
-    // fixed trip count, unrolled: every load of the thread is in flight before the first
-    // LDS store waits on one
-    {
-        constexpr int NU = (kLH * kLW + kThreads - 1) / kThreads;
-        float lv[NU];
+    // a column left of the image goes past every row's records (with room for the four bytes of
+    // the access), one at or past W is past them as it is
+    T.xm = T.x0 - kHalo + T.lane;
+    const unsigned col = 4u * (unsigned)max(T.xm, -2), colx = 4u * (unsigned)T.lane;
+    const int xx = min(T.x0 - kHalo + 64, T.W); // the second loads' first column (x0 + 60: never negative)
+    // every load of the thread is in flight before the first LDS store waits on one
+    float lv[NR], lx[NR];
 #pragma unroll
-        for (int u = 0; u < NU; ++u) {
-            const int i = threadIdx.x + u * kThreads;
-            const int r = i / kLW, c = i - r * kLW;
-            const int y = y0 - kHalo + r, x = x0 - kHalo + c;
-            lv[u] = (i < kLH * kLW && y >= 0 && y < H && x >= 0 && x < W) ? src[y * W + x] : 0.f;
-        }
+    for (int k = 0; k < NR; ++k) {
+        const int y = T.y0 - kHalo + T.wave + k * kWaves;
+        const bool in = (unsigned)y < (unsigned)T.H;
+        float *at = const_cast<float *>(src + (in ? y * T.W : 0));
+        lv[k] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
+            __builtin_amdgcn_make_buffer_rsrc(at, 0, in ? 4 * T.W : 0, 0x00020000), col, 0, 0));
+        // the row's XC columns from xx on, as far as the image goes: lanes XC and up read nothing
+        if constexpr (XC > 0)
+            lx[k] = __uint_as_float(__builtin_amdgcn_raw_buffer_load_b32(
+                __builtin_amdgcn_make_buffer_rsrc(at + (in ? xx : 0), 0, in ? 4 * min(T.W - xx, XC) : 0, 0x00020000), colx,
+                0, 0));
+    }
+    const auto quantised = [&](float v) {
+        if constexpr (SC) return rintf(gain * v) * kArmDown;
+        else return quantize ? rintf(gain * v) : v;
+    };
+    float *dst = &tile[T.wave][T.lane];
 #pragma unroll
-        for (int u = 0; u < NU; ++u) {
-            const int i = threadIdx.x + u * kThreads;
-            if constexpr (SC) {
-                if (i < kLH * kLW) tile[i / kLW][i % kLW] = rintf(gain * lv[u]) * kArmDown;
-            } else {
-                if (i < kLH * kLW) tile[i / kLW][i % kLW] = quantize ? rintf(gain * lv[u]) : lv[u];
-            }
+    for (int k = 0; k < NR; ++k) dst[k * kWaves * kLW] = quantised(lv[k]);
+    if constexpr (XC > 0) {
+        // (the second loads stay up there: left alone, the compiler sinks them into this branch,
+        // behind the waits of the stores above)
+#pragma unroll
+        for (int k = 0; k < NR; ++k) asm volatile("" : "+v"(lx[k]));
+        if (T.lane < XC) {
+#pragma unroll
+            for (int k = 0; k < NR; ++k) dst[k * kWaves * kLW + 64] = quantised(lx[k]);
         }
     }
     __syncthreads();
     return T;
 }
 
-// Scale, rate and the stores of the thread's latent n (row cy0 + n * kRowsPerPass of the tile)
-// from its mu mn and log-scale lsn; q is the latent's own quantised value.
-__device__ __forceinline__ void arm_emit(const ArmTile &T, const ArmGeom &g, int n, float mn, float lsn, float q,
-                                         float *__restrict__ o_mu, float *__restrict__ o_scale,
-                                         float *__restrict__ o_log_scale, float *__restrict__ o_rate, int64_t ostride)
+// The context gather: the byte offset in the tile of the top row that latent n of the thread
+// (row wave + n * kRowsPerPass) reads, at the thread's own column, and the context value at
+// (dy, dx) from it.  The offset is opaque, one register per latent: every read is then that
+// register plus a constant that a ds_read2_b32 can hold, where from one base for both latents the
+// compiler makes a new base register for most pairs of reads.
+template <int D>
+constexpr int arm_ctx_rows = D <= 16 ? 3 : 4; // rows above its own that a context of D reaches
+template <int D>
+__device__ __forceinline__ unsigned arm_ctx_base(const ArmTile &T, int n)
 {
-    const int y = T.y0 + threadIdx.x / kTX + n * kRowsPerPass, x = T.x0 + threadIdx.x % kTX;
-    if (y < T.H && x < T.W) {
+    unsigned at = 4u * (unsigned)((T.wave + n * kRowsPerPass + kHalo - arm_ctx_rows<D>) * kLW + T.lane);
+    asm volatile("" : "+v"(at));
+    return at;
+}
+template <int D>
+__device__ __forceinline__ float arm_ctx_at(const float (&tile)[kLH][kLW], unsigned base, int dy, int dx)
+{
+    return *(const float *)((const char *)&tile[0][0] + base + 4u * (unsigned)((arm_ctx_rows<D> + dy) * kLW + kHalo + dx));
+}
+
+// Where a thread's outputs go: the requested outputs of the tile's frame and grid (wave-uniform,
+// null where not asked for), the byte offset of the thread's first latent in them and whether
+// its column is inside the image.
+struct ArmOut {
+    float *mu, *scale, *log_scale, *rate;
+    unsigned at;
+    bool col;
+};
+__device__ __forceinline__ ArmOut arm_out_of(const ArmTile &T, const ArmGeom &g, float *__restrict__ o_mu,
+                                             float *__restrict__ o_scale, float *__restrict__ o_log_scale,
+                                             float *__restrict__ o_rate, int64_t ostride)
+{
+    const int64_t base = (int64_t)T.b * ostride + g.off[T.l];
+    const int x = T.xm + kHalo;
+    return ArmOut{o_mu ? o_mu + base : nullptr, o_scale ? o_scale + base : nullptr,
+                  o_log_scale ? o_log_scale + base : nullptr, o_rate ? o_rate + base : nullptr,
+                  4u * (unsigned)((T.y0 + T.wave) * T.W + x), x < T.W};
+}
+__device__ __forceinline__ float *arm_at(float *base, unsigned byte) { return (float *)((char *)base + byte); }
+
+// Scale, rate and the stores of the thread's latent n (row wave + n * kRowsPerPass of the tile)
+// from its mu mn and log-scale lsn; q is the latent's own quantised value.
+__device__ __forceinline__ void arm_emit(const ArmTile &T, const ArmOut &O, int n, float mn, float lsn, float q)
+{
+    const int y = T.y0 + T.wave + n * kRowsPerPass;
+    if (y < T.H && O.col) {
         // v_exp_f32 / v_log_f32 directly (the clamped exponent and p in [2^-16, 1] are far
         // from the ranges the library forms guard; errors well inside the rate tolerance)
         const float sc = __expf(fminf(fmaxf(lsn - 4.f, -4.6f), 5.0f));
-        const int64_t idx = (int64_t)T.b * ostride + g.off[T.l] + y * T.W + x;
-        if (o_mu) o_mu[idx] = mn;
-        if (o_scale) o_scale[idx] = sc;
-        if (o_log_scale) o_log_scale[idx] = lsn;
-        if (o_rate) {
+        const unsigned at = O.at + 4u * (unsigned)(n * kRowsPerPass * T.W);
+        if (O.mu) *arm_at(O.mu, at) = mn;
+        if (O.scale) *arm_at(O.scale, at) = sc;
+        if (O.log_scale) *arm_at(O.log_scale, at) = lsn;
+        if (O.rate) {
             const float is = __builtin_amdgcn_rcpf(sc);
             const float pr = fmaxf(laplace_cdf(q + 0.5f, mn, is) - laplace_cdf(q - 0.5f, mn, is), 1.52587890625e-05f);
-            o_rate[idx] = -__log2f(pr);
+            *arm_at(O.rate, at) = -__log2f(pr);
         }
     }
 }
@@ -178,13 +279,15 @@ __global__ __launch_bounds__(kThreads) void arm_fwd_kernel(
     const ArmTile T = arm_stage_tile(tile, lat, lat_stride, g, gain, quantize);
 
     const cfloat_ptr p = (cfloat_ptr)(size_t)(params + (int64_t)T.b * pstride);
-    const int cx = threadIdx.x % kTX;
-    const int cy0 = threadIdx.x / kTX;
+    const ArmOut O = arm_out_of(T, g, o_mu, o_scale, o_log_scale, o_rate, ostride);
 
     // the two latents of a thread travel as one packed pair (v_pk_fma_f32): every
     // wave-uniform weight feeds both with one instruction
-    // pair q = rows cy0 + (2q) * kRowsPerPass and cy0 + (2q + 1) * kRowsPerPass
+    // pair q = rows wave + (2q) * kRowsPerPass and wave + (2q + 1) * kRowsPerPass
     static_assert(kNL % 2 == 0, "packed pair layout");
+    unsigned cb[kNL];
+#pragma unroll
+    for (int n = 0; n < kNL; ++n) cb[n] = arm_ctx_base<D>(T, n);
     f2 a[kNP][D];
 #pragma unroll
     for (int i = 0; i < D; ++i) {
@@ -192,8 +295,7 @@ __global__ __launch_bounds__(kThreads) void arm_fwd_kernel(
         ctx_offset<D>(i, dy, dx);
 #pragma unroll
         for (int q = 0; q < kNP; ++q)
-            a[q][i] = f2{tile[cy0 + 2 * q * kRowsPerPass + kHalo + dy][cx + kHalo + dx],
-                         tile[cy0 + (2 * q + 1) * kRowsPerPass + kHalo + dy][cx + kHalo + dx]};
+            a[q][i] = f2{arm_ctx_at<D>(tile, cb[2 * q], dy, dx), arm_ctx_at<D>(tile, cb[2 * q + 1], dy, dx)};
     }
 
     if constexpr (NH >= 0) nh = NH;
@@ -243,8 +345,8 @@ __global__ __launch_bounds__(kThreads) void arm_fwd_kernel(
     }
 #pragma unroll
     for (int n = 0; n < kNL; ++n)
-        arm_emit(T, g, n, (n & 1) ? m[n >> 1].y : m[n >> 1].x, (n & 1) ? ls[n >> 1].y : ls[n >> 1].x,
-                 tile[cy0 + n * kRowsPerPass + kHalo][cx + kHalo], o_mu, o_scale, o_log_scale, o_rate, ostride);
+        arm_emit(T, O, n, (n & 1) ? m[n >> 1].y : m[n >> 1].x, (n & 1) ? ls[n >> 1].y : ls[n >> 1].x,
+                 arm_ctx_at<D>(tile, cb[n], 0, 0));
 }
 
 // The transposed copy of every frame's ARM parameters the pairs form reads (layout:
@@ -331,18 +433,20 @@ __global__ __launch_bounds__(kThreads) void arm_fwd_pairs_kernel(
     const ArmTile T = arm_stage_tile<SC>(tile, lat, lat_stride, g, gain, quantize);
 
     const cfloat_ptr P = (cfloat_ptr)(size_t)(packed + (int64_t)T.b * pkstride);
-    const int cx = threadIdx.x % kTX;
-    const int cy0 = threadIdx.x / kTX;
+    const ArmOut O = arm_out_of(T, g, o_mu, o_scale, o_log_scale, o_rate, ostride);
     if constexpr (NH >= 0) nh = NH;
 
-    // a[n][jp] = activations (2 jp, 2 jp + 1) of latent n (row cy0 + n * kRowsPerPass)
+    // a[n][jp] = activations (2 jp, 2 jp + 1) of latent n (row wave + n * kRowsPerPass)
+    unsigned cb[kNL];
+#pragma unroll
+    for (int n = 0; n < kNL; ++n) cb[n] = arm_ctx_base<D>(T, n);
     f2 a[kNL][HP];
 #pragma unroll
     for (int i = 0; i < D; ++i) {
         int dy, dx;
         ctx_offset<D>(i, dy, dx);
 #pragma unroll
-        for (int n = 0; n < kNL; ++n) a[n][i >> 1][i & 1] = tile[cy0 + n * kRowsPerPass + kHalo + dy][cx + kHalo + dx];
+        for (int n = 0; n < kNL; ++n) a[n][i >> 1][i & 1] = arm_ctx_at<D>(tile, cb[n], dy, dx);
     }
 
     const unsigned Wo = nh * LS;
@@ -413,12 +517,12 @@ __global__ __launch_bounds__(kThreads) void arm_fwd_pairs_kernel(
     }
 #pragma unroll
     for (int n = 0; n < kNL; ++n) {
-        float q = tile[cy0 + n * kRowsPerPass + kHalo][cx + kHalo];
+        float q = arm_ctx_at<D>(tile, cb[n], 0, 0);
         if constexpr (SC) {
             ml[n] *= kArmUp;
             q *= kArmUp;
         }
-        arm_emit(T, g, n, ml[n].x, ml[n].y, q, o_mu, o_scale, o_log_scale, o_rate, ostride);
+        arm_emit(T, O, n, ml[n].x, ml[n].y, q);
     }
 }
 
@@ -525,24 +629,66 @@ extern "C" int ccmi_arm_pack_host(const float *params, int dim_arm, int n_hidden
     return n;
 }
 
+// The geometry of a launch over `batch` frames and its tile count; refuses what the kernels'
+// 32-bit arithmetic does not cover.
+static int arm_geometry(int n_grids, const int *h, const int *w, int batch, ArmGeom *out, int64_t *n_tiles)
+{
+    if (n_grids < 1 || n_grids > CCMI_MAX_GRIDS || !h || !w || batch < 1)
+        return ccmi_set_error(CCMI_ERR_ARG, "arm: bad grids or batch");
+    ArmGeom g{};
+    g.n = n_grids;
+    int64_t off = 0, tiles = 0;
+    for (int l = 0; l < n_grids; ++l) {
+        if (h[l] < 1 || w[l] < 1) return ccmi_set_error(CCMI_ERR_ARG, "arm: grid %d has size %dx%d", l, h[l], w[l]);
+        if (off + (int64_t)h[l] * w[l] > kArmMaxLatents)
+            return ccmi_set_error(CCMI_ERR_ARG, "arm: more than 2^30 latents in a frame");
+        g.h[l] = h[l];
+        g.w[l] = w[l];
+        g.off[l] = (int)off;
+        g.tiles_x[l] = ccmi_div_up(w[l], kTX);
+        g.by_tiles_x[l] = arm_div_of((unsigned)g.tiles_x[l]);
+        g.tile_start[l] = (int)tiles;
+        tiles += (int64_t)g.tiles_x[l] * ccmi_div_up(h[l], kTY);
+        off += (int64_t)h[l] * w[l];
+    }
+    for (int l = n_grids; l < CCMI_MAX_GRIDS; ++l) g.tile_start[l] = INT32_MAX;
+    g.ntl = (int)tiles;
+    g.by_ntl = arm_div_of((unsigned)tiles);
+    // the tile id is a 31-bit number (arm_div), and so is the grid's x dimension
+    if (tiles * batch > INT32_MAX) return ccmi_set_error(CCMI_ERR_ARG, "arm: 2^31 tiles or more in a launch");
+    *out = g;
+    *n_tiles = tiles * batch;
+    return CCMI_OK;
+}
+
+extern "C" int ccmi_arm_tile_map(int n_grids, const int *h, const int *w, int batch, int64_t first, int count,
+                                 int *out, int64_t *n_tiles)
+{
+    ArmGeom g;
+    int64_t total = 0;
+    if (int rc = arm_geometry(n_grids, h, w, batch, &g, &total)) return rc;
+    if (n_tiles) *n_tiles = total;
+    if (count < 0 || first < 0 || first + count > total || (count > 0 && !out))
+        return ccmi_set_error(CCMI_ERR_ARG, "arm_tile_map: tiles outside the launch's %lld", (long long)total);
+    for (int i = 0; i < count; ++i) {
+        const ArmTile T = arm_tile_of(g, (unsigned)(first + i));
+        out[4 * i] = T.b;
+        out[4 * i + 1] = T.l;
+        out[4 * i + 2] = T.y0;
+        out[4 * i + 3] = T.x0;
+    }
+    return CCMI_OK;
+}
+
 int ccmi_launch_arm_f32(const ccmi_arm_args *a, hipStream_t s, int form)
 {
-    ArmGeom g{};
-    g.n = a->n_grids;
-    int off = 0, tiles = 0;
-    for (int l = 0; l < a->n_grids; ++l) {
-        g.h[l] = a->h[l];
-        g.w[l] = a->w[l];
-        g.off[l] = off;
-        g.tiles_x[l] = ccmi_div_up(a->w[l], kTX);
-        g.tile_start[l] = tiles;
-        tiles += g.tiles_x[l] * ccmi_div_up(a->h[l], kTY);
-        off += a->h[l] * a->w[l];
-    }
-    g.tile_start[a->n_grids] = tiles;
+    ArmGeom g;
+    int64_t tiles = 0;
+    if (int rc = arm_geometry(a->n_grids, a->h, a->w, a->batch, &g, &tiles)) return rc;
+    const int off = g.off[g.n - 1] + g.h[g.n - 1] * g.w[g.n - 1];
     if ((a->latent_stride != 0 && a->latent_stride < off) || a->out_stride < off)
         return ccmi_set_error(CCMI_ERR_ARG, "arm: stride smaller than the %d latents of a frame", off);
-    dim3 grid((unsigned)(tiles * a->batch));
+    dim3 grid((unsigned)tiles);
 
     // pairs form (dim_arm 8 and 16): pack the weights on this stream, then the kernel that reads
     // the copy.  Without a buffer (none may be allocated while the stream captures) form 0 runs

@@ -103,6 +103,15 @@ int ccmi_arm_forward_f32_form(const ccmi_arm_args *args, void *stream, int form)
  * hidden layer, each row padded with zeros to 16 floats; then (W_out[0][i], W_out[1][i]) for
  * i < d, b_out[2], zeros. */
 int ccmi_arm_pack_host(const float *params, int dim_arm, int n_hidden, float *out);
+/* The tiles of a ccmi_arm_forward_f32 launch over `batch` frames of the grids h[], w[], on the
+ * host, with the constants the kernels use: a workgroup owns 8 x 64 latents of one grid of one
+ * frame; the tiles are numbered frame by frame, in a frame grid by grid, in a grid row by row.
+ * Writes the launch's tile count to *n_tiles (may be NULL) and, for the tiles first .. first +
+ * count - 1, (frame, grid, first row, first column) to out[4 * i ..].  CCMI_ERR_ARG for what the
+ * launch itself refuses (a frame of more than 2^30 latents, 2^31 tiles or more) and for tiles
+ * outside the launch. */
+int ccmi_arm_tile_map(int n_grids, const int *h, const int *w, int batch, int64_t first, int count, int *out,
+                      int64_t *n_tiles);
 
 /* Standalone pieces of the ARM for API parity with the reference modules (the fused
  * ccmi_arm_forward_f32 is what CoolChicEncoder.forward uses):
