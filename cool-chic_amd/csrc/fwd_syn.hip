@@ -162,21 +162,27 @@ __device__ unsigned long long g_fstamp[8];
 using FT = UpsTile<8, 7, kRH, kRW>;
 constexpr int kHsRows = kRH / 2 + 1 + FT::NS - 1; // half-res rows under <= kRH clamped rows
 constexpr int kHrRows = kRH + 7 - 1;              // refine rows incl. the 7-tap halo
-constexpr int kSW = kRW / 2 + 1 + FT::NS - 1 + 3; // raw source tile pitch (37 used)
+constexpr int kSW = kRW / 2 + 1 + FT::NS - 1 + 2; // raw source tile pitch (37 used; odd: the rows of
+                                                  // phase B's pair 32, 8 apart, fall in distinct banks)
 constexpr int kTW = kRW + 7 - 1 + 2;              // raw latent tile pitch (70 used, 72 read)
 
 // Fused upsampling stages the level-1 channels in NG groups of GC (one group's raw tile and
 // horizontal passes in LDS at a time), and the head's weight records live in region 1 once the
-// gathers are done: 52 KB of LDS for the 7-grid hop decoder, three resident workgroups per CU
-// (measured: one workgroup per CU instead of two costs +41 %, tools/occ_probe.sh).
+// gathers are done (or behind the pool, staged once per run: fused_run_recs, an opt-in build):
+// 51 KB of LDS for the 7-grid hop decoder, three resident workgroups per CU (measured: one
+// workgroup per CU instead of two costs +41 %, tools/occ_probe.sh).
 constexpr int fused_groups(int cin, bool ups) { return ups && cin - 1 >= 4 ? 2 : 1; }
 // carry rows of a run: per 3x3 layer, the last two rows of the window's bottom wave, kept for
 // the top wave of the run's next window ([layer][2 rows][CMID][column])
 constexpr int fused_carry_floats(int cmid) { return kMaxSp * 2 * cmid * kRW; }
+// a channel group's raw tiles (region 0 under fused upsampling), rounded to whole 128-bit words so
+// that everything behind region 0 stays 16-byte aligned
+constexpr int fused_raw_floats(int gc) { return (gc * kHsRows * kSW + kHrRows * kTW + 3) / 4 * 4; }
+// the pool without per-run head records (fused_run_recs below)
 constexpr int fused_lds_floats(int cin, int cmid, bool ups)
 {
     const int C = ups ? cin - 1 : 0, GC = (C + fused_groups(cin, ups) - 1) / fused_groups(cin, ups);
-    const int raw = ups ? GC * kHsRows * kSW + kHrRows * kTW : 0;
+    const int raw = ups ? fused_raw_floats(GC) : 0;
     const int stage = ups ? GC * kHsRows * kRW + kHrRows * kRW : 0;
     const int xr = 2 * cmid * kFThreads; // a 3x3 layer's halo-row exchange buffer
     const int b0 = xr > raw ? xr : raw;
@@ -192,6 +198,24 @@ constexpr int fused_wpe(int cin, int cmid, bool ups, bool mh = false)
     if (!mh) return CCMI_FUSED_WPE; // window-size A/B builds only
 #endif
     return !mh && 4 * fused_lds_floats(cin, cmid, ups) <= 160 * 1024 / 3 ? 6 : 4;
+}
+// Head records staged once per run, in LDS of their own behind the pool (kRunRecPitch floats per
+// hidden unit: three 128-bit words, the fields of a 7-grid record with up to 4 outputs): the
+// unrolled VALU head with two channel groups, where the records fit under 160 KB / 3.  That is
+// the 7-grid 48-wide head with a 3-channel tail (hop, plain and folded: 54,576 B); with a
+// 4-channel tail they do not fit (53,808 B without them) and, like every other instantiation,
+// it stages its records in region 1 in every window.
+// Off in the product build (-DCCMI_FUSED_RUN_RECS=1 builds it): it saves two barriers and the
+// staging per window, and measured 1.5 % slower on the headline than per-window staging at
+// 52,272 B (profiles/fused_rows_ab.txt; DESIGN.md 5 "Stride-2 row pairs").
+#ifndef CCMI_FUSED_RUN_RECS
+#define CCMI_FUSED_RUN_RECS 0
+#endif
+constexpr int kRunRecPitch = 12;
+constexpr bool fused_run_recs(int cin, int cmid, bool ups, bool mh, int hid)
+{
+    return CCMI_FUSED_RUN_RECS && ups && !mh && hid > 0 && fused_groups(cin, ups) == 2 && cin + 1 + cmid <= kRunRecPitch &&
+           4 * (fused_lds_floats(cin, cmid, ups) + kRunRecPitch * hid) <= 160 * 1024 / 3;
 }
 
 // MH: split-f16 MFMA first head layer (a separate instantiation: compiled into the default
@@ -210,11 +234,15 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
     constexpr int C = UPS ? CIN - 1 : 0, NG = fused_groups(CIN, UPS), GC = (C + NG - 1) / NG;
     // region 0: raw input tiles of a channel group (UPS, phases A-B), then the 3x3 layers'
     // halo-row buffer 0; region 1: the group's horizontal-pass results (UPS), then the head's
-    // weight records, then the halo-row buffer 1
-    constexpr int kRaw = UPS ? GC * kHsRows * kSW + kHrRows * kTW : 0;
+    // weight records (unless kRunRecs), then the halo-row buffer 1
+    constexpr int kRaw = UPS ? fused_raw_floats(GC) : 0;
     constexpr int kBuf0 = 2 * CMID * kFThreads > kRaw ? 2 * CMID * kFThreads : kRaw;
     constexpr int kTot = fused_lds_floats(CIN, CMID, UPS);
-    __shared__ __attribute__((aligned(16))) float s_pool[kTot];
+    // kRunRecs: the head's weight records behind the pool, staged once per run (fused_run_recs)
+    constexpr bool kRunRecs = fused_run_recs(CIN, CMID, UPS, MH, HID);
+    constexpr int kRecPitch = kRunRecs ? kRunRecPitch : 16;
+    static_assert(kBuf0 % 4 == 0 && kTot % 4 == 0, "the records are read as 128-bit words");
+    __shared__ __attribute__((aligned(16))) float s_pool[kTot + (kRunRecs ? kRunRecPitch * HID : 0)];
     float *s_st = s_pool;                      // [GC][kHsRows][kSW] raw source tile (UPS only)
     float *s_yt = s_st + GC * kHsRows * kSW;   // [kHrRows][kTW] raw latent tile (UPS only)
     float *s_hs = s_pool + kBuf0;              // [GC][kHsRows][kRW]   (UPS only)
@@ -224,7 +252,7 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
 #if defined(CCMI_ARM_STAMPS)
     unsigned long long t_prev = __builtin_amdgcn_s_memtime();
 #endif
-    // head hidden unit j as a record of 16 floats, its fields dense from slot 0: w0[j][0..CIN),
+    // head hidden unit j as a record of kRecPitch floats, its fields dense from slot 0: w0[j][0..CIN),
     // b0[j], w1[0..CMID)[j].  The VALU head reads a record back as kRecVecs broadcast
     // ds_read_b128 (all lanes, one address; three for up to 12 fields: hop has 11), issued a
     // unit ahead of use, unlike the SGPR path whose scalar loads the compiler waits on at once.
@@ -238,9 +266,9 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
     // against 12 here, more than the unit's 80 VALU cycles on each of four SIMDs leave room
     // for.  The operands are taken in place by op_sel instead (head_hidden2 / head_out2,
     // fwd_common.h).
-    float(*s_head)[16] = reinterpret_cast<float(*)[16]>(s_pool + kBuf0);
+    float *s_head = s_pool + (kRunRecs ? kTot : kBuf0); // [unit][kRecPitch]
     float *s_w1p = s_pool + kBuf0 + kMaxHid * 16; // MH: the second layer's weights by lane row
-    static_assert(CIN + 1 + CMID <= 16, "hidden-unit record");
+    static_assert(CIN + 1 + CMID <= kRecPitch, "hidden-unit record");
     constexpr int kRecVecs = (CIN + 1 + CMID + 3) / 4;
 
     // XCD-aware order of the runs (raster order, frame after frame, a contiguous stretch per
@@ -256,18 +284,61 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
     const int oy0 = y0 - Ak.n_sp, ox0 = x0 - Ak.n_sp; // global coords of the first window's (0,0)
     // per-run table in LDS: the 8-bit output quotients (own area)
     if (Ak.qmax == 255.f) s_lut8[threadIdx.x & 255] = (float)(threadIdx.x & 255) / 255.f;
+    // the thread index as an opaque copy per use (see the top of the loop)
+    auto tixf = []() __attribute__((always_inline)) {
+        int t = threadIdx.x;
+        asm volatile("" : "+v"(t));
+        return t;
+    };
+    // The head's weight records (L2-resident: every workgroup of a frame reads the same ones) are
+    // fetched into two registers per thread (fetch_recs) and stored into LDS from there
+    // (store_recs): once per run where they have LDS of their own (kRunRecs), else in every
+    // window, where they share region 1 with the horizontal passes.
+    constexpr int kHeadRegs = (kMaxHid * 16 + kFThreads - 1) / kFThreads;
+    // scaled ReLU for the unrolled VALU head (HID > 0, !MH; launched only with a first-layer ReLU)
+    constexpr bool kScaledRelu = HID > 0 && !MH;
+    constexpr float kW0Scale = kScaledRelu ? 0x1p-32f : 1.f, kW1Scale = kScaledRelu ? 0x1p32f : 1.f;
+    auto fetch_recs = [&](const FusedArgs &A, cfloat_ptr prm, float(&hv)[kHeadRegs]) __attribute__((always_inline)) {
+        const int tid = tixf();
+#pragma unroll
+        for (int k = 0; k < kHeadRegs; ++k) {
+            const int i = tid + k * kFThreads, j = i >> 4, f = i & 15;
+            float v = 0.f;
+            if (i < kMaxHid * 16 && A.n_head == 2 && j < A.hid) {
+                // the unrolled VALU head's records carry the scaled-ReLU exponents ("Scaled ReLU" below):
+                // hidden weights / bias x 2^-32, output weights x 2^32 -- exact power-of-two scalings
+                if (f < CIN) v = prm[A.w0_off + j * CIN + f] * kW0Scale;
+                else if (f == CIN) v = prm[A.b0_off + j] * kW0Scale;
+                else if (f <= CIN + CMID) v = prm[A.w1_off + (f - CIN - 1) * A.hid + j] * kW1Scale;
+            }
+            hv[k] = v;
+        }
+    };
+    auto store_recs = [&](const float(&hv)[kHeadRegs]) __attribute__((always_inline)) {
+        const int tid = tixf();
+        constexpr int kUnits = kRunRecs ? HID : kMaxHid;
+#pragma unroll
+        for (int k = 0; k < kHeadRegs; ++k) {
+            const int i = tid + k * kFThreads, j = i >> 4, f = i & 15;
+            if (j < kUnits && f <= CIN + CMID) s_head[j * kRecPitch + f] = hv[k]; // other slots are never operands
+        }
+    };
+    if constexpr (kRunRecs) {
+        // This run's records (one frame, one workgroup).  Their first reader is the first
+        // window's head, behind that window's barriers; nothing else ever writes the area.
+        const FusedArgs &A = *(const FusedArgs *)fresh_kernargs();
+        float hv[kHeadRegs];
+        fetch_recs(A, (cfloat_ptr)(size_t)(A.params + (int64_t)b0 * A.pstride), hv);
+        store_recs(hv);
+    }
     // The walk.  The trip count is a function of the work item alone (scalar), every barrier
     // below is reached by all waves in every iteration, and nothing leaves the loop early.
 #pragma clang loop unroll(disable)
     for (int win = 0; win < nwin; ++win) {
     // Loop-invariant values must not be hoisted out of this loop: held across a whole window
     // they cost the kernel its 6 waves per SIMD.  So the thread index is an opaque copy per
-    // use (values derived from it, lane masks and LDS addresses, were hoisted and spilled),
-    auto tixf = []() __attribute__((always_inline)) {
-        int t = threadIdx.x;
-        asm volatile("" : "+v"(t));
-        return t;
-    };
+    // use, tixf above (values derived from it, lane masks and LDS addresses, were hoisted and
+    // spilled),
     // and the kernel's arguments are re-read from the kernarg segment in every window, through
     // a pointer the compiler cannot see through (hoisted, they filled the SGPRs and the spilled
     // ones took vector registers).
@@ -301,40 +372,18 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
     };
 
     const float *lut8 = A.qmax == 255.f ? s_lut8 : nullptr;
-    // per-frame table in LDS: the head's weight records (region 1: before anything else
-    // without fused upsampling, after the gathers with it)
-    // the records (L2-resident: every workgroup of a frame reads the same ones) are fetched
-    // into two registers before the last upsampling group, so their latency hides behind its
-    // passes, and staged once region 1 is free
-    constexpr int kHeadRegs = (kMaxHid * 16 + kFThreads - 1) / kFThreads;
-    // scaled ReLU for the unrolled VALU head (HID > 0, !MH; launched only with a first-layer ReLU)
-    constexpr bool kScaledRelu = HID > 0 && !MH;
-    constexpr float kW0Scale = kScaledRelu ? 0x1p-32f : 1.f, kW1Scale = kScaledRelu ? 0x1p32f : 1.f;
+    // per-window staging of the head's weight records (!kRunRecs), in region 1: before anything
+    // else without fused upsampling, after the gathers with it.  They are fetched before the
+    // last upsampling group, so their latency hides behind its passes, and staged once region 1
+    // is free
     float hv[kHeadRegs];
     auto load_head = [&]() {
-        const int tid = tixf();
-#pragma unroll
-        for (int k = 0; k < kHeadRegs; ++k) {
-            const int i = tid + k * kFThreads, j = i >> 4, f = i & 15;
-            float v = 0.f;
-            if (i < kMaxHid * 16 && A.n_head == 2 && j < A.hid) {
-                // the unrolled VALU head's records carry the scaled-ReLU exponents ("Scaled ReLU" below):
-                // hidden weights / bias x 2^-32, output weights x 2^32 -- exact power-of-two scalings
-                if (f < CIN) v = prm[A.w0_off + j * CIN + f] * kW0Scale;
-                else if (f == CIN) v = prm[A.b0_off + j] * kW0Scale;
-                else if (f <= CIN + CMID) v = prm[A.w1_off + (f - CIN - 1) * A.hid + j] * kW1Scale;
-            }
-            hv[k] = v;
-        }
+        if constexpr (!kRunRecs) fetch_recs(A, prm, hv);
     };
     auto stage_head = [&]() {
-        const int tid = tixf();
-#pragma unroll
-        for (int k = 0; k < kHeadRegs; ++k) {
-            const int i = tid + k * kFThreads, j = i >> 4, f = i & 15;
-            if (i < kMaxHid * 16 && f <= CIN + CMID) s_head[j][f] = hv[k]; // other slots are never operands
-        }
+        if constexpr (!kRunRecs) store_recs(hv);
         if constexpr (MH) {
+            const int tid = tixf();
             // [tile][lane row][m][4 units]: the second layer's weights of the 4 hidden units a
             // lane's accumulator registers hold (one ds_read_b128 per output channel)
             constexpr int n = (HID / 16) * 4 * CMID * 4;
@@ -747,8 +796,14 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
         }
     }
 
-    // the current stage's image at this thread's 4 rows: row pairs (rb, rb+1), (rb+2, rb+3)
-    f2 img[NR / 2][CMID];
+    // the current stage's image at this thread's 4 rows, as stride-2 row pairs: img[q] = {row
+    // rb + q, row rb + q + 2}.  A 3x3 layer's five input pairs are then two pairs made of a row
+    // from above and the pairs as they stand (no pair straddles two others), and a pair holds
+    // rows of one parity: pair 0 the even image rows, which is all the 4:2:0 chroma stores.
+    constexpr int NP = NR / 2; // pairs: NP = 2 in what follows
+    static_assert(NR % 4 == 0, "a pair's rows have one parity");
+    f2 img[NP][CMID];
+    auto row_of = [&](int p, int m) __attribute__((always_inline)) { return p < NP ? img[p][m].x : img[p - NP][m].y; };
     // ------------------------ pass 0: per-pixel 1x1 head ------------------------
     {
         const FusedArgs &A = *(const FusedArgs *)fresh_kernargs(); // (re-read: see the top of the loop)
@@ -756,8 +811,18 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
         const cfloat_ptr b1 = prm + A.b1_off;
         float o[NR][CMID];
         // region 1 (the last group's horizontal passes) is free once every wave has gathered:
-        // the head's weight records go there
-        if constexpr (UPS) {
+        // the head's weight records go there.
+        // With kRunRecs nothing is staged here and the head needs no barrier of its own.  What
+        // the two barriers of the per-window staging ordered besides the records:
+        //  * region 0 is next written by publish(xb0) below.  Its raw tiles were last read by the
+        //    last group's phase B (the source rows) and by group 0's gather (the latent tile's
+        //    residual); with two groups both lie before the barrier that closes the last group's
+        //    phase B, which every wave has passed before it publishes.
+        //  * region 1 (the last group's horizontal passes, read by the gather) is next written by
+        //    the first non-last 3x3 layer's publish(xout), behind that layer's barrier, which a
+        //    wave reaches only after its gather; with a single 3x3 layer, by the next window's
+        //    phase B, behind the barrier that closes this window.
+        if constexpr (UPS && !kRunRecs) {
             __syncthreads();
             stage_head();
         }
@@ -775,7 +840,7 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
 #pragma unroll
                 for (int k = 0; k < 2; ++k) {
                     const int ch = 4 * k + lg;
-                    a1[mt][k] = ch <= CIN ? s_head[16 * mt + lr][ch] : 0.f; // slot CIN: the bias
+                    a1[mt][k] = ch <= CIN ? s_head[(16 * mt + lr) * kRecPitch + ch] : 0.f; // slot CIN: the bias
                 }
             const f2 lo0 = f2(A.relu0 ? 0.f : -INFINITY);
             const float lo1 = A.relu1 ? 0.f : -INFINITY;
@@ -846,20 +911,21 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
 #pragma unroll
             for (int q = 0; q < NR / 2; ++q) {
 #pragma unroll
-                for (int k = 0; k < CIN; ++k) xp[q][k] = f2{x[2 * q][k], x[2 * q + 1][k]};
+                for (int k = 0; k < CIN; ++k) xp[q][k] = f2{x[q][k], x[q + NR / 2][k]}; // stride-2 row pairs
 #pragma unroll
                 for (int m = 0; m < CMID; ++m) op[q][m] = f2(0.f);
             }
-            __syncthreads(); // s_head staged
+            if constexpr (!kRunRecs) __syncthreads(); // s_head staged
             // software pipelined: the record of unit j+1 is loaded while unit j computes
             struct Rec { f4v v[kRecVecs]; };
             // records through an LDS pointer the compiler cannot fold to a constant, so the
             // unrolled reads are base + immediate offset (not one v_mov of an address each)
             typedef const __attribute__((address_space(3))) f4v *lds_f4;
-            lds_f4 hb = (lds_f4)(&s_head[0][0]);
+            constexpr int kRecStep = kRecPitch / 4; // a record's pitch in 128-bit words
+            lds_f4 hb = (lds_f4)s_head;
             asm volatile("" : "+v"(hb));
             auto load = [&](int j) {
-                const lds_f4 p = hb + 4 * (j < hid ? j : hid - 1);
+                const lds_f4 p = hb + kRecStep * (j < hid ? j : hid - 1);
                 Rec r;
 #pragma unroll
                 for (int i = 0; i < kRecVecs; ++i) r.v[i] = p[i];
@@ -909,7 +975,7 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
                 constexpr int kHidVecs = CIN / 4 + 1;
                 auto read = [&](Rec &r, int j, int v0, int v1) __attribute__((always_inline)) {
 #pragma unroll
-                    for (int i = v0; i < v1; ++i) r.v[i] = hb[4 * j + i];
+                    for (int i = v0; i < v1; ++i) r.v[i] = hb[kRecStep * j + i];
                 };
                 Rec cur, nxt;
                 read(cur, 0, 0, kRecVecs);
@@ -942,8 +1008,8 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
             for (int q = 0; q < NR / 2; ++q)
 #pragma unroll
                 for (int m = 0; m < CMID; ++m) {
-                    o[2 * q][m] = fmaxf(op[q][m].x + b1[m], lo1);
-                    o[2 * q + 1][m] = fmaxf(op[q][m].y + b1[m], lo1);
+                    o[q][m] = fmaxf(op[q][m].x + b1[m], lo1);
+                    o[q + NR / 2][m] = fmaxf(op[q][m].y + b1[m], lo1);
                 }
         } else {
             const float lo0 = A.relu0 ? 0.f : -INFINITY;
@@ -973,7 +1039,7 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
 #pragma unroll
         for (int q = 0; q < NR / 2; ++q)
 #pragma unroll
-            for (int m = 0; m < CMID; ++m) img[q][m] = f2{o[2 * q][m], o[2 * q + 1][m]};
+            for (int m = 0; m < CMID; ++m) img[q][m] = f2{o[q][m], o[q + NR / 2][m]};
     }
 
     // ------------------------ 3x3 layers, replicate padding ------------------------
@@ -1008,8 +1074,8 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
         const int tid = tixf();
 #pragma unroll
         for (int m = 0; m < CMID; ++m) {
-            xb[m * kFThreads + tid] = img[NR / 2 - 1][m].x;            // the thread's row NR - 2
-            xb[(CMID + m) * kFThreads + tid] = img[NR / 2 - 1][m].y;   // and row NR - 1
+            xb[m * kFThreads + tid] = row_of(NR - 2, m);            // the thread's row NR - 2 (img[NP - 2].y)
+            xb[(CMID + m) * kFThreads + tid] = row_of(NR - 1, m);   // and row NR - 1 (img[NP - 1].y)
         }
     };
     auto shr1 = [](float v) __attribute__((always_inline)) { // lane c <- lane c - 1 (0 at lane 0)
@@ -1023,8 +1089,15 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
     const bool cols_inner = ox >= 0 && ox + kRW <= A.W;        // every lane an image column
     // one 3x3 layer: img (stage s input) -> img (stage s output, one row up); the non-last
     // layers publish their output's last two rows into xout
-    auto layer = [&](auto LAST, int s, const float *xin, float *xout) __attribute__((always_inline)) {
+    // c420 (last layer only, wave-uniform): the output is stored as 4:2:0 planes, which keep the
+    // chroma channels m >= 1 on even image rows only.  Image-row parity is the parity of the
+    // register row: register row r of the last stage is image row y0 - 2 n_sp + kRH win + r with
+    // y0 and kRH even, and rb is a multiple of 4.  So the even rows are exactly the pairs q of
+    // even q, and the last layer skips the chroma channels' other pairs (a scalar branch
+    // around them; one copy of the layer).
+    auto layer = [&](auto LAST, bool c420, int s, const float *xin, float *xout) __attribute__((always_inline)) {
         constexpr bool last = decltype(LAST)::value;
+        static_assert(kRH % 2 == 0, "row parity");
         const int tid = tixf();
         const int wrow = __builtin_amdgcn_readfirstlane(tid >> 6) * NR; // rb, wave-uniform
         float *cr = s_carry + s * (2 * CMID * kRW) + (tid & (kRW - 1)); // this layer's carry rows, own column
@@ -1054,7 +1127,7 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
 #pragma unroll
         for (int m = 0; m < CMID; ++m)
 #pragma unroll
-            for (int p = 0; p < NR; ++p) v[p + 2][m] = (p & 1) ? img[p / 2][m].y : img[p / 2][m].x;
+            for (int p = 0; p < NR; ++p) v[p + 2][m] = row_of(p, m);
         if (wrow == kRH - NR) {
             // the bottom wave's last two rows are rows -2, -1 of the next window (the top wave
             // has read the previous ones before the barrier above; the next read is behind the
@@ -1078,22 +1151,24 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
 #pragma unroll
                     for (int m = 0; m < CMID; ++m) v[i][m] = v[i + 1][m];
         }
-        // packed row pairs: P[r][k] = {v[r], v[r + 1]}, r = 0 .. NR; output row pair q (the
-        // thread's rows 2q, 2q + 1 of the next stage) is centred on P[2q + 1]
-        f2 P[NR + 1][CMID];
+        // stride-2 row pairs: E[i][k] = {v[i], v[i + NP]}, i = 0 .. NP + 1.  E[2 ..] are the
+        // thread's own pairs img[0 ..] as they stand; E[0] and E[1] take the row from above in
+        // the low half and a copy of img[0].x / img[1].x in the high half.  Output pair q (the
+        // thread's rows q, q + NP of the next stage) reads E[q + dy] and is centred on E[q + 1].
+        f2 E[NP + 2][CMID];
 #pragma unroll
-        for (int r = 0; r <= NR; ++r)
+        for (int i = 0; i < NP + 2; ++i)
 #pragma unroll
-            for (int k = 0; k < CMID; ++k) P[r][k] = f2{v[r][k], v[r + 1][k]};
+            for (int k = 0; k < CMID; ++k) E[i][k] = f2{v[i][k], v[i + NP][k]};
         // the weights are wave-uniform scalar loads; the output channel loop is unrolled (the
         // outputs stay in registers, which a runtime channel index would send to scratch)
-        f2 nxt[NR / 2][CMID];
-#pragma unroll
-        for (int m = 0; m < CMID; ++m) {
+        f2 nxt[NP][CMID];
+        // output channel m (unrolled by the callers) on the pairs q = qa, qa + qs, ...
+        auto chan = [&](cfloat_ptr wt, cfloat_ptr bs, int m, int qa, int qs) __attribute__((always_inline)) {
             const cfloat_ptr wm = wt + m * CMID * 9;
-            f2 S[3][NR / 2];
+            f2 S[3][NP];
 #pragma unroll
-            for (int q = 0; q < NR / 2; ++q) {
+            for (int q = qa; q < NP; q += qs) {
                 S[0][q] = f2(0.f);
                 S[1][q] = f2(bs[m]);
                 S[2][q] = f2(0.f);
@@ -1106,16 +1181,45 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
                     for (int dx = 0; dx < 3; ++dx) {
                         const f2 w = f2(wm[(k * 3 + dy) * 3 + dx]);
 #pragma unroll
-                        for (int q = 0; q < NR / 2; ++q) S[dx][q] = __builtin_elementwise_fma(w, P[2 * q + dy][k], S[dx][q]);
+                        for (int q = qa; q < NP; q += qs) S[dx][q] = __builtin_elementwise_fma(w, E[q + dy][k], S[dx][q]);
                     }
 #pragma unroll
-            for (int q = 0; q < NR / 2; ++q) {
+            for (int q = qa; q < NP; q += qs) {
                 f2 acc;
                 acc.x = (S[1][q].x + shr1(S[0][q].x)) + shl1(S[2][q].x);
                 acc.y = (S[1][q].y + shr1(S[0][q].y)) + shl1(S[2][q].y);
-                // residual: the input at the centre (row pair 2q + 1 = v[2q + 1], v[2q + 2])
-                nxt[q][m] = __builtin_elementwise_max(__builtin_elementwise_fma(rsd, P[2 * q + 1][m], acc), lo);
+                // residual: the input at the centre (pair E[q + 1] = v[q + 1], v[q + 1 + NP])
+                nxt[q][m] = __builtin_elementwise_max(__builtin_elementwise_fma(rsd, E[q + 1][m], acc), lo);
             }
+        };
+        if constexpr (last && CMID == 3) {
+            // the stage that is stored: luma on every pair, chroma on the pairs of even rows,
+            // and on the others unless the store drops them
+            chan(wt, bs, 0, 0, 1);
+#pragma unroll
+            for (int m = 1; m < CMID; ++m) {
+                chan(wt, bs, m, 0, 2);
+#pragma unroll
+                for (int q = 1; q < NP; q += 2) nxt[q][m] = f2(0.f);
+            }
+            // (finished here: left alone, the compiler sinks half of these chains below the branch
+            // and holds their weights in SGPRs across it)
+#pragma unroll
+            for (int m = 0; m < CMID; ++m)
+#pragma unroll
+                for (int q = 0; q < NP; q += (m > 0 ? 2 : 1)) asm volatile("" : "+v"(nxt[q][m]));
+            if (!c420) {
+                // the weights once more, through pointers the compiler cannot match with the ones
+                // above (it would keep all 56 of the chroma channels' in SGPRs for this branch,
+                // and spill)
+                cfloat_ptr wt2 = wt, bs2 = bs;
+                asm volatile("" : "+s"(wt2), "+s"(bs2));
+#pragma unroll
+                for (int m = 1; m < CMID; ++m) chan(wt2, bs2, m, 1, 2);
+            }
+        } else {
+#pragma unroll
+            for (int m = 0; m < CMID; ++m) chan(wt, bs, m, 0, 1);
         }
 #pragma unroll
         for (int q = 0; q < NR / 2; ++q)
@@ -1151,12 +1255,13 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
     };
     publish(xb0);
     for (int s = 0; s < A.n_sp - 1; ++s) {
-        layer(std::false_type{}, s, xb0, xb1);
+        layer(std::false_type{}, false, s, xb0, xb1);
         float *const t = xb0;
         xb0 = xb1;
         xb1 = t;
     }
-    layer(std::true_type{}, A.n_sp - 1, xb0, nullptr);
+    // (c420: the same condition as the 4:2:0 store loops below)
+    layer(std::true_type{}, A.yuv420 && A.qmax > 0.f, A.n_sp - 1, xb0, nullptr);
     // stores: this thread's own pixels of the last layer, from registers, one branch-free loop
     // per output format
     {
@@ -1181,8 +1286,10 @@ __global__ __launch_bounds__(kFThreads) __attribute__((amdgpu_waves_per_eu(fused
                 const uint32_t cpx = (uint32_t)((gy >> 1) * (int)cw + (gx >> 1));
 #pragma unroll
                 for (int m = 0; m < CMID; ++m) {
-                    if (fmt == 2 && m > 0 && (gy & 1)) break; // 420: odd rows carry no chroma (wave-uniform)
-                    float v = (p & 1) ? img[p / 2][m].y : img[p / 2][m].x;
+                    // 420: odd rows carry no chroma, and gy is odd where p is (see C420 above; the
+                    // last layer did not evaluate those)
+                    if (fmt == 2 && m > 0 && (p & 1)) break;
+                    float v = row_of(p, m);
                     if constexpr (fmt > 0) {
                         v = tab ? lut8[(int)fminf(fmaxf(rintf(v * 255.f), 0.f), 255.f)]
                                 : fminf(fmaxf(rintf(v * A.qmax) / A.qmax, 0.f), 1.f);
