@@ -118,7 +118,9 @@ def _full_kernels(arch: Arch, blocks: torch.Tensor, lay: Layout) -> torch.Tensor
 class _Eval:
     """Batched eval forwards with shared latents / shared stages (stride-0 inputs)."""
 
-    def __init__(self, arch: Arch, latent: torch.Tensor, target: torch.Tensor, yuv420: bool, bitdepth: int):
+    def __init__(self, arch: Arch, latent: torch.Tensor, target: torch.Tensor, yuv420: bool, bitdepth: int,
+                 distortion=None):
+        self.distortion = distortion
         self.a, self.lat, self.tgt, self.yuv420, self.bd = arch, latent.contiguous(), target.contiguous(), yuv420, bitdepth
         self.dev = latent.device
         self.h = (C.c_int * MAX_GRIDS)(*[s[0] for s in arch.sizes])
@@ -188,16 +190,20 @@ class _Eval:
         pa = PostArgs(in_=raw.data_ptr(), in_stride=3 * H * W, h=H, w=W, bitdepth=self.bd, yuv420=int(self.yuv420),
                       out=dec.data_ptr(), out_stride=n, batch=B)
         check(self.L.ccmi_post_f32(C.byref(pa), self.s))
+        if self.distortion is not None:  # D of the decoded rows against the shared target, in the MSE's place
+            from .metrics import distortion
+            return distortion(dec, self.tgt, self.distortion, yuv420=self.yuv420, clamp=False, size=(H, W))[:, 0].double()
         return self.reduce(dec, self.tgt, 1) / n
 
 
 def quantize_model(arch: Arch, latent: torch.Tensor, params: torch.Tensor, target: torch.Tensor, lmbda: float,
-                   yuv420: bool = True, bitdepth: int = 8, chunk: int = 64) -> QuantizedModel:
+                   yuv420: bool = True, bitdepth: int = 8, chunk: int = 64, distortion=None) -> QuantizedModel:
     """Greedy per-module search of the quantisation steps (quantizemodel.py:120-245) for
     one frame: latent [N] (float, before gain), params [P] (ccmi.train layout), target
-    (flat, ccmi.train layout) on the GPU."""
+    (flat, ccmi.train layout) on the GPU.  distortion (a ccmi.metrics.Distortion): the candidates
+    are scored with ccmi.metrics.distortion of their decoded frame in the MSE's place."""
     lay = Layout.of(arch)
-    ev = _Eval(arch, latent.float(), target.float(), yuv420, bitdepth)
+    ev = _Eval(arch, latent.float(), target.float(), yuv420, bitdepth, distortion)
     fp = params.detach().float().cpu().numpy()
     cur = fp.copy()
     res = QuantizedModel(params=cur)

@@ -53,6 +53,12 @@ def _bind():
         L.ccmi_train_workspace_bytes.restype = C.c_size_t
         L.ccmi_train_param_count.argtypes = [C.POINTER(TrainArgs)]
         L.ccmi_train_param_count.restype = C.c_size_t
+        if hasattr(L, "ccmi_train_step_dist"):  # absent from older builds loaded for A/B runs
+            from .metrics import TrainDist
+            L.ccmi_train_step_dist.argtypes = [C.POINTER(TrainArgs), C.POINTER(TrainDist), C.c_void_p]
+            L.ccmi_train_step_dist.restype = C.c_int
+            L.ccmi_train_workspace_bytes_dist.argtypes = [C.POINTER(TrainArgs), C.POINTER(TrainDist)]
+            L.ccmi_train_workspace_bytes_dist.restype = C.c_size_t
         L._ccmi_train_bound = True
     return L
 
@@ -120,12 +126,17 @@ def pack_params(arm, ups_half, pre_half, syn) -> torch.Tensor:
 
 class Overfitter:
     """GPU state of `batch` frames being overfitted together: latents, parameters and the
-    Adam moments live in HBM; step() runs one training iteration for all of them."""
+    Adam moments live in HBM; step() runs one training iteration for all of them.
+
+    distortion: a ccmi.metrics.Distortion; every step() and validate() then runs
+    ccmi_train_step_dist with it (loss = D + lmbda rate / (H W)) and fills self.dist, [B, 4] =
+    (D, MS, MSE, min v_s).  None: ccmi_train_step, the MSE alone."""
 
     def __init__(self, arch: Arch, latents: torch.Tensor, params: torch.Tensor, targets: torch.Tensor,
-                 yuv420: bool = True, seed: int = 0):
+                 yuv420: bool = True, seed: int = 0, distortion=None):
         require_cuda(latents, params, targets)
         self.arch, self.yuv420, self.seed = arch, bool(yuv420), seed
+        self.distortion, self.dist = distortion, None
         self.B = latents.shape[0]
         self.latents = latents.float().contiguous()
         self.params = params.float().contiguous()
@@ -146,8 +157,10 @@ class Overfitter:
         # train.py:226-236); uniform steps use the scalar path
         self.steps = torch.zeros(self.B, dtype=torch.int32, device=dev)
         self.steps_uniform = True
-        self.loss = torch.zeros(self.B, 4, device=dev)
-        self.ws = torch.empty(L.ccmi_train_workspace_bytes(C.byref(a)), dtype=torch.uint8, device=dev)
+        self._realloc()
+
+    def _dist_struct(self):
+        return None if self.distortion is None else self.distortion.train_struct(self.yuv420, self.dist)
 
     def reset_optimizer(self):
         """A new torch.optim.Adam: every training phase builds its own (train.py:184)."""
@@ -160,8 +173,16 @@ class Overfitter:
     def _realloc(self):
         self.loss = torch.zeros(self.B, 4, device=self.latents.device)
         a = self._args()
-        self.ws = torch.empty(_bind().ccmi_train_workspace_bytes(C.byref(a)), dtype=torch.uint8,
-                              device=self.latents.device)
+        if self.distortion is None:
+            nws = _bind().ccmi_train_workspace_bytes(C.byref(a))
+        else:
+            self.dist = torch.zeros(self.B, 4, device=self.latents.device)
+            d = self._dist_struct()
+            nws = _bind().ccmi_train_workspace_bytes_dist(C.byref(a), C.byref(d))
+            if nws == 0:
+                from . import last_error
+                raise ValueError("distortion: " + last_error())
+        self.ws = torch.empty(nws, dtype=torch.uint8, device=self.latents.device)
 
     def keep(self, idx: torch.Tensor):
         """Keep frames idx (a [B'] index tensor) of the batch, in that order."""
@@ -237,7 +258,12 @@ class Overfitter:
         a.loss_out = self.loss.data_ptr()
         a.update = 2 if update == "latent" else int(bool(update))
         a.workspace, a.workspace_bytes = self.ws.data_ptr(), self.ws.numel()
-        check(_bind().ccmi_train_step(C.byref(a), torch.cuda.current_stream(self.latents.device).cuda_stream))
+        stream = torch.cuda.current_stream(self.latents.device).cuda_stream
+        if self.distortion is None:
+            check(_bind().ccmi_train_step(C.byref(a), stream))
+        else:
+            d = self._dist_struct()
+            check(_bind().ccmi_train_step_dist(C.byref(a), C.byref(d), stream))
         return self.loss
 
 
@@ -308,7 +334,7 @@ def c3x_iterations(scale: float = 1.0) -> int:
         sum(max(1, int(p.max_itr * scale)) for p in C3X_PHASES)
 
 
-def run_phase(of: Overfitter, ph: Phase, lmbda: float, scale: float = 1.0) -> torch.Tensor:
+def run_phase(of: Overfitter, ph: Phase, lmbda: float, scale: float = 1.0, distortion=None) -> torch.Tensor:
     """train() (enc/training/train.py:86-374) for every frame of the batch at once: Adam
     restarted, cosine learning rate stepped every freq_valid iterations, linear soft-round
     temperature / noise schedules, validation every freq_valid iterations keeping each
@@ -322,7 +348,17 @@ def run_phase(of: Overfitter, ph: Phase, lmbda: float, scale: float = 1.0) -> to
     stops (other phases: it leaves the batch, so the remaining frames run alone).  With
     scale < 1, patience and freq_valid are scaled like max_itr (as tools/gen_golden_rd.py
     scales the reference's presets).  Sets of.phase_iterations (per frame of the batch, in
-    batch order).  Returns the best validation [B, 4]."""
+    batch order).  Returns the best validation [B, 4].  distortion (a ccmi.metrics.Distortion): the
+    phase trains and validates with it instead of the Overfitter's own (restored afterwards)."""
+    if distortion is not None and distortion != of.distortion:
+        saved = of.distortion
+        of.distortion = distortion
+        of._realloc()
+        try:
+            return run_phase(of, ph, lmbda, scale)
+        finally:
+            of.distortion = saved
+            of._realloc()
     n = max(1, int(ph.max_itr * scale))
     freq = max(1, int(ph.freq_valid * scale)) if scale < 1 else ph.freq_valid
     pat = max(1, int(ph.patience * scale)) if scale < 1 else ph.patience
@@ -401,14 +437,17 @@ def run_phase(of: Overfitter, ph: Phase, lmbda: float, scale: float = 1.0) -> to
 
 
 def overfit(arch: Arch, targets: torch.Tensor, lmbda: float, yuv420: bool = True, scale: float = 1.0,
-            seed: int = 0, warmup=C3X_WARMUP, phases=C3X_PHASES, bitdepth: int = 8) -> tuple[Overfitter, torch.Tensor]:
+            seed: int = 0, warmup=C3X_WARMUP, phases=C3X_PHASES, bitdepth: int = 8,
+            distortion=None) -> tuple[Overfitter, torch.Tensor]:
     """The c3x encoding schedule (enc/training/warmup.py + train.py phases) for a batch of
     frames [B, target_len] on one GPU.  Warm-up candidates of every frame train together
     as one batch; after each warm-up stage each frame keeps its best candidates.  After a
     phase flagged quantize_model, every frame's networks are quantised
     (ccmi.quantize.quantize_model, as video.py:302-310) and later phases train with them;
     the per-frame QuantizedModel list is state.quantized (None if no phase asks for it);
-    state.iterations the per-frame iteration counts.  Returns (state, best validation)."""
+    state.iterations the per-frame iteration counts.  Returns (state, best validation).
+    distortion (a ccmi.metrics.Distortion): every step, validation and the quantisation search use
+    D = alpha_mse MSE + beta_ms (1 - MS-SSIM) in the MSE's place; None runs today's code."""
     import time
     dev = targets.device
     B = targets.shape[0]
@@ -419,7 +458,8 @@ def overfit(arch: Arch, targets: torch.Tensor, lmbda: float, yuv420: bool = True
     g = torch.Generator().manual_seed(seed)
     params = torch.stack([init_params(arch, g) for _ in range(B * n0)]).to(dev)
     lat = torch.zeros(B * n0, arch.n_latents, device=dev)
-    of = Overfitter(arch, lat, params, targets.repeat_interleave(n0, dim=0), yuv420=yuv420, seed=seed)
+    of = Overfitter(arch, lat, params, targets.repeat_interleave(n0, dim=0), yuv420=yuv420, seed=seed,
+                    distortion=distortion)
     ncand = n0
     # iterations per image as the reference's FrameEncoderManager.iterations_counter counts
     # them: the sum over the image's own warm-up candidates (trained one after another in
@@ -450,7 +490,8 @@ def overfit(arch: Arch, targets: torch.Tensor, lmbda: float, yuv420: bool = True
             t0 = time.perf_counter()
             qms = []
             for b in range(of.B):
-                qm = quantize_model(arch, of.latents[b], of.params[b], of.targets[b], lmbda, yuv420, bitdepth)
+                qm = quantize_model(arch, of.latents[b], of.params[b], of.targets[b], lmbda, yuv420, bitdepth,
+                                    distortion=distortion)
                 of.params[b].copy_(torch.from_numpy(qm.params).to(of.params.device))
                 qms.append(qm)
             of.quantized = qms

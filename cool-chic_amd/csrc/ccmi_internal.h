@@ -39,6 +39,10 @@ int ccmi_launch_arm_f32(const ccmi_arm_args *a, hipStream_t s, int form);
 int ccmi_launch_ups_f32(const ccmi_ups_args *a, hipStream_t s);
 int ccmi_launch_syn_f32(const ccmi_syn_args *a, hipStream_t s);
 int ccmi_launch_post_f32(const ccmi_post_args *a, hipStream_t s);
+// MS-SSIM distortion (dist_msssim.hip).  ccmi_msssim_check: every argument error of ccmi_msssim_f32,
+// no HIP call; ccmi_launch_msssim checks the same and enqueues the kernels.
+int ccmi_msssim_check(const ccmi_msssim_args *a);
+int ccmi_launch_msssim(const ccmi_msssim_args *a, hipStream_t s);
 
 // The packed-weight buffer of the ARM's pairs form for stream s of the current device (contract:
 // ccmi.h, ccmi_arm_forward_f32_form).  *out = a device buffer of >= bytes, or nullptr (with

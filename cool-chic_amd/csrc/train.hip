@@ -2827,6 +2827,7 @@ struct AdamArgs {
     float *loss_out; // optional [B][4]: t_finish's row, written by workgroup (0, b)
     const float *rslots, *mslots;
     float inv_total, lam_px;
+    const float *dist4; // optional [B][4]: finish_row
 };
 
 // per-frame bias corrections when frames carry their own Adam step (a frame whose optimizer
@@ -2854,7 +2855,7 @@ __global__ void t_adam_bc(const int32_t *__restrict__ steps, double lr, double b
 // into the last t_sp_fwd (zero when t_loss ran: it adds into acc4[b][0])
 __device__ __forceinline__ void finish_row(const float *__restrict__ acc4, const float *__restrict__ rslots,
                                            const float *__restrict__ mslots, float inv_total, float lam_px,
-                                           float *__restrict__ out, int b)
+                                           float *__restrict__ out, int b, const float *__restrict__ dist4)
 {
     float rate = 0.f, sq = acc4[b * 4 + 0];
 #pragma unroll 8
@@ -2862,8 +2863,9 @@ __device__ __forceinline__ void finish_row(const float *__restrict__ acc4, const
         rate += rslots[b * kDwSlots + k];
         sq += mslots[b * kDwSlots + k];
     }
-    const float mse = sq * inv_total;
-    out[b * 4 + 0] = mse + lam_px * rate;
+    // dist4: [B][4] of the MS-SSIM stage (ccmi_train_step_dist): D and MSE come from there
+    const float mse = dist4 ? dist4[b * 4 + 2] : sq * inv_total;
+    out[b * 4 + 0] = (dist4 ? dist4[b * 4 + 0] : mse) + lam_px * rate;
     out[b * 4 + 1] = mse;
     out[b * 4 + 2] = rate;
     out[b * 4 + 3] = sqrtf(acc4[b * 4 + 2]);
@@ -2873,7 +2875,7 @@ __global__ void t_adam(const float *__restrict__ G, float *__restrict__ lat, flo
 {
     const int b = blockIdx.y;
     const int64_t i = (int64_t)blockIdx.x * kT + threadIdx.x;
-    if (A.loss_out && i == 0) finish_row(acc4, A.rslots, A.mslots, A.inv_total, A.lam_px, A.loss_out, b); // (t_finish folded in)
+    if (A.loss_out && i == 0) finish_row(acc4, A.rslots, A.mslots, A.inv_total, A.lam_px, A.loss_out, b, A.dist4); // (t_finish folded in)
     if (i >= A.n || (A.latents_only && i >= A.N)) return;
     if (A.bc && A.bc[2 * b + 1] < 0.f) return; // frozen frame (adam_steps <= 0)
     float coef = 1.f;
@@ -2893,10 +2895,10 @@ __global__ void t_adam(const float *__restrict__ G, float *__restrict__ lat, flo
 // one thread per frame, ceil(B / 64) blocks of 64 (one block of B threads is no valid launch
 // past B = 1024)
 __global__ void t_finish(const float *__restrict__ acc4, const float *__restrict__ rslots, const float *__restrict__ mslots,
-                         float inv_total, float lam_px, float *__restrict__ out, int B)
+                         float inv_total, float lam_px, float *__restrict__ out, int B, const float *__restrict__ dist4)
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
-    if (b < B) finish_row(acc4, rslots, mslots, inv_total, lam_px, out, b);
+    if (b < B) finish_row(acc4, rslots, mslots, inv_total, lam_px, out, b, dist4);
 }
 
 // ------------------------------------------------------------------ host planning
@@ -3250,13 +3252,52 @@ extern "C" size_t ccmi_train_param_count(const ccmi_train_args *a)
     return (size_t)pl.g.P;
 }
 
-extern "C" size_t ccmi_train_workspace_bytes(const ccmi_train_args *a)
+// The MS-SSIM stage of ccmi_train_step_dist: the step's raw output [B][3][H][W] as the planes of
+// ccmi_msssim_args (4:2:0: chroma at even rows and columns, as t_loss), the target as Y.  x, grad, out
+// and the workspace are left to the caller; grad is set to a non-null placeholder so that the
+// workspace counts the gradient's part.
+static ccmi_msssim_args dist_args(const ccmi_train_args *a, const ccmi_train_dist *d, int H, int W)
+{
+    ccmi_msssim_args m{};
+    const int64_t npx = (int64_t)H * W;
+    m.batch = a->batch;
+    m.n_planes = 3;
+    m.n_scales = d->n_scales;
+    m.clamp = 1;
+    for (int p = 0; p < 3; ++p) {
+        const int sub = a->yuv420 && p > 0 ? 2 : 1;
+        m.h[p] = H / sub;
+        m.w[p] = W / sub;
+        m.x_off[p] = p * npx;
+        m.x_pitch[p] = W;
+        m.x_sub[p] = sub;
+        m.channel_weights[p] = d->channel_weights[p];
+    }
+    m.x_stride = 3 * npx;
+    m.y = a->target;
+    m.y_stride = a->target_stride;
+    for (int s = 0; s < 5; ++s) m.weights[s] = d->weights[s];
+    m.alpha_mse = d->alpha_mse;
+    m.beta_ms = d->beta_ms;
+    return m;
+}
+
+extern "C" size_t ccmi_train_workspace_bytes_dist(const ccmi_train_args *a, const ccmi_train_dist *d)
 {
     if (!a) return 0;
     Plan pl;
     if (make_plan(a, pl)) return 0;
-    return pl.total;
+    if (!d) return pl.total;
+    ccmi_msssim_args m = dist_args(a, d, pl.g.H, pl.g.W);
+    float one;
+    m.grad = &one; // counted, never written
+    const size_t n = ccmi_msssim_workspace_bytes(&m);
+    if (!n) return 0;
+    // after the step's own plan: the stage's [B][4] row, then its workspace
+    return align256(pl.total) + align256(sizeof(float) * 4 * (size_t)a->batch) + n;
 }
+
+extern "C" size_t ccmi_train_workspace_bytes(const ccmi_train_args *a) { return ccmi_train_workspace_bytes_dist(a, nullptr); }
 
 // The ARM's side stream (CCMI_ARM_OVERLAP): leased from the process-wide pool for one call
 // (ccmi_api.cpp; st[0], events ev[0] fork and ev[1] join).  SideJoin orders the side stream
@@ -3291,13 +3332,35 @@ __global__ void t_diag_spin(uint64_t ticks)
 }
 #endif
 
-extern "C" int ccmi_train_step(const ccmi_train_args *a, void *stream)
+extern "C" int ccmi_train_step(const ccmi_train_args *a, void *stream) { return ccmi_train_step_dist(a, nullptr, stream); }
+
+extern "C" int ccmi_train_step_dist(const ccmi_train_args *a, const ccmi_train_dist *d, void *stream)
 {
     if (!a || !a->latent || !a->params || !a->target) return ccmi_set_error(CCMI_ERR_ARG, "train: null argument");
     Plan pl;
     if (int rc = make_plan(a, pl)) return rc;
-    if (!a->workspace || a->workspace_bytes < pl.total)
-        return ccmi_set_error(CCMI_ERR_ARG, "train: workspace of %zu bytes needed", pl.total);
+    size_t need = pl.total;
+    ccmi_msssim_args ms{};
+    float *dist4 = nullptr; // the MS-SSIM stage's [B][4] row (finish_row reads D and MSE from it)
+    if (d) {
+        if (a->grad_raw) return ccmi_set_error(CCMI_ERR_ARG, "train: a distortion and grad_raw are exclusive");
+        if (a->target_stride <= 0) return ccmi_set_error(CCMI_ERR_ARG, "train: a distortion needs a target per frame");
+        need = ccmi_train_workspace_bytes_dist(a, d);
+        if (!need) return CCMI_ERR_ARG; // the message is ccmi_msssim's
+    }
+    if (!a->workspace || a->workspace_bytes < need)
+        return ccmi_set_error(CCMI_ERR_ARG, "train: workspace of %zu bytes needed", need);
+    if (d) {
+        uint8_t *w8 = static_cast<uint8_t *>(a->workspace) + align256(pl.total);
+        ms = dist_args(a, d, pl.g.H, pl.g.W);
+        dist4 = d->dist_out ? d->dist_out : reinterpret_cast<float *>(w8);
+        ms.out = dist4;
+        ms.x = reinterpret_cast<float *>(static_cast<uint8_t *>(a->workspace) + pl.z[pl.g.n_sp]);
+        ms.workspace = w8 + align256(sizeof(float) * 4 * (size_t)a->batch);
+        ms.workspace_bytes = need - (size_t)(static_cast<uint8_t *>(ms.workspace) - static_cast<uint8_t *>(a->workspace));
+        ms.grad = a->forward_only ? nullptr : reinterpret_cast<float *>(static_cast<uint8_t *>(a->workspace) + pl.graw);
+        if (int rc = ccmi_msssim_check(&ms)) return rc;
+    }
     if (a->update && (!a->adam_m || !a->adam_v || (a->step < 1 && !a->adam_steps)))
         return ccmi_set_error(CCMI_ERR_ARG, "train: Adam state and step >= 1 needed to update");
     if ((a->quantizer == CCMI_Q_SOFTROUND || a->quantizer == CCMI_Q_SOFTROUND_ALONE || a->quantizer == CCMI_Q_STE) &&
@@ -3399,7 +3462,7 @@ extern "C" int ccmi_train_step(const ccmi_train_args *a, void *stream)
                   a->param_stride, F(pl.z[0]), nullptr, 0); // two pixels per thread
     // the training step's MSE fused into the last 3x3 layer (no separate t_loss pass over the
     // synthesis output); the output itself is stored only when something reads it
-    const bool fuse_loss = !a->forward_only && !a->grad_raw && g.n_sp > 0;
+    const bool fuse_loss = !d && !a->forward_only && !a->grad_raw && g.n_sp > 0;
     for (int i = 0; i < g.n_sp; ++i) {
         const bool fl = fuse_loss && i == g.n_sp - 1;
         const int store = !fl || a->raw_out || g.sp_relu[i];
@@ -3422,18 +3485,26 @@ extern "C" int ccmi_train_step(const ccmi_train_args *a, void *stream)
         if (a->loss_out) {
             // with a real target (target_stride > 0) the loss row holds the built-in MSE too;
             // otherwise (autograd: the loss lives in torch) MSE reads 0 and loss = lmbda-rate
-            if (a->target && a->target_stride > 0)
+            if (d) {
+                if (int rc = ccmi_launch_msssim(&ms, s)) return rc;
+            } else if (a->target && a->target_stride > 0)
                 hipLaunchKernelGGL(t_loss, dim3(sum_blocks(npx, kLossPx), B), dim3(kT), 0, s, F(pl.z[g.n_sp]), g,
                                    a->target, a->target_stride, a->yuv420, graw, acc4);
             const float total = a->yuv420 ? (float)(npx + 2 * (int64_t)(g.H / 2) * (g.W / 2)) : (float)(3 * npx);
-            hipLaunchKernelGGL(t_finish, dim3((unsigned)ccmi_div_up(B, 64)), dim3(64), 0, s, acc4, F(pl.rslots), F(pl.mslots), 1.f / total, lam_px, a->loss_out, B);
+            hipLaunchKernelGGL(t_finish, dim3((unsigned)ccmi_div_up(B, 64)), dim3(64), 0, s, acc4, F(pl.rslots), F(pl.mslots), 1.f / total, lam_px, a->loss_out, B, dist4);
         }
         CCMI_HIP_CHECK(hipGetLastError());
         return CCMI_OK;
     }
     if (a->grad_raw) // the caller's d loss / d raw output (autograd); no built-in MSE term
         CCMI_HIP_CHECK(hipMemcpyAsync(graw, a->grad_raw, sizeof(float) * 3 * npx * B, hipMemcpyDeviceToDevice, s));
-    else if (!fuse_loss)
+    else if (d) {
+        // the MS-SSIM stage in t_loss's place: it writes d loss / d raw at the sampled positions; the
+        // chroma planes' unsampled ones (4:2:0) are cleared first, every frame's pair in one memset
+        if (a->yuv420)
+            CCMI_HIP_CHECK(hipMemset2DAsync(graw + npx, sizeof(float) * 3 * npx, 0, sizeof(float) * 2 * npx, (size_t)B, s));
+        if (int rc = ccmi_launch_msssim(&ms, s)) return rc;
+    } else if (!fuse_loss)
         hipLaunchKernelGGL(t_loss, dim3(sum_blocks(npx, kLossPx), B), dim3(kT), 0, s, F(pl.z[g.n_sp]), g, a->target, a->target_stride,
                            a->yuv420, graw, acc4);
 
@@ -3558,13 +3629,13 @@ extern "C" int ccmi_train_step(const ccmi_train_args *a, void *stream)
                        GS, acc4);
     const float total = a->yuv420 ? (float)(npx + 2 * (int64_t)(g.H / 2) * (g.W / 2)) : (float)(3 * npx);
     if (a->loss_out && !a->update)
-        hipLaunchKernelGGL(t_finish, dim3((unsigned)ccmi_div_up(B, 64)), dim3(64), 0, s, acc4, F(pl.rslots), F(pl.mslots), 1.f / total, lam_px, a->loss_out, B);
+        hipLaunchKernelGGL(t_finish, dim3((unsigned)ccmi_div_up(B, 64)), dim3(64), 0, s, acc4, F(pl.rslots), F(pl.mslots), 1.f / total, lam_px, a->loss_out, B, dist4);
     if (a->update) {
         const double bc1 = 1.0 - std::pow((double)a->beta1, a->step), bc2 = 1.0 - std::pow((double)a->beta2, a->step);
         AdamArgs A{(float)(a->lr / bc1), (float)(1.0 / std::sqrt(bc2)), a->beta1, a->beta2, a->eps, a->clip, g.N,
                    a->update == 2 ? 1 : 0, GS, GS,
                    a->latent_stride, a->param_stride, (int64_t)a->latent_stride + a->param_stride, nullptr,
-                   a->loss_out, F(pl.rslots), F(pl.mslots), 1.f / total, lam_px};
+                   a->loss_out, F(pl.rslots), F(pl.mslots), 1.f / total, lam_px, dist4};
         if (a->adam_steps) {
             A.bc = F(pl.bc);
             hipLaunchKernelGGL(t_adam_bc, dim3((unsigned)ccmi_div_up(B, 64)), dim3(64), 0, s, a->adam_steps, (double)a->lr,

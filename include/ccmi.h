@@ -1434,6 +1434,88 @@ size_t ccmi_train_param_count(const ccmi_train_args *args);
 size_t ccmi_train_workspace_bytes(const ccmi_train_args *args);
 int ccmi_train_step(const ccmi_train_args *args, void *stream);
 
+/* ------------------------------------------------------------------------- */
+/* MS-SSIM distortion: value and gradient for batches of frames, on the GPU     */
+/* ------------------------------------------------------------------------- */
+
+/* D = alpha_mse MSE + beta_ms (1 - MS) of `batch` frames x against targets y, and optionally dD/dx.
+ * tests/msssim_ref.py restates this text in torch (any dtype, gradient by autograd) and
+ * tests/test_msssim_gpu.py holds the kernels to its float64 run.
+ *
+ * Inputs.  For frame b and plane p < n_planes <= 3, X_p and Y_p have h[p] x w[p] samples.  Sample
+ *   (i, j) of X_p is x[b x_stride + x_off[p] + i x_sub[p] x_pitch[p] + j x_sub[p]], x_sub 1 or 2, so
+ *   one call reads the training step's raw output [3][H][W] under 4:2:0 (chroma at even rows and
+ *   columns: x_off = {0, HW, 2HW}, x_pitch = W, x_sub = {1, 2, 2}, h[1] = H / 2, w[1] = W / 2), a packed
+ *   4:4:4 frame and the packed Y, U, V of ccmi_post_f32.  With clamp != 0, X = min(max(x, 0), 1) (the
+ *   train-mode frame output).  Y is used as given: frame b's planes packed h[p] x w[p] one after the
+ *   other at y + b y_stride; y_stride 0 is one target for every frame.
+ * Window.  g_k = exp(-(k - 5)^2 / 4.5) / sum, k = 0 .. 10, computed in double and rounded once to
+ *   float32; separable, "valid" (no padding): a plane of h x w has (h - 10)(w - 10) positions.
+ * Constants.  C1 = 1e-4, C2 = 9e-4 (data range 1).
+ * Per scale s = 0 .. S - 1, 1 <= S = n_scales <= 5, in float32 (G* is the window):
+ *     mu_x = G*X, mu_y = G*Y
+ *     s_xx = G*(X X) - mu_x^2, s_yy likewise, s_xy = G*(X Y) - mu_x mu_y
+ *     cs = (2 s_xy + C2) / (s_xx + s_yy + C2),  l = (2 mu_x mu_y + C1) / (mu_x^2 + mu_y^2 + C1)
+ *     v_s = mean over the positions of cs (s < S - 1), of cs l (s = S - 1)
+ *   The kernels form the statistics of X - 1/2 and Y - 1/2: the variances are the same and the
+ *   cancellation smaller.
+ * Next scale.  A 2 x 2 mean as avg_pool2d(2, padding = size mod 2, count_include_pad = True):
+ *     h_{s+1} = ceil(h_s / 2),  X_{s+1}(i, j) = 1/4 sum_{a, b in {0, 1}} X_s(2i - ph + a, 2j - pw + b),
+ *     ph = h_s mod 2, pw = w_s mod 2, samples outside the plane 0, the divisor always 4; Y likewise.
+ *   Every scale of every plane needs min(h_s, w_s) >= 11 (five scales: a side of at least 161, the
+ *   chain 161, 81, 41, 21, 11), else CCMI_ERR_ARG naming plane and scale.
+ * Combination.  MS_p = prod_s max(v_s, 0)^weights[s]; a plane with any v_s <= 0 has MS_p = 0 and
+ *   gradient 0.  MS = sum_p channel_weights[p] MS_p.  MSE = sum over every sample of every plane of
+ *   (X - Y)^2 / the number of samples (loss.py _compute_mse's weighting).
+ * Outputs.  out[b][4] = { D, MS, MSE, min over (p, s) of v_s before the max } (the last entry shows
+ *   that the max was not hit).  grad, when given, has x's addressing and stride; only the sampled
+ *   positions are written: dD/dx through the clamp, 0 where x lies outside [0, 1] (as the step's MSE).
+ * Determinism.  The sums behind v_s and the MSE are one partial per workgroup, added in a fixed
+ *   order (no float atomics): a frame gives the same bits alone, at any row of any batch, on every call.
+ * Workspace.  With al(n) = 4 n rounded up to a multiple of 256 bytes, B = batch, and per frame
+ *   pyr = sum_p sum_{s >= 1} h_s w_s, pos = sum_p sum_s (h_s - 10)(w_s - 10),
+ *   tiles = sum_p sum_s ceil((h_s - 10) / 22) ceil((w_s - 10) / 32):
+ *     2 al(B pyr) + al(2 B tiles) + al(16 B), and with grad + al(B pyr) + al(3 B pos).
+ * CCMI_ERR_ARG with a message, before any HIP call: a null args / out / x / y, batch outside
+ *   1 .. 65535, n_planes or n_scales out of range, a plane below the size rule, a weight, channel
+ *   weight, alpha_mse or beta_ms that is negative or not finite, x_sub outside {1, 2}, x_off < 0, an
+ *   x_pitch shorter than a row of samples, 0 < y_stride < a frame's samples, a short workspace.
+ * Not measured: rate-distortion results of streams tuned for this metric. */
+typedef struct ccmi_msssim_args {
+    int batch, n_planes, n_scales, clamp;
+    int h[3], w[3];
+    const float *x;
+    int64_t x_stride;       /* per frame */
+    int64_t x_off[3], x_pitch[3];
+    int x_sub[3];
+    const float *y;
+    int64_t y_stride;
+    float weights[5], channel_weights[3], alpha_mse, beta_ms;
+    float *out;             /* [batch][4] */
+    float *grad;            /* optional */
+    void *workspace;        /* ccmi_msssim_workspace_bytes() (0 for invalid shapes; grad counts) */
+    size_t workspace_bytes;
+} ccmi_msssim_args;
+size_t ccmi_msssim_workspace_bytes(const ccmi_msssim_args *args);
+int ccmi_msssim_f32(const ccmi_msssim_args *args, void *stream);
+
+/* The overfit step with D of ccmi_msssim_args as its distortion, in one pass: the planes are the
+ * step's train-mode output (clamp on; 4:2:0: chroma of H / 2 x W / 2 at even rows and columns of the
+ * raw output) against `target`.  dist = NULL is ccmi_train_step: the same launches.  With a dist the
+ * last synthesis layer stores its output (no fused MSE), under 4:2:0 one memset clears the chroma
+ * planes of d loss / d raw, and the MS-SSIM kernels write the rest of it.  loss_out[b] =
+ * { D + lmbda rate_bits / (H W), MSE, rate_bits, grad_norm }; dist_out[b] as ccmi_msssim_args.out.
+ * forward_only with a target (target_stride > 0) fills loss_out and dist_out and writes no gradient.
+ * CCMI_ERR_ARG: dist together with grad_raw, and what ccmi_msssim_f32 refuses.  The workspace is
+ * ccmi_train_workspace_bytes_dist(args, dist) (= ccmi_train_workspace_bytes for dist = NULL). */
+typedef struct ccmi_train_dist {
+    int n_scales;
+    float weights[5], channel_weights[3], alpha_mse, beta_ms;
+    float *dist_out;        /* optional [batch][4] */
+} ccmi_train_dist;
+size_t ccmi_train_workspace_bytes_dist(const ccmi_train_args *args, const ccmi_train_dist *dist);
+int ccmi_train_step_dist(const ccmi_train_args *args, const ccmi_train_dist *dist, void *stream);
+
 /* quantize (quantizer.py:116-232) of n values x (already multiplied by the encoder gain):
  * y = Q(x) and dy = dQ/dx as the reference's autograd sees it (softround derivative for
  * "ste", 1 for "true_ste" and "none", 0 for "hardround"); noise: optional [n] additive
