@@ -30,6 +30,91 @@ def test_frames_are_off_the_floor_and_well_conditioned(case):
         assert all(math.isfinite(x) for x in f.eval64)
 
 
+def test_default_setting_gives_the_same_frame_bit_for_bit():
+    """frame()'s quantiser setting defaults to the warm-up's: a call that spells the defaults out
+    gives the cached frame's inputs and float64 gradients bit for bit (the same generator calls in
+    the same order)."""
+    c = R.CASE["hop"]
+    f = R.case_frames(c)[1]
+    g = R.frame(c.H, c.W, R.case_seed(c, 1), c.yuv420, qtype="softround", ntype="kumaraswamy", T=R.TEMP, nparam=R.NOISE_A,
+                lat_plant=None, **c.arch)
+    assert g is not f
+    for k in ("lat", "params", "target", "noise"):
+        assert torch.equal(getattr(f, k), getattr(g, k)), k
+    assert f.row64 == g.row64 and f.row32 == g.row32 and f.eval64 == g.eval64
+    assert len(f.g64) == len(g.g64) and all(np.array_equal(a, b) for a, b in zip(f.g64, g.g64))
+    assert all(np.array_equal(a, b) for a, b in zip(f.g32, g.g32))
+    assert (f.e32, f.p_min, f.S) == (g.e32, g.p_min, g.S)
+    # 0.05 randn, as before the plant existed
+    gen = torch.Generator().manual_seed(1000 + R.case_seed(c, 1))
+    lat = torch.cat([(0.05 * torch.randn(h, w, generator=gen)).reshape(-1) for h, w in f.mp.sizes])
+    assert torch.equal(lat, f.lat)
+
+
+SCHEDULE_FRAMES = [(s, c) for s in R.SCHEDULE + [R.STE_END] for c in R.SCHEDULE_CASES]
+
+
+@pytest.mark.parametrize("setting,case", SCHEDULE_FRAMES, ids=lambda x: x if isinstance(x, str) else x.name)
+def test_schedule_frames_are_off_the_floor_and_well_conditioned(setting, case):
+    c = R.CASE[case]
+    frs = R.schedule_frames(setting, case)
+    assert len(frs) == R.SCHEDULE_D
+    e = [f.e32 for f in frs]
+    print(f"\n{setting.name} {case}: e32 2^{math.log2(min(e)):.1f} .. 2^{math.log2(max(e)):.1f}, "
+          f"p_min {min(f.p_min for f in frs):.1e}")
+    for d, f in enumerate(frs):
+        what = f"{setting.name} {case} frame {d} (seed {R.schedule_seed(setting, case, d)})"
+        assert f.e32 <= R.E32_MAX, (what, f.e32)
+        assert f.p_min >= R.P_MIN, (what, f.p_min)
+        assert -4.6 + 1 <= f.ls_lo and f.ls_hi <= 5 - 1, (what, f.ls_lo, f.ls_hi)
+        assert (f.N, f.P) == (R.units(c.H, c.W, **c.arch).N, R.units(c.H, c.W, **c.arch).P)
+        if setting.name == "hardround":
+            # dq = 0: the latent gradients are exactly zero, and nothing else is
+            assert all(not f.g64[i].any() and f.S[i] == 0 for i in range(f.n_grids))
+            assert min(f.S[f.n_grids:]) > 0, (what, f.S)
+            assert not f.noise.any()
+        else:
+            assert min(f.S) > 0, (what, f.S)
+        for a, b in zip(f.row32, f.row64):
+            assert abs(a - b) <= 1e-6 * abs(b), (what, a, b)
+        assert (setting.ntype == "none") == (not f.noise.any())
+        if setting.ntype == "gaussian":
+            assert 0.9 * setting.nparam < float(f.noise.std()) < 1.1 * setting.nparam
+        x = f.lat * f.gain
+        if setting.lat_plant == "coarse":
+            assert bool(torch.round(x[-f.sizes[f.n_grids - 1]:]).any())
+        if setting.lat_plant == "half":
+            # on the peak of ste's derivative at T = 1e-4: |frac - 1/2| <= 8.5e-4 everywhere
+            fr = (x.double() - torch.floor(x.double()) - 0.5).abs()
+            assert float(fr.max()) <= 8.5e-4 and float(fr.min()) == 0
+
+
+def test_schedule_table():
+    assert [s.name for s in R.SCHEDULE] == ["warmup-a1", "main-start", "main-mid", "main-end", "ste-warm", "true-ste",
+                                            "alone-end", "noise-only", "hardround"]
+    m = R.SETTING
+    assert (m["main-start"].T, m["main-start"].nparam) == (0.3, 0.25)
+    assert (m["main-mid"].T, m["main-mid"].nparam) == (0.2, 0.175)
+    assert (m["main-end"].T, m["main-end"].nparam) == (0.1, 0.1)
+    assert (m["warmup-a1"].qtype, m["warmup-a1"].ntype, m["warmup-a1"].nparam) == ("softround", "kumaraswamy", 1.0)
+    assert (R.STE_END.T, R.STE_END.qtype) == (1e-4, "true_ste")
+    # the preset's own figures (ccmi/train.py)
+    from ccmi import train as T
+    main = [p for p in T.C3X_PHASES if p.quantizer_type == "softround"]
+    assert {p.softround_temperature for p in main} == {(0.3, 0.1)} and {p.noise_parameter for p in main} == {(0.25, 0.1)}
+    ste = [p for p in T.C3X_PHASES if p.quantizer_type == "ste"]
+    assert ste and all(p.softround_temperature == (1e-4, 1e-4) for p in ste)
+    # seeds: distinct among themselves and from every case's
+    seeds = [R.schedule_seed(s, c, d) for s, c in SCHEDULE_FRAMES if s.name != "hardround" for d in range(R.SCHEDULE_D)]
+    older = [R.case_seed(c, d) for c in OWN_FRAMES for d in range(c.D)]
+    assert len(set(seeds + older)) == len(seeds) + len(older)
+    for (name, case, d) in R.SCHEDULE_RESEED:
+        assert (name in R.SETTING or name == R.STE_END.name) and case in R.SCHEDULE_CASES and d < R.SCHEDULE_D
+    # hardround's frames are true-ste's, latent gradients zeroed
+    a, b = R.schedule_frames("hardround", "hop")[0], R.schedule_frames("true-ste", "hop")[0]
+    assert a.row64 == b.row64 and all(np.array_equal(x, y) for x, y in zip(a.g64[a.n_grids:], b.g64[b.n_grids:]))
+
+
 def test_cases_share_or_own_their_frames():
     for c in R.CASES:
         o = R.CASE[c.frames_of]

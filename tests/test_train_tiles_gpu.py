@@ -71,35 +71,64 @@ def _check_rows(loss, ref_rows, idx, what):
     return worst
 
 
-def _check_case(case, gpu):
-    frs = R.case_frames(case)
-    B = R.batch_of(case, _cus(gpu))
-    e = max(f.e32 for f in frs)
-    assert e <= R.E32_MAX
-    of, noise, idx = _overfitter(frs, B, gpu)
-    gout = torch.full((B, of.N + of.P), float("nan"), device=gpu)
-    loss = of.step("softround", "kumaraswamy", R.TEMP, R.NOISE_A, R.LMBDA, update=False, noise=noise, grad_out=gout)
-    torch.cuda.synchronize()
-    what = f"{case.name} B={B}"
-    _check_rows(loss, [f.row64 for f in frs], idx, what)
-    # every entry of every frame, on the device: [D, N + P] references and bounds, cycled by idx
+WARMUP = ("softround", "kumaraswamy", R.TEMP, R.NOISE_A)   # quantiser, noise, temperature, noise parameter
+
+
+def _ratio(err, bnd):
+    """err / bnd entry by entry; where the bound is 0 (a gradient that is zero by definition) the
+    error has to be 0 too."""
+    return torch.where(bnd > 0, err / bnd, torch.where(err == 0, 0.0, float("inf")).to(err.dtype))
+
+
+def _check_grads(frs, e, idx, gout, loss, what, norm=True, columns=None):
+    """gout [B, N + P] (and loss[:, 3], the norm) against the frames' float64 references, every
+    entry of every frame on the device: [D, N + P] references and bounds, cycled by idx.
+    columns: a slice of the row to check (all of it by default).  Returns the worst ratio per
+    tensor."""
+    gpu = gout.device
     ref = torch.tensor(np.stack([np.concatenate(f.g64) for f in frs]), device=gpu)
     bnd = torch.tensor(np.stack([np.repeat(R.grad_bounds(f, e), f.sizes) for f in frs]), device=gpu)
     assert bool(torch.isfinite(gout).all()), f"{what}: a gradient entry is not finite (or not written)"
-    ratio = (gout.double() - ref[idx]).abs() / bnd[idx]
+    ratio = _ratio((gout.double() - ref[idx]).abs(), bnd[idx])
+    lo, hi, _ = (columns or slice(None)).indices(gout.shape[1])
     per, o = [], 0
     for n in frs[0].sizes:
-        per.append(float(ratio[:, o:o + n].max()))
+        per.append(float(ratio[:, o:o + n].max()) if lo <= o and o + n <= hi else 0.0)
         o += n
-    nrm = [R.norm_bound(f, e) for f in frs]
-    nref = torch.tensor([r for r, _ in nrm], dtype=torch.float64, device=gpu)[idx]
-    nbnd = torch.tensor([b for _, b in nrm], dtype=torch.float64, device=gpu)[idx]
-    nratio = (loss[:, 3].double() - nref).abs() / nbnd
+    nr = 0.0
+    if norm:
+        nrm = [R.norm_bound(f, e) for f in frs]
+        nref = torch.tensor([r for r, _ in nrm], dtype=torch.float64, device=gpu)[idx]
+        nbnd = torch.tensor([b for _, b in nrm], dtype=torch.float64, device=gpu)[idx]
+        nratio = (loss[:, 3].double() - nref).abs() / nbnd
+        nr = float(nratio.max())
     worst_t = int(np.argmax(per))
     print(f"{what}: e {e:.2e}, worst gradient error / bound {max(per):.3f} (tensor {worst_t} of {len(per)}), "
-          f"latents {max(per[:frs[0].n_grids]):.3f}, norm {float(nratio.max()):.3f}")
+          f"latents {max(per[:frs[0].n_grids]):.3f}, norm {nr:.3f}")
     assert max(per) <= 1.0, (what, "tensor", worst_t, per)
-    assert float(nratio.max()) <= 1.0, (what, "gradient norm", float(nratio.max()), int(nratio.argmax()))
+    if norm:
+        assert nr <= 1.0, (what, "gradient norm", nr, int(nratio.argmax()))
+    return per
+
+
+def _check_frames(frs, B, gpu, what, setting=WARMUP, of=None):
+    """One step(update=False) of B frames cycling frs at a quantiser setting, noise handed in:
+    loss rows, every gradient entry and the norm against the frames' references.  of: an
+    (Overfitter, noise, idx) of these frames to reuse.  Returns it."""
+    e = max(f.e32 for f in frs)
+    assert e <= R.E32_MAX
+    of, noise, idx = of or _overfitter(frs, B, gpu)
+    gout = torch.full((B, of.N + of.P), float("nan"), device=gpu)
+    loss = of.step(*setting, R.LMBDA, update=False, noise=noise, grad_out=gout)
+    torch.cuda.synchronize()
+    _check_rows(loss, [f.row64 for f in frs], idx, what)
+    _check_grads(frs, e, idx, gout, loss, what)
+    return of, noise, idx
+
+
+def _check_case(case, gpu):
+    B = R.batch_of(case, _cus(gpu))
+    _check_frames(R.case_frames(case), B, gpu, f"{case.name} B={B}")
 
 
 def _cases(group):
