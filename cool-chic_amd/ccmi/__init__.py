@@ -23,7 +23,7 @@ OK, ERR_ARG, ERR_HIP, ERR_UNSUPPORTED, ERR_BITSTREAM, ERR_IO = range(6)
 # Public symbols of include/ccmi.h (checked by tests/test_abi.py).
 EXPORTED = [
     "ccmi_last_error", "ccmi_version", "ccmi_device_count",
-    "ccmi_arm_forward_f32", "ccmi_arm_forward_f32_form", "ccmi_arm_pack_host", "ccmi_arm_tile_map", "ccmi_arm_context_f32", "ccmi_arm_mlp_f32", "ccmi_ups_workspace_bytes", "ccmi_ups_forward_f32",
+    "ccmi_arm_forward_f32", "ccmi_arm_forward_f32_form", "ccmi_arm_pack_host", "ccmi_arm_tile_map", "ccmi_arm_context_f32", "ccmi_arm_mlp_f32", "ccmi_ups_workspace_bytes", "ccmi_ups_forward_f32", "ccmi_ups_forward_f32_form",
     "ccmi_syn_workspace_bytes", "ccmi_syn_forward_f32", "ccmi_post_f32", "ccmi_decode_forward_f32",
     "ccmi_fused_run_plan",
     "ccmi_decode_file", "ccmi_decode_batch", "ccmi_decode_output_size", "ccmi_decode_last_timing",
@@ -113,6 +113,7 @@ class DecodeArgs(C.Structure):
 
 ARM_FORM_DEFAULT, ARM_FORM_ROWS, ARM_FORM_PAIRS = 0, 1, 2  # ccmi_arm_forward_f32_form (CCMI_ARM_FORM_*)
 HEAD_DEFAULT, HEAD_VALU, HEAD_MFMA, HEAD_GENERIC = 0, 1, 2, 3  # ccmi_decode_args.head (CCMI_HEAD_*)
+UPS_FORM_DEFAULT, UPS_FORM_LEVELS = 0, 1  # ccmi_ups_forward_f32_form (CCMI_UPS_FORM_*)
 
 
 _lib = None
@@ -147,6 +148,9 @@ def lib() -> C.CDLL:
         L.ccmi_arm_forward_f32_form.restype = C.c_int
         L.ccmi_arm_pack_host.argtypes = [C.POINTER(C.c_float), C.c_int, C.c_int, C.POINTER(C.c_float)]
         L.ccmi_arm_pack_host.restype = C.c_int
+    if hasattr(L, "ccmi_ups_forward_f32_form"):  # absent from older builds loaded for A/B runs
+        L.ccmi_ups_forward_f32_form.argtypes = [C.POINTER(UpsArgs), C.c_void_p, C.c_int]
+        L.ccmi_ups_forward_f32_form.restype = C.c_int
     if hasattr(L, "ccmi_arm_tile_map"):  # absent from older builds loaded for A/B runs
         L.ccmi_arm_tile_map.argtypes = [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int, C.c_int64, C.c_int,
                                         C.POINTER(C.c_int), C.POINTER(C.c_int64)]

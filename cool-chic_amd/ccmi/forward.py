@@ -89,8 +89,9 @@ def arm_forward(latent: torch.Tensor, sizes, params: torch.Tensor, dim_arm: int,
 
 
 def ups_forward(latent: torch.Tensor, sizes, params: torch.Tensor, ups_k: int, n_ups: int, pre_k: int, n_pre: int,
-                gain: float = 16.0, quantize: bool = True) -> torch.Tensor:
-    """latent [B, N] flat grids -> [B, L, H, W] dense synthesis input."""
+                gain: float = 16.0, quantize: bool = True, form: int = 0) -> torch.Tensor:
+    """latent [B, N] flat grids -> [B, L, H, W] dense synthesis input.
+    form: the pyramid's form (ccmi.UPS_FORM_*); every form gives the same bits."""
     squeeze = latent.dim() == 1
     latent = latent.unsqueeze(0) if squeeze else latent
     B, N = latent.shape
@@ -112,7 +113,10 @@ def ups_forward(latent: torch.Tensor, sizes, params: torch.Tensor, ups_k: int, n
                 quantize=int(bool(quantize)), ups_k=ups_k, n_ups=n_ups, pre_k=pre_k, n_pre=n_pre,
                 params=ptr(params), param_stride=pstride, out=ptr(out), out_stride=L * H * W,
                 workspace=ptr(ws), workspace_bytes=nws, batch=B)
-    check(lib().ccmi_ups_forward_f32(a, stream_handle(latent.device)))
+    if form:
+        check(lib().ccmi_ups_forward_f32_form(a, stream_handle(latent.device), int(form)))
+    else:
+        check(lib().ccmi_ups_forward_f32(a, stream_handle(latent.device)))
     return out[0] if squeeze else out
 
 
@@ -179,7 +183,7 @@ def post_forward(x: torch.Tensor, bitdepth: int = 8, yuv420: bool = False) -> to
 def decode_forward(latent: torch.Tensor, sizes, ups_params: torch.Tensor, ups_k: int, n_ups: int, pre_k: int,
                    n_pre: int, layers, syn_params: torch.Tensor, gain: float = 16.0, quantize: bool = True,
                    bitdepth: int = 8, yuv420: bool = False, head: int = 0, fold: bool = False,
-                   walk: bool = True) -> torch.Tensor:
+                   walk: bool = True, ups_levels: bool = False) -> torch.Tensor:
     """Fused upsampling -> synthesis -> post (ccmi_decode_forward_f32): latent [B, N] ->
     post-processed frames (layout of post_forward), or with bitdepth=0 the raw synthesis
     output [B, C_out, H, W].  head: ccmi.HEAD_* (the 1x1 head on the VALU or on f32 MFMA).
@@ -187,6 +191,8 @@ def decode_forward(latent: torch.Tensor, sizes, ups_params: torch.Tensor, ups_k:
     bit 3, opt-in: the same values bit for bit, measured slower).
     walk=False gives every workgroup of the fused kernel a single window instead of a run of
     them (stages bit 4: the same values bit for bit, every window pays the vertical halo).
+    ups_levels=True runs the pyramid one launch per level (stages bit 5, ccmi.UPS_FORM_LEVELS: the
+    same values bit for bit).
     Raises CcmiError(ERR_UNSUPPORTED) for architectures without a fused kernel (use
     ups_forward / syn_forward / post_forward)."""
     squeeze = latent.dim() == 1
@@ -223,7 +229,7 @@ def decode_forward(latent: torch.Tensor, sizes, ups_params: torch.Tensor, ups_k:
                   B, L, H, W, syn_stride)
     y.in_ = None
     a = DecodeArgs(ups=u, syn=y, bitdepth=int(bitdepth), yuv420=int(bool(yuv420)), out=ptr(out), out_stride=n,
-                   head=int(head), stages=(8 if fold else 0) | (0 if walk else 16))
+                   head=int(head), stages=(8 if fold else 0) | (0 if walk else 16) | (32 if ups_levels else 0))
     check(lib().ccmi_decode_forward_f32(a, stream_handle(latent.device)))
     if bitdepth == 0 or not yuv420:
         out = out.view(B, n_out, H, W)

@@ -36,7 +36,8 @@ static inline int ccmi_div_up(int a, int b) { return (a + b - 1) / b; }
 
 // Stage launchers (return CCMI_OK or an error code; never exit()).
 int ccmi_launch_arm_f32(const ccmi_arm_args *a, hipStream_t s, int form);
-int ccmi_launch_ups_f32(const ccmi_ups_args *a, hipStream_t s);
+int ccmi_launch_ups_f32(const ccmi_ups_args *a, hipStream_t s); // CCMI_UPS_FORM_DEFAULT
+int ccmi_launch_ups_f32_form(const ccmi_ups_args *a, hipStream_t s, int form);
 int ccmi_launch_syn_f32(const ccmi_syn_args *a, hipStream_t s);
 int ccmi_launch_post_f32(const ccmi_post_args *a, hipStream_t s);
 // MS-SSIM distortion (dist_msssim.hip).  ccmi_msssim_check: every argument error of ccmi_msssim_f32,

@@ -288,7 +288,8 @@ struct UpsTile {
 // but the last, which produces the full-resolution stack); fills *last with the arguments
 // of the final step (source level 1 -> level 0).  prev (fold): step L-3 (level 2 -> 1) is not
 // launched either, its arguments go to *prev for a kernel that evaluates it in place.
-// Returns CCMI_OK or an error code.
-int ups_pyramid(const ccmi_ups_args *a, hipStream_t s, LevelArgs *last, bool launch = true, LevelArgs *prev = nullptr);
+// form (CCMI_UPS_FORM_*): the level kernel the launched steps use.  Returns CCMI_OK or an error code.
+int ups_pyramid(const ccmi_ups_args *a, hipStream_t s, LevelArgs *last, bool launch = true, LevelArgs *prev = nullptr,
+                int form = CCMI_UPS_FORM_DEFAULT);
 
 } // namespace ccmi_fwd

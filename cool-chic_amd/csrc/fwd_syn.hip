@@ -1593,7 +1593,11 @@ extern "C" int ccmi_decode_forward_f32(const ccmi_decode_args *a, void *stream)
     P.fa.head_generic = a->head == CCMI_HEAD_GENERIC;
     const bool fold = (stages & 8) && u.n_grids >= 3 && fold_eligible(P.fa, P.cmid);
     LevelArgs last{}, prev{};
-    if (int rc = ups_pyramid(&u, s, &last, (stages & 1) != 0, fold ? &prev : nullptr)) return rc;
+    // stages bit 5: the pyramid's levels by ups_level_fixed (the form before the row kernel), for A/B
+    // runs and tests
+    if (int rc = ups_pyramid(&u, s, &last, (stages & 1) != 0, fold ? &prev : nullptr,
+                             (stages & 32) ? CCMI_UPS_FORM_LEVELS : CCMI_UPS_FORM_DEFAULT))
+        return rc;
     if (!(stages & 2)) return CCMI_OK;
     if ((int64_t)4 * last.C * last.hs * last.ws >= ((int64_t)1 << 31) || (int64_t)4 * last.hd * last.wd >= ((int64_t)1 << 31))
         return ccmi_set_error(CCMI_ERR_UNSUPPORTED, "decode: level-1 stack of %d x %d x %d exceeds 2 GB buffer addressing", last.C,

@@ -148,6 +148,16 @@ typedef struct ccmi_ups_args {
 } ccmi_ups_args;
 size_t ccmi_ups_workspace_bytes(int n_grids, const int *h, const int *w, int batch);
 int ccmi_ups_forward_f32(const ccmi_ups_args *args, void *stream);
+/* The same with the form of the pyramid chosen; every form gives the same bits in out.
+ *   CCMI_UPS_FORM_DEFAULT: with ups_k = 8 and pre_k = 7, per step one launch of the row kernel (a
+ *     workgroup makes one channel, or half of the refined latent, of a 32 x 128 destination tile
+ *     with 128-bit stores); other tap counts run LEVELS;
+ *   CCMI_UPS_FORM_LEVELS:  per step one launch with one channel of a 16 x 64 tile per workgroup.
+ * Both write every level's stack to the workspace.
+ * ccmi_ups_forward_f32 is the call with CCMI_UPS_FORM_DEFAULT. */
+#define CCMI_UPS_FORM_DEFAULT 0
+#define CCMI_UPS_FORM_LEVELS 1
+int ccmi_ups_forward_f32_form(const ccmi_ups_args *args, void *stream, int form);
 
 /* Synthesis: Synthesis.forward (synthesis.py:264-277, SynthesisConv2d :69-84):
  * conv layers with replicate padding, optional residual, optional ReLU.
@@ -220,7 +230,9 @@ typedef struct ccmi_decode_args {
                                bit for bit; measured slower).  bit 4: the
                                fused kernel's runs hold one window each (cap 1 of
                                ccmi_fused_run_plan: every window pays the vertical halo; same
-                               values bit for bit, for A/B runs and tests) */
+                               values bit for bit, for A/B runs and tests).  bit 5: the
+                               pyramid in CCMI_UPS_FORM_LEVELS (same values bit for bit, for
+                               A/B runs and tests) */
     int head;               /* synthesis 1x1 head arithmetic, CCMI_HEAD_*: both are fp32 (the
                                MFMA form's products are exact f32 fmas, summed in another
                                order); MFMA needs 7 inputs, 48 hidden units and >= 1 3x3 layer
