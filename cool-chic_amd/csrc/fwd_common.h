@@ -58,7 +58,7 @@ __host__ __device__ constexpr int arm_pack_src(int d, int nh, int t)
 
 // ---------------------------------------------------------------- head weight records
 // The packed FMAs of a 1x1 head that reads its weights from LDS records (the fused kernel's VALU
-// head in fwd_syn.hip, the training forward's t_head_fwd in train.hip).  A hidden unit's record
+// head in fwd_syn.hip, the training forward's t_head_fwd in train_head.hip).  A hidden unit's record
 // is 16 floats, its fields dense from slot 0: w0[0..CIN), b0, w1[0..CMID), read back as whole
 // 128-bit vectors.  Both halves of an FMA are d = fma(w, x, c) with the weight w one half of an
 // aligned register pair, selected by op_sel / op_sel_hi, so a weight is used where its

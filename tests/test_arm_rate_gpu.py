@@ -1,4 +1,4 @@
-"""The path-A ARM and rate (fwd_arm.hip, and the training step's rate form in train.hip) against
+"""The path-A ARM and rate (fwd_arm.hip, and the training step's rate form in train_arm.hip) against
 the float64 reference of tests/arm_ref.py, on inputs that leave the rate and scale clamps
 (tests/test_arm_ref.py asserts that on the reference): every (dim_arm, n_hidden) that
 ccmi_arm_forward_f32 accepts, in the rows form, the pairs form and the default form, the drop-in
@@ -16,7 +16,7 @@ tightened to these):
                              dim_arm 32 (rows)     0.103  0.175      0.166  0.436  0.113
                              large q, rows, pairs  0.125  0.129      0.118  0.452  0.036
   ccmi_arm_mlp_f32                                 0.200  0.184      0.187
-  training step's rate (train.hip arm_rate)                                 0.474  0.027
+  training step's rate (train_arm.hip arm_rate)                                 0.474  0.027
   ccmi_arm_context_f32: equal to the oracle, element for element.
 The rows, pairs and default forms give the same figures (the same bits), and so do quantize = 1
 and 0.  The torch fp32 oracle reaches the same 0.474 per latent on the (24, 2) cases
@@ -177,7 +177,7 @@ def test_arm_mlp_within_bounds(ccmi_lib, gpu, d, nh):
 
 @pytest.mark.parametrize("d,nh", R.TRAIN_ARMS)
 def test_training_rate_form_within_bounds(ccmi_lib, gpu, d, nh):
-    """The training step's rate (train.hip arm_rate: expm1f, an IEEE division) through
+    """The training step's rate (train_arm.hip arm_rate: expm1f, an IEEE division) through
     ccmi.autograd.TrainForward with the true_ste quantizer (forward: round) and no noise, on the
     mid and high frames at 37x130 with the smallest synthesis the step accepts: the same per-latent
     and total bounds as the eval form, so both forms meet one reference latent by latent."""

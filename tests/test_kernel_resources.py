@@ -36,7 +36,7 @@ BUDGET = {
     # indices too (two of them were spilled, reloaded with a vmcnt(0) inside the tile loop):
     # one spilled value left, live only in the prologue / epilogue
     "t_arm16<2>": (128, 1, 8),
-    "t_head_bwd<7, 3, true>": (168, 0, 0),  # unit-pair packed form (output-ReLU architectures)
+    "t_head_bwd<7, 3>": (168, 0, 0),  # unit-pair packed form (output-ReLU architectures)
     # the tiled form (linear output layer, every reference architecture): 4 waves / SIMD
     "t_head_bwd_t<7, 3>": (128, 0, 0),
     # 3x3 backward, one launch (input + 4x4x1-MFMA weight gradients): 5 waves / SIMD (<= 96 VGPRs,

@@ -51,7 +51,7 @@ def test_quantize_model_matches_reference_search(gpu):
 
 def test_train_and_eval_rate_forms_agree(gpu):
     """The Laplace rate (arm.py:355-370, coolchic.py:419-424) exists in two fp32 forms: the
-    training step (train.hip arm_rate: expm1f and an IEEE division, as torch evaluates it) and
+    training step (train_arm.hip arm_rate: expm1f and an IEEE division, as torch evaluates it) and
     the eval forward that quantize_model / test() use (fwd_arm.hip laplace_cdf: v_exp_f32 - 1
     and one v_rcp_f32 shared by both CDF terms, 5 % faster).  On the reference-trained model
     of the quantize fixture, the two total rates (hard-rounded latents, the same network)

@@ -91,9 +91,9 @@ def test_gpu_gradients_match_reference(f, gpu):
     _gradients_match_reference(f, gpu)
 
 
-# the opt-in kernel forms the library ships next to the defaults (train.hip head_bwd_regs /
-# sp_bwd_persistent, read per launch): the register-form head backward (t_head_bwd_m) and the
-# one-tile-per-workgroup 3x3 backward (t_sp_bwd<3>)
+# the opt-in kernel forms the library ships next to the defaults (train_head.hip head_bwd_regs /
+# train_sp.hip sp_bwd_persistent, read per launch): the register-form head backward
+# (t_head_bwd_m) and the one-tile-per-workgroup 3x3 backward (t_sp_bwd<3>)
 @pytest.mark.parametrize("env", [("CCMI_HEAD_BWD_REGS", "1"), ("CCMI_SP_BWD_PF", "0")], ids=lambda e: f"{e[0]}={e[1]}")
 def test_gpu_gradients_opt_in_kernel_forms(env, gpu, monkeypatch):
     monkeypatch.setenv(*env)
@@ -297,7 +297,7 @@ def _random_arch_vs_oracle(gpu, H, W, seed, K=8, Kp=7, yuv420=False, **kw):
         o += n
 
 
-@pytest.mark.parametrize("K,Kp", [(4, 3), (6, 1), (6, 5), (8, 1), (8, 5), (8, 9)])
+@pytest.mark.parametrize("K,Kp", [(4, 3), (4, 7), (6, 1), (6, 5), (6, 9), (8, 1), (8, 3), (8, 5), (8, 9)])
 def test_gpu_gradients_other_kernel_sizes(K, Kp, gpu):
     """The upsampling backward for every kernel-size pair the training step accepts (the goldens
     hold the default 8 / 7 only): K = 8 runs the one-launch-per-level kernel (t_lvl_bwd), 4 / 6
@@ -315,12 +315,15 @@ def test_gpu_gradients_arm_variants(dim_arm, n_hidden, gpu):
 
 @pytest.mark.parametrize("n_grids,layers,yuv420", [
     (2, "16-1-linear-relu|3-1-linear-none", False),
+    (3, "16-1-linear-relu|3-1-linear-none", False),
     (4, "40-1-linear-relu|3-1-linear-none|3-3-residual-relu", True),
     (5, "64-1-linear-relu|3-1-linear-relu|3-3-residual-relu|3-3-residual-relu|3-3-residual-none", False),
+    (6, "40-1-linear-relu|3-1-linear-none|3-3-residual-relu", False),
     (7, "24-1-linear-relu|3-1-linear-none|3-3-linear-relu|3-3-residual-none", True),
+    (8, "24-1-linear-relu|3-1-linear-none|3-3-linear-relu|3-3-residual-none", False),
 ])
 def test_gpu_gradients_synthesis_and_grid_variants(n_grids, layers, yuv420, gpu):
-    """Latent-pyramid depth 2..7 (the 1x1 head's input width) and synthesis heads of 16..64
+    """Latent-pyramid depth 2..8 (the 1x1 head's input width) and synthesis heads of 16..64
     channels followed by 0..3 3x3 layers, residual or not, with 444 and 420 targets (even frame
     size, as 420 needs; the coarser levels are odd and crop)."""
     import forward_oracle as fo

@@ -1,4 +1,4 @@
-"""The training step's gradients (train.hip) at every quantiser setting of the c3x schedule, against
+"""The training step's gradients (train.hip and its stage units train_*.hip) at every quantiser setting of the c3x schedule, against
 the oracle in float64: tests/test_train_tiles_gpu.py holds them at the warm-up's setting only
 (softround + kumaraswamy a = 2, T = 0.3), 800 of the preset's 14,000 iterations per image.
 

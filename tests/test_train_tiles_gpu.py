@@ -1,4 +1,4 @@
-"""The training step's gradients (train.hip) off the rate floor, with every persistent kernel on
+"""The training step's gradients (train.hip and its stage units train_*.hip) off the rate floor, with every persistent kernel on
 its second and later work units: against the oracle in float64 (tests/train_ref.py; the frames'
 preconditions and the cases' workgroup arithmetic are pinned on the CPU by tests/test_train_ref.py).
 

@@ -1,7 +1,7 @@
 // Layout probe for v_mfma_f32_4x4x1_16b_f32 (the head backward's weight-gradient MFMA):
 // one wave, A = lane id, B = 1 -> D[bk][m][n] = A of the lane supplying row m of block bk;
 // then A = 1, B = lane id -> the lane supplying column n.  Prints, per lane and register, the
-// supplying lanes, and checks them against the layout train.hip assumes (mfma4x4).
+// supplying lanes, and checks them against the layout the training kernels assume (mfma4x4, train_internal.h).
 // Build: hipcc --offload-arch=gfx950 -O2 tools/mfma4x4_probe.hip -o tools/ablib/mfma4x4_probe
 #include <hip/hip_runtime.h>
 #include <cstdio>
