@@ -1198,85 +1198,88 @@ def _model_outs(geom, fmt, dtype, channels_last, out, dev):
     return res, op, cap, frames
 
 
-def _plan_model(plan, head, n, rects, fmt, rs, output_bitdepth, output_chroma_format, warp=None, info=None,
-                window=None, col=None, flt=None, tone=None, mx=None):
-    """(ccmi_frame_geom array, workspace bytes) of a formatted call: plan is the source's *_rs_plan
-    entry point (rs None: exactly the *_fmt_plan call), head its first two arguments.  With warp
-    (a ccmi_warp) plan is the *_warp_plan entry point, which takes no regions; info / window: its
-    optional per-frame outputs.  With col (a ccmi_colour) plan is the *_col_plan entry point, which
-    takes all of them; with flt (a ccmi_filter) the *_flt_plan entry point, which takes col (or None)
-    and flt; with tone (a ccmi_tone) the *_tone_plan entry point, which takes col, tone and flt (or None);
-    with mx (a ccmi_mix) the *_mix_plan entry point, which takes col, tone, flt (or None) and mx."""
-    geom, need = (FrameGeom * n)(), C.c_size_t(0)
+class _Sink:
+    """What a formatted call of n frames takes after the format: the ccmi_rect array (None: whole frames,
+    and always None with a warp), the ccmi_resample (None without size, or with a warp), the ccmi_warp,
+    ccmi_colour, ccmi_tone, ccmi_filter and ccmi_mix (each None when absent), and keep, what they point to."""
+
+    def __init__(self, n, rects=None, rs=None, warp=None, col=None, tone=None, flt=None, mx=None, keep=None):
+        self.n, self.rects, self.keep = n, rects, keep
+        self.rs, self.warp, self.col, self.tone, self.flt, self.mx = rs, warp, col, tone, flt, mx
+        ref = C.byref  # the six stage arguments of the *_mix pair, in their order
+        self._stages = (None if rs is None else ref(rs), None if warp is None else ref(warp),
+                        None if col is None else ref(col), None if tone is None else ref(tone),
+                        None if flt is None else ref(flt), None if mx is None else ref(mx))
+
+    def plan_args(self, output_bitdepth, output_chroma_format, fmt):
+        """n .. mix of the *_mix_plan prototypes: what lies between the source's head and geom."""
+        return (self.n, self.rects, output_bitdepth, output_chroma_format, C.byref(fmt)) + self._stages
+
+    def run_args(self, op, cap, fmt):
+        """n .. mix of the *_mix prototypes: what lies between the source's head and out_bitdepth."""
+        return (self.n, self.rects, op, cap, C.byref(fmt)) + self._stages
+
+
+def _sink(n, rects=None, roi=None, size=None, affine=None, perspective=None, pad="fill", fill=0.0,
+          interpolation="bilinear", clamp=False, colour_ops=None, blur=None, solarize=None, tone_ops=None, erase=None,
+          erase_seed=None, mix=None):
+    """The _Sink of the keywords of a *_model call of n frames.  rects: the regions' ccmi_rect array, None, or
+    a callable that makes either (called after the stages are marshalled, and not with a warp)."""
+    interp = _interp(interpolation, clamp)
+    warp, keep_w = _warp(affine, n, size, roi, pad, fill, interp, perspective)
+    col, keep_c = _colour(colour_ops, n)
+    flt, keep_f = _filter(blur, solarize, n)
+    tone, keep_t = _tone(tone_ops, n)
+    mx, keep_m = _mix(erase, erase_seed, mix, n)
+    if warp is not None:
+        rects = None
+    elif callable(rects):
+        rects = rects()
+    rs = None if size is None or warp is not None else _resample(size, interp)
+    return _Sink(n, rects, rs, warp, col, tone, flt, mx, (keep_w, keep_c, keep_f, keep_t, keep_m))
+
+
+def _stream_source(sp, ln):
+    """A source is (plan entry point, run entry point, their first two arguments, the device or None for
+    the current one): here of marshalled streams, LatentStore._source() of a store.  Both name the *_mix
+    pair, the superset of every formatted call: a stage that is NULL leaves, by ccmi.h, the narrower
+    call itself (down to *_fmt), so the absent keywords cost a NULL each and no other entry point."""
+    L = _bind()
+    return L.ccmi_decode_batch_dev_mix_plan, L.ccmi_decode_batch_dev_mix, (sp, ln), None
+
+
+def _plain_fmt():
+    """The format the header-only calls plan with: the element type, colour and strides do not change a plan."""
+    fmt = TensorFmt(elem=ELEM_F32, colour=COLOUR_ASIS)
+    for c in range(3):
+        fmt.scale[c] = 1.0
+    return fmt
+
+
+def _plan_model(source, sink, fmt, output_bitdepth, output_chroma_format, info=None, window=None):
+    """(ccmi_frame_geom array, workspace bytes) of a formatted call.  info / window: the plan's optional
+    per-frame outputs; the library takes a window only with a warp."""
+    plan, _, head, _ = source
+    geom, need = (FrameGeom * sink.n)(), C.c_size_t(0)
     probe = TensorFmt.from_buffer_copy(fmt)  # planar strides: the geometry does not depend on them
-    if mx is not None:
-        check(plan(*head, n, None if warp is not None else rects, output_bitdepth, output_chroma_format, C.byref(probe),
-                   None if warp is not None else rs, None if warp is None else C.byref(warp),
-                   None if col is None else C.byref(col), None if tone is None else C.byref(tone),
-                   None if flt is None else C.byref(flt), C.byref(mx), geom, info, window, C.byref(need)))
-    elif tone is not None:
-        check(plan(*head, n, None if warp is not None else rects, output_bitdepth, output_chroma_format, C.byref(probe),
-                   None if warp is not None else rs, None if warp is None else C.byref(warp),
-                   None if col is None else C.byref(col), C.byref(tone), None if flt is None else C.byref(flt), geom, info,
-                   window, C.byref(need)))
-    elif flt is not None:
-        check(plan(*head, n, None if warp is not None else rects, output_bitdepth, output_chroma_format, C.byref(probe),
-                   None if warp is not None else rs, None if warp is None else C.byref(warp),
-                   None if col is None else C.byref(col), C.byref(flt), geom, info, window, C.byref(need)))
-    elif col is not None:
-        check(plan(*head, n, None if warp is not None else rects, output_bitdepth, output_chroma_format, C.byref(probe),
-                   None if warp is not None else rs, None if warp is None else C.byref(warp), C.byref(col), geom, info,
-                   window, C.byref(need)))
-    elif warp is not None:
-        check(plan(*head, n, output_bitdepth, output_chroma_format, C.byref(probe), C.byref(warp), geom, info, window,
-                   C.byref(need)))
-    else:
-        check(plan(*head, n, rects, output_bitdepth, output_chroma_format, C.byref(probe), rs, geom, info, C.byref(need)))
+    check(plan(*head, *sink.plan_args(output_bitdepth, output_chroma_format, probe), geom, info, window, C.byref(need)))
     return geom, need.value
 
 
-def _run_model(plan, run, head, n, rects, dev, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth,
-               output_chroma_format, workspace, stream_handle, size, warp=None, col=None, flt=None, tone=None,
-               interp=(FILTER_TRIANGLE, 0), mx=None):
-    """The body of decode_batch_model and LatentStore.render_model: plan / run are the source's
-    *_rs_plan / *_rs entry points, or with warp (a ccmi_warp, which carries the size) its
-    *_warp_plan / *_warp ones, or with col (a ccmi_colour) its *_col_plan / *_col ones, or with flt (a
-    ccmi_filter) its *_flt_plan / *_flt ones, or with tone (a ccmi_tone) its *_tone_plan / *_tone ones, or
-    with mx (a ccmi_mix) its *_mix_plan / *_mix ones; head their first two arguments; dev None: the current
-    device.  interp: _interp()'s pair, for the resample (a warp carries its own)."""
+def _run_model(source, sink, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth, output_chroma_format,
+               workspace, stream_handle):
+    """The body of decode_batch_model and LatentStore.render_model: one plan and one run of the source's
+    *_mix pair."""
     import torch
+    _, run, head, dev = source
     dtype = torch.float32 if dtype is None else dtype
-    fmt, keep = _model_fmt(n, colour, mean, std, dtype, mirror)
-    rs = None if size is None or warp is not None else C.byref(_resample(size, interp))
-    geom, need = _plan_model(plan, head, n, rects, fmt, rs, output_bitdepth, output_chroma_format, warp, col=col, flt=flt,
-                             tone=tone, mx=mx)
+    fmt, keep = _model_fmt(sink.n, colour, mean, std, dtype, mirror)
+    geom, need = _plan_model(source, sink, fmt, output_bitdepth, output_chroma_format)
     dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else dev
     res, op, cap, frames = _model_outs(geom, fmt, dtype, channels_last, out, dev)
     stream_handle, workspace = _stream_ws(dev, stream_handle, workspace, need)
-    if mx is not None:
-        check(run(*head, n, None if warp is not None else rects, op, cap, C.byref(fmt), None if warp is not None else rs,
-                  None if warp is None else C.byref(warp), None if col is None else C.byref(col),
-                  None if tone is None else C.byref(tone), None if flt is None else C.byref(flt), C.byref(mx),
-                  output_bitdepth, output_chroma_format, workspace.data_ptr(), workspace.numel(), stream_handle))
-    elif tone is not None:
-        check(run(*head, n, None if warp is not None else rects, op, cap, C.byref(fmt), None if warp is not None else rs,
-                  None if warp is None else C.byref(warp), None if col is None else C.byref(col), C.byref(tone),
-                  None if flt is None else C.byref(flt), output_bitdepth, output_chroma_format, workspace.data_ptr(),
-                  workspace.numel(), stream_handle))
-    elif flt is not None:
-        check(run(*head, n, None if warp is not None else rects, op, cap, C.byref(fmt), None if warp is not None else rs,
-                  None if warp is None else C.byref(warp), None if col is None else C.byref(col), C.byref(flt),
-                  output_bitdepth, output_chroma_format, workspace.data_ptr(), workspace.numel(), stream_handle))
-    elif col is not None:
-        check(run(*head, n, None if warp is not None else rects, op, cap, C.byref(fmt), None if warp is not None else rs,
-                  None if warp is None else C.byref(warp), C.byref(col), output_bitdepth, output_chroma_format,
-                  workspace.data_ptr(), workspace.numel(), stream_handle))
-    elif warp is not None:
-        check(run(*head, n, op, cap, C.byref(fmt), C.byref(warp), output_bitdepth, output_chroma_format,
-                  workspace.data_ptr(), workspace.numel(), stream_handle))
-    else:
-        check(run(*head, n, rects, op, cap, C.byref(fmt), rs, output_bitdepth, output_chroma_format,
-                  workspace.data_ptr(), workspace.numel(), stream_handle))
+    check(run(*head, *sink.run_args(op, cap, fmt), output_bitdepth, output_chroma_format, workspace.data_ptr(),
+              workspace.numel(), stream_handle))
     del keep, frames
     return res
 
@@ -1294,6 +1297,10 @@ def decode_batch_model(streams: Sequence[bytes], roi=None, colour: str = "rgb", 
     (v - mean) / std per channel as v * float32(1 / std) + float32(-mean / std), written by the
     decoder's output kernel itself: no float32 frame set and no further pass.  The contract, step
     by step, is ccmi.h's (ccmi_tensor_fmt).
+
+    Whatever the keywords, the call made is ccmi_decode_batch_dev_mix (and its _plan) with every absent
+    stage NULL, which the library defines to be the narrower call: the entry point a paragraph below
+    names is the one whose contract in ccmi.h the keyword follows, and the one the call then equals.
 
     roi as for decode_batch_tensors; every region must have one size, and 420 samples need even
     x, y, w and h (output_chroma_format=444 takes any).  channels_last=True: an [n, h, w, 3]
@@ -1372,40 +1379,10 @@ def decode_batch_model(streams: Sequence[bytes], roi=None, colour: str = "rgb", 
     keep their kernels and bits."""
     n = len(streams)
     keep, sp, ln = _marshal(streams)
-    L = _bind()
-    interp = _interp(interpolation, clamp)
-    warp, keep_w = _warp(affine, n, size, roi, pad, fill, interp, perspective)
-    col, keep_c = _colour(colour_ops, n)
-    flt, keep_f = _filter(blur, solarize, n)
-    tone, keep_t = _tone(tone_ops, n)
-    mx, keep_m = _mix(erase, erase_seed, mix, n)
-    if mx is not None:
-        return _run_model(L.ccmi_decode_batch_dev_mix_plan, L.ccmi_decode_batch_dev_mix, (sp, ln), n,
-                          None if warp is not None else _rects(roi, streams, n), None, colour, mean, std, dtype,
-                          channels_last, mirror, out, output_bitdepth, output_chroma_format, workspace, stream_handle, size,
-                          warp, col, flt, tone, interp=interp, mx=mx)
-    if tone is not None:
-        return _run_model(L.ccmi_decode_batch_dev_tone_plan, L.ccmi_decode_batch_dev_tone, (sp, ln), n,
-                          None if warp is not None else _rects(roi, streams, n), None, colour, mean, std, dtype,
-                          channels_last, mirror, out, output_bitdepth, output_chroma_format, workspace, stream_handle, size,
-                          warp, col, flt, tone, interp=interp)
-    if flt is not None:
-        return _run_model(L.ccmi_decode_batch_dev_flt_plan, L.ccmi_decode_batch_dev_flt, (sp, ln), n,
-                          None if warp is not None else _rects(roi, streams, n), None, colour, mean, std, dtype,
-                          channels_last, mirror, out, output_bitdepth, output_chroma_format, workspace, stream_handle, size,
-                          warp, col, flt, interp=interp)
-    if col is not None:
-        return _run_model(L.ccmi_decode_batch_dev_col_plan, L.ccmi_decode_batch_dev_col, (sp, ln), n,
-                          None if warp is not None else _rects(roi, streams, n), None, colour, mean, std, dtype,
-                          channels_last, mirror, out, output_bitdepth, output_chroma_format, workspace, stream_handle, size,
-                          warp, col, interp=interp)
-    if warp is not None:
-        return _run_model(L.ccmi_decode_batch_dev_warp_plan, L.ccmi_decode_batch_dev_warp, (sp, ln), n, None, None,
-                          colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth, output_chroma_format,
-                          workspace, stream_handle, size, warp, interp=interp)
-    return _run_model(L.ccmi_decode_batch_dev_rs_plan, L.ccmi_decode_batch_dev_rs, (sp, ln), n, _rects(roi, streams, n),
-                      None, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth, output_chroma_format,
-                      workspace, stream_handle, size, interp=interp)
+    sink = _sink(n, lambda: _rects(roi, streams, n), roi, size, affine, perspective, pad, fill, interpolation, clamp,
+                 colour_ops, blur, solarize, tone_ops, erase, erase_seed, mix)
+    return _run_model(_stream_source(sp, ln), sink, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth,
+                      output_chroma_format, workspace, stream_handle)
 
 
 def weights_i32(stream: bytes):
@@ -1749,6 +1726,12 @@ class LatentStore:
         rects = _roi_rects(roi, m, whole, "frame")
         return m, (None if index is None else (C.c_int * m)(*idx)), rects
 
+    def _source(self, idx):
+        """This store as the source of a formatted call (see _stream_source); idx: _frames()'s index array."""
+        L = _bind()
+        return (L.ccmi_latents_render_mix_plan, L.ccmi_latents_render_mix, (self._handle(), idx),
+                getattr(self._store, "device", None))
+
     def _plan(self, index, roi, output_bitdepth, output_chroma_format, dtype, info=None):
         L = _bind()
         m, idx, rects = self._frames(index, roi)
@@ -1798,70 +1781,41 @@ class LatentStore:
                      affine=None, pad: str = "fill", fill=0.0, colour_ops=None, blur=None, solarize=None,
                      tone_ops=None, erase=None, erase_seed=None, mix=None, interpolation: str = "bilinear",
                      clamp: bool = False, perspective=None):
-        """render() into the tensor a model takes (ccmi_latents_render_fmt; with size
-        ccmi_latents_render_rs; with affine ccmi_latents_render_warp): frames and regions as for
+        """render() into the tensor a model takes: frames and regions as for
         render(), the result and every other argument as for decode_batch_model, whose output for
-        the same streams and arguments it equals bit for bit.  workspace with a size or an affine:
+        the same streams and arguments it equals bit for bit.  The call made is ccmi_latents_render_mix
+        (and its _plan) with every absent stage NULL, which the library defines to be the narrower call:
+        ccmi_latents_render_fmt; with size ccmi_latents_render_rs; with affine ccmi_latents_render_warp;
+        with colour_ops ccmi_latents_render_col, with blur or solarize ccmi_latents_render_flt, with
+        tone_ops ccmi_latents_render_tone.  workspace with a size or an affine:
         at least what render_model_workspace_bytes() reports (the resample's intermediate and a
-        warp's windows are not part of render_geometry()'s figure).  With colour_ops
-        ccmi_latents_render_col, with blur or solarize ccmi_latents_render_flt, with tone_ops
-        ccmi_latents_render_tone:
+        warp's windows are not part of render_geometry()'s figure);
         render_model_workspace_bytes() takes the same arguments.  interpolation= / clamp= as for
         decode_batch_model (a bicubic warp's windows, and so its workspace, are a tap wider);
         perspective= as for decode_batch_model, in place of affine=; erase= / erase_seed= / mix= as for
         decode_batch_model (ccmi_latents_render_mix), partners being frames of this call."""
         m, idx, rects = self._frames(index, None if affine is not None or perspective is not None else roi)
-        L = _bind()
-        interp = _interp(interpolation, clamp)
-        warp, keep_w = _warp(affine, m, size, roi, pad, fill, interp, perspective)
-        col, keep_c = _colour(colour_ops, m)
-        flt, keep_f = _filter(blur, solarize, m)
-        tone, keep_t = _tone(tone_ops, m)
-        mx, keep_m = _mix(erase, erase_seed, mix, m)
-        if mx is not None:
-            return _run_model(L.ccmi_latents_render_mix_plan, L.ccmi_latents_render_mix, (self._handle(), idx), m, rects,
-                              self._store.device, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth,
-                              output_chroma_format, workspace, stream_handle, size, warp, col, flt, tone,
-                              interp=interp, mx=mx)
-        if tone is not None:
-            return _run_model(L.ccmi_latents_render_tone_plan, L.ccmi_latents_render_tone, (self._handle(), idx), m, rects,
-                              self._store.device, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth,
-                              output_chroma_format, workspace, stream_handle, size, warp, col, flt, tone,
-                              interp=interp)
-        if flt is not None:
-            return _run_model(L.ccmi_latents_render_flt_plan, L.ccmi_latents_render_flt, (self._handle(), idx), m, rects,
-                              self._store.device, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth,
-                              output_chroma_format, workspace, stream_handle, size, warp, col, flt, interp=interp)
-        if col is not None:
-            return _run_model(L.ccmi_latents_render_col_plan, L.ccmi_latents_render_col, (self._handle(), idx), m, rects,
-                              self._store.device, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth,
-                              output_chroma_format, workspace, stream_handle, size, warp, col, interp=interp)
-        if warp is not None:
-            return _run_model(L.ccmi_latents_render_warp_plan, L.ccmi_latents_render_warp, (self._handle(), idx), m,
-                              None, self._store.device, colour, mean, std, dtype, channels_last, mirror, out,
-                              output_bitdepth, output_chroma_format, workspace, stream_handle, size, warp, interp=interp)
-        return _run_model(L.ccmi_latents_render_rs_plan, L.ccmi_latents_render_rs, (self._handle(), idx), m, rects,
-                          self._store.device, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth,
-                          output_chroma_format, workspace, stream_handle, size, interp=interp)
+        sink = _sink(m, rects, roi, size, affine, perspective, pad, fill, interpolation, clamp, colour_ops, blur, solarize,
+                     tone_ops, erase, erase_seed, mix)
+        return _run_model(self._source(idx), sink, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth,
+                          output_chroma_format, workspace, stream_handle)
 
     def warp_plan(self, index, affine, size, pad: str = "fill", fill=0.0, output_bitdepth: int = 0,
                   output_chroma_format: int = 0, interpolation: str = "bilinear", clamp: bool = False,
                   perspective=None) -> list:
-        """What render_model(affine=...) will do, per output frame (ccmi_latents_render_warp_plan,
-        header-only), like roi_plan: {'window': (x, y, w, h), the rectangle of the frame the tail
-        renders for that frame's matrix, 'windowed', 'arm_rows'}.  interpolation="bicubic": the window
+        """What render_model(affine=...) will do, per output frame (header-only: ccmi_latents_render_mix_plan
+        with a warp alone, by ccmi.h the ccmi_latents_render_warp_plan call), like roi_plan: {'window':
+        (x, y, w, h), the rectangle of the frame the tail renders for that frame's matrix, 'windowed',
+        'arm_rows'}.  interpolation="bicubic": the window
         of the 16 taps, one pixel wider on every side the frame allows.  perspective= (with affine=None):
         the plan of render_model(perspective=...)."""
         m, idx, _ = self._frames(index, None)
-        warp, keep_w = _warp(affine, m, size, None, pad, fill, _interp(interpolation, clamp), perspective)
-        if warp is None:
+        if affine is None and perspective is None:
             raise ValueError("LatentStore.warp_plan: affine is None")
-        fmt = TensorFmt(elem=ELEM_F32, colour=COLOUR_ASIS)
-        for c in range(3):
-            fmt.scale[c] = 1.0
+        sink = _sink(m, size=size, affine=affine, perspective=perspective, pad=pad, fill=fill, interpolation=interpolation,
+                     clamp=clamp)
         info, window = (RoiInfo * m)(), (Rect * m)()
-        _plan_model(_bind().ccmi_latents_render_warp_plan, (self._handle(), idx), m, None, fmt, None, output_bitdepth,
-                    output_chroma_format, warp, info, window)
+        _plan_model(self._source(idx), sink, _plain_fmt(), output_bitdepth, output_chroma_format, info, window)
         return [{"window": (r.x, r.y, r.w, r.h), "windowed": bool(i.windowed),
                  "arm_rows": [int(v) for v in i.arm_rows[: i.n_grids]]} for i, r in zip(info, window)]
 
@@ -1870,7 +1824,9 @@ class LatentStore:
                                      colour_ops=None, blur=None, solarize=None, tone_ops=None, erase=None,
                                      erase_seed=None, mix=None, interpolation: str = "bilinear", clamp: bool = False,
                                      perspective=None) -> int:
-        """Header-only: the workspace render_model needs for these frames, regions and size, or
+        """Header-only: the workspace render_model needs, from render_model's own plan call
+        (ccmi_latents_render_mix_plan with the absent stages NULL: by ccmi.h the narrower plan named with
+        each figure here), for these frames, regions and size, or
         these frames, matrices and size (ccmi_latents_render_rs_plan / _warp_plan; the element type,
         colour and strides do not change it), these colour ops (ccmi_latents_render_col_plan:
         the op tables and the contrast ops' accumulators) and this blur and solarize
@@ -1880,37 +1836,9 @@ class LatentStore:
         (ccmi_latents_render_mix_plan): 256 bytes per mix-staged frame and a second float32 frame for
         those with a blur or a solarize, on top of their staging (ccmi.h's formula)."""
         m, idx, rects = self._frames(index, None if affine is not None or perspective is not None else roi)
-        fmt = TensorFmt(elem=ELEM_F32, colour=COLOUR_ASIS)
-        for c in range(3):
-            fmt.scale[c] = 1.0
-        interp = _interp(interpolation, clamp)
-        warp, keep_w = _warp(affine, m, size, roi, pad, fill, interp, perspective)
-        col, keep_c = _colour(colour_ops, m)
-        flt, keep_f = _filter(blur, solarize, m)
-        tone, keep_t = _tone(tone_ops, m)
-        mx, keep_m = _mix(erase, erase_seed, mix, m)
-        if mx is not None:
-            rs = None if size is None or warp is not None else C.byref(_resample(size, interp))
-            return _plan_model(_bind().ccmi_latents_render_mix_plan, (self._handle(), idx), m, rects, fmt, rs,
-                               output_bitdepth, output_chroma_format, warp, col=col, flt=flt, tone=tone, mx=mx)[1]
-        if tone is not None:
-            rs = None if size is None or warp is not None else C.byref(_resample(size, interp))
-            return _plan_model(_bind().ccmi_latents_render_tone_plan, (self._handle(), idx), m, rects, fmt, rs,
-                               output_bitdepth, output_chroma_format, warp, col=col, flt=flt, tone=tone)[1]
-        if flt is not None:
-            rs = None if size is None or warp is not None else C.byref(_resample(size, interp))
-            return _plan_model(_bind().ccmi_latents_render_flt_plan, (self._handle(), idx), m, rects, fmt, rs,
-                               output_bitdepth, output_chroma_format, warp, col=col, flt=flt)[1]
-        if col is not None:
-            rs = None if size is None or warp is not None else C.byref(_resample(size, interp))
-            return _plan_model(_bind().ccmi_latents_render_col_plan, (self._handle(), idx), m, rects, fmt, rs,
-                               output_bitdepth, output_chroma_format, warp, col=col)[1]
-        if warp is not None:
-            return _plan_model(_bind().ccmi_latents_render_warp_plan, (self._handle(), idx), m, None, fmt, None,
-                               output_bitdepth, output_chroma_format, warp)[1]
-        rs = None if size is None else C.byref(_resample(size, interp))
-        return _plan_model(_bind().ccmi_latents_render_rs_plan, (self._handle(), idx), m, rects, fmt, rs, output_bitdepth,
-                           output_chroma_format)[1]
+        sink = _sink(m, rects, roi, size, affine, perspective, pad, fill, interpolation, clamp, colour_ops, blur, solarize,
+                     tone_ops, erase, erase_seed, mix)
+        return _plan_model(self._source(idx), sink, _plain_fmt(), output_bitdepth, output_chroma_format)[1]
 
     def latents(self, i: int) -> list:
         """Stream i's integer latents: one int32 device tensor [h_l, w_l] per grid."""

@@ -1061,66 +1061,71 @@ extern "C" int ccmi_decode_batch_ws(const uint8_t *const *streams, const size_t 
 }
 
 // ------------------------------------------------------------------ device sinks
-// Thirty-six entry points over one table: the source is the caller's streams or a latent store, the
-// sink plain samples (sample_type; with or without a region) or formatted ones (fmt, forced to
-// CCMI_SAMPLE_F32, the call whose output kernel the format replaces; with or without a resample,
-// or with a warp, which takes no region; with or without colour ops, tone ops, a filter and a mix),
-// and each comes as a plan and as a run.  `who` is the entry point's name for the error text,
-// `missing` its own null-argument check beyond the source's.
-struct Sink {
-    const ccmi_rect *roi;
-    int sample;
-    const ccmi_tensor_fmt *fmt;
-    const ccmi_resample *rs;
-    const ccmi_warp *warp;
-    const ccmi_colour *colour;
-    const ccmi_filter *filter = nullptr;
+// Thirty-six entry points over one table, each a Source, a Sink and one return through sink_plan or
+// sink_run:
+//   source  the caller's streams (ccmi_decode_batch_dev*)  |  a latent store (ccmi_latents_render*)
+//   sink    plain samples of sample_type: whole frames, or regions (_roi; the store's call takes both)
+//           formatted ones (fmt; forced to CCMI_SAMPLE_F32, the call whose output kernel the format
+//           replaces): _fmt; _rs, with a resample; _warp, with a warp, which takes no region; then _col,
+//           _flt, _tone and _mix, each the superset of all before it with one more stage (colour ops,
+//           a filter, tone ops, a mix).  A stage that is NULL is the call before, itself, under the
+//           name it was entered by; what may not go together is the plan's to refuse
+//   form    a plan (geom, info, window, workspace_bytes)  |  a run (outputs, workspace, stream)
+// `who` is the entry point's name for the error text, `needs` what it requires beyond the source and
+// its own outputs: the _warp entry points a warp with its matrices, the supersets only the matrices
+// of a warp that is there; a window without a warp is refused by whoever takes a window.
+struct Source {
+    const uint8_t *const *streams;
+    const size_t *lens;
+    const ccmi_latents *h;
+    const int *index;
+    int n;
+    bool store;
+};
+
+static Source from_streams(const uint8_t *const *streams, const size_t *lens, int n)
+{
+    return Source{streams, lens, nullptr, nullptr, n, false};
+}
+
+static Source from_store(const ccmi_latents *h, const int *index, int m) { return Source{nullptr, nullptr, h, index, m, true}; }
+
+struct Sink { // in the entry points' argument order; an entry point writes the members it has
+    const ccmi_rect *roi = nullptr;
+    int sample = CCMI_SAMPLE_F32;
+    const ccmi_tensor_fmt *fmt = nullptr;
+    const ccmi_resample *rs = nullptr;
+    const ccmi_warp *warp = nullptr;
+    const ccmi_colour *colour = nullptr;
     const ccmi_tone *tone = nullptr;
+    const ccmi_filter *filter = nullptr;
     const ccmi_mix *mix = nullptr;
 };
 
-static Sink samples(const ccmi_rect *roi, int sample_type) { return Sink{roi, sample_type, nullptr, nullptr, nullptr, nullptr}; }
+enum Needs { PLAIN, FMT, FMT_WARP };
+constexpr int F32 = CCMI_SAMPLE_F32;
 
-static Sink formatted(const ccmi_rect *roi, const ccmi_tensor_fmt *fmt, const ccmi_resample *rs)
+static bool absent(const Sink &k, Needs needs)
 {
-    return Sink{roi, CCMI_SAMPLE_F32, fmt, rs, nullptr, nullptr};
+    if (needs == PLAIN) return false;
+    return !k.fmt || (needs == FMT_WARP ? !k.warp || !k.warp->matrix : k.warp && !k.warp->matrix);
 }
 
-static Sink warped(const ccmi_tensor_fmt *fmt, const ccmi_warp *warp)
+// streams: null arguments, then the sample type; a store: the handle and the sample type, then (a run)
+// a plan-only handle, then null arguments; then, for both, the plan's own errors
+static int sink_request(const char *who, const Source &src, const Sink &k, int out_bitdepth, int out_chroma, bool run,
+                        bool missing, DecodeRequest &rq)
 {
-    return Sink{nullptr, CCMI_SAMPLE_F32, fmt, nullptr, warp, nullptr};
-}
-
-// the superset: a resample or a warp or neither, and colour ops; what may not go together is the plan's to refuse
-static Sink coloured(const ccmi_rect *roi, const ccmi_tensor_fmt *fmt, const ccmi_resample *rs, const ccmi_warp *warp,
-                     const ccmi_colour *colour)
-{
-    return Sink{roi, CCMI_SAMPLE_F32, fmt, rs, warp, colour};
-}
-
-// ... and a per-frame blur / solarize after the colour ops
-static Sink filtered(const ccmi_rect *roi, const ccmi_tensor_fmt *fmt, const ccmi_resample *rs, const ccmi_warp *warp,
-                     const ccmi_colour *colour, const ccmi_filter *filter)
-{
-    return Sink{roi, CCMI_SAMPLE_F32, fmt, rs, warp, colour, filter};
-}
-
-// ... and per-frame tone ops between the two
-static Sink toned(const ccmi_rect *roi, const ccmi_tensor_fmt *fmt, const ccmi_resample *rs, const ccmi_warp *warp,
-                  const ccmi_colour *colour, const ccmi_tone *tone, const ccmi_filter *filter)
-{
-    return Sink{roi, CCMI_SAMPLE_F32, fmt, rs, warp, colour, filter, tone};
-}
-
-// ... and the erase / mix pass on the normalised frames
-static Sink mixed(const ccmi_rect *roi, const ccmi_tensor_fmt *fmt, const ccmi_resample *rs, const ccmi_warp *warp,
-                  const ccmi_colour *colour, const ccmi_tone *tone, const ccmi_filter *filter, const ccmi_mix *mix)
-{
-    return Sink{roi, CCMI_SAMPLE_F32, fmt, rs, warp, colour, filter, tone, mix};
-}
-
-static void set_sink(DecodeRequest &rq, const Sink &k)
-{
+    clear_last();
+    if (src.store && !src.h) return ccmi_set_error(CCMI_ERR_ARG, "render: the handle is NULL (no frame 0)");
+    if (!src.store && (!src.streams || !src.lens || missing)) return ccmi_set_error(CCMI_ERR_ARG, "%s: null argument", who);
+    if (k.sample < 0) return ccmi_set_error(CCMI_ERR_ARG, "decode: unknown sample type %d", k.sample);
+    if (src.store && run && !src.h->resident)
+        return ccmi_set_error(CCMI_ERR_ARG, "render: the handle is plan-only (built without a store): no frame 0 to render");
+    if (missing) return ccmi_set_error(CCMI_ERR_ARG, "%s: null argument", who);
+    rq = request(src.streams, src.lens, src.n, out_bitdepth, out_chroma);
+    rq.src = src.h;
+    rq.index = src.index;
     rq.sample = k.sample;
     rq.roi = k.roi;
     rq.fmt = k.fmt;
@@ -1130,48 +1135,29 @@ static void set_sink(DecodeRequest &rq, const Sink &k)
     rq.filter = k.filter;
     rq.tone = k.tone;
     rq.mix = k.mix;
-}
-
-// streams as the source: null arguments, then the sample type, then the plan's own errors
-static int stream_request(const char *who, const uint8_t *const *streams, const size_t *lens, int n, const Sink &k,
-                          int out_bitdepth, int out_chroma, bool missing, DecodeRequest &rq)
-{
-    clear_last();
-    if (!streams || !lens || missing) return ccmi_set_error(CCMI_ERR_ARG, "%s: null argument", who);
-    if (k.sample < 0) return ccmi_set_error(CCMI_ERR_ARG, "decode: unknown sample type %d", k.sample);
-    rq = request(streams, lens, n, out_bitdepth, out_chroma);
-    set_sink(rq, k);
     return CCMI_OK;
 }
 
-// a latent store as the source: the handle and the sample type, then (a run) a plan-only handle,
-// then null arguments, then the plan's own errors
-static int latents_request(const char *who, const ccmi_latents *h, const int *index, int m, const Sink &k,
-                           int out_bitdepth, int out_chroma, bool run, bool missing, DecodeRequest &rq)
+static int sink_plan(const char *who, const Source &src, const Sink &k, Needs needs, int out_bitdepth, int out_chroma,
+                     ccmi_frame_geom *geom, ccmi_roi_info *info, ccmi_rect *window, size_t *workspace_bytes)
 {
-    clear_last();
-    if (!h) return ccmi_set_error(CCMI_ERR_ARG, "render: the handle is NULL (no frame 0)");
-    if (k.sample < 0) return ccmi_set_error(CCMI_ERR_ARG, "decode: unknown sample type %d", k.sample);
-    if (run && !h->resident)
-        return ccmi_set_error(CCMI_ERR_ARG, "render: the handle is plan-only (built without a store): no frame 0 to render");
-    if (missing) return ccmi_set_error(CCMI_ERR_ARG, "%s: null argument", who);
-    rq = request(nullptr, nullptr, m, out_bitdepth, out_chroma);
-    rq.src = h;
-    rq.index = index;
-    set_sink(rq, k);
-    return CCMI_OK;
-}
-
-static int sink_plan(DecodeRequest &rq, ccmi_frame_geom *geom, ccmi_roi_info *info, size_t *workspace_bytes)
-{
+    DecodeRequest rq;
+    if (int rc = sink_request(who, src, k, out_bitdepth, out_chroma, false,
+                              absent(k, needs) || (window && !k.warp) || !geom || !workspace_bytes, rq))
+        return rc;
     rq.geom = geom;
     rq.info = info;
+    rq.window = window;
     return plan_only(rq, workspace_bytes);
 }
 
-static int sink_run(DecodeRequest &rq, void *const *out_dev, const size_t *out_caps, void *workspace,
-                    size_t workspace_bytes, void *stream)
+static int sink_run(const char *who, const Source &src, const Sink &k, Needs needs, void *const *out_dev,
+                    const size_t *out_caps, int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes,
+                    void *stream)
 {
+    DecodeRequest rq;
+    if (int rc = sink_request(who, src, k, out_bitdepth, out_chroma, true, !out_dev || !out_caps || absent(k, needs), rq))
+        return rc;
     rq.dev = out_dev;
     rq.caps = out_caps;
     rq.ws = workspace;
@@ -1183,33 +1169,24 @@ extern "C" int ccmi_decode_batch_dev_plan(const uint8_t *const *streams, const s
                                           int out_chroma, int sample_type, ccmi_frame_geom *geom,
                                           size_t *workspace_bytes)
 {
-    DecodeRequest rq;
-    if (int rc = stream_request("decode_batch_dev_plan", streams, lens, n, samples(nullptr, sample_type), out_bitdepth,
-                                out_chroma, !geom || !workspace_bytes, rq))
-        return rc;
-    return sink_plan(rq, geom, nullptr, workspace_bytes);
+    return sink_plan("decode_batch_dev_plan", from_streams(streams, lens, n), Sink{nullptr, sample_type}, PLAIN, out_bitdepth,
+                     out_chroma, geom, nullptr, nullptr, workspace_bytes);
 }
 
 extern "C" int ccmi_decode_batch_dev(const uint8_t *const *streams, const size_t *lens, int n, void *const *out_dev,
                                      const size_t *out_caps, int sample_type, int out_bitdepth, int out_chroma,
                                      void *workspace, size_t workspace_bytes, void *stream)
 {
-    DecodeRequest rq;
-    if (int rc = stream_request("decode_batch_dev", streams, lens, n, samples(nullptr, sample_type), out_bitdepth,
-                                out_chroma, !out_dev || !out_caps, rq))
-        return rc;
-    return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
+    return sink_run("decode_batch_dev", from_streams(streams, lens, n), Sink{nullptr, sample_type}, PLAIN, out_dev, out_caps,
+                    out_bitdepth, out_chroma, workspace, workspace_bytes, stream);
 }
 
 extern "C" int ccmi_decode_batch_dev_roi_plan(const uint8_t *const *streams, const size_t *lens, int n,
                                               const ccmi_rect *roi, int out_bitdepth, int out_chroma, int sample_type,
                                               ccmi_frame_geom *geom, ccmi_roi_info *info, size_t *workspace_bytes)
 {
-    DecodeRequest rq;
-    if (int rc = stream_request("decode_batch_dev_roi_plan", streams, lens, n, samples(roi, sample_type), out_bitdepth,
-                                out_chroma, !geom || !workspace_bytes, rq))
-        return rc;
-    return sink_plan(rq, geom, info, workspace_bytes);
+    return sink_plan("decode_batch_dev_roi_plan", from_streams(streams, lens, n), Sink{roi, sample_type}, PLAIN, out_bitdepth,
+                     out_chroma, geom, info, nullptr, workspace_bytes);
 }
 
 extern "C" int ccmi_decode_batch_dev_roi(const uint8_t *const *streams, const size_t *lens, int n, const ccmi_rect *roi,
@@ -1217,25 +1194,17 @@ extern "C" int ccmi_decode_batch_dev_roi(const uint8_t *const *streams, const si
                                          int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes,
                                          void *stream)
 {
-    DecodeRequest rq;
-    if (int rc = stream_request("decode_batch_dev_roi", streams, lens, n, samples(roi, sample_type), out_bitdepth,
-                                out_chroma, !out_dev || !out_caps, rq))
-        return rc;
-    return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
+    return sink_run("decode_batch_dev_roi", from_streams(streams, lens, n), Sink{roi, sample_type}, PLAIN, out_dev, out_caps,
+                    out_bitdepth, out_chroma, workspace, workspace_bytes, stream);
 }
 
-// The resampling sink is the formatted call with a ccmi_resample next to the format; rs NULL is
-// that call itself, under its own name.
 extern "C" int ccmi_decode_batch_dev_rs_plan(const uint8_t *const *streams, const size_t *lens, int n,
                                              const ccmi_rect *roi, int out_bitdepth, int out_chroma,
                                              const ccmi_tensor_fmt *fmt, const ccmi_resample *rs, ccmi_frame_geom *geom,
                                              ccmi_roi_info *info, size_t *workspace_bytes)
 {
-    DecodeRequest rq;
-    if (int rc = stream_request(rs ? "decode_batch_dev_rs_plan" : "decode_batch_dev_fmt_plan", streams, lens, n,
-                                formatted(roi, fmt, rs), out_bitdepth, out_chroma, !fmt || !geom || !workspace_bytes, rq))
-        return rc;
-    return sink_plan(rq, geom, info, workspace_bytes);
+    return sink_plan(rs ? "decode_batch_dev_rs_plan" : "decode_batch_dev_fmt_plan", from_streams(streams, lens, n),
+                     Sink{roi, F32, fmt, rs}, FMT, out_bitdepth, out_chroma, geom, info, nullptr, workspace_bytes);
 }
 
 extern "C" int ccmi_decode_batch_dev_rs(const uint8_t *const *streams, const size_t *lens, int n, const ccmi_rect *roi,
@@ -1243,166 +1212,9 @@ extern "C" int ccmi_decode_batch_dev_rs(const uint8_t *const *streams, const siz
                                         const ccmi_resample *rs, int out_bitdepth, int out_chroma, void *workspace,
                                         size_t workspace_bytes, void *stream)
 {
-    DecodeRequest rq;
-    if (int rc = stream_request(rs ? "decode_batch_dev_rs" : "decode_batch_dev_fmt", streams, lens, n,
-                                formatted(roi, fmt, rs), out_bitdepth, out_chroma, !out_dev || !out_caps || !fmt, rq))
-        return rc;
-    return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
-}
-
-// The warping sink: the formatted call with a ccmi_warp in place of the regions.
-extern "C" int ccmi_decode_batch_dev_warp_plan(const uint8_t *const *streams, const size_t *lens, int n,
-                                               int out_bitdepth, int out_chroma, const ccmi_tensor_fmt *fmt,
-                                               const ccmi_warp *warp, ccmi_frame_geom *geom, ccmi_roi_info *info,
-                                               ccmi_rect *window, size_t *workspace_bytes)
-{
-    DecodeRequest rq;
-    if (int rc = stream_request("decode_batch_dev_warp_plan (frame 0)", streams, lens, n, warped(fmt, warp), out_bitdepth,
-                                out_chroma, !fmt || !warp || !warp->matrix || !geom || !workspace_bytes, rq))
-        return rc;
-    rq.window = window;
-    return sink_plan(rq, geom, info, workspace_bytes);
-}
-
-extern "C" int ccmi_decode_batch_dev_warp(const uint8_t *const *streams, const size_t *lens, int n,
-                                          void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
-                                          const ccmi_warp *warp, int out_bitdepth, int out_chroma, void *workspace,
-                                          size_t workspace_bytes, void *stream)
-{
-    DecodeRequest rq;
-    if (int rc = stream_request("decode_batch_dev_warp (frame 0)", streams, lens, n, warped(fmt, warp), out_bitdepth,
-                                out_chroma, !out_dev || !out_caps || !fmt || !warp || !warp->matrix, rq))
-        return rc;
-    return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
-}
-
-// The colouring sink: the superset of the three above with a ccmi_colour (colour NULL: that call itself).
-extern "C" int ccmi_decode_batch_dev_col_plan(const uint8_t *const *streams, const size_t *lens, int n,
-                                              const ccmi_rect *roi, int out_bitdepth, int out_chroma,
-                                              const ccmi_tensor_fmt *fmt, const ccmi_resample *rs, const ccmi_warp *warp,
-                                              const ccmi_colour *colour, ccmi_frame_geom *geom, ccmi_roi_info *info,
-                                              ccmi_rect *window, size_t *workspace_bytes)
-{
-    DecodeRequest rq;
-    if (int rc = stream_request("decode_batch_dev_col_plan (frame 0)", streams, lens, n, coloured(roi, fmt, rs, warp, colour),
-                                out_bitdepth, out_chroma,
-                                !fmt || (warp && !warp->matrix) || (window && !warp) || !geom || !workspace_bytes, rq))
-        return rc;
-    rq.window = window;
-    return sink_plan(rq, geom, info, workspace_bytes);
-}
-
-extern "C" int ccmi_decode_batch_dev_col(const uint8_t *const *streams, const size_t *lens, int n, const ccmi_rect *roi,
-                                         void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
-                                         const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
-                                         int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes,
-                                         void *stream)
-{
-    DecodeRequest rq;
-    if (int rc = stream_request("decode_batch_dev_col (frame 0)", streams, lens, n, coloured(roi, fmt, rs, warp, colour),
-                                out_bitdepth, out_chroma, !out_dev || !out_caps || !fmt || (warp && !warp->matrix), rq))
-        return rc;
-    return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
-}
-
-// The filtering sink: the colouring sink with a ccmi_filter (filter NULL: that call itself); the _tone
-// calls after each are the same with a ccmi_tone (tone NULL: the _flt call itself).
-extern "C" int ccmi_decode_batch_dev_flt_plan(const uint8_t *const *streams, const size_t *lens, int n,
-                                              const ccmi_rect *roi, int out_bitdepth, int out_chroma,
-                                              const ccmi_tensor_fmt *fmt, const ccmi_resample *rs, const ccmi_warp *warp,
-                                              const ccmi_colour *colour, const ccmi_filter *filter, ccmi_frame_geom *geom,
-                                              ccmi_roi_info *info, ccmi_rect *window, size_t *workspace_bytes)
-{
-    DecodeRequest rq;
-    if (int rc = stream_request("decode_batch_dev_flt_plan (frame 0)", streams, lens, n,
-                                filtered(roi, fmt, rs, warp, colour, filter), out_bitdepth, out_chroma,
-                                !fmt || (warp && !warp->matrix) || (window && !warp) || !geom || !workspace_bytes, rq))
-        return rc;
-    rq.window = window;
-    return sink_plan(rq, geom, info, workspace_bytes);
-}
-
-// The mixing sink: the _tone sink with a ccmi_mix (mix NULL: that call itself, which is how the _tone
-// entry points run).
-static int dev_mix_plan(const char *who, const uint8_t *const *streams, const size_t *lens, int n, const Sink &k,
-                        int out_bitdepth, int out_chroma, ccmi_frame_geom *geom, ccmi_roi_info *info, ccmi_rect *window,
-                        size_t *workspace_bytes)
-{
-    DecodeRequest rq;
-    if (int rc = stream_request(who, streams, lens, n, k, out_bitdepth, out_chroma,
-                                !k.fmt || (k.warp && !k.warp->matrix) || (window && !k.warp) || !geom || !workspace_bytes, rq))
-        return rc;
-    rq.window = window;
-    return sink_plan(rq, geom, info, workspace_bytes);
-}
-
-static int dev_mix_run(const char *who, const uint8_t *const *streams, const size_t *lens, int n, const Sink &k,
-                       void *const *out_dev, const size_t *out_caps, int out_bitdepth, int out_chroma, void *workspace,
-                       size_t workspace_bytes, void *stream)
-{
-    DecodeRequest rq;
-    if (int rc = stream_request(who, streams, lens, n, k, out_bitdepth, out_chroma,
-                                !out_dev || !out_caps || !k.fmt || (k.warp && !k.warp->matrix), rq))
-        return rc;
-    return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
-}
-
-extern "C" int ccmi_decode_batch_dev_tone_plan(const uint8_t *const *streams, const size_t *lens, int n,
-                                               const ccmi_rect *roi, int out_bitdepth, int out_chroma,
-                                               const ccmi_tensor_fmt *fmt, const ccmi_resample *rs, const ccmi_warp *warp,
-                                               const ccmi_colour *colour, const ccmi_tone *tone, const ccmi_filter *filter,
-                                               ccmi_frame_geom *geom, ccmi_roi_info *info, ccmi_rect *window,
-                                               size_t *workspace_bytes)
-{
-    return dev_mix_plan("decode_batch_dev_tone_plan (frame 0)", streams, lens, n, toned(roi, fmt, rs, warp, colour, tone, filter),
-                        out_bitdepth, out_chroma, geom, info, window, workspace_bytes);
-}
-
-extern "C" int ccmi_decode_batch_dev_mix_plan(const uint8_t *const *streams, const size_t *lens, int n,
-                                              const ccmi_rect *roi, int out_bitdepth, int out_chroma,
-                                              const ccmi_tensor_fmt *fmt, const ccmi_resample *rs, const ccmi_warp *warp,
-                                              const ccmi_colour *colour, const ccmi_tone *tone, const ccmi_filter *filter,
-                                              const ccmi_mix *mix, ccmi_frame_geom *geom, ccmi_roi_info *info,
-                                              ccmi_rect *window, size_t *workspace_bytes)
-{
-    return dev_mix_plan("decode_batch_dev_mix_plan (frame 0)", streams, lens, n,
-                        mixed(roi, fmt, rs, warp, colour, tone, filter, mix), out_bitdepth, out_chroma, geom, info, window,
-                        workspace_bytes);
-}
-
-extern "C" int ccmi_decode_batch_dev_flt(const uint8_t *const *streams, const size_t *lens, int n, const ccmi_rect *roi,
-                                         void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
-                                         const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
-                                         const ccmi_filter *filter, int out_bitdepth, int out_chroma, void *workspace,
-                                         size_t workspace_bytes, void *stream)
-{
-    DecodeRequest rq;
-    if (int rc = stream_request("decode_batch_dev_flt (frame 0)", streams, lens, n,
-                                filtered(roi, fmt, rs, warp, colour, filter), out_bitdepth, out_chroma,
-                                !out_dev || !out_caps || !fmt || (warp && !warp->matrix), rq))
-        return rc;
-    return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
-}
-
-extern "C" int ccmi_decode_batch_dev_tone(const uint8_t *const *streams, const size_t *lens, int n, const ccmi_rect *roi,
-                                          void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
-                                          const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
-                                          const ccmi_tone *tone, const ccmi_filter *filter, int out_bitdepth, int out_chroma,
-                                          void *workspace, size_t workspace_bytes, void *stream)
-{
-    return dev_mix_run("decode_batch_dev_tone (frame 0)", streams, lens, n, toned(roi, fmt, rs, warp, colour, tone, filter),
-                       out_dev, out_caps, out_bitdepth, out_chroma, workspace, workspace_bytes, stream);
-}
-
-extern "C" int ccmi_decode_batch_dev_mix(const uint8_t *const *streams, const size_t *lens, int n, const ccmi_rect *roi,
-                                         void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
-                                         const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
-                                         const ccmi_tone *tone, const ccmi_filter *filter, const ccmi_mix *mix,
-                                         int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes,
-                                         void *stream)
-{
-    return dev_mix_run("decode_batch_dev_mix (frame 0)", streams, lens, n, mixed(roi, fmt, rs, warp, colour, tone, filter, mix),
-                       out_dev, out_caps, out_bitdepth, out_chroma, workspace, workspace_bytes, stream);
+    return sink_run(rs ? "decode_batch_dev_rs" : "decode_batch_dev_fmt", from_streams(streams, lens, n),
+                    Sink{roi, F32, fmt, rs}, FMT, out_dev, out_caps, out_bitdepth, out_chroma, workspace, workspace_bytes,
+                    stream);
 }
 
 extern "C" int ccmi_decode_batch_dev_fmt_plan(const uint8_t *const *streams, const size_t *lens, int n,
@@ -1421,6 +1233,113 @@ extern "C" int ccmi_decode_batch_dev_fmt(const uint8_t *const *streams, const si
 {
     return ccmi_decode_batch_dev_rs(streams, lens, n, roi, out_dev, out_caps, fmt, nullptr, out_bitdepth, out_chroma,
                                     workspace, workspace_bytes, stream);
+}
+
+extern "C" int ccmi_decode_batch_dev_warp_plan(const uint8_t *const *streams, const size_t *lens, int n,
+                                               int out_bitdepth, int out_chroma, const ccmi_tensor_fmt *fmt,
+                                               const ccmi_warp *warp, ccmi_frame_geom *geom, ccmi_roi_info *info,
+                                               ccmi_rect *window, size_t *workspace_bytes)
+{
+    return sink_plan("decode_batch_dev_warp_plan (frame 0)", from_streams(streams, lens, n), Sink{nullptr, F32, fmt, nullptr, warp},
+                     FMT_WARP, out_bitdepth, out_chroma, geom, info, window, workspace_bytes);
+}
+
+extern "C" int ccmi_decode_batch_dev_warp(const uint8_t *const *streams, const size_t *lens, int n,
+                                          void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
+                                          const ccmi_warp *warp, int out_bitdepth, int out_chroma, void *workspace,
+                                          size_t workspace_bytes, void *stream)
+{
+    return sink_run("decode_batch_dev_warp (frame 0)", from_streams(streams, lens, n), Sink{nullptr, F32, fmt, nullptr, warp},
+                    FMT_WARP, out_dev, out_caps, out_bitdepth, out_chroma, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ccmi_decode_batch_dev_col_plan(const uint8_t *const *streams, const size_t *lens, int n,
+                                              const ccmi_rect *roi, int out_bitdepth, int out_chroma,
+                                              const ccmi_tensor_fmt *fmt, const ccmi_resample *rs, const ccmi_warp *warp,
+                                              const ccmi_colour *colour, ccmi_frame_geom *geom, ccmi_roi_info *info,
+                                              ccmi_rect *window, size_t *workspace_bytes)
+{
+    return sink_plan("decode_batch_dev_col_plan (frame 0)", from_streams(streams, lens, n), Sink{roi, F32, fmt, rs, warp, colour},
+                     FMT, out_bitdepth, out_chroma, geom, info, window, workspace_bytes);
+}
+
+extern "C" int ccmi_decode_batch_dev_col(const uint8_t *const *streams, const size_t *lens, int n, const ccmi_rect *roi,
+                                         void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
+                                         const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
+                                         int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes,
+                                         void *stream)
+{
+    return sink_run("decode_batch_dev_col (frame 0)", from_streams(streams, lens, n), Sink{roi, F32, fmt, rs, warp, colour}, FMT,
+                    out_dev, out_caps, out_bitdepth, out_chroma, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ccmi_decode_batch_dev_flt_plan(const uint8_t *const *streams, const size_t *lens, int n,
+                                              const ccmi_rect *roi, int out_bitdepth, int out_chroma,
+                                              const ccmi_tensor_fmt *fmt, const ccmi_resample *rs, const ccmi_warp *warp,
+                                              const ccmi_colour *colour, const ccmi_filter *filter, ccmi_frame_geom *geom,
+                                              ccmi_roi_info *info, ccmi_rect *window, size_t *workspace_bytes)
+{
+    return sink_plan("decode_batch_dev_flt_plan (frame 0)", from_streams(streams, lens, n),
+                     Sink{roi, F32, fmt, rs, warp, colour, nullptr, filter}, FMT, out_bitdepth, out_chroma, geom, info, window,
+                     workspace_bytes);
+}
+
+extern "C" int ccmi_decode_batch_dev_flt(const uint8_t *const *streams, const size_t *lens, int n, const ccmi_rect *roi,
+                                         void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
+                                         const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
+                                         const ccmi_filter *filter, int out_bitdepth, int out_chroma, void *workspace,
+                                         size_t workspace_bytes, void *stream)
+{
+    return sink_run("decode_batch_dev_flt (frame 0)", from_streams(streams, lens, n),
+                    Sink{roi, F32, fmt, rs, warp, colour, nullptr, filter}, FMT, out_dev, out_caps, out_bitdepth, out_chroma,
+                    workspace, workspace_bytes, stream);
+}
+
+extern "C" int ccmi_decode_batch_dev_tone_plan(const uint8_t *const *streams, const size_t *lens, int n,
+                                               const ccmi_rect *roi, int out_bitdepth, int out_chroma,
+                                               const ccmi_tensor_fmt *fmt, const ccmi_resample *rs, const ccmi_warp *warp,
+                                               const ccmi_colour *colour, const ccmi_tone *tone, const ccmi_filter *filter,
+                                               ccmi_frame_geom *geom, ccmi_roi_info *info, ccmi_rect *window,
+                                               size_t *workspace_bytes)
+{
+    return sink_plan("decode_batch_dev_tone_plan (frame 0)", from_streams(streams, lens, n),
+                     Sink{roi, F32, fmt, rs, warp, colour, tone, filter}, FMT, out_bitdepth, out_chroma, geom, info, window,
+                     workspace_bytes);
+}
+
+extern "C" int ccmi_decode_batch_dev_tone(const uint8_t *const *streams, const size_t *lens, int n, const ccmi_rect *roi,
+                                          void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
+                                          const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
+                                          const ccmi_tone *tone, const ccmi_filter *filter, int out_bitdepth, int out_chroma,
+                                          void *workspace, size_t workspace_bytes, void *stream)
+{
+    return sink_run("decode_batch_dev_tone (frame 0)", from_streams(streams, lens, n),
+                    Sink{roi, F32, fmt, rs, warp, colour, tone, filter}, FMT, out_dev, out_caps, out_bitdepth, out_chroma,
+                    workspace, workspace_bytes, stream);
+}
+
+extern "C" int ccmi_decode_batch_dev_mix_plan(const uint8_t *const *streams, const size_t *lens, int n,
+                                              const ccmi_rect *roi, int out_bitdepth, int out_chroma,
+                                              const ccmi_tensor_fmt *fmt, const ccmi_resample *rs, const ccmi_warp *warp,
+                                              const ccmi_colour *colour, const ccmi_tone *tone, const ccmi_filter *filter,
+                                              const ccmi_mix *mix, ccmi_frame_geom *geom, ccmi_roi_info *info,
+                                              ccmi_rect *window, size_t *workspace_bytes)
+{
+    return sink_plan("decode_batch_dev_mix_plan (frame 0)", from_streams(streams, lens, n),
+                     Sink{roi, F32, fmt, rs, warp, colour, tone, filter, mix}, FMT, out_bitdepth, out_chroma, geom, info, window,
+                     workspace_bytes);
+}
+
+extern "C" int ccmi_decode_batch_dev_mix(const uint8_t *const *streams, const size_t *lens, int n, const ccmi_rect *roi,
+                                         void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
+                                         const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
+                                         const ccmi_tone *tone, const ccmi_filter *filter, const ccmi_mix *mix,
+                                         int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes,
+                                         void *stream)
+{
+    return sink_run("decode_batch_dev_mix (frame 0)", from_streams(streams, lens, n),
+                    Sink{roi, F32, fmt, rs, warp, colour, tone, filter, mix}, FMT, out_dev, out_caps, out_bitdepth, out_chroma,
+                    workspace, workspace_bytes, stream);
 }
 
 extern "C" int ccmi_latents_plan(const uint8_t *const *streams, const size_t *lens, int n, int latent_type,
@@ -1527,26 +1446,21 @@ extern "C" int ccmi_latents_values(const ccmi_latents *h, int i, int32_t *out_de
     return CCMI_OK;
 }
 
+// The device sinks' table (above) over a latent store.
 extern "C" int ccmi_latents_render_plan(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
                                         int out_bitdepth, int out_chroma, int sample_type, ccmi_frame_geom *geom,
                                         ccmi_roi_info *info, size_t *workspace_bytes)
 {
-    DecodeRequest rq;
-    if (int rc = latents_request("latents_render_plan", h, index, m, samples(roi, sample_type), out_bitdepth, out_chroma,
-                                 false, !geom || !workspace_bytes, rq))
-        return rc;
-    return sink_plan(rq, geom, info, workspace_bytes);
+    return sink_plan("latents_render_plan", from_store(h, index, m), Sink{roi, sample_type}, PLAIN, out_bitdepth, out_chroma,
+                     geom, info, nullptr, workspace_bytes);
 }
 
 extern "C" int ccmi_latents_render(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
                                    void *const *out_dev, const size_t *out_caps, int sample_type, int out_bitdepth,
                                    int out_chroma, void *workspace, size_t workspace_bytes, void *stream)
 {
-    DecodeRequest rq;
-    if (int rc = latents_request("latents_render", h, index, m, samples(roi, sample_type), out_bitdepth, out_chroma, true,
-                                 !out_dev || !out_caps, rq))
-        return rc;
-    return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
+    return sink_run("latents_render", from_store(h, index, m), Sink{roi, sample_type}, PLAIN, out_dev, out_caps, out_bitdepth,
+                    out_chroma, workspace, workspace_bytes, stream);
 }
 
 extern "C" int ccmi_latents_render_rs_plan(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
@@ -1554,12 +1468,8 @@ extern "C" int ccmi_latents_render_rs_plan(const ccmi_latents *h, const int *ind
                                            const ccmi_resample *rs, ccmi_frame_geom *geom, ccmi_roi_info *info,
                                            size_t *workspace_bytes)
 {
-    DecodeRequest rq;
-    if (int rc = latents_request(rs ? "latents_render_rs_plan" : "latents_render_fmt_plan", h, index, m,
-                                 formatted(roi, fmt, rs), out_bitdepth, out_chroma, false,
-                                 !fmt || !geom || !workspace_bytes, rq))
-        return rc;
-    return sink_plan(rq, geom, info, workspace_bytes);
+    return sink_plan(rs ? "latents_render_rs_plan" : "latents_render_fmt_plan", from_store(h, index, m), Sink{roi, F32, fmt, rs},
+                     FMT, out_bitdepth, out_chroma, geom, info, nullptr, workspace_bytes);
 }
 
 extern "C" int ccmi_latents_render_rs(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
@@ -1567,156 +1477,8 @@ extern "C" int ccmi_latents_render_rs(const ccmi_latents *h, const int *index, i
                                       const ccmi_resample *rs, int out_bitdepth, int out_chroma, void *workspace,
                                       size_t workspace_bytes, void *stream)
 {
-    DecodeRequest rq;
-    if (int rc = latents_request(rs ? "latents_render_rs" : "latents_render_fmt", h, index, m, formatted(roi, fmt, rs),
-                                 out_bitdepth, out_chroma, true, !out_dev || !out_caps || !fmt, rq))
-        return rc;
-    return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
-}
-
-extern "C" int ccmi_latents_render_warp_plan(const ccmi_latents *h, const int *index, int m, int out_bitdepth,
-                                             int out_chroma, const ccmi_tensor_fmt *fmt, const ccmi_warp *warp,
-                                             ccmi_frame_geom *geom, ccmi_roi_info *info, ccmi_rect *window,
-                                             size_t *workspace_bytes)
-{
-    DecodeRequest rq;
-    if (int rc = latents_request("latents_render_warp_plan (frame 0)", h, index, m, warped(fmt, warp), out_bitdepth,
-                                 out_chroma, false, !fmt || !warp || !warp->matrix || !geom || !workspace_bytes, rq))
-        return rc;
-    rq.window = window;
-    return sink_plan(rq, geom, info, workspace_bytes);
-}
-
-extern "C" int ccmi_latents_render_warp(const ccmi_latents *h, const int *index, int m, void *const *out_dev,
-                                        const size_t *out_caps, const ccmi_tensor_fmt *fmt, const ccmi_warp *warp,
-                                        int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes,
-                                        void *stream)
-{
-    DecodeRequest rq;
-    if (int rc = latents_request("latents_render_warp (frame 0)", h, index, m, warped(fmt, warp), out_bitdepth, out_chroma,
-                                 true, !out_dev || !out_caps || !fmt || !warp || !warp->matrix, rq))
-        return rc;
-    return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
-}
-
-extern "C" int ccmi_latents_render_col_plan(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
-                                            int out_bitdepth, int out_chroma, const ccmi_tensor_fmt *fmt,
-                                            const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
-                                            ccmi_frame_geom *geom, ccmi_roi_info *info, ccmi_rect *window,
-                                            size_t *workspace_bytes)
-{
-    DecodeRequest rq;
-    if (int rc = latents_request("latents_render_col_plan (frame 0)", h, index, m, coloured(roi, fmt, rs, warp, colour),
-                                 out_bitdepth, out_chroma, false,
-                                 !fmt || (warp && !warp->matrix) || (window && !warp) || !geom || !workspace_bytes, rq))
-        return rc;
-    rq.window = window;
-    return sink_plan(rq, geom, info, workspace_bytes);
-}
-
-extern "C" int ccmi_latents_render_col(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
-                                       void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
-                                       const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
-                                       int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes,
-                                       void *stream)
-{
-    DecodeRequest rq;
-    if (int rc = latents_request("latents_render_col (frame 0)", h, index, m, coloured(roi, fmt, rs, warp, colour),
-                                 out_bitdepth, out_chroma, true, !out_dev || !out_caps || !fmt || (warp && !warp->matrix), rq))
-        return rc;
-    return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
-}
-
-static int lat_mix_plan(const char *who, const ccmi_latents *h, const int *index, int m, const Sink &k, int out_bitdepth,
-                        int out_chroma, ccmi_frame_geom *geom, ccmi_roi_info *info, ccmi_rect *window, size_t *workspace_bytes)
-{
-    DecodeRequest rq;
-    if (int rc = latents_request(who, h, index, m, k, out_bitdepth, out_chroma, false,
-                                 !k.fmt || (k.warp && !k.warp->matrix) || (window && !k.warp) || !geom || !workspace_bytes, rq))
-        return rc;
-    rq.window = window;
-    return sink_plan(rq, geom, info, workspace_bytes);
-}
-
-static int lat_mix_run(const char *who, const ccmi_latents *h, const int *index, int m, const Sink &k, void *const *out_dev,
-                       const size_t *out_caps, int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes,
-                       void *stream)
-{
-    DecodeRequest rq;
-    if (int rc = latents_request(who, h, index, m, k, out_bitdepth, out_chroma, true,
-                                 !out_dev || !out_caps || !k.fmt || (k.warp && !k.warp->matrix), rq))
-        return rc;
-    return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
-}
-
-extern "C" int ccmi_latents_render_flt_plan(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
-                                            int out_bitdepth, int out_chroma, const ccmi_tensor_fmt *fmt,
-                                            const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
-                                            const ccmi_filter *filter, ccmi_frame_geom *geom, ccmi_roi_info *info,
-                                            ccmi_rect *window, size_t *workspace_bytes)
-{
-    DecodeRequest rq;
-    if (int rc = latents_request("latents_render_flt_plan (frame 0)", h, index, m,
-                                 filtered(roi, fmt, rs, warp, colour, filter), out_bitdepth, out_chroma, false,
-                                 !fmt || (warp && !warp->matrix) || (window && !warp) || !geom || !workspace_bytes, rq))
-        return rc;
-    rq.window = window;
-    return sink_plan(rq, geom, info, workspace_bytes);
-}
-
-extern "C" int ccmi_latents_render_tone_plan(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
-                                             int out_bitdepth, int out_chroma, const ccmi_tensor_fmt *fmt,
-                                             const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
-                                             const ccmi_tone *tone, const ccmi_filter *filter, ccmi_frame_geom *geom,
-                                             ccmi_roi_info *info, ccmi_rect *window, size_t *workspace_bytes)
-{
-    return lat_mix_plan("latents_render_tone_plan (frame 0)", h, index, m, toned(roi, fmt, rs, warp, colour, tone, filter),
-                        out_bitdepth, out_chroma, geom, info, window, workspace_bytes);
-}
-
-extern "C" int ccmi_latents_render_mix_plan(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
-                                            int out_bitdepth, int out_chroma, const ccmi_tensor_fmt *fmt,
-                                            const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
-                                            const ccmi_tone *tone, const ccmi_filter *filter, const ccmi_mix *mix,
-                                            ccmi_frame_geom *geom, ccmi_roi_info *info, ccmi_rect *window,
-                                            size_t *workspace_bytes)
-{
-    return lat_mix_plan("latents_render_mix_plan (frame 0)", h, index, m, mixed(roi, fmt, rs, warp, colour, tone, filter, mix),
-                        out_bitdepth, out_chroma, geom, info, window, workspace_bytes);
-}
-
-extern "C" int ccmi_latents_render_flt(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
-                                       void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
-                                       const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
-                                       const ccmi_filter *filter, int out_bitdepth, int out_chroma, void *workspace,
-                                       size_t workspace_bytes, void *stream)
-{
-    DecodeRequest rq;
-    if (int rc = latents_request("latents_render_flt (frame 0)", h, index, m,
-                                 filtered(roi, fmt, rs, warp, colour, filter), out_bitdepth, out_chroma, true,
-                                 !out_dev || !out_caps || !fmt || (warp && !warp->matrix), rq))
-        return rc;
-    return sink_run(rq, out_dev, out_caps, workspace, workspace_bytes, stream);
-}
-
-extern "C" int ccmi_latents_render_tone(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
-                                        void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
-                                        const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
-                                        const ccmi_tone *tone, const ccmi_filter *filter, int out_bitdepth, int out_chroma,
-                                        void *workspace, size_t workspace_bytes, void *stream)
-{
-    return lat_mix_run("latents_render_tone (frame 0)", h, index, m, toned(roi, fmt, rs, warp, colour, tone, filter), out_dev,
-                       out_caps, out_bitdepth, out_chroma, workspace, workspace_bytes, stream);
-}
-
-extern "C" int ccmi_latents_render_mix(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
-                                       void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
-                                       const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
-                                       const ccmi_tone *tone, const ccmi_filter *filter, const ccmi_mix *mix,
-                                       int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes, void *stream)
-{
-    return lat_mix_run("latents_render_mix (frame 0)", h, index, m, mixed(roi, fmt, rs, warp, colour, tone, filter, mix),
-                       out_dev, out_caps, out_bitdepth, out_chroma, workspace, workspace_bytes, stream);
+    return sink_run(rs ? "latents_render_rs" : "latents_render_fmt", from_store(h, index, m), Sink{roi, F32, fmt, rs}, FMT,
+                    out_dev, out_caps, out_bitdepth, out_chroma, workspace, workspace_bytes, stream);
 }
 
 extern "C" int ccmi_latents_render_fmt_plan(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
@@ -1734,6 +1496,109 @@ extern "C" int ccmi_latents_render_fmt(const ccmi_latents *h, const int *index, 
 {
     return ccmi_latents_render_rs(h, index, m, roi, out_dev, out_caps, fmt, nullptr, out_bitdepth, out_chroma, workspace,
                                   workspace_bytes, stream);
+}
+
+extern "C" int ccmi_latents_render_warp_plan(const ccmi_latents *h, const int *index, int m, int out_bitdepth,
+                                             int out_chroma, const ccmi_tensor_fmt *fmt, const ccmi_warp *warp,
+                                             ccmi_frame_geom *geom, ccmi_roi_info *info, ccmi_rect *window,
+                                             size_t *workspace_bytes)
+{
+    return sink_plan("latents_render_warp_plan (frame 0)", from_store(h, index, m), Sink{nullptr, F32, fmt, nullptr, warp},
+                     FMT_WARP, out_bitdepth, out_chroma, geom, info, window, workspace_bytes);
+}
+
+extern "C" int ccmi_latents_render_warp(const ccmi_latents *h, const int *index, int m, void *const *out_dev,
+                                        const size_t *out_caps, const ccmi_tensor_fmt *fmt, const ccmi_warp *warp,
+                                        int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes,
+                                        void *stream)
+{
+    return sink_run("latents_render_warp (frame 0)", from_store(h, index, m), Sink{nullptr, F32, fmt, nullptr, warp}, FMT_WARP,
+                    out_dev, out_caps, out_bitdepth, out_chroma, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ccmi_latents_render_col_plan(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
+                                            int out_bitdepth, int out_chroma, const ccmi_tensor_fmt *fmt,
+                                            const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
+                                            ccmi_frame_geom *geom, ccmi_roi_info *info, ccmi_rect *window,
+                                            size_t *workspace_bytes)
+{
+    return sink_plan("latents_render_col_plan (frame 0)", from_store(h, index, m), Sink{roi, F32, fmt, rs, warp, colour}, FMT,
+                     out_bitdepth, out_chroma, geom, info, window, workspace_bytes);
+}
+
+extern "C" int ccmi_latents_render_col(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
+                                       void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
+                                       const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
+                                       int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes,
+                                       void *stream)
+{
+    return sink_run("latents_render_col (frame 0)", from_store(h, index, m), Sink{roi, F32, fmt, rs, warp, colour}, FMT, out_dev,
+                    out_caps, out_bitdepth, out_chroma, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ccmi_latents_render_flt_plan(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
+                                            int out_bitdepth, int out_chroma, const ccmi_tensor_fmt *fmt,
+                                            const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
+                                            const ccmi_filter *filter, ccmi_frame_geom *geom, ccmi_roi_info *info,
+                                            ccmi_rect *window, size_t *workspace_bytes)
+{
+    return sink_plan("latents_render_flt_plan (frame 0)", from_store(h, index, m),
+                     Sink{roi, F32, fmt, rs, warp, colour, nullptr, filter}, FMT, out_bitdepth, out_chroma, geom, info, window,
+                     workspace_bytes);
+}
+
+extern "C" int ccmi_latents_render_flt(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
+                                       void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
+                                       const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
+                                       const ccmi_filter *filter, int out_bitdepth, int out_chroma, void *workspace,
+                                       size_t workspace_bytes, void *stream)
+{
+    return sink_run("latents_render_flt (frame 0)", from_store(h, index, m), Sink{roi, F32, fmt, rs, warp, colour, nullptr, filter},
+                    FMT, out_dev, out_caps, out_bitdepth, out_chroma, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ccmi_latents_render_tone_plan(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
+                                             int out_bitdepth, int out_chroma, const ccmi_tensor_fmt *fmt,
+                                             const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
+                                             const ccmi_tone *tone, const ccmi_filter *filter, ccmi_frame_geom *geom,
+                                             ccmi_roi_info *info, ccmi_rect *window, size_t *workspace_bytes)
+{
+    return sink_plan("latents_render_tone_plan (frame 0)", from_store(h, index, m),
+                     Sink{roi, F32, fmt, rs, warp, colour, tone, filter}, FMT, out_bitdepth, out_chroma, geom, info, window,
+                     workspace_bytes);
+}
+
+extern "C" int ccmi_latents_render_tone(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
+                                        void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
+                                        const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
+                                        const ccmi_tone *tone, const ccmi_filter *filter, int out_bitdepth, int out_chroma,
+                                        void *workspace, size_t workspace_bytes, void *stream)
+{
+    return sink_run("latents_render_tone (frame 0)", from_store(h, index, m), Sink{roi, F32, fmt, rs, warp, colour, tone, filter},
+                    FMT, out_dev, out_caps, out_bitdepth, out_chroma, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ccmi_latents_render_mix_plan(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
+                                            int out_bitdepth, int out_chroma, const ccmi_tensor_fmt *fmt,
+                                            const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
+                                            const ccmi_tone *tone, const ccmi_filter *filter, const ccmi_mix *mix,
+                                            ccmi_frame_geom *geom, ccmi_roi_info *info, ccmi_rect *window,
+                                            size_t *workspace_bytes)
+{
+    return sink_plan("latents_render_mix_plan (frame 0)", from_store(h, index, m),
+                     Sink{roi, F32, fmt, rs, warp, colour, tone, filter, mix}, FMT, out_bitdepth, out_chroma, geom, info, window,
+                     workspace_bytes);
+}
+
+extern "C" int ccmi_latents_render_mix(const ccmi_latents *h, const int *index, int m, const ccmi_rect *roi,
+                                       void *const *out_dev, const size_t *out_caps, const ccmi_tensor_fmt *fmt,
+                                       const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
+                                       const ccmi_tone *tone, const ccmi_filter *filter, const ccmi_mix *mix,
+                                       int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes, void *stream)
+{
+    return sink_run("latents_render_mix (frame 0)", from_store(h, index, m),
+                    Sink{roi, F32, fmt, rs, warp, colour, tone, filter, mix}, FMT, out_dev, out_caps, out_bitdepth, out_chroma,
+                    workspace, workspace_bytes, stream);
 }
 
 namespace ccmi {

@@ -339,7 +339,7 @@ def test_zero_strides_and_mix_staged_frames_of_several_sizes(store):
     assert (fmt.stride_c, fmt.stride_y, fmt.stride_x) == (0, 0, 0)
     mx, keep_m = decode._mix(erase, None, mix, m)
     head = (store._handle(), idx)
-    geom, need = decode._plan_model(L.ccmi_latents_render_mix_plan, head, m, rects, fmt, None, 0, 444, mx=mx)
+    geom, need = decode._plan_model(store._source(idx), decode._Sink(m, rects, mx=mx, keep=keep_m), fmt, 0, 444)
     assert [(g.height, g.width) for g in geom] == sizes
     slack, offs, pos = 4096, [], 4096
     for h, w in sizes:

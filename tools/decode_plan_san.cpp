@@ -14,7 +14,8 @@
 //   cd cool-chic_amd && hipcc -O1 -g -std=c++17 -fwrapv --offload-arch=gfx950 \
 //       -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
 //       -x hip ../tools/decode_plan_san.cpp csrc/dec_plan.cpp csrc/dec_host.cpp csrc/ccmi_api.cpp \
-//       csrc/dec_arm.hip csrc/dec_tail.hip csrc/dec_out.hip csrc/dec_latents.hip -o /tmp/decode_plan_san
+//       csrc/dec_arm.hip csrc/dec_tail.hip csrc/dec_out.hip csrc/dec_filter.hip csrc/dec_tone.hip \
+//       csrc/dec_mix.hip csrc/dec_latents.hip -o /tmp/decode_plan_san
 //   /tmp/decode_plan_san $(find ../tests/golden/cool ../tests/golden/cool_synth -name '*.cool')
 #include <stdio.h>
 #include <stdlib.h>
@@ -26,7 +27,7 @@
 #include "../cool-chic_amd/csrc/ccmi_internal.h"
 
 // the float forward path is not linked: ccmi_api.cpp only needs the symbols
-int ccmi_launch_arm_f32(const ccmi_arm_args *, hipStream_t) { return CCMI_ERR_UNSUPPORTED; }
+int ccmi_launch_arm_f32(const ccmi_arm_args *, hipStream_t, int) { return CCMI_ERR_UNSUPPORTED; }
 int ccmi_launch_ups_f32(const ccmi_ups_args *, hipStream_t) { return CCMI_ERR_UNSUPPORTED; }
 int ccmi_launch_syn_f32(const ccmi_syn_args *, hipStream_t) { return CCMI_ERR_UNSUPPORTED; }
 int ccmi_launch_post_f32(const ccmi_post_args *, hipStream_t) { return CCMI_ERR_UNSUPPORTED; }
