@@ -43,6 +43,8 @@ EXPORTED = [
     "ccmi_decode_batch_dev_flt_plan", "ccmi_decode_batch_dev_flt", "ccmi_latents_render_flt_plan", "ccmi_latents_render_flt",
     "ccmi_decode_batch_dev_tone_plan", "ccmi_decode_batch_dev_tone", "ccmi_latents_render_tone_plan", "ccmi_latents_render_tone",
     "ccmi_decode_batch_dev_mix_plan", "ccmi_decode_batch_dev_mix", "ccmi_latents_render_mix_plan", "ccmi_latents_render_mix",
+    "ccmi_decode_batch_dev_blend_plan", "ccmi_decode_batch_dev_blend", "ccmi_latents_render_blend_plan",
+    "ccmi_latents_render_blend",
     "ccmi_ups_workspace_bytes_i32", "ccmi_ups_forward_i32", "ccmi_syn_workspace_bytes_i32", "ccmi_syn_forward_i32",
     "ccmi_cool_parse", "ccmi_code_wb", "ccmi_decode_wb", "ccmi_code_latent_layer", "ccmi_arm_forward_i32",
     "ccmi_encode_frame", "ccmi_row_reduce_f32", "ccmi_train_param_count", "ccmi_train_workspace_bytes", "ccmi_train_step",

@@ -61,6 +61,10 @@ _PROTOS = {
     "ccmi_decode_batch_dev_mix": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _Z, _P],
     "ccmi_latents_render_mix_plan": [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "ccmi_latents_render_mix": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _Z, _P],
+    "ccmi_decode_batch_dev_blend_plan": [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "ccmi_decode_batch_dev_blend": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _Z, _P],
+    "ccmi_latents_render_blend_plan": [_P, _P, _I, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "ccmi_latents_render_blend": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _Z, _P],
     "ccmi_latents_plan": [_P, _P, _I, _I, _P, _P, _P],
     "ccmi_latents_decode": [_P, _P, _I, _I, _P, _Z, _P, _Z, _P, _P],
     "ccmi_latents_free": [_P],
@@ -937,6 +941,169 @@ def trivial_augment_wide(n: int, num_magnitude_bins: int = 31, generator=None, s
     return _ra_draw(n, 1, 0, int(num_magnitude_bins), generator, size, base, True)
 
 
+# AugMix's op table (torchvision's AugMix._augmentation_space): name, signed; the last four with all_ops
+_AM_OPS = (("ShearX", True), ("ShearY", True), ("TranslateX", True), ("TranslateY", True), ("Rotate", True),
+           ("Posterize", False), ("Solarize", False), ("AutoContrast", False), ("Equalize", False),
+           ("Brightness", True), ("Color", True), ("Contrast", True), ("Sharpness", True))
+_AM_BINS = 10  # torchvision's _PARAMETER_MAX
+
+
+def _am_magnitude(name, k, size):
+    """The magnitude of bin k of 10 of AugMix's op `name` for frames of `size` = (H, W)."""
+    import numpy as np
+    lin = lambda hi: float(np.linspace(0.0, hi, _AM_BINS)[k])  # noqa: E731
+    if name in ("ShearX", "ShearY"):
+        return lin(0.3)
+    if name in ("Brightness", "Color", "Contrast", "Sharpness"):
+        return lin(0.9)
+    if name == "TranslateX":
+        return lin(size[1] / 3.0)
+    if name == "TranslateY":
+        return lin(size[0] / 3.0)
+    if name == "Rotate":
+        return lin(30.0)
+    if name == "Posterize":
+        return float(max(4 - int(round(k / ((_AM_BINS - 1) / 4))), 1))  # the library posterizes to 1 .. 8 bits
+    if name == "Solarize":
+        return float(np.linspace(1.0, 0.0, _AM_BINS)[k])
+    return 0.0
+
+
+def aug_mix(n: int, size, severity: int = 3, mixture_width: int = 3, chain_depth: int = -1, alpha: float = 1.0,
+            all_ops: bool = True, generator=None, base=None) -> dict:
+    """n draws of torchvision's AugMix(severity, mixture_width, chain_depth, alpha, all_ops) for frames stored
+    at size = (H, W), as ONE call of m = n (1 + mixture_width) frames of the *_model calls: a dict with
+      'repeat'    int array [m]: frame j of the call is frame repeat[j] of the n (repeat index, roi and
+                  mirror by it: a frame and its chains share them),
+      'matrices'  float32 [m, 2, 3] for affine= (with size=size),
+      'tone_ops'  m tone lists for tone_ops=,
+      'blend'     m entries for blend=,  'silent'  m flags for silent=.
+    Frame j (1 + width) is frame j itself, clean: the base matrix (None: the identity; else one [2, 3]
+    matrix or one per frame of the n, as for rand_augment()), no tone ops, not silent, and the blend list
+    [(itself, m_0), (chain 1, w_1), ..., (chain width, w_width)].  Its chains follow it and are silent, so
+    the call returns n frames.
+    A chain is chain_depth ops (<= 0: 1 .. 3, drawn uniformly), each drawn uniformly from the op table:
+    ShearX, ShearY (0 .. 0.3), TranslateX, TranslateY (0 .. W / 3, H / 3 pixels), Rotate (0 .. 30 degrees),
+    Posterize (4 - round(bin / 2.25) bits: 4 .. 1; torchvision's 0 bits at bins 8 and 9, a black frame, is
+    drawn as 1 bit), Solarize (threshold 1 .. 0), AutoContrast, Equalize, and with
+    all_ops Brightness, Color, Contrast, Sharpness (1 +- 0 .. 0.9).  The magnitude is one of 10 bins, its
+    index drawn uniformly below severity (1 .. 10); signed ops take a random sign.
+    Weights: (m_0, m_1) ~ Beta(alpha, alpha) as a Dirichlet of two, (d_1 .. d_width) ~ Dirichlet(alpha),
+    w_i = d_i m_1, all rounded to float32 here: non-negative, and m_0 + sum w_i = 1 within float32 rounding.
+    As in rand_augment(), a chain's geometric ops are composed into one matrix that runs first, in one
+    warp, and its photometric ops follow in their order; AugMix's interleaving inside a chain is not
+    reproduced, with rand_augment()'s caveat for statistics ops.  generator: a torch.Generator (CPU); the
+    same seed gives the same draws."""
+    import numpy as np
+    import torch
+    size = (int(size[0]), int(size[1]))
+    width, depth = int(mixture_width), int(chain_depth)
+    if not 1 <= int(severity) <= _AM_BINS:
+        raise ValueError(f"aug_mix: severity {severity} (1 .. {_AM_BINS})")
+    if not 1 <= width <= BLEND_MAX_TERMS - 1:
+        raise ValueError(f"aug_mix: mixture_width {mixture_width} (1 .. {BLEND_MAX_TERMS - 1})")
+    if depth > TONE_MAX_OPS:
+        raise ValueError(f"aug_mix: chain_depth {chain_depth} (at most {TONE_MAX_OPS})")
+    if base is not None:
+        base = np.asarray(base, dtype=np.float64).reshape(-1, 2, 3)
+        if base.shape[0] not in (1, n):
+            raise ValueError(f"augment: base takes one [2, 3] matrix, or one per frame ({n}), got {base.shape[0]}")
+    ops = _AM_OPS if all_ops else _AM_OPS[:9]
+    m = n * (1 + width)
+    mats, tones, blend = np.zeros((m, 2, 3), dtype=np.float32), [], []
+    # torch has no public Dirichlet or gamma draw that takes a generator; this private one is what torchvision's
+    # AugMix calls (torch.distributions.Dirichlet would draw from the global generator instead)
+    if not hasattr(torch, "_sample_dirichlet"):
+        raise RuntimeError("aug_mix: this torch has no torch._sample_dirichlet(concentration, generator)")
+    two = torch._sample_dirichlet(torch.full((n, 2), float(alpha), dtype=torch.float64), generator)
+    chains = torch._sample_dirichlet(torch.full((n, width), float(alpha), dtype=torch.float64), generator)
+    weights = torch.cat([two[:, :1], chains * two[:, 1:]], dim=1).to(torch.float32).numpy()
+    for j in range(n):
+        clean = j * (1 + width)
+        geo0 = np.eye(3)
+        if base is not None:
+            geo0[:2] = base[j % base.shape[0]]
+        mats[clean] = geo0[:2]
+        tones.append([])
+        blend.append([(clean + i, float(weights[j, i])) for i in range(1 + width)])
+        for i in range(width):
+            geo, tone = geo0.copy(), []
+            d = depth if depth > 0 else int(torch.randint(1, 4, (1,), generator=generator))
+            for _ in range(d):
+                name, signed = ops[int(torch.randint(len(ops), (1,), generator=generator))]
+                k = int(torch.randint(int(severity), (1,), generator=generator))
+                mag = _am_magnitude(name, k, size)
+                if signed and int(torch.randint(2, (1,), generator=generator)):
+                    mag = -mag
+                geo = _ra_apply(name, mag, size, geo, tone)
+            mats[clean + 1 + i] = geo[:2]
+            tones.append(tone)
+            blend.append(None)
+    silent = [(j % (1 + width)) != 0 for j in range(m)]
+    return {"repeat": np.repeat(np.arange(n), 1 + width), "matrices": mats, "tone_ops": tones, "blend": blend,
+            "silent": silent}
+
+
+# AutoAugment's ImageNet policy (torchvision's AutoAugment._get_policies): 25 pairs of (op, probability, bin)
+_AA_IMAGENET = (
+    (("Posterize", 0.4, 8), ("Rotate", 0.6, 9)), (("Solarize", 0.6, 5), ("AutoContrast", 0.6, None)),
+    (("Equalize", 0.8, None), ("Equalize", 0.6, None)), (("Posterize", 0.6, 7), ("Posterize", 0.6, 6)),
+    (("Equalize", 0.4, None), ("Solarize", 0.2, 4)), (("Equalize", 0.4, None), ("Rotate", 0.8, 8)),
+    (("Solarize", 0.6, 3), ("Equalize", 0.6, None)), (("Posterize", 0.8, 5), ("Equalize", 1.0, None)),
+    (("Rotate", 0.2, 3), ("Solarize", 0.6, 8)), (("Equalize", 0.6, None), ("Posterize", 0.4, 6)),
+    (("Rotate", 0.8, 8), ("Color", 0.4, 0)), (("Rotate", 0.4, 9), ("Equalize", 0.6, None)),
+    (("Equalize", 0.0, None), ("Equalize", 0.8, None)), (("Invert", 0.6, None), ("Equalize", 1.0, None)),
+    (("Color", 0.6, 4), ("Contrast", 1.0, 8)), (("Rotate", 0.8, 8), ("Color", 1.0, 2)),
+    (("Color", 0.8, 8), ("Solarize", 0.8, 7)), (("Sharpness", 0.4, 7), ("Invert", 0.6, None)),
+    (("ShearX", 0.6, 5), ("Equalize", 1.0, None)), (("Color", 0.4, 0), ("Equalize", 0.6, None)),
+    (("Equalize", 0.4, None), ("Solarize", 0.2, 4)), (("Solarize", 0.6, 5), ("AutoContrast", 0.6, None)),
+    (("Invert", 0.6, None), ("Equalize", 1.0, None)), (("Color", 0.6, 4), ("Contrast", 1.0, 8)),
+    (("Equalize", 0.8, None), ("Equalize", 0.6, None)))
+_AA_SIGNED = ("ShearX", "ShearY", "TranslateX", "TranslateY", "Rotate", "Brightness", "Color", "Contrast", "Sharpness")
+_INVERT = ((-1.0, 0.0, 0.0, 1.0), (0.0, -1.0, 0.0, 1.0), (0.0, 0.0, -1.0, 1.0))  # 1 - x as a matrix tone op
+
+
+def auto_augment(n: int, policy: str = "imagenet", generator=None, size=(224, 224), base=None):
+    """n draws of torchvision's AutoAugment(AutoAugmentPolicy.IMAGENET): what rand_augment() returns,
+    (matrices, tone lists), with the same composition and caveats.  Per frame one of the policy's 25
+    sub-policies is drawn uniformly; each of its two ops is applied with its probability at its bin of 10:
+    ShearX 0 .. 0.3, Rotate 0 .. 30 degrees, Color, Contrast and Sharpness 1 +- 0 .. 0.9 (signed ops take a
+    random sign), Posterize 8 - round(bin / 2.25) bits (8 .. 4), Solarize threshold 1 .. 0, AutoContrast,
+    Equalize, and Invert, which is the matrix tone op 1 - x.  generator: a torch.Generator (CPU); the same
+    seed gives the same draws."""
+    import numpy as np
+    import torch
+    if policy != "imagenet":
+        raise ValueError(f"auto_augment: policy {policy!r} ('imagenet')")
+    size = (int(size[0]), int(size[1]))
+    if base is not None:
+        base = np.asarray(base, dtype=np.float64).reshape(-1, 2, 3)
+        if base.shape[0] not in (1, n):
+            raise ValueError(f"augment: base takes one [2, 3] matrix, or one per frame ({n}), got {base.shape[0]}")
+    mats, tones = np.zeros((n, 2, 3), dtype=np.float32), []
+    for j in range(n):
+        geo = np.eye(3)
+        if base is not None:
+            geo[:2] = base[j % base.shape[0]]
+        tone = []
+        sub = _AA_IMAGENET[int(torch.randint(len(_AA_IMAGENET), (1,), generator=generator))]
+        probs = torch.rand(2, generator=generator, dtype=torch.float64).tolist()
+        signs = torch.randint(2, (2,), generator=generator).tolist()
+        for (name, p, k), u, sign in zip(sub, probs, signs):
+            if not u <= p:
+                continue
+            if name == "Invert":
+                tone.append(("matrix", _INVERT))
+                continue
+            mag = _ra_magnitude(name, k, _AM_BINS, size, False) if k is not None else 0.0
+            if name in _AA_SIGNED and sign:
+                mag = -mag
+            geo = _ra_apply(name, mag, size, geo, tone)
+        mats[j] = geo[:2]
+        tones.append(tone)
+    return mats, tones
+
+
 MIX_MAX_RECTS = 4  # CCMI_MIX_MAX_RECTS
 
 
@@ -1121,6 +1288,50 @@ def mixup_cutmix(n: int, size, mixup_alpha: float = 0.8, cutmix_alpha: float = 1
     return mix, label_lam
 
 
+BLEND_MAX_TERMS = 8  # CCMI_BLEND_MAX_TERMS
+
+
+class Blend(C.Structure):
+    """ccmi_blend: per-frame term counts, the flat sources and weights, and the per-frame silent flags."""
+    _fields_ = [("count", C.c_void_p), ("source", C.c_void_p), ("weight", C.c_void_p), ("silent", C.c_void_p)]
+
+
+def _blend(blend, silent, n):
+    """blend= / silent= of a *_model call -> (ccmi_blend, what it points to, the silent flags as a list of
+    bool), or (None, None, None) with both None.  blend: one entry per frame, None or a list of at most 8
+    (source, weight), source a frame of this call; silent: one flag per frame, True: the frame is rendered
+    as a source only and has no output.  The library checks the values; the shapes are checked here."""
+    import numpy as np
+    if blend is None and silent is None:
+        return None, None, None
+    counts = np.zeros(n, dtype=np.int32)
+    src, wgt = [], []
+    if blend is not None:
+        entries = list(blend)
+        if len(entries) != n:
+            raise ValueError(f"model output: blend takes one entry per frame ({n}), got {len(entries)}")
+        for j, e in enumerate(entries):
+            e = [] if e is None else list(e)
+            if len(e) > BLEND_MAX_TERMS:
+                raise ValueError(f"model output: frame {j}: {len(e)} blend terms (at most {BLEND_MAX_TERMS})")
+            counts[j] = len(e)
+            for t in e:
+                if len(t) != 2:
+                    raise ValueError("model output: a blend term is (source, weight)")
+                src.append(int(t[0]))
+                wgt.append(t[1])
+    flags = np.zeros(n, dtype=np.int32)
+    if silent is not None:
+        quiet = [bool(v) for v in silent]
+        if len(quiet) != n:
+            raise ValueError(f"model output: silent takes one flag per frame ({n}), got {len(quiet)}")
+        flags[:] = quiet
+    source = np.array(src + [0], dtype=np.int32)
+    weight = np.array(wgt + [0.0], dtype=np.float32)
+    bl = Blend(count=counts.ctypes.data, source=source.ctypes.data, weight=weight.ctypes.data, silent=flags.ctypes.data)
+    return bl, (counts, source, weight, flags), [bool(v) for v in flags]
+
+
 def last_tail_groups() -> tuple:
     """(batched tail groups, per-frame tails) this thread's last decode or render call launched
     (ccmi_decode_last_tail_groups): frames that share a group share one launch per tail stage."""
@@ -1161,11 +1372,15 @@ def _model_fmt(n, colour, mean, std, dtype, mirror):
     return fmt, flags
 
 
-def _model_outs(geom, fmt, dtype, channels_last, out, dev):
+def _model_outs(geom, fmt, dtype, channels_last, out, dev, silent=None):
     """Destination tensors of a *_model call: fills fmt's strides; returns (result, pointers,
-    capacities in bytes, what they point into)."""
+    capacities in bytes, what they point into).  silent: the call's silent flags or None; the result and
+    out= then hold the other frames only, in call order, and a silent frame's pointer is NULL."""
     import torch
-    n, g0 = len(geom), geom[0]
+    emit = [i for i in range(len(geom)) if not (silent and silent[i])]
+    if not emit:
+        raise ValueError("model output: every frame is silent")
+    m, n, g0 = len(geom), len(emit), geom[0]
     h, w = g0.height, g0.width
     if any((g.width, g.height) != (w, h) for g in geom):
         raise ValueError("model output: every region must have one size, since the frames form one [n, 3, h, w] "
@@ -1190,10 +1405,10 @@ def _model_outs(geom, fmt, dtype, channels_last, out, dev):
     if strides == (0, 0, 0):  # would read as "planar contiguous" in ccmi_tensor_fmt
         raise ValueError("model output: out tensors with all-zero strides alias")
     fmt.stride_c, fmt.stride_y, fmt.stride_x = strides
-    op = (C.c_void_p * n)(*[t.data_ptr() for t in frames])
-    cap = (C.c_size_t * n)()
-    for i, t in enumerate(frames):  # what the tensor's storage holds from its first element on
+    op, cap = (C.c_void_p * m)(), (C.c_size_t * m)()
+    for i, t in zip(emit, frames):  # what the tensor's storage holds from its first element on
         st = t.untyped_storage()
+        op[i] = t.data_ptr()
         cap[i] = max(st.nbytes() - (t.data_ptr() - st.data_ptr()), 0)
     return res, op, cap, frames
 
@@ -1201,28 +1416,31 @@ def _model_outs(geom, fmt, dtype, channels_last, out, dev):
 class _Sink:
     """What a formatted call of n frames takes after the format: the ccmi_rect array (None: whole frames,
     and always None with a warp), the ccmi_resample (None without size, or with a warp), the ccmi_warp,
-    ccmi_colour, ccmi_tone, ccmi_filter and ccmi_mix (each None when absent), and keep, what they point to."""
+    ccmi_colour, ccmi_tone, ccmi_filter, ccmi_mix and ccmi_blend (each None when absent), keep, what they
+    point to, and silent, the blend's silent flags as a list of bool (None: every frame has an output)."""
 
-    def __init__(self, n, rects=None, rs=None, warp=None, col=None, tone=None, flt=None, mx=None, keep=None):
-        self.n, self.rects, self.keep = n, rects, keep
-        self.rs, self.warp, self.col, self.tone, self.flt, self.mx = rs, warp, col, tone, flt, mx
-        ref = C.byref  # the six stage arguments of the *_mix pair, in their order
+    def __init__(self, n, rects=None, rs=None, warp=None, col=None, tone=None, flt=None, mx=None, keep=None, bl=None,
+                 silent=None):
+        self.n, self.rects, self.keep, self.silent = n, rects, keep, silent
+        self.rs, self.warp, self.col, self.tone, self.flt, self.mx, self.bl = rs, warp, col, tone, flt, mx, bl
+        ref = C.byref  # the seven stage arguments of the *_blend pair, in their order
         self._stages = (None if rs is None else ref(rs), None if warp is None else ref(warp),
                         None if col is None else ref(col), None if tone is None else ref(tone),
-                        None if flt is None else ref(flt), None if mx is None else ref(mx))
+                        None if flt is None else ref(flt), None if bl is None else ref(bl),
+                        None if mx is None else ref(mx))
 
     def plan_args(self, output_bitdepth, output_chroma_format, fmt):
-        """n .. mix of the *_mix_plan prototypes: what lies between the source's head and geom."""
+        """n .. mix of the *_blend_plan prototypes: what lies between the source's head and geom."""
         return (self.n, self.rects, output_bitdepth, output_chroma_format, C.byref(fmt)) + self._stages
 
     def run_args(self, op, cap, fmt):
-        """n .. mix of the *_mix prototypes: what lies between the source's head and out_bitdepth."""
+        """n .. mix of the *_blend prototypes: what lies between the source's head and out_bitdepth."""
         return (self.n, self.rects, op, cap, C.byref(fmt)) + self._stages
 
 
 def _sink(n, rects=None, roi=None, size=None, affine=None, perspective=None, pad="fill", fill=0.0,
           interpolation="bilinear", clamp=False, colour_ops=None, blur=None, solarize=None, tone_ops=None, erase=None,
-          erase_seed=None, mix=None):
+          erase_seed=None, mix=None, blend=None, silent=None):
     """The _Sink of the keywords of a *_model call of n frames.  rects: the regions' ccmi_rect array, None, or
     a callable that makes either (called after the stages are marshalled, and not with a warp)."""
     interp = _interp(interpolation, clamp)
@@ -1231,21 +1449,22 @@ def _sink(n, rects=None, roi=None, size=None, affine=None, perspective=None, pad
     flt, keep_f = _filter(blur, solarize, n)
     tone, keep_t = _tone(tone_ops, n)
     mx, keep_m = _mix(erase, erase_seed, mix, n)
+    bl, keep_b, quiet = _blend(blend, silent, n)
     if warp is not None:
         rects = None
     elif callable(rects):
         rects = rects()
     rs = None if size is None or warp is not None else _resample(size, interp)
-    return _Sink(n, rects, rs, warp, col, tone, flt, mx, (keep_w, keep_c, keep_f, keep_t, keep_m))
+    return _Sink(n, rects, rs, warp, col, tone, flt, mx, (keep_w, keep_c, keep_f, keep_t, keep_m, keep_b), bl, quiet)
 
 
 def _stream_source(sp, ln):
     """A source is (plan entry point, run entry point, their first two arguments, the device or None for
-    the current one): here of marshalled streams, LatentStore._source() of a store.  Both name the *_mix
+    the current one): here of marshalled streams, LatentStore._source() of a store.  Both name the *_blend
     pair, the superset of every formatted call: a stage that is NULL leaves, by ccmi.h, the narrower
     call itself (down to *_fmt), so the absent keywords cost a NULL each and no other entry point."""
     L = _bind()
-    return L.ccmi_decode_batch_dev_mix_plan, L.ccmi_decode_batch_dev_mix, (sp, ln), None
+    return L.ccmi_decode_batch_dev_blend_plan, L.ccmi_decode_batch_dev_blend, (sp, ln), None
 
 
 def _plain_fmt():
@@ -1269,14 +1488,14 @@ def _plan_model(source, sink, fmt, output_bitdepth, output_chroma_format, info=N
 def _run_model(source, sink, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth, output_chroma_format,
                workspace, stream_handle):
     """The body of decode_batch_model and LatentStore.render_model: one plan and one run of the source's
-    *_mix pair."""
+    *_blend pair."""
     import torch
     _, run, head, dev = source
     dtype = torch.float32 if dtype is None else dtype
     fmt, keep = _model_fmt(sink.n, colour, mean, std, dtype, mirror)
     geom, need = _plan_model(source, sink, fmt, output_bitdepth, output_chroma_format)
     dev = torch.device("cuda", torch.cuda.current_device()) if dev is None else dev
-    res, op, cap, frames = _model_outs(geom, fmt, dtype, channels_last, out, dev)
+    res, op, cap, frames = _model_outs(geom, fmt, dtype, channels_last, out, dev, sink.silent)
     stream_handle, workspace = _stream_ws(dev, stream_handle, workspace, need)
     check(run(*head, *sink.run_args(op, cap, fmt), output_bitdepth, output_chroma_format, workspace.data_ptr(),
               workspace.numel(), stream_handle))
@@ -1288,8 +1507,8 @@ def decode_batch_model(streams: Sequence[bytes], roi=None, colour: str = "rgb", 
                        channels_last: bool = False, mirror=None, out=None, output_bitdepth: int = 0,
                        output_chroma_format: int = 0, workspace=None, stream_handle: int | None = None, size=None,
                        affine=None, pad: str = "fill", fill=0.0, colour_ops=None, blur=None, solarize=None,
-                       tone_ops=None, erase=None, erase_seed=None, mix=None, interpolation: str = "bilinear",
-                       clamp: bool = False, perspective=None):
+                       tone_ops=None, erase=None, erase_seed=None, mix=None, blend=None, silent=None,
+                       interpolation: str = "bilinear", clamp: bool = False, perspective=None):
     """Decode .cool streams into the tensor a model takes (ccmi_decode_batch_dev_fmt): one
     [n, 3, h, w] tensor of `dtype` (torch.float32, the default, torch.float16 or torch.bfloat16),
     every channel at full size (420 chroma nearest-upsampled), RGB (colour="rgb": YUV streams go
@@ -1298,7 +1517,7 @@ def decode_batch_model(streams: Sequence[bytes], roi=None, colour: str = "rgb", 
     decoder's output kernel itself: no float32 frame set and no further pass.  The contract, step
     by step, is ccmi.h's (ccmi_tensor_fmt).
 
-    Whatever the keywords, the call made is ccmi_decode_batch_dev_mix (and its _plan) with every absent
+    Whatever the keywords, the call made is ccmi_decode_batch_dev_blend (and its _plan) with every absent
     stage NULL, which the library defines to be the narrower call: the entry point a paragraph below
     names is the one whose contract in ccmi.h the keyword follows, and the one the call then equals.
 
@@ -1376,11 +1595,20 @@ def decode_batch_model(streams: Sequence[bytes], roi=None, colour: str = "rgb", 
     inside the box; the partner enters erased but unmixed (batch.roll() / flip() of the erased batch) and
     must be stored at the frame's size.  random_erasing() and mixup_cutmix() draw such lists.  The frames
     concerned are staged in float32 like blurred ones and formatted by one launch per call; the others
-    keep their kernels and bits."""
+    keep their kernels and bits.
+
+    blend= / silent= (ccmi_decode_batch_dev_blend; with or without everything above): weighted sums of
+    staged frames of this call BEFORE the normalisation (the contract's step 3b).  blend: one entry per
+    frame, None or a list of at most 8 (source, weight): the frame becomes w_0 * source_0 + w_1 * source_1
+    + ..., each source as staged (after its own geometry, colour, tone ops and filter; its own blend list
+    does not enter), at the frame's stored size; erase and mix then apply to the sum, and a partner enters
+    with its own sum.  silent: one flag per frame, True: the frame is rendered as a source only; the
+    returned tensor, and out=, then hold the other frames only, in call order.  aug_mix() draws such
+    lists.  With streams every repeat of a stream is decoded again: build a LatentStore for AugMix."""
     n = len(streams)
     keep, sp, ln = _marshal(streams)
     sink = _sink(n, lambda: _rects(roi, streams, n), roi, size, affine, perspective, pad, fill, interpolation, clamp,
-                 colour_ops, blur, solarize, tone_ops, erase, erase_seed, mix)
+                 colour_ops, blur, solarize, tone_ops, erase, erase_seed, mix, blend, silent)
     return _run_model(_stream_source(sp, ln), sink, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth,
                       output_chroma_format, workspace, stream_handle)
 
@@ -1729,7 +1957,7 @@ class LatentStore:
     def _source(self, idx):
         """This store as the source of a formatted call (see _stream_source); idx: _frames()'s index array."""
         L = _bind()
-        return (L.ccmi_latents_render_mix_plan, L.ccmi_latents_render_mix, (self._handle(), idx),
+        return (L.ccmi_latents_render_blend_plan, L.ccmi_latents_render_blend, (self._handle(), idx),
                 getattr(self._store, "device", None))
 
     def _plan(self, index, roi, output_bitdepth, output_chroma_format, dtype, info=None):
@@ -1779,11 +2007,11 @@ class LatentStore:
                      channels_last: bool = False, mirror=None, out=None, output_bitdepth: int = 0,
                      output_chroma_format: int = 0, workspace=None, stream_handle: int | None = None, size=None,
                      affine=None, pad: str = "fill", fill=0.0, colour_ops=None, blur=None, solarize=None,
-                     tone_ops=None, erase=None, erase_seed=None, mix=None, interpolation: str = "bilinear",
-                     clamp: bool = False, perspective=None):
+                     tone_ops=None, erase=None, erase_seed=None, mix=None, blend=None, silent=None,
+                     interpolation: str = "bilinear", clamp: bool = False, perspective=None):
         """render() into the tensor a model takes: frames and regions as for
         render(), the result and every other argument as for decode_batch_model, whose output for
-        the same streams and arguments it equals bit for bit.  The call made is ccmi_latents_render_mix
+        the same streams and arguments it equals bit for bit.  The call made is ccmi_latents_render_blend
         (and its _plan) with every absent stage NULL, which the library defines to be the narrower call:
         ccmi_latents_render_fmt; with size ccmi_latents_render_rs; with affine ccmi_latents_render_warp;
         with colour_ops ccmi_latents_render_col, with blur or solarize ccmi_latents_render_flt, with
@@ -1793,17 +2021,18 @@ class LatentStore:
         render_model_workspace_bytes() takes the same arguments.  interpolation= / clamp= as for
         decode_batch_model (a bicubic warp's windows, and so its workspace, are a tap wider);
         perspective= as for decode_batch_model, in place of affine=; erase= / erase_seed= / mix= as for
-        decode_batch_model (ccmi_latents_render_mix), partners being frames of this call."""
+        decode_batch_model (ccmi_latents_render_mix), partners being frames of this call; blend= / silent= as
+        for decode_batch_model (ccmi_latents_render_blend), sources being frames of this call: see aug_mix()."""
         m, idx, rects = self._frames(index, None if affine is not None or perspective is not None else roi)
         sink = _sink(m, rects, roi, size, affine, perspective, pad, fill, interpolation, clamp, colour_ops, blur, solarize,
-                     tone_ops, erase, erase_seed, mix)
+                     tone_ops, erase, erase_seed, mix, blend, silent)
         return _run_model(self._source(idx), sink, colour, mean, std, dtype, channels_last, mirror, out, output_bitdepth,
                           output_chroma_format, workspace, stream_handle)
 
     def warp_plan(self, index, affine, size, pad: str = "fill", fill=0.0, output_bitdepth: int = 0,
                   output_chroma_format: int = 0, interpolation: str = "bilinear", clamp: bool = False,
                   perspective=None) -> list:
-        """What render_model(affine=...) will do, per output frame (header-only: ccmi_latents_render_mix_plan
+        """What render_model(affine=...) will do, per output frame (header-only: ccmi_latents_render_blend_plan
         with a warp alone, by ccmi.h the ccmi_latents_render_warp_plan call), like roi_plan: {'window':
         (x, y, w, h), the rectangle of the frame the tail renders for that frame's matrix, 'windowed',
         'arm_rows'}.  interpolation="bicubic": the window
@@ -1822,10 +2051,10 @@ class LatentStore:
     def render_model_workspace_bytes(self, index=None, roi=None, size=None, output_bitdepth: int = 0,
                                      output_chroma_format: int = 0, affine=None, pad: str = "fill", fill=0.0,
                                      colour_ops=None, blur=None, solarize=None, tone_ops=None, erase=None,
-                                     erase_seed=None, mix=None, interpolation: str = "bilinear", clamp: bool = False,
-                                     perspective=None) -> int:
+                                     erase_seed=None, mix=None, blend=None, silent=None,
+                                     interpolation: str = "bilinear", clamp: bool = False, perspective=None) -> int:
         """Header-only: the workspace render_model needs, from render_model's own plan call
-        (ccmi_latents_render_mix_plan with the absent stages NULL: by ccmi.h the narrower plan named with
+        (ccmi_latents_render_blend_plan with the absent stages NULL: by ccmi.h the narrower plan named with
         each figure here), for these frames, regions and size, or
         these frames, matrices and size (ccmi_latents_render_rs_plan / _warp_plan; the element type,
         colour and strides do not change it), these colour ops (ccmi_latents_render_col_plan:
@@ -1834,10 +2063,12 @@ class LatentStore:
         that takes the stage) and these tone ops (ccmi_latents_render_tone_plan: ccmi.h's formula).
         perspective= in place of affine=: the same plans with CCMI_WARP_PROJECTIVE.  erase= / mix=
         (ccmi_latents_render_mix_plan): 256 bytes per mix-staged frame and a second float32 frame for
-        those with a blur or a solarize, on top of their staging (ccmi.h's formula)."""
+        those with a blur or a solarize, on top of their staging (ccmi.h's formula).  blend= / silent=
+        (ccmi_latents_render_blend_plan): the blend-staged frames counted as mix-staged, and 64 bytes for
+        each mix-staged frame, rounded up to 256 as a whole."""
         m, idx, rects = self._frames(index, None if affine is not None or perspective is not None else roi)
         sink = _sink(m, rects, roi, size, affine, perspective, pad, fill, interpolation, clamp, colour_ops, blur, solarize,
-                     tone_ops, erase, erase_seed, mix)
+                     tone_ops, erase, erase_seed, mix, blend, silent)
         return _plan_model(self._source(idx), sink, _plain_fmt(), output_bitdepth, output_chroma_format)[1]
 
     def latents(self, i: int) -> list:
@@ -1863,4 +2094,5 @@ __all__ = ["last_timing", "LatentStore", "last_arm_flags", "decode_latents", "de
            "decode_batch_tensors", "decode_batch_geometry", "roi_plan", "decode_batch_model", "last_tail_groups",
            "affine_matrix", "perspective_matrix", "random_perspective", "hue_matrix", "grey_matrix", "colour_jitter",
            "gaussian_taps", "gaussian_blur", "random_solarize", "rand_augment", "trivial_augment_wide",
+           "aug_mix", "auto_augment",
            "weights_i32", "ups_forward_i32", "syn_forward_i32", "CcmiError"]

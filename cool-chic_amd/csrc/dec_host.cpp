@@ -390,6 +390,7 @@ struct Run {
     size_t lat_tab() const { return pl.lat_tab_off - pl.tail_off; } // of the job table in `tab`
     size_t flt_tab() const { return pl.flt_tab_off - pl.tail_off; } // of the filter stage's tables in `tab`
     size_t mix_tab() const { return pl.mix_tab_off - pl.tail_off; } // of the mix table in `tab`
+    size_t blend_tab() const { return pl.blend_tab_off - pl.tail_off; } // of the blend table in `tab`
     uint32_t *status() const { return reinterpret_cast<uint32_t *>(dev + pl.status_off); }
 };
 
@@ -523,6 +524,9 @@ int build_tail_groups(Run &r)
         t.syn.out = reinterpret_cast<int32_t *>(r.dev + p.synout_off);
         t.syn.workspace = reinterpret_cast<int32_t *>(r.dev + p.synws_off);
         t.dst = r.rq.device() ? static_cast<uint8_t *>(r.rq.dev[i]) : r.dev + p.out_off;
+        // ccmi_blend: whatever out_dev holds for a silent frame is not looked at.  No tail kernel writes a
+        // mix-staged frame's dst, and its table entry gets none (dec_blend_fill): the staging frame stands in
+        if (p.silent) t.dst = r.dev + p.flt_off;
         t.rs_tmp = p.rs_elems ? reinterpret_cast<float *>(r.dev + p.rs_off) : nullptr;
         if (t.fmt.col && r.pl.cols[i].contrast >= 0)
             r.pl.cols[i].acc = reinterpret_cast<unsigned long long *>(r.dev + r.pl.col_off) + i;
@@ -578,6 +582,13 @@ void build_mix_table(Run &r, int &max_oh, int &max_ow)
         const int oh = sized ? t.fmt.out_h : t.roi.rect.h(), ow = sized ? t.fmt.out_w : t.roi.rect.w();
         dec_mix_fill(r.tab.data() + r.mix_tab(), t, oh, ow, t.mix->partner >= 0 ? r.pl.mixes[t.mix->partner].entry : -1);
         max_oh = std::max(max_oh, oh), max_ow = std::max(max_ow, ow);
+    }
+    for (size_t i = 0; i < r.pl.blends.size(); ++i) { // ccmi_blend: the terms, by the sources' entries
+        const DecBlend &b = r.pl.blends[i];
+        if (!b.count && !b.silent) continue;
+        int src[CCMI_BLEND_MAX_TERMS] = {};
+        for (int t = 0; t < b.count; ++t) src[t] = r.pl.mixes[b.src[t]].entry;
+        dec_blend_fill(r.tab.data() + r.mix_tab(), r.tab.data() + r.blend_tab(), r.pl.mixes[i].entry, b, src);
     }
 }
 
@@ -914,7 +925,7 @@ int decode_run(const DecodeRequest &rq, DecodePlan &pl, hipStream_t s)
     if (!render)
         if (int rc = build_arm_groups(r)) return rc;
     // the tables of the call: the tail groups', then the latent store's jobs, in one copy
-    r.tab.assign(std::max(r.lat_tab() + pl.lat_tab_cap, r.mix_tab() + pl.mix_table_bytes()) + 1, 0);
+    r.tab.assign(std::max(r.lat_tab() + pl.lat_tab_cap, r.blend_tab() + pl.blend_table_bytes()) + 1, 0);
     if (!rq.lat_store)
         if (int rc = build_tail_groups(r)) return rc;
     if (rq.lat_store) build_pack_jobs(r);
@@ -923,7 +934,7 @@ int decode_run(const DecodeRequest &rq, DecodePlan &pl, hipStream_t s)
     int mix_oh = 0, mix_ow = 0;
     if (pl.n_mix) { // ... or the mix table after them
         build_mix_table(r, mix_oh, mix_ow);
-        r.tab_used = r.mix_tab() + pl.mix_table_bytes();
+        r.tab_used = r.blend_tab() + pl.blend_table_bytes(); // ... and the blend table after it
     }
     if (r.tab_used)
         CCMI_HIP_CHECK(hipMemcpyAsync(r.dev + pl.tail_off, r.tab.data(), r.tab_used, hipMemcpyHostToDevice, s));
@@ -939,7 +950,10 @@ int decode_run(const DecodeRequest &rq, DecodePlan &pl, hipStream_t s)
         const FramePlan *m0 = nullptr;
         for (const FramePlan &p : pl.fr)
             if (p.tail.mix && !m0) m0 = &p;
-        if (int rc = launch_dec_mix(r.dev + pl.mix_tab_off, pl.n_mix, mix_oh, mix_ow, m0->tail.fmt, s)) return rc;
+        if (int rc = pl.blends.empty() ? launch_dec_mix(r.dev + pl.mix_tab_off, pl.n_mix, mix_oh, mix_ow, m0->tail.fmt, s)
+                                       : launch_dec_blend(r.dev + pl.mix_tab_off, r.dev + pl.blend_tab_off, pl.n_mix, mix_oh,
+                                                          mix_ow, m0->tail.fmt, s))
+            return rc;
         ev.rec(3, s); // the mix launch ends the tail (store_timing; forked chunks record their own tail ends)
     }
     if (!rq.lat_store) { // what launch_chunk ran: every group, and a tail of its own per other frame
@@ -1061,15 +1075,15 @@ extern "C" int ccmi_decode_batch_ws(const uint8_t *const *streams, const size_t 
 }
 
 // ------------------------------------------------------------------ device sinks
-// Thirty-six entry points over one table, each a Source, a Sink and one return through sink_plan or
+// Forty entry points over one table, each a Source, a Sink and one return through sink_plan or
 // sink_run:
 //   source  the caller's streams (ccmi_decode_batch_dev*)  |  a latent store (ccmi_latents_render*)
 //   sink    plain samples of sample_type: whole frames, or regions (_roi; the store's call takes both)
 //           formatted ones (fmt; forced to CCMI_SAMPLE_F32, the call whose output kernel the format
 //           replaces): _fmt; _rs, with a resample; _warp, with a warp, which takes no region; then _col,
-//           _flt, _tone and _mix, each the superset of all before it with one more stage (colour ops,
-//           a filter, tone ops, a mix).  A stage that is NULL is the call before, itself, under the
-//           name it was entered by; what may not go together is the plan's to refuse
+//           _flt, _tone, _mix and _blend, each the superset of all before it with one more stage (colour
+//           ops, a filter, tone ops, a mix, a blend).  A stage that is NULL is the call before, itself, under
+//           the name it was entered by; what may not go together is the plan's to refuse
 //   form    a plan (geom, info, window, workspace_bytes)  |  a run (outputs, workspace, stream)
 // `who` is the entry point's name for the error text, `needs` what it requires beyond the source and
 // its own outputs: the _warp entry points a warp with its matrices, the supersets only the matrices
@@ -1100,6 +1114,7 @@ struct Sink { // in the entry points' argument order; an entry point writes the 
     const ccmi_tone *tone = nullptr;
     const ccmi_filter *filter = nullptr;
     const ccmi_mix *mix = nullptr;
+    const ccmi_blend *blend = nullptr; // the prototypes take it before mix
 };
 
 enum Needs { PLAIN, FMT, FMT_WARP };
@@ -1135,6 +1150,7 @@ static int sink_request(const char *who, const Source &src, const Sink &k, int o
     rq.filter = k.filter;
     rq.tone = k.tone;
     rq.mix = k.mix;
+    rq.blend = k.blend;
     return CCMI_OK;
 }
 
@@ -1340,6 +1356,30 @@ extern "C" int ccmi_decode_batch_dev_mix(const uint8_t *const *streams, const si
     return sink_run("decode_batch_dev_mix (frame 0)", from_streams(streams, lens, n),
                     Sink{roi, F32, fmt, rs, warp, colour, tone, filter, mix}, FMT, out_dev, out_caps, out_bitdepth, out_chroma,
                     workspace, workspace_bytes, stream);
+}
+
+extern "C" int ccmi_decode_batch_dev_blend_plan(const uint8_t *const *streams, const size_t *lens, int n,
+                                                const ccmi_rect *roi, int out_bitdepth, int out_chroma, const ccmi_tensor_fmt *fmt,
+                                                const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
+                                                const ccmi_tone *tone, const ccmi_filter *filter, const ccmi_blend *blend,
+                                                const ccmi_mix *mix, ccmi_frame_geom *geom, ccmi_roi_info *info, ccmi_rect *window,
+                                                size_t *workspace_bytes)
+{
+    return sink_plan("decode_batch_dev_blend_plan (frame 0)", from_streams(streams, lens, n),
+                     Sink{roi, F32, fmt, rs, warp, colour, tone, filter, mix, blend}, FMT, out_bitdepth, out_chroma, geom, info,
+                     window, workspace_bytes);
+}
+
+extern "C" int ccmi_decode_batch_dev_blend(const uint8_t *const *streams, const size_t *lens, int n,
+                                           const ccmi_rect *roi, void *const *out_dev, const size_t *out_caps,
+                                           const ccmi_tensor_fmt *fmt, const ccmi_resample *rs, const ccmi_warp *warp,
+                                           const ccmi_colour *colour, const ccmi_tone *tone, const ccmi_filter *filter,
+                                           const ccmi_blend *blend, const ccmi_mix *mix, int out_bitdepth, int out_chroma,
+                                           void *workspace, size_t workspace_bytes, void *stream)
+{
+    return sink_run("decode_batch_dev_blend (frame 0)", from_streams(streams, lens, n),
+                    Sink{roi, F32, fmt, rs, warp, colour, tone, filter, mix, blend}, FMT, out_dev, out_caps, out_bitdepth,
+                    out_chroma, workspace, workspace_bytes, stream);
 }
 
 extern "C" int ccmi_latents_plan(const uint8_t *const *streams, const size_t *lens, int n, int latent_type,
@@ -1599,6 +1639,30 @@ extern "C" int ccmi_latents_render_mix(const ccmi_latents *h, const int *index, 
     return sink_run("latents_render_mix (frame 0)", from_store(h, index, m),
                     Sink{roi, F32, fmt, rs, warp, colour, tone, filter, mix}, FMT, out_dev, out_caps, out_bitdepth, out_chroma,
                     workspace, workspace_bytes, stream);
+}
+
+extern "C" int ccmi_latents_render_blend_plan(const ccmi_latents *h, const int *index, int m,
+                                              const ccmi_rect *roi, int out_bitdepth, int out_chroma, const ccmi_tensor_fmt *fmt,
+                                              const ccmi_resample *rs, const ccmi_warp *warp, const ccmi_colour *colour,
+                                              const ccmi_tone *tone, const ccmi_filter *filter, const ccmi_blend *blend,
+                                              const ccmi_mix *mix, ccmi_frame_geom *geom, ccmi_roi_info *info, ccmi_rect *window,
+                                              size_t *workspace_bytes)
+{
+    return sink_plan("latents_render_blend_plan (frame 0)", from_store(h, index, m),
+                     Sink{roi, F32, fmt, rs, warp, colour, tone, filter, mix, blend}, FMT, out_bitdepth, out_chroma, geom, info,
+                     window, workspace_bytes);
+}
+
+extern "C" int ccmi_latents_render_blend(const ccmi_latents *h, const int *index, int m,
+                                         const ccmi_rect *roi, void *const *out_dev, const size_t *out_caps,
+                                         const ccmi_tensor_fmt *fmt, const ccmi_resample *rs, const ccmi_warp *warp,
+                                         const ccmi_colour *colour, const ccmi_tone *tone, const ccmi_filter *filter,
+                                         const ccmi_blend *blend, const ccmi_mix *mix, int out_bitdepth, int out_chroma,
+                                         void *workspace, size_t workspace_bytes, void *stream)
+{
+    return sink_run("latents_render_blend (frame 0)", from_store(h, index, m),
+                    Sink{roi, F32, fmt, rs, warp, colour, tone, filter, mix, blend}, FMT, out_dev, out_caps, out_bitdepth,
+                    out_chroma, workspace, workspace_bytes, stream);
 }
 
 namespace ccmi {

@@ -264,6 +264,19 @@ struct DecMix {
 // what the stage adds to the call's tables per mix-staged frame (the workspace formula of ccmi.h)
 constexpr size_t kMixTableBytes = 256;
 
+// ccmi_blend of one frame (step 3b of the contract in ccmi.h), validated by the plan.  A blend-staged frame
+// (terms, silent, or a source) is mix-staged: its DecMix is staged and has an entry.  The terms travel in
+// the blend table, the sibling of the mix table that follows it: kBlendTableBytes per mix-staged frame, the
+// whole rounded up to 256; dec_blend_batch (dec_blend.hip) is then the call's one launch.
+struct DecBlend {
+    int count = 0;  // terms
+    int silent = 0; // rendered and staged, no output
+    int src[CCMI_BLEND_MAX_TERMS] = {}; // frames of the call
+    float w[CCMI_BLEND_MAX_TERMS] = {};
+};
+constexpr size_t kBlendTableBytes = 64;
+inline size_t dec_blend_table_bytes(int n_mix) { return (kBlendTableBytes * (size_t)n_mix + 255) / 256 * 256; }
+
 // the form of a tail group's output section: the plain entry, or its resample / warp / projective warp extension
 enum { kOutPlain = 0, kOutRs = 1, kOutWarp = 2, kOutPersp = 3 };
 inline int dec_out_form(const DecFmt &f) { return f.rs ? kOutRs : f.warp ? (f.persp ? kOutPersp : kOutWarp) : kOutPlain; }
@@ -362,6 +375,12 @@ const float *dec_mix_source(const DecTailFrame &f);
 // strides are each frame's own and travel in its entry), max_oh x max_ow: the largest stored frame among them.
 void dec_mix_fill(void *host_tab, const DecTailFrame &f, int oh, int ow, int partner_entry);
 int launch_dec_mix(const void *dev_tab, int n_entries, int max_oh, int max_ow, const DecFmt &fmt, hipStream_t s);
+// ccmi_blend: after dec_mix_fill, the terms of entry `entry` (src_entries: the sources' entries of the mix
+// table) into both host tables, and no destination for a silent frame; launch_dec_blend is launch_dec_mix
+// for a call with a blend table (dec_blend_batch: K sources per frame, silent entries leave at once)
+void dec_blend_fill(void *host_mix_tab, void *host_blend_tab, int entry, const DecBlend &b, const int *src_entries);
+int launch_dec_blend(const void *dev_mix_tab, const void *dev_blend_tab, int n_entries, int max_oh, int max_ow,
+                     const DecFmt &fmt, hipStream_t s);
 
 // The tone stage (dec_tone.hip), between the staging launches and the filter launch: segment after
 // segment, a statistics pass where a frame's terminator needs one, then the apply pass (in place) or

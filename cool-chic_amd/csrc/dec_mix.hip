@@ -20,42 +20,10 @@
 // tile that meets a rectangle with sigma > 0 pays for the draws (two mix64, logf, sqrtf, cospif per
 // element).  A stream: 12 (24 with a partner) bytes read and 3 sizeof(T) written per pixel, no LDS.
 // Every product and sum is its own float32 operation (fmt_mul / fmt_add), in the contract's order.
-#include "ccmi_noise.h"
-#include "dec_out_fmt.h"
+#include "dec_mix_entry.h"
 
 namespace ccmi {
 namespace {
-
-constexpr int kThreads = kOutThreads;
-constexpr int kTileH = 16;             // rows of a tile
-constexpr int kTileG = 16;             // groups of 4 destination pixels per tile row
-static_assert(kThreads == kTileH * kTileG, "one group per thread");
-
-// one mix-staged frame (DecMix with its device pointers): kMixTableBytes of the call's mix table
-struct DecMixEntry {
-    const float *src; // [3][oh][ow], the frame as it will be stored (mirrored already), before step 4
-    void *dst;
-    unsigned long long seed;
-    int oh, ow;
-    int partner; // the partner's entry, or -1
-    int count;
-    float lam, oml;
-    int bx, by, bw, bh; // bw == 0: no box
-    DecMixRect r[CCMI_MIX_MAX_RECTS];
-    // the frame's own resolved strides (elements): all-zero strides in ccmi_tensor_fmt resolve to each
-    // frame's stored size, and the mix-staged frames of one call may differ in size
-    long long sc, sy, sx;
-    int pad_[10];
-};
-static_assert(sizeof(DecMixEntry) == kMixTableBytes, "the mix entry of kMixTableBytes");
-
-typedef float __attribute__((address_space(1))) GlobalFloat;
-
-// the tile's pixel rectangle [x0, x1) x [y0, y1) against the rectangle (x, y, w, h)
-__device__ __forceinline__ bool meets(int x0, int x1, int y0, int y1, int x, int y, int w, int h)
-{
-    return w > 0 && h > 0 && x < x1 && x + w > x0 && y < y1 && y + h > y0;
-}
 
 // steps 4 and 4e of frame E for the thread's 4 pixels d0 .. d0 + 3 of row y: a[c][k]
 __device__ __forceinline__ void staged_group(const DecMixEntry &E, const DecFmtCall &C, bool live, int y, int d0, bool any,
@@ -158,9 +126,6 @@ __global__ __launch_bounds__(kThreads) void dec_mix_batch(const DecMixEntry *__r
         for (int k = 0; k < 4; ++k) v[c][k] = fmt_elem<T>(a[c][k]);
     fmt_store<T>(v, dst, C, row, d0, ow, nchw, nhwc);
 }
-
-int mix_tiles_x(int ow) { return (fmt_row_groups(ow) + kTileG - 1) / kTileG; }
-int mix_tiles_y(int oh) { return (oh + kTileH - 1) / kTileH; }
 
 } // namespace
 

@@ -360,6 +360,32 @@ int mix_frame_sized(const DecMix &d, int i, const std::vector<int> &oh, const st
     return CCMI_OK;
 }
 
+// ccmi_blend of frame i of n, whose terms start at `first` of the flat arrays: everything that needs no
+// stored size, validated into d; mx: the frame's resolved ccmi_mix, or NULL
+int blend_frame(const ccmi_blend &bl, int i, int n, size_t first, const DecMix *mx, DecBlend &d)
+{
+    d = DecBlend{};
+    const int cnt = bl.count ? bl.count[i] : 0;
+    if (cnt < 0 || cnt > CCMI_BLEND_MAX_TERMS)
+        return ccmi_set_error(CCMI_ERR_ARG, "frame %d: %d blend terms (0 .. %d)", i, cnt, CCMI_BLEND_MAX_TERMS);
+    if (cnt > 0 && (!bl.source || !bl.weight))
+        return ccmi_set_error(CCMI_ERR_ARG, "frame %d: blend %s are NULL", i, bl.source ? "weights" : "sources");
+    d.count = cnt;
+    d.silent = bl.silent && bl.silent[i] ? 1 : 0;
+    for (int t = 0; t < cnt; ++t) {
+        const int q = bl.source[first + t];
+        const float w = bl.weight[first + t];
+        if (q < 0 || q >= n)
+            return ccmi_set_error(CCMI_ERR_ARG, "frame %d: blend term %d: source %d (a frame 0 .. %d)", i, t, q, n - 1);
+        if (!std::isfinite(w)) return ccmi_set_error(CCMI_ERR_ARG, "frame %d: blend term %d: weight is not finite", i, t);
+        d.src[t] = q, d.w[t] = w;
+    }
+    if (d.silent && (cnt > 0 || (mx && (mx->count > 0 || mx->partner >= 0))))
+        return ccmi_set_error(CCMI_ERR_ARG, "frame %d: a silent frame with %s (it writes no output)", i,
+                              cnt > 0 ? "blend terms" : mx->count > 0 ? "erase rectangles" : "a partner");
+    return CCMI_OK;
+}
+
 // ccmi_tone of frame i, whose ops start at `first` of the flat array: validated, resolved (1 - f, the
 // posterize levels) and cut into segments in d
 int tone_ops(const ccmi_tone &tn, int i, size_t first, DecTone &d)
@@ -529,7 +555,7 @@ int plan_tensor_sink(const DecodeRequest &rq, int i, FramePlan &p)
         for (int l = 0; l < f.n_layers; ++l) I.arm_rows[l] = t.roi.arm_rows[l];
         I.windowed = p.batchable ? 1 : 0;
     }
-    if (rq.dev) {
+    if (rq.dev && !p.silent) { // ccmi_blend: nothing is written for a silent frame, its output is not looked at
         if (!rq.dev[i]) return ccmi_set_error(CCMI_ERR_ARG, "decode: output %d is NULL", i);
         if (reinterpret_cast<uintptr_t>(rq.dev[i]) % unit)
             return ccmi_set_error(CCMI_ERR_ARG, "decode: output %d is not aligned to its %zu-byte samples", i, unit);
@@ -579,7 +605,7 @@ int plan_frame(const DecodeRequest &rq, int i, FramePlan &p)
     t.kind = p.of.kind;
     t.sample = rq.sample;
     const size_t bytes = p.of.header + p.of.payload;
-    if ((rq.outs || rq.dev) && rq.caps && rq.caps[i] < bytes)
+    if ((rq.outs || rq.dev) && rq.caps && !p.silent && rq.caps[i] < bytes)
         return ccmi_set_error(CCMI_ERR_ARG, "%s %d: output buffer of %zu bytes, need %zu", rq.src ? "frame" : "stream", i,
                               rq.caps[i], bytes);
     if (rq.sizes) rq.sizes[i] = bytes;
@@ -673,6 +699,8 @@ void plan_layout(const DecodeRequest &rq, DecodePlan &pl)
     tot += pl.flt_table_bytes();
     pl.mix_tab_off = tot; // ccmi_mix: the mix table ends the image
     tot += pl.mix_table_bytes();
+    pl.blend_tab_off = tot; // ccmi_blend: ... or its sibling, the blend table
+    tot += pl.blend_table_bytes();
     if (!pl.tones.empty()) { // ccmi_tone: the accumulator blocks of the call's statistic ops, frame after frame
         pl.tone_acc_off = tot;
         for (size_t i = 0; i < pl.fr.size(); ++i) {
@@ -774,14 +802,38 @@ int decode_plan(const DecodeRequest &rq, DecodePlan &pl)
                     pl.mixes[i].staged = 1;
                     if (pl.mixes[i].partner >= 0) pl.mixes[pl.mixes[i].partner].staged = 1;
                 }
-            if (takes.empty()) takes.assign(rq.n, 0);
-            // a frame staged for the mix alone passes the filter stage with radius 0 and no solarize
-            pl.flts.resize(rq.n);
+        }
+    }
+    if (rq.blend) { // every frame's terms and silence: the blend-staged frames are mix-staged
+        if (!rq.fmt) return ccmi_set_error(CCMI_ERR_ARG, "frame 0: blend without a format");
+        size_t first = 0;
+        bool any = false;
+        pl.blends.resize(rq.n);
+        for (int i = 0; i < rq.n; ++i) {
+            const DecMix *mx = pl.mixes.empty() ? nullptr : &pl.mixes[i];
+            if (int rc = blend_frame(*rq.blend, i, rq.n, first, mx, pl.blends[i])) return rc;
+            first += (size_t)pl.blends[i].count;
+            any = any || pl.blends[i].count > 0 || pl.blends[i].silent;
+        }
+        if (!any) pl.blends.clear(); // no frame has terms or is silent: the call without blend
+        if (any) {
+            if (pl.mixes.empty()) pl.mixes.assign(rq.n, DecMix{});
             for (int i = 0; i < rq.n; ++i) {
-                if (!pl.mixes[i].staged) continue;
-                pl.mixes[i].entry = pl.n_mix++;
-                if (!takes[i]) takes[i] = 1, ++pl.n_flt;
+                const DecBlend &b = pl.blends[i];
+                pl.fr[i].silent = b.silent != 0;
+                if (b.count > 0 || b.silent) pl.mixes[i].staged = 1;
+                for (int t = 0; t < b.count; ++t) pl.mixes[b.src[t]].staged = 1;
             }
+        }
+    }
+    if (!pl.mixes.empty()) {
+        if (takes.empty()) takes.assign(rq.n, 0);
+        // a frame staged for the mix alone passes the filter stage with radius 0 and no solarize
+        pl.flts.resize(rq.n);
+        for (int i = 0; i < rq.n; ++i) {
+            if (!pl.mixes[i].staged) continue;
+            pl.mixes[i].entry = pl.n_mix++;
+            if (!takes[i]) takes[i] = 1, ++pl.n_flt;
         }
     }
     if (!pl.n_flt) pl.flts.clear(); // no frame takes the stage: the call without a filter
@@ -803,6 +855,14 @@ int decode_plan(const DecodeRequest &rq, DecodePlan &pl)
     }
     for (int i = 0; i < rq.n && pl.n_mix; ++i)
         if (int rc = mix_frame_sized(pl.mixes[i], i, oh, ow)) return rc;
+    for (size_t i = 0; i < pl.blends.size(); ++i) // a source is read at the frame's own (c, i, k)
+        for (int t = 0; t < pl.blends[i].count; ++t) {
+            const int q = pl.blends[i].src[t];
+            if (oh[q] != oh[i] || ow[q] != ow[i])
+                return ccmi_set_error(CCMI_ERR_ARG,
+                                      "frame %zu: blend term %d: source %d is stored at %d x %d, the frame at %d x %d", i, t, q,
+                                      ow[q], oh[q], ow[i], oh[i]);
+        }
     plan_layout(rq, pl);
     return CCMI_OK;
 }

@@ -96,6 +96,9 @@ struct DecodeRequest {
     // with fmt, optional: per-frame erase rectangles, partners, blend weights and boxes (ccmi_mix); the
     // mix-staged frames take the filter's stage and are formatted by the call's one mix launch
     const ccmi_mix *mix = nullptr;
+    // with fmt, optional: per-frame weighted sums of staged frames and silent frames (ccmi_blend); the
+    // blend-staged frames are mix-staged and the call's one launch is dec_blend_batch
+    const ccmi_blend *blend = nullptr;
     // either sink
     const size_t *caps = nullptr;    // [n], optional: capacity in bytes of outs[i] / dev[i]
     size_t *sizes = nullptr;         // [n], optional: bytes written per stream (filled by the plan)
@@ -121,6 +124,7 @@ struct FramePlan {
     bool batchable = false; // single branch and an architecture the batched tail takes
     bool arm24 = false;     // every ARM weight fits 24 signed bits (decode_run, once they are decoded)
     int src = -1;           // latent-store source: the handle's stream this frame renders
+    bool silent = false;    // ccmi_blend: rendered and staged, no output (set before the frame is planned)
     // tail arguments: architecture, output format and region (tail.roi) from the plan, device
     // pointers and syn.f24 from decode_run
     DecTailFrame tail;
@@ -170,6 +174,12 @@ struct DecodePlan {
     int n_mix = 0;
     size_t mix_tab_off = 0;
     size_t mix_table_bytes() const { return kMixTableBytes * (size_t)n_mix; }
+    // ccmi_blend with a frame that has terms or is silent: every frame's DecBlend; the blend-staged frames
+    // count among the n_mix mix-staged ones (mixes is then sized whether or not the call has a ccmi_mix), and
+    // the blend table follows the mix table in the one host image
+    std::vector<DecBlend> blends;
+    size_t blend_tab_off = 0;
+    size_t blend_table_bytes() const { return blends.empty() ? 0 : dec_blend_table_bytes(n_mix); }
 #if defined(CCMI_ARM_STAMPS)
     size_t dbg_off = 0;
 #endif

@@ -1230,6 +1230,92 @@ int ccmi_latents_render_mix(const ccmi_latents *h, const int *index /* [m] or NU
                             const ccmi_mix *mix /* or NULL */, int out_bitdepth, int out_chroma, void *workspace,
                             size_t workspace_bytes, void *stream);
 
+/* Blend stage: the mix sink with weighted sums of up to CCMI_BLEND_MAX_TERMS staged frames of the call, and
+ * with frames that are rendered as sources only -- what AugMix needs: several differently augmented renders
+ * of one frame summed with per-frame weights BEFORE the normalisation and the one rounding.
+ * Frame j of a call of n frames HAS TERMS when count[j] = K > 0: sources s_0 .. s_{K-1} (frames of this
+ * call) and weights w_0 .. w_{K-1}.  It is SILENT when silent[j] != 0.  A frame is BLEND-STAGED when it has
+ * terms, is silent, or is a source of a frame with terms.  Blend-staged frames are mix-staged in the sense
+ * above: they take the filter's staging frame, have an entry of the mix table and are formatted by the
+ * call's one launch after the join, together with the frames `mix` stages.  Every other frame keeps its
+ * kernels and its bits.
+ *   3b. blend, between step 3y-2 and step 4 (named 3b: 3z is the colour stage's step).  With y^f_c(i, k)
+ *       the staged value of frame f after step 3y-2 (the y_c of the mix stage above), for a frame with terms:
+ *           z_c = w_0 y^{s_0}_c,  then  z_c = z_c + (w_t y^{s_t}_c)  for t = 1 .. K - 1 ascending,
+ *       every product and every sum one float32 operation (no fused multiply-add), at the same (c, i, k) of
+ *       every source.  A frame without terms: z_c = y_c.  Steps 4, 4e, 4m, 5 and 6 then run on z_c in place
+ *       of y_c, with the frame's own rectangles, seed, partner and box.
+ *   A source enters as its own staged y: the source's own terms do not enter (the rule a partner follows for
+ *   its partner).  A source may be the frame itself, may repeat, and may be silent or not.
+ *   The partner p of step 4m enters with ITS step 3b (then its steps 4 and 4e): MixUp or CutMix of an
+ *   AugMixed batch mixes the blended partner.
+ *   count[j] = 1, source j, weight 1.0f: the bits of the same frame merely mix-staged (1.0f y == y).
+ * A SILENT frame is planned, decoded and staged like any other: geom[j], info[j] and window[j] are filled.
+ * Nothing is written for it: out_dev[j] may be NULL, out_caps[j] is not read, its alignment is not checked
+ * and it takes no part in any check of the outputs.
+ *
+ * One superset pair per source: the _mix argument list with `blend` after `filter` and before `mix`.
+ * blend NULL, or no frame with terms and no silent frame: exactly the _mix call -- plan, workspace,
+ * launches (dec_mix_batch), ccmi_decode_last_tail_groups and bits.  Otherwise, with M = the frames that are
+ * mix-staged by `mix` or blend-staged, the workspace is that of the _mix call in which the M frames are
+ * mix-staged (its formula above, the blend-staged frames counted), plus exactly
+ *     256 ceil(|M| / 4)  bytes:
+ * the blend table, a sibling of the mix table that follows it in the call's one upload: 64 bytes per frame
+ * of M (8 source entries, 8 weights), rounded up to 256 as a whole.  The number of terms sits in the frame's
+ * 256-byte mix entry, whose layout is otherwise unchanged.  The launch is then dec_blend_batch, the form of
+ * the mix kernel that reads K sources per frame: 12 K bytes read per pixel (12 K_p more where a partner
+ * enters), 3 sizeof(elem) written; an entry without a destination (a silent frame) leaves at block start.
+ * Checked by the plan before any GPU work, CCMI_ERR_ARG naming the frame (and the term) and nothing written:
+ * blend without a format; a count outside [0, CCMI_BLEND_MAX_TERMS]; source or weight NULL while a count is
+ * positive; a source outside [0, n); a source whose stored size differs from the frame's; a weight that is
+ * not finite; a silent frame with terms, erase rectangles or a partner; a non-silent frame whose out_dev[j]
+ * is NULL (run calls); and everything the _mix plan checks.
+ * Not covered: sources of another stored size; AugMix's interleaving of geometric and photometric ops inside
+ * a chain (ccmi/decode.py's aug_mix composes the geometry first, as rand_augment does); JSD-consistency
+ * label handling; elastic transforms.  A coded-stream call decodes a stream once per repeat: build a store.
+ * Measured (profiles/decode_blend_ab.txt): 960 class-E frames, RandomResizedCrop bases, AugMix(severity 3, width
+ * 3), 3840 rendered frames for 960 bf16 outputs of 224 x 224: 179.6-180.6 ms per call (tail 164.0 ms) against
+ * 181.4-182.2 ms for the 3840 frames without blend, all emitting, and 183.5-183.8 ms for their float32 render
+ * followed by the sum, normalisation and cast as torch operations; peak allocation above store and workspace
+ * 276 MiB against 1103 MiB and 4961 MiB; the workspace grows by 884.9 MiB over that of the 3840 frames. */
+enum { CCMI_BLEND_MAX_TERMS = 8 };
+typedef struct ccmi_blend {
+    const int   *count;   /* host, [n] or NULL: terms of frame j, 0 (no blend) .. 8            */
+    const int   *source;  /* host, flat, frame j's follow frame j - 1's: a frame of this call  */
+    const float *weight;  /* host, flat, same order                                            */
+    const int   *silent;  /* host, [n] or NULL: != 0: frame j is rendered and writes no output */
+} ccmi_blend;
+int ccmi_decode_batch_dev_blend_plan(const uint8_t *const *streams, const size_t *lens, int n,
+                                     const ccmi_rect *roi /* [n] or NULL */, int out_bitdepth, int out_chroma,
+                                     const ccmi_tensor_fmt *fmt, const ccmi_resample *rs /* or NULL */,
+                                     const ccmi_warp *warp /* or NULL */, const ccmi_colour *colour /* or NULL */,
+                                     const ccmi_tone *tone /* or NULL */, const ccmi_filter *filter /* or NULL */,
+                                     const ccmi_blend *blend /* or NULL */, const ccmi_mix *mix /* or NULL */,
+                                     ccmi_frame_geom *geom /* [n] */, ccmi_roi_info *info /* [n] or NULL */,
+                                     ccmi_rect window[] /* [n] or NULL; warp only */, size_t *workspace_bytes);
+int ccmi_decode_batch_dev_blend(const uint8_t *const *streams, const size_t *lens, int n,
+                                const ccmi_rect *roi /* [n] or NULL */, void *const *out_dev, const size_t *out_caps,
+                                const ccmi_tensor_fmt *fmt, const ccmi_resample *rs /* or NULL */,
+                                const ccmi_warp *warp /* or NULL */, const ccmi_colour *colour /* or NULL */,
+                                const ccmi_tone *tone /* or NULL */, const ccmi_filter *filter /* or NULL */,
+                                const ccmi_blend *blend /* or NULL */, const ccmi_mix *mix /* or NULL */,
+                                int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes, void *stream);
+int ccmi_latents_render_blend_plan(const ccmi_latents *h, const int *index /* [m] or NULL */, int m,
+                                   const ccmi_rect *roi /* [m] or NULL */, int out_bitdepth, int out_chroma,
+                                   const ccmi_tensor_fmt *fmt, const ccmi_resample *rs /* or NULL */,
+                                   const ccmi_warp *warp /* or NULL */, const ccmi_colour *colour /* or NULL */,
+                                   const ccmi_tone *tone /* or NULL */, const ccmi_filter *filter /* or NULL */,
+                                   const ccmi_blend *blend /* or NULL */, const ccmi_mix *mix /* or NULL */,
+                                   ccmi_frame_geom *geom /* [m] */, ccmi_roi_info *info /* [m] or NULL */,
+                                   ccmi_rect window[] /* [m] or NULL; warp only */, size_t *workspace_bytes);
+int ccmi_latents_render_blend(const ccmi_latents *h, const int *index /* [m] or NULL */, int m,
+                              const ccmi_rect *roi /* [m] or NULL */, void *const *out_dev, const size_t *out_caps,
+                              const ccmi_tensor_fmt *fmt, const ccmi_resample *rs /* or NULL */,
+                              const ccmi_warp *warp /* or NULL */, const ccmi_colour *colour /* or NULL */,
+                              const ccmi_tone *tone /* or NULL */, const ccmi_filter *filter /* or NULL */,
+                              const ccmi_blend *blend /* or NULL */, const ccmi_mix *mix /* or NULL */,
+                              int out_bitdepth, int out_chroma, void *workspace, size_t workspace_bytes, void *stream);
+
 /* Network weights of a stream's intra frame as the decoder's fixed-point integers
  * (cc-frame-decoder.cpp:201-353, read_arm / read_ups / read_syn):
  *   arm: per hidden layer W[d][d] (out, in) then b[d]; then W_out[2][d], b_out[2]
